@@ -296,6 +296,31 @@ def other_configs(unet, device, S, which=((128, 400, 3, "BASELINE configs[1]: 12
     return out
 
 
+DUMP_BUDGET_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(outdir, arrays, budget=DUMP_BUDGET_BYTES, seed=0):
+    """--dump-outputs: every array -> outdir/<name>.npy in float32.  When the arrays do not fit the byte budget together, each one is
+    replaced by a fixed, seeded sample of its flat elements (ascending positions), and the positions go to <name>_index.npy (float64,
+    exact): the same arguments give the same files, so two builds can be compared output for output.  Returns {file: shape}."""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.size for a in arrays.values())
+    os.makedirs(outdir, exist_ok=True)
+    written = {}
+    for name, a in arrays.items():
+        files = {name: a}
+        if total * 4 > budget - 1024 * len(arrays):
+            # 4 bytes of value + 8 bytes of position per sampled element (1 KiB per array kept for the .npy headers)
+            k = (budget - 2048 * len(arrays)) // 12 * a.size // total
+            idx = np.sort(np.random.default_rng(seed).choice(a.size, k, replace=False))
+            files = {name: a.reshape(-1)[idx], name + "_index": idx.astype(np.float64)}
+        for f, v in files.items():
+            np.save(os.path.join(outdir, f + ".npy"), v)
+            written[f + ".npy"] = list(v.shape)
+    return written
+
+
 class LaunchError(SystemExit):
     """bench.py refuses to run rather than report a GPU count it did not use (exit code 2, message on stderr)."""
 
@@ -430,7 +455,13 @@ def main():
                          "path is not launch-bound; kept as an option)")
     ap.add_argument("--eager-every", type=int, default=10,
                     help="with graphs: every n-th DDIM step runs eagerly so HIP events sample the conv kernel live")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed -- the sampled clip (B,3,T,h,w); T-shard: the whole "
+                         "clip, replica: every rank's clip -- as DIR/sample.npy in float32, at most 64 MB (beyond that a fixed seeded "
+                         "sample of its elements, positions in DIR/sample_index.npy)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error(f"--steps {args.steps} --warmup {args.warmup}: need at least one timed step and no negative warm-up")
 
     what, cmd = launch_plan(args.gpus, os.environ, torch.cuda.device_count(), sys.argv[1:])
     if what == "spawn":
@@ -540,6 +571,19 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
     assert torch.isfinite(out).all(), "non-finite output"
+    if args.dump_outputs:
+        # OUTSIDE the timed region, before anything else runs on the model (graph replay may hand out a buffer it reuses)
+        if dist is not None:
+            parts = [torch.empty_like(out) for _ in range(ranks_seen)]
+            dist.all_gather(parts, out.contiguous())
+            sample = torch.cat(parts, 2 if comm is not None else 0).cpu()     # T-shard: frames of one clip; replica: clips
+            del parts
+        else:
+            sample = out.cpu()
+        if rank == 0:
+            files = dump_outputs(args.dump_outputs, {"sample": sample.numpy()})
+            print(f"bench.py: --dump-outputs wrote {files} to {args.dump_outputs}", file=sys.stderr, flush=True)
+        del sample
 
     per_rank = None
     if dist is not None:

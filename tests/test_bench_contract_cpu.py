@@ -117,3 +117,30 @@ def test_stdout_redirection_keeps_foreign_prints_off_the_json_stream(tmp_path):
             "print('{\"metric\": 1}')\n" % ROOT)
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and r.stdout.strip() == '{"metric": 1}' and "banner" in r.stderr and "banner2" in r.stderr
+
+
+def test_dump_outputs_writes_float32_within_budget(tmp_path):
+    """--dump-outputs: arrays that fit are written whole in float32; larger ones as the same seeded sample every time, with their
+    flat positions, never more than the budget in all."""
+    import numpy as np
+    a = np.arange(2 * 3 * 5, dtype=np.float64).reshape(2, 3, 5)
+    assert bench.dump_outputs(str(tmp_path / "whole"), {"sample": a}) == {"sample.npy": [2, 3, 5]}
+    got = np.load(tmp_path / "whole" / "sample.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, a.astype(np.float32))
+    big = np.random.default_rng(1).standard_normal((4, 3, 100, 50)).astype(np.float32)       # 240 kB against a 100 kB budget
+    runs = []
+    for d in ("s1", "s2"):
+        files = bench.dump_outputs(str(tmp_path / d), {"sample": big}, budget=100_000)
+        assert set(files) == {"sample.npy", "sample_index.npy"}
+        assert sum((tmp_path / d / f).stat().st_size for f in files) <= 100_000
+        v, i = np.load(tmp_path / d / "sample.npy"), np.load(tmp_path / d / "sample_index.npy")
+        assert v.dtype == np.float32 and i.dtype == np.float64 and len(v) == len(i) > 0 and np.all(np.diff(i) > 0)
+        assert np.array_equal(v, big.reshape(-1)[i.astype(np.int64)])
+        runs.append((v, i))
+    assert np.array_equal(runs[0][0], runs[1][0]) and np.array_equal(runs[0][1], runs[1][1])
+
+
+def test_bench_refuses_zero_timed_steps():
+    import subprocess
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 2 and r.stdout.strip() == "" and "--steps 0" in r.stderr
