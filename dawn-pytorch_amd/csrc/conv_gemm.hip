@@ -31,7 +31,7 @@ namespace {
 // 3x3/s1/p1 convs whose tile geometry fits (+5..19 %, profiles/r1_l_conv_halo.txt), 0x1000 split-operand bf16
 // MFMA version of that kernel when the caller supplies w_bf3 (6 cross terms; 0x2000: all 9), 0x4000 its second
 // generation (conv3x3_bf16_v2_kernel: +5..20 %, profiles/r1_n_conv_bf16.txt), 0x10/0x20 fp32-kernel perf ablations,
-// (8 << 16) the s_memtime build of the split kernel, 0x400 -- ONLY in the experimental build of tools/build_sk_timing_lib.sh (-DDAWN_WITH_STREAMK; the
+// (8 << 16) the s_memtime build of the split kernel, 0x400 -- ONLY in the experimental build of hipbuild.py sktiming (-DDAWN_WITH_STREAMK; the
 // shipped library ignores the bit since round 4) -- the persistent stream-K 3x3 kernel (tools/ubench/conv3x3_sk.hip) when the caller
 // supplies dawn_conv_desc.sk_ws (0x200: without the half-tile offset between co-resident workgroups; 0x40 + bits 16..17: issue-priority
 // alternation between them; bits 20..23 there: leave n/16 of the resident slots to a concurrent stream).  NOT in the shipped
@@ -54,7 +54,7 @@ namespace {
 // perf-ablation kernels (0x10 / 0x20: wrong results by design; (n << 16): ablated / s_memtime-instrumented builds of the
 // split 3x3 kernel; 0x40000000, read from dawn_conv_desc.policy directly: the row-stationary GEMM kernels fetch their rows in a
 // line-coalesced pattern -- the right bytes in the wrong lanes, profiles/r5_row_fetch_pattern_ablation.txt) exist only in
-// -DDAWN_ABLATION builds (tools/build_timing_lib.sh), never in the shipped library.
+// -DDAWN_ABLATION builds (hipbuild.py ablation), never in the shipped library.
 // 0x80000 (A/B, round 6; read from dawn_conv_desc.policy directly, same bits out): the split 1x1 tile GEMM deals its tiles to the XCDs in
 // launch order instead of one contiguous range of row panels per XCD (see gemm1x1_bf16_kernel).
 constexpr int DAWN_CONV_POLICY_DEFAULT = 0x2B00580D;

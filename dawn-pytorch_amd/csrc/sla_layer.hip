@@ -766,7 +766,7 @@ extern "C" int dawn_sla_layer_c64(const float* x, int F, int HW, const float* wq
         const int nblk = (int)((total + per - 1) / per);
         // 96 KB of Wq planes + 64 KB of fp32 M, or (shipped) 64 KB of Wq planes + 96 KB of M planes: 160 KB either way
 #ifdef DAWN_SLA_OUT_FP32
-        constexpr bool OUTB = false;        // A/B build (tools/build_variant_lib.sh): the out product on the fp32 pipe as in rounds 2-5
+        constexpr bool OUTB = false;        // A/B build (hipbuild.py --source sla_layer): the out product on the fp32 pipe as in rounds 2-5
 #else
         constexpr bool OUTB = true;
 #endif

@@ -53,7 +53,7 @@ class HipOps:
         self.conv_policy = 0         # dawn_conv_desc.policy of every conv_gemm launch (0 = shipped kernel policy)
         self.temporal_flags = 0      # kernel-family selector of the fused temporal layer (0 = automatic; A/B and tests)
         self.temporal_attn_flags = 0  # dawn_temporal_attn_ex flags (1 = the fp32-MFMA attention core; A/B and tests)
-        self.sk_ws = None            # experimental library only (tools/build_sk_timing_lib.sh): scratch tensor handed to dawn_conv_desc.sk_ws
+        self.sk_ws = None            # experimental library only (hipbuild.py sktiming): scratch tensor handed to dawn_conv_desc.sk_ws
         self.fuse_h1 = True          # cross-attention kernels write h1 = SiLU(GN(c1)) + h_cond themselves (False: A/B, two-stream form)
         self._sel_ws = {}            # (device index, stream) -> scratch of the threshold selection (histograms, state)
         self._tickets = {}           # (device index, stream) -> the zeroed device word of the convs' fused GroupNorm finalisation

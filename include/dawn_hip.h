@@ -65,7 +65,7 @@ typedef struct dawn_conv_desc {
     void* sk_ws; size_t sk_ws_bytes;               /* RESERVED, leave NULL / 0 (kept for the struct layout).  Round 3: hand-off scratch of a persistent stream-K
                                                       form of the 3x3 kernel -- faster in isolation, slower end to end on a power-limited chip; since round 4 that
                                                       kernel lives in tools/ubench/conv3x3_sk.hip and exists only in the experimental library of
-                                                      tools/build_sk_timing_lib.sh.  The shipped library ignores both fields */
+                                                      the hipbuild.py sktiming preset.  The shipped library ignores both fields */
     const void* w_wino;                            /* optional (3x3/s1/p1 convs): the Winograd F(2x2,3x3) image of the weights, U = G g G^T computed in
                                                       fp64 and split into three bf16 planes, in the fragment order of conv3x3_wino_kernel:
                                                       [(C0+C1)/16][16 positions][N/16][2][64 lanes][8] (pack.pack_wino_bf3).  With policy bit
@@ -113,7 +113,7 @@ int dawn_conv_gemm_nblocks(long M, int N);
  * 0x1000 split-operand (bf16 pipe) kernels when w_bf3 is supplied, 0x2000 all 9 cross terms instead of 6, 0x4000
  * second-generation split 3x3 kernel, 0x1000000 that kernel on v_mfma_f32_16x16x32_bf16 (two cross terms per instruction: less energy per
  * flop on a power-limited chip), 0x2000000 the Winograd F(2x2,3x3) form of that conv where w_wino is supplied and the shape fits (2.25x fewer matrix-pipe flops); 0x4000000 (A/B) the direct kernel for convs of fewer than 128 input channels even where the Winograd form fits (measured slower, not shipped); 0x8000000 (shipped) the Winograd F(4x4,3x3) form where w_wino4 is supplied, dawn_conv3x3_wino4_ok and the shape is one it measured faster on (64 input channels at image width 64, up to 128 at image width 32) -- with 0x10000000 wherever it fits; 0x20000000 (shipped) both Winograd kernels walk their tiles back to front -- last frame first: the end of the input, written last by the producer, is what the memory-side cache still holds (bit-identical outputs); 0x400 is ignored (round 3's opt-in stream-K variant: experimental builds only).  Every combination computes the same function (tests run the kernel families
- * against each other); perf-ablation / s_memtime builds exist only under -DDAWN_ABLATION (tools/build_timing_lib.sh). */
+ * against each other); perf-ablation / s_memtime builds exist only under -DDAWN_ABLATION (hipbuild.py presets). */
 
 /* ---- A3 GroupNorm(8) statistics over (C/8, F, H, W) (MT:230,235; nn.GroupNorm on a 5-D tensor) --
  * partial: per-block fp64 (sum, sumsq) per group -> part[nblk][16]; reduce: fixed-order sum ->

@@ -28,7 +28,7 @@ def main():
     ap.add_argument("--check", action="store_true", help="compare the extra policy's output with the Winograd one (bit-identical expected)")
     ap.add_argument("--stagger", type=int, nargs="*", default=[], help="with --wino4: also time start-stagger units (policy bits 20..23)")
     ap.add_argument("--wino4", action="store_true", help="also time the F(4x4,3x3) kernel (policy bit 0x8000000) where its geometry fits")
-    ap.add_argument("--stamps4", action="store_true", help="F(4x4) instrumented build (tools/build_wino4_timing_lib.sh, DAWN_WINO4_ABL=64): per-wave s_memtime timeline")
+    ap.add_argument("--stamps4", action="store_true", help="F(4x4) instrumented build (hipbuild.py wino4timing, DAWN_WINO4_ABL=64): per-wave s_memtime timeline")
     ap.add_argument("--stamps", action="store_true", help="instrumented build (DAWN_WINO_ABL=64): print the s_memtime timeline of a few workgroups")
     a = ap.parse_args()
     ops = HipOps()

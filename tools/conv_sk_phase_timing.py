@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """GPU tool: per-phase s_memtime profile of the persistent stream-K 3x3 conv kernel (instrumented build:
-tools/build_sk_timing_lib.sh, loaded through DAWN_HIP_LIB).
+`python3 hipbuild.py sktiming`, loaded through DAWN_HIP_LIB).
     DAWN_HIP_LIB=tools/ubench/libdawn_hip_sktiming.bin python tools/conv_sk_phase_timing.py [--C1 64] [--leave 8]
 Wave 0 of every workgroup stamps units 2..5 of its range (TSTAMP() in conv3x3_sk.hip): per unit
   top | [requests issued, MFMAs issued, loads landed, barrier passed] x 3 kernel rows | planes written.

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""GPU box (debug library: tools/build_tl16_debug_lib.sh -DDAWN_TL16_DUMP, DAWN_HIP_LIB=tools/ubench/libdawn_hip_tl16debug.bin):
+"""GPU box (debug library: `python3 hipbuild.py tl16debug -DDAWN_TL16_DUMP`, DAWN_HIP_LIB=tools/ubench/libdawn_hip_tl16debug.bin):
 run the window-tiled layer repeatedly on the same input and report which (pixel, head, tile) intermediates differ between runs."""
 import ctypes, os, sys
 import torch

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """GPU tool: s_memtime phase profile of temporal_layer_c64_kernel (needs the instrumented build:
-    hipcc ... -DDAWN_TL_TIMING on temporal_layer.hip, see tools/build_timing_lib.sh).  Prints mean cycles between stamps."""
+    `python3 hipbuild.py tltiming`, then DAWN_HIP_LIB=tools/ubench/libdawn_hip_tltiming.bin).  Prints mean cycles between stamps."""
 import ctypes, os, sys
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

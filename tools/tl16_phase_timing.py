@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """GPU tool: s_memtime phase profile of the window-tiled fused temporal layer (csrc/temporal_layer16.hip).  Needs the instrumented
-library: tools/build_tl16_debug_lib.sh -DDAWN_TL_TIMING, then DAWN_HIP_LIB=tools/ubench/libdawn_hip_tl16debug.bin.
+library: `python3 hipbuild.py tl16debug -DDAWN_TL_TIMING`, then DAWN_HIP_LIB=tools/ubench/libdawn_hip_tl16debug.bin.
 Prints mean cycles between stamps per wave (stamps cost cycles themselves: read the proportions, not the totals)."""
 import ctypes, os, sys
 import numpy as np, torch

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """GPU tool: s_memtime phase profile of xattn_c64_kernel<64> (needs xattn_layer.hip built with -DDAWN_XA_TIMING:
-    hipcc ... -DDAWN_XA_TIMING -c xattn_layer.hip, link to a second .so and point DAWN_HIP_LIB at it).  --split: bf16-pipe to_q."""
+    python3 hipbuild.py --source xattn_layer -o tools/ubench/libdawn_hip_xatiming.bin -DDAWN_XA_TIMING, DAWN_HIP_LIB at it).  --split: bf16-pipe to_q."""
 import ctypes, os, sys
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
