@@ -99,6 +99,11 @@ SIGNATURES = {
     "dawn_ubench_mfma_bf16": [_i, _i, c_f, c_f, C.POINTER(C.c_float), c_f],
     "dawn_ddim_update": [c_f, c_f, c_f, c_f, _f, _f, _f, _l, c_f, c_f],
     "dawn_cfg_combine": [c_f, c_f, _f, _l, c_f, c_f],
+    "dawn_cfg_x0": [c_f, c_f, _f, c_f, _f, _f, _l, c_f, c_f, c_f, c_f],
+    # guided whole-path entries (include/dawn_hip.h; the dawn_shard_comm* travels as a void*)
+    "dawn_workspace_bytes_guided": [c_f, _i, _i, _i, _i, _i],
+    "dawn_unet_forward_guided": [c_f, _i, _i, _i, c_f, c_f, c_f, _f, _f, c_f, c_f, C.c_size_t, c_f, c_f],
+    "dawn_sampler_run_guided": [c_f, _i, _i, _i, c_f, c_f, _f, c_f, _i, c_f, C.c_uint64, c_f, c_f, c_f, c_f, C.c_size_t, c_f, c_f],
     "dawn_philox_normal": [c_f, _i, _i, _i, _i, _i, C.c_uint64, C.c_uint32, c_f],
     "dawn_affine_act": [c_f, _i, c_f, c_f, _i, c_f, _l, _i, c_f],
     "dawn_bn_relu_pool2": [c_f, c_f, c_f, c_f, _i, _i, _i, _i, c_f],
@@ -120,7 +125,7 @@ class DawnHipError(RuntimeError):
     pass
 
 
-LONG_RESULT = {"dawn_sla_ws_floats"}       # entry points that return a size (long), not a status
+LONG_RESULT = {"dawn_sla_ws_floats", "dawn_workspace_bytes_guided"}       # entry points that return a size (long), not a status
 
 
 def lib() -> C.CDLL:

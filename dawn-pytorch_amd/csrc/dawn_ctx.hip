@@ -433,7 +433,30 @@ struct Eval {
     }
 
     // ---- ResnetBlock_ca_mul (unet_forward._resblock)
-    T2 resblock(const RB& rb, const T2& x, const T2* x2, int Fr, int H, int W, const float* film_all) {
+    // conv1 of a ResBlock + its GroupNorm coefficients (main stream): reads x and the time FiLM only
+    void conv1_stats(const RB& rb, const T2& x, const T2* x2, int Fr, int H, int W, const float* fs, const float* fsh, T2& c1, float*& ab1,
+                     double*& part) {
+        const int Co = rb.Co;
+        const long rows = (long)Fr * H * W, total_rows = rows;
+        part = gn_part_alloc(rows, Co);
+        int nblk = 0;
+        c1 = t2(rows, Co);
+        ab1 = falloc(2 * (size_t)Co);
+        {
+            ConvArgs a;
+            a.in0 = x.p; a.C0 = x.C; a.ld0 = x.C; a.in1 = x2 ? x2->p : nullptr; a.C1 = x2 ? x2->C : 0; a.ld1 = a.C1;
+            a.w = rb.w1; a.w_bf3 = rb.w1s; a.w_wino = rb.w1w; a.w_wino4 = rb.w1w4; a.bias = rb.b1; a.N = Co; a.Fr = Fr; a.Hi = H; a.Wi = W; a.KH = 3; a.KW = 3; a.pad = 1;
+            a.out = c1.p; a.ld_out = Co; a.gn_part = part; a.gn_rows = &nblk;
+            a.gn_gamma = rb.g1; a.gn_beta = rb.be1; a.gn_fs = fs; a.gn_fsh = fsh; a.gn_a = ab1; a.gn_b = ab1 + Co; a.gn_total_rows = total_rows;
+            conv(a);
+        }
+        gn_coeffs(part, nblk, total_rows, Co, rb.g1, rb.be1, fs, fsh, ab1, ab1 + Co);
+    }
+
+    // pre_c1 / pre_ab1: conv1 + coefficients computed by the caller (the guided evaluation's shared prefix; the caller owns them);
+    // keep_pre: another branch reads them again, so h1 gets a tensor of its own instead of being written over c1
+    T2 resblock(const RB& rb, const T2& x, const T2* x2, int Fr, int H, int W, const float* film_all, const T2* pre_c1 = nullptr,
+                float* pre_ab1 = nullptr, bool keep_pre = false) {
         const int Co = rb.Co, HW = H * W;
         const long rows = (long)Fr * HW, total_rows = rows;
         T2 hcond;
@@ -479,22 +502,15 @@ struct Eval {
             to_main();
         }
         // conv1 + GroupNorm statistics from its epilogue (main stream)
-        double* part = gn_part_alloc(rows, Co);
-        int nblk = 0;
-        T2 c1 = t2(rows, Co);
-        float* ab1 = falloc(2 * (size_t)Co);
-        {
-            ConvArgs a;
-            a.in0 = x.p; a.C0 = x.C; a.ld0 = x.C; a.in1 = x2 ? x2->p : nullptr; a.C1 = x2 ? x2->C : 0; a.ld1 = a.C1;
-            a.w = rb.w1; a.w_bf3 = rb.w1s; a.w_wino = rb.w1w; a.w_wino4 = rb.w1w4; a.bias = rb.b1; a.N = Co; a.Fr = Fr; a.Hi = H; a.Wi = W; a.KH = 3; a.KW = 3; a.pad = 1;
-            a.out = c1.p; a.ld_out = Co; a.gn_part = part; a.gn_rows = &nblk;
-            a.gn_gamma = rb.g1; a.gn_beta = rb.be1; a.gn_fs = fs; a.gn_fsh = fsh; a.gn_a = ab1; a.gn_b = ab1 + Co; a.gn_total_rows = total_rows;
-            conv(a);
-        }
-        gn_coeffs(part, nblk, total_rows, Co, rb.g1, rb.be1, fs, fsh, ab1, ab1 + Co);
+        T2 c1;
+        float* ab1 = nullptr;
+        double* part = nullptr;
+        if (pre_c1) { c1 = *pre_c1; ab1 = pre_ab1; }
+        else conv1_stats(rb, x, x2, Fr, H, W, fs, fsh, c1, ab1, part);
         T2 h1;
         if (fuse_h1) {
-            h1 = c1;                                    // written OVER c1 (the epilogue reads an element of c1, writes the same element of h1)
+            // written OVER c1 (the epilogue reads an element of c1, writes the same element of h1) unless another branch reads c1 again
+            h1 = keep_pre ? t2(rows, Co) : c1;
             if (h1_c64) {
                 LAUNCH(dawn_xattn_layer_c64_h1(x.p, x.C, x.C, x2 ? x2->p : nullptr, x2 ? x2->C : 0, x2 ? x2->C : 0, rows, HW, rb.wq, rb.wqs,
                                                rb.g3, clipf(xt_h1), 1e-5f, c1.p, ab1, ab1 + Co, h1.p, cur));
@@ -507,8 +523,10 @@ struct Eval {
             if (rb.conditioned) join();
             h1 = gn_apply_res(c1, ab1, ab1 + Co, hcond.p);
         }
-        if (h1.p != c1.p) rel(c1);
-        A.free(ab1); A.free(part);
+        if (!(pre_c1 && keep_pre)) {                   // (a prefix's c1 / ab1 pass to this block when no other branch reads them)
+            if (h1.p != c1.p) rel(c1);
+            A.free(ab1); A.free(part);
+        }
         if (hcond.p) rel(hcond);
         double* part2 = gn_part_alloc(rows, Co);
         int nblk2 = 0;
@@ -724,6 +742,43 @@ struct Eval {
 
     // ---- one evaluation: x3 (3,F,h,w) latent, t -> eps (3,F,h,w)   (unet_forward.unet_forward)
     void forward(const float* x3, float t, float* eps_out) {
+        float* film = begin(t);
+        T2 r, x;
+        init_layers(x3, r, x);
+        rest(x3, film, r, x, nullptr, nullptr, false, eps_out);
+        end(film);
+    }
+
+    // ---- one guided evaluation (unet_forward.unet_forward_guided): the condition-free prefix once, the conditional branch (clip) keeping
+    // it intact, the null branch (null_clip) consuming it, then eps = null + (cond - null) * scale -- or, with x0_out, the sampler's
+    // dawn_cfg_x0 (guided eps, x0 = recip * x3 - recipm1 * eps and the first quantile histogram in one launch)
+    void forward_guided(const float* x3, float t, const void* null_clip, float scale, float* eps_out, float* x0_out = nullptr,
+                        unsigned* hist1 = nullptr, float recip = 0.f, float recipm1 = 0.f) {
+        float* film = begin(t);
+        T2 r, x;
+        init_layers(x3, r, x);
+        const RB& rb = c->downs[0].rb1;
+        T2 c1;
+        float* ab1 = nullptr;
+        double* part = nullptr;
+        conv1_stats(rb, x, nullptr, F, H0, W0, film + rb.film_off, film + rb.film_off + rb.Co, c1, ab1, part);
+        A.free(part);
+        const long n = 3L * F * H0 * W0;
+        float* e_c = falloc((size_t)n);
+        rest(x3, film, r, x, &c1, ab1, true, e_c);
+        float* e_n = falloc((size_t)n);
+        const char* cond_clip = clip;
+        clip = (const char*)null_clip;
+        rest(x3, film, r, x, &c1, ab1, false, e_n);
+        clip = cond_clip;
+        if (x0_out) LAUNCH(dawn_cfg_x0(e_n, e_c, scale, x3, recip, recipm1, n, eps_out, x0_out, hist1, cur));
+        else LAUNCH(dawn_cfg_combine(e_n, e_c, scale, n, eps_out, cur));
+        A.free(e_n); A.free(e_c);
+        end(film);
+    }
+
+    // ticket + time FiLM (sinusoidal -> Linear -> GELU -> Linear -> [SiLU -> Linear] for every block in one GEMV)
+    float* begin(float t) {
         const int dim = c->cfg.dim;
         gn_ticket = (unsigned*)falloc(4);
         // (a non-zero ticket means the last workgroup of a conv never sees itself as last: gn_a / gn_b would stay unwritten -- a failed
@@ -739,18 +794,35 @@ struct Eval {
         LAUNCH(dawn_linear(e1, 1, c->time_dim, c->time_dim, c->t_w2, c->t_b2, c->time_dim, 2, e2, c->time_dim, cur));
         LAUNCH(dawn_linear(e2, 1, c->time_dim, c->time_dim, c->film_w, c->film_b, c->film_total, 1, film, c->film_total, cur));
         A.free(e0); A.free(e1); A.free(e2);
-        int H = H0, W = W0;
-        T2 r = t2((long)F * H * W, dim);
-        LAUNCH(dawn_init_conv_x(x3, c->w3, clipf(L.fea_pre), F, H, W, dim, r.p, cur));
-        T2 x = temporal(c->init_tattn, r, F, H, W);
+        return film;
+    }
+    void end(float* film) {
+        A.free(film);
+        if (gn_ticket) { A.free(gn_ticket); gn_ticket = nullptr; }
+    }
+
+    // init conv -> r (the heads' skip), init temporal layer -> x; r.p = nullptr in the long-clip lean form
+    void init_layers(const float* x3, T2& r, T2& x) {
+        r = t2((long)F * H0 * W0, c->cfg.dim);
+        LAUNCH(dawn_init_conv_x(x3, c->w3, clipf(L.fea_pre), F, H0, W0, c->cfg.dim, r.p, cur));
+        x = temporal(c->init_tattn, r, F, H0, W0);
         // long clips: the heads' skip is recomputed at the end (0.8 % of an evaluation) instead of held through it (unet_forward)
-        const bool lean = F > c->long_clip_frames;          // (sharded ranks too: the skip is frame-local, no halo is involved)
-        if (lean) rel(r);
+        if (F > c->long_clip_frames) rel(r);                // (sharded ranks too: the skip is frame-local, no halo is involved)
+    }
+
+    // everything after the init layers.  pre_c1 / pre_ab1: downs[0].rb1's conv1 + coefficients from the guided prefix; keep: another
+    // branch still reads the prefix (r, x, c1, ab1), so none of it is released or written over
+    void rest(const float* x3, const float* film, T2 r, T2 x, const T2* pre_c1, float* pre_ab1, bool keep, float* eps_out) {
+        const int dim = c->cfg.dim;
+        int H = H0, W = W0;
+        const bool lean = F > c->long_clip_frames;
         struct Skip { T2 t; int H, W; };
         std::vector<Skip> skips;
         for (size_t l = 0; l < c->downs.size(); ++l) {
             Level& lv = c->downs[l];
-            T2 y = resblock(lv.rb1, x, nullptr, F, H, W, film); rel(x); x = y;
+            T2 y = l == 0 ? resblock(lv.rb1, x, nullptr, F, H, W, film, pre_c1, pre_ab1, keep) : resblock(lv.rb1, x, nullptr, F, H, W, film);
+            if (!(l == 0 && keep)) rel(x);
+            x = y;
             y = resblock(lv.rb2, x, nullptr, F, H, W, film); rel(x); x = y;
             y = spatial_linear(lv.sla, x, F, H, W, !sc); if (y.p != x.p) rel(x); x = y;
             y = temporal(lv.tattn, x, F, H, W, true); if (y.p != x.p) rel(x); x = y;
@@ -809,12 +881,11 @@ struct Eval {
         } else {
             T2 hg = resblock(c->head_g, x, &r, F, H, W, film);            // torch.cat((x, r)) MT:955
             T2 ho = resblock(c->head_o, x, &r, F, H, W, film);
-            rel(x); rel(r);
+            rel(x);
+            if (!keep) rel(r);
             LAUNCH(dawn_head_out(hg.p, ho.p, c->wg, c->bg, c->wo, c->bo, (long)F * H * W, hg.C, eps_out, cur));
             rel(hg); rel(ho);
         }
-        A.free(film);
-        if (gn_ticket) { A.free(gn_ticket); gn_ticket = nullptr; }
     }
 };
 
@@ -1000,7 +1071,7 @@ extern "C" int dawn_clip_prepare(dawn_ctx* c, int F, int h, int w, const float* 
     return 0;
 }
 
-static size_t workspace_bytes_impl(dawn_ctx* c, int F, int h, int w, const dawn_shard_comm* shard) {
+static size_t workspace_bytes_impl(dawn_ctx* c, int F, int h, int w, const dawn_shard_comm* shard, bool guided = false) {
     if (!c || F <= 0 || h <= 0 || w <= 0) return 0;
     // sized for BOTH schedules (two-stream: frees inside a side-stream region are deferred to the join; one-stream: immediate --
     // with a first-fit arena neither high-water mark bounds the other), so that toggling DAWN_OPT_OVERLAP after sizing cannot make a
@@ -1013,7 +1084,8 @@ static size_t workspace_bytes_impl(dawn_ctx* c, int F, int h, int w, const dawn_
         {
             Eval ev(c, nullptr, F, h, w, nullptr);
             ev.set_shard(shard);
-            ev.forward((const float*)4096, 0.f, (float*)4096);
+            if (guided) ev.forward_guided((const float*)4096, 0.f, (const void*)4096, 2.f, (float*)4096);
+            else ev.forward((const float*)4096, 0.f, (float*)4096);
         }
         if (c->arena.high > fwd) fwd = c->arena.high;
     }
@@ -1035,6 +1107,15 @@ extern "C" size_t dawn_workspace_bytes_sharded(dawn_ctx* c, int F, int h, int w,
     return workspace_bytes_impl(c, F, h, w, &geo);
 }
 
+extern "C" size_t dawn_workspace_bytes_guided(dawn_ctx* c, int F, int h, int w, int rank, int world) {
+    if (world < 1 || rank < 0 || rank >= world) return 0;
+    if (world == 1) return workspace_bytes_impl(c, F, h, w, nullptr, true);
+    dawn_shard_comm geo;
+    memset(&geo, 0, sizeof(geo));
+    geo.rank = rank; geo.world = world;
+    return workspace_bytes_impl(c, F, h, w, &geo, true);
+}
+
 static int shard_check(const dawn_shard_comm* comm) {
     if (comm && (comm->world < 1 || comm->rank < 0 || comm->rank >= comm->world))
         return dawn_set_error_msg(-212, "dawn_shard_comm: need 0 <= rank < world");
@@ -1050,15 +1131,30 @@ extern "C" int dawn_unet_forward_sharded(dawn_ctx* c, int F, int h, int w, const
     ev.forward(x3, t, eps_out);
     return ev.rc;
 }
+// cond_scale == 1: the unguided evaluation (the reference skips the null branch then, MT:885-886)
+extern "C" int dawn_unet_forward_guided(dawn_ctx* c, int F, int h, int w, const void* clip_mem, const void* null_clip_mem, const float* x3,
+                                        float t, float cond_scale, float* eps_out, void* workspace, size_t workspace_bytes,
+                                        const dawn_shard_comm* comm, void* stream) {
+    if (!c || !clip_mem || !null_clip_mem || !x3 || !eps_out || !workspace)
+        return dawn_set_error_msg(-202, "dawn_unet_forward_guided: null argument");
+    if (shard_check(comm)) return -212;
+    c->arena.reset(workspace, workspace_bytes, false);
+    Eval ev(c, (hipStream_t)stream, F, h, w, clip_mem);
+    ev.set_shard(comm);
+    if (cond_scale == 1.0f) ev.forward(x3, t, eps_out);
+    else ev.forward_guided(x3, t, null_clip_mem, cond_scale, eps_out);
+    return ev.rc;
+}
 extern "C" int dawn_unet_forward(dawn_ctx* c, int F, int h, int w, const void* clip_mem, const float* x3, float t,
                                  float* eps_out, void* workspace, size_t workspace_bytes, void* stream) {
     return dawn_unet_forward_sharded(c, F, h, w, clip_mem, x3, t, eps_out, workspace, workspace_bytes, nullptr, stream);
 }
 
-extern "C" int dawn_sampler_run_sharded(dawn_ctx* c, int F, int h, int w, const void* clip_mem, const float* x_init, int S,
-                                        const dawn_ddim_step* steps, uint64_t seed, const float* const* noises, float* x_out,
-                                        float* thresholds, void* workspace, size_t workspace_bytes, const dawn_shard_comm* comm,
-                                        void* stream) {
+// null_clip_mem != NULL and cond_scale != 1: every evaluation guided (Eval::forward_guided, whose last launch is dawn_cfg_x0)
+static int sampler_run_impl(dawn_ctx* c, int F, int h, int w, const void* clip_mem, const void* null_clip_mem, float cond_scale,
+                            const float* x_init, int S, const dawn_ddim_step* steps, uint64_t seed, const float* const* noises, float* x_out,
+                            float* thresholds, void* workspace, size_t workspace_bytes, const dawn_shard_comm* comm, void* stream) {
+    const bool guided = null_clip_mem && cond_scale != 1.0f;
     if (!c || !clip_mem || !x_init || !steps || !x_out || !workspace) return dawn_set_error_msg(-202, "dawn_sampler_run: null argument");
     if (shard_check(comm)) return -212;
     if (comm && (!comm->allreduce_sum_u32 || !comm->allreduce_min_u32))
@@ -1105,14 +1201,22 @@ extern "C" int dawn_sampler_run_sharded(dawn_ctx* c, int F, int h, int w, const 
     for (int i = 0; i < S; ++i) {
         const dawn_ddim_step& st = steps[i];
         c->arena.reset(ws, fwd_bytes, false);
-        {
+        if (guided) {
+            HCK(hipMemsetAsync(hist1, 0, 2048 * 4, s));
             Eval ev(c, s, F, h, w, clip_mem);
             ev.set_shard(comm);
-            ev.forward(x, (float)st.t, eps);
+            ev.forward_guided(x, (float)st.t, null_clip_mem, cond_scale, eps, x0, hist1, st.recip, st.recipm1);
             if (ev.rc) return ev.rc;
+        } else {
+            {
+                Eval ev(c, s, F, h, w, clip_mem);
+                ev.set_shard(comm);
+                ev.forward(x, (float)st.t, eps);
+                if (ev.rc) return ev.rc;
+            }
+            HCK(hipMemsetAsync(hist1, 0, 2048 * 4, s));
+            CK(dawn_ddim_x0(x, eps, st.recip, st.recipm1, n, x0, hist1, s));
         }
-        HCK(hipMemsetAsync(hist1, 0, 2048 * 4, s));
-        CK(dawn_ddim_x0(x, eps, st.recip, st.recipm1, n, x0, hist1, s));
         SHARD_CB(comm->allreduce_sum_u32(comm->user, hist1, 2048, stream));
         HCK(hipMemsetAsync(state, 0, 16, s));
         CK(dawn_select_scan(hist1, 2048, lo, state, 1, s));
@@ -1139,6 +1243,21 @@ extern "C" int dawn_sampler_run_sharded(dawn_ctx* c, int F, int h, int w, const 
     if (S == 0) HCK(hipMemcpyAsync(x_out, x, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
     return 0;
 #undef SHARD_CB
+}
+extern "C" int dawn_sampler_run_sharded(dawn_ctx* c, int F, int h, int w, const void* clip_mem, const float* x_init, int S,
+                                        const dawn_ddim_step* steps, uint64_t seed, const float* const* noises, float* x_out,
+                                        float* thresholds, void* workspace, size_t workspace_bytes, const dawn_shard_comm* comm,
+                                        void* stream) {
+    return sampler_run_impl(c, F, h, w, clip_mem, nullptr, 1.0f, x_init, S, steps, seed, noises, x_out, thresholds, workspace,
+                            workspace_bytes, comm, stream);
+}
+extern "C" int dawn_sampler_run_guided(dawn_ctx* c, int F, int h, int w, const void* clip_mem, const void* null_clip_mem, float cond_scale,
+                                       const float* x_init, int S, const dawn_ddim_step* steps, uint64_t seed, const float* const* noises,
+                                       float* x_out, float* thresholds, void* workspace, size_t workspace_bytes, const dawn_shard_comm* comm,
+                                       void* stream) {
+    if (!null_clip_mem) return dawn_set_error_msg(-202, "dawn_sampler_run_guided: null argument");
+    return sampler_run_impl(c, F, h, w, clip_mem, null_clip_mem, cond_scale, x_init, S, steps, seed, noises, x_out, thresholds,
+                            workspace, workspace_bytes, comm, stream);
 }
 extern "C" int dawn_sampler_run(dawn_ctx* c, int F, int h, int w, const void* clip_mem, const float* x_init, int S,
                                 const dawn_ddim_step* steps, uint64_t seed, const float* const* noises, float* x_out,

@@ -173,6 +173,30 @@ __global__ __launch_bounds__(256) void cfg_combine_kernel(const float* __restric
         out[i] = __fadd_rn(e_null[i], __fmul_rn(__fsub_rn(e_cond[i], e_null[i]), scale));
 }
 
+// classifier-free guidance combine followed by the x0 prediction and the first radix-select histogram, in ONE pass: the same
+// fp32 expressions as cfg_combine_kernel then ddim_x0_kernel, so eps, x0 and the histogram are bit-identical to the two-launch
+// sequence.  (gfx950 ISA, -O3: the compiler contracts these expressions, identically in all three kernels -- eps = v_fmac(null,
+// cond - null, scale), x0 = v_fma(recip, x, -(recipm1 * eps)).)  eps_out may alias e_null or e_cond (element-wise read-then-write).
+__global__ __launch_bounds__(256) void cfg_x0_kernel(const float* e_null, const float* e_cond, float scale,
+                                                     const float* __restrict__ x, float recip, float recipm1, long n,
+                                                     float* eps_out, float* __restrict__ x0, unsigned* __restrict__ hist) {
+    __shared__ unsigned hs[2048];
+    for (int i = threadIdx.x; i < 2048; i += 256) hs[i] = 0;
+    __syncthreads();
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        const float en = e_null[i];
+        const float e = __fadd_rn(en, __fmul_rn(__fsub_rn(e_cond[i], en), scale));
+        eps_out[i] = e;
+        const float v = __fsub_rn(__fmul_rn(recip, x[i]), __fmul_rn(recipm1, e));
+        x0[i] = v;
+        const unsigned u = __float_as_uint(v) & 0x7fffffffu;
+        atomicAdd(&hs[u >> 20], 1u);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < 2048; i += 256)
+        if (hs[i]) atomicAdd(&hist[i], hs[i]);
+}
+
 int grid_for(long n) {
     long g = (n + 255) / 256;
     if (g > 2048) g = 2048;
@@ -230,6 +254,14 @@ extern "C" int dawn_cfg_combine(const float* e_null, const float* e_cond, float 
                                 void* stream) {
     hipLaunchKernelGGL(cfg_combine_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, e_null, e_cond, scale,
                        n, out);
+    DAWN_LAUNCH_CHECK();
+    return 0;
+}
+extern "C" int dawn_cfg_x0(const float* e_null, const float* e_cond, float scale, const float* x, float recip, float recipm1, long n,
+                           float* eps_out, float* x0_out, unsigned* hist1, void* stream) {
+    if (x0_out == x || x0_out == eps_out) return dawn_set_error_msg(-73, "dawn_cfg_x0: x0_out must not alias x or eps_out");
+    hipLaunchKernelGGL(cfg_x0_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, e_null, e_cond, scale, x, recip,
+                       recipm1, n, eps_out, x0_out, hist1);
     DAWN_LAUNCH_CHECK();
     return 0;
 }

@@ -224,12 +224,18 @@ class CtxEvaluator:
     def _stream() -> int:
         return torch.cuda.current_stream().cuda_stream
 
-    def workspace(self, F: int, h: int, w: int, shard: Optional[ShardCallbacks] = None) -> Tensor:
+    def workspace(self, F: int, h: int, w: int, shard: Optional[ShardCallbacks] = None, guided: bool = False) -> Tensor:
         key = (F, h, w, self._policy, None if shard is None else (shard.rank, shard.world))
+        if guided:
+            key = key + ("guided",)
         need = self._need.get(key)
         if need is None:                    # sized in C for both schedules (one / two streams)
-            need = self._need[key] = int(self.L.dawn_workspace_bytes(self.h, F, h, w) if shard is None else
-                                         self.L.dawn_workspace_bytes_sharded(self.h, F, h, w, shard.rank, shard.world))
+            if guided:
+                rank, world = (0, 1) if shard is None else (shard.rank, shard.world)
+                need = self._need[key] = int(self.L.dawn_workspace_bytes_guided(self.h, F, h, w, rank, world))
+            else:
+                need = self._need[key] = int(self.L.dawn_workspace_bytes(self.h, F, h, w) if shard is None else
+                                             self.L.dawn_workspace_bytes_sharded(self.h, F, h, w, shard.rank, shard.world))
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         return self._ws
@@ -247,6 +253,12 @@ class CtxEvaluator:
                                        None if rcos is None else rcos.data_ptr(), None if rsin is None else rsin.data_ptr(),
                                        mem.data_ptr(), mem.numel(), ws.data_ptr(), ws.numel(), self._stream()), "dawn_clip_prepare")
         return {"mem": mem, "F": F, "h": h, "w": w}
+
+    def prepare_null_clip(self, fea272: Tensor, F: int, rcos: Optional[Tensor] = None, rsin: Optional[Tensor] = None) -> dict:
+        """The clip of the all-zero condition (learn_null_cond=False, MT:920) for guided sampling: ONE zero row read with row stride 0."""
+        cd = sum(self.P.cond_dims)
+        zero = torch.zeros(1, cd, device=fea272.device, dtype=torch.float32).expand(F, cd)
+        return self.prepare_clip(fea272, zero, rcos, rsin)
 
     def _shard_call(self, shard: ShardCallbacks, rc: int, what: str) -> None:
         err, shard.error = shard.error, None
@@ -271,9 +283,30 @@ class CtxEvaluator:
                                        ws.data_ptr(), ws.numel(), self._stream()), "dawn_unet_forward")
         return out
 
+    def forward_guided(self, clip: dict, null_clip: dict, x3: Tensor, t: float, cond_scale: float,
+                       shard: Optional[ShardCallbacks] = None) -> Tensor:
+        """dawn_unet_forward_guided: null + (cond - null) * cond_scale, the condition-free prefix evaluated once."""
+        F, h, w = clip["F"], clip["h"], clip["w"]
+        if not (x3.is_cuda and x3.is_contiguous() and tuple(x3.shape) == (3, F, h, w) and x3.dtype == torch.float32):
+            raise _lib.DawnHipError(f"forward_guided: x3 must be a contiguous fp32 GPU tensor of shape (3, {F}, {h}, {w})")
+        out = torch.empty_like(x3)
+        ws = self.workspace(F, h, w, shard, guided=True)
+        comm = None
+        if shard is not None:
+            shard.ws = ws
+            comm = C.addressof(shard.c)
+        rc = self.L.dawn_unet_forward_guided(self.h, F, h, w, clip["mem"].data_ptr(), null_clip["mem"].data_ptr(), x3.data_ptr(), float(t),
+                                             float(cond_scale), out.data_ptr(), ws.data_ptr(), ws.numel(), comm, self._stream())
+        if shard is not None:
+            self._shard_call(shard, rc, "dawn_unet_forward_guided")
+        else:
+            check(rc, "dawn_unet_forward_guided")
+        return out
+
     def sample(self, clip: dict, x_init: Tensor, steps: Sequence[dict], seed: int = 0,
                noises: Optional[List[Optional[Tensor]]] = None, want_thresholds: bool = False,
-               shard: Optional[ShardCallbacks] = None):
+               shard: Optional[ShardCallbacks] = None, null_clip: Optional[dict] = None, cond_scale: float = 1.0):
+        """cond_scale != 1 (with null_clip = prepare_null_clip(...)): guided sampling, dawn_sampler_run_guided."""
         F, h, w = clip["F"], clip["h"], clip["w"]
         S = len(steps)
         arr = (DdimStep * max(S, 1))()
@@ -291,6 +324,22 @@ class CtxEvaluator:
         x_init = x_init.contiguous().float()
         out = torch.empty_like(x_init)
         thr = torch.empty(S, 2, device=self.device) if want_thresholds else None
+        if cond_scale != 1.0:
+            if null_clip is None:
+                raise _lib.DawnHipError("sample: cond_scale != 1 needs null_clip (prepare_null_clip)")
+            ws = self.workspace(F, h, w, shard, guided=True)
+            comm = None
+            if shard is not None:
+                shard.ws = ws
+                comm = C.addressof(shard.c)
+            rc = self.L.dawn_sampler_run_guided(self.h, F, h, w, clip["mem"].data_ptr(), null_clip["mem"].data_ptr(), float(cond_scale),
+                                                x_init.data_ptr(), S, arr, int(seed), nz, out.data_ptr(),
+                                                None if thr is None else thr.data_ptr(), ws.data_ptr(), ws.numel(), comm, self._stream())
+            if shard is not None:
+                self._shard_call(shard, rc, "dawn_sampler_run_guided")
+            else:
+                check(rc, "dawn_sampler_run_guided")
+            return (out, thr) if want_thresholds else out
         ws = self.workspace(F, h, w, shard)
         if shard is not None:
             shard.ws = ws

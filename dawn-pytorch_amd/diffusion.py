@@ -78,8 +78,10 @@ class GaussianDiffusion(nn.Module):
         self.noise_seed: Optional[int] = None     # int -> shard-invariant Philox stream on device
         self.use_graph = False                    # capture one UNet evaluation per clip as a HIP graph
         self.eager_every = 0                      # with use_graph: run every n-th step eagerly (profiling hooks)
-        self.use_ctx = False                      # run the DDIM loop through the C-side evaluator (dawn_sampler_run); same
-                                                  # kernels and arguments as the Python orchestration: bit-identical output
+        self.use_ctx = False                      # run the DDIM loop through the C-side evaluator (dawn_sampler_run, or
+                                                  # dawn_sampler_run_guided when cond_scale != 1); same kernels and arguments as
+                                                  # the Python orchestration: bit-identical output
+        self.last_route: Optional[str] = None     # "ctx" or "python": which host ran the last sample()
         self.last_trace: Optional[list] = None
 
     # ------------------------------------------------------------------ reference call surface
@@ -120,11 +122,12 @@ class GaussianDiffusion(nn.Module):
         if cond is not None and cond.shape[1] != T:
             raise ValueError(f"cond has {cond.shape[1]} frames but num_frames={T}; call update_num_frames first (UVG:370)")
         outs, traces = [], []
-        if self.use_ctx and comm is None and cond_scale == 1.0 and not trace and fea.is_cuda:
+        if self.use_ctx and comm is None and not trace and fea.is_cuda:
             ev = unet.ctx_evaluator()
             rcos, rsin = P.rotary_tables(T + 2 * P.win)
             for b in range(B):
                 clip = ev.prepare_clip(fea[b].contiguous().float(), cond[b].contiguous().float(), rcos, rsin)
+                null_clip = ev.prepare_null_clip(fea[b].contiguous().float(), T, rcos, rsin) if cond_scale != 1.0 else None
                 seed = self.noise_seed
                 if x_init is not None:
                     x0 = x_init[b].contiguous().float()
@@ -140,8 +143,9 @@ class GaussianDiffusion(nn.Module):
                     # unseeded (MT:1201 draws from the global generator): ONE draw from it seeds the evaluator's counter-based
                     # generator -- S x 3 x T x h x w floats of pre-drawn noise would be GBs for the long clips the path supports
                     run_seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-                outs.append(ev.sample(clip, x0, steps, seed=run_seed or 0, noises=nz))
+                outs.append(ev.sample(clip, x0, steps, seed=run_seed or 0, noises=nz, null_clip=null_clip, cond_scale=cond_scale))
             self.last_trace = None
+            self.last_route = "ctx"
             return torch.stack(outs, 0)
         for b in range(B):
             cs = unet.build_clip(fea[b].contiguous().float(), cond[b].contiguous().float(), comm=comm,
@@ -170,6 +174,7 @@ class GaussianDiffusion(nn.Module):
                                          use_graph=self.use_graph, eager_every=self.eager_every))
             traces.append(tr)
         self.last_trace = traces if trace else None
+        self.last_route = "python"
         return torch.stack(outs, 0)
 
     def forward(self, *a, **k):

@@ -597,6 +597,24 @@ class HipOps:
               "dawn_cfg_combine")
         return out
 
+    def cfg_x0(self, e_null: Tensor, e_cond: Tensor, scale: float, x: Tensor, recip: float,
+               recipm1: float) -> Tuple[Tensor, Tensor, Tensor]:
+        """cfg_combine then ddim_x0 in ONE launch (dawn_cfg_x0, bit-identical to the pair) -> (eps, x0, hist)."""
+        n = x.numel()
+        _need(x.is_contiguous() and e_null.is_contiguous() and e_cond.is_contiguous() and e_null.numel() == n and e_cond.numel() == n,
+              "cfg_x0: contiguous e_null / e_cond / x of one size")
+        eps = torch.empty_like(e_cond)
+        x0 = torch.empty_like(x)
+        key = (x.device.index, self._stream())
+        ws = self._sel_ws.get(key)
+        if ws is None:
+            ws = self._sel_ws[key] = torch.empty(2048 + 1024 + 1024 + 8, device=x.device, dtype=torch.int32)
+        check(self.L.dawn_select_ws_reset(_p(ws), self._stream()), "dawn_select_ws_reset")
+        hist = ws[:2048]
+        check(self.L.dawn_cfg_x0(_p(e_null), _p(e_cond), float(scale), _p(x), recip, recipm1, n, _p(eps), _p(x0), _p(hist),
+                                 self._stream()), "dawn_cfg_x0")
+        return eps, x0, hist
+
     def philox_normal(self, Cc: int, F: int, f0: int, Ftotal: int, hw: int, seed: int, stream_id: int,
                       device) -> Tensor:
         out = torch.empty(Cc, F, hw, device=device, dtype=torch.float32)

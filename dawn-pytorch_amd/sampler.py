@@ -12,7 +12,7 @@ import torch
 import torch.nn.functional as F_
 
 from .pack import PackedUNet
-from .unet_forward import ClipState, unet_forward
+from .unet_forward import ClipState, unet_forward, unet_forward_guided
 
 Tensor = torch.Tensor
 
@@ -73,14 +73,19 @@ def ddim_sample_clip(ops, P: PackedUNet, cs: ClipState, x_init: Tensor, steps: S
                      eager_every: int = 0) -> Tensor:
     """x_init (3, F, h, w) on the ops' device -> final latent (3, F, h, w).
 
-    noise_fn(i) returns the N(0,1) tensor of step i (only called when t_next > 0, MT:1201)."""
+    noise_fn(i) returns the N(0,1) tensor of step i (only called when t_next > 0, MT:1201).
+    cond_scale != 1: every step evaluates both branches with the condition-free prefix once (unet_forward_guided; cs_null = the
+    clip state of the all-zero condition), then ONE launch forms the guided eps, x0 and the first quantile histogram (ops.cfg_x0)."""
     x = x_init.contiguous()
     n_total = 3 * cs.Ttotal * cs.h * cs.w
     graphed = None
-    if use_graph and cond_scale == 1.0 and cs.comm is None and x.is_cuda:
+    guided = cond_scale != 1.0
+    if guided and cs_null is None:
+        raise ValueError("cond_scale != 1 needs cs_null (the clip state of the all-zero condition)")
+    if use_graph and cs.comm is None and x.is_cuda:
         from .unet_forward import GraphedForward
         try:
-            graphed = GraphedForward(ops, P, cs, x, steps[0]["t"])
+            graphed = GraphedForward(ops, P, cs, x, steps[0]["t"], cs_null=cs_null if guided else None)
         except Exception as e:                                   # noqa: BLE001  (capture is an optimisation only)
             ops.graph_error = f"{type(e).__name__}: {str(e)[:200]}"
             graphed = None
@@ -92,18 +97,18 @@ def ddim_sample_clip(ops, P: PackedUNet, cs: ClipState, x_init: Tensor, steps: S
         ops.prof_on = (i % prof_every == 0)     # per-kernel HIP events (bench.py roofline) on every n-th step only
         # with a graph, every `eager_every`-th step still runs eagerly so that per-kernel HIP events (bench.py's
         # live roofline measurement) sample the timed region
-        if graphed is not None and not (eager_every and ops.prof is not None and i % eager_every == 0):
-            eps = graphed(x, st["t"])
+        replay = graphed is not None and not (eager_every and ops.prof is not None and i % eager_every == 0)
+        if guided:
+            eps_c, eps_null = graphed(x, st["t"]) if replay else unet_forward_guided(ops, P, cs, cs_null, x, st["t"])
+            eps, x0, hist = ops.cfg_x0(eps_null, eps_c, cond_scale, x, st["recip"], st["recipm1"])
+            del eps_c, eps_null
         else:
-            eps = unet_forward(ops, P, cs, x, st["t"])
-        if cond_scale != 1.0:
-            eps_null = unet_forward(ops, P, cs_null, x, st["t"])
-            eps = ops.cfg_combine(eps_null, eps, cond_scale)
-        x0, hist = ops.ddim_x0(x, eps, st["recip"], st["recipm1"])
+            eps = graphed(x, st["t"]) if replay else unet_forward(ops, P, cs, x, st["t"])
+            x0, hist = ops.ddim_x0(x, eps, st["recip"], st["recipm1"])
         s = ops.quantile_threshold(x0, hist, n_total, 0.9)
         noise = noise_fn(i) if st["t_next"] > 0 else None
         x = ops.ddim_update(x0, eps, s, noise, st["sqrt_alpha_next"], st["c"], st["sigma"])
         if trace is not None:
             # a graphed evaluation returns its static output buffer: clone, or every entry would alias the last step
-            trace.append(dict(eps=eps.clone() if graphed is not None else eps, s=s, x=x))
+            trace.append(dict(eps=eps.clone() if graphed is not None and not guided else eps, s=s, x=x))
     return x

@@ -15,7 +15,7 @@ import torch
 from torch import nn
 
 from .pack import PackedUNet, pack_unet
-from .unet_forward import ClipState, build_clip_state, unet_forward
+from .unet_forward import ClipState, build_clip_state, unet_forward, unet_forward_guided
 
 Tensor = torch.Tensor
 HIDDEN = 256          # attn_heads * attn_dim_head = 8 * 32
@@ -225,12 +225,37 @@ class Unet3D(nn.Module):
                                 f0=f0)
 
     def forward_with_cond_scale(self, *args, cond_scale=2., **kwargs):
-        logits = self.forward(*args, null_cond_prob=0., **kwargs)
         if cond_scale == 1 or not self.has_cond:
-            return logits
-        null_logits = self.forward(*args, null_cond_prob=1., **kwargs)
-        outs = [self._ops().cfg_combine(n.contiguous(), l.contiguous(), cond_scale) for n, l in zip(null_logits, logits)]
+            return self.forward(*args, null_cond_prob=0., **kwargs)
+        return self._forward_guided(*args, cond_scale=cond_scale, **kwargs)
+
+    @torch.no_grad()
+    def _forward_guided(self, x, time, cond=None, cond_scale=2., focus_present_mask=None, prob_focus_present=0.):
+        """null + (cond - null) * cond_scale (MT:884-890) with the condition-free prefix of the two evaluations run once
+        (unet_forward.unet_forward_guided); bit-identical to the two separate forward() calls + cfg_combine."""
+        self._check_inputs(x, cond, prob_focus_present, focus_present_mask)
+        ops, P = self._ops(), self.packed()
+        outs = []
+        for b in range(x.shape[0]):
+            fea272 = x[b, 3:, 0].contiguous()
+            cs = build_clip_state(ops, P, fea272, cond[b].contiguous().float(), self.win_width)
+            cs_null = build_clip_state(ops, P, fea272, torch.zeros_like(cond[b]).float(), self.win_width)    # MT:920
+            eps_c, eps_n = unet_forward_guided(ops, P, cs, cs_null, x[b, :3].contiguous(), int(time[b]))
+            outs.append(ops.cfg_combine(eps_n, eps_c, cond_scale))
+        self.null_cond_mask = torch.full((x.shape[0], self.num_frames), True, dtype=torch.bool, device=x.device)
         return torch.stack(outs, 0)
+
+    def _check_inputs(self, x, cond, prob_focus_present, focus_present_mask):
+        assert not (self.has_cond and cond is None), 'cond must be passed in if cond_dim specified'
+        if prob_focus_present or (focus_present_mask is not None and bool(focus_present_mask.any())):
+            raise NotImplementedError("training-time stochastic masks are out of scope of the HIP inference path")
+        # input validation (the hoisted init-conv part assumes it): EVERY frame carries the same fea / bbox channels, as
+        # `ddim_sample` builds them (MT:1167); checked in 32-frame slabs to bound the temporary
+        T = x.shape[2]
+        ref0 = x[:, 3:, :1]
+        for f0 in range(0, T, 32):
+            if not bool((x[:, 3:, f0:f0 + 32] == ref0).all()):
+                raise NotImplementedError("fea/bbox channels must be identical for every frame (MT:1167)")
 
     @torch.no_grad()
     def forward(self, x, time, cond=None, null_cond_prob=0., focus_present_mask=None, prob_focus_present=0.):

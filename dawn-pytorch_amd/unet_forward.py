@@ -99,8 +99,23 @@ def _ln_gemm(ops, x: Tensor, x2: Optional[Tensor], w: Tensor, N: int, w_bf3: Opt
     return ops.conv_gemm(ops.ln_rows(x, x2), w, N, w_bf3=w_bf3, **g)
 
 
+def _block_film(rb: PackedResBlock, film_all: Tensor):
+    return (film_all[rb.film_off:rb.film_off + rb.Co], film_all[rb.film_off + rb.Co:rb.film_off + 2 * rb.Co]) if rb.conditioned else None
+
+
+def _conv1_and_stats(ops, rb: PackedResBlock, x: Tensor, x2: Optional[Tensor], F: int, H: int, W: int, film, total_rows: int):
+    """conv1 of a ResBlock + its GroupNorm coefficients (partial sums from the conv epilogue, no separate statistics pass over c).
+    Reads x and the time FiLM only: the part of a block that does not see the condition."""
+    part = ops.conv_gn_part(F * H * W, rb.Co, x)
+    c = ops.conv_gemm(x, rb.w1, rb.Co, in1=x2, bias=rb.b1, KH=3, KW=3, pad=1, gn_part=part, w_bf3=rb.w1s, w_wino=rb.w1w,
+                      gn_fin=(rb.g1, rb.be1, film, total_rows), w_wino4=getattr(rb, "w1w4", None), F=F, Hi=H, Wi=W)
+    return c, ops.gn_coeffs(c, rb.g1, rb.be1, film, total_rows, part=part)
+
+
 def _resblock(ops, rb: PackedResBlock, x: Tensor, x2: Optional[Tensor], F: int, H: int, W: int, film_all: Tensor,
-              cs: ClipState) -> Tensor:
+              cs: ClipState, pre=None, keep_pre: bool = False) -> Tensor:
+    """pre = (c1, (a, b)) from _conv1_and_stats, computed by the caller (the guided evaluation's shared prefix); keep_pre: c1 is read
+    again by another branch, so h1 is written to a tensor of its own instead of over c1."""
     Co = rb.Co
     total_rows = cs.Ttotal * H * W
     g = dict(F=F, Hi=H, Wi=W)
@@ -113,11 +128,12 @@ def _resblock(ops, rb: PackedResBlock, x: Tensor, x2: Optional[Tensor], F: int, 
         """h_cond -- or, with gn = (c1, a, b), the block's h1 = SiLU(GN(c1)) + h_cond straight from the kernel's epilogue."""
         if fused_c64:
             return ops.xattn_layer_c64(x, x2, H * W, rb.wq, rb.wo, rb.g3, rb.q_scale, cs.kvtab[rb.cond_index],
-                                       cs.nulltab[rb.cond_index], xtab=cs.xtab[rb.cond_index], wq_bf3=rb.wqs, gn=gn, h1_over_c1=True)
+                                       cs.nulltab[rb.cond_index], xtab=cs.xtab[rb.cond_index], wq_bf3=rb.wqs, gn=gn,
+                                       h1_over_c1=not keep_pre)
         # LayerNorm_img is materialised (one streaming pass) so that to_q runs as a prologue-free GEMM
         q = _ln_gemm(ops, x, x2, rb.wq, 192, rb.wqs, **g)
         if fused_out:
-            return ops.xattn_sigma_out(q, H * W, cs.xtab[rb.cond_index], rb.g3, Co, gn=gn, h1_over_c1=True)
+            return ops.xattn_sigma_out(q, H * W, cs.xtab[rb.cond_index], rb.g3, Co, gn=gn, h1_over_c1=not keep_pre)
         ops.xattn_core(q, H * W, cs.kvtab[rb.cond_index], cs.nulltab[rb.cond_index], rb.q_scale)
         y3 = ops.empty(F * H * W, 3 * Co, like=x)
         for b in range(3):
@@ -126,22 +142,23 @@ def _resblock(ops, rb: PackedResBlock, x: Tensor, x2: Optional[Tensor], F: int, 
         return ops.xattn_ln_sum(y3, rb.g3, Co)
 
     def conv1_and_stats():
-        # GroupNorm partial sums come out of the conv epilogue (no separate statistics pass over c)
-        part = ops.conv_gn_part(F * H * W, Co, x)
-        c = ops.conv_gemm(x, rb.w1, Co, in1=x2, bias=rb.b1, KH=3, KW=3, pad=1, gn_part=part, w_bf3=rb.w1s, w_wino=rb.w1w,
-                          gn_fin=(rb.g1, rb.be1, film, total_rows), w_wino4=getattr(rb, "w1w4", None), **g)
-        return c, ops.gn_coeffs(c, rb.g1, rb.be1, film, total_rows, part=part)
+        if pre is not None:
+            return pre
+        return _conv1_and_stats(ops, rb, x, x2, F, H, W, film, total_rows)
 
     h1 = None
     if rb.conditioned:
-        film = (film_all[rb.film_off:rb.film_off + Co], film_all[rb.film_off + Co:rb.film_off + 2 * Co])
+        film = _block_film(rb, film_all)
         if (fused_c64 or fused_out) and getattr(ops, "fuse_h1", True):
             # conv1 + statistics first, then the cross-attention kernel writes h1 = SiLU(FiLM(GN(c1))) + h_cond from its epilogue:
             # no h_cond tensor, no GroupNorm-apply pass (20 launches and 0.42 GB per level-0 block less per evaluation).  The
             # two-stream overlap this replaces bought nothing on a power-limited chip (profiles/r3_*: 145.4 vs 140 frames/s without it)
             c1, ab1 = conv1_and_stats()
-            h1 = cross_attention(gn=(c1, ab1[0], ab1[1]))           # (written OVER c1: one tensor less through the caches)
+            h1 = cross_attention(gn=(c1, ab1[0], ab1[1]))           # (written OVER c1 unless keep_pre: one tensor less through the caches)
             del c1
+        elif pre is not None:
+            hcond = cross_attention()
+            c1, ab1 = pre
         else:
             # the HBM-bound cross-attention chain and the MFMA-bound conv1 + GroupNorm statistics only meet at
             # h1 = SiLU(GN(c1)) + h_cond: run them on two HIP streams so that they overlap on the GPU
@@ -152,7 +169,7 @@ def _resblock(ops, rb: PackedResBlock, x: Tensor, x2: Optional[Tensor], F: int, 
     # the 3x3 loader: an implicit GEMM reads every input element 9x, and 9x exp/div per element cost the conv
     # ~35 % of its MFMA rate (profiles/r1_b_conv_shapes.txt) -- far more than the extra 3 x C x 4 B per pixel.
     if h1 is None:
-        h1 = ops.gn_apply_res(c1, ab1[0], ab1[1], hcond, inplace=True)      # (over c1: it has no other reader)
+        h1 = ops.gn_apply_res(c1, ab1[0], ab1[1], hcond, inplace=not keep_pre)      # (over c1 when it has no other reader)
         del c1, hcond
     part2 = ops.conv_gn_part(F * H * W, Co, x)
     c2 = ops.conv_gemm(h1, rb.w2, Co, bias=rb.b2, KH=3, KW=3, pad=1, gn_part=part2, w_bf3=rb.w2s, w_wino=rb.w2w,
@@ -357,13 +374,23 @@ def unet_forward(ops, P: PackedUNet, cs: ClipState, x3: Tensor, t: float, film_a
     predicted noise (3, F, h, w).  Equivalent to Unet3D.forward(cat[x, fea], t, cond) with
     null_cond_prob = 0 (MT:892-956).  `film_all` (the only t-dependent input besides x) may be supplied
     precomputed so that the rest of the evaluation is a fixed launch sequence (see GraphedForward)."""
-    F, H, W = cs.F, cs.h, cs.w
+    film_all = _begin(ops, P, cs, x3, t, film_all)
+    return _unet_rest(ops, P, cs, x3, film_all, list(_init_layers(ops, P, cs, x3)))
+
+
+def _begin(ops, P: PackedUNet, cs: ClipState, x3: Tensor, t: float, film_all: Optional[Tensor]) -> Tensor:
     if hasattr(ops, "begin_evaluation"):
         ops.begin_evaluation(x3)      # (the fused GroupNorm hand-off starts every evaluation from a zeroed ticket)
     if film_all is None:
         film_all = time_film(ops, P, t, cs.fea_pre)
     if cs.comm is not None and hasattr(cs.comm, "keep_buffers"):
-        cs.comm.keep_buffers = F <= LONG_CLIP_FRAMES
+        cs.comm.keep_buffers = cs.F <= LONG_CLIP_FRAMES
+    return film_all
+
+
+def _init_layers(ops, P: PackedUNet, cs: ClipState, x3: Tensor):
+    """init_conv -> r (the heads' skip, MT:906-907) and the init temporal layer -> x (MT:908); None for r in the long-clip lean form."""
+    F, H, W = cs.F, cs.h, cs.w
     if cs.comm is not None and hasattr(cs.comm, "own_view"):
         # T-sharded: `r` stays a tensor of its own (it is the skip of the heads, MT:911 / 955); its frames are convolved edge frames
         # first and copied into the temporal layer's extended buffer, so that the halo transfer runs behind the interior frames
@@ -382,6 +409,26 @@ def unet_forward(ops, P: PackedUNet, cs: ClipState, x3: Tensor, t: float, film_a
     if F > LONG_CLIP_FRAMES:
         r = None                     # long clips / shards: the heads' skip is recomputed at the end (0.8 % of an evaluation; frame-local, so
                                      # no halo is involved) instead of held through the evaluation
+    return r, x
+
+
+def unet_prefix(ops, P: PackedUNet, cs: ClipState, x3: Tensor, film_all: Tensor):
+    """The part of an evaluation that does not see the condition (MT:905-908 run before the condition is masked, MT:917-922): init
+    conv -> r, init temporal layer -> x, and conv1 + GroupNorm coefficients of downs[0].rb1 (they read x and the time FiLM only).
+    Returns (r, x, (c1, (a, b))); both branches of a guided evaluation continue from it (_unet_rest)."""
+    r, x = _init_layers(ops, P, cs, x3)
+    rb = P.downs[0]["rb1"]
+    pre = _conv1_and_stats(ops, rb, x, None, cs.F, cs.h, cs.w, _block_film(rb, film_all), cs.Ttotal * cs.h * cs.w)
+    return r, x, pre
+
+
+def _unet_rest(ops, P: PackedUNet, cs: ClipState, x3: Tensor, film_all: Tensor, holder: list, keep_pre: bool = False) -> Tensor:
+    """Everything after the init layers.  holder = [r, x] or [r, x, pre] (pre: downs[0].rb1's conv1 + statistics from unet_prefix),
+    emptied here so that no caller frame keeps a level-0 tensor alive through the evaluation.  keep_pre: another branch still reads
+    the prefix, so nothing of it is written over."""
+    F, H, W = cs.F, cs.h, cs.w
+    r, x, pre = (holder + [None])[:3]
+    holder.clear()
     skips: List[Tuple[Tensor, int, int]] = []
     sharded = cs.comm is not None and hasattr(cs.comm, "own_view")
 
@@ -389,7 +436,8 @@ def unet_forward(ops, P: PackedUNet, cs: ClipState, x3: Tensor, t: float, film_a
         # (holder = [x], the only reference: the spatial layer's input is not held across the temporal layer -- peak memory)
         return _spatial_then_temporal(ops, sp, tattn, holder, F, H, W, cs, spatial)
     for lvl in P.downs:
-        x = _resblock(ops, lvl["rb1"], x, None, F, H, W, film_all, cs)
+        x = _resblock(ops, lvl["rb1"], x, None, F, H, W, film_all, cs, pre=pre, keep_pre=keep_pre)
+        pre = None
         x = _resblock(ops, lvl["rb2"], x, None, F, H, W, film_all, cs)
         holder = [x]
         del x
@@ -436,14 +484,36 @@ def unet_forward(ops, P: PackedUNet, cs: ClipState, x3: Tensor, t: float, film_a
     return eps.reshape(3, F, H, W)
 
 
+def unet_forward_guided(ops, P: PackedUNet, cs: ClipState, cs_null: ClipState, x3: Tensor, t: float,
+                        film_all: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """Both branches of a classifier-free-guided evaluation (Unet3D.forward_with_cond_scale, MT:879-890) -> (eps_cond, eps_null),
+    each bit-identical to its own unet_forward.  The prefix (unet_prefix) runs once; the conditional branch keeps it intact, the null
+    branch (cs_null: the clip state of the all-zero condition, MT:920) then consumes it.  Long clips recompute the heads' skip r in
+    each branch (as unet_forward does) instead of holding it."""
+    film_all = _begin(ops, P, cs, x3, t, film_all)
+    r, x, pre = unet_prefix(ops, P, cs, x3, film_all)
+    eps_c = _unet_rest(ops, P, cs, x3, film_all, [r, x, pre], keep_pre=True)
+    holder = [r, x, pre]
+    del r, x, pre
+    eps_n = _unet_rest(ops, P, cs_null, x3, film_all, holder)
+    return eps_c, eps_n
+
+
 class GraphedForward:
     """One UNet evaluation captured ONCE per clip as a HIP graph (torch.cuda.CUDAGraph is only the capture /
     replay plumbing: every node is one of our kernels launched through the C ABI on the capturing stream) and
     replayed for each DDIM step.  ~370 launches per evaluation are otherwise host-bound at the deep (small-
-    kernel) levels.  Inputs that change per step live in static buffers: the latent `x` and the FiLM vector."""
+    kernel) levels.  Inputs that change per step live in static buffers: the latent `x` and the FiLM vector.
+    With `cs_null` the graph holds the whole guided evaluation (unet_forward_guided: the shared prefix and both branches) and a
+    replay returns (eps_cond, eps_null)."""
 
-    def __init__(self, ops, P: PackedUNet, cs: ClipState, x_like: Tensor, t0: float):
+    def __init__(self, ops, P: PackedUNet, cs: ClipState, x_like: Tensor, t0: float, cs_null: Optional[ClipState] = None):
         self.ops, self.P, self.cs = ops, P, cs
+
+        def evaluate():
+            if cs_null is None:
+                return unet_forward(ops, P, cs, self.x, t0, film_all=self.film)
+            return unet_forward_guided(ops, P, cs, cs_null, self.x, t0, film_all=self.film)
         self.x = torch.empty_like(x_like)
         self.film = time_film(ops, P, t0, cs.fea_pre).clone()
         prof, ops.prof = ops.prof, None                      # no event records inside a capture
@@ -452,11 +522,11 @@ class GraphedForward:
             side = torch.cuda.Stream(device=x_like.device)
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):                    # warm-up outside capture (allocator, lazy inits)
-                unet_forward(ops, P, cs, self.x, t0, film_all=self.film)
+                evaluate()
             torch.cuda.current_stream().wait_stream(side)
             self.graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.graph):
-                self.out = unet_forward(ops, P, cs, self.x, t0, film_all=self.film)
+                self.out = evaluate()
         finally:
             ops.prof = prof
 

@@ -296,6 +296,11 @@ int dawn_ddim_update(const float* x0, const float* eps, const float* s, const fl
                      float sqrt_alpha_next, float c, float sigma, long n, float* x, void* stream);
 /* classifier-free guidance (Unet3D.forward_with_cond_scale MT:889-890): out = null + (cond-null)*scale */
 int dawn_cfg_combine(const float* e_null, const float* e_cond, float scale, long n, float* out, void* stream);
+/* cfg_combine then ddim_x0 in one pass: eps_out = null + (cond-null)*scale, x0_out = recip*x - recipm1*eps_out, and the 2048-bin
+ * histogram of |x0| added into hist1 (zeroed by the caller) -- bit-identical to dawn_cfg_combine followed by dawn_ddim_x0.
+ * eps_out may alias e_null or e_cond; x0_out must not alias x or eps_out. */
+int dawn_cfg_x0(const float* e_null, const float* e_cond, float scale, const float* x, float recip, float recipm1, long n,
+                float* eps_out, float* x0_out, unsigned* hist1, void* stream);
 /* counter-based N(0,1): Philox4x32-10 keyed by seed, counter = (stream_id, global element index / 4) */
 int dawn_philox_normal(float* out, int C, int F, int f0, int Ftotal, int hw, uint64_t seed, uint32_t stream_id,
                        void* stream);
@@ -446,6 +451,21 @@ int dawn_unet_forward_sharded(dawn_ctx* ctx, int F, int h, int w, const void* cl
 int dawn_sampler_run_sharded(dawn_ctx* ctx, int F, int h, int w, const void* clip_mem, const float* x_init, int S,
                              const dawn_ddim_step* steps, uint64_t seed, const float* const* noises, float* x_out,
                              float* thresholds, void* workspace, size_t workspace_bytes, const dawn_shard_comm* comm, void* stream);
+/* ---- classifier-free guidance on the whole path (Unet3D.forward_with_cond_scale MT:879-890, cond_scale != 1).  null_clip_mem is a clip
+ * prepared by dawn_clip_prepare from the SAME fea272 with an all-zero condition (learn_null_cond = False, MT:920): ld_cond = 0 with a
+ * single zero row of cond_dim floats is enough.  One guided evaluation runs the condition-free prefix ONCE (init conv, init temporal
+ * layer with its halo exchange, conv1 + GroupNorm statistics of downs[0].rb1), then the conditional and the null branch, then
+ * eps = null + (cond - null) * cond_scale; every result is bit-identical to two dawn_unet_forward calls + dawn_cfg_combine.
+ * comm = NULL: single GPU (rank 0, world 1 for the workspace query). */
+size_t dawn_workspace_bytes_guided(dawn_ctx* ctx, int F, int h, int w, int rank, int world);
+int dawn_unet_forward_guided(dawn_ctx* ctx, int F, int h, int w, const void* clip_mem, const void* null_clip_mem, const float* x3, float t,
+                             float cond_scale, float* eps_out, void* workspace, size_t workspace_bytes, const dawn_shard_comm* comm,
+                             void* stream);
+/* dawn_sampler_run(_sharded) with every evaluation guided; guided eps, x0 and the first quantile histogram come from one dawn_cfg_x0 launch */
+int dawn_sampler_run_guided(dawn_ctx* ctx, int F, int h, int w, const void* clip_mem, const void* null_clip_mem, float cond_scale,
+                            const float* x_init, int S, const dawn_ddim_step* steps, uint64_t seed, const float* const* noises,
+                            float* x_out, float* thresholds, void* workspace, size_t workspace_bytes, const dawn_shard_comm* comm,
+                            void* stream);
 /* after a stream synchronise: (kind, algorithmic flops, algorithmic bytes, ms) per conv launch recorded under
  * DAWN_OPT_PROFILE; kind 0 = split 3x3, 1 = split 1x1, 2 = fp32 MFMA; returns the number of entries (and clears them) */
 int dawn_ctx_profile_read(dawn_ctx* ctx, double* out4, int max_entries);

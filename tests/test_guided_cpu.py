@@ -1,0 +1,139 @@
+"""Guided sampling (cond_scale != 1) without a GPU: the C-ABI entries exist and are bound, the prefix / rest split of the Python
+orchestration reproduces the reference's guided DDIM trajectory on the torch reference op set, and the reference-pinned fixtures
+are well-formed data."""
+import os
+import re
+
+import numpy as np
+import torch
+
+from conftest import GOLDEN, ROOT, load_golden
+from oracle.ops_ref import RefOps
+import dawn_pytorch_amd as D
+from dawn_pytorch_amd import _lib
+from dawn_pytorch_amd.pack import pack_unet
+from dawn_pytorch_amd.unet_forward import build_clip_state, unet_forward, unet_forward_guided
+
+T = torch.from_numpy
+GUIDED = {"dawn_cfg_x0", "dawn_workspace_bytes_guided", "dawn_unet_forward_guided", "dawn_sampler_run_guided"}
+TINY_KW = dict(dim=16, cond_dim=32, cond_aud=24, cond_pose=6, cond_eye=2, num_frames=12, channels=19,
+               out_grid_dim=2, out_conf_dim=1, dim_mults=(1, 2), use_hubert_audio_cond=True, learn_null_cond=False,
+               use_final_activation=False, use_deconv=True, padding_mode="zeros", win_width=3)
+
+
+class GuidedRefOps(RefOps):
+    """The reference op set plus the fused guidance + x0 step, composed from its two reference ops."""
+
+    def cfg_x0(self, e_null, e_cond, scale, x, recip, recipm1):
+        eps = self.cfg_combine(e_null, e_cond, scale)
+        x0, hist = self.ddim_x0(x, eps, recip, recipm1)
+        return eps, x0, hist
+
+
+def test_guided_symbols_declared_exported_and_bound():
+    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "dawn_hip.h")).read(), flags=re.S)
+    declared = set(re.findall(r"\b(dawn_[a-z0-9_]+)\s*\(", src))
+    assert GUIDED <= declared
+    assert GUIDED <= set(_lib.SIGNATURES)
+    L = _lib.lib()
+    for n in GUIDED:
+        assert hasattr(L, n), n
+    assert L.dawn_abi_version() == 8
+    # argument counts of the bindings = the C declarations
+    for n in GUIDED:
+        decl = re.search(r"\b" + n + r"\s*\(([^;]*)\)\s*;", src, flags=re.S).group(1)
+        assert len(_lib.SIGNATURES[n]) == decl.count(",") + 1, n
+
+
+def _tiny_diffusion(sd, S, ops):
+    unet = D.DynamicNfUnet3D(default_num_frames=12, **TINY_KW)
+    unet.load_state_dict({k[len("denoise_fn."):]: v for k, v in sd.items()})
+    unet.ops = ops
+    diff = D.DynamicNfGaussianDiffusion(default_num_frames=12, denoise_fn=unet, num_frames=12, image_size=8, sampling_timesteps=S,
+                                        timesteps=1000, loss_type='l2', use_dynamic_thres=True, null_cond_prob=0.1,
+                                        ddim_sampling_eta=1.0)
+    diff.update_num_frames(12)
+    return unet, diff
+
+
+def test_guided_orchestration_matches_reference_trajectory(tiny):
+    g, sd = tiny
+    d = load_golden("ddim_guided_tiny.npz")
+    _, diff = _tiny_diffusion(sd, int(d["S"]), GuidedRefOps())
+    out = diff.sample(T(d["fea"]), T(d["bbox"]), cond=T(d["cond"]), cond_scale=float(d["cond_scale"]), x_init=T(d["x_init"]),
+                      noises=[n for n in T(d["noises"])], trace=True)
+    tr = diff.last_trace[0]
+    qs = torch.stack([e["s"][1] for e in tr])
+    torch.testing.assert_close(qs, T(d["quantiles"]).float(), atol=1e-4, rtol=1e-5)
+    for s in d["keep"].tolist():
+        torch.testing.assert_close(tr[s - 1]["x"], T(d[f"x_before_step_{s}"])[0], atol=1e-4, rtol=1e-5)
+    torch.testing.assert_close(out, T(d["out"]), atol=1e-4, rtol=1e-5)
+    # guidance changes the trajectory: the unguided golden is a different sample
+    assert float((out - T(load_golden("ddim_tiny.npz")["out"])).abs().max()) > 1e-2
+
+
+def test_prefix_shared_evaluation_equals_two_evaluations(tiny):
+    """unet_forward_guided (prefix once, both branches from it) == two independent unet_forward calls, on the fused and the op-by-op
+    routes of the reference op set."""
+    g, sd = tiny
+    P = pack_unet(sd, win=3, device="cpu")
+    x = T(g["x"])[0]
+    cond = T(g["cond"])[0]
+    ops = RefOps()
+    cs = build_clip_state(ops, P, x[3:, 0].contiguous(), cond)
+    cs_null = build_clip_state(ops, P, x[3:, 0].contiguous(), torch.zeros_like(cond))
+    eps_c, eps_n = unet_forward_guided(ops, P, cs, cs_null, x[:3].contiguous(), int(g["time"][0]))
+    assert torch.equal(eps_c, unet_forward(ops, P, cs, x[:3].contiguous(), int(g["time"][0])))
+    assert torch.equal(eps_n, unet_forward(ops, P, cs_null, x[:3].contiguous(), int(g["time"][0])))
+    # and the reference's guided forward (tiny_unet.npz: forward_with_cond_scale(cond_scale=2.5) of the reference)
+    got = ops.cfg_combine(eps_n, eps_c, 2.5)
+    torch.testing.assert_close(got, T(g["y_cond_scale_2p5"])[0], atol=1e-4, rtol=1e-5)
+
+
+def test_module_forward_with_cond_scale_matches_reference(tiny):
+    g, sd = tiny
+    unet, _ = _tiny_diffusion(sd, 1, RefOps())
+    y = unet.forward_with_cond_scale(T(g["x"]), T(g["time"]), cond=T(g["cond"]), cond_scale=2.5)
+    torch.testing.assert_close(y, T(g["y_cond_scale_2p5"]), atol=1e-4, rtol=1e-5)
+
+
+def test_guided_fixtures_are_read_only_well_formed_data():
+    for name, (Tt, h) in {"ddim_guided_tiny.npz": (12, 8), "ddim_guided_C1.npz": (16, 32)}.items():
+        path = os.path.join(GOLDEN, name)
+        assert os.path.getsize(path) < 2_000_000
+        with np.load(path, allow_pickle=False) as z:            # data only: no pickled objects
+            d = {k: z[k] for k in z.files}
+        S = int(d["S"])
+        assert float(d["cond_scale"]) == 2.5
+        assert d["quantiles"].shape == (S,) and np.isfinite(d["quantiles"]).all() and (d["quantiles"] > 0).all()
+        out = d["out"].reshape(-1, 3, Tt, h, h)
+        assert np.isfinite(out).all() and np.abs(out).max() <= 1.0 + 1e-6       # dynamic thresholding keeps |x0| <= 1 at the end
+        for s in d["keep"].tolist():
+            assert 0 < s < S and d[f"x_before_step_{s}"].reshape(-1, 3, Tt, h, h).shape[0] == 1
+        for v in d.values():
+            assert v.dtype != object
+
+
+def test_prefix_shared_evaluation_on_a_tshard_rank(tiny):
+    """The same equality on ONE interior rank of a T-sharded clip (simulated halos): the prefix's GroupNorm statistics are over the
+    whole clip, as in every other block, and the init layer's halo exchange happens once per guided evaluation."""
+    from dawn_pytorch_amd.tshard import SimulatedInteriorShard
+    g, sd = tiny
+    P = pack_unet(sd, win=3, device="cpu")
+    x = T(g["x"])[0]
+    cond = T(g["cond"])[0]
+    F = cond.shape[0]
+    evals = []
+    for guided in (False, True):
+        comm = SimulatedInteriorShard(F, world=3, rank=1)
+        ops = RefOps().with_comm(comm)
+        mk = lambda c: build_clip_state(ops, P, x[3:, 0].contiguous(), c, comm=comm, Ttotal=3 * F, f0=F)   # noqa: E731
+        cs, cs_null = mk(cond), mk(torch.zeros_like(cond))
+        if guided:
+            evals.append(unet_forward_guided(ops, P, cs, cs_null, x[:3].contiguous(), 300))
+        else:
+            evals.append((unet_forward(ops, P, cs, x[:3].contiguous(), 300), unet_forward(ops, P, cs_null, x[:3].contiguous(), 300)))
+        evals[-1] = (*evals[-1], comm.stats()["halo_exchanges"])
+    (c2, n2, h2), (cg, ng, hg) = evals
+    assert torch.equal(cg, c2) and torch.equal(ng, n2)
+    assert hg == h2 - 1, (hg, h2)
