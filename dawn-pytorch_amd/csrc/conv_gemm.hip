@@ -1794,7 +1794,10 @@ __global__ __launch_bounds__(256 * (CFG ? 1 : WN)) void gemm1x1_bf16_kernel(cons
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
+    // every stage wait below (vmcnt(NQ)) counts the A-row loads as the YOUNGEST NQ memory operations: the weight DMA of a stage
+    // is issued before its A rows, and the sched_barrier keeps the scheduler from moving either across the other
     issueB(0, 0);
+    __builtin_amdgcn_sched_barrier(0);
     loadA(0, 0);
     loadA(nS > 1 ? 1 : 0, 1);
 #pragma unroll
@@ -1815,6 +1818,7 @@ __global__ __launch_bounds__(256 * (CFG ? 1 : WN)) void gemm1x1_bf16_kernel(cons
         else asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();       // planes(s) + weights(s) complete; buffers of stage s-1 are free
         issueB(s + 1 < nS ? s + 1 : nS - 1, PAR ^ 1);
+        __builtin_amdgcn_sched_barrier(0);  // (the weight DMA before the A rows: the vmcnt(NQ) above relies on that order)
         // stage s+2's rows go into the register slot stage s used (split during stage s-1): a stage and a half ahead of their split
         loadA(s + 2 < nS ? s + 2 : nS - 1, PAR);
         __builtin_amdgcn_sched_barrier(0);  // (the fetches stay at the top of the stage)
@@ -2475,11 +2479,9 @@ static void launch_rowacc(const dawn_conv_desc& d, long M, hipStream_t s) {
 #undef LAUNCH_RA
 }
 
-bool try_launch_gemm1x1_rowacc(const dawn_conv_desc& d, long M, hipStream_t s) {
-    if (!gemm1x1_rowacc_ok(M, d.N, d.C0, d.C1)) return false;
-    if ((long)d.ld0 * 32 * 4 >= (1L << 31) || (long)d.ld1 * 32 * 4 >= (1L << 31) || (long)(d.C0 + d.C1) / 16 * 6 * d.N * 16 >= (1L << 31)) return false;
-    launch_rowacc<0>(d, M, s);
-    return true;
+static bool gemm1x1_rowacc_fits(const dawn_conv_desc& d, long M) {
+    return gemm1x1_rowacc_ok(M, d.N, d.C0, d.C1) && (long)d.ld0 * 32 * 4 < (1L << 31) && (long)d.ld1 * 32 * 4 < (1L << 31) &&
+           (long)(d.C0 + d.C1) / 16 * 6 * d.N * 16 < (1L << 31);
 }
 
 // Downsample (4x4 / stride 2 / pad 1) and Upsample (transposed 4x4 / stride 2 / pad 1 as 4 phases of 2x2 taps) on the split
@@ -2495,10 +2497,12 @@ static bool conv_resample_rowacc_ok(const dawn_conv_desc& d, long M) {
     return (long)(down ? 16 : 4) * d.C0 / 16 * 6 * d.N * 16 * (up ? 4 : 1) < (1L << 31);
 }
 
-bool try_launch_gemm1x1_rowreg(const dawn_conv_desc& d, long M, hipStream_t s) {
+static bool gemm1x1_rowreg_fits(const dawn_conv_desc& d, long M) {
+    return gemm1x1_rowreg_ok(M, d.N, d.C0, d.C1) && (long)d.ld0 * 32 * 4 < (1L << 31) && (long)d.ld1 * 32 * 4 < (1L << 31);
+}
+
+void launch_gemm1x1_rowreg(const dawn_conv_desc& d, long M, hipStream_t s) {
     const int K = d.C0 + d.C1;
-    if (!gemm1x1_rowreg_ok(M, d.N, d.C0, d.C1)) return false;
-    if ((long)d.ld0 * 32 * 4 >= (1L << 31) || (long)d.ld1 * 32 * 4 >= (1L << 31)) return false;
     const long nunits = (M / 256) * (d.N / 64);
     const int ncu = dawn_ncu();
     const int per = (int)((nunits + ncu - 1) / ncu);
@@ -2512,7 +2516,6 @@ bool try_launch_gemm1x1_rowreg(const dawn_conv_desc& d, long M, hipStream_t s) {
         (void)hipFuncSetAttribute((const void*)gemm1x1_rowreg_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         hipLaunchKernelGGL((gemm1x1_rowreg_kernel<4>), dim3(nwg), dim3(512), lds, s, d, M, per);
     }
-    return true;
 }
 
 template <int WN>
@@ -2570,12 +2573,9 @@ static bool gemm1x1_split_layout_ok(const dawn_conv_desc& d) {
     return true;
 }
 
-bool try_launch_gemm1x1_bf16(const dawn_conv_desc& d, long M, hipStream_t s) {
-    if (!gemm1x1_split_layout_ok(d)) return false;
+// the tiled split kernel (gemm1x1_bf16_kernel) for a descriptor split1x1_form() routed to it
+void launch_gemm1x1_tiled(const dawn_conv_desc& d, long M, hipStream_t s) {
     const int plan = gemm1x1_split_plan(M, d.N, d.C0, d.C1);
-    // short K: rows stationary in registers (policy bit 0x20000, A/B only: the tiled kernels)
-    if (!(policy_of(d) & 0x20000) && try_launch_gemm1x1_rowreg(d, M, s)) return true;
-    if (!(policy_of(d) & 0x20000) && try_launch_gemm1x1_rowacc(d, M, s)) return true;
     // policy bit 0x8000: 128 x 64 tiles for every eligible shape; 0x10000 (A/B only): never (the round-1 tile policy)
     if (plan != 0 && ((policy_of(d) & 0x8000) || (plan == 3 && !(policy_of(d) & 0x10000)))) launch_gemm1x1_bf16_small(d, M, s);
     else if (plan == 3) {                            // 0x10000: the round-1 choice for these shapes
@@ -2583,9 +2583,26 @@ bool try_launch_gemm1x1_bf16(const dawn_conv_desc& d, long M, hipStream_t s) {
         else launch_gemm1x1_bf16<1>(d, M, s);
     }
     else if (plan == 2) launch_gemm1x1_bf16<2>(d, M, s);
-    else if (plan == 1) launch_gemm1x1_bf16<1>(d, M, s);
-    else return false;
-    return true;
+    else launch_gemm1x1_bf16<1>(d, M, s);
+}
+
+// Which split-operand kernel serves a 1x1 projection or a 4x4 / stride-2 resample (DAWN_SPLIT1X1_* of include/dawn_hip.h; 0 = none
+// of them: the 3x3 paths or the fp32 kernels).  THE routing of dawn_conv_gemm -- it launches what this answers -- and of
+// dawn_gemm1x1_form.  With ln_eps > 0 only the row-stationary / row-accumulator kernels qualify (they hold whole rows).
+int split1x1_form(const dawn_conv_desc& d, long M) {
+    const int p = policy_of(d);
+    if (!(p & 0x1000) || !d.w_bf3) return DAWN_SPLIT1X1_NONE;
+    const bool rows_ok = !(p & 0x20000);             // policy bit 0x20000 (A/B only): the tiled kernel for every 1x1 shape
+    const bool proj = d.mode == 0 && d.KH == 1 && d.KW == 1 && d.stride == 1 && d.pad == 0 && !d.ch_a && !d.pro_act && !d.pro_add;
+    if (d.ln_eps > 0.f) {
+        if (!proj || d.row_mean || d.row_rstd || !gemm1x1_split_layout_ok(d) || !rows_ok) return DAWN_SPLIT1X1_NONE;
+        return gemm1x1_rowreg_fits(d, M) ? DAWN_SPLIT1X1_ROWREG : gemm1x1_rowacc_fits(d, M) ? DAWN_SPLIT1X1_ROWACC : DAWN_SPLIT1X1_NONE;
+    }
+    if (rows_ok && conv_resample_rowacc_ok(d, M)) return DAWN_SPLIT1X1_RESAMPLE;
+    if (!proj || (d.row_mean == nullptr) != (d.row_rstd == nullptr) || !gemm1x1_split_layout_ok(d)) return DAWN_SPLIT1X1_NONE;
+    if (rows_ok && gemm1x1_rowreg_fits(d, M)) return DAWN_SPLIT1X1_ROWREG;      // short K: rows stationary in registers
+    if (rows_ok && gemm1x1_rowacc_fits(d, M)) return DAWN_SPLIT1X1_ROWACC;
+    return gemm1x1_split_plan(M, d.N, d.C0, d.C1) != 0 ? DAWN_SPLIT1X1_TILED : DAWN_SPLIT1X1_NONE;
 }
 
 template <int BN, int WN>
@@ -2719,6 +2736,14 @@ extern "C" int dawn_conv3x3_form(const dawn_conv_desc* dp) {
     return 0;
 }
 
+/* Which split-operand kernel dawn_conv_gemm runs a 1x1 projection / 4x4 resample descriptor on (host code, launches nothing): the
+ * launch's own decision code, as dawn_conv3x3_form for the 3x3 convs. */
+extern "C" int dawn_gemm1x1_form(const dawn_conv_desc* dp) {
+    if (!dp) return DAWN_SPLIT1X1_NONE;
+    const dawn_conv_desc& d = *dp;
+    return split1x1_form(d, d.mode == 0 ? (long)d.F * d.Ho * d.Wo : (long)d.F * d.Hi * d.Wi);
+}
+
 extern "C" int dawn_conv_gemm(const dawn_conv_desc* dp, void* stream) {
     const dawn_conv_desc d = *dp;
     const int Cin = d.C0 + d.C1;
@@ -2733,22 +2758,15 @@ extern "C" int dawn_conv_gemm(const dawn_conv_desc* dp, void* stream) {
     const long M = (d.mode == 0) ? (long)d.F * d.Ho * d.Wo : (long)d.F * d.Hi * d.Wi;
     if (M <= 0 || d.N <= 0) return 0;
     hipStream_t s = (hipStream_t)stream;
-    if (d.ln_eps > 0.f) {                     // LayerNorm inside the GEMM: only the row-stationary kernel holds whole rows
-        if (!(d.w_bf3 && d.mode == 0 && d.KH == 1 && d.KW == 1 && d.stride == 1 && d.pad == 0 && !d.ch_a && !d.pro_act &&
-              !d.pro_add && !d.row_mean && !d.row_rstd && gemm1x1_split_layout_ok(d) && (policy_of(d) & 0x1000) &&
-              !(policy_of(d) & 0x20000) && (try_launch_gemm1x1_rowreg(d, M, s) || try_launch_gemm1x1_rowacc(d, M, s))))
-            return dawn_set_error_msg(-14, "dawn_conv_gemm: ln_eps needs a split 1x1 projection with dawn_gemm1x1_ln_inline_ok, 16-byte aligned "
-                                           "row strides and the split-kernel policy bits (0x1000 set, 0x20000 clear)");
-        DAWN_LAUNCH_CHECK();
-        return 0;
-    }
-    if ((policy_of(d) & 0x1000) && !(policy_of(d) & 0x20000) && d.w_bf3 && conv_resample_rowacc_ok(d, M)) {
-        if (d.mode == 0) launch_rowacc<1>(d, M, s); else launch_rowacc<2>(d, M, s);
-        DAWN_LAUNCH_CHECK();
-        return 0;
-    }
-    if ((policy_of(d) & 0x1000) && d.w_bf3 && d.mode == 0 && d.KH == 1 && d.KW == 1 && d.stride == 1 && d.pad == 0 && !d.ch_a &&
-        !d.pro_act && !d.pro_add && (d.row_mean == nullptr) == (d.row_rstd == nullptr) && try_launch_gemm1x1_bf16(d, M, s)) {
+    const int form1 = split1x1_form(d, M);
+    if (d.ln_eps > 0.f && form1 == DAWN_SPLIT1X1_NONE)    // LayerNorm inside the GEMM: only the row-stationary kernels hold whole rows
+        return dawn_set_error_msg(-14, "dawn_conv_gemm: ln_eps needs a split 1x1 projection with dawn_gemm1x1_ln_inline_ok, 16-byte aligned "
+                                       "row strides and the split-kernel policy bits (0x1000 set, 0x20000 clear)");
+    if (form1 != DAWN_SPLIT1X1_NONE) {
+        if (form1 == DAWN_SPLIT1X1_ROWREG) launch_gemm1x1_rowreg(d, M, s);
+        else if (form1 == DAWN_SPLIT1X1_ROWACC) launch_rowacc<0>(d, M, s);
+        else if (form1 == DAWN_SPLIT1X1_RESAMPLE) { if (d.mode == 0) launch_rowacc<1>(d, M, s); else launch_rowacc<2>(d, M, s); }
+        else launch_gemm1x1_tiled(d, M, s);
         DAWN_LAUNCH_CHECK();
         return 0;
     }

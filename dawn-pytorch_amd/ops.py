@@ -139,9 +139,11 @@ class HipOps:
                   pro_act: int = 0, pro_add: Optional[Tensor] = None, res: Optional[Tensor] = None,
                   tr: Optional[Tuple[Tensor, Tensor, Tensor]] = None, out: Optional[Tensor] = None,
                   gn_part: Optional[Tensor] = None, w_bf3: Optional[Tensor] = None, ln_eps: float = 0.0,
-                  w_wino: Optional[Tensor] = None, gn_fin: Optional[tuple] = None, w_wino4: Optional[Tensor] = None) -> Tensor:
+                  w_wino: Optional[Tensor] = None, gn_fin: Optional[tuple] = None, w_wino4: Optional[Tensor] = None,
+                  form_only: bool = False) -> Tensor:
         """gn_fin = (gamma, beta, film or None, total_rows[, eps]) with gn_part: ask the launch to finish the GroupNorm itself (the
-        Winograd 3x3 kernel's last workgroup reduces and finalises); gn_coeffs(part=...) then returns its coefficients without a launch."""
+        Winograd 3x3 kernel's last workgroup reduces and finalises); gn_coeffs(part=...) then returns its coefficients without a launch.
+        form_only: launch nothing and return (dawn_conv3x3_form, dawn_gemm1x1_form) of exactly this call's descriptor."""
         Ho = Hi if Ho is None else Ho
         Wo = Wi if Wo is None else Wo
         rows_out = F * Ho * Wo
@@ -173,6 +175,8 @@ class HipOps:
         d.ln_eps = ln_eps
         if self.sk_ws is not None and w_bf3 is not None and KH == 3 and KW == 3 and stride == 1 and mode == 0:
             d.sk_ws, d.sk_ws_bytes = _p(self.sk_ws), self.sk_ws.numel()        # (ignored by the shipped library)
+        if form_only:
+            return self.conv3x3_form(d), int(self.L.dawn_gemm1x1_form(C.byref(d)))
         nrows = C.c_int(0)
         fin_ab = None
         if gn_part is not None:

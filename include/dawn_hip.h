@@ -105,6 +105,14 @@ int dawn_conv3x3_wino4_ok(int F, int H, int W, int C0, int C1, int N);
 /* Which form of the 3x3 conv dawn_conv_gemm would run for this descriptor (host code, launches nothing; the launch's own decision
  * code): 2 = Winograd F(4x4,3x3), 1 = Winograd F(2x2,3x3), 0 = anything else. */
 int dawn_conv3x3_form(const dawn_conv_desc* d);
+/* Which split-operand kernel dawn_conv_gemm would run a 1x1 projection or a 4x4 / stride-2 resample descriptor on (host code, launches
+ * nothing; the launch's own decision code): */
+#define DAWN_SPLIT1X1_NONE 0      /* none of them: the 3x3 paths or the fp32 kernels */
+#define DAWN_SPLIT1X1_TILED 1     /* gemm1x1_bf16_kernel (256 x 64 / 256 x 128 / 128 x 64 tiles) */
+#define DAWN_SPLIT1X1_ROWREG 2    /* gemm1x1_rowreg_kernel (K = 64 / 128, rows stationary in registers) */
+#define DAWN_SPLIT1X1_ROWACC 3    /* gemm1x1_rowacc_kernel (K >= 256, N <= 192) */
+#define DAWN_SPLIT1X1_RESAMPLE 4  /* gemm1x1_rowacc_kernel in its Downsample (4x4 / stride 2) or Upsample (2x2 phases) mode */
+int dawn_gemm1x1_form(const dawn_conv_desc* d);
 /* upper bound on the thread blocks (= rows of gn_part) dawn_conv_gemm launches for an (M rows, N columns) output;
  * the launch reports the exact count through dawn_conv_desc.gn_rows */
 int dawn_conv_gemm_nblocks(long M, int N);

@@ -37,7 +37,9 @@ class RefOps:
         a = side()
         return a, main()
 
-    def empty(self, *shape, like: Tensor, dtype=torch.float32) -> Tensor:
+    def empty(self, *shape, like: Tensor, dtype=None) -> Tensor:
+        if dtype is None:            # float64 callers (the precision gates) get float64, everything else float32
+            dtype = torch.float64 if like.dtype == torch.float64 else torch.float32
         return torch.zeros(*shape, device=like.device, dtype=dtype)
 
     # ------------------------------------------------------------------ conv / linear
@@ -68,7 +70,7 @@ class RefOps:
         else:
             # 4 phase blocks (py,px) of 2x2 taps -> rebuild the ConvTranspose2d kernel (Cin, N, 4, 4)
             ksel = ((1, 3), (2, 0))
-            wt = torch.zeros(Cin, N, 4, 4, device=x.device)
+            wt = torch.zeros(Cin, N, 4, 4, device=x.device, dtype=x.dtype)
             for ph in range(4):
                 py, px = ph >> 1, ph & 1
                 blk = _unpack(w[ph]).reshape(2, 2, Cin, N)
@@ -110,8 +112,8 @@ class RefOps:
         cnt = float(total_rows) * (C // 8)
         mean = sums[:, 0] / cnt
         var = (sums[:, 1] / cnt - mean * mean).clamp(min=0)
-        rstd = (1.0 / torch.sqrt(var + eps)).float().repeat_interleave(C // 8)
-        mu = mean.float().repeat_interleave(C // 8)
+        rstd = (1.0 / torch.sqrt(var + eps)).to(x.dtype).repeat_interleave(C // 8)
+        mu = mean.to(x.dtype).repeat_interleave(C // 8)
         a = rstd * gamma
         b = beta - mu * a
         if film is not None:
@@ -205,7 +207,7 @@ class RefOps:
     def xattn_tables(self, kvtab, nulltab, q_scale, wo, Co):
         """[D | u_0..u_7 | y0] per (frame, branch), written from the definitions (fp64)."""
         F = kvtab.shape[0]
-        out = torch.zeros(F, 3, 64 + 9 * Co, dtype=torch.float64)
+        out = torch.zeros(F, 3, 64 + 9 * Co, dtype=torch.float64)            # (returned in the dtype of kvtab)
         for b in range(3):
             W = _unpack(wo[b]).double()                                   # (64, Co), k = 8 h + i
             kc, vc = kvtab[:, b, :64].double().view(F, 8, 8), kvtab[:, b, 64:].double().view(F, 8, 8)
@@ -215,7 +217,7 @@ class RefOps:
             y0 = (vn.repeat(8)[:, None] * W).sum(0)
             out[:, b, 64:64 + 8 * Co] = u.reshape(F, 8 * Co)
             out[:, b, 64 + 8 * Co:] = y0[None]
-        return out.float().to(kvtab.device)
+        return out.to(dtype=kvtab.dtype, device=kvtab.device)
 
     def xattn_layer_c64(self, x, x2, HW, wq, wo, g3, q_scale, kvtab, nulltab, eps=1e-5, xtab=None, wq_bf3=None, gn=None, h1_over_c1=False):
         """The ORIGINAL formulation (MT:516-559 op by op); `xtab` (the kernel's per-clip tables) is not used here, so the
@@ -224,7 +226,7 @@ class RefOps:
         stats = self.ln_rowstats(x, x2, eps)
         q = self.conv_gemm(x, wq, 192, in1=x2, row_stats=stats, F=rows, Hi=1, Wi=1)
         self.xattn_core(q, HW, kvtab, nulltab, q_scale)
-        y3 = torch.zeros(rows, 192, device=x.device)
+        y3 = torch.zeros(rows, 192, device=x.device, dtype=x.dtype)
         for b in range(3):
             self.conv_gemm(q[:, 64 * b:64 * b + 64], wo[b], 64, F=rows, Hi=1, Wi=1, out=y3[:, 64 * b:64 * b + 64])
         out = self.xattn_ln_sum(y3, g3, 64, eps)

@@ -1,0 +1,291 @@
+"""The fp32-accuracy gate of the split-bf16 kernels, and the cases it runs on.
+
+Every matrix kernel on the hot path splits its fp32 operands exactly into three bf16 planes and sums six cross terms in fp32, so its error
+against a float64 evaluation of the same op must be that of an fp32 computation.  `fp32_gate` asserts
+
+    rel_err(got) <= C_GATE * rel_err(base32) + FLOOR,      rel_err(t) = max|t - want64| / max|want64|,
+
+where want64 is the RefOps op (oracle/ops_ref.py) evaluated in float64 on CPU and base32 the same op in float32 on CPU (`Case.base32`:
+with torch's im2col + GEMM convolution -- oneDNN's direct convolution sums K almost in sequence and NNPACK transforms in fp32: at
+K >= 1152 their own error of 1..15e-6 is as large as the defects below).  Comparing with CPU fp32 at 1e-4 cannot see a kernel that has
+lost its third weight plane; this gate can, and tests/test_split_gate_cpu.py proves it for every case below: it rejects the two plane
+defects emulated in torch (`drop_third`, `stale_third`) and accepts the fp32 CPU result.  tests/test_hip_fp64_gates.py runs the same
+cases on the GPU kernels.
+
+The split weights are drawn by `coherent` (except where the op normalises them away, see xattn): random magnitudes and signs, with the low bits set so that the third bf16 plane is as large
+as it can be and has the weight's sign.  A lost or stale third plane then moves every output by ~7e-6 of its size, whatever K is --
+with independent random low bits the defect averages out to 2..3e-6, no larger than the GPU kernels' own fp32 accumulation error at
+K >= 512 (measured up to 6x CPU fp32 GEMM's), and no single gate factor could tell them apart.
+
+C_GATE is 2, as for the shipped direct 3x3 gate.  Where the MI355X measurement needs more, the case carries its own `c`, and the
+measured ratio (GPU error / CPU fp32 error, max over the cases of that kernel) is stated beside it.
+
+A case is (name, kind, params).  Shapes are production ones (profiles/r6_insitu_shapes.txt = configs[2],
+profiles/r6_config1_insitu_shapes.txt = configs[1]): H, W and the channel counts, which fix the kernel instantiation and tile geometry, are
+kept; only the number of frames (rows) is reduced.  `split` names the weights the kernel consumes as bf16 planes: the mutants change only
+those."""
+import json
+import os
+import warnings
+
+import torch
+
+from test_hip_ops import LOG      # the op-error log every GPU op test appends to (test_hip_ops.check)
+
+C_GATE = 2.0          # the factor of the whole file; a case widens it only with a measured reason stated beside it
+FLOOR = 1e-7          # relative to max|want64|: ~1 ulp of fp32 at the output's scale
+DEFAULT_POLICY = 0x2B00580D
+TILED_ONLY = DEFAULT_POLICY | 0x20000     # policy bit 0x20000: the tiled split kernel for every 1x1 shape (reaches its nS = 2 corner)
+
+
+# ---------------------------------------------------------------------------------------------- the gate
+def rel_err(t, want64):
+    return float((t.detach().cpu().double() - want64).abs().max() / want64.abs().max())
+
+
+def fp32_gate(name, got, want64, base32, c=C_GATE, floor=FLOOR, log=True):
+    """Assert that `got` is as accurate as CPU fp32 (see the module docstring); append its errors to the op-error log (LOG)."""
+    got = got.detach().cpu().double()
+    diff = got - want64
+    e, e32 = rel_err(got, want64), rel_err(base32, want64)
+    rec = {"op": f"fp64_gate/{name}", "rel_err": e, "rel_err_cpu_fp32": e32, "ratio": e / e32 if e32 > 0 else float("inf"),
+           "max_abs_err": float(diff.abs().max()), "rms_err": float(diff.pow(2).mean().sqrt()), "scale": float(want64.abs().max()),
+           "c": c, "floor": floor, "nan": bool(torch.isnan(got).any())}
+    if log:
+        os.makedirs(os.path.dirname(LOG), exist_ok=True)
+        with open(LOG, "a") as f:
+            f.write(json.dumps(rec) + "\n")
+    assert not rec["nan"], f"{name}: NaN"
+    assert e <= c * e32 + floor, f"{name}: rel err {e:.3e} > {c} x fp32's {e32:.3e} + {floor:.0e} (ratio {rec['ratio']:.2f})"
+    return rec
+
+
+def gate_rejects(got, want64, base32, c=C_GATE, floor=FLOOR):
+    return rel_err(got, want64) > c * rel_err(base32, want64) + floor
+
+
+# ---------------------------------------------------------------------------------------------- the plane defects
+def planes3(w):
+    """The exact split w = w1 + w2 + w3 of dawn_pytorch_amd.pack.pack_bf3, as float32 tensors."""
+    w = w.float()
+    w1 = w.to(torch.bfloat16).float()
+    r1 = w - w1
+    w2 = r1.to(torch.bfloat16).float()
+    return w1, w2, (r1 - w2).to(torch.bfloat16).float()
+
+
+def drop_third(w):
+    """Every weight truncated to its top two planes (the a1 . b3 term lost)."""
+    w1, w2, _ = planes3(w)
+    return w1.double() + w2.double()
+
+
+def stale_third(w, seed=1234):
+    """The third plane taken from another matrix of the same statistics (a prefetch of the wrong head / stage)."""
+    g = torch.Generator().manual_seed(seed)
+    other = torch.randn(w.shape, generator=g) * float(w.float().std())
+    w1, w2, _ = planes3(w)
+    return w1.double() + w2.double() + planes3(other)[2].double()
+
+
+# ---------------------------------------------------------------------------------------------- inputs
+def rnd(*shape, seed=0, scale=1.0):
+    g = torch.Generator().manual_seed(seed + sum(shape))
+    return torch.randn(*shape, generator=g) * scale
+
+
+def coherent(w):
+    """w with its three bf16 planes pinned: w1 = the bf16 value in the lowest 16th of w's binade, w2 and w3 each just under half an
+    ulp of the plane above, all with w's sign.  Exact in fp32 (24 significant bits), and pack_bf3 splits it back into those planes."""
+    w = w.float()
+    e = torch.floor(torch.log2(w.abs().clamp_min(1e-30)))
+    k = torch.floor((w.abs() / torch.exp2(e) - 1.0) * 16.0)                # 0..15
+    m = torch.exp2(e) * (1.0 + k / 128.0) + torch.exp2(e - 9) * 1.96875 + torch.exp2(e - 18) * 1.96875
+    return torch.where(w == 0, w, torch.sign(w) * m)
+
+
+def packd(w_kn):
+    """(K, N) -> [K/4][N][4] in the dtype of w_kn (pack_kn, without its cast to fp32)."""
+    K, N = w_kn.shape
+    return w_kn.reshape(K // 4, 4, N).permute(0, 2, 1).contiguous()
+
+
+def spread(x):
+    """The existing 3x3 gates' data: a few entries x1e4 and x1e-6 -- the split must stay exact across 10 decades."""
+    x = x.clone()
+    x[::7, ::5] *= 1.0e4
+    x[::11, ::3] *= 1.0e-6
+    return x
+
+
+def rope(F):
+    ang = torch.arange(F).float()[:, None] * (1.0 / (10000 ** (torch.arange(0, 32, 2).float() / 32)))[None]
+    return ang.cos().contiguous(), ang.sin().contiguous()
+
+
+class Case:
+    def __init__(self, name, kind, split=("w",), form=None, c=C_GATE, **p):
+        self.name, self.kind, self.split, self.form, self.c, self.p = name, kind, tuple(split), form, c, p
+
+    def __repr__(self):
+        return self.name
+
+    def with_frames(self, F):
+        """The same case on fewer frames (the CPU discrimination test: H, W and channels stay)."""
+        p = dict(self.p)
+        if self.kind == "gemm":
+            p["M"] = min(p["M"], F * 256)
+        elif "F" in p:
+            p["F"] = min(p["F"], F)
+        return Case(self.name, self.kind, self.split, self.form, self.c, **p)
+
+    # inputs: T = fp32 tensors / ints the op takes, Wkn = the fp32 weights in (K, N) form (the images the kernel splits)
+    def make(self):
+        p, k = self.p, self.kind
+        if k == "gemm":
+            M, C0, C1, N = p["M"], p["C0"], p.get("C1", 0), p["N"]
+            x0 = rnd(M, C0, seed=1) * (1.7 if p.get("ln") else 1.0) + (0.4 if p.get("ln") else 0.0)
+            T = dict(x0=x0, x1=rnd(M, C1, seed=5) if C1 else None, res=rnd(M, N, seed=3) if p.get("res") else None,
+                     bias=rnd(N, seed=4) if p.get("bias") else None)
+            return T, dict(w=coherent(rnd(C0 + C1, N, seed=2, scale=(C0 + C1) ** -0.5)))
+        if k in ("down", "up"):
+            from dawn_pytorch_amd.pack import conv_w_kn, deconv_w_kn_phases
+            F, H, C, N = p["F"], p["H"], p["C"], p["N"]
+            T = dict(x=rnd(F * H * H, C, seed=2), bias=rnd(N, seed=3))
+            if k == "down":
+                return T, dict(w=coherent(conv_w_kn(rnd(N, C, 1, 4, 4, seed=1, scale=(C * 16) ** -0.5))))
+            return T, dict(w=coherent(deconv_w_kn_phases(rnd(C, N, 1, 4, 4, seed=4, scale=(C * 4) ** -0.5))))
+        if k == "conv3":
+            F, H, C0, C1, N = p["F"], p["H"], p["C0"], p.get("C1", 0), p["N"]
+            x0, x1 = rnd(F * H * H, C0, seed=1), (rnd(F * H * H, C1, seed=6) if C1 else None)
+            if p.get("spread"):
+                x0, x1 = spread(x0), (spread(x1) if C1 else None)
+            return dict(x0=x0, x1=x1), dict(w=coherent(rnd(9 * (C0 + C1), N, seed=2, scale=(9 * (C0 + C1)) ** -0.5)))
+        if k in ("temporal", "temporal_seg"):
+            Fext, HW, win = p["F"], p["HW"], 40
+            rc, rs = rope(Fext)
+            T = dict(x=rnd(Fext * HW, 64, seed=1) * 1.3 + 0.2, rc=rc, rs=rs, band=rnd(2 * win + 1, 8, seed=4))
+            return T, dict(wqkv=coherent(rnd(64, 768, seed=2, scale=64 ** -0.5)), wout=coherent(rnd(256, 64, seed=3, scale=256 ** -0.5)))
+        if k == "sla":
+            F, HW = p["F"], p["HW"]
+            return (dict(x=rnd(F * HW, 64, seed=1) * 1.3 + 0.2, bias=rnd(64, seed=4)),
+                    # (the attention branch x8 against the residual: at x1 a lost plane is diluted below the gate's floor)
+                    dict(wqkv=coherent(rnd(64, 768, seed=2, scale=2.0 * 64 ** -0.5)), wout=rnd(256, 64, seed=3, scale=8.0 * 256 ** -0.5)))
+        if k == "xattn":
+            from oracle.ops_ref import RefOps
+            F, HW, C0, C1 = p["F"], p["HW"], p["C0"], p.get("C1", 0)
+            kvtab, nulltab = torch.zeros(F, 3, 128), torch.zeros(3, 16)
+            for b in range(3):
+                RefOps().xattn_prep(rnd(F, 128, seed=20 + b), rnd(8, seed=30 + b) * 0.2 + 1, rnd(2, 8, seed=40 + b), kvtab, b, nulltab)
+            T = dict(x=rnd(F * HW, C0, seed=1) * 1.5 + 0.3, x2=rnd(F * HW, C1, seed=2) if C1 else None, g3=rnd(3, 64, seed=4) * 0.2 + 1,
+                     qs=rnd(3, 8, seed=5) * 0.2 + 1, kvtab=kvtab, nulltab=nulltab)
+            # (not `coherent`: q is L2-normalised per head, so a defect that shrinks every weight alike cancels there)
+            Wkn = dict(wq=rnd(C0 + C1, 192, seed=3, scale=(C0 + C1) ** -0.5))
+            Wkn.update({f"wo{b}": rnd(64, 64, seed=10 + b, scale=0.125) for b in range(3)})
+            return T, Wkn
+        raise ValueError(k)
+
+    def ref(self, ops, T, Wkn, dtype):
+        """The RefOps op of this case, every floating tensor cast to dtype (float64: want64; float32: base32)."""
+        T = {k_: (v.to(dtype) if torch.is_tensor(v) else v) for k_, v in T.items()}
+        W = {k_: v.to(dtype) for k_, v in Wkn.items()}
+        p, k = self.p, self.kind
+        if k == "gemm":
+            M = p["M"]
+            return ops.conv_gemm(T["x0"], packd(W["w"]), p["N"], in1=T["x1"], F=M // 256, Hi=16, Wi=16, res=T["res"], bias=T["bias"],
+                                 ln_eps=1e-5 if p.get("ln") else 0.0)
+        if k == "down":
+            H = p["H"]
+            return ops.conv_gemm(T["x"], packd(W["w"]), p["N"], F=p["F"], Hi=H, Wi=H, Ho=H // 2, Wo=H // 2, KH=4, KW=4, stride=2, pad=1,
+                                 bias=T["bias"])
+        if k == "up":
+            H = p["H"]
+            return ops.conv_gemm(T["x"], torch.stack([packd(W["w"][i]) for i in range(4)], 0), p["N"], F=p["F"], Hi=H, Wi=H, Ho=2 * H,
+                                 Wo=2 * H, KH=2, KW=2, mode=1, bias=T["bias"])
+        if k == "conv3":
+            H = p["H"]
+            return ops.conv_gemm(T["x0"], packd(W["w"]), p["N"], in1=T["x1"], F=p["F"], Hi=H, Wi=H, KH=3, KW=3, pad=1)
+        if k in ("temporal", "temporal_seg"):
+            q0, Fq = p.get("q0", 0), p.get("Fq", p["F"])
+            fn = ops.temporal_layer_c64_segmented if k == "temporal_seg" else ops.temporal_layer_c64   # (segments rotate with their own positions)
+            return fn(T["x"], p["F"], p["HW"], q0, Fq, 40, packd(W["wqkv"]), packd(W["wout"]), T["rc"], T["rs"],
+                                          T["band"])
+        if k == "sla":
+            return ops.sla_layer_c64(T["x"], p["F"], p["HW"], packd(W["wqkv"]), packd(W["wout"]), T["bias"])
+        if k == "xattn":
+            return ops.xattn_layer_c64(T["x"], T["x2"], p["HW"], packd(W["wq"]), [packd(W[f"wo{b}"]) for b in range(3)], T["g3"], T["qs"],
+                                       T["kvtab"], T["nulltab"])
+        raise ValueError(k)
+
+    def base32(self, ops, T, Wkn):
+        """The op in float32 on CPU, convolutions through torch's im2col + GEMM path (oneDNN and NNPACK off)."""
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            with torch.backends.mkldnn.flags(enabled=False), torch.backends.nnpack.flags(enabled=False):
+                return self.ref(ops, T, Wkn, torch.float32)
+
+    def mutant(self, Wkn, defect):
+        """Wkn with `defect` (drop_third / stale_third) applied to every weight the kernel splits (float64)."""
+        return {k_: (defect(v) if k_ in self.split else v.double()) for k_, v in Wkn.items()}
+
+
+TILED, ROWREG, ROWACC, RESAMPLE = 1, 2, 3, 4          # dawn_gemm1x1_form
+DIRECT, WINO, WINO4 = 0, 1, 2                         # dawn_conv3x3_form
+
+# Gate factors widened past C_GATE, per kernel: the GPU error / CPU fp32 error measured on an MI355X (max over that kernel's cases).
+# Each kernel accumulates K in fp32 on the matrix pipe, one chain of 6 K / 16 MFMA additions per output (CPU GEMM blocks its sums):
+C_TILED = 5.0         # gemm1x1_bf16_kernel: 3.7 (K = 512 / 256 with independent random weights; 2.0 with `coherent` ones)
+C_ROWREG = 3.0        # gemm1x1_rowreg_kernel: 2.0
+C_ROWACC = 4.0        # gemm1x1_rowacc_kernel: 2.8
+C_ROWACC_LN = 8.0     # ... with the LayerNorm inside: 6.2 -- its statistics sweep takes the variance in one pass (s2 / K - mean^2, fp32) over
+                      # K = 512 channels of mean 0.4, std 1.7, where the CPU reference subtracts the mean first
+C_RESAMPLE = 9.0      # gemm1x1_rowacc_kernel, Downsample / Upsample modes: 7.0 (Downsample, K = 4096), 4.6 (Upsample, K = 1024)
+C_WINO4 = 8.5         # conv3x3_wino4_kernel: 7.8 (32 x 32, 128 channels; the F(4x4) transform adds values of different magnitude in fp32; the shipped gate
+                      # against the GPU's own fp32-MFMA kernel allows 5x).  The narrowest case of the file: its own error is a third of the
+                      # largest defect a weight pattern can make (2^-17), so c must sit between 7.8 and ~9 (test_split_gate_cpu)
+C_WINO = 5.5          # conv3x3_wino_kernel: 4.2 (the shipped gate against the GPU's direct split kernel allows 3x)
+C_DIRECT_DEEP = 11.0  # conv3x3_bf16_v2_kernel on 4 x 4-pixel frames, K = 4608 / 9216: 9.2 -- one chain over all 9 Cin products of an
+                      # output, where the Winograd forms at the same channel counts sum over Cin only (3.5 there)
+
+# deepest-level channel counts (512 -> 512 at 8 x 8 and 4 x 4, 512 + 512 -> 256) put K at 4608 / 9216
+CASES = [
+    # 1x1 family (M = rows; 256 rows = one 16 x 16 frame)
+    Case("gemm1x1/tiled_M12800_N768_K512_res", "gemm", form=TILED, c=C_TILED, M=12800, C0=512, N=768, res=True),
+    Case("gemm1x1/tiled_M51200_N768_K256", "gemm", form=TILED, c=C_TILED, M=51200, C0=256, N=768),
+    Case("gemm1x1/tiled_nS1_M12800_N128_K32", "gemm", form=TILED, c=C_TILED, M=12800, C0=32, N=128, bias=True),
+    Case("gemm1x1/tiled_nS2_M12800_N128_K64", "gemm", form=TILED, c=C_TILED, policy=TILED_ONLY, M=12800, C0=64, N=128),
+    Case("gemm1x1/tiled_nS3_M12800_N128_K96", "gemm", form=TILED, c=C_TILED, M=12800, C0=96, N=128, res=True),
+    # nine stages, the source switch after stage 5 (test_hip_ops.test_gemm1x1_split_variants' M = 25600 form of it runs on the fp32 kernel)
+    Case("gemm1x1/tiled_nS9_M12800_N256_K160+128", "gemm", form=TILED, c=C_TILED, M=12800, C0=160, C1=128, N=256, res=True),
+    Case("gemm1x1/rowreg_M51200_N64_K128", "gemm", form=ROWREG, c=C_ROWREG, M=51200, C0=128, N=64),
+    Case("gemm1x1/rowreg_M51200_N768_K128_ln", "gemm", form=ROWREG, c=C_ROWREG, M=51200, C0=128, N=768, ln=True),
+    Case("gemm1x1/rowacc_M51200_N128_K256", "gemm", form=ROWACC, c=C_ROWACC, M=51200, C0=256, N=128),
+    Case("gemm1x1/rowacc_M12800_N192_K512_ln", "gemm", form=ROWACC, c=C_ROWACC_LN, M=12800, C0=512, N=192, ln=True),
+    # resample forms of the row-accumulator kernel at configs[2]'s three level pairs (M >= 12800 output / input rows)
+    Case("resample/down_64x64_C64", "down", form=RESAMPLE, c=C_RESAMPLE, F=13, H=64, C=64, N=64),
+    Case("resample/down_32x32_C128", "down", form=RESAMPLE, c=C_RESAMPLE, F=50, H=32, C=128, N=128),
+    Case("resample/down_16x16_C256", "down", form=RESAMPLE, c=C_RESAMPLE, F=200, H=16, C=256, N=256),
+    Case("resample/up_8x8_C256", "up", form=RESAMPLE, c=C_RESAMPLE, F=200, H=8, C=256, N=256),
+    Case("resample/up_16x16_C128", "up", form=RESAMPLE, c=C_RESAMPLE, F=50, H=16, C=128, N=128),
+    Case("resample/up_32x32_C64", "up", form=RESAMPLE, c=C_RESAMPLE, F=13, H=32, C=64, N=64),
+    # 3x3 family at production geometry, N(0,1) data and data spread over 10 decades
+    *[Case(f"conv3x3/{nm}_{'spread' if s else 'n01'}", "conv3", form=fm, c=cg, spread=s, **kw) for s in (False, True) for nm, fm, cg, kw in (
+        ("wino4_64x64_C64_N64", WINO4, C_WINO4, dict(F=2, H=64, C0=64, N=64)),
+        ("wino4_32x32_C128_N128", WINO4, C_WINO4, dict(F=4, H=32, C0=128, N=128)),
+        ("wino_64x64_C64+64_N64", WINO, C_WINO, dict(F=2, H=64, C0=64, C1=64, N=64)),
+        ("wino_16x16_C512_N128", WINO, C_WINO, dict(F=8, H=16, C0=512, N=128)),
+        ("wino_8x8_C512_N512", WINO, C_WINO, dict(F=8, H=8, C0=512, N=512)),
+        ("wino_8x8_C512+512_N256", WINO, C_WINO, dict(F=8, H=8, C0=512, C1=512, N=256)),
+        ("direct_4x4_C512_N512", DIRECT, C_DIRECT_DEEP, dict(F=32, H=4, C0=512, N=512)),
+        ("direct_4x4_C512+512_N256", DIRECT, C_DIRECT_DEEP, dict(F=32, H=4, C0=512, C1=512, N=256)))],
+    # attention layers
+    Case("temporal/F200_q0_w40", "temporal", split=("wqkv", "wout"), F=200, HW=16),
+    Case("temporal/shard_F280_q40_Fq200", "temporal", split=("wqkv", "wout"), F=280, HW=16, q0=40, Fq=200),
+    Case("temporal/segmented_F400", "temporal_seg", split=("wqkv", "wout"), F=400, HW=8),
+    Case("sla/F8_HW256", "sla", split=("wqkv",), F=8, HW=256),
+    Case("sla/F9_HW2080", "sla", split=("wqkv",), F=9, HW=2080),
+    Case("xattn/C64_HW64", "xattn", split=("wq",), F=3, HW=64, C0=64),
+    Case("xattn/C64+64_HW64", "xattn", split=("wq",), F=3, HW=64, C0=64, C1=64),
+    Case("xattn/C64_HW4096", "xattn", split=("wq",), F=1, HW=4096, C0=64),
+    Case("xattn/C64+64_HW4096", "xattn", split=("wq",), F=1, HW=4096, C0=64, C1=64),
+]
