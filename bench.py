@@ -13,10 +13,15 @@ an `n_gpus: 1` line for `--gpus 8`:
   --mode tshard  (default): ONE clip of 200*N frames sharded along T, RCCL halo exchange + tiny
                  GroupNorm / quantile all-reduces (BASELINE configs[3] shape per GPU) -- weak scaling;
   --mode replica: N independent 200-frame clips, no collective (configs[4]) -- weak scaling.
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel = the
-split-operand 3x3 conv on the bf16 matrix pipe, timed live with HIP events on the launch stream; both the executed-pipe
-and the algorithmic fraction are stated), `max_clip_frames` (the second half of BASELINE's metric: bytes/frame fitted
-from two probe lengths against the HBM size) and `cpu_baseline` (the CPU oracle on the host cores, bounded sample)."""
+Prints ONE JSON line on rank 0 with `roofline` (dominant kernel = the split-operand 3x3 conv on the bf16 matrix pipe, timed live
+with HIP events on the launch stream during the timed steps; both the executed-pipe and the algorithmic fraction are stated).
+
+A plain run does only what that line needs: it sets up, warms up, times the steps, writes --dump-outputs and prints the line.
+`--full` adds, after the timed steps, every report that takes runs of its own: `roofline.power_ceiling` (an MFMA-only loop),
+`flow_decode`, `shard_sim`, `other_configs` (the other single-GPU workloads of BASELINE), `max_clip_frames` (the second half of
+BASELINE's metric: bytes/frame fitted from two probe lengths against the HBM size), `cpu_baseline` (the CPU oracle on the host
+cores, bounded sample) and, T-sharded, the per-rank halo and all-reduce waits of one more clip (`comm.per_rank`).
+--no-cpu-baseline, --no-max-clip, --no-decode, --no-shard-sim and --no-other-configs leave single reports of a --full run out."""
 import argparse
 import json
 import os
@@ -416,6 +421,10 @@ def main():
     ap.add_argument("--res", type=int, default=256)
     ap.add_argument("--ddim-steps", type=int, default=50)
     ap.add_argument("--mode", choices=["tshard", "replica"], default="tshard")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every report beside the headline figure (power ceiling, flow decode, "
+                         "shard_sim, other_configs, max_clip_frames, cpu_baseline, T-shard waits); without it the run ends after "
+                         "the timed steps, --dump-outputs and the result line")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample-frames", type=int, default=0,
                     help="frames of the CPU oracle's timed evaluation (0 = the benchmark's own clip length: SURVEY 8d D4)")
@@ -588,7 +597,7 @@ def main():
     per_rank = None
     if dist is not None:
         waits = {}
-        if comm is not None:
+        if comm is not None and args.full:
             # OUTSIDE the timed region: one more clip with HIP events around every halo_end and every all-reduce -- how long this
             # rank's compute stream waited for the neighbours' frames (0 when the transfer hid behind the producer) and what the
             # dependent all-reduces cost it, so that the first SCALE line explains itself
@@ -785,14 +794,15 @@ def main():
                 "note": "not a dawn_conv_gemm launch: listed beside the conv / GEMM classes with its own launch times; counters: profiles/r6_pmc_temporal_layer.md"})
         # the split kernels are POWER-limited (same instruction stream, zero-filled tensors: 28-38 % faster; profiles/
         # r3_conv_power_by_data.txt): price the dominant kernel against what an MFMA-only loop sustains on THIS box right now
-        try:
-            pc = power_ceiling(ops, device)
-            result["roofline"]["power_ceiling"] = pc
-            for r in [result["roofline"]] + result.get("roofline_other", []):
-                if r.get("frac_is") == "frac_executed":
-                    r["frac_of_power_ceiling"] = r["achieved"] / pc["mfma_lds_tflops"]
-        except Exception as e:                                # noqa: BLE001  (a report, never the metric)
-            result["roofline"]["power_ceiling"] = {"error": f"{type(e).__name__}: {str(e)[:200]}"}
+        if args.full:
+            try:
+                pc = power_ceiling(ops, device)
+                result["roofline"]["power_ceiling"] = pc
+                for r in [result["roofline"]] + result.get("roofline_other", []):
+                    if r.get("frac_is") == "frac_executed":
+                        r["frac_of_power_ceiling"] = r["achieved"] / pc["mfma_lds_tflops"]
+            except Exception as e:                            # noqa: BLE001  (a report, never the metric)
+                result["roofline"]["power_ceiling"] = {"error": f"{type(e).__name__}: {str(e)[:200]}"}
     elif diff.use_ctx:
         result["roofline"] = {"skipped": "--host ctx: per-launch HIP events are recorded by the Python host only (run without --host ctx, "
                                           "or read dawn_ctx_profile_read under DAWN_OPT_PROFILE)"}
@@ -803,7 +813,8 @@ def main():
     result["config"]["host"] = ("C-side evaluator (dawn_sampler_run)" if diff.use_ctx else "Python orchestration (ctypes launches)")
     result["config"]["launch"] = ("HIP graph replay per DDIM step" if diff.use_graph and getattr(ops, "graph_error", None) is None
                                   else "eager" + (f" (graph capture failed: {ops.graph_error})" if getattr(ops, "graph_error", None) else ""))
-    if n_gpus == 1 and not args.no_decode:
+    result["config"]["full"] = args.full
+    if args.full and n_gpus == 1 and not args.no_decode:
         # "report sample_one_video-inclusive separately".  OUTSIDE the timed region: the sampled clip
         # (grid = pred[:, :2], conf = (pred[:, 2] + 1) / 2, FD:365-366) goes through the HIP flow decode (SURVEY 8f N1,
         # FlowDecoder.decode_clip == the reference's per-frame loop FD:372-385) with a random-init LFG generator of the
@@ -828,15 +839,15 @@ def main():
         result["flow_decode"] = {"what": "LFG forward_with_flow for the whole clip (FlowDecoder.decode_clip), outside the timed region",
                                  "ms_per_clip": td * 1e3, "frames_per_s": T / td, "algorithmic_tflops": dfl / td / 1e12,
                                  "sampler_plus_decode_frames_per_s": T / (dt / args.steps + td)}
-    if n_gpus == 1 and mode == "single" and not args.no_shard_sim and not diff.use_ctx:
+    if args.full and n_gpus == 1 and mode == "single" and not args.no_shard_sim and not diff.use_ctx:
         try:
             result["shard_sim"] = shard_sim(unet, diff, T, h, device, clip_ms[len(clip_ms) // 2], rccl=not args.no_shard_sim_rccl)
         except Exception as e:                                # noqa: BLE001  (a report, never the metric)
             result["shard_sim"] = {"error": f"{type(e).__name__}: {str(e)[:200]}"}
-    if n_gpus == 1 and mode == "single" and not args.no_other_configs and (args.res, T, S) == (256, 200, 50):
+    if args.full and n_gpus == 1 and mode == "single" and not args.no_other_configs and (args.res, T, S) == (256, 200, 50):
         result["other_configs"] = other_configs(unet, device, S)
         unet.update_num_frames(T)
-    if not args.no_max_clip:
+    if args.full and not args.no_max_clip:
         try:
             result["max_clip_frames"] = max_clip_frames(unet, diff, h, device, n_gpus)
         except Exception as e:                                # noqa: BLE001  (a report, never the metric)
@@ -848,7 +859,7 @@ def main():
                           **(comm.stats() if comm is not None else {"halo_exchanges": 0, "all_reduces": 0,
                                                                    "note": "replica mode: no data-path collective"}),
                           "per_rank": per_rank}
-    if not args.no_cpu_baseline and n_gpus == 1:
+    if args.full and not args.no_cpu_baseline and n_gpus == 1:
         sd = {"denoise_fn." + k: v.detach().cpu() for k, v in unet.state_dict().items()}
         result["cpu_baseline"] = cpu_baseline(h, S, args.cpu_sample_frames or T, sd)
     if dist is not None:
