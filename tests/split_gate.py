@@ -12,6 +12,11 @@ lost its third weight plane; this gate can, and tests/test_split_gate_cpu.py pro
 defects emulated in torch (`drop_third`, `stale_third`) and accepts the fp32 CPU result.  tests/test_hip_fp64_gates.py runs the same
 cases on the GPU kernels.
 
+The attention kernels also split ACTIVATIONS in the kernel (ACT_OPERANDS: X, Q, K, V, P, O): the hooked float64 references below
+(`attn_core64`, `temporal_layer64`) apply a defect to one such operand where the kernels split it, and the CPU test shows that the gate
+rejects each operand's third plane dropped (`drop_third_act`) or read from the previous head (`stale_third_act`).  The fp32 attention
+kernels (temporal_attn_kernel, SLA, frame attention, the unfused cross-attention chain) are held to the same gate.
+
 The split weights are drawn by `coherent` (except where the op normalises them away, see xattn): random magnitudes and signs, with the low bits set so that the third bf16 plane is as large
 as it can be and has the weight's sign.  A lost or stale third plane then moves every output by ~7e-6 of its size, whatever K is --
 with independent random low bits the defect averages out to 2..3e-6, no larger than the GPU kernels' own fp32 accumulation error at
@@ -25,6 +30,7 @@ profiles/r6_config1_insitu_shapes.txt = configs[1]): H, W and the channel counts
 kept; only the number of frames (rows) is reduced.  `split` names the weights the kernel consumes as bf16 planes: the mutants change only
 those."""
 import json
+import math
 import os
 import warnings
 
@@ -88,6 +94,116 @@ def stale_third(w, seed=1234):
     return w1.double() + w2.double() + planes3(other)[2].double()
 
 
+def trunc_planes3(x):
+    """The exact split of dawn_split3_oct (csrc/dawn_common.h), the in-kernel split of every activation operand but X: p1 = the top 16
+    bits of x, p2 = the top 16 bits of x - p1, p3 = the top 16 bits of what is left (all fp32 subtractions, exact).  Float32 tensors."""
+    hi = lambda t: (t.contiguous().view(torch.int32) & -65536).view(torch.float32)
+    x = x.float()
+    p1 = hi(x)
+    r = x - p1
+    p2 = hi(r)
+    return p1, p2, hi(r - p2)
+
+
+def drop_third_act(t, split, axis):
+    """The operand t (float64) as the kernel would use it with the third plane of its fp32 value lost (the a3 terms dropped)."""
+    return t - split(t.float())[2].double()
+
+
+def stale_third_act(t, split, axis):
+    """... with the third plane read from the neighbour along `axis`: the same operand of the previous head (the K / V planes are
+    rewritten by every head behind one barrier: a race on it reads the previous head's), for X the previous frame row."""
+    p3 = split(t.float())[2].double()
+    return t - p3 + p3.roll(1, dims=axis)
+
+
+ACT_DEFECTS = (drop_third_act, stale_third_act)
+
+
+# ---------------------------------------------------------------------------------------------- hooked fp64 references
+# RefOps.temporal_attn and RefOps.temporal_layer_c64 (oracle/ops_ref.py) in float64, with a hook on every operand the kernels split in
+# the kernel: `defect = {operand: fn}`, fn(t, split, axis) as drop_third_act.  Each hook sits where the kernels split that operand.
+# Without hooks these are the RefOps ops (test_split_gate_cpu.test_hooked_reference_is_the_oracle).
+LOG2E = math.log2(math.e)
+
+
+def _hook(defect, name, t, split, axis):
+    fn = (defect or {}).get(name)
+    return t if fn is None else fn(t, split, axis)
+
+
+def attn_core64(qkv, Fext, HW, q0, Fq, win, rcos, rsin, band, defect=None):
+    """RefOps.temporal_attn in float64 with hooks on Q, K, V and P (all split by dawn_split3_oct / split3_quad: trunc_planes3)."""
+    x = qkv.double().reshape(Fext, HW, 3, 8, 32)
+    rcos, rsin, band = rcos.double(), rsin.double(), band.double()
+    q = x[:, :, 0].permute(1, 2, 0, 3) * 32 ** -0.5          # (HW, 8, Fext, 32): axis 1 = head
+    k = x[:, :, 1].permute(1, 2, 0, 3)
+    v = x[:, :, 2].permute(1, 2, 0, 3)
+
+    def rot(t):
+        c, s = rcos[:Fext], rsin[:Fext]
+        t1, t2 = t[..., 0::2], t[..., 1::2]
+        return torch.stack((t1 * c - t2 * s, t2 * c + t1 * s), dim=-1).flatten(-2)
+
+    q, k = rot(q)[:, :, q0:q0 + Fq], rot(k)
+    # Q: after the rotary, scaled by 32^-0.5 * log2(e) (the kernels' softmax runs in log2 units) -- temporal_layer.hip:1003 (EXT core and
+    # fused layer), temporal_layer16.hip:428 / :823 (fused 16 / 13-wave layers), :1150 (13-wave core)
+    if defect and "Q" in defect:
+        q = _hook(defect, "Q", q * LOG2E, trunc_planes3, 1) / LOG2E
+    # K: after the rotary, unscaled -- temporal_layer.hip:776 (EXT), :864 / :926 (fused); temporal_layer16.hip:339 / :860 / :1170
+    k = _hook(defect, "K", k, trunc_planes3, 1)
+    # V: as projected (loaded) -- temporal_layer.hip:794 (EXT), :889 / :948 (fused); temporal_layer16.hip:355 / :870 / :1157
+    v = _hook(defect, "V", v, trunc_planes3, 1)
+    i = torch.arange(q0, q0 + Fq)
+    j = torch.arange(Fext)
+    rel = j[None, :] - i[:, None]
+    inside = rel.abs() <= win
+    bias = band[(rel.clamp(-win, win) + win)].permute(2, 0, 1)           # (8, Fq, Fext)
+    sim = torch.einsum("nhid,nhjd->nhij", q, k) + bias[None]
+    sim = sim.masked_fill(~inside[None, None], float("-inf"))
+    if defect and "P" in defect:
+        # P: split BEFORE the normalisation, which divides P.V by the sum of the unsplit P -- temporal_layer.hip:1079, temporal_layer16.hip:559
+        # / :975 / :1279.  The 32 x 32 kernels (temporal_layer.hip) take 2^(s - m) against a running max (half A, then both halves, with
+        # alpha rescaling the half-A sum, :1155-1163); here exp(s - row max), which has the defect's size and sign, not the kernel's bits
+        e = torch.exp(sim - sim.amax(-1, keepdim=True))
+        o = torch.einsum("nhij,nhjd->nhid", _hook(defect, "P", e, trunc_planes3, 1), v) / e.sum(-1, keepdim=True)
+    else:
+        o = torch.einsum("nhij,nhjd->nhid", sim.softmax(dim=-1), v)      # (HW, 8, Fq, 32)
+    return o.permute(2, 0, 1, 3).reshape(Fq * HW, 256).contiguous()
+
+
+def temporal_layer64(x, Fext, HW, q0, Fq, win, wqkv, wout, rcos, rsin, band, eps=1e-5, defect=None):
+    """RefOps.temporal_layer_c64 in float64 with hooks on X, Q, K, V, P and O (packed weights as RefOps takes them)."""
+    from oracle.ops_ref import RefOps
+    ops = RefOps()
+    x = x.double()
+    stats = ops.ln_rowstats(x, None, eps)
+    if defect and "X" in defect:
+        # X: the LayerNorm'ed rows, split by ROUNDING (split3_quad_t's bf16 conversions: planes3, not dawn_split3_oct) --
+        # temporal_layer.hip:684, temporal_layer16.hip:200-208 / :711-719; stale = the third plane of the previous frame row
+        xn = ((x - stats[0][:, None]) * stats[1][:, None]).view(Fext, HW, 64)
+        xn = _hook(defect, "X", xn, planes3, 0).view(Fext * HW, 64)
+        qkv = ops.conv_gemm(xn, wqkv.double(), 768, F=Fext, Hi=1, Wi=HW)
+    else:
+        qkv = ops.conv_gemm(x, wqkv.double(), 768, row_stats=stats, F=Fext, Hi=1, Wi=HW)
+    o = attn_core64(qkv, Fext, HW, q0, Fq, win, rcos, rsin, band, defect)
+    # O: after the 1 / l normalisation, before the out-projection -- temporal_layer.hip:1185, temporal_layer16.hip:613 / :1001
+    o = _hook(defect, "O", o.view(Fq * HW, 8, 32), trunc_planes3, 1).reshape(Fq * HW, 256)
+    return ops.conv_gemm(o, wout.double(), 64, res=x[q0 * HW:(q0 + Fq) * HW], F=Fq, Hi=1, Wi=HW)
+
+
+def temporal_layer64_segmented(x, Fext, HW, q0, Fq, win, wqkv, wout, rcos, rsin, band, eps=1e-5, defect=None):
+    """RefOps.temporal_layer_c64_segmented (its 120-query segments) over temporal_layer64."""
+    from oracle.ops_ref import RefOps
+    out = torch.empty(Fq * HW, 64, dtype=torch.float64)
+    for a in range(q0, q0 + Fq, RefOps.SEG_QUERIES):
+        b = min(a + RefOps.SEG_QUERIES, q0 + Fq)
+        r0, r1 = max(0, a - win), min(Fext, b + win)
+        out[(a - q0) * HW:(b - q0) * HW] = temporal_layer64(x[r0 * HW:r1 * HW], r1 - r0, HW, a - r0, b - a, win, wqkv, wout, rcos, rsin,
+                                                            band, eps, defect)
+    return out
+
+
 # ---------------------------------------------------------------------------------------------- inputs
 def rnd(*shape, seed=0, scale=1.0):
     g = torch.Generator().manual_seed(seed + sum(shape))
@@ -118,6 +234,17 @@ def spread(x):
     return x
 
 
+def by_pixels(fn, qkv, F, HW, Fo, chunk=16):
+    """fn(qkv of `chunk` pixel columns, chunk) -> (Fo * chunk, 256), over all HW columns of a (F * HW, 768) qkv tensor: the temporal
+    attention of a column sees only that column, and a float64 score tensor of every column at once would take gigabytes."""
+    out = torch.empty(Fo, HW, 256, dtype=qkv.dtype)
+    x = qkv.view(F, HW, 768)
+    for a in range(0, HW, chunk):
+        b = min(a + chunk, HW)
+        out[:, a:b] = fn(x[:, a:b].reshape(F * (b - a), 768), b - a).view(Fo, b - a, 256)
+    return out.view(Fo * HW, 256)
+
+
 def rope(F):
     ang = torch.arange(F).float()[:, None] * (1.0 / (10000 ** (torch.arange(0, 32, 2).float() / 32)))[None]
     return ang.cos().contiguous(), ang.sin().contiguous()
@@ -135,6 +262,8 @@ class Case:
         p = dict(self.p)
         if self.kind == "gemm":
             p["M"] = min(p["M"], F * 256)
+        elif self.kind == "tattn":
+            p["HW"] = min(p["HW"], F)            # (tattn keeps its frames: F is the number of pixel columns here)
         elif "F" in p:
             p["F"] = min(p["F"], F)
         return Case(self.name, self.kind, self.split, self.form, self.c, **p)
@@ -183,6 +312,23 @@ class Case:
             Wkn = dict(wq=rnd(C0 + C1, 192, seed=3, scale=(C0 + C1) ** -0.5))
             Wkn.update({f"wo{b}": rnd(64, 64, seed=10 + b, scale=0.125) for b in range(3)})
             return T, Wkn
+        if k == "tattn":
+            Fext, win = p["F"], 40
+            rc, rs = rope(Fext)
+            # (N(0, 1) qkv, as test_hip_ops.test_temporal_attn: x2 makes the softmax peakier and CPU fp32's own error twice as large, and
+            # halves the gate's margin over a lost P plane)
+            return dict(qkv=rnd(Fext * p["HW"], 768, seed=1), rc=rc, rs=rs, band=rnd(2 * win + 1, 8, seed=4)), {}
+        if k in ("sla_unfused", "frame"):
+            return dict(qkv=rnd(p["F"] * p["HW"], 768, seed=1)), {}
+        if k == "xattn_unfused":
+            from oracle.ops_ref import RefOps
+            F, HW, Co = p["F"], p["HW"], p["Co"]
+            kvtab, nulltab = torch.zeros(F, 3, 128), torch.zeros(3, 16)
+            for b in range(3):
+                RefOps().xattn_prep(rnd(F, 128, seed=20 + b), rnd(8, seed=30 + b) * 0.2 + 1, rnd(2, 8, seed=40 + b), kvtab, b, nulltab)
+            T = dict(q=rnd(F * HW, 192, seed=1), g3=rnd(3, Co, seed=4) * 0.2 + 1, qs=rnd(3, 8, seed=5) * 0.2 + 1, kvtab=kvtab, nulltab=nulltab,
+                     y3=rnd(F * HW, 3 * Co, seed=6) * 0.5 + 0.1)
+            return T, {f"wo{b}": rnd(64, Co, seed=10 + b, scale=0.125) for b in range(3)}
         raise ValueError(k)
 
     def ref(self, ops, T, Wkn, dtype):
@@ -212,10 +358,39 @@ class Case:
                                           T["band"])
         if k == "sla":
             return ops.sla_layer_c64(T["x"], p["F"], p["HW"], packd(W["wqkv"]), packd(W["wout"]), T["bias"])
+        if k == "tattn":
+            Fext, HW, q0 = p["F"], p["HW"], p.get("q0", 0)
+            Fq = p.get("Fq", Fext)
+            return by_pixels(lambda qkv, n: ops.temporal_attn(qkv, Fext, n, q0, Fq, 40, T["rc"], T["rs"], T["band"]), T["qkv"], Fext, HW, Fq)
+        if k == "sla_unfused":
+            return ops.sla(T["qkv"], p["F"], p["HW"])
+        if k == "frame":
+            return ops.frame_attn(T["qkv"], p["F"], p["HW"])
+        if k == "xattn_unfused":
+            HW, Co, form = p["HW"], p["Co"], p["chain"]
+            if form == "ln_sum":
+                return ops.xattn_ln_sum(T["y3"], T["g3"], Co)
+            o = ops.xattn_core(T["q"].clone(), HW, T["kvtab"], T["nulltab"], T["qs"])
+            if form == "core":
+                return o
+            # "sigma": the original chain (core, the three to_out projections, their LayerNorms, the branch sum) that the per-clip tables
+            # of xattn_tables and the one-pass xattn_sigma_out replace
+            y3 = torch.cat([o[:, 64 * b:64 * b + 64] @ W[f"wo{b}"] for b in range(3)], 1)
+            return ops.xattn_ln_sum(y3, T["g3"], Co)
         if k == "xattn":
             return ops.xattn_layer_c64(T["x"], T["x2"], p["HW"], packd(W["wq"]), [packd(W[f"wo{b}"]) for b in range(3)], T["g3"], T["qs"],
                                        T["kvtab"], T["nulltab"])
         raise ValueError(k)
+
+    def ref_hooked(self, T, Wkn, defect=None):
+        """The float64 op of a temporal / temporal_seg / tattn case through the hooked references, `defect` applied."""
+        p, k = self.p, self.kind
+        q0, Fq = p.get("q0", 0), p.get("Fq", p["F"])
+        if k == "tattn":
+            return by_pixels(lambda qkv, n: attn_core64(qkv, p["F"], n, q0, Fq, 40, T["rc"], T["rs"], T["band"], defect), T["qkv"].double(),
+                             p["F"], p["HW"], Fq)
+        fn = temporal_layer64_segmented if k == "temporal_seg" else temporal_layer64
+        return fn(T["x"], p["F"], p["HW"], q0, Fq, 40, packd(Wkn["wqkv"]), packd(Wkn["wout"]), T["rc"], T["rs"], T["band"], defect=defect)
 
     def base32(self, ops, T, Wkn):
         """The op in float32 on CPU, convolutions through torch's im2col + GEMM path (oneDNN and NNPACK off)."""
@@ -244,6 +419,8 @@ C_WINO4 = 8.5         # conv3x3_wino4_kernel: 7.8 (32 x 32, 128 channels; the F(
                       # against the GPU's own fp32-MFMA kernel allows 5x).  The narrowest case of the file: its own error is a third of the
                       # largest defect a weight pattern can make (2^-17), so c must sit between 7.8 and ~9 (test_split_gate_cpu)
 C_WINO = 5.5          # conv3x3_wino_kernel: 4.2 (the shipped gate against the GPU's direct split kernel allows 3x)
+C_SLA_CTX = 3.0       # sla_context_kernel + sla_apply_kernel (fp32, no split operands): 2.46 at HW 1024 (0.94 at 256, 1.07 at 64) -- each context
+                      # row is one fp32 MFMA chain over all HW pixels, its softmax denominator one sequential sum of HW / 2 terms per lane
 C_DIRECT_DEEP = 11.0  # conv3x3_bf16_v2_kernel on 4 x 4-pixel frames, K = 4608 / 9216: 9.2 -- one chain over all 9 Cin products of an
                       # output, where the Winograd forms at the same channel counts sum over Cin only (3.5 there)
 
@@ -288,4 +465,32 @@ CASES = [
     Case("xattn/C64+64_HW64", "xattn", split=("wq",), F=3, HW=64, C0=64, C1=64),
     Case("xattn/C64_HW4096", "xattn", split=("wq",), F=1, HW=4096, C0=64),
     Case("xattn/C64+64_HW4096", "xattn", split=("wq",), F=1, HW=4096, C0=64, C1=64),
+    # the attention core of the unfused levels (HipOps.temporal_attn).  Frames as in production (win 40); the pixel columns shrink only
+    # while the automatic kernel stays the same: the split-operand EXT core (dawn_temporal_attn_bf16_try) from 128 columns, below that
+    # temporal_attn_kernel (fp32 MFMA)
+    Case("tattn/L1_256px_F200", "tattn", split=(), F=200, HW=256),                          # 32 x 32 and 16 x 16 levels at 256 px (FAC = 200)
+    Case("tattn/tshard_F280_q40_Fq200", "tattn", split=(), F=280, HW=128, q0=40, Fq=200),   # T-shard interior rank, long-clip row window (FAC = 0)
+    Case("tattn/delta7_F200_q47_Fq120", "tattn", split=(), F=200, HW=128, q0=47, Fq=120),   # (q0 - win) mod 16 = 7
+    Case("tattn/fp32_256px_F200", "tattn", split=(), F=200, HW=64),                         # 8 x 8 at 256 px: the fp32 kernel
+    Case("tattn/fp32_128px_F200", "tattn", split=(), F=200, HW=16),                         # 4 x 4 at 128 px
+    # the fp32 attention kernels (no split operands): ops.sla at the levels above 64 channels, ops.frame_attn (the mid level), the unfused
+    # cross-attention chain at the channel counts and grids of the two benchmark resolutions
+    Case("sla_unfused/HW1024", "sla_unfused", split=(), c=C_SLA_CTX, F=4, HW=1024),
+    Case("sla_unfused/HW256", "sla_unfused", split=(), c=C_SLA_CTX, F=8, HW=256),
+    Case("sla_unfused/HW64", "sla_unfused", split=(), c=C_SLA_CTX, F=32, HW=64),
+    Case("frame/N64", "frame", split=(), F=50, HW=64),
+    Case("frame/N16", "frame", split=(), F=100, HW=16),
+    *[Case(f"xattn_unfused/{form}_Co{Co}_HW{HW}", "xattn_unfused", split=(), F=F, HW=HW, Co=Co, chain=form)
+      for form in ("sigma", "ln_sum") for Co, HW, F in ((128, 1024, 2), (256, 256, 4), (512, 64, 8))],
+    Case("xattn_unfused/core_HW1024", "xattn_unfused", split=(), F=2, HW=1024, Co=128, chain="core"),
 ]
+
+# the operands each kernel family splits in the kernel (the weights' planes are covered by `split` and Case.mutant)
+ACT_OPERANDS = {"tattn": ("Q", "K", "V", "P"), "temporal": ("X", "Q", "K", "V", "P", "O"), "temporal_seg": ("X", "Q", "K", "V", "P", "O")}
+
+# (case, operand, defect) -> measured defect / CPU fp32 error ratio, for every activation defect that stays at or below the gate's bound
+# (test_split_gate_cpu asserts that exactly these are not rejected).  Empty: the smallest ratios, over the cases and the two defects, are
+# X 5.1 (rounded split: its third plane has either sign, half the truncated one's size), P 10.9, Q 11.8, K 11.9, V 14.4, O 16.0 -- each
+# above C_GATE = 2 with room for the kernels' measured factors
+BELOW_FP32_NOISE = {
+}

@@ -5,8 +5,10 @@ whose loads are placed by hand.
 The gate (split_gate.fp32_gate): max|hip - fp64| / max|fp64| <= C_GATE x the same for the RefOps op in fp32 on CPU + FLOOR.
 tests/test_split_gate_cpu.py shows that every case here rejects a kernel that lost its third weight plane or read a stale one.  C_GATE = 2
 holds for the temporal, SLA and cross-attention kernels; the 1x1, resample and 3x3 kernels carry factors widened to their measured
-ratios (split_gate.C_TILED ... C_DIRECT_DEEP, each with the MI355X measurement beside it).  Each gate appends its errors and its ratio
-to CPU fp32 to the op-error log of test_hip_ops.check (split_gate.LOG)."""
+ratios (split_gate.C_TILED ... C_DIRECT_DEEP, each with the MI355X measurement beside it).  The same gate holds the attention cores of the
+unfused levels (HipOps.temporal_attn: the split-operand EXT core, the fp32 kernel, the 13-wave core) and the fp32 attention kernels (SLA,
+frame attention, the unfused cross-attention chain).  Each gate appends its errors and its ratio to CPU fp32 to the op-error log of
+test_hip_ops.check (split_gate.LOG)."""
 import pytest
 import torch
 
@@ -155,6 +157,75 @@ def test_attention_layer_fp64_gate(hip, case):
     G.fp32_gate(case.name, got, want64, base32, c=case.c)
 
 
+# ---------------------------------------------------------------------------------------------- attention cores of the unfused levels
+# temporal_attn_flags (dawn_temporal_attn_ex): 0 automatic, 1 the fp32-MFMA kernel, 2 the split-operand EXT core on any grid, 4 the opt-in
+# window-tiled 13-wave core
+TATTN_FLAGS = (0, 1, 2, 4)
+TATTN_CASES = [c for c in G.CASES if c.kind == "tattn"]
+
+
+def attn13_fits(Fext, q0, Fq, win=40):
+    """The shapes the 13-wave core covers (the rule of test_hip_ops.test_temporal_attn)."""
+    return win <= 40 and Fext <= 208 and (Fq + (q0 - win) % 16 + 15) // 16 <= 13
+
+
+def core_call(hip, case, T):
+    """The fp32-kernel case kinds and tattn on the GPU."""
+    p, k = case.p, case.kind
+    if k == "tattn":
+        return hip.temporal_attn(cu(T["qkv"]), p["F"], p["HW"], p.get("q0", 0), p.get("Fq", p["F"]), 40, cu(T["rc"]), cu(T["rs"]),
+                                 cu(T["band"]))
+    if k == "sla_unfused":
+        return hip.sla(cu(T["qkv"]), p["F"], p["HW"])
+    if k == "frame":
+        return hip.frame_attn(cu(T["qkv"]), p["F"], p["HW"])
+    raise ValueError(k)
+
+
+@pytest.mark.parametrize("case", TATTN_CASES, ids=[c.name for c in TATTN_CASES])
+def test_temporal_attn_fp64_gate(hip, case):
+    """HipOps.temporal_attn, every kernel that covers the shape: automatic, fp32 MFMA, the EXT split core, the 13-wave core."""
+    T, Wkn, want64, base32 = references(case)
+    p = case.p
+    ran = []
+    try:
+        for flags in TATTN_FLAGS:
+            if flags == 4 and not attn13_fits(p["F"], p.get("q0", 0), p.get("Fq", p["F"])):
+                continue
+            hip.temporal_attn_flags = flags
+            got = core_call(hip, case, T)
+            torch.cuda.synchronize()
+            G.fp32_gate(f"{case.name}/flags{flags}", got, want64, base32, c=case.c)
+            ran.append(flags)
+    finally:
+        hip.temporal_attn_flags = 0
+    assert ran == ([0, 1, 2, 4] if attn13_fits(p["F"], p.get("q0", 0), p.get("Fq", p["F"])) else [0, 1, 2]), ran
+
+
+FP32_CASES = [c for c in G.CASES if c.kind in ("sla_unfused", "frame", "xattn_unfused")]
+
+
+@pytest.mark.parametrize("case", FP32_CASES, ids=[c.name for c in FP32_CASES])
+def test_fp32_attention_fp64_gate(hip, case):
+    """ops.sla (sla_context_kernel + sla_apply_kernel), ops.frame_attn, and the unfused cross-attention: xattn_tables + xattn_sigma_out
+    against the original chain, xattn_core, xattn_ln_sum."""
+    from dawn_pytorch_amd.pack import pack_kn
+    T, Wkn, want64, base32 = references(case)
+    if case.kind == "xattn_unfused":
+        p = case.p
+        if p["chain"] == "sigma":
+            xtab = hip.xattn_tables(cu(T["kvtab"]), cu(T["nulltab"]), cu(T["qs"]), [pack_kn(Wkn[f"wo{b}"]).cuda() for b in range(3)], p["Co"])
+            got = hip.xattn_sigma_out(cu(T["q"]), p["HW"], xtab, cu(T["g3"]), p["Co"])
+        elif p["chain"] == "core":
+            got = hip.xattn_core(cu(T["q"]).clone(), p["HW"], cu(T["kvtab"]), cu(T["nulltab"]), cu(T["qs"]))
+        else:
+            got = hip.xattn_ln_sum(cu(T["y3"]), cu(T["g3"]), p["Co"])
+    else:
+        got = core_call(hip, case, T)
+    torch.cuda.synchronize()
+    G.fp32_gate(case.name, got, want64, base32, c=case.c)
+
+
 # ---------------------------------------------------------------------------------------------- repeated-run bit identity
 def _repeat_equal(name, fn):
     first = fn()
@@ -191,3 +262,11 @@ def test_sla_apply_run_to_run_identical(hip):
     case = G.Case("sla/F200_HW256", "sla", split=("wqkv",), F=200, HW=256)
     T, Wkn = case.make()
     _repeat_equal(case.name, lambda: attention_call(hip, case, T, Wkn))
+
+
+def test_temporal_attn_ext_core_run_to_run_identical(hip):
+    """The automatic attention core of the unfused levels (the EXT form of temporal_layer_c64_bf16_kernel: K / V / Q tiles requested one head
+    ahead into pinned registers) at the 32 x 32 level of a 256-px clip, 200 frames: eight runs bit-identical."""
+    case = G.Case("tattn/F200_HW1024", "tattn", split=(), F=200, HW=1024)
+    T, _ = case.make()
+    _repeat_equal(case.name, lambda: core_call(hip, case, T))
