@@ -105,6 +105,9 @@ SIGNATURES = {
     "dawn_workspace_bytes_guided": [c_f, _i, _i, _i, _i, _i],
     "dawn_unet_forward_guided": [c_f, _i, _i, _i, c_f, c_f, c_f, _f, _f, c_f, c_f, C.c_size_t, c_f, c_f],
     "dawn_sampler_run_guided": [c_f, _i, _i, _i, c_f, c_f, _f, c_f, _i, c_f, C.c_uint64, c_f, c_f, c_f, c_f, C.c_size_t, c_f, c_f],
+    # ancestral (DDPM) sampling: step kernel and the whole-path entry (single / guided / sharded in one)
+    "dawn_ancestral_update": [c_f, c_f, c_f, c_f, _f, _f, _f, _l, c_f, c_f],
+    "dawn_sampler_run_ancestral": [c_f, _i, _i, _i, c_f, c_f, _f, c_f, _i, c_f, C.c_uint64, c_f, c_f, c_f, c_f, C.c_size_t, c_f, c_f],
     "dawn_philox_normal": [c_f, _i, _i, _i, _i, _i, C.c_uint64, C.c_uint32, c_f],
     "dawn_affine_act": [c_f, _i, c_f, c_f, _i, c_f, _l, _i, c_f],
     "dawn_bn_relu_pool2": [c_f, c_f, c_f, c_f, _i, _i, _i, _i, c_f],

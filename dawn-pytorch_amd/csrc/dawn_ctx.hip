@@ -1150,12 +1150,15 @@ extern "C" int dawn_unet_forward(dawn_ctx* c, int F, int h, int w, const void* c
     return dawn_unet_forward_sharded(c, F, h, w, clip_mem, x3, t, eps_out, workspace, workspace_bytes, nullptr, stream);
 }
 
-// null_clip_mem != NULL and cond_scale != 1: every evaluation guided (Eval::forward_guided, whose last launch is dawn_cfg_x0)
+// null_clip_mem != NULL and cond_scale != 1: every evaluation guided (Eval::forward_guided, whose last launch is dawn_cfg_x0).
+// Loop kind: DDIM steps (`steps`) or ancestral steps (`asteps`, exactly one of the two non-NULL); they differ in the step tail only.
 static int sampler_run_impl(dawn_ctx* c, int F, int h, int w, const void* clip_mem, const void* null_clip_mem, float cond_scale,
                             const float* x_init, int S, const dawn_ddim_step* steps, uint64_t seed, const float* const* noises, float* x_out,
-                            float* thresholds, void* workspace, size_t workspace_bytes, const dawn_shard_comm* comm, void* stream) {
+                            float* thresholds, void* workspace, size_t workspace_bytes, const dawn_shard_comm* comm, void* stream,
+                            const dawn_ancestral_step* asteps = nullptr) {
     const bool guided = null_clip_mem && cond_scale != 1.0f;
-    if (!c || !clip_mem || !x_init || !steps || !x_out || !workspace) return dawn_set_error_msg(-202, "dawn_sampler_run: null argument");
+    if (!c || !clip_mem || !x_init || !(steps || asteps) || !x_out || !workspace)
+        return dawn_set_error_msg(-202, "dawn_sampler_run: null argument");
     if (shard_check(comm)) return -212;
     if (comm && (!comm->allreduce_sum_u32 || !comm->allreduce_min_u32))
         return dawn_set_error_msg(-210, "dawn_sampler_run_sharded: dawn_shard_comm.allreduce_sum_u32 / allreduce_min_u32 is NULL");
@@ -1199,23 +1202,24 @@ static int sampler_run_impl(dawn_ctx* c, int F, int h, int w, const void* clip_m
         weight = (float)(pos - fl);
     }
     for (int i = 0; i < S; ++i) {
-        const dawn_ddim_step& st = steps[i];
+        const int t = asteps ? asteps[i].t : steps[i].t;
+        const float recip = asteps ? asteps[i].recip : steps[i].recip, recipm1 = asteps ? asteps[i].recipm1 : steps[i].recipm1;
         c->arena.reset(ws, fwd_bytes, false);
         if (guided) {
             HCK(hipMemsetAsync(hist1, 0, 2048 * 4, s));
             Eval ev(c, s, F, h, w, clip_mem);
             ev.set_shard(comm);
-            ev.forward_guided(x, (float)st.t, null_clip_mem, cond_scale, eps, x0, hist1, st.recip, st.recipm1);
+            ev.forward_guided(x, (float)t, null_clip_mem, cond_scale, eps, x0, hist1, recip, recipm1);
             if (ev.rc) return ev.rc;
         } else {
             {
                 Eval ev(c, s, F, h, w, clip_mem);
                 ev.set_shard(comm);
-                ev.forward(x, (float)st.t, eps);
+                ev.forward(x, (float)t, eps);
                 if (ev.rc) return ev.rc;
             }
             HCK(hipMemsetAsync(hist1, 0, 2048 * 4, s));
-            CK(dawn_ddim_x0(x, eps, st.recip, st.recipm1, n, x0, hist1, s));
+            CK(dawn_ddim_x0(x, eps, recip, recipm1, n, x0, hist1, s));
         }
         SHARD_CB(comm->allreduce_sum_u32(comm->user, hist1, 2048, stream));
         HCK(hipMemsetAsync(state, 0, 16, s));
@@ -1234,11 +1238,17 @@ static int sampler_run_impl(dawn_ctx* c, int F, int h, int w, const void* clip_m
         CK(dawn_select_finalize(state, hmin, weight, sthr, s));
         if (thresholds) HCK(hipMemcpyAsync(thresholds + 2 * i, sthr, 8, hipMemcpyDeviceToDevice, s));
         const float* nz = nullptr;
-        if (st.t_next > 0) {                                    // noise only if t_next > 0 (MT:1201)
+        if (asteps ? t > 0 : steps[i].t_next > 0) {            // noise only if t_next > 0 (MT:1201) / t > 0 (MT:1120)
             if (noises) nz = noises[i];
             else { CK(dawn_philox_normal(noise, 3, F, f0g, Ftot, h * w, seed, (uint32_t)(i + 1), s)); nz = noise; }
         }
-        CK(dawn_ddim_update(x0, eps, sthr, nz, st.sqrt_alpha_next, st.c, st.sigma, n, (i + 1 == S) ? x_out : x, s));
+        if (asteps) {
+            const dawn_ancestral_step& st = asteps[i];
+            CK(dawn_ancestral_update(x0, x, sthr, nz, st.c1, st.c2, st.std, n, (i + 1 == S) ? x_out : x, s));
+        } else {
+            const dawn_ddim_step& st = steps[i];
+            CK(dawn_ddim_update(x0, eps, sthr, nz, st.sqrt_alpha_next, st.c, st.sigma, n, (i + 1 == S) ? x_out : x, s));
+        }
     }
     if (S == 0) HCK(hipMemcpyAsync(x_out, x, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
     return 0;
@@ -1258,6 +1268,13 @@ extern "C" int dawn_sampler_run_guided(dawn_ctx* c, int F, int h, int w, const v
     if (!null_clip_mem) return dawn_set_error_msg(-202, "dawn_sampler_run_guided: null argument");
     return sampler_run_impl(c, F, h, w, clip_mem, null_clip_mem, cond_scale, x_init, S, steps, seed, noises, x_out, thresholds,
                             workspace, workspace_bytes, comm, stream);
+}
+extern "C" int dawn_sampler_run_ancestral(dawn_ctx* c, int F, int h, int w, const void* clip_mem, const void* null_clip_mem,
+                                          float cond_scale, const float* x_init, int S, const dawn_ancestral_step* steps, uint64_t seed,
+                                          const float* const* noises, float* x_out, float* thresholds, void* workspace,
+                                          size_t workspace_bytes, const dawn_shard_comm* comm, void* stream) {
+    return sampler_run_impl(c, F, h, w, clip_mem, null_clip_mem, cond_scale, x_init, S, nullptr, seed, noises, x_out, thresholds,
+                            workspace, workspace_bytes, comm, stream, steps);
 }
 extern "C" int dawn_sampler_run(dawn_ctx* c, int F, int h, int w, const void* clip_mem, const float* x_init, int S,
                                 const dawn_ddim_step* steps, uint64_t seed, const float* const* noises, float* x_out,

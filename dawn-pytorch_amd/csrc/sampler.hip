@@ -1,4 +1,4 @@
-// DDIM sampler step pieces, all on device, no host synchronisation inside the loop.
+// DDIM and ancestral sampler step pieces, all on device, no host synchronisation inside the loop.
 // Reference: GaussianDiffusion.ddim_sample MT:1169-1205 (predict_start_from_noise MT:1072-1076, dynamic
 // thresholding by torch.quantile(|x0|, 0.9) MT:1183-1196, DDIM update MT:1198-1205).
 //
@@ -119,6 +119,21 @@ __global__ __launch_bounds__(256) void ddim_update_kernel(const float* __restric
         float r = __fadd_rn(__fmul_rn(v, san), __fmul_rn(c, eps[i]));
         if (noise) r = __fadd_rn(r, __fmul_rn(sigma, noise[i]));
         x[i] = r;
+    }
+}
+
+// ancestral (DDPM) posterior step (GaussianDiffusion.p_sample MT:1113-1121 with q_posterior MT:1078-1085): the form of
+// ddim_update_kernel with eps := x_t, san := c1, c := c2, sigma := std, so the two are bit-identical.  out may alias x_t
+// (element-wise read-then-write): no __restrict__ on that pair.
+__global__ __launch_bounds__(256) void ancestral_update_kernel(const float* __restrict__ x0, const float* x_t,
+                                                               const float* __restrict__ sp, const float* __restrict__ noise,
+                                                               float c1, float c2, float std, long n, float* out) {
+    const float s = sp[0];
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        float v = fminf(fmaxf(x0[i], -s), s) / s;
+        float r = __fadd_rn(__fmul_rn(v, c1), __fmul_rn(c2, x_t[i]));
+        if (noise) r = __fadd_rn(r, __fmul_rn(std, noise[i]));
+        out[i] = r;
     }
 }
 
@@ -247,6 +262,15 @@ extern "C" int dawn_ddim_update(const float* x0, const float* eps, const float* 
                                 float sqrt_alpha_next, float c, float sigma, long n, float* x, void* stream) {
     hipLaunchKernelGGL(ddim_update_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, x0, eps, s, noise,
                        sqrt_alpha_next, c, sigma, n, x);
+    DAWN_LAUNCH_CHECK();
+    return 0;
+}
+extern "C" int dawn_ancestral_update(const float* x0, const float* x_t, const float* s, const float* noise, float c1, float c2,
+                                     float std, long n, float* out, void* stream) {
+    if (out == x0 || (noise && out == noise))
+        return dawn_set_error_msg(-78, "dawn_ancestral_update: out must not alias x0 or noise (out == x_t is allowed)");
+    hipLaunchKernelGGL(ancestral_update_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, x0, x_t, s, noise, c1, c2,
+                       std, n, out);
     DAWN_LAUNCH_CHECK();
     return 0;
 }

@@ -1,5 +1,5 @@
 """Python binding of the C-side evaluator (include/dawn_hip.h: dawn_ctx_* / dawn_clip_prepare / dawn_unet_forward /
-dawn_sampler_run; csrc/dawn_ctx.hip) -- what a non-Python host would call, used here by the tests (bit-identical to the
+dawn_sampler_run(_ancestral); csrc/dawn_ctx.hip) -- what a non-Python host would call, used here by the tests (bit-identical to the
 Python orchestration of unet_forward.py / sampler.py) and optionally by the sampler (`GaussianDiffusion.use_ctx`).
 
 PyTorch only provides device memory (the packed weights, the per-clip table memory, the workspace) and the stream."""
@@ -31,6 +31,12 @@ class DdimStep(C.Structure):
     """Mirror of ``dawn_ddim_step``."""
     _fields_ = [("t", C.c_int), ("t_next", C.c_int), ("recip", C.c_float), ("recipm1", C.c_float),
                 ("sqrt_alpha_next", C.c_float), ("c", C.c_float), ("sigma", C.c_float)]
+
+
+class AncestralStep(C.Structure):
+    """Mirror of ``dawn_ancestral_step``."""
+    _fields_ = [("t", C.c_int), ("recip", C.c_float), ("recipm1", C.c_float), ("c1", C.c_float), ("c2", C.c_float),
+                ("std", C.c_float)]
 
 
 OPT_CONV_POLICY, OPT_TEMPORAL_FLAGS, OPT_OVERLAP, OPT_PROFILE, OPT_LONG_CLIP_FRAMES = 1, 2, 3, 4, 5
@@ -351,6 +357,47 @@ class CtxEvaluator:
         check(self.L.dawn_sampler_run(self.h, F, h, w, clip["mem"].data_ptr(), x_init.data_ptr(), S, arr, int(seed), nz,
                                       out.data_ptr(), None if thr is None else thr.data_ptr(), ws.data_ptr(), ws.numel(),
                                       self._stream()), "dawn_sampler_run")
+        return (out, thr) if want_thresholds else out
+
+    def sample_ancestral(self, clip: dict, x_init: Tensor, steps: Sequence[dict], seed: int = 0,
+                         noises: Optional[List[Optional[Tensor]]] = None, want_thresholds: bool = False,
+                         shard: Optional[ShardCallbacks] = None, null_clip: Optional[dict] = None, cond_scale: float = 1.0):
+        """dawn_sampler_run_ancestral: the ancestral loop (sampler.ancestral_step_scalars), guided when cond_scale != 1 (null_clip =
+        prepare_null_clip(...)), one T-shard rank when `shard` is given.  noises[i] is read only for steps with t > 0."""
+        F, h, w = clip["F"], clip["h"], clip["w"]
+        S = len(steps)
+        arr = (AncestralStep * max(S, 1))()
+        for i, st in enumerate(steps):
+            arr[i].t, arr[i].recip, arr[i].recipm1 = int(st["t"]), st["recip"], st["recipm1"]
+            arr[i].c1, arr[i].c2, arr[i].std = st["c1"], st["c2"], st["std"]
+        nz = None
+        if noises is not None:
+            nz = (C.c_void_p * max(S, 1))()
+            for i in range(S):
+                t = noises[i] if i < len(noises) and steps[i]["t"] > 0 else None
+                if t is not None and not (t.is_cuda and t.is_contiguous() and t.numel() == 3 * F * h * w and t.dtype == torch.float32):
+                    raise _lib.DawnHipError(f"sample_ancestral: noises[{i}] must be a contiguous fp32 GPU tensor of {3 * F * h * w} elements")
+                if t is None and steps[i]["t"] > 0:
+                    raise _lib.DawnHipError(f"sample_ancestral: noises[{i}] missing for a step with t > 0")
+                nz[i] = None if t is None else t.data_ptr()
+        guided = cond_scale != 1.0
+        if guided and null_clip is None:
+            raise _lib.DawnHipError("sample_ancestral: cond_scale != 1 needs null_clip (prepare_null_clip)")
+        x_init = x_init.contiguous().float()
+        out = torch.empty_like(x_init)
+        thr = torch.empty(S, 2, device=self.device) if want_thresholds else None
+        ws = self.workspace(F, h, w, shard, guided=guided)
+        comm = None
+        if shard is not None:
+            shard.ws = ws
+            comm = C.addressof(shard.c)
+        rc = self.L.dawn_sampler_run_ancestral(self.h, F, h, w, clip["mem"].data_ptr(), null_clip["mem"].data_ptr() if guided else None,
+                                               float(cond_scale), x_init.data_ptr(), S, arr, int(seed), nz, out.data_ptr(),
+                                               None if thr is None else thr.data_ptr(), ws.data_ptr(), ws.numel(), comm, self._stream())
+        if shard is not None:
+            self._shard_call(shard, rc, "dawn_sampler_run_ancestral")
+        else:
+            check(rc, "dawn_sampler_run_ancestral")
         return (out, thr) if want_thresholds else out
 
     def profile_read(self):

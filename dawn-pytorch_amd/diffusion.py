@@ -2,8 +2,9 @@
 (`diffusion.sample(fea, bbox_mask, cond=..., batch_size, cond_scale)`, MT:1137-1153 -> `ddim_sample`
 MT:1156-1208) on the HIP op set.  Same constructor signature and the same 12 schedule buffers in the
 `state_dict` as the reference (MT:988-1055), so `model.diffusion.load_state_dict(ckpt['diffusion'])`
-(UVG:527-528) works unchanged.  Inference only: the ancestral sampler / training losses (MT:1087-1134,
-1226-1281) are out of scope."""
+(UVG:527-528) works unchanged.  `sample` dispatches as the reference does (MT:1150): DDIM when sampling_timesteps <
+timesteps, else the ancestral loop `p_sample_loop` (MT:1113-1135).  Inference only: the training losses (MT:1226-1281)
+are out of scope."""
 from __future__ import annotations
 
 from typing import List, Optional, Sequence
@@ -11,7 +12,8 @@ from typing import List, Optional, Sequence
 import torch
 from torch import nn
 
-from .sampler import cosine_schedule_buffers, ddim_sample_clip, ddim_step_scalars
+from .sampler import (ancestral_sample_clip, ancestral_step_scalars, cosine_schedule_buffers, ddim_sample_clip,
+                      ddim_step_scalars)
 
 Tensor = torch.Tensor
 
@@ -78,9 +80,10 @@ class GaussianDiffusion(nn.Module):
         self.noise_seed: Optional[int] = None     # int -> shard-invariant Philox stream on device
         self.use_graph = False                    # capture one UNet evaluation per clip as a HIP graph
         self.eager_every = 0                      # with use_graph: run every n-th step eagerly (profiling hooks)
-        self.use_ctx = False                      # run the DDIM loop through the C-side evaluator (dawn_sampler_run, or
-                                                  # dawn_sampler_run_guided when cond_scale != 1); same kernels and arguments as
-                                                  # the Python orchestration: bit-identical output
+        self.use_ctx = False                      # run the sampler loop through the C-side evaluator (dawn_sampler_run, or
+                                                  # dawn_sampler_run_guided when cond_scale != 1; dawn_sampler_run_ancestral for
+                                                  # the ancestral loop); same kernels and arguments as the Python orchestration:
+                                                  # bit-identical output
         self.last_route: Optional[str] = None     # "ctx" or "python": which host ran the last sample()
         self.last_trace: Optional[list] = None
 
@@ -93,19 +96,29 @@ class GaussianDiffusion(nn.Module):
         Extra keyword-only hooks (not in the reference): `x_init` / `noises` inject the random draws of
         MT:1166 / MT:1201 for parity tests; `comm` = T-shard communicator (cond then holds this rank's
         frames only)."""
-        if not self.is_ddim_sampling:
-            raise NotImplementedError("ancestral sampling (sampling_timesteps >= timesteps) is out of scope")
         batch_size = cond.shape[0] if cond is not None else batch_size
         fea = torch.cat([fea, bbox_mask], dim=1)                                     # MT:1151
         shape = (batch_size, self.channels, self.num_frames, fea.shape[-1], fea.shape[-1])
-        return self.ddim_sample(fea, shape, cond=cond, cond_scale=cond_scale, x_init=x_init, noises=noises,
-                                trace=trace, comm=comm)
+        sample_fn = self.ddim_sample if self.is_ddim_sampling else self.p_sample_loop  # MT:1150
+        return sample_fn(fea, shape, cond=cond, cond_scale=cond_scale, x_init=x_init, noises=noises, trace=trace, comm=comm)
+
+    @torch.inference_mode()
+    def p_sample_loop(self, fea, shape, cond=None, cond_scale=1., *, x_init=None, noises=None, trace=False, comm=None):
+        """The ancestral loop (MT:1124-1135): `num_timesteps` evaluations at t = num_timesteps-1 ... 0, whatever
+        sampling_timesteps is.  noises[i] (hook) is read only for steps with t > 0, so num_timesteps - 1 entries suffice."""
+        return self._sample_loop("ancestral", fea, shape, cond, cond_scale, x_init, noises, trace, comm)
 
     @torch.no_grad()
     def ddim_sample(self, fea, shape, cond=None, cond_scale=1., clip_denoised=True, *, x_init=None, noises=None,
                     trace=False, comm=None):
         if not clip_denoised:
             raise NotImplementedError("clip_denoised=False is not used by the reference pipeline")
+        return self._sample_loop("ddim", fea, shape, cond, cond_scale, x_init, noises, trace, comm)
+
+    def _sample_loop(self, kind, fea, shape, cond, cond_scale, x_init, noises, trace, comm):
+        """One host loop for both samplers (kind "ddim" / "ancestral"): the C-side evaluator when use_ctx, else the Python
+        orchestration; they share the evaluation, x0 and quantile and differ in the step scalars and the step tail."""
+        ancestral = kind == "ancestral"
         unet = self.denoise_fn
         ops = unet._ops()
         if comm is not None:
@@ -113,10 +126,16 @@ class GaussianDiffusion(nn.Module):
         _long_clip_allocator(shape[2], fea)
         P = unet.packed()
         B, C, T, h, w = shape
-        S, eta = self.sampling_timesteps, self.ddim_sampling_eta
-        steps = ddim_step_scalars({k: getattr(self, k) for k in ("alphas_cumprod_prev", "sqrt_recip_alphas_cumprod",
-                                                                  "sqrt_recipm1_alphas_cumprod")}, S, eta,
-                                  self.num_timesteps)
+        if ancestral:
+            steps = ancestral_step_scalars({k: getattr(self, k) for k in (
+                "sqrt_recip_alphas_cumprod", "sqrt_recipm1_alphas_cumprod", "posterior_mean_coef1", "posterior_mean_coef2",
+                "posterior_log_variance_clipped")}, self.num_timesteps)
+        else:
+            S, eta = self.sampling_timesteps, self.ddim_sampling_eta
+            steps = ddim_step_scalars({k: getattr(self, k) for k in ("alphas_cumprod_prev", "sqrt_recip_alphas_cumprod",
+                                                                      "sqrt_recipm1_alphas_cumprod")}, S, eta,
+                                      self.num_timesteps)
+        noisy = [st["t"] > 0 if ancestral else st["t_next"] > 0 for st in steps]    # steps that draw noise (MT:1120 / MT:1201)
         device = fea.device
         Ttotal, f0 = (T, 0) if comm is None else (comm.Ttotal, comm.f0)
         if cond is not None and cond.shape[1] != T:
@@ -137,13 +156,14 @@ class GaussianDiffusion(nn.Module):
                     x0 = torch.randn(3, T, h, w, device=device)                       # MT:1166
                 nz = None
                 if noises is not None:
-                    nz = [noises[i][b].contiguous() if st["t_next"] > 0 else None for i, st in enumerate(steps)]
+                    nz = [noises[i][b].contiguous() if noisy[i] else None for i in range(len(steps))]
                 run_seed = (seed + b) if seed is not None else None
                 if nz is None and run_seed is None:
                     # unseeded (MT:1201 draws from the global generator): ONE draw from it seeds the evaluator's counter-based
                     # generator -- S x 3 x T x h x w floats of pre-drawn noise would be GBs for the long clips the path supports
                     run_seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-                outs.append(ev.sample(clip, x0, steps, seed=run_seed or 0, noises=nz, null_clip=null_clip, cond_scale=cond_scale))
+                run = ev.sample_ancestral if ancestral else ev.sample
+                outs.append(run(clip, x0, steps, seed=run_seed or 0, noises=nz, null_clip=null_clip, cond_scale=cond_scale))
             self.last_trace = None
             self.last_route = "ctx"
             return torch.stack(outs, 0)
@@ -170,8 +190,8 @@ class GaussianDiffusion(nn.Module):
             else:
                 x0 = torch.randn(3, T, h, w, device=device)                           # MT:1166
             tr = [] if trace else None
-            outs.append(ddim_sample_clip(ops, P, cs, x0, steps, noise_fn, cond_scale, cs_null, tr,
-                                         use_graph=self.use_graph, eager_every=self.eager_every))
+            outs.append((ancestral_sample_clip if ancestral else ddim_sample_clip)(
+                ops, P, cs, x0, steps, noise_fn, cond_scale, cs_null, tr, use_graph=self.use_graph, eager_every=self.eager_every))
             traces.append(tr)
         self.last_trace = traces if trace else None
         self.last_route = "python"

@@ -595,6 +595,19 @@ class HipOps:
                                       _p(x), self._stream()), "dawn_ddim_update")
         return x
 
+    def ancestral_update(self, x0: Tensor, x_t: Tensor, s: Tensor, noise: Optional[Tensor], c1: float, c2: float, std: float,
+                         out: Optional[Tensor] = None) -> Tensor:
+        """Ancestral step (p_sample MT:1113-1121): c1 * clamp(x0, -s, s) / s + c2 * x_t (+ std * noise).  out = x_t updates in place."""
+        n = x0.numel()
+        _need(x0.is_contiguous() and x_t.is_contiguous() and x_t.numel() == n and (noise is None or (noise.is_contiguous() and noise.numel() == n)),
+              "ancestral_update: contiguous x0 / x_t / noise of one size")
+        if out is None:
+            out = torch.empty_like(x0)
+        _need(out.is_contiguous() and out.numel() == n, "ancestral_update: out contiguous of x0's size")
+        check(self.L.dawn_ancestral_update(_p(x0), _p(x_t), _p(s), _p(noise), float(c1), float(c2), float(std), n, _p(out),
+                                           self._stream()), "dawn_ancestral_update")
+        return out
+
     def cfg_combine(self, e_null: Tensor, e_cond: Tensor, scale: float) -> Tensor:
         out = torch.empty_like(e_cond)
         check(self.L.dawn_cfg_combine(_p(e_null), _p(e_cond), float(scale), e_cond.numel(), _p(out), self._stream()),

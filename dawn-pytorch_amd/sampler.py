@@ -1,4 +1,5 @@
-"""DDIM sampler loop for one clip on the op interface (`GaussianDiffusion.ddim_sample`, MT:1156-1208).
+"""DDIM sampler loop for one clip on the op interface (`GaussianDiffusion.ddim_sample`, MT:1156-1208), and the ancestral loop
+(`GaussianDiffusion.p_sample_loop`, MT:1113-1135) that shares it: the two differ in the step scalars and the step tail only.
 
 Host side: the cosine schedule tables and per-step scalars (tiny fp32/fp64 host arithmetic exactly as the
 reference computes them); device side: every tensor op of the loop goes through `ops` (HIP kernels).
@@ -67,15 +68,44 @@ def ddim_step_scalars(bufs: Dict[str, Tensor], S: int, eta: float, total: int = 
     return out
 
 
+def ancestral_step_scalars(bufs: Dict[str, Tensor], timesteps: int = 1000) -> List[dict]:
+    """Per-step scalars of the ancestral loop (p_sample MT:1113-1121), t = timesteps-1 ... 0: x0 from the non-`_prev` tables
+    (MT:1074-1075), the posterior mean coefficients (MT:1080-1081) and std = exp(0.5 * posterior_log_variance_clipped[t]) formed in
+    fp32 from the fp32 buffer as p_sample does (one element, like the reference's extract()).  `noise` = t > 0 (MT:1120: the
+    variance is not zero at t = 0, only the mask removes the noise there)."""
+    get = lambda k: bufs[k].detach().float().cpu()                               # noqa: E731
+    recip, recipm1 = get("sqrt_recip_alphas_cumprod"), get("sqrt_recipm1_alphas_cumprod")
+    c1, c2, lv = get("posterior_mean_coef1"), get("posterior_mean_coef2"), get("posterior_log_variance_clipped")
+    out = []
+    for t in reversed(range(timesteps)):
+        std = (0.5 * lv[t:t + 1]).exp()
+        out.append(dict(t=t, recip=float(recip[t]), recipm1=float(recipm1[t]), c1=float(c1[t]), c2=float(c2[t]), std=float(std[0]),
+                        noise=t > 0))
+    return out
+
+
+def ancestral_sample_clip(ops, P: PackedUNet, cs: ClipState, x_init: Tensor, steps: Sequence[dict],
+                          noise_fn: Callable[[int], Optional[Tensor]], cond_scale: float = 1.0,
+                          cs_null: Optional[ClipState] = None, trace: Optional[list] = None, use_graph: bool = False,
+                          eager_every: int = 0) -> Tensor:
+    """The ancestral loop (steps = ancestral_step_scalars(...)): the evaluation, x0 and quantile of ddim_sample_clip, then
+    ops.ancestral_update; noise_fn(i) is only called when t > 0 (MT:1120)."""
+    return ddim_sample_clip(ops, P, cs, x_init, steps, noise_fn, cond_scale, cs_null, trace, use_graph, eager_every, kind="ancestral")
+
+
 def ddim_sample_clip(ops, P: PackedUNet, cs: ClipState, x_init: Tensor, steps: Sequence[dict],
                      noise_fn: Callable[[int], Optional[Tensor]], cond_scale: float = 1.0,
                      cs_null: Optional[ClipState] = None, trace: Optional[list] = None, use_graph: bool = False,
-                     eager_every: int = 0) -> Tensor:
+                     eager_every: int = 0, kind: str = "ddim") -> Tensor:
     """x_init (3, F, h, w) on the ops' device -> final latent (3, F, h, w).
 
     noise_fn(i) returns the N(0,1) tensor of step i (only called when t_next > 0, MT:1201).
+    kind = "ancestral": the step tail of p_sample instead (ancestral_sample_clip).
     cond_scale != 1: every step evaluates both branches with the condition-free prefix once (unet_forward_guided; cs_null = the
     clip state of the all-zero condition), then ONE launch forms the guided eps, x0 and the first quantile histogram (ops.cfg_x0)."""
+    if kind not in ("ddim", "ancestral"):
+        raise ValueError(f"unknown sampler step kind {kind!r}")
+    ancestral = kind == "ancestral"
     x = x_init.contiguous()
     n_total = 3 * cs.Ttotal * cs.h * cs.w
     graphed = None
@@ -106,8 +136,12 @@ def ddim_sample_clip(ops, P: PackedUNet, cs: ClipState, x_init: Tensor, steps: S
             eps = graphed(x, st["t"]) if replay else unet_forward(ops, P, cs, x, st["t"])
             x0, hist = ops.ddim_x0(x, eps, st["recip"], st["recipm1"])
         s = ops.quantile_threshold(x0, hist, n_total, 0.9)
-        noise = noise_fn(i) if st["t_next"] > 0 else None
-        x = ops.ddim_update(x0, eps, s, noise, st["sqrt_alpha_next"], st["c"], st["sigma"])
+        if ancestral:
+            noise = noise_fn(i) if st["t"] > 0 else None
+            x = ops.ancestral_update(x0, x, s, noise, st["c1"], st["c2"], st["std"])
+        else:
+            noise = noise_fn(i) if st["t_next"] > 0 else None
+            x = ops.ddim_update(x0, eps, s, noise, st["sqrt_alpha_next"], st["c"], st["sigma"])
         if trace is not None:
             # a graphed evaluation returns its static output buffer: clone, or every entry would alias the last step
             trace.append(dict(eps=eps.clone() if graphed is not None and not guided else eps, s=s, x=x))

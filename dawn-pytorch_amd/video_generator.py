@@ -226,7 +226,8 @@ def parse_args(argv=None):
     p.add_argument('--cache_path', type=str, default='cache/tmp')
     p.add_argument('--resolution', type=int, default=128)
     p.add_argument('--config', type=str, default=None, help='DAWN_{res}.yaml (defaults to ./config/DAWN_<res>.yaml)')
-    p.add_argument('--sampling_step', type=int, default=None, help='override DDIM steps (YAML ships 20)')
+    p.add_argument('--sampling_step', type=int, default=None, help='override the sampler steps (YAML ships 20): DDIM below 1000, '
+                   'the 1000-step ancestral loop at 1000 or more')
     p.add_argument('--max_n_frames', type=int, default=None, help='override the clip-length cap (YAML ships 200)')
     p.add_argument('--pbnet_pose_ckpt', type=str, default='./pretrain_models/pbnet_seperate/pose/checkpoint_40000.pth.tar')
     p.add_argument('--pbnet_blink_ckpt', type=str, default='./pretrain_models/pbnet_seperate/blink/checkpoint_95000.pth.tar')

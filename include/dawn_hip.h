@@ -302,6 +302,11 @@ int dawn_select_ws_reset(unsigned* ws, void* stream);
 /* x = clamp(x0,-s,s)/s*sqrt_alpha_next + c*eps + sigma*noise   (noise may be NULL) */
 int dawn_ddim_update(const float* x0, const float* eps, const float* s, const float* noise,
                      float sqrt_alpha_next, float c, float sigma, long n, float* x, void* stream);
+/* ancestral (DDPM) step (p_sample MT:1113-1121): out = c1*clamp(x0,-s,s)/s + c2*x_t + std*noise   (noise may be NULL; s = s[0] of
+ * dawn_select_finalize).  Bit-identical to dawn_ddim_update(x0, x_t, s, noise, c1, c2, std) into a separate buffer.  out may alias
+ * x_t (the step updates in place); out must not alias x0 or noise. */
+int dawn_ancestral_update(const float* x0, const float* x_t, const float* s, const float* noise, float c1, float c2, float std,
+                          long n, float* out, void* stream);
 /* classifier-free guidance (Unet3D.forward_with_cond_scale MT:889-890): out = null + (cond-null)*scale */
 int dawn_cfg_combine(const float* e_null, const float* e_cond, float scale, long n, float* out, void* stream);
 /* cfg_combine then ddim_x0 in one pass: eps_out = null + (cond-null)*scale, x0_out = recip*x - recipm1*eps_out, and the 2048-bin
@@ -474,6 +479,24 @@ int dawn_sampler_run_guided(dawn_ctx* ctx, int F, int h, int w, const void* clip
                             const float* x_init, int S, const dawn_ddim_step* steps, uint64_t seed, const float* const* noises,
                             float* x_out, float* thresholds, void* workspace, size_t workspace_bytes, const dawn_shard_comm* comm,
                             void* stream);
+/* ---- ancestral sampling (GaussianDiffusion.p_sample_loop MT:1124-1135, taken when sampling_timesteps >= timesteps): one evaluation per
+ * integer time t = timesteps-1 ... 0, each followed by the same dynamic-threshold quantile as DDIM and the posterior step
+ * x = c1 * clamp(x0,-s,s)/s + c2 * x + std * noise (dawn_ancestral_update, in place).  Scalars are host arithmetic of the fp32 schedule
+ * tables: c1 / c2 = posterior_mean_coef1 / 2 [t], std = exp(0.5 * posterior_log_variance_clipped[t]) in fp32. */
+typedef struct dawn_ancestral_step {
+    int t;
+    float recip, recipm1;                /* sqrt_recip_alphas_cumprod[t], sqrt_recipm1_alphas_cumprod[t] */
+    float c1, c2, std;
+} dawn_ancestral_step;
+/* ONE entry for every form: guided (as dawn_sampler_run_guided) when null_clip_mem != NULL and cond_scale != 1, T-sharded (as
+ * dawn_sampler_run_sharded) when comm != NULL.  Noise of step i only when steps[i].t > 0: noises[i] when `noises` is given (S - 1
+ * entries suffice), else the counter-based generator (seed, stream i + 1).  thresholds (optional, 2 S floats): [max(1, q), q] of every
+ * step.  Workspace: the existing queries cover this entry -- dawn_workspace_bytes (single GPU), dawn_workspace_bytes_sharded (comm),
+ * dawn_workspace_bytes_guided (guided, either form); the loop keeps the same sampler state as the DDIM entries. */
+int dawn_sampler_run_ancestral(dawn_ctx* ctx, int F, int h, int w, const void* clip_mem, const void* null_clip_mem, float cond_scale,
+                               const float* x_init, int S, const dawn_ancestral_step* steps, uint64_t seed, const float* const* noises,
+                               float* x_out, float* thresholds, void* workspace, size_t workspace_bytes, const dawn_shard_comm* comm,
+                               void* stream);
 /* after a stream synchronise: (kind, algorithmic flops, algorithmic bytes, ms) per conv launch recorded under
  * DAWN_OPT_PROFILE; kind 0 = split 3x3, 1 = split 1x1, 2 = fp32 MFMA; returns the number of entries (and clears them) */
 int dawn_ctx_profile_read(dawn_ctx* ctx, double* out4, int max_entries);
