@@ -1152,15 +1152,26 @@ extern "C" int dawn_unet_forward(dawn_ctx* c, int F, int h, int w, const void* c
 
 // null_clip_mem != NULL and cond_scale != 1: every evaluation guided (Eval::forward_guided, whose last launch is dawn_cfg_x0).
 // Loop kind: DDIM steps (`steps`) or ancestral steps (`asteps`, exactly one of the two non-NULL); they differ in the step tail only.
+// clip = NULL: dynamic thresholding at 0.9, what the entries without a mode have always run.  DAWN_CLIP_STATIC / DAWN_CLIP_NONE: the
+// evaluation (guided: ending in dawn_cfg_combine, the eps dawn_cfg_x0 forms) and ONE fused tail launch, no selection, no all-reduce.
 static int sampler_run_impl(dawn_ctx* c, int F, int h, int w, const void* clip_mem, const void* null_clip_mem, float cond_scale,
                             const float* x_init, int S, const dawn_ddim_step* steps, uint64_t seed, const float* const* noises, float* x_out,
                             float* thresholds, void* workspace, size_t workspace_bytes, const dawn_shard_comm* comm, void* stream,
-                            const dawn_ancestral_step* asteps = nullptr) {
+                            const dawn_ancestral_step* asteps = nullptr, const dawn_clip_mode* clip = nullptr) {
     const bool guided = null_clip_mem && cond_scale != 1.0f;
+    const int kind = clip ? clip->kind : (int)DAWN_CLIP_DYNAMIC;
+    const double q = clip ? clip->q : 0.9;
+    if (kind != DAWN_CLIP_DYNAMIC && kind != DAWN_CLIP_STATIC && kind != DAWN_CLIP_NONE)
+        return dawn_set_error_msg(-214, "dawn_clip_mode: unknown kind (DAWN_CLIP_DYNAMIC, DAWN_CLIP_STATIC or DAWN_CLIP_NONE)");
+    if (kind == DAWN_CLIP_DYNAMIC && !(q >= 0.0 && q <= 1.0))
+        return dawn_set_error_msg(-214, "dawn_clip_mode: q must lie in [0, 1]");
+    if (kind == DAWN_CLIP_NONE && asteps)
+        return dawn_set_error_msg(-214, "dawn_clip_mode: DAWN_CLIP_NONE does not exist for ancestral steps (p_sample always clips, MT:1113)");
+    const bool dynamic = kind == DAWN_CLIP_DYNAMIC;
     if (!c || !clip_mem || !x_init || !(steps || asteps) || !x_out || !workspace)
         return dawn_set_error_msg(-202, "dawn_sampler_run: null argument");
     if (shard_check(comm)) return -212;
-    if (comm && (!comm->allreduce_sum_u32 || !comm->allreduce_min_u32))
+    if (comm && dynamic && (!comm->allreduce_sum_u32 || !comm->allreduce_min_u32))
         return dawn_set_error_msg(-210, "dawn_sampler_run_sharded: dawn_shard_comm.allreduce_sum_u32 / allreduce_min_u32 is NULL");
     hipStream_t s = (hipStream_t)stream;
     const long n = (long)3 * F * h * w;                       // this rank's elements
@@ -1191,12 +1202,12 @@ static int sampler_run_impl(dawn_ctx* c, int F, int h, int w, const void* clip_m
     unsigned long long lo;
     float weight;
     if (n_total <= (1L << 24)) {
-        const float pos = 0.9f * (float)(n_total - 1);
+        const float pos = (float)q * (float)(n_total - 1);
         const float fl = floorf(pos);
         lo = (unsigned long long)fl;
         weight = pos - fl;
     } else {
-        const double pos = 0.9 * (double)(n_total - 1);
+        const double pos = q * (double)(n_total - 1);
         const double fl = floor(pos);
         lo = (unsigned long long)fl;
         weight = (float)(pos - fl);
@@ -1205,6 +1216,25 @@ static int sampler_run_impl(dawn_ctx* c, int F, int h, int w, const void* clip_m
         const int t = asteps ? asteps[i].t : steps[i].t;
         const float recip = asteps ? asteps[i].recip : steps[i].recip, recipm1 = asteps ? asteps[i].recipm1 : steps[i].recipm1;
         c->arena.reset(ws, fwd_bytes, false);
+        if (!dynamic) {
+            {
+                Eval ev(c, s, F, h, w, clip_mem);
+                ev.set_shard(comm);
+                if (guided) ev.forward_guided(x, (float)t, null_clip_mem, cond_scale, eps);
+                else ev.forward(x, (float)t, eps);
+                if (ev.rc) return ev.rc;
+            }
+            const float* nz = nullptr;
+            if (asteps ? t > 0 : steps[i].t_next > 0) {
+                if (noises) nz = noises[i];
+                else { CK(dawn_philox_normal(noise, 3, F, f0g, Ftot, h * w, seed, (uint32_t)(i + 1), s)); nz = noise; }
+            }
+            float* dst = (i + 1 == S) ? x_out : x;
+            const int clamp = kind == DAWN_CLIP_STATIC;
+            if (asteps) CK(dawn_ancestral_step_fixed(x, eps, nz, recip, recipm1, asteps[i].c1, asteps[i].c2, asteps[i].std, clamp, n, nullptr, dst, s));
+            else CK(dawn_ddim_step_fixed(x, eps, nz, recip, recipm1, steps[i].sqrt_alpha_next, steps[i].c, steps[i].sigma, clamp, n, nullptr, dst, s));
+            continue;
+        }
         if (guided) {
             HCK(hipMemsetAsync(hist1, 0, 2048 * 4, s));
             Eval ev(c, s, F, h, w, clip_mem);
@@ -1251,6 +1281,8 @@ static int sampler_run_impl(dawn_ctx* c, int F, int h, int w, const void* clip_m
         }
     }
     if (S == 0) HCK(hipMemcpyAsync(x_out, x, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+    if (kind == DAWN_CLIP_STATIC && thresholds && S > 0)      // [1, 1] per step: 0x3f800000 is 1.0f
+        HCK(hipMemsetD32Async((hipDeviceptr_t)thresholds, 0x3f800000, (size_t)2 * S, s));
     return 0;
 #undef SHARD_CB
 }
@@ -1275,6 +1307,23 @@ extern "C" int dawn_sampler_run_ancestral(dawn_ctx* c, int F, int h, int w, cons
                                           size_t workspace_bytes, const dawn_shard_comm* comm, void* stream) {
     return sampler_run_impl(c, F, h, w, clip_mem, null_clip_mem, cond_scale, x_init, S, nullptr, seed, noises, x_out, thresholds,
                             workspace, workspace_bytes, comm, stream, steps);
+}
+extern "C" int dawn_sampler_run_clip(dawn_ctx* c, int F, int h, int w, const void* clip_mem, const void* null_clip_mem, float cond_scale,
+                                     const float* x_init, int S, const dawn_ddim_step* steps, uint64_t seed, const float* const* noises,
+                                     float* x_out, float* thresholds, void* workspace, size_t workspace_bytes, const dawn_shard_comm* comm,
+                                     const dawn_clip_mode* clip, void* stream) {
+    if (!steps) return dawn_set_error_msg(-202, "dawn_sampler_run_clip: null argument");
+    return sampler_run_impl(c, F, h, w, clip_mem, null_clip_mem, cond_scale, x_init, S, steps, seed, noises, x_out, thresholds,
+                            workspace, workspace_bytes, comm, stream, nullptr, clip);
+}
+extern "C" int dawn_sampler_run_ancestral_clip(dawn_ctx* c, int F, int h, int w, const void* clip_mem, const void* null_clip_mem,
+                                               float cond_scale, const float* x_init, int S, const dawn_ancestral_step* steps,
+                                               uint64_t seed, const float* const* noises, float* x_out, float* thresholds,
+                                               void* workspace, size_t workspace_bytes, const dawn_shard_comm* comm,
+                                               const dawn_clip_mode* clip, void* stream) {
+    if (!steps) return dawn_set_error_msg(-202, "dawn_sampler_run_ancestral_clip: null argument");
+    return sampler_run_impl(c, F, h, w, clip_mem, null_clip_mem, cond_scale, x_init, S, nullptr, seed, noises, x_out, thresholds,
+                            workspace, workspace_bytes, comm, stream, steps, clip);
 }
 extern "C" int dawn_sampler_run(dawn_ctx* c, int F, int h, int w, const void* clip_mem, const float* x_init, int S,
                                 const dawn_ddim_step* steps, uint64_t seed, const float* const* noises, float* x_out,

@@ -1,6 +1,7 @@
 // DDIM and ancestral sampler step pieces, all on device, no host synchronisation inside the loop.
 // Reference: GaussianDiffusion.ddim_sample MT:1169-1205 (predict_start_from_noise MT:1072-1076, dynamic
-// thresholding by torch.quantile(|x0|, 0.9) MT:1183-1196, DDIM update MT:1198-1205).
+// thresholding by torch.quantile(|x0|, q) MT:1183-1196, DDIM update MT:1198-1205).  The clipping modes without a quantile (static
+// s = 1, and no clipping) have ONE fused step-tail kernel per sampler instead: step_fixed_kernel below.
 //
 // The quantile is EXACT: a 3-pass radix select (11+10+10 bits) over the bit patterns of |x0| (non-negative
 // floats order like unsigned ints) finds the order statistic v[lo]; v[lo+1] is either the same value
@@ -8,6 +9,7 @@
 // lerp(v[lo], v[hi], w).  Histograms are plain unsigned counters so that T-shards can all-reduce them.
 #include "dawn_common.h"
 #include "../../include/dawn_hip.h"
+#include <stdio.h>
 
 namespace {
 
@@ -212,6 +214,56 @@ __global__ __launch_bounds__(256) void cfg_x0_kernel(const float* e_null, const 
         if (hs[i]) atomicAdd(&hist[i], hs[i]);
 }
 
+// ---- step tails of the clipping modes that need no quantile (static: s == 1, MT:1095 / MT:1184; none: clip_denoised=False, DDIM only).
+// ONE element-wise pass: x0 as ddim_x0_kernel forms it, v = clamp(x0, -1, 1) (clamp != 0) or x0, then the update of
+// ddim_update_kernel (ANC = false: second operand eps) or ancestral_update_kernel (ANC = true: second operand x_t = x), so static
+// equals the two-launch sequence with s = 1 bit for bit (clamp(x0,-1,1)/1 is exact).
+// The roundings are PINNED here, to the ones the kernels above compile to (gfx950 ISA, -O3; the __f*_rn spellings do not stop the
+// compiler's contraction): x0 = fma(recip, x, -(recipm1 * eps)) as in ddim_x0_kernel / cfg_x0_kernel; r = (v * a) + (b * m) with three
+// roundings and r = fma(sigma, noise, r) as in ddim_update_kernel / ancestral_update_kernel.  Left to the compiler, the 128-bit body and
+// the scalar tail of this very kernel came out contracted differently from each other; the GPU test holds the identity.
+// x0 never goes through memory unless x0_out is given.  out may alias x (every thread reads its elements before it writes them): no
+// __restrict__ on that pair.  vec != 0: every pointer is 16-byte aligned, 128-bit accesses over the first n/4*4 elements, scalar tail.
+__device__ __forceinline__ float step_fixed_one(float xv, float ev, float recip, float recipm1, float a, float b, int clamp,
+                                                bool anc, bool has_noise, float sg, float nz, float& x0v) {
+#pragma clang fp contract(off)
+    x0v = __builtin_fmaf(recip, xv, -(recipm1 * ev));
+    const float v = clamp ? fminf(fmaxf(x0v, -1.0f), 1.0f) : x0v;
+    float r = (v * a) + (b * (anc ? xv : ev));
+    if (has_noise) r = __builtin_fmaf(sg, nz, r);
+    return r;
+}
+
+template <bool ANC>
+__global__ __launch_bounds__(256) void step_fixed_kernel(const float* x, const float* __restrict__ eps,
+                                                         const float* __restrict__ noise, float recip, float recipm1, float a,
+                                                         float b, float sg, int clamp, long n, int vec,
+                                                         float* __restrict__ x0_out, float* out) {
+    const long stride = (long)gridDim.x * 256;
+    const long n4 = vec ? (n >> 2) : 0;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
+        const f32x4 xv = reinterpret_cast<const f32x4*>(x)[i];
+        const f32x4 ev = reinterpret_cast<const f32x4*>(eps)[i];
+        f32x4 nv = {0.f, 0.f, 0.f, 0.f};
+        if (noise) nv = reinterpret_cast<const f32x4*>(noise)[i];
+        f32x4 r, x0v;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            float t0;
+            r[k] = step_fixed_one(xv[k], ev[k], recip, recipm1, a, b, clamp, ANC, noise != nullptr, sg, nv[k], t0);
+            x0v[k] = t0;
+        }
+        if (x0_out) reinterpret_cast<f32x4*>(x0_out)[i] = x0v;
+        reinterpret_cast<f32x4*>(out)[i] = r;
+    }
+    for (long i = n4 * 4 + (long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+        float t0;
+        const float t = step_fixed_one(x[i], eps[i], recip, recipm1, a, b, clamp, ANC, noise != nullptr, sg, noise ? noise[i] : 0.f, t0);
+        if (x0_out) x0_out[i] = t0;
+        out[i] = t;
+    }
+}
+
 int grid_for(long n) {
     long g = (n + 255) / 256;
     if (g > 2048) g = 2048;
@@ -273,6 +325,54 @@ extern "C" int dawn_ancestral_update(const float* x0, const float* x_t, const fl
                        std, n, out);
     DAWN_LAUNCH_CHECK();
     return 0;
+}
+// [p, p + n) and [q, q + n) share an element (NULL never does)
+static bool ranges_overlap(const float* p, const float* q, long n) { return p && q && p < q + n && q < p + n; }
+static int step_fixed_launch(bool anc, const char* who, const float* x, const float* eps, const float* noise, float recip,
+                             float recipm1, float a, float b, float sg, int clamp, long n, float* x0_out, float* out, void* stream) {
+    char msg[160];
+    if (!x || !eps || !out || n < 0) {
+        snprintf(msg, sizeof(msg), "%s: null argument", who);
+        return dawn_set_error_msg(-79, msg);
+    }
+    if (clamp != 0 && clamp != 1) {
+        snprintf(msg, sizeof(msg), "%s: clamp must be 1 (static) or 0 (none)", who);
+        return dawn_set_error_msg(-79, msg);
+    }
+    if (anc && !clamp) {
+        snprintf(msg, sizeof(msg), "%s: clamp = 0 does not exist for the ancestral step (p_sample always clips, MT:1113)", who);
+        return dawn_set_error_msg(-79, msg);
+    }
+    const bool bad = (out != x && ranges_overlap(out, x, n)) || ranges_overlap(out, eps, n) || ranges_overlap(out, noise, n) ||
+                     ranges_overlap(out, x0_out, n) || ranges_overlap(x0_out, x, n) || ranges_overlap(x0_out, eps, n) ||
+                     ranges_overlap(x0_out, noise, n);
+    if (bad) {
+        snprintf(msg, sizeof(msg), "%s: out must not alias eps, noise or x0_out (out == x is allowed); x0_out must not alias an input", who);
+        return dawn_set_error_msg(-80, msg);
+    }
+    if (n == 0) return 0;
+    const uintptr_t bits = (uintptr_t)x | (uintptr_t)eps | (uintptr_t)noise | (uintptr_t)x0_out | (uintptr_t)out;
+    const int vec = (bits & 15) == 0 && n >= 4;
+    const int grid = grid_for(vec ? (n + 3) / 4 : n);
+    if (anc)
+        hipLaunchKernelGGL(step_fixed_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, eps, noise, recip, recipm1, a,
+                           b, sg, clamp, n, vec, x0_out, out);
+    else
+        hipLaunchKernelGGL(step_fixed_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, eps, noise, recip, recipm1, a,
+                           b, sg, clamp, n, vec, x0_out, out);
+    DAWN_LAUNCH_CHECK();
+    return 0;
+}
+extern "C" int dawn_ddim_step_fixed(const float* x, const float* eps, const float* noise, float recip, float recipm1,
+                                    float sqrt_alpha_next, float c, float sigma, int clamp, long n, float* x0_out, float* out,
+                                    void* stream) {
+    return step_fixed_launch(false, "dawn_ddim_step_fixed", x, eps, noise, recip, recipm1, sqrt_alpha_next, c, sigma, clamp, n, x0_out,
+                             out, stream);
+}
+extern "C" int dawn_ancestral_step_fixed(const float* x_t, const float* eps, const float* noise, float recip, float recipm1, float c1,
+                                         float c2, float std, int clamp, long n, float* x0_out, float* out, void* stream) {
+    return step_fixed_launch(true, "dawn_ancestral_step_fixed", x_t, eps, noise, recip, recipm1, c1, c2, std, clamp, n, x0_out, out,
+                             stream);
 }
 extern "C" int dawn_cfg_combine(const float* e_null, const float* e_cond, float scale, long n, float* out,
                                 void* stream) {

@@ -39,6 +39,20 @@ class AncestralStep(C.Structure):
                 ("std", C.c_float)]
 
 
+class ClipMode(C.Structure):
+    """Mirror of ``dawn_clip_mode``."""
+    _fields_ = [("kind", C.c_int), ("q", C.c_double)]
+
+
+CLIP_KINDS = {"dynamic": 0, "static": 1, "none": 2}      # DAWN_CLIP_DYNAMIC / _STATIC / _NONE
+
+
+def _clip_struct(clip, ancestral: bool) -> ClipMode:
+    from .sampler import clip_mode
+    kind, q = clip_mode(clip, ancestral)
+    return ClipMode(CLIP_KINDS[kind], 0.0 if q is None else q)
+
+
 OPT_CONV_POLICY, OPT_TEMPORAL_FLAGS, OPT_OVERLAP, OPT_PROFILE, OPT_LONG_CLIP_FRAMES = 1, 2, 3, 4, 5
 
 # ---- T-shard callbacks (include/dawn_hip.h: dawn_shard_comm)
@@ -311,8 +325,10 @@ class CtxEvaluator:
 
     def sample(self, clip: dict, x_init: Tensor, steps: Sequence[dict], seed: int = 0,
                noises: Optional[List[Optional[Tensor]]] = None, want_thresholds: bool = False,
-               shard: Optional[ShardCallbacks] = None, null_clip: Optional[dict] = None, cond_scale: float = 1.0):
-        """cond_scale != 1 (with null_clip = prepare_null_clip(...)): guided sampling, dawn_sampler_run_guided."""
+               shard: Optional[ShardCallbacks] = None, null_clip: Optional[dict] = None, cond_scale: float = 1.0, x0_clip=None):
+        """cond_scale != 1 (with null_clip = prepare_null_clip(...)): guided sampling, dawn_sampler_run_guided.
+        x0_clip (sampler.clip_mode; None: dynamic thresholding at 0.9 through the entries above): any x0 clipping mode through
+        dawn_sampler_run_clip, single / guided / sharded alike.  Thresholds: static [1, 1] per step, none: rows left as allocated."""
         F, h, w = clip["F"], clip["h"], clip["w"]
         S = len(steps)
         arr = (DdimStep * max(S, 1))()
@@ -330,6 +346,25 @@ class CtxEvaluator:
         x_init = x_init.contiguous().float()
         out = torch.empty_like(x_init)
         thr = torch.empty(S, 2, device=self.device) if want_thresholds else None
+        if x0_clip is not None:
+            mode = _clip_struct(x0_clip, False)
+            guided = cond_scale != 1.0
+            if guided and null_clip is None:
+                raise _lib.DawnHipError("sample: cond_scale != 1 needs null_clip (prepare_null_clip)")
+            ws = self.workspace(F, h, w, shard, guided=guided)
+            comm = None
+            if shard is not None:
+                shard.ws = ws
+                comm = C.addressof(shard.c)
+            rc = self.L.dawn_sampler_run_clip(self.h, F, h, w, clip["mem"].data_ptr(), null_clip["mem"].data_ptr() if guided else None,
+                                              float(cond_scale), x_init.data_ptr(), S, arr, int(seed), nz, out.data_ptr(),
+                                              None if thr is None else thr.data_ptr(), ws.data_ptr(), ws.numel(), comm,
+                                              C.addressof(mode), self._stream())
+            if shard is not None:
+                self._shard_call(shard, rc, "dawn_sampler_run_clip")
+            else:
+                check(rc, "dawn_sampler_run_clip")
+            return (out, thr) if want_thresholds else out
         if cond_scale != 1.0:
             if null_clip is None:
                 raise _lib.DawnHipError("sample: cond_scale != 1 needs null_clip (prepare_null_clip)")
@@ -361,9 +396,12 @@ class CtxEvaluator:
 
     def sample_ancestral(self, clip: dict, x_init: Tensor, steps: Sequence[dict], seed: int = 0,
                          noises: Optional[List[Optional[Tensor]]] = None, want_thresholds: bool = False,
-                         shard: Optional[ShardCallbacks] = None, null_clip: Optional[dict] = None, cond_scale: float = 1.0):
+                         shard: Optional[ShardCallbacks] = None, null_clip: Optional[dict] = None, cond_scale: float = 1.0,
+                         x0_clip=None):
         """dawn_sampler_run_ancestral: the ancestral loop (sampler.ancestral_step_scalars), guided when cond_scale != 1 (null_clip =
-        prepare_null_clip(...)), one T-shard rank when `shard` is given.  noises[i] is read only for steps with t > 0."""
+        prepare_null_clip(...)), one T-shard rank when `shard` is given.  noises[i] is read only for steps with t > 0.
+        x0_clip (sampler.clip_mode; None: dynamic thresholding at 0.9 through that entry): ("dynamic", q) or ("static",) through
+        dawn_sampler_run_ancestral_clip."""
         F, h, w = clip["F"], clip["h"], clip["w"]
         S = len(steps)
         arr = (AncestralStep * max(S, 1))()
@@ -391,13 +429,18 @@ class CtxEvaluator:
         if shard is not None:
             shard.ws = ws
             comm = C.addressof(shard.c)
-        rc = self.L.dawn_sampler_run_ancestral(self.h, F, h, w, clip["mem"].data_ptr(), null_clip["mem"].data_ptr() if guided else None,
-                                               float(cond_scale), x_init.data_ptr(), S, arr, int(seed), nz, out.data_ptr(),
-                                               None if thr is None else thr.data_ptr(), ws.data_ptr(), ws.numel(), comm, self._stream())
-        if shard is not None:
-            self._shard_call(shard, rc, "dawn_sampler_run_ancestral")
+        args = (self.h, F, h, w, clip["mem"].data_ptr(), null_clip["mem"].data_ptr() if guided else None, float(cond_scale),
+                x_init.data_ptr(), S, arr, int(seed), nz, out.data_ptr(), None if thr is None else thr.data_ptr(), ws.data_ptr(),
+                ws.numel(), comm)
+        if x0_clip is not None:
+            mode = _clip_struct(x0_clip, True)
+            rc, what = self.L.dawn_sampler_run_ancestral_clip(*args, C.addressof(mode), self._stream()), "dawn_sampler_run_ancestral_clip"
         else:
-            check(rc, "dawn_sampler_run_ancestral")
+            rc, what = self.L.dawn_sampler_run_ancestral(*args, self._stream()), "dawn_sampler_run_ancestral"
+        if shard is not None:
+            self._shard_call(shard, rc, what)
+        else:
+            check(rc, what)
         return (out, thr) if want_thresholds else out
 
     def profile_read(self):

@@ -3,8 +3,10 @@
 MT:1156-1208) on the HIP op set.  Same constructor signature and the same 12 schedule buffers in the
 `state_dict` as the reference (MT:988-1055), so `model.diffusion.load_state_dict(ckpt['diffusion'])`
 (UVG:527-528) works unchanged.  `sample` dispatches as the reference does (MT:1150): DDIM when sampling_timesteps <
-timesteps, else the ancestral loop `p_sample_loop` (MT:1113-1135).  Inference only: the training losses (MT:1226-1281)
-are out of scope."""
+timesteps, else the ancestral loop `p_sample_loop` (MT:1113-1135).  x0 is clipped as the reference clips it (MT:1094-1107,
+MT:1183-1196): `use_dynamic_thres=True` -> dynamic thresholding at `dynamic_thres_percentile` (the shipped pipeline: 0.9, FD:164),
+`use_dynamic_thres=False` (the constructor default) -> static clamp to [-1, 1], `ddim_sample(clip_denoised=False)` -> none.
+Inference only: the training losses (MT:1226-1281) are out of scope."""
 from __future__ import annotations
 
 from typing import List, Optional, Sequence
@@ -12,7 +14,7 @@ from typing import List, Optional, Sequence
 import torch
 from torch import nn
 
-from .sampler import (ancestral_sample_clip, ancestral_step_scalars, cosine_schedule_buffers, ddim_sample_clip,
+from .sampler import (CLIP_DEFAULT, ancestral_sample_clip, ancestral_step_scalars, clip_mode, cosine_schedule_buffers, ddim_sample_clip,
                       ddim_step_scalars)
 
 Tensor = torch.Tensor
@@ -74,16 +76,18 @@ class GaussianDiffusion(nn.Module):
         self.text_use_bert_cls = text_use_bert_cls
         self.use_dynamic_thres = use_dynamic_thres
         self.dynamic_thres_percentile = dynamic_thres_percentile
-        if not use_dynamic_thres or dynamic_thres_percentile != 0.9:
-            raise NotImplementedError("HIP sampler implements the shipped setting: dynamic thresholding at 0.9 (FD:164)")
+        # the x0 clipping mode every sampler path runs (sampler.clip_mode); a percentile outside [0, 1] raises ValueError here
+        # (torch.quantile would at the first step)
+        self.clip = clip_mode(("dynamic", dynamic_thres_percentile) if use_dynamic_thres else ("static",))
         # reproducibility knobs (the reference draws from the global torch generator)
         self.noise_seed: Optional[int] = None     # int -> shard-invariant Philox stream on device
         self.use_graph = False                    # capture one UNet evaluation per clip as a HIP graph
         self.eager_every = 0                      # with use_graph: run every n-th step eagerly (profiling hooks)
         self.use_ctx = False                      # run the sampler loop through the C-side evaluator (dawn_sampler_run, or
                                                   # dawn_sampler_run_guided when cond_scale != 1; dawn_sampler_run_ancestral for
-                                                  # the ancestral loop); same kernels and arguments as the Python orchestration:
-                                                  # bit-identical output
+                                                  # the ancestral loop; dawn_sampler_run_clip / _ancestral_clip for any clipping
+                                                  # mode but dynamic at 0.9); same kernels and arguments as the Python
+                                                  # orchestration: bit-identical output
         self.last_route: Optional[str] = None     # "ctx" or "python": which host ran the last sample()
         self.last_trace: Optional[list] = None
 
@@ -106,19 +110,21 @@ class GaussianDiffusion(nn.Module):
     def p_sample_loop(self, fea, shape, cond=None, cond_scale=1., *, x_init=None, noises=None, trace=False, comm=None):
         """The ancestral loop (MT:1124-1135): `num_timesteps` evaluations at t = num_timesteps-1 ... 0, whatever
         sampling_timesteps is.  noises[i] (hook) is read only for steps with t > 0, so num_timesteps - 1 entries suffice."""
-        return self._sample_loop("ancestral", fea, shape, cond, cond_scale, x_init, noises, trace, comm)
+        return self._sample_loop("ancestral", fea, shape, cond, cond_scale, x_init, noises, trace, comm, self.clip)
 
     @torch.no_grad()
     def ddim_sample(self, fea, shape, cond=None, cond_scale=1., clip_denoised=True, *, x_init=None, noises=None,
                     trace=False, comm=None):
-        if not clip_denoised:
-            raise NotImplementedError("clip_denoised=False is not used by the reference pipeline")
-        return self._sample_loop("ddim", fea, shape, cond, cond_scale, x_init, noises, trace, comm)
+        """clip_denoised=False (MT:1183): x0 is used as predicted, neither thresholded nor clamped."""
+        return self._sample_loop("ddim", fea, shape, cond, cond_scale, x_init, noises, trace, comm,
+                                 self.clip if clip_denoised else ("none", None))
 
-    def _sample_loop(self, kind, fea, shape, cond, cond_scale, x_init, noises, trace, comm):
+    def _sample_loop(self, kind, fea, shape, cond, cond_scale, x_init, noises, trace, comm, clip):
         """One host loop for both samplers (kind "ddim" / "ancestral"): the C-side evaluator when use_ctx, else the Python
-        orchestration; they share the evaluation, x0 and quantile and differ in the step scalars and the step tail."""
+        orchestration; they share the evaluation and differ in the step scalars and the step tail.  clip = (kind, q) of
+        sampler.clip_mode."""
         ancestral = kind == "ancestral"
+        clip = clip_mode(clip, ancestral)
         unet = self.denoise_fn
         ops = unet._ops()
         if comm is not None:
@@ -145,7 +151,7 @@ class GaussianDiffusion(nn.Module):
             ev = unet.ctx_evaluator()
             rcos, rsin = P.rotary_tables(T + 2 * P.win)
             for b in range(B):
-                clip = ev.prepare_clip(fea[b].contiguous().float(), cond[b].contiguous().float(), rcos, rsin)
+                clip_mem = ev.prepare_clip(fea[b].contiguous().float(), cond[b].contiguous().float(), rcos, rsin)
                 null_clip = ev.prepare_null_clip(fea[b].contiguous().float(), T, rcos, rsin) if cond_scale != 1.0 else None
                 seed = self.noise_seed
                 if x_init is not None:
@@ -163,7 +169,8 @@ class GaussianDiffusion(nn.Module):
                     # generator -- S x 3 x T x h x w floats of pre-drawn noise would be GBs for the long clips the path supports
                     run_seed = int(torch.randint(0, 2 ** 62, (1,)).item())
                 run = ev.sample_ancestral if ancestral else ev.sample
-                outs.append(run(clip, x0, steps, seed=run_seed or 0, noises=nz, null_clip=null_clip, cond_scale=cond_scale))
+                outs.append(run(clip_mem, x0, steps, seed=run_seed or 0, noises=nz, null_clip=null_clip, cond_scale=cond_scale,
+                                x0_clip=None if clip == CLIP_DEFAULT else clip))
             self.last_trace = None
             self.last_route = "ctx"
             return torch.stack(outs, 0)
@@ -191,7 +198,8 @@ class GaussianDiffusion(nn.Module):
                 x0 = torch.randn(3, T, h, w, device=device)                           # MT:1166
             tr = [] if trace else None
             outs.append((ancestral_sample_clip if ancestral else ddim_sample_clip)(
-                ops, P, cs, x0, steps, noise_fn, cond_scale, cs_null, tr, use_graph=self.use_graph, eager_every=self.eager_every))
+                ops, P, cs, x0, steps, noise_fn, cond_scale, cs_null, tr, use_graph=self.use_graph, eager_every=self.eager_every,
+                clip=clip))
             traces.append(tr)
         self.last_trace = traces if trace else None
         self.last_route = "python"

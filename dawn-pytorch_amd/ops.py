@@ -608,6 +608,37 @@ class HipOps:
                                            self._stream()), "dawn_ancestral_update")
         return out
 
+    def _step_fixed(self, fn, name: str, x: Tensor, eps: Tensor, noise: Optional[Tensor], recip: float, recipm1: float, a: float,
+                    b: float, sg: float, clamp: bool, want_x0: bool, out: Optional[Tensor]):
+        n = x.numel()
+        _need(x.is_contiguous() and eps.is_contiguous() and eps.numel() == n and (noise is None or (noise.is_contiguous() and noise.numel() == n)),
+              f"{name}: contiguous x / eps / noise of one size")
+        self._require(x, eps, noise, out)
+        if out is None:
+            out = torch.empty_like(x)
+        _need(out.is_contiguous() and out.numel() == n, f"{name}: out contiguous of x's size")
+        x0 = torch.empty_like(x) if want_x0 else None
+        check(fn(_p(x), _p(eps), _p(noise), float(recip), float(recipm1), float(a), float(b), float(sg), int(bool(clamp)), n, _p(x0),
+                 _p(out), self._stream()), name)
+        return (out, x0) if want_x0 else out
+
+    def ddim_step_fixed(self, x: Tensor, eps: Tensor, noise: Optional[Tensor], recip: float, recipm1: float, sqrt_alpha_next: float,
+                        c: float, sigma: float, clamp: bool = True, want_x0: bool = False, out: Optional[Tensor] = None):
+        """The whole DDIM step tail of the clipping modes without a quantile in ONE launch (dawn_ddim_step_fixed): x0 = recip*x -
+        recipm1*eps, v = clamp(x0, -1, 1) (clamp: static thresholding) or x0 (no clipping), v*sqrt_alpha_next + c*eps (+ sigma*noise).
+        Bit-identical to ddim_x0 + ddim_update with s = 1.  Returns the next latent, or (next latent, x0) with want_x0; out = x
+        updates in place."""
+        return self._step_fixed(self.L.dawn_ddim_step_fixed, "dawn_ddim_step_fixed", x, eps, noise, recip, recipm1, sqrt_alpha_next, c,
+                                sigma, clamp, want_x0, out)
+
+    def ancestral_step_fixed(self, x_t: Tensor, eps: Tensor, noise: Optional[Tensor], recip: float, recipm1: float, c1: float, c2: float,
+                             std: float, clamp: bool = True, want_x0: bool = False, out: Optional[Tensor] = None):
+        """The ancestral step tail with static thresholding in ONE launch (dawn_ancestral_step_fixed): c1*clamp(x0, -1, 1) + c2*x_t
+        (+ std*noise); bit-identical to ddim_x0 + ancestral_update with s = 1.  clamp=False is refused by the library (p_sample
+        always clips, MT:1113)."""
+        return self._step_fixed(self.L.dawn_ancestral_step_fixed, "dawn_ancestral_step_fixed", x_t, eps, noise, recip, recipm1, c1, c2,
+                                std, clamp, want_x0, out)
+
     def cfg_combine(self, e_null: Tensor, e_cond: Tensor, scale: float) -> Tensor:
         out = torch.empty_like(e_cond)
         check(self.L.dawn_cfg_combine(_p(e_null), _p(e_cond), float(scale), e_cond.numel(), _p(out), self._stream()),

@@ -84,28 +84,64 @@ def ancestral_step_scalars(bufs: Dict[str, Tensor], timesteps: int = 1000) -> Li
     return out
 
 
+CLIP_DEFAULT = ("dynamic", 0.9)        # the shipped pipeline's setting (FD:164)
+
+
+def clip_mode(clip, ancestral: bool = False):
+    """Normalise an x0 clipping mode (MT:1094-1107 / MT:1183-1196) to (kind, q):
+        ("dynamic", q)  s = max(1, quantile_q(|x0|)) over the clip, x0 = clamp(x0, -s, s) / s      use_dynamic_thres=True
+        ("static",)     x0 = clamp(x0, -1, 1)                                                      use_dynamic_thres=False
+        ("none",)       x0 unchanged; DDIM only (p_sample always clips, MT:1113)                   ddim_sample(clip_denoised=False)
+    A bare string names a mode without a percentile.  q outside [0, 1] raises ValueError (torch.quantile would at the first step)."""
+    if isinstance(clip, str):
+        clip = (clip,)
+    clip = tuple(clip)
+    if len(clip) == 2 and clip[1] is None:                       # the normalised form of a mode without a percentile
+        clip = clip[:1]
+    kind = clip[0] if clip else None
+    if kind == "dynamic":
+        if len(clip) != 2:
+            raise ValueError('clip = ("dynamic", q) needs the percentile q')
+        q = float(clip[1])
+        if not 0.0 <= q <= 1.0:                                  # (NaN fails both comparisons)
+            raise ValueError(f"dynamic thresholding percentile must lie in [0, 1], got {clip[1]!r}")
+        return "dynamic", q
+    if kind in ("static", "none") and len(clip) == 1:
+        if kind == "none" and ancestral:
+            raise ValueError('clip = ("none",) does not exist for the ancestral loop: p_sample always clips (MT:1113)')
+        return kind, None
+    raise ValueError(f'unknown clipping mode {clip!r}: ("dynamic", q), ("static",) or ("none",)')
+
+
 def ancestral_sample_clip(ops, P: PackedUNet, cs: ClipState, x_init: Tensor, steps: Sequence[dict],
                           noise_fn: Callable[[int], Optional[Tensor]], cond_scale: float = 1.0,
                           cs_null: Optional[ClipState] = None, trace: Optional[list] = None, use_graph: bool = False,
-                          eager_every: int = 0) -> Tensor:
+                          eager_every: int = 0, clip=CLIP_DEFAULT) -> Tensor:
     """The ancestral loop (steps = ancestral_step_scalars(...)): the evaluation, x0 and quantile of ddim_sample_clip, then
-    ops.ancestral_update; noise_fn(i) is only called when t > 0 (MT:1120)."""
-    return ddim_sample_clip(ops, P, cs, x_init, steps, noise_fn, cond_scale, cs_null, trace, use_graph, eager_every, kind="ancestral")
+    ops.ancestral_update; noise_fn(i) is only called when t > 0 (MT:1120).  clip: ("dynamic", q) or ("static",), see clip_mode."""
+    return ddim_sample_clip(ops, P, cs, x_init, steps, noise_fn, cond_scale, cs_null, trace, use_graph, eager_every, kind="ancestral",
+                            clip=clip)
 
 
 def ddim_sample_clip(ops, P: PackedUNet, cs: ClipState, x_init: Tensor, steps: Sequence[dict],
                      noise_fn: Callable[[int], Optional[Tensor]], cond_scale: float = 1.0,
                      cs_null: Optional[ClipState] = None, trace: Optional[list] = None, use_graph: bool = False,
-                     eager_every: int = 0, kind: str = "ddim") -> Tensor:
+                     eager_every: int = 0, kind: str = "ddim", clip=CLIP_DEFAULT) -> Tensor:
     """x_init (3, F, h, w) on the ops' device -> final latent (3, F, h, w).
 
     noise_fn(i) returns the N(0,1) tensor of step i (only called when t_next > 0, MT:1201).
     kind = "ancestral": the step tail of p_sample instead (ancestral_sample_clip).
     cond_scale != 1: every step evaluates both branches with the condition-free prefix once (unet_forward_guided; cs_null = the
-    clip state of the all-zero condition), then ONE launch forms the guided eps, x0 and the first quantile histogram (ops.cfg_x0)."""
+    clip state of the all-zero condition), then ONE launch forms the guided eps, x0 and the first quantile histogram (ops.cfg_x0).
+    clip (clip_mode): ("dynamic", q) runs the quantile selection at q; ("static",) / ("none",) need none -- the evaluation (guided:
+    ending in ops.cfg_combine, the eps ops.cfg_x0 forms) is followed by ONE fused launch for the whole step tail
+    (ops.ddim_step_fixed / ops.ancestral_step_fixed) and, T-sharded, by no all-reduce.  Trace entries: eps, x and s (static: a
+    constant [1, 1] tensor; none: None)."""
     if kind not in ("ddim", "ancestral"):
         raise ValueError(f"unknown sampler step kind {kind!r}")
     ancestral = kind == "ancestral"
+    clip_kind, q = clip_mode(clip, ancestral)
+    s_one = None
     x = x_init.contiguous()
     n_total = 3 * cs.Ttotal * cs.h * cs.w
     graphed = None
@@ -128,6 +164,25 @@ def ddim_sample_clip(ops, P: PackedUNet, cs: ClipState, x_init: Tensor, steps: S
         # with a graph, every `eager_every`-th step still runs eagerly so that per-kernel HIP events (bench.py's
         # live roofline measurement) sample the timed region
         replay = graphed is not None and not (eager_every and ops.prof is not None and i % eager_every == 0)
+        if clip_kind != "dynamic":
+            if guided:
+                eps_c, eps_null = graphed(x, st["t"]) if replay else unet_forward_guided(ops, P, cs, cs_null, x, st["t"])
+                eps = ops.cfg_combine(eps_null, eps_c, cond_scale)
+                del eps_c, eps_null
+            else:
+                eps = graphed(x, st["t"]) if replay else unet_forward(ops, P, cs, x, st["t"])
+            clamp = clip_kind == "static"
+            if ancestral:
+                noise = noise_fn(i) if st["t"] > 0 else None
+                x = ops.ancestral_step_fixed(x, eps, noise, st["recip"], st["recipm1"], st["c1"], st["c2"], st["std"], clamp)
+            else:
+                noise = noise_fn(i) if st["t_next"] > 0 else None
+                x = ops.ddim_step_fixed(x, eps, noise, st["recip"], st["recipm1"], st["sqrt_alpha_next"], st["c"], st["sigma"], clamp)
+            if trace is not None:
+                if clamp and s_one is None:
+                    s_one = torch.ones(2, device=x.device, dtype=torch.float32)
+                trace.append(dict(eps=eps.clone() if graphed is not None and not guided else eps, s=s_one if clamp else None, x=x))
+            continue
         if guided:
             eps_c, eps_null = graphed(x, st["t"]) if replay else unet_forward_guided(ops, P, cs, cs_null, x, st["t"])
             eps, x0, hist = ops.cfg_x0(eps_null, eps_c, cond_scale, x, st["recip"], st["recipm1"])
@@ -135,7 +190,7 @@ def ddim_sample_clip(ops, P: PackedUNet, cs: ClipState, x_init: Tensor, steps: S
         else:
             eps = graphed(x, st["t"]) if replay else unet_forward(ops, P, cs, x, st["t"])
             x0, hist = ops.ddim_x0(x, eps, st["recip"], st["recipm1"])
-        s = ops.quantile_threshold(x0, hist, n_total, 0.9)
+        s = ops.quantile_threshold(x0, hist, n_total, q)
         if ancestral:
             noise = noise_fn(i) if st["t"] > 0 else None
             x = ops.ancestral_update(x0, x, s, noise, st["c1"], st["c2"], st["std"])

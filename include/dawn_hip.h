@@ -291,7 +291,8 @@ int dawn_sinusoidal(float t, int dim, const float* freqs, float* out, void* stre
 /* x0 = recip*x - recipm1*eps ; also histogram of the top 11 bits of |x0| into hist[2048] */
 int dawn_ddim_x0(const float* x, const float* eps, float recip, float recipm1, long n, float* x0,
                  unsigned* hist, void* stream);
-/* radix-select helpers for the exact 0.9-quantile of |x0| (torch.quantile, linear interpolation) */
+/* radix-select helpers for the exact q-quantile of |x0| (torch.quantile, linear interpolation): `rank` / `weight` = floor and fraction
+ * of q * (n - 1), any q in [0, 1] (q = 1: rank n - 1, no element above it, the result is the maximum; q = 0: rank 0, weight 0) */
 int dawn_select_scan(const unsigned* hist, int nbins, unsigned long long rank, unsigned* state, int pass,
                      void* stream);
 int dawn_select_hist(const float* x0, long n, const unsigned* state, int pass, unsigned* hist, void* stream);
@@ -307,6 +308,21 @@ int dawn_ddim_update(const float* x0, const float* eps, const float* s, const fl
  * x_t (the step updates in place); out must not alias x0 or noise. */
 int dawn_ancestral_update(const float* x0, const float* x_t, const float* s, const float* noise, float c1, float c2, float std,
                           long n, float* out, void* stream);
+/* ---- step tails of the x0 clipping modes that need no quantile (MT:1094-1107 / MT:1183-1196), ONE element-wise launch each:
+ *   x0  = recip*x - recipm1*eps
+ *   v   = clamp(x0, -1, 1)   clamp = 1: static thresholding (use_dynamic_thres = False, the reference's constructor default)
+ *       = x0                 clamp = 0: no clipping (ddim_sample(clip_denoised=False)); DDIM only
+ *   out = v*sqrt_alpha_next + c*eps + sigma*noise        (dawn_ddim_step_fixed)
+ *   out = v*c1 + c2*x_t + std*noise                      (dawn_ancestral_step_fixed; clamp = 0 is an error: p_sample always clips)
+ * noise may be NULL (term dropped); x0_out may be NULL (x0 is then never written to memory).  The roundings are those of dawn_ddim_x0
+ * followed by dawn_ddim_update / dawn_ancestral_update, so clamp = 1 is bit-identical to that pair with s = 1, and clamp = 0 to
+ * dawn_ddim_x0 followed by the update without the clamp.  Aliasing: out == x (x_t) is allowed (the step updates in place); out must
+ * not overlap eps, noise or x0_out, nor x partially; x0_out must not overlap x, eps or noise: an error return, nothing launched.
+ * 128-bit accesses when every pointer is 16-byte aligned, scalar otherwise; any n >= 0. */
+int dawn_ddim_step_fixed(const float* x, const float* eps, const float* noise, float recip, float recipm1, float sqrt_alpha_next,
+                         float c, float sigma, int clamp, long n, float* x0_out, float* out, void* stream);
+int dawn_ancestral_step_fixed(const float* x_t, const float* eps, const float* noise, float recip, float recipm1, float c1, float c2,
+                              float std, int clamp, long n, float* x0_out, float* out, void* stream);
 /* classifier-free guidance (Unet3D.forward_with_cond_scale MT:889-890): out = null + (cond-null)*scale */
 int dawn_cfg_combine(const float* e_null, const float* e_cond, float scale, long n, float* out, void* stream);
 /* cfg_combine then ddim_x0 in one pass: eps_out = null + (cond-null)*scale, x0_out = recip*x - recipm1*eps_out, and the 2048-bin
@@ -385,7 +401,8 @@ int dawn_attn_bias32(const float* q, int ldq, const float* k, int ldk, const flo
  *   dawn_clip_prepare  per-clip tables (hoisted out of the DDIM loop: fea part of init_conv, condition -> k/v tables,
  *                      sigma-affine cross-attention tables, rotary + relative-position tables)   [FD:332-350, MT:1151,1167]
  *   dawn_unet_forward  one Unet3D.forward (null_cond_prob = 0) of one clip                       [MT:892-956]
- *   dawn_sampler_run   the DDIM loop: S x (forward, x0, dynamic-threshold quantile, update)      [MT:1156-1208]
+ *   dawn_sampler_run   the DDIM loop: S x (forward, x0, dynamic-threshold quantile at 0.9, update)  [MT:1156-1208]
+ *                      (other clipping modes / percentiles: dawn_sampler_run_clip, dawn_sampler_run_ancestral_clip below)
  * No allocation, no synchronisation: the caller owns the clip memory (dawn_clip_bytes) and the workspace
  * (dawn_workspace_bytes); launches go to `stream` and to one ctx-owned side stream forked / joined with events.
  * One host thread per ctx.  Single GPU (the T-shard exchanges live in the Python host, tshard.py). */
@@ -497,6 +514,30 @@ int dawn_sampler_run_ancestral(dawn_ctx* ctx, int F, int h, int w, const void* c
                                const float* x_init, int S, const dawn_ancestral_step* steps, uint64_t seed, const float* const* noises,
                                float* x_out, float* thresholds, void* workspace, size_t workspace_bytes, const dawn_shard_comm* comm,
                                void* stream);
+/* ---- x0 clipping modes of the whole-loop entries (MT:1094-1107 in p_mean_variance, MT:1183-1196 in ddim_sample).
+ *   DAWN_CLIP_DYNAMIC  s = max(1, quantile_q(|x0|)) over the whole clip, x0 = clamp(x0,-s,s)/s     (use_dynamic_thres = True)
+ *   DAWN_CLIP_STATIC   x0 = clamp(x0,-1,1)                            (use_dynamic_thres = False, the reference's constructor default)
+ *   DAWN_CLIP_NONE     x0 unchanged                                   (ddim_sample(clip_denoised=False); DDIM steps only)
+ * q is read for DAWN_CLIP_DYNAMIC only and must lie in [0, 1]; the rank is q * (n - 1) in fp32 up to 2^24 elements (torch.quantile forms
+ * it in the input dtype), in fp64 above.  STATIC / NONE run the evaluation (a guided one ends in dawn_cfg_combine) and then ONE
+ * dawn_ddim_step_fixed / dawn_ancestral_step_fixed launch per step: no histogram, no selection pass and, T-sharded, none of the four
+ * allreduce_sum_u32 / allreduce_min_u32 calls of the dynamic step tail (those two callbacks may then be NULL). */
+enum { DAWN_CLIP_DYNAMIC = 0, DAWN_CLIP_STATIC = 1, DAWN_CLIP_NONE = 2 };
+typedef struct dawn_clip_mode { int kind; double q; } dawn_clip_mode;
+/* dawn_sampler_run / _sharded / _guided in one entry (guided when null_clip_mem != NULL and cond_scale != 1, T-sharded when comm !=
+ * NULL) with the clipping mode; clip = NULL means {DAWN_CLIP_DYNAMIC, 0.9}, with which the result is bit-identical to those entries.
+ * thresholds (optional, 2 S floats): DYNAMIC [max(1, q-quantile), q-quantile] of every step; STATIC [1, 1] of every step; NONE leaves
+ * the rows untouched.  An unknown kind, a q outside [0, 1] or NaN: error return with a message, nothing launched.  Workspace: the
+ * existing queries, as for dawn_sampler_run_ancestral. */
+int dawn_sampler_run_clip(dawn_ctx* ctx, int F, int h, int w, const void* clip_mem, const void* null_clip_mem, float cond_scale,
+                          const float* x_init, int S, const dawn_ddim_step* steps, uint64_t seed, const float* const* noises,
+                          float* x_out, float* thresholds, void* workspace, size_t workspace_bytes, const dawn_shard_comm* comm,
+                          const dawn_clip_mode* clip, void* stream);
+/* dawn_sampler_run_ancestral with the clipping mode (DAWN_CLIP_NONE is an error here: the reference's p_sample always clips) */
+int dawn_sampler_run_ancestral_clip(dawn_ctx* ctx, int F, int h, int w, const void* clip_mem, const void* null_clip_mem,
+                                    float cond_scale, const float* x_init, int S, const dawn_ancestral_step* steps, uint64_t seed,
+                                    const float* const* noises, float* x_out, float* thresholds, void* workspace,
+                                    size_t workspace_bytes, const dawn_shard_comm* comm, const dawn_clip_mode* clip, void* stream);
 /* after a stream synchronise: (kind, algorithmic flops, algorithmic bytes, ms) per conv launch recorded under
  * DAWN_OPT_PROFILE; kind 0 = split 3x3, 1 = split 1x1, 2 = fp32 MFMA; returns the number of entries (and clears them) */
 int dawn_ctx_profile_read(dawn_ctx* ctx, double* out4, int max_entries);
