@@ -14,6 +14,8 @@
 #include "dawn_common.h"
 #include "../../include/dawn_hip.h"
 
+#include <stdio.h>
+
 namespace {
 
 // F.interpolate(mode='bilinear', align_corners=False) source index and weights for output index `dst`
@@ -166,19 +168,45 @@ __global__ __launch_bounds__(256) void warp_blend_kernel(const float* __restrict
     }
 }
 
+// u8_of: one value of the frame egress (see frames_to_u8_kernel below for the arithmetic it restates)
+__device__ __forceinline__ unsigned u8_of(float x, double m) {
+    float v = (float)((double)x + m);
+    v = fminf(fmaxf(v, 0.0f), 1.0f);
+    return (unsigned)(v * 255.0f);
+}
+
 // ---- final 7x7 conv C->3 + bias, sigmoid, and the last apply_optical against the source image (GEN:163-167), plus the
 // `deformed` output (GEN:152).  Tile = 32 x 16 output pixels of one frame, 256 threads, 2 pixels per thread (rows y and
 // y+8).  The input streams through LDS 8 channels at a time as a zero-padded (16+6) x (32+6) patch laid out
 // [channel quad][pixel][4] (consecutive lanes -> consecutive 16-byte slots: conflict-free b128 reads); the weights
 // [tap][channel quad][3 outputs][4 channels] stay in LDS for the whole block and are read as wave-uniform broadcasts.
+//
+// The kernel is a template over where the result goes; everything up to the blended value is the same source in both forms:
+//   FcOutF32  out_vid / warped_vid planar fp32 (dawn_final_conv_blend);
+//   FcOutU8   the frame egress of dawn_frames_to_u8 applied to the value out_vid would have received, written as (T,H,W,3)
+//             bytes (dawn_final_conv_blend_u8): no fp32 frame goes to memory.  A 32 x 16 tile is 16 rows of 96 contiguous
+//             bytes: they are staged in the patch region of LDS (free once the last channel chunk is consumed) and leave as
+//             24 4-byte stores per row; tiles cut by the image edge store their bytes one by one.
 constexpr int FC_TW = 32, FC_TH = 16, FC_PW = FC_TW + 6, FC_PH = FC_TH + 6, FC_PP = FC_PW * FC_PH;
 
+// The last blend as the fp32 kernel has always evaluated it: two rounded products and a rounded sum.  Spelled out because the
+// compiler's choice between that and a fused multiply-add depends on what consumes the value (it fused in the byte form), and
+// the two forms must produce the same fp32 value bit for bit.
+__device__ __forceinline__ float fc_blend(float wv, float oc, float s) {
+#pragma clang fp contract(off)
+    return wv * oc + s * (1.0f - oc);
+}
+
+struct FcOutF32 { float* out_vid; float* warped_vid; long out_plane; };
+struct FcOutU8 { unsigned char* frames; double m0, m1, m2; int bgr; };
+
+template <class Out>
 __global__ __launch_bounds__(256) void final_conv_blend_kernel(const float* __restrict__ x, int T, int H, int W, int C,
                                                                const float* __restrict__ w7, const float* __restrict__ bias3,
                                                                const float* __restrict__ src, const float* __restrict__ grid,
                                                                long grid_plane, const float* __restrict__ conf, int h, int w,
-                                                               float* __restrict__ out_vid, float* __restrict__ warped_vid,
-                                                               long out_plane) {
+                                                               const Out dst) {
+    constexpr bool U8 = __is_same(Out, FcOutU8);
     extern __shared__ __attribute__((aligned(16))) float sm[];
     float* Ws_ = sm;                                   // [49][C/4][3][4]
     float* Ps = sm + 49 * C * 3;                       // [2][FC_PP][4]
@@ -231,6 +259,9 @@ __global__ __launch_bounds__(256) void final_conv_blend_kernel(const float* __re
     const float* gxp = grid + (long)t * h * w;
     const float* gyp = gxp + grid_plane;
     const float* cfp = conf + (long)t * h * w;
+    unsigned char* tile = reinterpret_cast<unsigned char*>(Ps);      // U8: [FC_TH][FC_TW * 3] bytes
+    const bool full = X0 + FC_TW <= W && Y0 + FC_TH <= H;
+    if constexpr (U8) __syncthreads();                 // last chunk consumed: the patch region becomes the byte tile
 #pragma unroll
     for (int pI = 0; pI < 2; ++pI) {
         const int Y = Y0 + ly + 8 * pI, X = X0 + lx;
@@ -246,8 +277,27 @@ __global__ __launch_bounds__(256) void final_conv_blend_kernel(const float* __re
             for (int k = 0; k < 4; ++k)
                 if (cr.i[k] >= 0) wv += src[(long)ch * H * W + cr.i[k]] * cr.w[k];
             const float s = 1.0f / (1.0f + expf(-(acc[pI][ch] + bias3[ch])));
-            warped_vid[ch * out_plane + o] = wv;
-            out_vid[ch * out_plane + o] = wv * oc + s * (1.0f - oc);
+            const float v = fc_blend(wv, oc, s);
+            if constexpr (!U8) {
+                dst.warped_vid[ch * dst.out_plane + o] = wv;
+                dst.out_vid[ch * dst.out_plane + o] = v;
+            } else {
+                const unsigned char u = (unsigned char)u8_of(v, ch == 0 ? dst.m0 : (ch == 1 ? dst.m1 : dst.m2));
+                const int k = dst.bgr ? 2 - ch : ch;
+                if (full) tile[(ly + 8 * pI) * (FC_TW * 3) + lx * 3 + k] = u;
+                else dst.frames[o * 3 + k] = u;
+            }
+        }
+    }
+    if constexpr (U8) {
+        __syncthreads();
+        if (full) {
+            const unsigned* tw = reinterpret_cast<const unsigned*>(tile);
+            constexpr int RW = FC_TW * 3 / 4;          // 24 words per tile row
+            for (int i = tid; i < FC_TH * RW; i += 256) {
+                const int r = i / RW, c = i - r * RW;
+                reinterpret_cast<unsigned*>(dst.frames + (((long)t * H + Y0 + r) * W + X0) * 3)[c] = tw[i];
+            }
         }
     }
 }
@@ -257,11 +307,6 @@ __global__ __launch_bounds__(256) void final_conv_blend_kernel(const float* __re
 //   frame += mean/255 (float64 add, stored back as float32) ; clip(0,1) ; (frame*255) in float32 ; astype(uint8) = trunc.
 // 4 pixels per thread: three 16-byte plane reads, three packed 4-byte stores; one D2H copy of T*H*W*3 bytes follows
 // instead of the reference's T device->host copies of fp32 frames.
-__device__ __forceinline__ unsigned u8_of(float x, double m) {
-    float v = (float)((double)x + m);
-    v = fminf(fmaxf(v, 0.0f), 1.0f);
-    return (unsigned)(v * 255.0f);
-}
 __global__ __launch_bounds__(256) void frames_to_u8_kernel(const float* __restrict__ vid, long plane, long npix4, double m0,
                                                            double m1, double m2, int bgr, unsigned* __restrict__ out) {
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < npix4; i += (long)gridDim.x * 256) {
@@ -319,20 +364,50 @@ extern "C" int dawn_warp_blend(const float* skip, int Hs, int Ws, int C, const f
     return 0;
 }
 
+namespace {
+template <class Out>
+int launch_final_conv(const char* who, const float* x, int T, int H, int W, int C, const float* w7, const float* bias3,
+                      const float* src, const float* grid, long grid_plane, const float* conf, int h, int w, const Out& dst,
+                      void* stream) {
+    char msg[160];
+    if (C % 8 != 0) {
+        snprintf(msg, sizeof msg, "%s: C must be a multiple of 8", who);
+        return dawn_set_error_msg(-74, msg);
+    }
+    const size_t lds = ((size_t)49 * C * 3 + (size_t)2 * FC_PP * 4) * sizeof(float);
+    if (lds > 160 * 1024) {
+        snprintf(msg, sizeof msg, "%s: C too large for the LDS-resident weights", who);
+        return dawn_set_error_msg(-75, msg);
+    }
+    if (T <= 0) return 0;
+    const long nblk = (long)T * ((H + FC_TH - 1) / FC_TH) * ((W + FC_TW - 1) / FC_TW);
+    if (nblk > 0x7fffffffL) {
+        snprintf(msg, sizeof msg, "%s: too many tiles for one launch", who);
+        return dawn_set_error_msg(-76, msg);
+    }
+    (void)hipFuncSetAttribute((const void*)final_conv_blend_kernel<Out>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(final_conv_blend_kernel<Out>, dim3((unsigned)nblk), dim3(256), lds, (hipStream_t)stream, x, T, H, W, C,
+                       w7, bias3, src, grid, grid_plane, conf, h, w, dst);
+    DAWN_LAUNCH_CHECK();
+    return 0;
+}
+}  // namespace
+
 extern "C" int dawn_final_conv_blend(const float* x, int T, int H, int W, int C, const float* w7, const float* bias3,
                                      const float* src, const float* grid, long grid_plane, const float* conf, int h, int w,
                                      float* out_vid, float* warped_vid, long out_plane, void* stream) {
-    if (C % 8 != 0) return dawn_set_error_msg(-74, "dawn_final_conv_blend: C must be a multiple of 8");
-    const size_t lds = ((size_t)49 * C * 3 + (size_t)2 * FC_PP * 4) * sizeof(float);
-    if (lds > 160 * 1024) return dawn_set_error_msg(-75, "dawn_final_conv_blend: C too large for the LDS-resident weights");
-    if (T <= 0) return 0;
-    const long nblk = (long)T * ((H + FC_TH - 1) / FC_TH) * ((W + FC_TW - 1) / FC_TW);
-    if (nblk > 0x7fffffffL) return dawn_set_error_msg(-76, "dawn_final_conv_blend: too many tiles for one launch");
-    (void)hipFuncSetAttribute((const void*)final_conv_blend_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(final_conv_blend_kernel, dim3((unsigned)nblk), dim3(256), lds, (hipStream_t)stream, x, T, H, W, C, w7,
-                       bias3, src, grid, grid_plane, conf, h, w, out_vid, warped_vid, out_plane);
-    DAWN_LAUNCH_CHECK();
-    return 0;
+    return launch_final_conv("dawn_final_conv_blend", x, T, H, W, C, w7, bias3, src, grid, grid_plane, conf, h, w,
+                             FcOutF32{out_vid, warped_vid, out_plane}, stream);
+}
+
+extern "C" int dawn_final_conv_blend_u8(const float* x, int T, int H, int W, int C, const float* w7, const float* bias3,
+                                        const float* src, const float* grid, long grid_plane, const float* conf, int h, int w,
+                                        double mean0, double mean1, double mean2, int bgr, unsigned char* frames,
+                                        void* stream) {
+    if (W % 4 != 0 || ((uintptr_t)frames & 3) != 0)
+        return dawn_set_error_msg(-78, "dawn_final_conv_blend_u8: W must be a multiple of 4 and frames 4-byte aligned");
+    return launch_final_conv("dawn_final_conv_blend_u8", x, T, H, W, C, w7, bias3, src, grid, grid_plane, conf, h, w,
+                             FcOutU8{frames, mean0, mean1, mean2, bgr}, stream);
 }
 
 extern "C" int dawn_frames_to_u8(const float* vid, long plane, long npix, double mean0, double mean1, double mean2, int bgr,

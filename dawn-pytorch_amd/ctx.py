@@ -1,6 +1,7 @@
 """Python binding of the C-side evaluator (include/dawn_hip.h: dawn_ctx_* / dawn_clip_prepare / dawn_unet_forward /
 dawn_sampler_run(_ancestral); csrc/dawn_ctx.hip) -- what a non-Python host would call, used here by the tests (bit-identical to the
-Python orchestration of unet_forward.py / sampler.py) and optionally by the sampler (`GaussianDiffusion.use_ctx`).
+Python orchestration of unet_forward.py / sampler.py) and optionally by the sampler (`GaussianDiffusion.use_ctx`).  `DecoderEvaluator` at
+the end of the file binds the C-side flow decoder the same way (dawn_decoder_* / dawn_decode_clip; `FlowDecoder.use_ctx`).
 
 PyTorch only provides device memory (the packed weights, the per-clip table memory, the workspace) and the stream."""
 from __future__ import annotations
@@ -450,3 +451,135 @@ class CtxEvaluator:
         n = int(self.L.dawn_ctx_profile_read(self.h, buf, 65536))
         n = min(n, 65536)
         return [(int(buf[4 * i]), buf[4 * i + 1], buf[4 * i + 2], buf[4 * i + 3]) for i in range(n)]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# C-side flow decoder (include/dawn_hip.h: dawn_decoder_* / dawn_decode_clip; csrc/dawn_decoder.hip)
+class DecoderCfg(C.Structure):
+    """Mirror of ``dawn_decoder_cfg``."""
+    _fields_ = [("n_down", C.c_int), ("n_bottleneck", C.c_int), ("widths", C.c_int * 8)]
+
+
+def decoder_named_weights(dec) -> Dict[str, Tensor]:
+    """flow_decoder.FlowDecoder -> {name: device tensor} in the naming scheme of include/dawn_hip.h (decoder section)."""
+    out: Dict[str, Tensor] = {"first_w3": dec.first_w3, "first_bias": dec.first_bias, "first.a": dec.first_ab[0],
+                              "first.b": dec.first_ab[1], "final_w7": dec.final_w7, "final_bias": dec.final_bias}
+
+    def conv(p: str, c):
+        out[p + "w"], out[p + "bias"] = c.w, c.bias
+        if c.ws is not None:
+            out[p + "ws"] = c.ws
+        if c.a is not None:
+            out[p + "a"], out[p + "b"] = c.a, c.b
+
+    for i, c in enumerate(dec.downs):
+        conv(f"downs.{i}.", c)
+    for i, c in enumerate(dec.ups):
+        conv(f"ups.{i}.", c)
+    for i, (ab1, c1, ab2, c2) in enumerate(dec.bott):
+        out[f"bott.{i}.a1"], out[f"bott.{i}.b1"], out[f"bott.{i}.a2"], out[f"bott.{i}.b2"] = ab1[0], ab1[1], ab2[0], ab2[1]
+        conv(f"bott.{i}.c1.", c1)
+        conv(f"bott.{i}.c2.", c2)
+    return out
+
+
+class DecoderEvaluator:
+    """One `dawn_decoder` for one `FlowDecoder` on one device: what a non-Python host would call to turn the sampler's latent into
+    frames.  PyTorch provides the device memory (packed weights, skip memory, workspace, outputs) and the stream.  `weights` lets a
+    test hand in an edited table (a missing name must be an error)."""
+
+    def __init__(self, dec, weights: Optional[Dict[str, Tensor]] = None):
+        self.L = _lib.lib()
+        self.device = dec.first_w3.device
+        self.weights = decoder_named_weights(dec) if weights is None else dict(weights)      # keeps every tensor alive
+        cfg = DecoderCfg()
+        cfg.n_down, cfg.n_bottleneck = len(dec.downs), len(dec.bott)
+        cfg.widths[0] = dec.C0
+        for i, c in enumerate(dec.downs):
+            cfg.widths[i + 1] = c.N
+        self.cfg = cfg
+        arr = (NamedPtr * max(1, len(self.weights)))()
+        self._names = [k.encode() for k in self.weights]
+        for i, (k, t) in enumerate(self.weights.items()):
+            if not t.is_cuda or not t.is_contiguous():
+                raise _lib.DawnHipError(f"packed weight {k} must be a contiguous GPU tensor")
+            arr[i].name, arr[i].ptr = self._names[i], t.data_ptr()
+        h = C.c_void_p()
+        check(self.L.dawn_decoder_create(C.addressof(cfg), C.addressof(arr), len(self.weights), C.addressof(h)), "dawn_decoder_create")
+        self.h = h
+        self._ws: Optional[Tensor] = None
+
+    def __del__(self):
+        h, self.h = getattr(self, "h", None), None
+        if h:
+            self.L.dawn_decoder_destroy(h)
+
+    @staticmethod
+    def _stream() -> int:
+        return torch.cuda.current_stream().cuda_stream
+
+    def workspace_bytes(self, H: int, W: int, chunk: int) -> int:
+        return int(self.L.dawn_decoder_workspace_bytes(self.h, H, W, chunk))
+
+    def workspace(self, H: int, W: int, chunk: int) -> Tensor:
+        need = self.workspace_bytes(H, W, chunk)
+        if need == 0:
+            raise _lib.DawnHipError(f"dawn_decoder_workspace_bytes: {self.L.dawn_last_error().decode()}")
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = None
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self._ws
+
+    def encode(self, img: Tensor, want_fea: bool = False):
+        """img (3,H,W) fp32 contiguous -> (skip memory, fea (Cb,H/k,W/k) or None)."""
+        _, H, W = img.shape
+        if not (img.is_cuda and img.is_contiguous() and img.dtype == torch.float32 and img.shape[0] == 3):
+            raise _lib.DawnHipError("DecoderEvaluator.encode: img must be a contiguous fp32 GPU tensor (3,H,W)")
+        nb = int(self.L.dawn_decoder_skip_bytes(self.h, H, W))
+        if nb == 0:
+            raise _lib.DawnHipError(f"dawn_decoder_skip_bytes: {self.L.dawn_last_error().decode()}")
+        mem = torch.empty(nb, dtype=torch.uint8, device=self.device)
+        k = 1 << self.cfg.n_down
+        fea = torch.empty(self.cfg.widths[self.cfg.n_down], H // k, W // k, device=self.device) if want_fea else None
+        ws = self.workspace(H, W, 1)
+        check(self.L.dawn_decoder_encode(self.h, H, W, img.data_ptr(), mem.data_ptr(), nb, None if fea is None else fea.data_ptr(),
+                                         ws.data_ptr(), ws.numel(), self._stream()), "dawn_decoder_encode")
+        return mem, fea
+
+    def decode(self, img: Tensor, skip_mem: Tensor, *, T: int, h: int, w: int, chunk: int, latent: Optional[Tensor] = None,
+               grid: Optional[Tensor] = None, conf: Optional[Tensor] = None, out_vid: Optional[Tensor] = None,
+               warped_vid: Optional[Tensor] = None, frames: Optional[Tensor] = None, mean=(0.0, 0.0, 0.0), bgr: bool = False,
+               workspace: Optional[Tensor] = None) -> None:
+        """One clip: `latent` (3,T,h,w) as the sampler returns it, or `grid` (2,T,h,w) + `conf` (T,h,w).  Planes may be strided (a
+        frame range of a longer clip); rows and frames must be dense.  out_vid / warped_vid: (3,T,H,W) views with dense frames;
+        frames: (T,H,W,3) uint8 contiguous."""
+        _, H, W = img.shape
+        g = latent if latent is not None else grid
+        if not (g is not None and g.is_cuda and g.dtype == torch.float32 and tuple(g.shape[1:]) == (T, h, w)
+                and g.stride(3) == 1 and g.stride(2) == w and g.stride(1) == h * w and g.shape[0] == (3 if latent is not None else 2)):
+            raise _lib.DawnHipError("DecoderEvaluator.decode: latent (3,T,h,w) / grid (2,T,h,w) must be fp32 GPU planes with dense frames")
+        if latent is None and not (conf is not None and conf.is_cuda and conf.is_contiguous() and tuple(conf.shape) == (T, h, w)
+                                   and conf.dtype == torch.float32):
+            raise _lib.DawnHipError("DecoderEvaluator.decode: conf must be a contiguous fp32 GPU tensor (T,h,w)")
+        plane = 0
+        for o in (out_vid, warped_vid):
+            if o is not None:
+                if not (o.is_cuda and o.dtype == torch.float32 and tuple(o.shape) == (3, T, H, W) and o.stride(3) == 1
+                        and o.stride(2) == W and o.stride(1) == H * W):
+                    raise _lib.DawnHipError("DecoderEvaluator.decode: out_vid / warped_vid must be fp32 (3,T,H,W) with dense frames")
+                plane = o.stride(0)
+        if out_vid is not None and warped_vid is not None and out_vid.stride(0) != warped_vid.stride(0):
+            raise _lib.DawnHipError("DecoderEvaluator.decode: out_vid and warped_vid must share their plane stride")
+        if frames is not None and not (frames.is_cuda and frames.dtype == torch.uint8 and frames.is_contiguous()
+                                       and tuple(frames.shape) == (T, H, W, 3)):
+            raise _lib.DawnHipError("DecoderEvaluator.decode: frames must be a contiguous uint8 GPU tensor (T,H,W,3)")
+        ws = workspace if workspace is not None else self.workspace(H, W, max(1, min(chunk, T)))
+        m = (C.c_double * 3)(*[float(v) / 255.0 for v in mean])
+        p = lambda t: None if t is None else t.data_ptr()      # noqa: E731
+        tail = (chunk, p(out_vid), p(warped_vid), plane, p(frames), m, 1 if bgr else 0, ws.data_ptr(), ws.numel(), self._stream())
+        if latent is not None:
+            check(self.L.dawn_decode_clip(self.h, H, W, T, h, w, img.data_ptr(), skip_mem.data_ptr(), latent.data_ptr(),
+                                          latent.stride(0), *tail), "dawn_decode_clip")
+        else:
+            check(self.L.dawn_decode_clip_conf(self.h, H, W, T, h, w, img.data_ptr(), skip_mem.data_ptr(), grid.data_ptr(),
+                                               grid.stride(0), conf.data_ptr(), *tail), "dawn_decode_clip_conf")

@@ -12,7 +12,10 @@ What changes relative to the reference's execution (results are the same within 
     kernel that consumes it (`warp_blend(prev_ab=...)`), which also performs the occlusion blend (GEN:80-87), the
     flow / occlusion resize (GEN:65-68, 81-82) and the next block's nearest x2 upsampling (UTIL:106);
   * every 3x3 convolution runs through `dawn_conv_gemm` (split-operand bf16 MFMA kernel, fp32-accurate);
-  * the final 7x7 conv, sigmoid, last blend and the `deformed` output are one kernel writing (3,T,H,W) directly.
+  * the final 7x7 conv, sigmoid, last blend and the `deformed` output are one kernel writing (3,T,H,W) directly -- or, for the
+    byte outputs (`decode_clip_u8`, `stream_frames_u8`), the same kernel writing (T,H,W,3) uint8 frames with no fp32 clip at all.
+
+`use_ctx = True` hands the same launch sequence to the C-side decoder (include/dawn_hip.h: dawn_decoder_*, dawn_decode_clip).
 """
 from __future__ import annotations
 
@@ -141,14 +144,20 @@ class FlowDecoder:
         k = 1 << len(self.downs)
         outs = []
         for b in range(B):
+            if self._via_ctx(source_image):
+                outs.append(self._evaluator().encode(source_image[b].float().contiguous(), want_fea=True)[1])
+                continue
             f = self.encode(source_image[b])[-1]
             outs.append(f.view(H // k, W // k, -1).permute(2, 0, 1))
         return torch.stack(outs, 0).contiguous()
 
     # ------------------------------------------------------------------ decoder
-    def _decode_frames(self, skips: List[Tensor], src: Tensor, H: int, W: int, g: Tensor, cf: Tensor, out_vid: Tensor,
-                       warped_vid: Tensor) -> None:
-        """g (2,n,h,w) view, cf (n,h,w); writes out_vid / warped_vid (3,n,H,W) views.  GEN:152-167."""
+    def _decode_frames(self, skips: List[Tensor], src: Tensor, H: int, W: int, g: Tensor, cf: Tensor, out_vid: Optional[Tensor],
+                       warped_vid: Optional[Tensor], frames: Optional[Tensor] = None, mean=(0.0, 0.0, 0.0),
+                       bgr: bool = False) -> None:
+        """g (2,n,h,w) view, cf (n,h,w); writes out_vid / warped_vid (3,n,H,W) views and / or frames (n,H,W,3) uint8.  GEN:152-167.
+        With `frames` alone the last launch is the fused final_conv_blend_u8 where the op set has it (no fp32 frame is written);
+        otherwise final_conv_blend followed by frames_to_u8 on the chunk -- which is also the definition of the fused op's result."""
         ops = self.ops
         n = g.shape[1]
         k = 1 << len(self.downs)
@@ -166,7 +175,43 @@ class FlowDecoder:
             prev = self._conv3(u, up, n, Hc, Wc)                                    # UTIL:107; its BN+ReLU ride on the consumer
             prev_ab = (up.a, up.b)
         xf = ops.warp_blend(skips[0], H, W, g, cf, prev=prev, prev_ab=prev_ab)      # GEN:161-162
+        if frames is not None and out_vid is None and hasattr(ops, "final_conv_blend_u8"):
+            ops.final_conv_blend_u8(xf, H, W, self.final_w7, self.final_bias, src, g, cf, frames, mean=mean, bgr=bgr)
+            return
+        if out_vid is None:
+            out_vid = torch.empty(3, n, H, W, device=xf.device, dtype=torch.float32)
+            warped_vid = torch.empty_like(out_vid)
         ops.final_conv_blend(xf, H, W, self.final_w7, self.final_bias, src, g, cf, out_vid, warped_vid)   # GEN:163-167, 152
+        if frames is not None:
+            frames.copy_(ops.frames_to_u8(out_vid, mean=mean, bgr=bgr))
+
+    # ---- the two hosts of the launch sequence: this file's orchestration, or the C-side decoder (use_ctx; ctx.DecoderEvaluator)
+    use_ctx = False      # True: GPU clips go through dawn_decoder_encode / dawn_decode_clip (bit-identical to the orchestration here)
+
+    def _evaluator(self):
+        if getattr(self, "_ctx_eval", None) is None:
+            from .ctx import DecoderEvaluator
+            self._ctx_eval = DecoderEvaluator(self)
+        return self._ctx_eval
+
+    def _via_ctx(self, t: Tensor) -> bool:
+        return bool(self.use_ctx) and t.is_cuda
+
+    def _begin_clip(self, src: Tensor):
+        """Once per clip: the encoder skips, as a list (orchestration here) or as the C-side decoder's skip memory."""
+        if self._via_ctx(src):
+            return self._evaluator().encode(src)[0]
+        return self.encode(src)
+
+    def _chunk(self, state, src: Tensor, H: int, W: int, g: Tensor, cf: Tensor, out_vid: Optional[Tensor],
+               warped_vid: Optional[Tensor], frames: Optional[Tensor] = None, mean=(0.0, 0.0, 0.0), bgr: bool = False,
+               chunk: Optional[int] = None) -> None:
+        """Frames of g / cf (any number: the C side splits them into chunks itself) into the given outputs."""
+        if isinstance(state, list):
+            return self._decode_frames(state, src, H, W, g, cf, out_vid, warped_vid, frames, mean, bgr)
+        _, n, h, w = g.shape
+        self._evaluator().decode(src, state, T=n, h=h, w=w, chunk=chunk or n, grid=g, conf=cf, out_vid=out_vid,
+                                 warped_vid=warped_vid, frames=frames, mean=mean, bgr=bgr)
 
     @torch.no_grad()
     def decode_clip(self, sample_img: Tensor, grid: Tensor, conf: Tensor, chunk: Optional[int] = None) -> Dict[str, Tensor]:
@@ -181,12 +226,91 @@ class FlowDecoder:
         warped = torch.empty_like(out_vid)
         for b in range(B):
             src = sample_img[b].float().contiguous()
-            skips = self.encode(src)
+            state = self._begin_clip(src)
+            if not isinstance(state, list):                                         # C side: one call, it runs the chunk loop
+                self._chunk(state, src, H, W, grid[b], conf[b, 0], out_vid[b], warped[b], chunk=chunk)
+                continue
             for t0 in range(0, T, chunk):
                 t1 = min(T, t0 + chunk)
-                self._decode_frames(skips, src, H, W, grid[b, :, t0:t1], conf[b, 0, t0:t1], out_vid[b, :, t0:t1],
+                self._decode_frames(state, src, H, W, grid[b, :, t0:t1], conf[b, 0, t0:t1], out_vid[b, :, t0:t1],
                                     warped[b, :, t0:t1])
         return {"sample_out_vid": out_vid, "sample_warped_vid": warped}
+
+    @torch.no_grad()
+    def decode_clip_u8(self, sample_img: Tensor, grid: Tensor, conf: Tensor, *, mean=(0.0, 0.0, 0.0), bgr: bool = False,
+                       chunk: Optional[int] = None) -> Tensor:
+        """decode_clip + the frame egress without the fp32 clips: -> (B,T,H,W,3) uint8 on the inputs' device, byte
+        for byte `ops.frames_to_u8(decode_clip(...)["sample_out_vid"][b], mean, bgr)`.  `mean` = the config's 0..255 offsets."""
+        B, _, T, h, w = grid.shape
+        _, _, H, W = sample_img.shape
+        chunk = chunk or self.chunk
+        grid = grid.float().contiguous()
+        conf = conf.float().contiguous()
+        out = torch.empty(B, T, H, W, 3, device=grid.device, dtype=torch.uint8)
+        for b in range(B):
+            src = sample_img[b].float().contiguous()
+            state = self._begin_clip(src)
+            if not isinstance(state, list):
+                self._chunk(state, src, H, W, grid[b], conf[b, 0], None, None, out[b], mean, bgr, chunk=chunk)
+                continue
+            for t0 in range(0, T, chunk):
+                t1 = min(T, t0 + chunk)
+                self._decode_frames(state, src, H, W, grid[b, :, t0:t1], conf[b, 0, t0:t1], None, None, out[b, t0:t1], mean, bgr)
+        return out
+
+    @torch.no_grad()
+    def stream_frames_u8(self, sample_img: Tensor, grid: Tensor, conf: Tensor, *, mean=(0.0, 0.0, 0.0), bgr: bool = False,
+                         chunk: Optional[int] = None, item: int = 0):
+        """Generator over the chunks of batch item `item`: yields (t0, frames) with frames a host ndarray (n,H,W,3) uint8, the bytes
+        of decode_clip_u8 for the frames [t0, t0 + n), in order.  On the GPU the device->host copy of a chunk runs on a side stream
+        into pinned memory while the next chunk decodes; the consumer waits for that chunk's copy event only (no device-wide
+        synchronise), and no clip-sized tensor exists on the device: two chunk-sized byte buffers plus the chunk's activations.
+        A YIELDED ARRAY IS VALID UNTIL THE NEXT `next()` ONLY: it aliases one of two pinned staging buffers, which the chunk after
+        the next one overwrites -- copy it if it has to live longer.  CPU tensors: the plain loop, every chunk its own array."""
+        _, _, T, h, w = grid.shape
+        _, _, H, W = sample_img.shape
+        chunk = max(1, min(chunk or self.chunk, T))
+        g = grid[item].float().contiguous()
+        cf = conf[item, 0].float().contiguous()
+        src = sample_img[item].float().contiguous()
+        state = self._begin_clip(src)
+        spans = [(t0, min(T, t0 + chunk)) for t0 in range(0, T, chunk)]
+        if not g.is_cuda:
+            for t0, t1 in spans:
+                fr = torch.empty(t1 - t0, H, W, 3, dtype=torch.uint8)
+                self._chunk(state, src, H, W, g[:, t0:t1], cf[t0:t1], None, None, fr, mean, bgr)
+                yield t0, fr.numpy()
+            return
+        main = torch.cuda.current_stream(g.device)
+        side = torch.cuda.Stream(device=g.device)
+        dev = [torch.empty(chunk, H, W, 3, device=g.device, dtype=torch.uint8) for _ in range(2)]
+        host = [torch.empty(chunk, H, W, 3, dtype=torch.uint8, pin_memory=True) for _ in range(2)]
+        copied = [None, None]                          # event of the last copy out of dev[k] / into host[k]
+        pending = None
+        try:
+            for i, (t0, t1) in enumerate(spans):
+                k, n = i & 1, t1 - t0
+                if copied[k] is not None:
+                    main.wait_event(copied[k])         # dev[k] is free once chunk i - 2 has left it
+                self._chunk(state, src, H, W, g[:, t0:t1], cf[t0:t1], None, None, dev[k][:n], mean, bgr)
+                decoded = torch.cuda.Event()
+                decoded.record(main)
+                with torch.cuda.stream(side):
+                    side.wait_event(decoded)
+                    host[k][:n].copy_(dev[k][:n], non_blocking=True)
+                    copied[k] = torch.cuda.Event()
+                    copied[k].record(side)
+                if pending is not None:                # hand out chunk i - 1 while chunk i decodes
+                    pt0, pn, pk = pending
+                    copied[pk].synchronize()
+                    yield pt0, host[pk][:pn].numpy()
+                pending = (t0, n, k)
+            if pending is not None:
+                pt0, pn, pk = pending
+                copied[pk].synchronize()
+                yield pt0, host[pk][:pn].numpy()
+        finally:
+            side.synchronize()                         # an abandoned generator must not free buffers under a copy in flight
 
     @torch.no_grad()
     def forward_with_flow(self, source_image: Tensor, optical_flow: Tensor, occlusion_map: Tensor) -> Dict[str, Tensor]:

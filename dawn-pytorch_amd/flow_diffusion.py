@@ -98,6 +98,13 @@ class FlowDiffusion(nn.Module):
             self._decoder = FlowDecoder.from_generator(self.generator, device)
         return self._decoder
 
+    def decodes_natively(self, sample_img) -> bool:
+        """Does sample_one_video decode this clip with `FlowDecoder` (rather than frame by frame through the injected generator)?"""
+        native = self.native_decode
+        if native is None:
+            native = sample_img.is_cuda and (self._decoder is not None or hasattr(self.generator, "state_dict"))
+        return bool(native)
+
     def generate_bbox_mask(self, bbox, size=32):
         """FD:182-201.  bbox (B,6,1) = [x_min,x_max,y_min,y_max,H,W].  Unlike the reference this does not
         rescale the caller's tensor in place and indexes with int32 (the reference's uint8 indices wrap
@@ -130,8 +137,11 @@ class FlowDiffusion(nn.Module):
 
     @torch.no_grad()
     def sample_one_video(self, sample_img, sample_audio_hubert, sample_pose, sample_eye, sample_bbox, cond_scale,
-                         init_pose=None, init_eye=None, real_vid=None):
-        """FD:325-406."""
+                         init_pose=None, init_eye=None, real_vid=None, frames_u8: Optional[dict] = None):
+        """FD:325-406.  `frames_u8` (not in the reference): None = the fp32 clips as always; dict(mean=(0,0,0), bgr=False, chunk=None,
+        stream=False) = decode straight to bytes instead (native decode only): out["sample_frames_u8"] is the (B,T,H,W,3) uint8
+        device tensor of FlowDecoder.decode_clip_u8 -- or, with stream=True (B == 1), the chunk generator of
+        FlowDecoder.stream_frames_u8 -- and "sample_out_vid" / "sample_warped_vid" are never materialised."""
         out = {}
         fea = self.generator.compute_fea(sample_img)                                   # (B,256,h,w)  GEN:132-136
         bbox_mask = self.face_loc_emb(self.generate_bbox_mask(sample_bbox, size=sample_img.shape[-1]))
@@ -141,9 +151,18 @@ class FlowDiffusion(nn.Module):
         out["sample_vid_grid"] = pred[:, :2]
         out["sample_vid_conf"] = (pred[:, 2].unsqueeze(1) + 1) * 0.5
         out["ddim_seconds"] = time.time() - t0
-        native = self.native_decode
-        if native is None:
-            native = sample_img.is_cuda and (self._decoder is not None or hasattr(self.generator, "state_dict"))
+        native = self.decodes_natively(sample_img)
+        if frames_u8 is not None:
+            if not native:
+                raise ValueError("sample_one_video(frames_u8=...) needs the native flow decode (native_decode, or a clip on the GPU)")
+            kw = dict(frames_u8)
+            stream = kw.pop("stream", False)
+            dec = self.flow_decoder(sample_img.device)
+            if stream and sample_img.shape[0] != 1:
+                raise ValueError("frames_u8 stream=True takes one clip (B == 1)")
+            fn = dec.stream_frames_u8 if stream else dec.decode_clip_u8
+            out["sample_frames_u8"] = fn(sample_img, out["sample_vid_grid"], out["sample_vid_conf"], **kw)
+            return out
         if native:                                                                     # FD:372-385 as one batched decode
             out.update(self.flow_decoder(sample_img.device).decode_clip(sample_img, out["sample_vid_grid"],
                                                                         out["sample_vid_conf"]))

@@ -722,6 +722,21 @@ class HipOps:
                                            _p(conf), h, w, _p(out_vid), _p(warped_vid), out_vid.stride(0),
                                            self._stream()), "dawn_final_conv_blend")
 
+    def final_conv_blend_u8(self, x: Tensor, H: int, W: int, w7: Tensor, bias3: Tensor, src: Tensor, grid: Tensor,
+                            conf: Tensor, frames: Tensor, mean=(0.0, 0.0, 0.0), bgr: bool = False) -> None:
+        """final_conv_blend with frames_to_u8 as its store: frames (T,H,W,3) uint8 (contiguous; a frame range of a longer clip is
+        fine) receives the bytes frames_to_u8 would make of final_conv_blend's out_vid, bit for bit; no fp32 frame is written."""
+        _, T, h, w = grid.shape
+        Cc = x.shape[1]
+        _need(x.is_contiguous() and x.shape[0] == T * H * W and src.is_contiguous() and src.shape == (3, H, W), "final_conv_blend_u8: x.is_contiguous() and x.shape[0] == T * H * W and src.is_contiguous() and src.shape == (3, H, W)")
+        _need(grid.stride(3) == 1 and grid.stride(2) == w and grid.stride(1) == h * w and conf.is_contiguous(), "final_conv_blend_u8: grid.stride(3) == 1 and grid.stride(2) == w and grid.stride(1) == h * w and conf.is_contiguous()")
+        _need(frames.dtype == torch.uint8 and frames.shape == (T, H, W, 3) and frames.is_contiguous(), "final_conv_blend_u8: frames.dtype == torch.uint8 and frames.shape == (T, H, W, 3) and frames.is_contiguous()")
+        self._require(x, w7, bias3, src, grid, conf, frames)
+        m = [float(v) / 255.0 for v in mean]
+        check(self.L.dawn_final_conv_blend_u8(_p(x), T, H, W, Cc, _p(w7), _p(bias3), _p(src), _p(grid), grid.stride(0), _p(conf),
+                                              h, w, m[0], m[1], m[2], 1 if bgr else 0, _p(frames), self._stream()),
+              "dawn_final_conv_blend_u8")
+
     # ------------------------------------------------------------------ frame egress (SURVEY 8f N2)
     def frames_to_u8(self, vid: Tensor, mean=(0.0, 0.0, 0.0), bgr: bool = False) -> Tensor:
         """(3,T,H,W) fp32 in [0,1] -> (T,H,W,3) uint8 with `_process_output_frame`'s arithmetic (UVG:533-548):

@@ -22,6 +22,29 @@ import yaml
 from .flow_diffusion import FlowDiffusion
 
 
+class _LastOutput(dict):
+    """`VideoGenerator.last_output` after a streamed decode.  The streaming path never materialises the fp32 clips, so
+    "sample_out_vid" / "sample_warped_vid" are not stored; `out[key]`, `key in out` and `out.get(key)` answer for them all the same, by
+    running `VideoGenerator.decode_last_clips()` once and keeping its result.  `keys()` and iteration list what is stored."""
+    LAZY = ("sample_out_vid", "sample_warped_vid")
+
+    def __init__(self, out, decode):
+        super().__init__(out)
+        self._decode = decode
+
+    def __missing__(self, key):
+        if key not in self.LAZY:
+            raise KeyError(key)
+        self.update(self._decode())
+        return dict.__getitem__(self, key)
+
+    def __contains__(self, key):
+        return key in self.LAZY or dict.__contains__(self, key)
+
+    def get(self, key, default=None):
+        return self[key] if key in self else default
+
+
 class VideoGenerator:
     def __init__(self, args, *, generator=None, frontend=None, config: Optional[dict] = None, device=None,
                  allow_random_weights: bool = False, deterministic: bool = True, hubert=None, pbnet=None):
@@ -149,20 +172,33 @@ class VideoGenerator:
         init_blink = real_bb[0, :2].unsqueeze(0)
         poses, blink, real_bb = poses.permute(1, 0), blink.permute(1, 0), real_bb.permute(1, 0)
         dev = self.device
+        mean = tuple(cfg.get('mean', (0, 0, 0)))
+        sample_img = image_tensor.unsqueeze(0).to(dev) / 255.
+        stream = self.video_model.decodes_natively(sample_img)
         with torch.no_grad():
             self.video_model.update_num_frames(T)
             out = self.video_model.sample_one_video(
-                sample_img=image_tensor.unsqueeze(0).to(dev) / 255., sample_audio_hubert=ref_hubert.unsqueeze(0).to(dev),
+                sample_img=sample_img, sample_audio_hubert=ref_hubert.unsqueeze(0).to(dev),
                 sample_pose=poses.unsqueeze(0).to(dev), sample_eye=blink[:2].unsqueeze(0).to(dev),
                 sample_bbox=real_bb[2:].unsqueeze(0).to(dev), init_pose=init_pose.to(dev), init_eye=init_blink.to(dev),
-                cond_scale=cfg['cond_scale'])
-        # frame egress (UVG:383-397 + `_process_output_frame` UVG:533-548): one conversion launch for the whole clip
-        # ((3,T,H,W) fp32 -> (T,H,W,3) uint8, numpy's exact arithmetic) and ONE device->host copy, instead of T copies
-        # of fp32 frames converted on the host.  RGB order here (PIL); `bgr=True` gives cv2's order.
-        frames = self.video_model.unet._ops().frames_to_u8(out["sample_out_vid"][0].float().contiguous(),
-                                                           mean=tuple(cfg.get('mean', (0, 0, 0))), bgr=False).cpu().numpy()
-        for i, fr in enumerate(frames):
-            Image.fromarray(fr).save(os.path.join(img_dir, f"{i:03d}.png"))
+                cond_scale=cfg['cond_scale'], frames_u8=dict(mean=mean, bgr=False, stream=True) if stream else None)
+        # frame egress (UVG:383-397 + `_process_output_frame` UVG:533-548), RGB order here (PIL); `bgr=True` gives cv2's order.
+        if stream:
+            # native decode: the decoder's last kernel writes the (T,H,W,3) bytes itself (numpy's exact arithmetic), chunk by chunk;
+            # each chunk's device->host copy and PNG encoding overlap the decode of the next one, and no fp32 clip is materialised
+            frames = np.empty((T, size, size, 3), dtype=np.uint8)
+            for t0, chunk in out.pop("sample_frames_u8"):
+                frames[t0:t0 + len(chunk)] = chunk
+                for i, fr in enumerate(chunk, start=t0):
+                    Image.fromarray(fr).save(os.path.join(img_dir, f"{i:03d}.png"))
+            self._last_clip = (sample_img, out["sample_vid_grid"], out["sample_vid_conf"])
+            out = _LastOutput(out, self.decode_last_clips)
+        else:
+            # the injected generator decoded frame by frame: one conversion launch for the whole clip and ONE device->host copy
+            frames = self.video_model.unet._ops().frames_to_u8(out["sample_out_vid"][0].float().contiguous(), mean=mean,
+                                                               bgr=False).cpu().numpy()
+            for i, fr in enumerate(frames):
+                Image.fromarray(fr).save(os.path.join(img_dir, f"{i:03d}.png"))
         self.last_output = out
         mp4 = os.path.join(video_dir, f"{name}.mp4")
         try:                                                                                 # UVG:566-586 (ffmpeg mux)
@@ -174,6 +210,12 @@ class VideoGenerator:
         except FileNotFoundError:
             pass
         return frames
+
+    def decode_last_clips(self):
+        """The fp32 clips {"sample_out_vid", "sample_warped_vid"} (B,3,T,H,W) of the last streamed `generate_final_video`: that
+        path writes bytes only, so they cost one more decode of the clip, run here on request (`last_output[...]` asks for it)."""
+        img, grid, conf = self._last_clip
+        return self.video_model.flow_decoder(img.device).decode_clip(img, grid, conf)
 
     def run(self):
         """UVG:402-414."""

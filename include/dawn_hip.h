@@ -366,6 +366,13 @@ int dawn_final_conv_blend(const float* x, int T, int H, int W, int C, const floa
  * BGR (bgr != 0: cv2.cvtColor(RGB2BGR) for cv2.VideoWriter / imwrite).  mean0..2 = the caller's mean_c/255 as doubles. */
 int dawn_frames_to_u8(const float* vid, long plane, long npix, double mean0, double mean1, double mean2, int bgr,
                       unsigned char* out, void* stream);
+/* dawn_final_conv_blend with the egress above as its store: frames (T,H,W,3) uint8 receives, for every pixel and channel, exactly the
+ * byte dawn_frames_to_u8 would make of the value dawn_final_conv_blend writes to out_vid (same kernel source up to the blended fp32
+ * value, then the same u8 function); no fp32 frame is written, `deformed` is not produced.  Frame t of the launch goes to
+ * frames + t*H*W*3.  W % 4 == 0 and a 4-byte aligned `frames` (rows leave as 4-byte stores): error otherwise, nothing launched. */
+int dawn_final_conv_blend_u8(const float* x, int T, int H, int W, int C, const float* w7, const float* bias3,
+                             const float* src, const float* grid, long grid_plane, const float* conf, int h, int w,
+                             double mean0, double mean1, double mean2, int bgr, unsigned char* frames, void* stream);
 
 /* ---- HuBERT audio features + 25 fps interpolation (UVG:202-250, 433-501; transformers.HubertModel with
  * feat_extract_norm = "layer", do_stable_layer_norm = True = hubert-large-ls960-ft).  Activations are (time, channels)
@@ -395,7 +402,9 @@ int dawn_attn_bias32(const float* q, int ldq, const float* k, int ldk, const flo
                      void* stream);
 
 /* ---- whole-path entry points (C-side evaluator, csrc/dawn_ctx.hip) ----------------------------------
- * A host in any language runs the denoiser with these five calls; the Python package keeps its own orchestration
+ * A host in any language runs the denoiser with these five calls (create, prepare, forward or sampler_run, destroy, plus the two
+ * size queries) and turns its latent into frames with the decoder entries further down (dawn_decoder_create, dawn_decoder_encode,
+ * dawn_decode_clip: sampler -> decode -> bytes without Python); the Python package keeps its own orchestration
  * (unet_forward.py, needed for the T-sharded path) and the GPU tests require both to agree bit for bit.
  *   dawn_ctx_create    packed weights (device pointers by name, layouts of pack.py) + architecture -> opaque ctx
  *   dawn_clip_prepare  per-clip tables (hoisted out of the DDIM loop: fea part of init_conv, condition -> k/v tables,
@@ -538,6 +547,54 @@ int dawn_sampler_run_ancestral_clip(dawn_ctx* ctx, int F, int h, int w, const vo
                                     float cond_scale, const float* x_init, int S, const dawn_ancestral_step* steps, uint64_t seed,
                                     const float* const* noises, float* x_out, float* thresholds, void* workspace,
                                     size_t workspace_bytes, const dawn_shard_comm* comm, const dawn_clip_mode* clip, void* stream);
+/* ---- SURVEY 8(f) N1 + N2 as a whole path: the LFG flow decode of a sampled clip, down to uint8 frames (csrc/dawn_decoder.hip).
+ * The same launch sequence as dawn-pytorch_amd/flow_decoder.py (FlowDecoder.encode / _decode_frames / decode_clip), results bit-identical
+ * to it (tests/test_hip_decode_u8.py).  Same contract as dawn_ctx: opaque handle, device pointers by name, caller-owned memory, every
+ * launch on `stream`, no allocation, no synchronisation.  The decoder is immutable after creation (the size queries are pure functions).
+ *   dawn_decoder_create   packed weights + topology -> opaque decoder
+ *   dawn_decoder_encode   once per clip: source image -> encoder skips (GEN:140-146) and, optionally, `fea` for dawn_clip_prepare
+ *   dawn_decode_clip      the sampler's latent (3,T,h,w) -> fp32 clips and / or (T,H,W,3) uint8 frames, chunk by chunk
+ * Weight names = the packed fields FlowDecoder.__init__ builds (i = block index; <conv> = w | ws | bias, `ws` = the pack_bf3 image,
+ * optional, absent when 9 * Cin % 16 != 0):
+ *   "first_w3" (147, C0)   "first_bias" (C0)   "first.a" "first.b" (C0)                      first 7x7 conv, its BatchNorm as a / b
+ *   "downs.i.<conv>" "downs.i.a" "downs.i.b"                                                  DownBlock2d i: 3x3 conv, BatchNorm
+ *   "bott.i.a1" "bott.i.b1" "bott.i.c1.<conv>" "bott.i.a2" "bott.i.b2" "bott.i.c2.<conv>"     ResBlock2d i
+ *   "ups.i.<conv>" "ups.i.a" "ups.i.b"                                                        UpBlock2d i
+ *   "final_w7" [49][C0/4][3][4]   "final_bias" (3)                                           final 7x7 conv */
+typedef struct dawn_decoder dawn_decoder;
+typedef struct dawn_decoder_cfg {
+    int n_down;              /* DownBlock2d count = UpBlock2d count (2) */
+    int n_bottleneck;        /* ResBlock2d count (6) */
+    int widths[8];           /* widths[0] = channels after the first conv (64), widths[i] = after down block i - 1 (128, 256);
+                                up block i maps widths[n_down - i] -> widths[n_down - i - 1].  Multiples of 8 */
+} dawn_decoder_cfg;
+/* a missing name or an unusable width: error return with a message, *out untouched */
+int dawn_decoder_create(const dawn_decoder_cfg* cfg, const dawn_named_ptr* weights, int n_weights, dawn_decoder** out);
+void dawn_decoder_destroy(dawn_decoder* dec);
+/* bytes of the per-clip skip memory (encoder outputs at every level) for H x W images (multiples of 2^n_down; 0 otherwise) */
+size_t dawn_decoder_skip_bytes(dawn_decoder* dec, int H, int W);
+/* bytes of the workspace that covers dawn_decoder_encode and dawn_decode_clip with chunks of up to `chunk` frames */
+size_t dawn_decoder_workspace_bytes(dawn_decoder* dec, int H, int W, int chunk);
+/* img3 (3,H,W) fp32 planar in [0,1] -> skip_mem; fea_out optional: (widths[n_down], H/2^n, W/2^n) reference layout = Generator.compute_fea
+ * (GEN:132-136), the first 256 channels of dawn_clip_prepare's fea272 */
+int dawn_decoder_encode(dawn_decoder* dec, int H, int W, const float* img3, void* skip_mem, size_t skip_bytes, float* fea_out,
+                        void* workspace, size_t workspace_bytes, void* stream);
+/* latent: the (3,T,h,w) output of any dawn_sampler_run*, taken as is -- three planes `latent_plane` floats apart: x and y of the
+ * sampling grid, then p with occlusion = (p + 1) * 0.5 (two fp32 roundings, as torch evaluates FD:360), formed per chunk into the
+ * workspace.  Frames are decoded `chunk` at a time (the launch sequence of FlowDecoder._decode_frames).  Outputs, each optional:
+ *   out_vid, warped_vid   fp32 (3,T,H,W) planar, channel planes out_plane floats apart (both or neither);
+ *   frames_u8             (T,H,W,3) uint8: the egress of dawn_frames_to_u8 with mean3 = 3 HOST doubles (mean_c / 255; NULL = 0) and
+ *                         the bgr flag.  Alone: every chunk ends in dawn_final_conv_blend_u8 and no fp32 frame is written anywhere;
+ *                         with the fp32 pair: dawn_final_conv_blend, then dawn_frames_to_u8 on the chunk.
+ * Neither output, W % 4 != 0 with frames_u8, a short workspace: error return with a message, nothing launched. */
+int dawn_decode_clip(dawn_decoder* dec, int H, int W, int T, int h, int w, const float* img3, const void* skip_mem,
+                     const float* latent, long latent_plane, int chunk, float* out_vid, float* warped_vid, long out_plane,
+                     unsigned char* frames_u8, const double* mean3, int bgr, void* workspace, size_t workspace_bytes, void* stream);
+/* the same for a host that holds the occlusion map already: grid = two planes (T,h,w) grid_plane floats apart, conf (T,h,w) */
+int dawn_decode_clip_conf(dawn_decoder* dec, int H, int W, int T, int h, int w, const float* img3, const void* skip_mem,
+                          const float* grid, long grid_plane, const float* conf, int chunk, float* out_vid, float* warped_vid,
+                          long out_plane, unsigned char* frames_u8, const double* mean3, int bgr, void* workspace,
+                          size_t workspace_bytes, void* stream);
 /* after a stream synchronise: (kind, algorithmic flops, algorithmic bytes, ms) per conv launch recorded under
  * DAWN_OPT_PROFILE; kind 0 = split 3x3, 1 = split 1x1, 2 = fp32 MFMA; returns the number of entries (and clears them) */
 int dawn_ctx_profile_read(dawn_ctx* ctx, double* out4, int max_entries);

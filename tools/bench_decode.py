@@ -3,10 +3,16 @@
 the shipped generator topology (64/128/256 channels, 6 bottleneck blocks) and seeded random weights.
 
     python tools/bench_decode.py [--res 256] [--frames 200] [--iters 3] [--cpu-frames 2] [--chunk 64]
+    python tools/bench_decode.py --u8 [--iters 5] [--chunk 64] [--out profiles/decode_u8.json]
 
 Prints one JSON line: decoded frames/s, algorithmic TFLOP/s of the convolutions (dense math of GEN:138-171 per frame,
 encoder excluded -- it runs once per clip here and once per FRAME in the reference), the per-kernel-class time split
-measured with HIP events, and the CPU oracle (oracle/lfg_ref.py) timed on `--cpu-frames` frames beside it."""
+measured with HIP events, and the CPU oracle (oracle/lfg_ref.py) timed on `--cpu-frames` frames beside it.
+
+`--u8` times the two ways from a sampled clip to frames in host memory, at 256^2 / 200 frames and at 128^2 / 400 frames, alternating
+them in one process: (a) `decode_clip` + `frames_to_u8` + `.cpu()` (two fp32 clips on the device, one conversion launch, one copy)
+and (b) `stream_frames_u8` drained to the host (the decoder's last kernel writes the bytes; each chunk's copy overlaps the next
+chunk's decode).  Host wall clock around work that ends with the bytes in host memory; peak allocated device bytes of each."""
 import argparse
 import json
 import os
@@ -130,12 +136,74 @@ def run(res=256, frames=200, iters=3, chunk=64, cpu_frames=2, seed=0):
     return result
 
 
+def run_u8(iters=5, chunk=64, seed=0, cases=((256, 200), (128, 400))):
+    """(a) and (b) of the module docstring, alternating a, b, a, b, ... after one warm-up of each; medians and all samples."""
+    import numpy as np
+    from dawn_pytorch_amd.flow_decoder import FlowDecoder
+    from dawn_pytorch_amd.ops import HipOps
+    dev = torch.device("cuda:0")
+    ops = HipOps()
+    dec = FlowDecoder(lfg_state_dict(seed), dev, ops=ops, chunk=chunk)
+    results = []
+    for res, frames in cases:
+        img = torch.rand(1, 3, res, res, generator=torch.Generator().manual_seed(1)).to(dev)
+        grid, conf = synthetic_motion(frames, res // 4, dev)
+
+        def two_step():
+            vid = dec.decode_clip(img, grid, conf)["sample_out_vid"][0]
+            return ops.frames_to_u8(vid).cpu().numpy()
+
+        def streamed():
+            out = np.empty((frames, res, res, 3), dtype=np.uint8)
+            for t0, fr in dec.stream_frames_u8(img, grid, conf):
+                out[t0:t0 + len(fr)] = fr
+            return out
+
+        def timed(fn):
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+            base = torch.cuda.memory_allocated()
+            t0 = time.perf_counter()
+            out = fn()
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) * 1e3, torch.cuda.max_memory_allocated() - base, out
+
+        _, _, a0 = timed(two_step)                     # warm-up of every shape; the two must agree byte for byte
+        _, _, b0 = timed(streamed)
+        same = bool(np.array_equal(a0, b0))
+        del a0, b0
+        ta, tb, pa, pb = [], [], 0, 0
+        for _ in range(iters):
+            ms, peak, _o = timed(two_step)
+            ta.append(ms); pa = max(pa, peak)
+            ms, peak, _o = timed(streamed)
+            tb.append(ms); pb = max(pb, peak)
+        med = lambda v: sorted(v)[len(v) // 2]         # noqa: E731
+        results.append({"workload": f"{res}x{res}, {frames} frames, chunk {chunk}", "bytes_identical": same,
+                        "two_step_ms": med(ta), "streamed_ms": med(tb), "two_step_all_ms": ta, "streamed_all_ms": tb,
+                        "two_step_peak_device_bytes": pa, "streamed_peak_device_bytes": pb,
+                        "fp32_clip_bytes": 3 * frames * res * res * 4})
+    return {"metric": "sampled clip -> uint8 frames in host memory, ms per clip (host wall clock, ends after the last byte arrived)",
+            "a": "decode_clip + frames_to_u8 + .cpu()", "b": "stream_frames_u8 drained to the host", "iters": iters,
+            "order": "a, b alternating in one process after one warm-up of each", "data": "synthetic", "cases": results}
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--res", type=int, default=256)
     ap.add_argument("--frames", type=int, default=200)
-    ap.add_argument("--iters", type=int, default=3)
+    ap.add_argument("--iters", type=int, default=None, help="timed repetitions (default 3; 5 with --u8)")
     ap.add_argument("--chunk", type=int, default=64)
     ap.add_argument("--cpu-frames", type=int, default=2)
+    ap.add_argument("--u8", action="store_true", help="time decode_clip + frames_to_u8 + .cpu() against stream_frames_u8")
+    ap.add_argument("--out", type=str, default=None, help="--u8: also write the JSON result to this file")
     a = ap.parse_args()
-    print(json.dumps(run(a.res, a.frames, a.iters, a.chunk, a.cpu_frames)))
+    if a.u8:
+        r = run_u8(5 if a.iters is None else a.iters, a.chunk)
+        if a.out:
+            with open(a.out, "w") as f:
+                json.dump(r, f, indent=1)
+                f.write("\n")
+        print(json.dumps(r))
+        sys.exit(0)
+    print(json.dumps(run(a.res, a.frames, 3 if a.iters is None else a.iters, a.chunk, a.cpu_frames)))
