@@ -46,6 +46,7 @@ class ConvDesc(C.Structure):
         ("gn_a", c_f), ("gn_b", c_f),
         ("gn_ticket", c_f),
         ("w_wino4", c_f),
+        ("border", _i),
     ]
 
 

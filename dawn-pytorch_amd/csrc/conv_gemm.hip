@@ -66,6 +66,15 @@ constexpr int DAWN_CONV_POLICY_MASK = 0x3FF3FFCF;
 static inline int policy_of(const dawn_conv_desc& d) { return (d.policy ? d.policy : DAWN_CONV_POLICY_DEFAULT) & DAWN_CONV_POLICY_MASK; }
 __device__ unsigned long long* g_dbg = nullptr;   // s_memtime stamps of the instrumented build (ABL bit 3)
 
+// dawn_conv_desc.border (mode 1): where a 2x2 phase tap that falls outside the H x W input reads.  0 leaves the coordinate alone
+// (the callers' bounds test then reads zero), 1 clamps it to the edge pixel, 2 wraps it to the opposite edge.  A tap is at most one
+// pixel outside, so one conditional step is enough; an in-range coordinate comes back unchanged for every border.
+__device__ __forceinline__ int dawn_border_coord(int i, int n, int border) {
+    if (border == 1) return i < 0 ? 0 : (i >= n ? n - 1 : i);
+    if (border == 2) return i < 0 ? i + n : (i >= n ? i - n : i);
+    return i;
+}
+
 struct RowInfo {
     long rowoff;  // (f*Hi + yb)*Wi + xb : input pixel index of tap (0,0) (may point outside; bounds via yb/xb)
     int yb, xb;
@@ -168,9 +177,15 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(const dawn_conv_desc d, 
         gc = c;
 #pragma unroll
         for (int i = 0; i < RPT; ++i) {
-            const int yi = ri[i].yb + dy, xi = ri[i].xb + dx;
+            int yi = ri[i].yb + dy, xi = ri[i].xb + dx;
+            long poff = tapoff;
+            if (d.border) {            // (uniform; mode 1 only) a remapped tap's pixel: rowoff + tapoff holds for in-range taps only
+                yi = dawn_border_coord(yi, d.Hi, d.border);
+                xi = dawn_border_coord(xi, d.Wi, d.border);
+                poff = (long)(yi - ri[i].yb) * d.Wi + (xi - ri[i].xb);
+            }
             const bool inb = ri[i].valid && yi >= 0 && yi < d.Hi && xi >= 0 && xi < d.Wi;
-            const long pix = inb ? ri[i].rowoff + tapoff : 0;
+            const long pix = inb ? ri[i].rowoff + poff : 0;
             ginb[i] = inb;
             f32x4 v = {0.f, 0.f, 0.f, 0.f};
             if (inb) v = *reinterpret_cast<const f32x4*>(src + pix * ld + cs);
@@ -407,9 +422,15 @@ __global__ __launch_bounds__(256) void conv_gemm_glds_kernel(const dawn_conv_des
         const int cs0 = src1 ? cbase - d.C0 : cbase;
 #pragma unroll
         for (int j = 0; j < NAI; ++j) {
-            const int yi = ri[j].yb + dy, xi = ri[j].xb + dx;
+            int yi = ri[j].yb + dy, xi = ri[j].xb + dx;
+            long poff = tapoff;
+            if (d.border) {            // (uniform; mode 1 only) as conv_gemm_kernel
+                yi = dawn_border_coord(yi, d.Hi, d.border);
+                xi = dawn_border_coord(xi, d.Wi, d.border);
+                poff = (long)(yi - ri[j].yb) * d.Wi + (xi - ri[j].xb);
+            }
             const bool inb = ri[j].valid && yi >= 0 && yi < d.Hi && xi >= 0 && xi < d.Wi;
-            const float* g = inb ? src + (ri[j].rowoff + tapoff) * ld + cs0 + kql[j] * 4 : dawn_zero_block;
+            const float* g = inb ? src + (ri[j].rowoff + poff) * ld + cs0 + kql[j] * 4 : dawn_zero_block;
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
                                              (__attribute__((address_space(3))) void*)(As + buf * BM * BK + (wave * NAI + j) * 256),
                                              16, 0, 0);
@@ -2225,6 +2246,10 @@ __global__ __launch_bounds__(512) void gemm1x1_rowacc_kernel(const dawn_conv_des
                 const int phase = (int)(panel / ppp), ppy = phase >> 1, ppx = phase & 1;
                 iy = py_ + ((tap >> 1) ? (ppy ? 1 : -1) : 0);
                 ix = px_ + ((tap & 1) ? (ppx ? 1 : -1) : 0);
+                if (d.border) {        // (uniform) outside taps read the edge / the opposite edge instead of zero: always in range below
+                    iy = dawn_border_coord(iy, d.Hi, d.border);
+                    ix = dawn_border_coord(ix, d.Wi, d.border);
+                }
             }
             const bool inb = iy >= 0 && iy < d.Hi && ix >= 0 && ix < d.Wi;
             unsigned off = inb ? (unsigned)(((iy * d.Wi + ix) * d.ld0 + c0 + 8 * half) * 4) : 0xffffff00u;   // padding reads 0
@@ -2753,6 +2778,8 @@ extern "C" int dawn_conv_gemm(const dawn_conv_desc* dp, void* stream) {
         return dawn_set_error_msg(-11, "dawn_conv_gemm: pixel strides must be multiples of 4 floats");
     if (d.mode == 1 && (d.KH != 2 || d.KW != 2 || d.Ho != 2 * d.Hi || d.Wo != 2 * d.Wi))
         return dawn_set_error_msg(-12, "dawn_conv_gemm: mode 1 expects 2x2 phase taps and 2x upsampling");
+    if (d.border < 0 || d.border > 2 || (d.border && d.mode != 1))
+        return dawn_set_error_msg(-15, "dawn_conv_gemm: border is 0 (zero), 1 (edge) or 2 (wrap), and non-zero only in mode 1");
     if ((d.ch_a || d.pro_add) && d.C1 != 0)
         return dawn_set_error_msg(-13, "dawn_conv_gemm: channel-affine / add prologue needs a single source");
     const long M = (d.mode == 0) ? (long)d.F * d.Ho * d.Wo : (long)d.F * d.Hi * d.Wi;

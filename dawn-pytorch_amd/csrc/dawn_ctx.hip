@@ -85,6 +85,7 @@ struct dawn_ctx {
     hipStream_t side = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     int conv_policy = 0, temporal_flags = 0, overlap = 1;
+    int up_border = 0;              // dawn_conv_desc.border of the Upsample launches (DAWN_OPT_UP_BORDER)
     int long_clip_frames = 4096;    // unet_forward.LONG_CLIP_FRAMES: clips longer than this run the memory-lean form (DAWN_OPT_LONG_CLIP_FRAMES)
     Arena arena;
     // profiling of conv launches (bench.py roofline): optional
@@ -259,7 +260,7 @@ struct Eval {
         const float* in0 = nullptr; int C0 = 0; int ld0 = 0;
         const float* in1 = nullptr; int C1 = 0; int ld1 = 0;
         const float* w = nullptr; const void* w_bf3 = nullptr; const void* w_wino = nullptr; const void* w_wino4 = nullptr; const float* bias = nullptr; int N = 0;
-        int Fr = 0, Hi = 0, Wi = 0, Ho = 0, Wo = 0, KH = 1, KW = 1, stride = 1, pad = 0, mode = 0;
+        int Fr = 0, Hi = 0, Wi = 0, Ho = 0, Wo = 0, KH = 1, KW = 1, stride = 1, pad = 0, mode = 0, border = 0;
         const float *row_mean = nullptr, *row_rstd = nullptr;
         float ln_eps = 0.f;
         const float* res = nullptr; int ld_res = 0;
@@ -276,7 +277,7 @@ struct Eval {
         memset(&d, 0, sizeof(d));
         d.in0 = a.in0; d.in1 = a.in1; d.C0 = a.C0; d.C1 = a.C1; d.ld0 = a.ld0; d.ld1 = a.ld1;
         d.F = a.Fr; d.Hi = a.Hi; d.Wi = a.Wi; d.Ho = a.Ho ? a.Ho : a.Hi; d.Wo = a.Wo ? a.Wo : a.Wi;
-        d.KH = a.KH; d.KW = a.KW; d.stride = a.stride; d.pad = a.pad; d.mode = a.mode;
+        d.KH = a.KH; d.KW = a.KW; d.stride = a.stride; d.pad = a.pad; d.mode = a.mode; d.border = a.border;
         d.w = a.w; d.bias = a.bias; d.N = a.N; d.row_mean = a.row_mean; d.row_rstd = a.row_rstd; d.ln_eps = a.ln_eps;
         d.res = a.res; d.ld_res = a.ld_res; d.tr = a.tr; d.ld_tr = a.ld_tr; d.tr_a = a.tr_a; d.tr_b = a.tr_b;
         d.out = a.out; d.ld_out = a.ld_out; d.gn_part = a.gn_part; d.w_bf3 = a.w_bf3; d.w_wino = a.w_wino; d.w_wino4 = a.w_wino4; d.gn_rows = a.gn_rows;
@@ -809,7 +810,7 @@ struct Eval {
                 T2 up = t2((long)F * (2 * H) * (2 * W), x.C);
                 ConvArgs a;
                 a.in0 = x.p; a.C0 = x.C; a.ld0 = x.C; a.w = lv.rs_w; a.w_bf3 = lv.rs_ws; a.bias = lv.rs_b; a.N = x.C; a.Fr = F; a.Hi = H; a.Wi = W;
-                a.Ho = 2 * H; a.Wo = 2 * W; a.KH = 2; a.KW = 2; a.mode = 1; a.out = up.p; a.ld_out = x.C;
+                a.Ho = 2 * H; a.Wo = 2 * W; a.KH = 2; a.KW = 2; a.mode = 1; a.border = c->up_border; a.out = up.p; a.ld_out = x.C;
                 conv(a);
                 rel(x); x = up;
                 H *= 2; W *= 2;
@@ -934,12 +935,15 @@ extern "C" void dawn_ctx_destroy(dawn_ctx* c) {
 }
 
 extern "C" int dawn_ctx_set_option(dawn_ctx* c, int option, int value) {
+    if (option == DAWN_OPT_UP_BORDER && (value < 0 || value > 2))
+        return dawn_set_error_msg(-204, "dawn_ctx_set_option: DAWN_OPT_UP_BORDER is 0 (zero), 1 (edge) or 2 (wrap)");
     if (!c) return dawn_set_error_msg(-202, "dawn_ctx_set_option: null ctx");
     switch (option) {
         case DAWN_OPT_CONV_POLICY: c->conv_policy = value; return 0;
         case DAWN_OPT_TEMPORAL_FLAGS: c->temporal_flags = value; return 0;
         case DAWN_OPT_OVERLAP: c->overlap = value ? 1 : 0; return 0;
         case DAWN_OPT_LONG_CLIP_FRAMES: c->long_clip_frames = value > 0 ? value : 4096; return 0;
+        case DAWN_OPT_UP_BORDER: c->up_border = value; return 0;
         case DAWN_OPT_PROFILE:
             c->prof_on = value != 0;
             return 0;

@@ -54,7 +54,7 @@ def _clip_struct(clip, ancestral: bool) -> ClipMode:
     return ClipMode(CLIP_KINDS[kind], 0.0 if q is None else q)
 
 
-OPT_CONV_POLICY, OPT_TEMPORAL_FLAGS, OPT_OVERLAP, OPT_PROFILE, OPT_LONG_CLIP_FRAMES = 1, 2, 3, 4, 5
+OPT_CONV_POLICY, OPT_TEMPORAL_FLAGS, OPT_OVERLAP, OPT_PROFILE, OPT_LONG_CLIP_FRAMES, OPT_UP_BORDER = 1, 2, 3, 4, 5, 6
 
 # ---- T-shard callbacks (include/dawn_hip.h: dawn_shard_comm)
 HALO_BEGIN_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_long, C.c_void_p)
@@ -228,6 +228,8 @@ class CtxEvaluator:
         self._ws: Optional[Tensor] = None
         self._need = {}              # (F, h, w, conv policy) -> dawn_workspace_bytes (a dry evaluation on the host: cached)
         self._policy = 0
+        if P.up_border:              # folded up convs (use_deconv=False): what their outside taps read
+            self.set_option(OPT_UP_BORDER, P.up_border)
 
     def __del__(self):
         h, self.h = getattr(self, "h", None), None

@@ -140,10 +140,11 @@ class HipOps:
                   tr: Optional[Tuple[Tensor, Tensor, Tensor]] = None, out: Optional[Tensor] = None,
                   gn_part: Optional[Tensor] = None, w_bf3: Optional[Tensor] = None, ln_eps: float = 0.0,
                   w_wino: Optional[Tensor] = None, gn_fin: Optional[tuple] = None, w_wino4: Optional[Tensor] = None,
-                  form_only: bool = False) -> Tensor:
+                  form_only: bool = False, border: int = 0) -> Tensor:
         """gn_fin = (gamma, beta, film or None, total_rows[, eps]) with gn_part: ask the launch to finish the GroupNorm itself (the
         Winograd 3x3 kernel's last workgroup reduces and finalises); gn_coeffs(part=...) then returns its coefficients without a launch.
-        form_only: launch nothing and return (dawn_conv3x3_form, dawn_gemm1x1_form) of exactly this call's descriptor."""
+        form_only: launch nothing and return (dawn_conv3x3_form, dawn_gemm1x1_form) of exactly this call's descriptor.
+        border (mode 1): what a phase tap outside the input reads -- 0 zero, 1 the edge pixel, 2 the opposite edge (pack.up_border)."""
         Ho = Hi if Ho is None else Ho
         Wo = Wi if Wo is None else Wo
         rows_out = F * Ho * Wo
@@ -156,6 +157,7 @@ class HipOps:
         d.ld0, d.ld1 = _ld(in0), _ld(in1)
         d.F, d.Hi, d.Wi, d.Ho, d.Wo = F, Hi, Wi, Ho, Wo
         d.KH, d.KW, d.stride, d.pad, d.mode = KH, KW, stride, pad, mode
+        d.border = border
         d.w, d.bias, d.N = _p(w), _p(bias), N
         if row_stats is not None:
             d.row_mean, d.row_rstd = _p(row_stats[0]), _p(row_stats[1])

@@ -185,6 +185,38 @@ def deconv_w_kn_phases(w5: Tensor) -> Tensor:
     return torch.stack(blocks, 0)                                             # (4, 4*Ci, Co)
 
 
+def upconv_w_kn_phases(w5: Tensor) -> Tensor:
+    """Conv3d weight (Co, Ci, 1, 3, 3) that follows nn.Upsample(scale (1,2,2), nearest) (MT:169-172, use_deconv=False) -> the 4 phase
+    blocks of 2x2 taps of deconv_w_kn_phases, same block / tap order and offsets.  With u[i] = x[i >> 1], output row 2a reads
+    u[2a-1], u[2a], u[2a+1] = x[a-1], x[a], x[a] and row 2a+1 reads x[a], x[a], x[a+1], so per axis
+    phase bit 0: (tap 0: w[1] + w[2], offset 0), (tap 1: w[0], offset -1);  phase bit 1: (tap 0: w[0] + w[1], offset 0), (tap 1: w[2], offset +1)
+    and a 2-D tap is the sum of the kernel entries of the product set: summed in fp64, rounded once to fp32.  What a tap outside the
+    input reads is the conv's padding_mode (up_border)."""
+    Co, Ci = w5.shape[:2]
+    if not (tuple(w5.shape[2:]) == (1, 3, 3)):
+        raise ValueError(f"w5.shape[2:] == (1, 3, 3): {tuple(w5.shape)}")
+    ksel = (((1, 2), (0,)), ((0, 1), (2,)))
+    g = w5[:, :, 0].double()                                                  # (Co, Ci, 3, 3)
+    blocks = []
+    for py in range(2):
+        for px in range(2):
+            taps = []
+            for ty in range(2):
+                for tx in range(2):
+                    taps.append(sum(g[:, :, ky, kx] for ky in ksel[py][ty] for kx in ksel[px][tx]).t())      # (Ci, Co)
+            blocks.append(torch.stack(taps, 0).reshape(4 * Ci, Co))
+    return torch.stack(blocks, 0).float()                                     # (4, 4*Ci, Co)
+
+
+def up_border(padding_mode: str) -> int:
+    """dawn_conv_desc.border of the folded up conv for a Conv3d padding_mode: the row that pads the nearest-upsampled image is zero,
+    a copy of the edge row (reflect: u[-1] = u[1] = x[0]; replicate: u[-1] = u[0] = x[0]) or the opposite edge row (circular)."""
+    try:
+        return {"zeros": 0, "reflect": 1, "replicate": 1, "circular": 2}[padding_mode]
+    except (KeyError, TypeError):
+        raise ValueError(f"padding_mode must be one of 'zeros', 'reflect', 'replicate', 'circular': {padding_mode!r}") from None
+
+
 def rel_pos_bucket(rel: Tensor, num_buckets: int = 32, max_distance: int = 32) -> Tensor:
     """RelativePositionBias._relative_position_bucket (MT:92-109), rel = k_pos - q_pos, fp32 log."""
     n = -rel
@@ -278,6 +310,7 @@ class PackedUNet:
     rot_freqs: Tensor = None               # (16,)
     sin_freqs: Tensor = None               # (dim/2,) SinusoidalPosEmb table (MT:157-159)
     n_cond_blocks: int = 0
+    up_border: int = 0                     # dawn_conv_desc.border of the up convs (use_deconv=False nets: up_border(padding_mode))
 
     def band(self, win: int) -> Tensor:
         """bias by offset d = j - i in [-win, win] -> (2*win+1, 8) (MT:111-119 inside the window).  Cached per window: a clip
@@ -312,7 +345,9 @@ class PackedUNet:
         return cache[key]
 
 
-def pack_unet(sd: Dict[str, Tensor], win: int, device, prefix: str = "denoise_fn.") -> PackedUNet:
+def pack_unet(sd: Dict[str, Tensor], win: int, device, prefix: str = "denoise_fn.", padding_mode: str = "zeros") -> PackedUNet:
+    """padding_mode: that of the up convs of a use_deconv=False net (ups.L.4.1.weight in the state dict, MT:169-172); a
+    use_deconv=True net (ups.L.4.weight) ignores it, as the reference does."""
     g = lambda k: sd[prefix + k].detach().float()
     has = lambda k: (prefix + k) in sd
     dev = lambda t: t.contiguous().to(device)
@@ -430,9 +465,12 @@ def pack_unet(sd: Dict[str, Tensor], win: int, device, prefix: str = "denoise_fn
         q = f"ups.{l}."
         lvl = {"rb1": resblock(q + "0."), "rb2": resblock(q + "1."), "sla": attn(q + "2.", True),
                "tattn": attn(q + "3."), "up": None}
-        if has(q + "4.weight"):
-            ph = deconv_w_kn_phases(g(q + "4.weight"))
-            lvl["up"] = (dev(torch.stack([pack_kn(ph[i]) for i in range(4)], 0)), dev(g(q + "4.bias")),
+        upconv = has(q + "4.1.weight")                         # nearest x2 + 3x3 conv (use_deconv=False): folded into the same phase blocks
+        if upconv:
+            P.up_border = up_border(padding_mode)
+        if upconv or has(q + "4.weight"):
+            ph = upconv_w_kn_phases(g(q + "4.1.weight")) if upconv else deconv_w_kn_phases(g(q + "4.weight"))
+            lvl["up"] = (dev(torch.stack([pack_kn(ph[i]) for i in range(4)], 0)), dev(g(q + ("4.1.bias" if upconv else "4.bias"))),
                          torch.stack([pack_bf3(ph[i]) for i in range(4)], 0).to(device) if ph[0].shape[0] % 256 == 0 else None)
         P.ups.append(lvl)
     P.head_g = resblock("final_conv.0.")

@@ -14,7 +14,7 @@ from typing import Dict, Optional, Sequence, Tuple
 import torch
 from torch import nn
 
-from .pack import PackedUNet, pack_unet
+from .pack import PackedUNet, pack_unet, up_border
 from .unet_forward import ClipState, build_clip_state, unet_forward, unet_forward_guided
 
 Tensor = torch.Tensor
@@ -24,8 +24,9 @@ XA_INNER = 64         # CrossAttention heads * dim_head = 8 * 8 (MT:488-497)
 
 def unet_param_spec(dim: int, channels: int, dim_mults: Sequence[int], cond_aud: int, cond_pose: int, cond_eye: int,
                     out_grid_dim: int = 2, out_conf_dim: int = 1, heads: int = 8,
-                    init_kernel_size: int = 7) -> Dict[str, Tuple[Tuple[int, ...], str]]:
-    """name -> (shape, init kind).  Mirrors the module tree of MT:728-877 (probed key list: SURVEY §8a)."""
+                    init_kernel_size: int = 7, use_deconv: bool = True) -> Dict[str, Tuple[Tuple[int, ...], str]]:
+    """name -> (shape, init kind).  Mirrors the module tree of MT:728-877 (probed key list: SURVEY §8a).  use_deconv=False: the
+    Upsample of a level is nn.Sequential(nn.Upsample, nn.Conv3d (1,3,3)) (MT:169-172), keys ups.L.4.1.* instead of ups.L.4.*."""
     spec: Dict[str, Tuple[Tuple[int, ...], str]] = {}
     time_dim = dim * 4
     k = init_kernel_size
@@ -103,8 +104,10 @@ def unet_param_spec(dim: int, channels: int, dim_mults: Sequence[int], cond_aud:
         resblock(p + ".1", ci, ci, True)
         sla(p + ".2", ci)
         temporal(p + ".3", ci)
-        if i < n - 1:
+        if i < n - 1 and use_deconv:
             conv(p + ".4", ci, ci, 4, 4)      # ConvTranspose3d: (C_in, C_out, 1, 4, 4) with C_in == C_out
+        elif i < n - 1:
+            conv(p + ".4.1", ci, ci, 3, 3)    # nn.Upsample (no parameters) + Conv3d (C_out, C_in, 1, 3, 3)
     resblock("final_conv.0", dim * 2, dim, False)
     conv("final_conv.1", out_grid_dim, dim, 1, 1)
     resblock("occlusion_map.0", dim * 2, dim, False)
@@ -157,11 +160,14 @@ class Unet3D(nn.Module):
         if not use_sparse_linear_attn: unsupported.append("use_sparse_linear_attn=False")
         if use_final_activation: unsupported.append("use_final_activation=True")
         if learn_null_cond: unsupported.append("learn_null_cond=True")
-        if not use_deconv: unsupported.append("use_deconv=False")
         if (out_grid_dim, out_conf_dim) != (2, 1): unsupported.append("out dims != (2,1)")
         if (channels - 3) % 16 != 0 or dim % 16 != 0: unsupported.append("channels-3 and dim must be multiples of 16")
         if unsupported:
             raise NotImplementedError("Unet3D (HIP build) does not support: " + "; ".join(unsupported))
+        if not use_deconv:
+            up_border(padding_mode)         # ValueError for an unknown mode, as nn.Conv3d raises (use_deconv=True ignores it: MT:167)
+        self.use_deconv = bool(use_deconv)
+        self.padding_mode = padding_mode
         self.null_cond_mask = None
         self.channels = channels
         self.num_frames = num_frames
@@ -175,7 +181,8 @@ class Unet3D(nn.Module):
         self.ops = None                     # set to an op backend; default HipOps is created lazily
         self._packed: Optional[PackedUNet] = None
         self._packed_key = None
-        spec = unet_param_spec(dim, channels, dim_mults, cond_aud, cond_pose, cond_eye, out_grid_dim, out_conf_dim)
+        spec = unet_param_spec(dim, channels, dim_mults, cond_aud, cond_pose, cond_eye, out_grid_dim, out_conf_dim,
+                               use_deconv=self.use_deconv)
         shared_freqs = None
         for name, (shape, kind) in spec.items():
             if kind == "rotary":            # one RotaryEmbedding module aliased under every temporal attention
@@ -197,7 +204,7 @@ class Unet3D(nn.Module):
         key = (params[0].device, self.win_width, tuple(p._version for p in params), tuple(p.data_ptr() for p in params[:4]))
         if self._packed is None or self._packed_key != key:
             sd = {k: v for k, v in self.state_dict().items()}
-            self._packed = pack_unet(sd, self.win_width, params[0].device, prefix="")
+            self._packed = pack_unet(sd, self.win_width, params[0].device, prefix="", padding_mode=self.padding_mode)
             self._packed_key = key
         return self._packed
 

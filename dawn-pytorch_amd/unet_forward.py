@@ -465,7 +465,9 @@ def _unet_rest(ops, P: PackedUNet, cs: ClipState, x3: Tensor, film_all: Tensor, 
         x = _spatial_temporal(lvl["sla"], lvl["tattn"], holder, _spatial_linear)
         if lvl["up"] is not None:
             wu, bu, wus = lvl["up"]
-            x = ops.conv_gemm(x, wu, x.shape[1], F=F, Hi=H, Wi=W, Ho=2 * H, Wo=2 * W, KH=2, KW=2, mode=1, bias=bu, w_bf3=wus)
+            # (border only where it says something: backends without the argument keep serving the transposed conv and the zeros up conv)
+            kw = {"border": P.up_border} if P.up_border else {}
+            x = ops.conv_gemm(x, wu, x.shape[1], F=F, Hi=H, Wi=W, Ho=2 * H, Wo=2 * W, KH=2, KW=2, mode=1, bias=bu, w_bf3=wus, **kw)
             H, W = 2 * H, 2 * W
     if r is None:
         # long clips: recompute the skip, and run the heads one after the other (each head's tensor is projected to its rows of eps and

@@ -38,7 +38,7 @@ typedef struct dawn_conv_desc {
     int C0, C1, ld0, ld1;               /* channels per source, pixel stride (floats) per source */
     int F, Hi, Wi, Ho, Wo;
     int KH, KW, stride, pad;
-    int mode;                           /* 0 = conv, 1 = transposed 4x4/s2/p1 as 4 output phases of 2x2 taps */
+    int mode;                           /* 0 = conv, 1 = transposed 4x4/s2/p1 as 4 output phases of 2x2 taps (see `border` at the end) */
     const float* w;                     /* packed [K/4][N][4], k = tap*(C0+C1)+c; mode 1: 4 consecutive phase blocks */
     const float* bias;                  /* N or NULL */
     int N;
@@ -93,6 +93,13 @@ typedef struct dawn_conv_desc {
      * matrix-pipe flops than the direct form, fp32 results to fp32-F(4x4) accuracy: ~2x the direct form's rounding error); the gn_* fields
      * above are honoured exactly as by the F(2x2) kernel */
     const void* w_wino4;
+    /* mode 1 only: what a 2x2 phase tap outside the Hi x Wi input reads.  0 = zero (the transposed conv; what a zero-initialised
+     * descriptor says), 1 = the edge pixel (index clamped), 2 = the opposite edge (index wrapped).  With the folded weights of
+     * pack.upconv_w_kn_phases this is nn.Upsample(scale (1,2,2), nearest) + nn.Conv3d (1,3,3)/s1/p(0,1,1) of MT:169-172 without the
+     * upsampled tensor: padding_mode zeros = 0, reflect and replicate = 1 (the padded row of the upsampled image is a copy of the
+     * edge row either way), circular = 2.  Pixels whose four taps are in range take the same path for every value.  Non-zero in
+     * mode 0, or any other value: error -15, nothing is launched. */
+    int border;
 } dawn_conv_desc;
 int dawn_conv_gemm(const dawn_conv_desc* d, void* stream);
 /* 1 when a 3x3 / stride 1 / pad 1 conv of this shape (F frames of H x W pixels, C0 + C1 input channels, N output channels) runs in the
@@ -430,15 +437,25 @@ typedef struct dawn_named_ptr { const char* name; const void* ptr; } dawn_named_
  * mid.tattn|ups.L.sla|ups.L.tattn>.<wqkv|wout|bout|wqkv_s|wout_s|wout_sp>"; ResBlocks "<downs.L.rb1|...|mid.rb1|mid.rb2|
  * head_g|head_o>.<w1|b1|g1|be1|w2|b2|g2|be2|wr|br|w1s|w2s|wrs|wq|wqs|q_scale|g3|wo.B|wos.B|mlp_w.B|mlp_b.B|kv_w.B|k_scale.B|
  * null_kv.B>" (B = 0..2: pose, aud, eye); "downs.L.down.<w|b|ws>", "ups.L.up.<w|b|ws>" (ws optional: pack_bf3 image(s) of the
- * resampling convolution for the split pipeline; dawn_pytorch_amd/ctx.py builds the table). */
+ * resampling convolution for the split pipeline; dawn_pytorch_amd/ctx.py builds the table).
+ * "ups.L.up.w" is four phase blocks (py, px) of 2x2 taps (ty, tx), each [4 C / 4][C][4] with k = (2 ty + tx) C + c; tap 0 sits on the
+ * input pixel, tap 1 one pixel before it (phase bit 0) or after it (phase bit 1).  use_deconv=True checkpoints (ups.L.4.weight,
+ * (C, C, 1, 4, 4)): tap t of phase bit p is kernel row / column ((1, 3), (2, 0))[p][t] (pack.deconv_w_kn_phases).  use_deconv=False
+ * checkpoints (ups.L.4.1.weight, (C, C, 1, 3, 3): nearest x2 upsample + 3x3 conv, MT:169-172): the host FOLDS the 3x3 kernel, per
+ * axis tap 0 = w[1] + w[2], tap 1 = w[0] for phase bit 0 and tap 0 = w[0] + w[1], tap 1 = w[2] for phase bit 1, a 2-D tap being
+ * the sum of the kernel entries of the product set (pack.upconv_w_kn_phases: summed in fp64, rounded once), and sets
+ * DAWN_OPT_UP_BORDER from the checkpoint's padding_mode. */
 int dawn_ctx_create(const dawn_unet_cfg* cfg, const dawn_named_ptr* weights, int n_weights, dawn_ctx** out);
 void dawn_ctx_destroy(dawn_ctx* ctx);
-enum { DAWN_OPT_CONV_POLICY = 1, DAWN_OPT_TEMPORAL_FLAGS = 2, DAWN_OPT_OVERLAP = 3, DAWN_OPT_PROFILE = 4, DAWN_OPT_LONG_CLIP_FRAMES = 5 };
+enum { DAWN_OPT_CONV_POLICY = 1, DAWN_OPT_TEMPORAL_FLAGS = 2, DAWN_OPT_OVERLAP = 3, DAWN_OPT_PROFILE = 4, DAWN_OPT_LONG_CLIP_FRAMES = 5,
+       DAWN_OPT_UP_BORDER = 6 };
 /* tuning state lives in the ctx: conv policy bits (dawn_conv_desc.policy), temporal-layer kernel family, two-stream
  * overlap on/off, per-launch HIP events around every dawn_conv_gemm (read with dawn_ctx_profile_read), the clip length above which an
  * evaluation runs in its memory-lean form (default 4096 frames: qkv tensors of the unfused attention levels per frame segment, the
  * heads' skip recomputed, the heads one after the other: 4.65 instead of 7.8 MB of workspace per frame at 256x256 for ~3 % of time;
- * set it BEFORE dawn_workspace_bytes) */
+ * set it BEFORE dawn_workspace_bytes); DAWN_OPT_UP_BORDER = dawn_conv_desc.border of the Upsample launches (0 zero: the default,
+ * and the only value for use_deconv=True weights; 1 edge: padding_mode reflect / replicate; 2 wrap: circular; anything else is an
+ * error) -- it reaches dawn_unet_forward, the guided and sharded forwards and every dawn_sampler_run* entry */
 int dawn_ctx_set_option(dawn_ctx* ctx, int option, int value);
 size_t dawn_clip_bytes(dawn_ctx* ctx, int F, int h, int w);
 size_t dawn_workspace_bytes(dawn_ctx* ctx, int F, int h, int w);      /* covers prepare, forward and sampler_run */
