@@ -1,6 +1,6 @@
 // Winograd F(2x2, 3x3) form of the split-operand 3x3 convolution (gfx950): 2.25x fewer matrix-pipe flops than the direct form.
 //
-// Same function as conv3x3_bf16_v2_kernel (conv_gemm.hip): every stride-1 3x3 ResBlock conv (MT:229 Block.proj inside MT:233-248),
+// Same function as conv3x3_bf16_v2_kernel (conv3x3_split.hip): every stride-1 3x3 ResBlock conv (MT:229 Block.proj inside MT:233-248),
 // fp32 in / fp32 out, channels-last.  The split kernels are POWER-limited: what pays is removing matrix-pipe work, not
 // scheduling it better.  Lavin's F(2x2, 3x3):  Y = A^T [ (G g G^T) . (B^T d B) ] A  per 2x2 output tile and (cin, cout) pair --
 // 16 multiplies for 4 outputs instead of 36 -- so the conv becomes 16 independent (tiles x Cin) . (Cin x Cout) GEMMs, one per

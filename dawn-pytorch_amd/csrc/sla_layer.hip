@@ -156,7 +156,7 @@ __global__ __launch_bounds__(512) void sla_c64_context_kernel(const float* __res
 // bf16 split of to_qkv, pack_bf3 layout [K/16][3][2][768][8]):
 //  * K and V projections run on the bf16 matrix pipe: the LayerNorm'ed tile is split ONCE per tile into three bf16
 //    planes in LDS (x = x1+x2+x3, shared by the 8 head-waves), the head's weight pieces live in registers, 6 exact
-//    cross terms accumulate in fp32 (see conv_gemm.hip) -- 48 bf16 MFMAs instead of 64 fp32 ones per tile;
+//    cross terms accumulate in fp32 (see conv3x3_halo_bf16_kernel in conv_gemm.hip) -- 48 bf16 MFMAs instead of 64 fp32 ones per tile;
 //  * the softmax over pixels uses a running column max (flash-attention style rescale of ctx / den when it
 //    grows) instead of a first sweep that recomputes K only to find the max: softmax is shift-invariant, so
 //    the result differs from the two-sweep kernel by rounding only.

@@ -56,7 +56,7 @@ __device__ __forceinline__ f32x16 proj_T(const float* wp, int Nw, int n, int hal
 }
 
 // ---- WMODE 2: Q/K/V projections on the bf16 matrix pipe with exactly split operands (fp32 results, see
-// conv_gemm.hip).  The LayerNorm'ed rows are split ONCE (phase 0) into three bf16 planes in LDS
+// conv3x3_halo_bf16_kernel in conv_gemm.hip).  The LayerNorm'ed rows are split ONCE (phase 0) into three bf16 planes in LDS
 // ([plane 3][chunk 4][k-half 2][row][8 channels], shared by all 8 heads x {q,k,v}), the pre-split weight fragments
 // (pack_bf3 image [4][3][2][768][8]) are read straight from L2 one chunk ahead: 24 bf16 MFMAs (768 cycles) replace
 // 32 fp32 MFMAs (2048 cycles) per 32x32 projection tile, and the per-head weight staging + its barrier disappear.
@@ -492,7 +492,7 @@ __global__ __launch_bounds__(512) void temporal_layer_c64_kernel(
 // WMODE 3: EVERY large contraction of the layer on the bf16 matrix pipe with exactly split operands (fp32 results):
 // besides the Q/K/V projections (WMODE 2) also S^T = K . Q^T and O^T = V^T . P^T.  The fp32 versions of those two cost
 // 2 x 4096 MFMA cycles per (32-query tile, head) on v_mfma_f32_32x32x2_f32; with K / Q / V / P each written as three
-// bf16 pieces and the 6 cross terms down to 2^-16 (conv_gemm.hip) they cost 2 x 1536.
+// bf16 pieces and the 6 cross terms down to 2^-16 (conv3x3_halo_bf16_kernel, conv_gemm.hip) they cost 2 x 1536.
 //   * K is split ONCE per head by the wave that projects it (after the rotary) into three bf16 planes in LDS
 //     ([plane][d-chunk 2][k-half 2][row] x 16 B: the A fragment of a key tile is one ds_read_b128 per plane and chunk);
 //   * V is projected NON-transposed (operands swapped: D = X . Wv, lane = feature d, registers = keys), so that a lane

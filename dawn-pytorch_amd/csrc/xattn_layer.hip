@@ -39,7 +39,7 @@ __device__ __forceinline__ f32x16 zz16() {
 __device__ __forceinline__ float x32(float v) { return v + __shfl_xor(v, 32, 64); }
 
 // SPLIT: to_q -- 87 % of the kernel's matrix work -- on the bf16 pipe with the exact 3-way operand split (6 cross terms, fp32
-// accumulate, see conv_gemm.hip): the pre-split weight planes (pack_bf3 image, [CIN/16][3][2][192][8]) take the place of the fp32
+// accumulate, see conv3x3_halo_bf16_kernel in conv_gemm.hip): the pre-split weight planes (pack_bf3 image, [CIN/16][3][2][192][8]) take the place of the fp32
 // weights in LDS (72 / 144 KB), the lane's LayerNorm'ed channels (8 consecutive ones per k-step: B operand, lane = pixel) are
 // split once per tile in registers.  144 (288) bf16 MFMAs of 32 cycles instead of 192 (384) fp32 ones of 64 per tile.
 typedef dawn_bf16x8 bf16x8x;

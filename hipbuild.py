@@ -39,8 +39,10 @@ PRESETS = {
                      out="tools/ubench/libdawn_hip_sktiming.bin"),
     # window-tiled temporal layer with -DDAWN_TL16_DUMP (tools/debug_tl16_dump.py) or -DDAWN_TL_TIMING (tools/tl16_phase_timing.py)
     "tl16debug": dict(flags={"temporal_layer16": CLI_FLAGS}, out="tools/ubench/libdawn_hip_tl16debug.bin"),
-    # temporal layer stamps + conv ablations / dawn_conv_set_debug / policy 0x40000000 (tools/bench_resample.py)
-    "ablation": dict(flags={"temporal_layer": ["-DDAWN_TL_TIMING"], "conv_gemm": ["-DDAWN_ABLATION"]},
+    # temporal layer stamps + conv ablations / dawn_conv_set_debug / policy 0x40000000 (tools/bench_resample.py).  Every unit of the
+    # conv / GEMM family takes the flag: conv_split.h, which all four include, derives the policy mask from it
+    "ablation": dict(flags={"temporal_layer": ["-DDAWN_TL_TIMING"],
+                            **{u: ["-DDAWN_ABLATION"] for u in ("conv_gemm", "conv3x3_split", "gemm1x1_tiled", "gemm1x1_rows")}},
                      out="tools/ubench/libdawn_hip_ablation.bin"),
 }
 

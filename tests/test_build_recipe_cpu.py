@@ -14,7 +14,7 @@ DROPPED = {}   # preset -> csrc stems it leaves out on purpose (none today)
 
 def test_shipped_source_set_is_the_csrc_glob():
     assert hipbuild.sources() == sorted(CSRC.glob("*.hip"))
-    assert {"dawn_api", "conv_gemm", "temporal_layer16"} <= {s.stem for s in hipbuild.sources()}
+    assert {"dawn_api", "conv_gemm", "conv3x3_split", "gemm1x1_tiled", "gemm1x1_rows", "temporal_layer16"} <= {s.stem for s in hipbuild.sources()}
     assert [o for _, o, f in hipbuild.shipped_units()] == [Path(ROOT, "build", s.stem + ".o") for s in hipbuild.sources()]
 
 
@@ -39,7 +39,8 @@ def test_presets_keep_their_flags_and_outputs():
     flags = {name: {s.stem: f for s, _, f in hipbuild.preset_units(name, ["-DX"]) if f is not None} for name in hipbuild.PRESETS}
     assert flags["sktiming"] == {"conv_gemm": ["-DDAWN_WITH_STREAMK"], "conv3x3_sk": ["-DDAWN_ABLATION"]}
     assert flags["tl16debug"] == {"temporal_layer16": ["-DX"]}
-    assert flags["ablation"] == {"temporal_layer": ["-DDAWN_TL_TIMING"], "conv_gemm": ["-DDAWN_ABLATION"]}
+    assert flags["ablation"] == {"temporal_layer": ["-DDAWN_TL_TIMING"], "conv_gemm": ["-DDAWN_ABLATION"], "conv3x3_split": ["-DDAWN_ABLATION"],
+                                 "gemm1x1_tiled": ["-DDAWN_ABLATION"], "gemm1x1_rows": ["-DDAWN_ABLATION"]}
     for p in hipbuild.PRESETS.values():
         assert p["out"].startswith("tools/ubench/") and p["out"].endswith(".bin")
 

@@ -1,4 +1,4 @@
-"""The stage wait of gemm1x1_bf16_kernel (`s_waitcnt vmcnt(NQ) lgkmcnt(0)`, csrc/conv_gemm.hip) lets the NQ youngest memory operations stay in
+"""The stage wait of gemm1x1_bf16_kernel (`s_waitcnt vmcnt(NQ) lgkmcnt(0)`, csrc/gemm1x1_tiled.hip) lets the NQ youngest memory operations stay in
 flight and names them the A rows of the next stage.  That is only true while every stage issues its weight LDS-DMA BEFORE its A-row loads;
 a `sched_barrier(0)` between issueB and loadA states it in the source.  This test checks it in the device code of the built object: in the
 prologue and in each stage, every LDS-DMA `buffer_load ... lds` precedes every A-row `buffer_load`, and both precede the next stage wait.
@@ -25,8 +25,8 @@ def llvm_bin():
     return None
 
 
-OBJ = os.path.join(ROOT, "build", "conv_gemm.o")
-SRC = os.path.join(ROOT, "dawn-pytorch_amd", "csrc", "conv_gemm.hip")
+OBJ = os.path.join(ROOT, "build", "gemm1x1_tiled.o")
+SRC = os.path.join(ROOT, "dawn-pytorch_amd", "csrc", "gemm1x1_tiled.hip")
 KERNEL = re.compile(r"_ZN12_GLOBAL__N_119gemm1x1_bf16_kernelILi(\d+)ELi(\d+)ELi(\d+)EEEv14dawn_conv_descl")
 STAGE_WAIT = re.compile(r"^s_waitcnt vmcnt\((4|8)\) lgkmcnt\(0\)")
 DMA = re.compile(r"^buffer_load_dword\S*\s.*\slds$")

@@ -162,7 +162,7 @@ def test_product_path_fails_loudly_without_gpu(tiny):
 def test_pack_bf3_is_an_exact_three_way_split():
     """pack_bf3 (host side of the split-operand kernels): the three bf16 planes sum EXACTLY to the fp32 weight,
     each plane is the round-to-nearest-even bf16 of the running residual, and the layout is [K/16][3][2][N][8]
-    with k = 16*chunk + 8*half + e  (csrc/conv_gemm.hip reads plane p / k-half h / column n at ((c*3+p)*2+h)*N+n)."""
+    with k = 16*chunk + 8*half + e  (the split-operand kernels -- csrc/conv_split.h names their files -- read plane p / k-half h / column n at ((c*3+p)*2+h)*N+n)."""
     from dawn_pytorch_amd.pack import pack_bf3
     g = torch.Generator().manual_seed(7)
     K, N = 48, 20

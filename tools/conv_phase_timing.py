@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """GPU tool: per-phase s_memtime profile of the split-operand 3x3 conv kernel (instrumented build, ABL bit 3).
     python tools/conv_phase_timing.py [--case l0_3x3_cat]
-Prints, averaged over workgroups, the cycles between consecutive stamps (see TSTAMP() in conv_gemm.hip)."""
+Prints, averaged over workgroups, the cycles between consecutive stamps (see TSTAMP() in conv3x3_split.hip)."""
 import argparse, ctypes, os, sys
 import numpy as np
 import torch

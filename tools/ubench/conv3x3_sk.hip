@@ -1,6 +1,6 @@
 // Third-generation split-operand 3x3 convolution: PERSISTENT workgroups + stream-K balance (gfx950).
 //
-// Same arithmetic as conv3x3_bf16_v2_kernel (conv_gemm.hip): every 3x3 ResBlock conv (MT:229 Block.proj inside MT:233-248)
+// Same arithmetic as conv3x3_bf16_v2_kernel (conv3x3_split.hip): every 3x3 ResBlock conv (MT:229 Block.proj inside MT:233-248)
 // as an implicit GEMM on v_mfma_f32_32x32x16_bf16 with the exact 3-way operand split (x = x1+x2+x3, w = w1+w2+w3 as bf16,
 // six cross terms, fp32 accumulate), 256-pixel x 64-channel tiles, the (TR+2) x (WT+2) halo patch of a 16-channel chunk
 // staged once in LDS as three bf16 planes, weights by LDS-DMA one kernel row (3 taps) at a time.  What changes is the
