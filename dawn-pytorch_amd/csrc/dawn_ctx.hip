@@ -87,6 +87,8 @@ struct dawn_ctx {
     int conv_policy = 0, temporal_flags = 0, overlap = 1;
     int up_border = 0;              // dawn_conv_desc.border of the Upsample launches (DAWN_OPT_UP_BORDER)
     int long_clip_frames = 4096;    // unet_forward.LONG_CLIP_FRAMES: clips longer than this run the memory-lean form (DAWN_OPT_LONG_CLIP_FRAMES)
+    int fold_heads = 1;             // the heads end in one dawn_heads_eps launch (DAWN_OPT_FOLD_HEADS; 0: res_conv GEMMs + dawn_head_out)
+    float* heads_fold = nullptr;    // device, owned: Wf (3, 2 dim) then bf (3) of dawn_fold_heads; nullptr where the heads cannot be folded
     Arena arena;
     // profiling of conv launches (bench.py roofline): optional
     bool prof_on = false;
@@ -404,8 +406,10 @@ struct Eval {
 
     // pre_c1 / pre_ab1: conv1 + coefficients computed by the caller (the guided evaluation's shared prefix; the caller owns them);
     // keep_pre: another branch reads them again, so h1 gets a tensor of its own instead of being written over c1
+    // tail_ab2: the block stops after conv2 + its GroupNorm coefficients and returns c2, *tail_ab2 = (a2 | b2) (the caller releases both):
+    // the folded heads, whose SiLU(GN(c2)) + res_conv happens inside dawn_heads_eps
     T2 resblock(const RB& rb, const T2& x, const T2* x2, int Fr, int H, int W, const float* film_all, const T2* pre_c1 = nullptr,
-                float* pre_ab1 = nullptr, bool keep_pre = false) {
+                float* pre_ab1 = nullptr, bool keep_pre = false, float** tail_ab2 = nullptr) {
         const int Co = rb.Co, HW = H * W;
         const long rows = (long)Fr * HW, total_rows = rows;
         T2 hcond;
@@ -490,6 +494,11 @@ struct Eval {
         }
         rel(h1);
         gn_coeffs(part2, nblk2, total_rows, Co, rb.g2, rb.be2, nullptr, nullptr, ab2, ab2 + Co);
+        if (tail_ab2) {
+            A.free(part2);
+            *tail_ab2 = ab2;
+            return c2;
+        }
         T2 out;
         if (rb.wr) {
             out = t2(rows, Co);
@@ -816,10 +825,25 @@ struct Eval {
                 H *= 2; W *= 2;
             }
         }
+        const long rows = (long)F * H * W;
+        const bool fold = c->fold_heads && c->heads_fold;
+        const float *Wf = c->heads_fold, *bf = c->heads_fold ? c->heads_fold + 3 * 2 * (size_t)dim : nullptr;
         if (lean) {
             // ... and the heads run one after the other, each projected to its rows of eps and dropped before the other one runs
-            r = t2((long)F * H * W, dim);
+            r = t2(rows, dim);
             LAUNCH(dawn_init_conv_x(x3, c->w3, clipf(L.fea_pre), F, H, W, dim, r.p, cur));
+            if (fold) {
+                float* ab = nullptr;
+                T2 c2 = resblock(c->head_g, x, &r, F, H, W, film, nullptr, nullptr, false, &ab);
+                LAUNCH(dawn_heads_eps(c2.p, ab, ab + dim, nullptr, nullptr, nullptr, x.p, x.C, x.C, r.p, r.C, r.C, c->wg, c->wo, Wf, bf, rows,
+                                      dim, eps_out, cur));
+                rel(c2); A.free(ab);
+                c2 = resblock(c->head_o, x, &r, F, H, W, film, nullptr, nullptr, false, &ab);
+                LAUNCH(dawn_heads_eps(nullptr, nullptr, nullptr, c2.p, ab, ab + dim, x.p, x.C, x.C, r.p, r.C, r.C, c->wg, c->wo, Wf, bf, rows,
+                                      dim, eps_out, cur));
+                rel(x); rel(r); rel(c2); A.free(ab);
+                return;
+            }
             T2 hg = resblock(c->head_g, x, &r, F, H, W, film);
             LAUNCH(dawn_head_out(hg.p, nullptr, c->wg, c->bg, c->wo, c->bo, (long)F * H * W, hg.C, eps_out, cur));
             rel(hg);
@@ -827,6 +851,17 @@ struct Eval {
             rel(x); rel(r);
             LAUNCH(dawn_head_out(nullptr, ho.p, c->wg, c->bg, c->wo, c->bo, (long)F * H * W, ho.C, eps_out, cur));
             rel(ho);
+        } else if (fold) {
+            // both blocks stop at conv2: SiLU(GN(c2)), the folded res_conv of [x | r] (torch.cat((x, r)) MT:955) and the projection are
+            // one launch; x and r live until it is enqueued (r beyond it while another branch reads the prefix)
+            float *abg = nullptr, *abo = nullptr;
+            T2 cg = resblock(c->head_g, x, &r, F, H, W, film, nullptr, nullptr, false, &abg);
+            T2 co = resblock(c->head_o, x, &r, F, H, W, film, nullptr, nullptr, false, &abo);
+            LAUNCH(dawn_heads_eps(cg.p, abg, abg + dim, co.p, abo, abo + dim, x.p, x.C, x.C, r.p, r.C, r.C, c->wg, c->wo, Wf, bf, rows, dim,
+                                  eps_out, cur));
+            rel(x);
+            if (!keep) rel(r);
+            rel(cg); rel(co); A.free(abg); A.free(abo);
         } else {
             T2 hg = resblock(c->head_g, x, &r, F, H, W, film);            // torch.cat((x, r)) MT:955
             T2 ho = resblock(c->head_o, x, &r, F, H, W, film);
@@ -887,6 +922,32 @@ int build_levels(dawn_ctx* c) {
     return 0;
 }
 
+// The heads' res_conv folded into the output projection (dawn_fold_heads: the one implementation, the Python packer calls it too), once
+// per ctx: the weights come back to the host, res_conv from its packed [Cin/4][Co][4] image to the (Co, Cin) the helper takes.
+int fold_heads(dawn_ctx* c) {
+    const int Co = c->cfg.dim, Cin = 2 * Co;
+    if (!c->head_g.wr || !c->head_o.wr || Co > 256) return 0;      // (nothing to fold / wider than dawn_heads_eps takes: the unfolded sequence runs)
+    std::vector<float> wg(2 * Co), bg(2), wo(Co), bo(1), br[2], wr[2], pk((size_t)Cin * Co), f(3 * (size_t)Cin + 3);
+    HCK(hipMemcpy(wg.data(), c->wg, wg.size() * 4, hipMemcpyDeviceToHost));
+    HCK(hipMemcpy(bg.data(), c->bg, bg.size() * 4, hipMemcpyDeviceToHost));
+    HCK(hipMemcpy(wo.data(), c->wo, wo.size() * 4, hipMemcpyDeviceToHost));
+    HCK(hipMemcpy(bo.data(), c->bo, bo.size() * 4, hipMemcpyDeviceToHost));
+    const RB* heads[2] = {&c->head_g, &c->head_o};
+    for (int h = 0; h < 2; ++h) {
+        br[h].resize(Co);
+        wr[h].resize((size_t)Co * Cin);
+        HCK(hipMemcpy(br[h].data(), heads[h]->br, (size_t)Co * 4, hipMemcpyDeviceToHost));
+        HCK(hipMemcpy(pk.data(), heads[h]->wr, pk.size() * 4, hipMemcpyDeviceToHost));
+        for (int k = 0; k < Cin; ++k)
+            for (int co = 0; co < Co; ++co) wr[h][(size_t)co * Cin + k] = pk[((size_t)(k / 4) * Co + co) * 4 + k % 4];
+    }
+    CK(dawn_fold_heads(wg.data(), bg.data(), wo.data(), bo.data(), wr[0].data(), br[0].data(), wr[1].data(), br[1].data(), Co, Cin,
+                       f.data(), f.data() + 3 * (size_t)Cin));
+    HCK(hipMalloc((void**)&c->heads_fold, f.size() * 4));
+    HCK(hipMemcpy(c->heads_fold, f.data(), f.size() * 4, hipMemcpyHostToDevice));
+    return 0;
+}
+
 }  // namespace
 
 extern "C" int dawn_rel_pos_bucket(int rel) { return rel_pos_bucket(rel); }
@@ -919,7 +980,8 @@ extern "C" int dawn_ctx_create(const dawn_unet_cfg* cfg, const dawn_named_ptr* w
         if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming);
         if (e != hipSuccess) rc = dawn_set_error(e, __FILE__, __LINE__);
     }
-    if (rc != 0) { delete c; return rc; }
+    if (rc == 0) rc = fold_heads(c);
+    if (rc != 0) { dawn_ctx_destroy(c); return rc; }
     *out = c;
     return 0;
 }
@@ -931,6 +993,7 @@ extern "C" void dawn_ctx_destroy(dawn_ctx* c) {
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
     for (auto& p : c->prof) { (void)hipEventDestroy(p.e0); (void)hipEventDestroy(p.e1); }
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
+    if (c->heads_fold) (void)hipFree(c->heads_fold);
     delete c;
 }
 
@@ -944,6 +1007,7 @@ extern "C" int dawn_ctx_set_option(dawn_ctx* c, int option, int value) {
         case DAWN_OPT_OVERLAP: c->overlap = value ? 1 : 0; return 0;
         case DAWN_OPT_LONG_CLIP_FRAMES: c->long_clip_frames = value > 0 ? value : 4096; return 0;
         case DAWN_OPT_UP_BORDER: c->up_border = value; return 0;
+        case DAWN_OPT_FOLD_HEADS: c->fold_heads = value ? 1 : 0; return 0;
         case DAWN_OPT_PROFILE:
             c->prof_on = value != 0;
             return 0;

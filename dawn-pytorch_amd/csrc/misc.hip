@@ -155,6 +155,93 @@ __global__ __launch_bounds__(256) void head_out_kernel(const float* __restrict__
     }
 }
 
+// Both head blocks' tails and the output projection in one streaming pass (the heads' res_conv folded into the projection: both are
+// linear and nothing sits between them).  Per row, with [x|r] = [in0 | in1]:
+//   eps[0:2] = Wg.SiLU(a2g*c2g + b2g) + Wf[0:2].[x|r] + bf[0:2]        Wf[0:2] = Wg.Wr_g, bf[0:2] = Wg.br_g + bg
+//   eps[2]   = Wo.SiLU(a2o*c2o + b2o) + Wf[2].[x|r]   + bf[2]          Wf[2]   = Wo.Wr_o, bf[2]   = Wo.br_o + bo   (dawn_fold_heads)
+// so the 128 -> 64 res_conv GEMMs and the hg / ho tensors never exist.  head_out_kernel's layout: 16 lanes per row, a lane owns the
+// channel quads sub*4 + 64 q of every source and keeps their weights / GroupNorm coefficients in registers; a thread walks HEADS_RPT
+// rows (all their loads issued before the first use).  c2g or c2o may be NULL: only the other head's rows of eps are written.
+constexpr int HEADS_RPT = 4;
+template <int NQ>
+__global__ __launch_bounds__(256) void heads_eps_kernel(const float* __restrict__ c2g, const float* __restrict__ a2g, const float* __restrict__ b2g,
+                                                        const float* __restrict__ c2o, const float* __restrict__ a2o, const float* __restrict__ b2o,
+                                                        const float* __restrict__ in0, int ld0, int C0, const float* __restrict__ in1, int ld1, int C1,
+                                                        const float* __restrict__ wg, const float* __restrict__ wo, const float* __restrict__ Wf,
+                                                        const float* __restrict__ bf, long rows, int Co, float* __restrict__ eps_out) {
+    const int sub = threadIdx.x & 15;
+    const long row0 = (long)blockIdx.x * (16 * HEADS_RPT) + (threadIdx.x >> 4);
+    const int Cin = C0 + C1;
+    const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
+    // a lane's constants; quads past the end of a source keep zero weights and are never loaded
+    f32x4 wg0[NQ], wg1[NQ], wo2[NQ], ag[NQ], bgn[NQ], ao[NQ], bon[NQ], f0[NQ][3], f1[NQ][3];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+        const int c = sub * 4 + 64 * q;
+        wg0[q] = wg1[q] = wo2[q] = ag[q] = bgn[q] = ao[q] = bon[q] = z4;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) f0[q][j] = f1[q][j] = z4;
+        if (c < Co) {
+            if (c2g) {
+                wg0[q] = *reinterpret_cast<const f32x4*>(wg + c);
+                wg1[q] = *reinterpret_cast<const f32x4*>(wg + Co + c);
+                ag[q] = *reinterpret_cast<const f32x4*>(a2g + c);
+                bgn[q] = *reinterpret_cast<const f32x4*>(b2g + c);
+            }
+            if (c2o) {
+                wo2[q] = *reinterpret_cast<const f32x4*>(wo + c);
+                ao[q] = *reinterpret_cast<const f32x4*>(a2o + c);
+                bon[q] = *reinterpret_cast<const f32x4*>(b2o + c);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            if (c < C0) f0[q][j] = *reinterpret_cast<const f32x4*>(Wf + (long)j * Cin + c);
+            if (c < C1) f1[q][j] = *reinterpret_cast<const f32x4*>(Wf + (long)j * Cin + C0 + c);
+        }
+    }
+    f32x4 vg[HEADS_RPT][NQ], vo[HEADS_RPT][NQ], v0[HEADS_RPT][NQ], v1[HEADS_RPT][NQ];
+#pragma unroll
+    for (int i = 0; i < HEADS_RPT; ++i) {
+        const long row = row0 + 16 * i;
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            const int c = sub * 4 + 64 * q;
+            const bool in = row < rows;
+            vg[i][q] = (in && c2g && c < Co) ? *reinterpret_cast<const f32x4*>(c2g + row * Co + c) : z4;
+            vo[i][q] = (in && c2o && c < Co) ? *reinterpret_cast<const f32x4*>(c2o + row * Co + c) : z4;
+            v0[i][q] = (in && c < C0) ? *reinterpret_cast<const f32x4*>(in0 + row * ld0 + c) : z4;
+            v1[i][q] = (in && c < C1) ? *reinterpret_cast<const f32x4*>(in1 + row * ld1 + c) : z4;
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < HEADS_RPT; ++i) {
+        const long row = row0 + 16 * i;
+        float e0 = 0.f, e1 = 0.f, e2 = 0.f;
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                // (zero weights past a source's end: SiLU(0) * 0 and 0 * 0 add nothing)
+                const float sg = dawn_silu(vg[i][q][e] * ag[q][e] + bgn[q][e]);
+                const float so = dawn_silu(vo[i][q][e] * ao[q][e] + bon[q][e]);
+                const float x0 = v0[i][q][e], x1 = v1[i][q][e];
+                e0 += sg * wg0[q][e] + x0 * f0[q][0][e] + x1 * f1[q][0][e];
+                e1 += sg * wg1[q][e] + x0 * f0[q][1][e] + x1 * f1[q][1][e];
+                e2 += so * wo2[q][e] + x0 * f0[q][2][e] + x1 * f1[q][2][e];
+            }
+        }
+        e0 = wave_sum(e0, 16); e1 = wave_sum(e1, 16); e2 = wave_sum(e2, 16);
+        if (row < rows && sub == 0) {
+            if (c2g) {
+                eps_out[row] = e0 + bf[0];
+                eps_out[rows + row] = e1 + bf[1];
+            }
+            if (c2o) eps_out[2 * rows + row] = e2 + bf[2];
+        }
+    }
+}
+
 // out[m][n] = bias[n] + sum_k act(in[m][k]) * W[n][k]; one wave per output element.
 __global__ __launch_bounds__(256) void linear_kernel(const float* __restrict__ in, int M, int K, int ld_in,
                                                      const float* __restrict__ W, const float* __restrict__ bias, int N,
@@ -220,6 +307,53 @@ extern "C" int dawn_head_out(const float* hg, const float* ho, const float* wg, 
     hipLaunchKernelGGL(head_out_kernel, dim3(dawn_cdiv(rows, 16)), dim3(256), 0, (hipStream_t)stream, hg, ho, wg, bg,
                        wo, bo, rows, Co, eps_out);
     DAWN_LAUNCH_CHECK();
+    return 0;
+}
+extern "C" int dawn_heads_eps(const float* c2g, const float* a2g, const float* b2g, const float* c2o, const float* a2o, const float* b2o,
+                              const float* in0, int ld0, int C0, const float* in1, int ld1, int C1, const float* wg, const float* wo,
+                              const float* Wf, const float* bf, long rows, int Co, float* eps_out, void* stream) {
+    if (Co <= 0 || Co % 4 != 0 || C0 <= 0 || C0 % 4 != 0 || C1 < 0 || C1 % 4 != 0 || ld0 % 4 != 0 || ld1 % 4 != 0 || ld0 < C0 || ld1 < C1)
+        return dawn_set_error_msg(-62, "dawn_heads_eps: Co, C0, C1, ld0 and ld1 must be multiples of 4 (ld >= C)");
+    if (Co > 256 || C0 > 256 || C1 > 256) return dawn_set_error_msg(-62, "dawn_heads_eps: more than 256 channels in one source");
+    if ((!c2g && !c2o) || !in0 || (C1 > 0 && !in1) || !Wf || !bf || !eps_out || (c2g && (!a2g || !b2g || !wg)) || (c2o && (!a2o || !b2o || !wo)))
+        return dawn_set_error_msg(-62, "dawn_heads_eps: null argument");
+    const uintptr_t al = (uintptr_t)c2g | (uintptr_t)a2g | (uintptr_t)b2g | (uintptr_t)c2o | (uintptr_t)a2o | (uintptr_t)b2o | (uintptr_t)in0 |
+                         (uintptr_t)in1 | (uintptr_t)wg | (uintptr_t)wo | (uintptr_t)Wf;
+    if (al & 15) return dawn_set_error_msg(-62, "dawn_heads_eps: pointers must be 16-byte aligned");
+    if (rows <= 0) return 0;
+    const int mc = Co > C0 ? (Co > C1 ? Co : C1) : (C0 > C1 ? C0 : C1);
+    const dim3 grid(dawn_cdiv(rows, 16 * HEADS_RPT)), block(256);
+#define HEADS_LAUNCH(NQ)                                                                                                              \
+    hipLaunchKernelGGL(heads_eps_kernel<NQ>, grid, block, 0, (hipStream_t)stream, c2g, a2g, b2g, c2o, a2o, b2o, in0, ld0, C0, in1, ld1, C1, \
+                       wg, wo, Wf, bf, rows, Co, eps_out)
+    if (mc <= 64) HEADS_LAUNCH(1);
+    else if (mc <= 128) HEADS_LAUNCH(2);
+    else HEADS_LAUNCH(4);
+#undef HEADS_LAUNCH
+    DAWN_LAUNCH_CHECK();
+    return 0;
+}
+// Host: the heads' res_conv folded into the output projection (heads_eps_kernel).  wg (2, Co), wo (1, Co), wr_g / wr_o (Co, Cin) row-major,
+// all host memory -> Wf (3, Cin), bf (3).  Every sum runs over co = 0 .. Co-1 in fp64 (the products of two fp32 values are exact there)
+// and is rounded to fp32 once; both hosts call this one function, so they hold the same bits.
+extern "C" int dawn_fold_heads(const float* wg, const float* bg, const float* wo, const float* bo, const float* wr_g, const float* br_g,
+                               const float* wr_o, const float* br_o, int Co, int Cin, float* Wf, float* bf) {
+    if (!wg || !bg || !wo || !bo || !wr_g || !br_g || !wr_o || !br_o || !Wf || !bf || Co <= 0 || Cin <= 0)
+        return dawn_set_error_msg(-63, "dawn_fold_heads: null argument or empty shape");
+    for (int j = 0; j < 3; ++j) {
+        const float* w = j < 2 ? wg + (long)j * Co : wo;
+        const float* wr = j < 2 ? wr_g : wr_o;
+        const float* br = j < 2 ? br_g : br_o;
+        for (int k = 0; k < Cin; ++k) {
+            double s = 0.0;
+            for (int co = 0; co < Co; ++co) s += (double)w[co] * (double)wr[(long)co * Cin + k];
+            Wf[(long)j * Cin + k] = (float)s;
+        }
+        double s = 0.0;
+        for (int co = 0; co < Co; ++co) s += (double)w[co] * (double)br[co];
+        s += (double)(j < 2 ? bg[j] : bo[0]);
+        bf[j] = (float)s;
+    }
     return 0;
 }
 extern "C" int dawn_linear(const float* in, int M, int K, int ld_in, const float* W, const float* bias, int N,

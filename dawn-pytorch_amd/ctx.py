@@ -7,6 +7,7 @@ PyTorch only provides device memory (the packed weights, the per-clip table memo
 from __future__ import annotations
 
 import ctypes as C
+import os
 from typing import Dict, List, Optional, Sequence
 
 import torch
@@ -54,7 +55,7 @@ def _clip_struct(clip, ancestral: bool) -> ClipMode:
     return ClipMode(CLIP_KINDS[kind], 0.0 if q is None else q)
 
 
-OPT_CONV_POLICY, OPT_TEMPORAL_FLAGS, OPT_OVERLAP, OPT_PROFILE, OPT_LONG_CLIP_FRAMES, OPT_UP_BORDER = 1, 2, 3, 4, 5, 6
+OPT_CONV_POLICY, OPT_TEMPORAL_FLAGS, OPT_OVERLAP, OPT_PROFILE, OPT_LONG_CLIP_FRAMES, OPT_UP_BORDER, OPT_FOLD_HEADS = 1, 2, 3, 4, 5, 6, 7
 
 # ---- T-shard callbacks (include/dawn_hip.h: dawn_shard_comm)
 HALO_BEGIN_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_long, C.c_void_p)
@@ -230,6 +231,8 @@ class CtxEvaluator:
         self._policy = 0
         if P.up_border:              # folded up convs (use_deconv=False): what their outside taps read
             self.set_option(OPT_UP_BORDER, P.up_border)
+        if os.environ.get("DAWN_FOLD_HEADS", "1") == "0":      # (the A/B switch HipOps.fold_heads reads: both hosts follow it)
+            self.set_option(OPT_FOLD_HEADS, 0)
 
     def __del__(self):
         h, self.h = getattr(self, "h", None), None

@@ -11,6 +11,7 @@ on CPU and to check every kernel individually on the GPU.
 from __future__ import annotations
 
 import ctypes as C
+import os
 from typing import Optional, Tuple
 
 import torch
@@ -55,6 +56,9 @@ class HipOps:
         self.temporal_attn_flags = 0  # dawn_temporal_attn_ex flags (1 = the fp32-MFMA attention core; A/B and tests)
         self.sk_ws = None            # experimental library only (hipbuild.py sktiming): scratch tensor handed to dawn_conv_desc.sk_ws
         self.fuse_h1 = True          # cross-attention kernels write h1 = SiLU(GN(c1)) + h_cond themselves (False: A/B, two-stream form)
+        # the heads' res_conv folded into the output projection: both head blocks end in one heads_eps launch (False, or DAWN_FOLD_HEADS=0
+        # in the environment: A/B, res_conv GEMMs + head_out)
+        self.fold_heads = os.environ.get("DAWN_FOLD_HEADS", "1") != "0"
         self._sel_ws = {}            # (device index, stream) -> scratch of the threshold selection (histograms, state)
         self._tickets = {}           # (device index, stream) -> the zeroed device word of the convs' fused GroupNorm finalisation
         self.fuse_gn = True          # GroupNorm coefficients from the conv launch itself where the kernel can (False: A/B, separate launch)
@@ -88,6 +92,7 @@ class HipOps:
         o.temporal_attn_flags = self.temporal_attn_flags
         o.sk_ws = self.sk_ws
         o.fuse_h1 = self.fuse_h1
+        o.fold_heads = self.fold_heads
         o._sel_ws = self._sel_ws
         o._tickets = self._tickets
         o.fuse_gn = self.fuse_gn
@@ -509,6 +514,37 @@ class HipOps:
             out = self.empty(3, rows, like=ref)
         check(self.L.dawn_head_out(_p(hg), _p(ho), _p(wg), _p(bg), _p(wo), _p(bo), rows, Co, _p(out),
                                    self._stream()), "dawn_head_out")
+        return out
+
+    def heads_eps(self, gn_g: Optional[Tuple[Tensor, Tensor, Tensor]], gn_o: Optional[Tuple[Tensor, Tensor, Tensor]], x: Tensor,
+                  x2: Optional[Tensor], wg: Tensor, wo: Tensor, wf: Tensor, bf: Tensor, out: Optional[Tensor] = None) -> Optional[Tensor]:
+        """eps (3, rows) from the head blocks' conv2 outputs: gn_g / gn_o = (c2, a2, b2) of final_conv.0 / occlusion_map.0, [x | x2] the
+        blocks' input, wf / bf the folded res_conv (pack.fold_heads).  One of gn_g / gn_o may be None: only the other head's rows of
+        `out` are written.  Returns None where the kernel does not take the shapes (the caller runs res_conv + head_out)."""
+        ref = gn_g if gn_g is not None else gn_o
+        _need(ref is not None and (out is not None or (gn_g is not None and gn_o is not None)), "heads_eps: one head needs `out`")
+        rows, Co = ref[0].shape
+        C0, C1 = x.shape[1], 0 if x2 is None else x2.shape[1]
+        for t in (gn_g, gn_o):
+            _need(t is None or (t[0].is_contiguous() and t[0].shape == (rows, Co) and t[1].numel() == Co and t[2].numel() == Co),
+                  "heads_eps: c2 contiguous (rows, Co), a2 / b2 of Co elements")
+        _need(x.shape[0] == rows and (x2 is None or x2.shape[0] == rows) and wf.is_contiguous() and tuple(wf.shape) == (3, C0 + C1)
+              and bf.numel() == 3 and wg.is_contiguous() and tuple(wg.shape) == (2, Co) and wo.is_contiguous() and wo.numel() == Co,
+              "heads_eps: x / x2 of `rows` rows, wf (3, C0 + C1), bf (3,), wg (2, Co), wo (1, Co)")
+        flat = [u for t in (gn_g, gn_o) if t is not None for u in t]
+        self._require(x, x2, wg, wo, wf, bf, out, *flat)
+        ptrs = [x, x2, wg, wo, wf] + flat
+        if Co % 4 or C0 % 4 or C1 % 4 or _ld(x) % 4 or (x2 is not None and _ld(x2) % 4) or max(Co, C0, C1) > 256 \
+                or any(t is not None and t.data_ptr() % 16 for t in ptrs):
+            return None                                   # (what dawn_heads_eps refuses with an error code)
+        if out is None:
+            out = self.empty(3, rows, like=x)
+        _need(out.is_contiguous() and tuple(out.shape) == (3, rows), "heads_eps: out.is_contiguous() and out.shape == (3, rows)")
+        g3 = gn_g if gn_g is not None else (None, None, None)
+        o3 = gn_o if gn_o is not None else (None, None, None)
+        check(self.L.dawn_heads_eps(_p(g3[0]), _p(g3[1]), _p(g3[2]), _p(o3[0]), _p(o3[1]), _p(o3[2]), _p(x), _ld(x), C0, _p(x2),
+                                    0 if x2 is None else _ld(x2), C1, _p(wg), _p(wo), _p(wf), _p(bf), rows, Co, _p(out), self._stream()),
+              "dawn_heads_eps")
         return out
 
     def linear(self, x: Tensor, W: Tensor, bias: Optional[Tensor], act_in: int = 0,

@@ -162,6 +162,21 @@ def unpack_kn(wp: Tensor) -> Tensor:
     return wp.permute(0, 2, 1).reshape(K4 * 4, N)
 
 
+def fold_heads(wg: Tensor, bg: Tensor, wo: Tensor, bo: Tensor, wr_g: Tensor, br_g: Tensor, wr_o: Tensor, br_o: Tensor):
+    """The heads' res_conv folded into the output projection: Wf (3, Cin) = [Wg.Wr_g ; Wo.Wr_o], bf (3,) = [Wg.br_g + bg ; Wo.br_o + bo]
+    from wg (2, Co), wo (1, Co), wr (Co, Cin).  Computed by the library's host function dawn_fold_heads (fp64 sums in a fixed order,
+    rounded once) -- the C evaluator calls the same function, so both hosts hold the same bits."""
+    from . import _lib
+    Co, Cin = wr_g.shape
+    if not (tuple(wg.shape) == (2, Co) and tuple(wo.shape) == (1, Co) and tuple(wr_o.shape) == (Co, Cin) and bg.numel() == 2
+            and bo.numel() == 1 and br_g.numel() == Co and br_o.numel() == Co):
+        raise ValueError("fold_heads: wg (2, Co), wo (1, Co), wr (Co, Cin), bg (2,), bo (1,), br (Co,)")
+    host = [t.detach().to("cpu", torch.float32).contiguous() for t in (wg, bg, wo, bo, wr_g, br_g, wr_o, br_o)]
+    wf, bf = torch.empty(3, Cin, dtype=torch.float32), torch.empty(3, dtype=torch.float32)
+    _lib.check(_lib.lib().dawn_fold_heads(*[t.data_ptr() for t in host], Co, Cin, wf.data_ptr(), bf.data_ptr()), "dawn_fold_heads")
+    return wf, bf
+
+
 def conv_w_kn(w5: Tensor) -> Tensor:
     """Conv3d weight (Co, Ci, 1, kh, kw) -> (kh*kw*Ci, Co), k = (ky*kw + kx)*Ci + ci."""
     Co, Ci, _, kh, kw = w5.shape
@@ -306,6 +321,8 @@ class PackedUNet:
     bg: Tensor = None
     wo: Tensor = None
     bo: Tensor = None
+    heads_wf: Optional[Tensor] = None      # (3, 2 dim) / (3,): the heads' res_conv folded into wg / wo (fold_heads; ops.heads_eps); None where a
+    heads_bf: Optional[Tensor] = None      # head block has no res_conv
     rel_emb: Tensor = None                 # (32, 8)
     rot_freqs: Tensor = None               # (16,)
     sin_freqs: Tensor = None               # (dim/2,) SinusoidalPosEmb table (MT:157-159)
@@ -477,6 +494,12 @@ def pack_unet(sd: Dict[str, Tensor], win: int, device, prefix: str = "denoise_fn
     P.head_o = resblock("occlusion_map.0.")
     P.wg, P.bg = dev(g("final_conv.1.weight").reshape(2, -1)), dev(g("final_conv.1.bias"))
     P.wo, P.bo = dev(g("occlusion_map.1.weight").reshape(1, -1)), dev(g("occlusion_map.1.bias"))
+    if has("final_conv.0.res_conv.weight") and has("occlusion_map.0.res_conv.weight"):
+        # a derived weight image like the split / Winograd ones above: built once per packed model, a repack builds a new one
+        wf, bf = fold_heads(g("final_conv.1.weight").reshape(2, -1), g("final_conv.1.bias"), g("occlusion_map.1.weight").reshape(1, -1),
+                            g("occlusion_map.1.bias"), g("final_conv.0.res_conv.weight").reshape(dim, -1), g("final_conv.0.res_conv.bias"),
+                            g("occlusion_map.0.res_conv.weight").reshape(dim, -1), g("occlusion_map.0.res_conv.bias"))
+        P.heads_wf, P.heads_bf = dev(wf), dev(bf)
     P.film_w = dev(torch.cat(film_w, 0))
     P.film_b = dev(torch.cat(film_b, 0))
     P.n_cond_blocks = state["cond_idx"]

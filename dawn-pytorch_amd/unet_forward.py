@@ -116,6 +116,22 @@ def _resblock(ops, rb: PackedResBlock, x: Tensor, x2: Optional[Tensor], F: int, 
               cs: ClipState, pre=None, keep_pre: bool = False) -> Tensor:
     """pre = (c1, (a, b)) from _conv1_and_stats, computed by the caller (the guided evaluation's shared prefix); keep_pre: c1 is read
     again by another branch, so h1 is written to a tensor of its own instead of over c1."""
+    return _resblock_tail(ops, rb, x, x2, F, H, W, *_resblock_body(ops, rb, x, x2, F, H, W, film_all, cs, pre, keep_pre))
+
+
+def _resblock_tail(ops, rb: PackedResBlock, x: Tensor, x2: Optional[Tensor], F: int, H: int, W: int, c2: Tensor, a2: Tensor, b2: Tensor) -> Tensor:
+    """SiLU(GN(c2)) + res_conv([x | x2]) (or + x): the end of a ResBlock."""
+    if rb.wr is not None:
+        return ops.conv_gemm(x, rb.wr, rb.Co, in1=x2, bias=rb.br, tr=(c2, a2, b2), w_bf3=rb.wrs, F=F, Hi=H, Wi=W)
+    if not (x2 is None):
+        raise ValueError("x2 is None")
+    return ops.gn_apply_res(c2, a2, b2, x, inplace=True)
+
+
+def _resblock_body(ops, rb: PackedResBlock, x: Tensor, x2: Optional[Tensor], F: int, H: int, W: int, film_all: Tensor,
+                   cs: ClipState, pre=None, keep_pre: bool = False) -> Tuple[Tensor, Tensor, Tensor]:
+    """A ResBlock up to conv2 and its GroupNorm coefficients -> (c2, a2, b2).  The head blocks stop here when their res_conv is folded
+    into the output projection (ops.heads_eps applies SiLU(GN(c2)) itself)."""
     Co = rb.Co
     total_rows = cs.Ttotal * H * W
     g = dict(F=F, Hi=H, Wi=W)
@@ -176,11 +192,7 @@ def _resblock(ops, rb: PackedResBlock, x: Tensor, x2: Optional[Tensor], F: int, 
                        gn_fin=(rb.g2, rb.be2, None, total_rows), w_wino4=getattr(rb, "w2w4", None), **g)
     del h1
     a2, b2 = ops.gn_coeffs(c2, rb.g2, rb.be2, None, total_rows, part=part2)
-    if rb.wr is not None:
-        return ops.conv_gemm(x, rb.wr, Co, in1=x2, bias=rb.br, tr=(c2, a2, b2), w_bf3=rb.wrs, **g)
-    if not (x2 is None):
-        raise ValueError("x2 is None")
-    return ops.gn_apply_res(c2, a2, b2, x, inplace=True)
+    return c2, a2, b2
 
 
 def _chunks(a: int, b: int, n: int):
@@ -469,19 +481,45 @@ def _unet_rest(ops, P: PackedUNet, cs: ClipState, x3: Tensor, film_all: Tensor, 
             kw = {"border": P.up_border} if P.up_border else {}
             x = ops.conv_gemm(x, wu, x.shape[1], F=F, Hi=H, Wi=W, Ho=2 * H, Wo=2 * W, KH=2, KW=2, mode=1, bias=bu, w_bf3=wus, **kw)
             H, W = 2 * H, 2 * W
+    # the heads' res_conv folded into the output projection (P.heads_wf): each block stops at conv2 and one streaming kernel goes from
+    # (c2g, c2o, x, r) to eps.  Backends without the op (the torch reference ops) and fold_heads = False run the unfolded sequence, and so
+    # do shapes the kernel does not take (heads_eps returns None)
+    fold = hasattr(ops, "heads_eps") and getattr(ops, "fold_heads", True) and getattr(P, "heads_wf", None) is not None
     if r is None:
         # long clips: recompute the skip, and run the heads one after the other (each head's tensor is projected to its rows of eps and
         # dropped before the other head runs): 4 level-0 tensors at the peak instead of 5
         r = ops.init_conv_x(x3, P.w3, cs.fea_pre, F, H, W, P.dim)
-        hg = _resblock(ops, P.head_g, x, r, F, H, W, film_all, cs)
-        eps = ops.empty(3, F * H * W, like=hg)
+        if fold:
+            tg = _resblock_body(ops, P.head_g, x, r, F, H, W, film_all, cs)
+            eps = ops.empty(3, F * H * W, like=tg[0])
+            if ops.heads_eps(tg, None, x, r, P.wg, P.wo, P.heads_wf, P.heads_bf, out=eps) is not None:
+                del tg
+                to = _resblock_body(ops, P.head_o, x, r, F, H, W, film_all, cs)
+                if ops.heads_eps(None, to, x, r, P.wg, P.wo, P.heads_wf, P.heads_bf, out=eps) is None:
+                    raise ValueError("heads_eps took one head and refused the other")
+                return eps.reshape(3, F, H, W)
+            hg = _resblock_tail(ops, P.head_g, x, r, F, H, W, *tg)
+            del tg
+        else:
+            hg = _resblock(ops, P.head_g, x, r, F, H, W, film_all, cs)
+            eps = ops.empty(3, F * H * W, like=hg)
         ops.head_out(hg, None, P.wg, P.bg, P.wo, P.bo, out=eps)
         del hg
         ho = _resblock(ops, P.head_o, x, r, F, H, W, film_all, cs)
         ops.head_out(None, ho, P.wg, P.bg, P.wo, P.bo, out=eps)
         return eps.reshape(3, F, H, W)
-    hg = _resblock(ops, P.head_g, x, r, F, H, W, film_all, cs)               # torch.cat((x, r)) MT:955
-    ho = _resblock(ops, P.head_o, x, r, F, H, W, film_all, cs)
+    if fold:
+        tg = _resblock_body(ops, P.head_g, x, r, F, H, W, film_all, cs)      # torch.cat((x, r)) MT:955
+        to = _resblock_body(ops, P.head_o, x, r, F, H, W, film_all, cs)
+        eps = ops.heads_eps(tg, to, x, r, P.wg, P.wo, P.heads_wf, P.heads_bf)   # (3, rows)
+        if eps is not None:
+            return eps.reshape(3, F, H, W)
+        hg = _resblock_tail(ops, P.head_g, x, r, F, H, W, *tg)
+        ho = _resblock_tail(ops, P.head_o, x, r, F, H, W, *to)
+        del tg, to
+    else:
+        hg = _resblock(ops, P.head_g, x, r, F, H, W, film_all, cs)           # torch.cat((x, r)) MT:955
+        ho = _resblock(ops, P.head_o, x, r, F, H, W, film_all, cs)
     eps = ops.head_out(hg, ho, P.wg, P.bg, P.wo, P.bo)                        # (3, rows)
     return eps.reshape(3, F, H, W)
 

@@ -286,6 +286,20 @@ int dawn_init_conv_x(const float* x, const float* w3, const float* fea_pre, int 
  * other head's rows of eps_out are written ------ */
 int dawn_head_out(const float* hg, const float* ho, const float* wg, const float* bg, const float* wo,
                   const float* bo, long rows, int Co, float* eps_out, void* stream);
+/* ---- the same heads with each head block's res_conv (MT:417) folded into its output projection: one streaming kernel from the
+ * blocks' conv2 outputs to eps, eps[0:2] = Wg.SiLU(a2g*c2g + b2g) + Wf[0:2].[in0|in1] + bf[0:2], eps[2] = Wo.SiLU(a2o*c2o + b2o) +
+ * Wf[2].[in0|in1] + bf[2] (a2 / b2: the GroupNorm coefficients of dawn_gn_finalize, length Co; Wf (3, C0 + C1) and bf (3) from
+ * dawn_fold_heads, on the device).  c2g or c2o (with its a / b) may be NULL: only the other head's rows of eps_out (3, rows) are
+ * written.  Co, C0, C1, ld0, ld1 multiples of 4, at most 256 channels per source, 16-byte aligned pointers: anything else is
+ * refused with an error code (the caller then runs res_conv through dawn_conv_gemm and dawn_head_out) */
+int dawn_heads_eps(const float* c2g, const float* a2g, const float* b2g, const float* c2o, const float* a2o, const float* b2o,
+                   const float* in0, int ld0, int C0, const float* in1, int ld1, int C1, const float* wg, const float* wo,
+                   const float* Wf, const float* bf, long rows, int Co, float* eps_out, void* stream);
+/* host only (every pointer is host memory): Wf[0:2] = Wg.Wr_g, Wf[2] = Wo.Wr_o, bf = [Wg.br_g + bg ; Wo.br_o + bo] with wg (2, Co),
+ * wo (1, Co), wr_g / wr_o (Co, Cin) row-major (the res_conv weights as the checkpoint holds them); summed over co in ascending order
+ * in fp64 and rounded to fp32 once.  A constant of the model: computed once per packed model */
+int dawn_fold_heads(const float* wg, const float* bg, const float* wo, const float* bo, const float* wr_g, const float* br_g,
+                    const float* wr_o, const float* br_o, int Co, int Cin, float* Wf, float* bf);
 
 /* ---- small dense ops: time / condition MLPs (MT:366-384, 789-794) ----------------------------- */
 /* out[m][n] = bias[n] + sum_k act(in[m][k]) * W[n][k];  act_in: 0 none, 1 SiLU, 2 exact GELU */
@@ -448,14 +462,17 @@ typedef struct dawn_named_ptr { const char* name; const void* ptr; } dawn_named_
 int dawn_ctx_create(const dawn_unet_cfg* cfg, const dawn_named_ptr* weights, int n_weights, dawn_ctx** out);
 void dawn_ctx_destroy(dawn_ctx* ctx);
 enum { DAWN_OPT_CONV_POLICY = 1, DAWN_OPT_TEMPORAL_FLAGS = 2, DAWN_OPT_OVERLAP = 3, DAWN_OPT_PROFILE = 4, DAWN_OPT_LONG_CLIP_FRAMES = 5,
-       DAWN_OPT_UP_BORDER = 6 };
+       DAWN_OPT_UP_BORDER = 6, DAWN_OPT_FOLD_HEADS = 7 };
 /* tuning state lives in the ctx: conv policy bits (dawn_conv_desc.policy), temporal-layer kernel family, two-stream
  * overlap on/off, per-launch HIP events around every dawn_conv_gemm (read with dawn_ctx_profile_read), the clip length above which an
  * evaluation runs in its memory-lean form (default 4096 frames: qkv tensors of the unfused attention levels per frame segment, the
  * heads' skip recomputed, the heads one after the other: 4.65 instead of 7.8 MB of workspace per frame at 256x256 for ~3 % of time;
  * set it BEFORE dawn_workspace_bytes); DAWN_OPT_UP_BORDER = dawn_conv_desc.border of the Upsample launches (0 zero: the default,
  * and the only value for use_deconv=True weights; 1 edge: padding_mode reflect / replicate; 2 wrap: circular; anything else is an
- * error) -- it reaches dawn_unet_forward, the guided and sharded forwards and every dawn_sampler_run* entry */
+ * error) -- it reaches dawn_unet_forward, the guided and sharded forwards and every dawn_sampler_run* entry; DAWN_OPT_FOLD_HEADS
+ * (default 1; set it BEFORE dawn_workspace_bytes): the heads' res_conv folded into the output projection, the end of an evaluation is
+ * one dawn_heads_eps launch (0: res_conv through dawn_conv_gemm, then dawn_head_out).  The folded (3, 2 dim) matrix is computed in
+ * dawn_ctx_create with dawn_fold_heads and lives in a small device buffer that the ctx owns (the one exception to "no allocation") */
 int dawn_ctx_set_option(dawn_ctx* ctx, int option, int value);
 size_t dawn_clip_bytes(dawn_ctx* ctx, int F, int h, int w);
 size_t dawn_workspace_bytes(dawn_ctx* ctx, int F, int h, int w);      /* covers prepare, forward and sampler_run */
