@@ -124,6 +124,8 @@ SIGNATURES = {
     "dawn_final_conv_blend": [c_f, _i, _i, _i, _i, c_f, c_f, c_f, c_f, _l, c_f, _i, _i, c_f, c_f, _l, c_f],
     "dawn_frames_to_u8": [c_f, _l, _l, _d, _d, _d, _i, c_f, c_f],
     "dawn_final_conv_blend_u8": [c_f, _i, _i, _i, _i, c_f, c_f, c_f, c_f, _l, c_f, _i, _i, _d, _d, _d, _i, c_f, c_f],
+    "dawn_frames_to_yuv420": [c_f, _l, _i, _i, _i, _d, _d, _d, c_f, c_f],
+    "dawn_final_conv_blend_yuv420": [c_f, _i, _i, _i, _i, c_f, c_f, c_f, c_f, _l, c_f, _i, _i, _d, _d, _d, c_f, c_f],
     # whole-path flow decode (csrc/dawn_decoder.hip; handles, the cfg struct and the named-pointer table travel as void*: ctx.py)
     "dawn_decoder_create": [c_f, c_f, _i, c_f],
     "dawn_decoder_destroy": [c_f],
@@ -134,6 +136,9 @@ SIGNATURES = {
                          c_f],
     "dawn_decode_clip_conf": [c_f, _i, _i, _i, _i, _i, c_f, c_f, c_f, _l, c_f, _i, c_f, c_f, _l, c_f, C.POINTER(C.c_double), _i, c_f,
                               C.c_size_t, c_f],
+    "dawn_decode_clip_yuv420": [c_f, _i, _i, _i, _i, _i, c_f, c_f, c_f, _l, _i, c_f, C.POINTER(C.c_double), c_f, C.c_size_t, c_f],
+    "dawn_decode_clip_conf_yuv420": [c_f, _i, _i, _i, _i, _i, c_f, c_f, c_f, _l, c_f, _i, c_f, C.POINTER(C.c_double), c_f, C.c_size_t,
+                                     c_f],
     "dawn_wave_normalize": [c_f, _l, c_f, c_f, c_f],
     "dawn_hubert_conv0": [c_f, _l, c_f, c_f, _i, _i, _i, c_f, c_f],
     "dawn_ln_affine_act": [c_f, _l, _i, c_f, c_f, _f, _i, c_f, c_f],

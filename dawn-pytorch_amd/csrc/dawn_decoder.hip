@@ -178,6 +178,7 @@ struct Outputs {
     unsigned char* frames;
     double m[3];
     int bgr;
+    unsigned char* yuv;               // I420 frames (T, 3HW/2): the only output when set
 };
 
 // FlowDecoder._decode_frames for the frames [t0, t0 + n) of the clip.  g = grid planes of the chunk (gp floats apart); cf = the
@@ -236,7 +237,10 @@ int decode_chunk(const dawn_decoder* d, DawnArena& A, int H, int W, int n, int t
     A.free(prev);
     if (!dry) {
         const long fpix = (long)H * W;
-        if (o.out_vid) {
+        if (o.yuv) {
+            CK(dawn_final_conv_blend_yuv420(xf, n, H, W, C0, d->final_w7, d->final_bias, img3, g, gp, cf, h, w, o.m[0], o.m[1], o.m[2],
+                                            o.yuv + (long)t0 * (fpix / 2 * 3), stream));
+        } else if (o.out_vid) {
             float* ov = o.out_vid + (long)t0 * fpix;
             CK(dawn_final_conv_blend(xf, n, H, W, C0, d->final_w7, d->final_bias, img3, g, gp, cf, h, w, ov,
                                      o.warped_vid + (long)t0 * fpix, o.out_plane, stream));
@@ -255,15 +259,19 @@ int decode_chunk(const dawn_decoder* d, DawnArena& A, int H, int W, int n, int t
 int decode_clip(dawn_decoder* d, const char* who, int H, int W, int T, int h, int w, const float* img3, const void* skip_mem,
                 const float* grid, long grid_plane, const float* conf, const float* lat2, int chunk, float* out_vid, float* warped_vid,
                 long out_plane, unsigned char* frames_u8, const double* mean3, int bgr, void* workspace, size_t workspace_bytes,
-                void* stream) {
+                void* stream, unsigned char* frames_yuv = nullptr, bool yuv = false) {
     char m[200];
     if (!d) return dawn_set_error_msg(-233, "dawn_decode_clip: NULL decoder");
     CK(bad_size(d, H, W, who));
+    if (yuv && (H % 2 != 0 || W % 4 != 0 || !frames_yuv || ((uintptr_t)frames_yuv & 3) != 0)) {
+        snprintf(m, sizeof m, "%s: frames_yuv420 needs an even H, W %% 4 == 0 and a non-NULL 4-byte aligned buffer (H = %d, W = %d)", who, H, W);
+        return dawn_set_error_msg(-240, m);
+    }
     if ((out_vid == nullptr) != (warped_vid == nullptr)) {
         snprintf(m, sizeof m, "%s: out_vid and warped_vid come as a pair", who);
         return dawn_set_error_msg(-234, m);
     }
-    if (!out_vid && !frames_u8) {
+    if (!out_vid && !frames_u8 && !yuv) {
         snprintf(m, sizeof m, "%s: no output requested (out_vid / warped_vid and frames_u8 are all NULL)", who);
         return dawn_set_error_msg(-235, m);
     }
@@ -280,7 +288,7 @@ int decode_clip(dawn_decoder* d, const char* who, int H, int W, int T, int h, in
         snprintf(m, sizeof m, "%s: workspace of %zu bytes, %zu needed (dawn_decoder_workspace_bytes)", who, workspace_bytes, need);
         return dawn_set_error_msg(-232, m);
     }
-    Outputs o = {out_vid, warped_vid, out_plane, frames_u8, {0.0, 0.0, 0.0}, bgr ? 1 : 0};
+    Outputs o = {out_vid, warped_vid, out_plane, frames_u8, {0.0, 0.0, 0.0}, bgr ? 1 : 0, frames_yuv};
     if (mean3) { o.m[0] = mean3[0]; o.m[1] = mean3[1]; o.m[2] = mean3[2]; }
     for (int t0 = 0; t0 < T; t0 += chunk) {
         const int n = T - t0 < chunk ? T - t0 : chunk;
@@ -388,4 +396,21 @@ extern "C" int dawn_decode_clip_conf(dawn_decoder* dec, int H, int W, int T, int
     if (!conf) return dawn_set_error_msg(-238, "dawn_decode_clip_conf: NULL conf");
     return decode_clip(dec, "dawn_decode_clip_conf", H, W, T, h, w, img3, skip_mem, grid, grid_plane, conf, nullptr, chunk, out_vid,
                        warped_vid, out_plane, frames_u8, mean3, bgr, workspace, workspace_bytes, stream);
+}
+
+extern "C" int dawn_decode_clip_yuv420(dawn_decoder* dec, int H, int W, int T, int h, int w, const float* img3, const void* skip_mem,
+                                       const float* latent, long latent_plane, int chunk, unsigned char* frames_yuv420,
+                                       const double* mean3, void* workspace, size_t workspace_bytes, void* stream) {
+    return decode_clip(dec, "dawn_decode_clip_yuv420", H, W, T, h, w, img3, skip_mem, latent, latent_plane, nullptr,
+                       latent ? latent + 2 * latent_plane : nullptr, chunk, nullptr, nullptr, 0, nullptr, mean3, 0, workspace,
+                       workspace_bytes, stream, frames_yuv420, true);
+}
+
+extern "C" int dawn_decode_clip_conf_yuv420(dawn_decoder* dec, int H, int W, int T, int h, int w, const float* img3,
+                                            const void* skip_mem, const float* grid, long grid_plane, const float* conf, int chunk,
+                                            unsigned char* frames_yuv420, const double* mean3, void* workspace, size_t workspace_bytes,
+                                            void* stream) {
+    if (!conf) return dawn_set_error_msg(-238, "dawn_decode_clip_conf_yuv420: NULL conf");
+    return decode_clip(dec, "dawn_decode_clip_conf_yuv420", H, W, T, h, w, img3, skip_mem, grid, grid_plane, conf, nullptr, chunk, nullptr,
+                       nullptr, 0, nullptr, mean3, 0, workspace, workspace_bytes, stream, frames_yuv420, true);
 }

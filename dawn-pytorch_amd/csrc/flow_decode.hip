@@ -175,6 +175,38 @@ __device__ __forceinline__ unsigned u8_of(float x, double m) {
     return (unsigned)(v * 255.0f);
 }
 
+// ---- yuv420p egress: BT.601 limited range in 8-bit fixed point, on the RGB bytes u8_of defines (>> = arithmetic shift):
+//   Y = ((66 R + 129 G + 25 B + 128) >> 8) + 16 per pixel;  R', G', B' = (sum of the 2x2 block + 2) >> 2 (centre-sited box);
+//   U = ((-38 R' - 74 G' + 112 B' + 128) >> 8) + 128;  V = ((112 R' - 94 G' - 18 B' + 128) >> 8) + 128.
+// Y stays in [16,235], U and V in [16,240] for every input: no clamp.  I420: per frame Y (H*W), U (H/2 * W/2), V (the same).
+__device__ __forceinline__ unsigned yuv_y(unsigned R, unsigned G, unsigned B) { return ((66u * R + 129u * G + 25u * B + 128u) >> 8) + 16u; }
+__device__ __forceinline__ unsigned yuv_u(int R, int G, int B) { return (unsigned)(((-38 * R - 74 * G + 112 * B + 128) >> 8) + 128); }
+__device__ __forceinline__ unsigned yuv_v(int R, int G, int B) { return (unsigned)(((112 * R - 94 * G - 18 * B + 128) >> 8) + 128); }
+
+// four RGB pixels packed as 12 bytes in three words -> byte k
+__device__ __forceinline__ unsigned rgb12_byte(const unsigned (&q)[3], int k) { return (q[k >> 2] >> (8 * (k & 3))) & 255u; }
+// the four Y bytes of such a group as one word
+__device__ __forceinline__ unsigned yuv_y4(const unsigned (&q)[3]) {
+    unsigned y = 0;
+#pragma unroll
+    for (int p = 0; p < 4; ++p) y |= yuv_y(rgb12_byte(q, 3 * p), rgb12_byte(q, 3 * p + 1), rgb12_byte(q, 3 * p + 2)) << (8 * p);
+    return y;
+}
+// two rows of such groups = two 2x2 blocks: their U bytes (low half) and V bytes (high half)
+__device__ __forceinline__ unsigned yuv_uv2(const unsigned (&a)[3], const unsigned (&b)[3]) {
+    unsigned uv = 0;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        int c[3];
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch)
+            c[ch] = (int)(rgb12_byte(a, 6 * j + ch) + rgb12_byte(a, 6 * j + 3 + ch) + rgb12_byte(b, 6 * j + ch) +
+                          rgb12_byte(b, 6 * j + 3 + ch) + 2u) >> 2;
+        uv |= (yuv_u(c[0], c[1], c[2]) << (8 * j)) | (yuv_v(c[0], c[1], c[2]) << (16 + 8 * j));
+    }
+    return uv;
+}
+
 // ---- final 7x7 conv C->3 + bias, sigmoid, and the last apply_optical against the source image (GEN:163-167), plus the
 // `deformed` output (GEN:152).  Tile = 32 x 16 output pixels of one frame, 256 threads, 2 pixels per thread (rows y and
 // y+8).  The input streams through LDS 8 channels at a time as a zero-padded (16+6) x (32+6) patch laid out
@@ -187,6 +219,11 @@ __device__ __forceinline__ unsigned u8_of(float x, double m) {
 //             bytes (dawn_final_conv_blend_u8): no fp32 frame goes to memory.  A 32 x 16 tile is 16 rows of 96 contiguous
 //             bytes: they are staged in the patch region of LDS (free once the last channel chunk is consumed) and leave as
 //             24 4-byte stores per row; tiles cut by the image edge store their bytes one by one.
+//   FcOutYuv420  the same RGB bytes (RGB order) converted to I420 (dawn_final_conv_blend_yuv420; definition at yuv_y above): every
+//             tile, edge-cut ones too, stages its bytes in that tile, and its valid part is converted from LDS.  Even H and W % 4 == 0
+//             with a tile origin at multiples of (16,32) make the valid part whole groups of 4 pixels x 2 rows: no chroma block
+//             straddles a tile or the image edge, Y leaves as 4-byte words (8 per tile row) and U, V as 2-byte pairs (the chroma
+//             planes and their rows are 2-byte aligned, no more, when W % 8 != 0).
 constexpr int FC_TW = 32, FC_TH = 16, FC_PW = FC_TW + 6, FC_PH = FC_TH + 6, FC_PP = FC_PW * FC_PH;
 
 // The last blend as the fp32 kernel has always evaluated it: two rounded products and a rounded sum.  Spelled out because the
@@ -199,6 +236,7 @@ __device__ __forceinline__ float fc_blend(float wv, float oc, float s) {
 
 struct FcOutF32 { float* out_vid; float* warped_vid; long out_plane; };
 struct FcOutU8 { unsigned char* frames; double m0, m1, m2; int bgr; };
+struct FcOutYuv420 { unsigned char* frames; double m0, m1, m2; };
 
 template <class Out>
 __global__ __launch_bounds__(256) void final_conv_blend_kernel(const float* __restrict__ x, int T, int H, int W, int C,
@@ -206,7 +244,7 @@ __global__ __launch_bounds__(256) void final_conv_blend_kernel(const float* __re
                                                                const float* __restrict__ src, const float* __restrict__ grid,
                                                                long grid_plane, const float* __restrict__ conf, int h, int w,
                                                                const Out dst) {
-    constexpr bool U8 = __is_same(Out, FcOutU8);
+    constexpr bool U8 = __is_same(Out, FcOutU8), YUV = __is_same(Out, FcOutYuv420), F32 = __is_same(Out, FcOutF32);
     extern __shared__ __attribute__((aligned(16))) float sm[];
     float* Ws_ = sm;                                   // [49][C/4][3][4]
     float* Ps = sm + 49 * C * 3;                       // [2][FC_PP][4]
@@ -259,9 +297,9 @@ __global__ __launch_bounds__(256) void final_conv_blend_kernel(const float* __re
     const float* gxp = grid + (long)t * h * w;
     const float* gyp = gxp + grid_plane;
     const float* cfp = conf + (long)t * h * w;
-    unsigned char* tile = reinterpret_cast<unsigned char*>(Ps);      // U8: [FC_TH][FC_TW * 3] bytes
+    unsigned char* tile = reinterpret_cast<unsigned char*>(Ps);      // U8, YUV: [FC_TH][FC_TW * 3] bytes
     const bool full = X0 + FC_TW <= W && Y0 + FC_TH <= H;
-    if constexpr (U8) __syncthreads();                 // last chunk consumed: the patch region becomes the byte tile
+    if constexpr (U8 || YUV) __syncthreads();          // last chunk consumed: the patch region becomes the byte tile
 #pragma unroll
     for (int pI = 0; pI < 2; ++pI) {
         const int Y = Y0 + ly + 8 * pI, X = X0 + lx;
@@ -278,9 +316,12 @@ __global__ __launch_bounds__(256) void final_conv_blend_kernel(const float* __re
                 if (cr.i[k] >= 0) wv += src[(long)ch * H * W + cr.i[k]] * cr.w[k];
             const float s = 1.0f / (1.0f + expf(-(acc[pI][ch] + bias3[ch])));
             const float v = fc_blend(wv, oc, s);
-            if constexpr (!U8) {
+            if constexpr (F32) {
                 dst.warped_vid[ch * dst.out_plane + o] = wv;
                 dst.out_vid[ch * dst.out_plane + o] = v;
+            } else if constexpr (YUV) {
+                tile[(ly + 8 * pI) * (FC_TW * 3) + lx * 3 + ch] =
+                    (unsigned char)u8_of(v, ch == 0 ? dst.m0 : (ch == 1 ? dst.m1 : dst.m2));
             } else {
                 const unsigned char u = (unsigned char)u8_of(v, ch == 0 ? dst.m0 : (ch == 1 ? dst.m1 : dst.m2));
                 const int k = dst.bgr ? 2 - ch : ch;
@@ -297,6 +338,32 @@ __global__ __launch_bounds__(256) void final_conv_blend_kernel(const float* __re
             for (int i = tid; i < FC_TH * RW; i += 256) {
                 const int r = i / RW, c = i - r * RW;
                 reinterpret_cast<unsigned*>(dst.frames + (((long)t * H + Y0 + r) * W + X0) * 3)[c] = tw[i];
+            }
+        }
+    }
+    if constexpr (YUV) {
+        __syncthreads();
+        const unsigned* tw = reinterpret_cast<const unsigned*>(tile);
+        constexpr int RW = FC_TW * 3 / 4, GW = FC_TW / 4;           // 24 words, 8 groups of 4 pixels per tile row
+        const int vg = ((W - X0 < FC_TW ? W - X0 : FC_TW)) >> 2;    // valid groups per row, valid rows
+        const int vr = H - Y0 < FC_TH ? H - Y0 : FC_TH;
+        unsigned char* fr = dst.frames + (long)t * ((long)H * W / 2 * 3);
+        if (tid < FC_TH * GW) {                                     // waves 0-1: Y, one word per thread
+            const int r = tid / GW, c = tid - r * GW;
+            if (r < vr && c < vg) {
+                const unsigned q[3] = {tw[r * RW + 3 * c], tw[r * RW + 3 * c + 1], tw[r * RW + 3 * c + 2]};
+                reinterpret_cast<unsigned*>(fr + (long)(Y0 + r) * W + X0)[c] = yuv_y4(q);
+            }
+        } else if (tid < FC_TH * GW + FC_TH / 2 * GW) {             // wave 2: chroma, two 2x2 blocks per thread
+            const int j = tid - FC_TH * GW, r = j / GW, c = j - r * GW;
+            if (2 * r < vr && c < vg) {
+                const unsigned* p = tw + 2 * r * RW + 3 * c;
+                const unsigned a[3] = {p[0], p[1], p[2]}, b[3] = {p[RW], p[RW + 1], p[RW + 2]};
+                const unsigned uv = yuv_uv2(a, b);
+                const long HW = (long)H * W;
+                const long co = (long)((Y0 >> 1) + r) * (W >> 1) + (X0 >> 1) + 2 * c;
+                *reinterpret_cast<unsigned short*>(fr + HW + co) = (unsigned short)(uv & 0xffffu);
+                *reinterpret_cast<unsigned short*>(fr + HW + (HW >> 2) + co) = (unsigned short)(uv >> 16);
             }
         }
     }
@@ -325,9 +392,52 @@ __global__ __launch_bounds__(256) void frames_to_u8_kernel(const float* __restri
     }
 }
 
+// ---- the same egress to I420 (definition at yuv_y above) for a clip that exists as fp32 planes: (3,T,H,W) -> (T, 3HW/2) bytes.
+// A thread owns two rows x four columns: six 16-byte loads, two 4-byte Y stores, one 2-byte U and one 2-byte V store.
+__global__ __launch_bounds__(256) void frames_to_yuv420_kernel(const float* __restrict__ vid, long plane, int T, int H, int W,
+                                                               double m0, double m1, double m2, unsigned char* __restrict__ out) {
+    const int gw = W >> 2, hh = H >> 1;
+    const long total = (long)T * hh * gw, HW = (long)H * W;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+        const int c = (int)(i % gw);
+        const long r2 = i / gw;
+        const int by = (int)(r2 % hh);
+        const long t = r2 / hh;
+        const float* v0 = vid + (t * H + 2 * by) * W + 4 * c;
+        unsigned q[2][3];
+#pragma unroll
+        for (int dy = 0; dy < 2; ++dy) {
+            const f32x4 r = *reinterpret_cast<const f32x4*>(v0 + dy * W);
+            const f32x4 g = *reinterpret_cast<const f32x4*>(v0 + dy * W + plane);
+            const f32x4 b = *reinterpret_cast<const f32x4*>(v0 + dy * W + 2 * plane);
+            unsigned k[12];
+#pragma unroll
+            for (int p = 0; p < 4; ++p) { k[3 * p] = u8_of(r[p], m0); k[3 * p + 1] = u8_of(g[p], m1); k[3 * p + 2] = u8_of(b[p], m2); }
+#pragma unroll
+            for (int w = 0; w < 3; ++w) q[dy][w] = k[4 * w] | (k[4 * w + 1] << 8) | (k[4 * w + 2] << 16) | (k[4 * w + 3] << 24);
+        }
+        unsigned char* fr = out + t * (HW / 2 * 3);
+        reinterpret_cast<unsigned*>(fr + (long)(2 * by) * W)[c] = yuv_y4(q[0]);
+        reinterpret_cast<unsigned*>(fr + (long)(2 * by + 1) * W)[c] = yuv_y4(q[1]);
+        const unsigned uv = yuv_uv2(q[0], q[1]);
+        const long co = (long)by * (W >> 1) + 2 * c;
+        *reinterpret_cast<unsigned short*>(fr + HW + co) = (unsigned short)(uv & 0xffffu);
+        *reinterpret_cast<unsigned short*>(fr + HW + (HW >> 2) + co) = (unsigned short)(uv >> 16);
+    }
+}
+
 int grid_for(long total) {
     long g = (total + 255) / 256;
     return (int)(g > 65536 ? 65536 : (g < 1 ? 1 : g));
+}
+
+// the I420 outputs' argument rule: even H, W % 4 == 0 (every frame and Y row 4-byte aligned, chroma rows of even length) and a
+// 4-byte aligned buffer
+int bad_yuv420(const char* who, int H, int W, const void* out) {
+    if (H > 0 && W > 0 && H % 2 == 0 && W % 4 == 0 && out && ((uintptr_t)out & 3) == 0) return 0;
+    char msg[200];
+    snprintf(msg, sizeof msg, "%s: yuv420p needs an even H, W %% 4 == 0 and a non-NULL 4-byte aligned output (H = %d, W = %d)", who, H, W);
+    return dawn_set_error_msg(-84, msg);
 }
 
 }  // namespace
@@ -408,6 +518,26 @@ extern "C" int dawn_final_conv_blend_u8(const float* x, int T, int H, int W, int
         return dawn_set_error_msg(-78, "dawn_final_conv_blend_u8: W must be a multiple of 4 and frames 4-byte aligned");
     return launch_final_conv("dawn_final_conv_blend_u8", x, T, H, W, C, w7, bias3, src, grid, grid_plane, conf, h, w,
                              FcOutU8{frames, mean0, mean1, mean2, bgr}, stream);
+}
+
+extern "C" int dawn_final_conv_blend_yuv420(const float* x, int T, int H, int W, int C, const float* w7, const float* bias3,
+                                            const float* src, const float* grid, long grid_plane, const float* conf, int h, int w,
+                                            double mean0, double mean1, double mean2, unsigned char* frames, void* stream) {
+    if (const int rc = bad_yuv420("dawn_final_conv_blend_yuv420", H, W, frames)) return rc;
+    return launch_final_conv("dawn_final_conv_blend_yuv420", x, T, H, W, C, w7, bias3, src, grid, grid_plane, conf, h, w,
+                             FcOutYuv420{frames, mean0, mean1, mean2}, stream);
+}
+
+extern "C" int dawn_frames_to_yuv420(const float* vid, long plane, int T, int H, int W, double mean0, double mean1, double mean2,
+                                     unsigned char* out, void* stream) {
+    if (const int rc = bad_yuv420("dawn_frames_to_yuv420", H, W, out)) return rc;
+    if (!vid || plane % 4 != 0 || ((uintptr_t)vid & 15) != 0)
+        return dawn_set_error_msg(-85, "dawn_frames_to_yuv420: vid must be non-NULL and 16-byte aligned, the plane stride a multiple of 4");
+    if (T <= 0) return 0;
+    hipLaunchKernelGGL(frames_to_yuv420_kernel, dim3(grid_for((long)T * (H / 2) * (W / 4))), dim3(256), 0, (hipStream_t)stream, vid,
+                       plane, T, H, W, mean0, mean1, mean2, out);
+    DAWN_LAUNCH_CHECK();
+    return 0;
 }
 
 extern "C" int dawn_frames_to_u8(const float* vid, long plane, long npix, double mean0, double mean1, double mean2, int bgr,

@@ -554,10 +554,11 @@ class DecoderEvaluator:
     def decode(self, img: Tensor, skip_mem: Tensor, *, T: int, h: int, w: int, chunk: int, latent: Optional[Tensor] = None,
                grid: Optional[Tensor] = None, conf: Optional[Tensor] = None, out_vid: Optional[Tensor] = None,
                warped_vid: Optional[Tensor] = None, frames: Optional[Tensor] = None, mean=(0.0, 0.0, 0.0), bgr: bool = False,
-               workspace: Optional[Tensor] = None) -> None:
+               workspace: Optional[Tensor] = None, yuv: Optional[Tensor] = None) -> None:
         """One clip: `latent` (3,T,h,w) as the sampler returns it, or `grid` (2,T,h,w) + `conf` (T,h,w).  Planes may be strided (a
         frame range of a longer clip); rows and frames must be dense.  out_vid / warped_vid: (3,T,H,W) views with dense frames;
-        frames: (T,H,W,3) uint8 contiguous."""
+        frames: (T,H,W,3) uint8 contiguous.  yuv: (T, 3HW/2) uint8 contiguous, the I420 frames of dawn_decode_clip_yuv420 -- the only
+        output of its call (no fp32 clip, no RGB bytes, no bgr)."""
         _, H, W = img.shape
         g = latent if latent is not None else grid
         if not (g is not None and g.is_cuda and g.dtype == torch.float32 and tuple(g.shape[1:]) == (T, h, w)
@@ -581,6 +582,19 @@ class DecoderEvaluator:
         ws = workspace if workspace is not None else self.workspace(H, W, max(1, min(chunk, T)))
         m = (C.c_double * 3)(*[float(v) / 255.0 for v in mean])
         p = lambda t: None if t is None else t.data_ptr()      # noqa: E731
+        if yuv is not None:
+            if out_vid is not None or warped_vid is not None or frames is not None or bgr:
+                raise _lib.DawnHipError("DecoderEvaluator.decode: yuv is the only output of its call (no out_vid / warped_vid / frames / bgr)")
+            if not (yuv.is_cuda and yuv.dtype == torch.uint8 and yuv.is_contiguous() and tuple(yuv.shape) == (T, H * W * 3 // 2)):
+                raise _lib.DawnHipError("DecoderEvaluator.decode: yuv must be a contiguous uint8 GPU tensor (T, 3*H*W/2)")
+            tail = (chunk, yuv.data_ptr(), m, ws.data_ptr(), ws.numel(), self._stream())
+            if latent is not None:
+                check(self.L.dawn_decode_clip_yuv420(self.h, H, W, T, h, w, img.data_ptr(), skip_mem.data_ptr(), latent.data_ptr(),
+                                                     latent.stride(0), *tail), "dawn_decode_clip_yuv420")
+            else:
+                check(self.L.dawn_decode_clip_conf_yuv420(self.h, H, W, T, h, w, img.data_ptr(), skip_mem.data_ptr(), grid.data_ptr(),
+                                                          grid.stride(0), conf.data_ptr(), *tail), "dawn_decode_clip_conf_yuv420")
+            return
         tail = (chunk, p(out_vid), p(warped_vid), plane, p(frames), m, 1 if bgr else 0, ws.data_ptr(), ws.numel(), self._stream())
         if latent is not None:
             check(self.L.dawn_decode_clip(self.h, H, W, T, h, w, img.data_ptr(), skip_mem.data_ptr(), latent.data_ptr(),

@@ -13,7 +13,8 @@ What changes relative to the reference's execution (results are the same within 
     flow / occlusion resize (GEN:65-68, 81-82) and the next block's nearest x2 upsampling (UTIL:106);
   * every 3x3 convolution runs through `dawn_conv_gemm` (split-operand bf16 MFMA kernel, fp32-accurate);
   * the final 7x7 conv, sigmoid, last blend and the `deformed` output are one kernel writing (3,T,H,W) directly -- or, for the
-    byte outputs (`decode_clip_u8`, `stream_frames_u8`), the same kernel writing (T,H,W,3) uint8 frames with no fp32 clip at all.
+    byte outputs (`decode_clip_u8`, `stream_frames_u8`), the same kernel writing (T,H,W,3) uint8 frames with no fp32 clip at all --
+    or (`decode_clip_yuv420`, `stream_frames_yuv420`) writing what an encoder reads, (T, 3HW/2) planar YUV 4:2:0 (egress.py).
 
 `use_ctx = True` hands the same launch sequence to the C-side decoder (include/dawn_hip.h: dawn_decoder_*, dawn_decode_clip).
 """
@@ -24,6 +25,7 @@ from typing import Dict, List, Optional
 
 import torch
 
+from .egress import yuv420_frame_bytes, yuv420_from_rgb_u8
 from .pack import pack_bf3, pack_kn
 
 Tensor = torch.Tensor
@@ -154,10 +156,12 @@ class FlowDecoder:
     # ------------------------------------------------------------------ decoder
     def _decode_frames(self, skips: List[Tensor], src: Tensor, H: int, W: int, g: Tensor, cf: Tensor, out_vid: Optional[Tensor],
                        warped_vid: Optional[Tensor], frames: Optional[Tensor] = None, mean=(0.0, 0.0, 0.0),
-                       bgr: bool = False) -> None:
+                       bgr: bool = False, yuv: Optional[Tensor] = None) -> None:
         """g (2,n,h,w) view, cf (n,h,w); writes out_vid / warped_vid (3,n,H,W) views and / or frames (n,H,W,3) uint8.  GEN:152-167.
         With `frames` alone the last launch is the fused final_conv_blend_u8 where the op set has it (no fp32 frame is written);
-        otherwise final_conv_blend followed by frames_to_u8 on the chunk -- which is also the definition of the fused op's result."""
+        otherwise final_conv_blend followed by frames_to_u8 on the chunk -- which is also the definition of the fused op's result.
+        `yuv` (n, 3HW/2) uint8, alone: the fused final_conv_blend_yuv420 where the op set has it; otherwise final_conv_blend ->
+        frames_to_u8 (RGB) -> egress.yuv420_from_rgb_u8, the definition of that op's result."""
         ops = self.ops
         n = g.shape[1]
         k = 1 << len(self.downs)
@@ -175,7 +179,10 @@ class FlowDecoder:
             prev = self._conv3(u, up, n, Hc, Wc)                                    # UTIL:107; its BN+ReLU ride on the consumer
             prev_ab = (up.a, up.b)
         xf = ops.warp_blend(skips[0], H, W, g, cf, prev=prev, prev_ab=prev_ab)      # GEN:161-162
-        if frames is not None and out_vid is None and hasattr(ops, "final_conv_blend_u8"):
+        if yuv is not None and hasattr(ops, "final_conv_blend_yuv420"):
+            ops.final_conv_blend_yuv420(xf, H, W, self.final_w7, self.final_bias, src, g, cf, yuv, mean=mean)
+            return
+        if yuv is None and frames is not None and out_vid is None and hasattr(ops, "final_conv_blend_u8"):
             ops.final_conv_blend_u8(xf, H, W, self.final_w7, self.final_bias, src, g, cf, frames, mean=mean, bgr=bgr)
             return
         if out_vid is None:
@@ -184,6 +191,8 @@ class FlowDecoder:
         ops.final_conv_blend(xf, H, W, self.final_w7, self.final_bias, src, g, cf, out_vid, warped_vid)   # GEN:163-167, 152
         if frames is not None:
             frames.copy_(ops.frames_to_u8(out_vid, mean=mean, bgr=bgr))
+        if yuv is not None:
+            yuv.copy_(yuv420_from_rgb_u8(ops.frames_to_u8(out_vid, mean=mean, bgr=False)))
 
     # ---- the two hosts of the launch sequence: this file's orchestration, or the C-side decoder (use_ctx; ctx.DecoderEvaluator)
     use_ctx = False      # True: GPU clips go through dawn_decoder_encode / dawn_decode_clip (bit-identical to the orchestration here)
@@ -205,13 +214,13 @@ class FlowDecoder:
 
     def _chunk(self, state, src: Tensor, H: int, W: int, g: Tensor, cf: Tensor, out_vid: Optional[Tensor],
                warped_vid: Optional[Tensor], frames: Optional[Tensor] = None, mean=(0.0, 0.0, 0.0), bgr: bool = False,
-               chunk: Optional[int] = None) -> None:
+               chunk: Optional[int] = None, yuv: Optional[Tensor] = None) -> None:
         """Frames of g / cf (any number: the C side splits them into chunks itself) into the given outputs."""
         if isinstance(state, list):
-            return self._decode_frames(state, src, H, W, g, cf, out_vid, warped_vid, frames, mean, bgr)
+            return self._decode_frames(state, src, H, W, g, cf, out_vid, warped_vid, frames, mean, bgr, yuv)
         _, n, h, w = g.shape
         self._evaluator().decode(src, state, T=n, h=h, w=w, chunk=chunk or n, grid=g, conf=cf, out_vid=out_vid,
-                                 warped_vid=warped_vid, frames=frames, mean=mean, bgr=bgr)
+                                 warped_vid=warped_vid, frames=frames, mean=mean, bgr=bgr, yuv=yuv)
 
     @torch.no_grad()
     def decode_clip(self, sample_img: Tensor, grid: Tensor, conf: Tensor, chunk: Optional[int] = None) -> Dict[str, Tensor]:
@@ -259,14 +268,34 @@ class FlowDecoder:
         return out
 
     @torch.no_grad()
-    def stream_frames_u8(self, sample_img: Tensor, grid: Tensor, conf: Tensor, *, mean=(0.0, 0.0, 0.0), bgr: bool = False,
-                         chunk: Optional[int] = None, item: int = 0):
-        """Generator over the chunks of batch item `item`: yields (t0, frames) with frames a host ndarray (n,H,W,3) uint8, the bytes
-        of decode_clip_u8 for the frames [t0, t0 + n), in order.  On the GPU the device->host copy of a chunk runs on a side stream
-        into pinned memory while the next chunk decodes; the consumer waits for that chunk's copy event only (no device-wide
-        synchronise), and no clip-sized tensor exists on the device: two chunk-sized byte buffers plus the chunk's activations.
-        A YIELDED ARRAY IS VALID UNTIL THE NEXT `next()` ONLY: it aliases one of two pinned staging buffers, which the chunk after
-        the next one overwrites -- copy it if it has to live longer.  CPU tensors: the plain loop, every chunk its own array."""
+    def decode_clip_yuv420(self, sample_img: Tensor, grid: Tensor, conf: Tensor, *, mean=(0.0, 0.0, 0.0),
+                           chunk: Optional[int] = None) -> Tensor:
+        """decode_clip_u8 for an encoder: -> (B,T,3HW/2) uint8 on the inputs' device, every frame planar YUV 4:2:0 (I420: Y, then U, then
+        V; BT.601 limited range, 2x2 box chroma -- the definition in egress.py), byte for byte
+        `egress.yuv420_from_rgb_u8(decode_clip_u8(..., mean=mean, bgr=False)[b])`.  Neither fp32 clips nor RGB bytes are written where
+        the op set has the fused kernel.  Even H, W % 4 == 0."""
+        B, _, T, h, w = grid.shape
+        _, _, H, W = sample_img.shape
+        chunk = chunk or self.chunk
+        grid = grid.float().contiguous()
+        conf = conf.float().contiguous()
+        out = torch.empty(B, T, yuv420_frame_bytes(H, W), device=grid.device, dtype=torch.uint8)
+        for b in range(B):
+            src = sample_img[b].float().contiguous()
+            state = self._begin_clip(src)
+            if not isinstance(state, list):
+                self._chunk(state, src, H, W, grid[b], conf[b, 0], None, None, None, mean, chunk=chunk, yuv=out[b])
+                continue
+            for t0 in range(0, T, chunk):
+                t1 = min(T, t0 + chunk)
+                self._decode_frames(state, src, H, W, grid[b, :, t0:t1], conf[b, 0, t0:t1], None, None, None, mean, yuv=out[b, t0:t1])
+        return out
+
+    def _stream_chunks(self, sample_img: Tensor, grid: Tensor, conf: Tensor, chunk: Optional[int], item: int, frame_shape, decode):
+        """The chunk loop both byte streams share: yields (t0, host ndarray (n, *frame_shape) uint8).  decode(state, src, H, W, g, cf,
+        buf) writes the frames of one chunk into buf (n, *frame_shape).  On the GPU the device->host copy of a chunk runs on a side
+        stream into pinned memory while the next chunk decodes; the consumer waits for that chunk's copy event only (no device-wide
+        synchronise), and no clip-sized tensor exists on the device: two chunk-sized byte buffers plus the chunk's activations."""
         _, _, T, h, w = grid.shape
         _, _, H, W = sample_img.shape
         chunk = max(1, min(chunk or self.chunk, T))
@@ -277,14 +306,14 @@ class FlowDecoder:
         spans = [(t0, min(T, t0 + chunk)) for t0 in range(0, T, chunk)]
         if not g.is_cuda:
             for t0, t1 in spans:
-                fr = torch.empty(t1 - t0, H, W, 3, dtype=torch.uint8)
-                self._chunk(state, src, H, W, g[:, t0:t1], cf[t0:t1], None, None, fr, mean, bgr)
+                fr = torch.empty(t1 - t0, *frame_shape, dtype=torch.uint8)
+                decode(state, src, H, W, g[:, t0:t1], cf[t0:t1], fr)
                 yield t0, fr.numpy()
             return
         main = torch.cuda.current_stream(g.device)
         side = torch.cuda.Stream(device=g.device)
-        dev = [torch.empty(chunk, H, W, 3, device=g.device, dtype=torch.uint8) for _ in range(2)]
-        host = [torch.empty(chunk, H, W, 3, dtype=torch.uint8, pin_memory=True) for _ in range(2)]
+        dev = [torch.empty(chunk, *frame_shape, device=g.device, dtype=torch.uint8) for _ in range(2)]
+        host = [torch.empty(chunk, *frame_shape, dtype=torch.uint8, pin_memory=True) for _ in range(2)]
         copied = [None, None]                          # event of the last copy out of dev[k] / into host[k]
         pending = None
         try:
@@ -292,7 +321,7 @@ class FlowDecoder:
                 k, n = i & 1, t1 - t0
                 if copied[k] is not None:
                     main.wait_event(copied[k])         # dev[k] is free once chunk i - 2 has left it
-                self._chunk(state, src, H, W, g[:, t0:t1], cf[t0:t1], None, None, dev[k][:n], mean, bgr)
+                decode(state, src, H, W, g[:, t0:t1], cf[t0:t1], dev[k][:n])
                 decoded = torch.cuda.Event()
                 decoded.record(main)
                 with torch.cuda.stream(side):
@@ -311,6 +340,34 @@ class FlowDecoder:
                 yield pt0, host[pk][:pn].numpy()
         finally:
             side.synchronize()                         # an abandoned generator must not free buffers under a copy in flight
+
+    @torch.no_grad()
+    def stream_frames_u8(self, sample_img: Tensor, grid: Tensor, conf: Tensor, *, mean=(0.0, 0.0, 0.0), bgr: bool = False,
+                         chunk: Optional[int] = None, item: int = 0):
+        """Generator over the chunks of batch item `item`: yields (t0, frames) with frames a host ndarray (n,H,W,3) uint8, the bytes
+        of decode_clip_u8 for the frames [t0, t0 + n), in order.  On the GPU the device->host copy of a chunk runs on a side stream
+        into pinned memory while the next chunk decodes; the consumer waits for that chunk's copy event only (no device-wide
+        synchronise), and no clip-sized tensor exists on the device: two chunk-sized byte buffers plus the chunk's activations.
+        A YIELDED ARRAY IS VALID UNTIL THE NEXT `next()` ONLY: it aliases one of two pinned staging buffers, which the chunk after
+        the next one overwrites -- copy it if it has to live longer.  CPU tensors: the plain loop, every chunk its own array."""
+        _, _, H, W = sample_img.shape
+
+        def decode(state, src, H, W, g, cf, buf):
+            self._chunk(state, src, H, W, g, cf, None, None, buf, mean, bgr)
+        yield from self._stream_chunks(sample_img, grid, conf, chunk, item, (H, W, 3), decode)
+
+    @torch.no_grad()
+    def stream_frames_yuv420(self, sample_img: Tensor, grid: Tensor, conf: Tensor, *, mean=(0.0, 0.0, 0.0),
+                             chunk: Optional[int] = None, item: int = 0):
+        """stream_frames_u8 for an encoder: yields (t0, frames) with frames a host ndarray (n, 3HW/2) uint8, the bytes of
+        decode_clip_yuv420 for the frames [t0, t0 + n), in order -- `frames.tobytes()` is what `-f rawvideo -pix_fmt yuv420p` reads.
+        Half the device->host bytes of the RGB stream; the same staging, and the same rule: A YIELDED ARRAY IS VALID UNTIL THE NEXT
+        `next()` ONLY."""
+        _, _, H, W = sample_img.shape
+
+        def decode(state, src, H, W, g, cf, buf):
+            self._chunk(state, src, H, W, g, cf, None, None, None, mean, yuv=buf)
+        yield from self._stream_chunks(sample_img, grid, conf, chunk, item, (yuv420_frame_bytes(H, W),), decode)
 
     @torch.no_grad()
     def forward_with_flow(self, source_image: Tensor, optical_flow: Tensor, occlusion_map: Tensor) -> Dict[str, Tensor]:

@@ -141,7 +141,9 @@ class FlowDiffusion(nn.Module):
         """FD:325-406.  `frames_u8` (not in the reference): None = the fp32 clips as always; dict(mean=(0,0,0), bgr=False, chunk=None,
         stream=False) = decode straight to bytes instead (native decode only): out["sample_frames_u8"] is the (B,T,H,W,3) uint8
         device tensor of FlowDecoder.decode_clip_u8 -- or, with stream=True (B == 1), the chunk generator of
-        FlowDecoder.stream_frames_u8 -- and "sample_out_vid" / "sample_warped_vid" are never materialised."""
+        FlowDecoder.stream_frames_u8 -- and "sample_out_vid" / "sample_warped_vid" are never materialised.  dict(format="yuv420p",
+        mean=, chunk=, stream=) decodes to planar YUV 4:2:0 instead (format defaults to "rgb"): out["sample_frames_yuv420"] is the
+        (B,T,3HW/2) uint8 tensor of FlowDecoder.decode_clip_yuv420, or the generator of stream_frames_yuv420; it has no bgr."""
         out = {}
         fea = self.generator.compute_fea(sample_img)                                   # (B,256,h,w)  GEN:132-136
         bbox_mask = self.face_loc_emb(self.generate_bbox_mask(sample_bbox, size=sample_img.shape[-1]))
@@ -157,9 +159,18 @@ class FlowDiffusion(nn.Module):
                 raise ValueError("sample_one_video(frames_u8=...) needs the native flow decode (native_decode, or a clip on the GPU)")
             kw = dict(frames_u8)
             stream = kw.pop("stream", False)
+            fmt = kw.pop("format", "rgb")
+            if fmt not in ("rgb", "yuv420p"):
+                raise ValueError(f"frames_u8 format must be 'rgb' or 'yuv420p', not {fmt!r}")
+            if fmt == "yuv420p" and kw.pop("bgr", False):
+                raise ValueError("frames_u8 format='yuv420p' has no channel order: bgr=True is not allowed")
             dec = self.flow_decoder(sample_img.device)
             if stream and sample_img.shape[0] != 1:
                 raise ValueError("frames_u8 stream=True takes one clip (B == 1)")
+            if fmt == "yuv420p":
+                fn = dec.stream_frames_yuv420 if stream else dec.decode_clip_yuv420
+                out["sample_frames_yuv420"] = fn(sample_img, out["sample_vid_grid"], out["sample_vid_conf"], **kw)
+                return out
             fn = dec.stream_frames_u8 if stream else dec.decode_clip_u8
             out["sample_frames_u8"] = fn(sample_img, out["sample_vid_grid"], out["sample_vid_conf"], **kw)
             return out

@@ -775,6 +775,22 @@ class HipOps:
                                               h, w, m[0], m[1], m[2], 1 if bgr else 0, _p(frames), self._stream()),
               "dawn_final_conv_blend_u8")
 
+    def final_conv_blend_yuv420(self, x: Tensor, H: int, W: int, w7: Tensor, bias3: Tensor, src: Tensor, grid: Tensor,
+                                conf: Tensor, frames: Tensor, mean=(0.0, 0.0, 0.0)) -> None:
+        """final_conv_blend with the yuv420p egress as its store (definition: egress.py / dawn_frames_to_yuv420): frames (T, 3HW/2) uint8
+        (contiguous; a frame range of a longer clip is fine) receives the I420 bytes of final_conv_blend_u8's RGB frames; neither an fp32
+        frame nor an RGB byte is written."""
+        _, T, h, w = grid.shape
+        Cc = x.shape[1]
+        _need(x.is_contiguous() and x.shape[0] == T * H * W and src.is_contiguous() and src.shape == (3, H, W), "final_conv_blend_yuv420: x.is_contiguous() and x.shape[0] == T * H * W and src.is_contiguous() and src.shape == (3, H, W)")
+        _need(grid.stride(3) == 1 and grid.stride(2) == w and grid.stride(1) == h * w and conf.is_contiguous(), "final_conv_blend_yuv420: grid.stride(3) == 1 and grid.stride(2) == w and grid.stride(1) == h * w and conf.is_contiguous()")
+        _need(frames.dtype == torch.uint8 and frames.shape == (T, H * W * 3 // 2) and frames.is_contiguous(), "final_conv_blend_yuv420: frames.dtype == torch.uint8 and frames.shape == (T, H * W * 3 // 2) and frames.is_contiguous()")
+        self._require(x, w7, bias3, src, grid, conf, frames)
+        m = [float(v) / 255.0 for v in mean]
+        check(self.L.dawn_final_conv_blend_yuv420(_p(x), T, H, W, Cc, _p(w7), _p(bias3), _p(src), _p(grid), grid.stride(0), _p(conf),
+                                                  h, w, m[0], m[1], m[2], _p(frames), self._stream()),
+              "dawn_final_conv_blend_yuv420")
+
     # ------------------------------------------------------------------ frame egress (SURVEY 8f N2)
     def frames_to_u8(self, vid: Tensor, mean=(0.0, 0.0, 0.0), bgr: bool = False) -> Tensor:
         """(3,T,H,W) fp32 in [0,1] -> (T,H,W,3) uint8 with `_process_output_frame`'s arithmetic (UVG:533-548):
@@ -786,6 +802,20 @@ class HipOps:
         m = [float(x) / 255.0 for x in mean]
         check(self.L.dawn_frames_to_u8(_p(vid), vid.stride(0), T * H * W, m[0], m[1], m[2], 1 if bgr else 0, _p(out),
                                        self._stream()), "dawn_frames_to_u8")
+        return out
+
+    def frames_to_yuv420(self, vid: Tensor, mean=(0.0, 0.0, 0.0), out: Optional[Tensor] = None) -> Tensor:
+        """(3,T,H,W) fp32 in [0,1] -> (T, 3HW/2) uint8 I420 frames: the RGB bytes of frames_to_u8 (RGB order) through the yuv420p
+        definition of egress.py / dawn_frames_to_yuv420 (BT.601 limited range, 2x2 box chroma).  Even H, W % 4 == 0."""
+        _, T, H, W = vid.shape
+        _need(vid.shape[0] == 3 and vid.stride(3) == 1 and vid.stride(2) == W and vid.stride(1) == H * W, "frames_to_yuv420: vid.shape[0] == 3 and vid.stride(3) == 1 and vid.stride(2) == W and vid.stride(1) == H * W")
+        self._require(vid)
+        if out is None:
+            out = torch.empty(T, H * W * 3 // 2, device=vid.device, dtype=torch.uint8)
+        _need(out.dtype == torch.uint8 and out.shape == (T, H * W * 3 // 2) and out.is_contiguous(), "frames_to_yuv420: out.dtype == torch.uint8 and out.shape == (T, H * W * 3 // 2) and out.is_contiguous()")
+        m = [float(x) / 255.0 for x in mean]
+        check(self.L.dawn_frames_to_yuv420(_p(vid), vid.stride(0), T, H, W, m[0], m[1], m[2], _p(out), self._stream()),
+              "dawn_frames_to_yuv420")
         return out
 
     # ------------------------------------------------------------------ HuBERT audio features (SURVEY 8f N3)

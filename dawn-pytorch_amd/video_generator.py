@@ -12,6 +12,8 @@ from __future__ import annotations
 import argparse
 import os
 import os.path as osp
+import shlex
+import shutil
 import subprocess
 from typing import Optional
 
@@ -47,13 +49,23 @@ class _LastOutput(dict):
 
 class VideoGenerator:
     def __init__(self, args, *, generator=None, frontend=None, config: Optional[dict] = None, device=None,
-                 allow_random_weights: bool = False, deterministic: bool = True, hubert=None, pbnet=None):
+                 allow_random_weights: bool = False, deterministic: bool = True, hubert=None, pbnet=None,
+                 video_egress: str = "png", encoder_cmd=None):
         """`allow_random_weights`: explicit opt-in (benches, tests) to run with the deterministic random-init denoiser
         when the configured checkpoint is absent; without it a missing checkpoint raises, as the reference's
         `torch.load` does (UVG:527).  `deterministic`: seed the sampler's counter-based noise with the config's
         `random_seed` (the reference never seeds torch); False draws from torch's global generator.
         NOTE (reference quirk, kept): `FlowDiffusion.face_loc_emb` is never saved / loaded by the reference (it is a
-        sibling of `.diffusion`, FD:169), so it stays at its constructor initialisation here too."""
+        sibling of `.diffusion`, FD:169), so it stays at its constructor initialisation here too.
+        `video_egress`: "png" = the reference's path (PNG files, then ffmpeg reads them back); "yuv420p" (native decode only) = the
+        decoder writes planar YUV 4:2:0 frames, which stream into an encoder process's stdin chunk by chunk, and no PNG is written.
+        `encoder_cmd` (yuv420p only): the encoder's argv (list, or a string split like a shell would), to which the output path
+        `<output>/<name>/video/<name>.mp4` is appended; it reads raw I420 frames of the clip's size at 25 fps from stdin.  None: ffmpeg
+        when there is one on PATH, else the frames go to `<name>.y4m` in the same directory."""
+        if video_egress not in ("png", "yuv420p"):
+            raise ValueError(f"video_egress must be 'png' or 'yuv420p', not {video_egress!r}")
+        self.video_egress = video_egress
+        self.encoder_cmd = shlex.split(encoder_cmd) if isinstance(encoder_cmd, str) else (list(encoder_cmd) if encoder_cmd else None)
         self.hubert = hubert              # hubert.HubertFeatures: stage 2 (process_audio, UVG:202-250) on the GPU (SURVEY 8f N3)
         self.pbnet = pbnet                # (pose, blink) pbnet.PoseBlinkGenerator pair: stage 3 (generate_pose_blink, UVG:252-302; N4)
         self.allow_random_weights = bool(allow_random_weights) or bool(getattr(args, "allow_random_weights", False))
@@ -152,8 +164,10 @@ class VideoGenerator:
         name = os.path.splitext(os.path.basename(self.image_path))[0]
         video_dir = os.path.join(self.output_path, name, 'video')
         img_dir = os.path.join(self.output_path, name, 'img')
+        yuv = self.video_egress == "yuv420p"
         os.makedirs(video_dir, exist_ok=True)
-        os.makedirs(img_dir, exist_ok=True)
+        if not yuv:
+            os.makedirs(img_dir, exist_ok=True)
         size = cfg['input_size']
         image = Image.open(self.image_path).convert("RGB").resize((size, size), Image.BILINEAR)
         image_tensor = torch.from_numpy(np.array(image)).permute(2, 0, 1).float()        # 0..255, like ToTensor()*255
@@ -175,13 +189,22 @@ class VideoGenerator:
         mean = tuple(cfg.get('mean', (0, 0, 0)))
         sample_img = image_tensor.unsqueeze(0).to(dev) / 255.
         stream = self.video_model.decodes_natively(sample_img)
+        if yuv and not stream:
+            raise ValueError("video_egress='yuv420p' needs the native flow decode (native_decode, or a clip on the GPU)")
+        egress = dict(format="yuv420p", mean=mean, stream=True) if yuv else dict(mean=mean, bgr=False, stream=True)
         with torch.no_grad():
             self.video_model.update_num_frames(T)
             out = self.video_model.sample_one_video(
                 sample_img=sample_img, sample_audio_hubert=ref_hubert.unsqueeze(0).to(dev),
                 sample_pose=poses.unsqueeze(0).to(dev), sample_eye=blink[:2].unsqueeze(0).to(dev),
                 sample_bbox=real_bb[2:].unsqueeze(0).to(dev), init_pose=init_pose.to(dev), init_eye=init_blink.to(dev),
-                cond_scale=cfg['cond_scale'], frames_u8=dict(mean=mean, bgr=False, stream=True) if stream else None)
+                cond_scale=cfg['cond_scale'], frames_u8=egress if stream else None)
+        if yuv:
+            # the decoder's last kernel writes what the encoder reads; each chunk goes to the encoder while the next one decodes
+            frames = self._encode_yuv420(out.pop("sample_frames_yuv420"), T, size, size, video_dir, name)
+            self._last_clip = (sample_img, out["sample_vid_grid"], out["sample_vid_conf"])
+            self.last_output = _LastOutput(out, self.decode_last_clips)
+            return frames
         # frame egress (UVG:383-397 + `_process_output_frame` UVG:533-548), RGB order here (PIL); `bgr=True` gives cv2's order.
         if stream:
             # native decode: the decoder's last kernel writes the (T,H,W,3) bytes itself (numpy's exact arithmetic), chunk by chunk;
@@ -209,6 +232,56 @@ class VideoGenerator:
                            stderr=subprocess.DEVNULL)
         except FileNotFoundError:
             pass
+        return frames
+
+    def _yuv420_encoder(self, H: int, W: int, mp4: str):
+        """argv of the process that reads the raw I420 stream from stdin and writes `mp4`, or None: no encoder here."""
+        if self.encoder_cmd is not None:
+            return self.encoder_cmd + [mp4]
+        if shutil.which("ffmpeg") is None:
+            return None
+        cmd = ['ffmpeg', '-y', '-f', 'rawvideo', '-pix_fmt', 'yuv420p', '-s', f'{W}x{H}', '-framerate', '25',
+               '-color_range', 'tv', '-colorspace', 'smpte170m', '-i', '-']                # BT.601 limited range, as the frames are
+        if self.audio_path and osp.exists(self.audio_path):
+            cmd += ['-i', self.audio_path, '-shortest']
+        return cmd + ['-pix_fmt', 'yuv420p', mp4]
+
+    def _encode_yuv420(self, chunks, T: int, H: int, W: int, video_dir: str, name: str) -> np.ndarray:
+        """Feed the (t0, (n, 3HW/2) uint8) chunks of FlowDecoder.stream_frames_yuv420 to the encoder's stdin as they arrive -- or, with
+        no encoder, to `<name>.y4m` -- and return all of them as one (T, 3HW/2) array.  The encoder is a child process (Popen); its
+        stdin is closed and it is waited for; a non-zero exit or a broken pipe raises."""
+        frames = np.empty((T, H * W * 3 // 2), dtype=np.uint8)
+        cmd = self._yuv420_encoder(H, W, os.path.join(video_dir, f"{name}.mp4"))
+        if cmd is None:
+            with open(os.path.join(video_dir, f"{name}.y4m"), "wb") as f:
+                f.write(f"YUV4MPEG2 W{W} H{H} F25:1 Ip A1:1 C420jpeg\n".encode())
+                for t0, chunk in chunks:
+                    frames[t0:t0 + len(chunk)] = chunk
+                    for fr in chunk:
+                        f.write(b"FRAME\n")
+                        f.write(fr.tobytes())
+            return frames
+        proc = subprocess.Popen(cmd, stdin=subprocess.PIPE, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+        broken = None
+        try:
+            for t0, chunk in chunks:
+                frames[t0:t0 + len(chunk)] = chunk
+                proc.stdin.write(chunk.tobytes())
+            proc.stdin.close()
+        except BrokenPipeError as e:                                                        # the encoder went away mid-stream
+            broken = e
+        finally:
+            if hasattr(chunks, "close"):
+                chunks.close()
+            if broken is not None or not proc.stdin.closed:
+                try:
+                    proc.stdin.close()
+                except OSError:
+                    pass
+            rc = proc.wait()
+        if broken is not None or rc != 0:
+            raise RuntimeError(f"video encoder {cmd[0]!r} failed (exit status {rc}"
+                               f"{', broken pipe' if broken is not None else ''})") from broken
         return frames
 
     def decode_last_clips(self):
@@ -273,6 +346,9 @@ def parse_args(argv=None):
     p.add_argument('--max_n_frames', type=int, default=None, help='override the clip-length cap (YAML ships 200)')
     p.add_argument('--pbnet_pose_ckpt', type=str, default='./pretrain_models/pbnet_seperate/pose/checkpoint_40000.pth.tar')
     p.add_argument('--pbnet_blink_ckpt', type=str, default='./pretrain_models/pbnet_seperate/blink/checkpoint_95000.pth.tar')
+    p.add_argument('--video_egress', type=str, default='png', choices=('png', 'yuv420p'),
+                   help='png: PNG frames that ffmpeg reads back (the reference); yuv420p: the decoder writes planar YUV 4:2:0, piped '
+                        'into the encoder as it decodes (no PNG files)')
     p.add_argument('--allow_random_weights', action='store_true',
                    help='run with the deterministic random-init denoiser when the checkpoint is absent (plumbing only)')
     return p.parse_args(argv)
@@ -284,7 +360,7 @@ def main():
     if osp.exists(args.pbnet_pose_ckpt) and osp.exists(args.pbnet_blink_ckpt):     # stage 3 here, else via the cache files
         from .pbnet import load_pbnet
         pbnet = load_pbnet(args.pbnet_pose_ckpt, args.pbnet_blink_ckpt, device="cuda:0" if torch.cuda.is_available() else "cpu")
-    VideoGenerator(args, pbnet=pbnet).run()
+    VideoGenerator(args, pbnet=pbnet, video_egress=args.video_egress).run()
 
 
 if __name__ == "__main__":

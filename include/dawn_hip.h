@@ -395,6 +395,26 @@ int dawn_final_conv_blend_u8(const float* x, int T, int H, int W, int C, const f
                              const float* src, const float* grid, long grid_plane, const float* conf, int h, int w,
                              double mean0, double mean1, double mean2, int bgr, unsigned char* frames, void* stream);
 
+/* ---- yuv420p egress: the frames as planar YUV 4:2:0 (I420), what `-f rawvideo -pix_fmt yuv420p` and a Y4M FRAME read.
+ * Input: the RGB bytes R,G,B of the egress above (u8 with mean_c/255, RGB order, i.e. dawn_frames_to_u8(..., bgr = 0)).
+ * Output: BT.601 limited range in 8-bit fixed point, `>>` an arithmetic shift (floor):
+ *   Y  = (( 66*R + 129*G +  25*B + 128) >> 8) + 16                       per pixel
+ *   R' = (R00 + R01 + R10 + R11 + 2) >> 2   (same for G', B')            per 2x2 block, rows 2i,2i+1 x cols 2j,2j+1 (centre-sited)
+ *   U  = ((-38*R' -  74*G' + 112*B' + 128) >> 8) + 128
+ *   V  = ((112*R' -  94*G' -  18*B' + 128) >> 8) + 128
+ * Y is in [16,235], U and V in [16,240] for every input (no clamp).  Layout: each frame contiguous, Y (H*W bytes), then U
+ * ((H/2)*(W/2)), then V (the same); frames back to back: (T, 3*H*W/2) uint8.  H % 2 == 0, W % 4 == 0 and a non-NULL 4-byte aligned
+ * output (Y rows leave as 4-byte stores, chroma as 2-byte stores): error otherwise, nothing launched.
+ * dawn_frames_to_yuv420: vid = three fp32 planes (`plane` floats apart, a multiple of 4; 16-byte aligned) of a (3,T,H,W) clip. */
+int dawn_frames_to_yuv420(const float* vid, long plane, int T, int H, int W, double mean0, double mean1, double mean2,
+                          unsigned char* out, void* stream);
+/* dawn_final_conv_blend with the yuv420p egress defined above as its store: the same kernel source as dawn_final_conv_blend_u8 up to the
+ * RGB bytes (bgr = 0), which stay in LDS and are converted there; no fp32 frame and no RGB byte is written.  Frame t of the launch goes
+ * to frames + t*3*H*W/2. */
+int dawn_final_conv_blend_yuv420(const float* x, int T, int H, int W, int C, const float* w7, const float* bias3,
+                                 const float* src, const float* grid, long grid_plane, const float* conf, int h, int w,
+                                 double mean0, double mean1, double mean2, unsigned char* frames, void* stream);
+
 /* ---- HuBERT audio features + 25 fps interpolation (UVG:202-250, 433-501; transformers.HubertModel with
  * feat_extract_norm = "layer", do_stable_layer_norm = True = hubert-large-ls960-ft).  Activations are (time, channels)
  * rows; the conv layers 1..6, the grouped positional conv and every Linear run through dawn_conv_gemm. */
@@ -629,6 +649,18 @@ int dawn_decode_clip_conf(dawn_decoder* dec, int H, int W, int T, int h, int w, 
                           const float* grid, long grid_plane, const float* conf, int chunk, float* out_vid, float* warped_vid,
                           long out_plane, unsigned char* frames_u8, const double* mean3, int bgr, void* workspace,
                           size_t workspace_bytes, void* stream);
+/* dawn_decode_clip / dawn_decode_clip_conf with yuv420p frames as the one output: the same launch sequence, every chunk ending in
+ * dawn_final_conv_blend_yuv420; no fp32 frame and no RGB byte is written anywhere.  frames_yuv420 = (T, 3*H*W/2) uint8, I420, the
+ * definition stated at dawn_frames_to_yuv420 (Y = ((66R + 129G + 25B + 128) >> 8) + 16; U, V from the rounded 2x2 box average of R, G, B:
+ * U = ((-38R' - 74G' + 112B' + 128) >> 8) + 128, V = ((112R' - 94G' - 18B' + 128) >> 8) + 128; BT.601 limited range) on the RGB bytes
+ * of frames_u8 with bgr = 0.  The workspace is the one dawn_decoder_workspace_bytes states (no more than the frames_u8-alone path).
+ * Odd H, W % 4 != 0, a NULL or unaligned output, a short workspace: error return with a message, nothing launched. */
+int dawn_decode_clip_yuv420(dawn_decoder* dec, int H, int W, int T, int h, int w, const float* img3, const void* skip_mem,
+                            const float* latent, long latent_plane, int chunk, unsigned char* frames_yuv420, const double* mean3,
+                            void* workspace, size_t workspace_bytes, void* stream);
+int dawn_decode_clip_conf_yuv420(dawn_decoder* dec, int H, int W, int T, int h, int w, const float* img3, const void* skip_mem,
+                                 const float* grid, long grid_plane, const float* conf, int chunk, unsigned char* frames_yuv420,
+                                 const double* mean3, void* workspace, size_t workspace_bytes, void* stream);
 /* after a stream synchronise: (kind, algorithmic flops, algorithmic bytes, ms) per conv launch recorded under
  * DAWN_OPT_PROFILE; kind 0 = split 3x3, 1 = split 1x1, 2 = fp32 MFMA; returns the number of entries (and clears them) */
 int dawn_ctx_profile_read(dawn_ctx* ctx, double* out4, int max_entries);

@@ -4,6 +4,7 @@ the shipped generator topology (64/128/256 channels, 6 bottleneck blocks) and se
 
     python tools/bench_decode.py [--res 256] [--frames 200] [--iters 3] [--cpu-frames 2] [--chunk 64]
     python tools/bench_decode.py --u8 [--iters 5] [--chunk 64] [--out profiles/decode_u8.json]
+    python tools/bench_decode.py --yuv420 [--iters 5] [--chunk 64] [--out profiles/decode_yuv420.json]
 
 Prints one JSON line: decoded frames/s, algorithmic TFLOP/s of the convolutions (dense math of GEN:138-171 per frame,
 encoder excluded -- it runs once per clip here and once per FRAME in the reference), the per-kernel-class time split
@@ -12,7 +13,12 @@ measured with HIP events, and the CPU oracle (oracle/lfg_ref.py) timed on `--cpu
 `--u8` times the two ways from a sampled clip to frames in host memory, at 256^2 / 200 frames and at 128^2 / 400 frames, alternating
 them in one process: (a) `decode_clip` + `frames_to_u8` + `.cpu()` (two fp32 clips on the device, one conversion launch, one copy)
 and (b) `stream_frames_u8` drained to the host (the decoder's last kernel writes the bytes; each chunk's copy overlaps the next
-chunk's decode).  Host wall clock around work that ends with the bytes in host memory; peak allocated device bytes of each."""
+chunk's decode).  Host wall clock around work that ends with the bytes in host memory; peak allocated device bytes of each.
+
+`--yuv420` times `stream_frames_u8` against `stream_frames_yuv420` the same way (alternating in one process, host wall clock until the
+last byte is in host memory), plus the device time of the two forms of the final-conv kernel alone (HIP events around one chunk's
+launch), and checks the yuv bytes against egress.yuv420_from_rgb_u8 of the RGB ones.  A report, not a gate: from the byte counts the
+expectation is device time within noise of the u8 form and half the device->host bytes."""
 import argparse
 import json
 import os
@@ -188,6 +194,76 @@ def run_u8(iters=5, chunk=64, seed=0, cases=((256, 200), (128, 400))):
             "order": "a, b alternating in one process after one warm-up of each", "data": "synthetic", "cases": results}
 
 
+def run_yuv420(iters=5, chunk=64, seed=0, cases=((256, 200), (128, 400))):
+    """stream_frames_u8 (a) against stream_frames_yuv420 (b), alternating a, b, a, b, ... after one warm-up of each."""
+    import numpy as np
+    from dawn_pytorch_amd.egress import yuv420_from_rgb_u8
+    from dawn_pytorch_amd.flow_decoder import FlowDecoder
+    from dawn_pytorch_amd.ops import HipOps
+    dev = torch.device("cuda:0")
+    ops = HipOps()
+    dec = FlowDecoder(lfg_state_dict(seed), dev, ops=ops, chunk=chunk)
+    results = []
+    for res, frames in cases:
+        img = torch.rand(1, 3, res, res, generator=torch.Generator().manual_seed(1)).to(dev)
+        grid, conf = synthetic_motion(frames, res // 4, dev)
+        fb = res * res * 3 // 2
+
+        def rgb():
+            out = np.empty((frames, res, res, 3), dtype=np.uint8)
+            for t0, fr in dec.stream_frames_u8(img, grid, conf):
+                out[t0:t0 + len(fr)] = fr
+            return out
+
+        def yuv():
+            out = np.empty((frames, fb), dtype=np.uint8)
+            for t0, fr in dec.stream_frames_yuv420(img, grid, conf):
+                out[t0:t0 + len(fr)] = fr
+            return out
+
+        def timed(fn):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = fn()
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) * 1e3, out
+
+        _, a0 = timed(rgb)                             # warm-up of every shape; b must be the definition applied to a
+        _, b0 = timed(yuv)
+        same = bool(np.array_equal(yuv420_from_rgb_u8(torch.from_numpy(a0)).numpy(), b0))
+        del a0, b0
+        ta, tb = [], []
+        for _ in range(iters):
+            ta.append(timed(rgb)[0])
+            tb.append(timed(yuv)[0])
+        # the last kernel of a chunk alone, both forms, on the same input
+        n = min(chunk, frames)
+        C0 = dec.C0
+        x = torch.randn(n * res * res, C0, generator=torch.Generator().manual_seed(2)).to(dev)
+        g, cf = grid[0, :, :n], conf[0, 0, :n].contiguous()
+        fu8 = torch.empty(n, res, res, 3, device=dev, dtype=torch.uint8)
+        fyuv = torch.empty(n, fb, device=dev, dtype=torch.uint8)
+        ku, ky = [], []
+        for i in range(iters + 1):
+            for fn, buf, acc in ((ops.final_conv_blend_u8, fu8, ku), (ops.final_conv_blend_yuv420, fyuv, ky)):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fn(x, res, res, dec.final_w7, dec.final_bias, img[0].contiguous(), g, cf, buf)
+                e1.record()
+                e1.synchronize()
+                if i:
+                    acc.append(e0.elapsed_time(e1))
+        med = lambda v: sorted(v)[len(v) // 2]         # noqa: E731
+        results.append({"workload": f"{res}x{res}, {frames} frames, chunk {chunk}", "yuv_is_definition_of_rgb": same,
+                        "stream_u8_ms": med(ta), "stream_yuv420_ms": med(tb), "stream_u8_all_ms": ta, "stream_yuv420_all_ms": tb,
+                        "d2h_bytes_u8": frames * res * res * 3, "d2h_bytes_yuv420": frames * fb,
+                        "final_conv_u8_kernel_ms": med(ku), "final_conv_yuv420_kernel_ms": med(ky), "kernel_frames": n,
+                        "final_conv_u8_kernel_all_ms": ku, "final_conv_yuv420_kernel_all_ms": ky})
+    return {"metric": "sampled clip -> frames in host memory, ms per clip (host wall clock, ends after the last byte arrived)",
+            "a": "stream_frames_u8 drained to the host", "b": "stream_frames_yuv420 drained to the host", "iters": iters,
+            "order": "a, b alternating in one process after one warm-up of each", "data": "synthetic", "cases": results}
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--res", type=int, default=256)
@@ -196,10 +272,11 @@ if __name__ == "__main__":
     ap.add_argument("--chunk", type=int, default=64)
     ap.add_argument("--cpu-frames", type=int, default=2)
     ap.add_argument("--u8", action="store_true", help="time decode_clip + frames_to_u8 + .cpu() against stream_frames_u8")
-    ap.add_argument("--out", type=str, default=None, help="--u8: also write the JSON result to this file")
+    ap.add_argument("--yuv420", action="store_true", help="time stream_frames_u8 against stream_frames_yuv420")
+    ap.add_argument("--out", type=str, default=None, help="--u8 / --yuv420: also write the JSON result to this file")
     a = ap.parse_args()
-    if a.u8:
-        r = run_u8(5 if a.iters is None else a.iters, a.chunk)
+    if a.u8 or a.yuv420:
+        r = (run_yuv420 if a.yuv420 else run_u8)(5 if a.iters is None else a.iters, a.chunk)
         if a.out:
             with open(a.out, "w") as f:
                 json.dump(r, f, indent=1)
