@@ -146,6 +146,11 @@ SIGNATURES = {
     "dawn_attn64": [c_f, _i, _i, c_f, c_f],
     "dawn_interp_linear": [c_f, _l, _i, c_f, _l, c_f, c_f],
 }
+# device helpers of the C-side evaluator (csrc/dawn_ctx.hip calls them; from Python only the op tests do)
+CTX_HELPER_SIGNATURES = {
+    "dawn_chw_to_hwc": [c_f, _i, _l, c_f, c_f],
+    "dawn_rotary_tables": [c_f, _i, _i, c_f, c_f, c_f],
+}
 
 _lib = None
 
@@ -168,7 +173,7 @@ def lib() -> C.CDLL:
         L = C.CDLL(str(LIB_PATH))
         L.dawn_last_error.restype = C.c_char_p
         L.dawn_abi_version.restype = _i
-        for name, args in SIGNATURES.items():
+        for name, args in {**SIGNATURES, **CTX_HELPER_SIGNATURES}.items():
             fn = getattr(L, name)
             fn.argtypes = args
             fn.restype = _l if name in LONG_RESULT else _i

@@ -332,7 +332,12 @@ __device__ __attribute__((aligned(64))) float dawn_zero_block[16];
 // NST = 3: three LDS stages, loads issued TWO chunks ahead and retired with a COUNTED s_waitcnt vmcnt(IPC) + raw
 // s_barrier (a __syncthreads() would drain the whole DMA queue), so one chunk of loads is always in flight
 // across the barrier (cdna_hip_programming.md "Pipelining across barriers").
-template <int BN, int NST, int BK, int WN = 2>
+// FOLD (K >= GLDS_FOLD_MIN_K, the 1-D convs and Linears of the HuBERT stage, the 7x7 fea conv): every GLDS_FOLD_K products the MFMA
+// accumulators are added to a second set and cleared.  One fp32 chain over all of K (K / 2 MFMA additions per output) measured 6.4x (K =
+// 1536), 9.3x (K = 4096) and 12x (K = 8192) the error of a blocked CPU fp32 GEMM against float64, half of what a 16-bit-mantissa operand
+// costs; two-level chains of GLDS_FOLD_K / 2 + K / GLDS_FOLD_K additions stay at CPU fp32's level (tests/stage_gate.py).
+constexpr int GLDS_FOLD_K = 512, GLDS_FOLD_MIN_K = 1024;
+template <int BN, int NST, int BK, int WN = 2, bool FOLD = false>
 __global__ __launch_bounds__(256) void conv_gemm_glds_kernel(const dawn_conv_desc d, const int xcd_remap) {
     constexpr int BM = 64 * (4 / WN), KQ = BK / 4; // 4 waves as (4/WN) x WN, 64 rows each; KQ 16-B slots per A row
     constexpr int WTN = BN / WN;
@@ -448,6 +453,16 @@ __global__ __launch_bounds__(256) void conv_gemm_glds_kernel(const dawn_conv_des
         for (int j = 0; j < TN; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    constexpr int FOLD_CHUNKS = GLDS_FOLD_K / BK;
+    f32x16 tot[FOLD ? TM : 1][FOLD ? TN : 1];
+    if (FOLD) {
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int j = 0; j < TN; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) tot[FOLD ? i : 0][FOLD ? j : 0][r] = 0.f;
+    }
 
     issue(0, 0);
     if (NST == 3) {
@@ -490,6 +505,17 @@ __global__ __launch_bounds__(256) void conv_gemm_glds_kernel(const dawn_conv_des
                     for (int j = 0; j < TN; ++j)
                         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(b[j][s], a[i][s], acc[i][j], 0, 0, 0);   // D^T: lane = row
         }
+        if (FOLD && ((chunk + 1) & (FOLD_CHUNKS - 1)) == 0) {   // (uniform) close this chain of GLDS_FOLD_K products
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int j = 0; j < TN; ++j)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        tot[FOLD ? i : 0][FOLD ? j : 0][r] += acc[i][j][r];
+                        acc[i][j][r] = 0.f;
+                    }
+        }
         if (NST == 3) {
             // chunk+1 must have landed, chunk+2 (just issued) may stay in flight; all reads of `buf` retired
             if (chunk + 2 < nChunks) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(IPC) : "memory");
@@ -500,6 +526,15 @@ __global__ __launch_bounds__(256) void conv_gemm_glds_kernel(const dawn_conv_des
             __syncthreads();   // drains the LDS-DMA of chunk+1 (vmcnt) and retires every read of `buf`
             buf ^= 1;
         }
+    }
+
+    if (FOLD) {
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int j = 0; j < TN; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[i][j][r] += tot[FOLD ? i : 0][FOLD ? j : 0][r];
     }
 
     // ---- epilogue.  The tiles are accumulated TRANSPOSED (A = weights, B = rows): lane = output row, registers
@@ -1129,12 +1164,17 @@ void launch(const dawn_conv_desc& d, long M, hipStream_t s) {
             return;
         }
         if (d.gn_rows) *d.gn_rows = nwg;   // rows of gn_part this launch writes
-        if (((policy_of(d) & 0x80) || deep) && d.C0 % 32 == 0 && d.C1 % 32 == 0)
-            hipLaunchKernelGGL((conv_gemm_glds_kernel<BN, 2, 32>), grid, dim3(256), 0, s, d, remap);
-        else if (policy_of(d) & 0x100)
+        const bool fold = d.KH * d.KW * (d.C0 + d.C1) >= GLDS_FOLD_MIN_K;     // two-level K accumulation (see the kernel)
+        if (((policy_of(d) & 0x80) || deep) && d.C0 % 32 == 0 && d.C1 % 32 == 0) {
+            if (fold) hipLaunchKernelGGL((conv_gemm_glds_kernel<BN, 2, 32, 2, true>), grid, dim3(256), 0, s, d, remap);
+            else hipLaunchKernelGGL((conv_gemm_glds_kernel<BN, 2, 32>), grid, dim3(256), 0, s, d, remap);
+        } else if (policy_of(d) & 0x100) {
             hipLaunchKernelGGL((conv_gemm_glds_kernel<BN, 3, 16>), grid, dim3(256), 0, s, d, remap);
-        else
+        } else if (fold) {
+            hipLaunchKernelGGL((conv_gemm_glds_kernel<BN, 2, 16, 2, true>), grid, dim3(256), 0, s, d, remap);
+        } else {
             hipLaunchKernelGGL((conv_gemm_glds_kernel<BN, 2, 16>), grid, dim3(256), 0, s, d, remap);
+        }
         return;
     }
     if (d.ch_a || d.pro_act || d.pro_add) launch_pro<BM, BN, BK, WM, WN, 2>(d, M, s);

@@ -101,7 +101,7 @@ def decoder_forward(sd: SD, x: Tensor, z: Tensor, y: Tensor, mask: Tensor, heads
     d = mem.shape[2]
     bias_t = rel_pos_bias(sd["time_rel_pos_bias_tgt.relative_attention_bias.weight"], T, num_buckets, max_distance, window)[None]
     bias_m = rel_pos_bias(sd["time_rel_pos_bias_mem.relative_attention_bias.weight"], T, num_buckets, max_distance, window)[None]
-    tq = F.linear(torch.zeros(bs, T, d), sd["init_proj.weight"], sd["init_proj.bias"])                               # :347, :353
+    tq = F.linear(torch.zeros(bs, T, d, dtype=mem.dtype), sd["init_proj.weight"], sd["init_proj.bias"])                               # :347, :353
     # init_temporal_attn = Residual(PreNorm(LayerNorm(gamma only), Attention)) :298, :16-43
     g = sd["init_temporal_attn.fn.norm.gamma"]
     xn = (tq - tq.mean(-1, keepdim=True)) / (tq.var(-1, unbiased=False, keepdim=True) + 1e-5).sqrt() * g

@@ -81,17 +81,21 @@ def test_hubert_stage_vs_reference_golden():
     assert e1 < 3e-4 and e2 < 3e-4 and e3 < 3e-4 and out.dtype == np.float32 and out.shape == g["target_audio"].shape
 
 
+def _hubert_large_config(layers):
+    from transformers import HubertConfig
+    return HubertConfig(hidden_size=1024, num_hidden_layers=layers, num_attention_heads=16, intermediate_size=4096,
+                        conv_dim=(512,) * 7, conv_stride=(5, 2, 2, 2, 2, 2, 2), conv_kernel=(10, 3, 3, 3, 3, 2, 2), conv_bias=True,
+                        feat_extract_norm="layer", do_stable_layer_norm=True, num_conv_pos_embeddings=128,
+                        num_conv_pos_embedding_groups=16, hidden_dropout=0.0, attention_dropout=0.0, feat_proj_dropout=0.0,
+                        activation_dropout=0.0, layerdrop=0.0, apply_spec_augment=False)
+
+
 def test_hubert_large_architecture_vs_transformers():
     """hubert-large-ls960-ft's architecture (24 x 1024, 16 heads, 7 x 512 conv stack, 128-tap / 16-group positional conv),
     random init: HIP vs transformers.HubertModel on the host cores, 1.3 s of audio."""
-    from transformers import HubertConfig, HubertModel
-    cfg = HubertConfig(hidden_size=1024, num_hidden_layers=24, num_attention_heads=16, intermediate_size=4096,
-                       conv_dim=(512,) * 7, conv_stride=(5, 2, 2, 2, 2, 2, 2), conv_kernel=(10, 3, 3, 3, 3, 2, 2), conv_bias=True,
-                       feat_extract_norm="layer", do_stable_layer_norm=True, num_conv_pos_embeddings=128,
-                       num_conv_pos_embedding_groups=16, hidden_dropout=0.0, attention_dropout=0.0, feat_proj_dropout=0.0,
-                       activation_dropout=0.0, layerdrop=0.0, apply_spec_augment=False)
+    from transformers import HubertModel
     torch.manual_seed(0)
-    model = HubertModel(cfg).eval()
+    model = HubertModel(_hubert_large_config(24)).eval()
     x = rnd(16000 + 4800 + 13, seed=11)
     with torch.no_grad():
         want = model(x[None]).last_hidden_state[0]
@@ -100,3 +104,23 @@ def test_hubert_large_architecture_vs_transformers():
     err = float((got - want).abs().max())
     print(f"hubert-large architecture: max|hip - transformers| = {err:.2e} (max|ref| {float(want.abs().max()):.2f})")
     assert got.shape == want.shape and err < 2e-3
+
+
+def test_hubert_large_widths_fp64_gate():
+    """The whole stage at fp32 accuracy: hubert-large's widths, 4 encoder layers (depth only accumulates: the kernel instantiations are
+    those of the 24-layer model), 1.3 s of audio.  HIP must be as close to transformers.HubertModel evaluated in float64 as the same
+    model in fp32 on the host cores is, x 3 + 2e-6 of the output's scale (the flow decoder's gate); both errors go to the op-error log."""
+    from transformers import HubertModel
+    from split_gate import fp32_gate
+    torch.manual_seed(0)
+    model = HubertModel(_hubert_large_config(4)).eval()
+    x = rnd(16000 + 4800 + 13, seed=11)
+    hf = HubertFeatures.from_model(model, "cuda:0")
+    got = hf.encode(x.cuda()).cpu()
+    with torch.no_grad():
+        base32 = model(x[None]).last_hidden_state[0]
+        want64 = model.double()(x[None].double()).last_hidden_state[0]
+    assert got.shape == want64.shape
+    rec = fp32_gate("hubert_large_widths_4layers", got, want64, base32, c=3.0, floor=2e-6)
+    print(f"hubert-large widths, 4 layers: max|hip - fp64| = {rec['max_abs_err']:.2e}, fp32 transformers' {rec['rel_err_cpu_fp32'] * rec['scale']:.2e}"
+          f" (max|fp64| {rec['scale']:.2f})")

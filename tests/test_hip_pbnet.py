@@ -113,3 +113,20 @@ def test_pbnet_shipped_size_vs_oracle_and_stage(tmp_path):
     assert pose.shape == (Tn, 6) and blink.shape == (Tn, 2) and not pose.is_cuda
     torch.testing.assert_close(pose, wp, atol=2e-2, rtol=1e-5)                  # (de-normalised by ranges of up to 1080)
     torch.testing.assert_close(blink, wb, atol=2e-5, rtol=0)
+
+
+@pytest.mark.parametrize("name,in_dim,seed", [("pose", 6, 1), ("blink", 2, 2)])
+def test_pbnet_shipped_size_fp64_gate(name, in_dim, seed):
+    """The shipped-size decoders at fp32 accuracy: HIP must be as close to the oracle evaluated in float64 as the fp32 oracle on the host
+    cores is, x 3 + 2e-6 of the output's scale (the flow decoder's gate); both errors go to the op-error log."""
+    from split_gate import fp32_gate
+    Tn = 200
+    sd = _random_decoder_sd(in_dim, seed=seed)
+    gn = torch.Generator().manual_seed(5)
+    audio, z, ip = torch.randn(1, Tn, 1024, generator=gn), torch.randn(Tn, 1, 256, generator=gn), torch.rand(1, 1, in_dim, generator=gn)
+    dur = torch.tensor([Tn])
+    got = PoseBlinkGenerator(sd, archiname=MODELS[name], device="cuda").generate(ip, audio, dur, z=z)["output"]
+    base32 = R.generate(sd, ip, audio, dur, z, archiname=MODELS[name])
+    want64 = R.generate({k: v.double() for k, v in sd.items()}, ip.double(), audio.double(), dur, z.double(), archiname=MODELS[name])
+    assert want64.dtype == torch.float64 and base32.dtype == torch.float32
+    fp32_gate(f"pbnet_full/{name}", got, want64, base32, c=3.0, floor=2e-6)
