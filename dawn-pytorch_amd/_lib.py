@@ -54,6 +54,7 @@ class ConvDesc(C.Structure):
 SIGNATURES = {
     "dawn_conv_gemm": [C.POINTER(ConvDesc), c_f],
     "dawn_conv3x3_form": [C.POINTER(ConvDesc)],
+    "dawn_conv3x3_direct_form": [C.POINTER(ConvDesc)],
     "dawn_gemm1x1_form": [C.POINTER(ConvDesc)],
     "dawn_conv_gemm_nblocks": [_l, _i],
     "dawn_conv3x3_wino_ok": [_i, _i, _i, _i, _i, _i],

@@ -545,7 +545,7 @@ __global__ __launch_bounds__(256 * WN, (K32 && PSEG == 28) ? 2 / WN : 1) void co
 }
 
 template <int WN>
-bool try_launch_bf16_v2(const dawn_conv_desc& d, long M, hipStream_t s, bool nine) {
+bool try_launch_bf16_v2(const dawn_conv_desc& d, long M, hipStream_t s, bool nine, bool dry /* decide only, launch nothing */) {
     constexpr int BM = 256, BN = 64 * WN;
     const int H = d.Hi, W = d.Wi;
     // tile width: whole image rows up to W = 64 (every level of the denoiser); wider images (the flow decoder's
@@ -567,6 +567,7 @@ bool try_launch_bf16_v2(const dawn_conv_desc& d, long M, hipStream_t s, bool nin
     if (P16 > 576 || (big_patch && !k32)) return false;
     const size_t lds = (size_t)6 * (P16 * 16 + 128) + (size_t)2 * 18 * BN * 16 + (timing || k32 ? 512 : 0);   // (+ the GroupNorm exchange)
     if (lds > 160 * 1024) return false;
+    if (dry) return true;
     const int nwg = (int)(M / BM) * (d.N / BN);
     const int remap = ((policy_of(d) & 4) && nwg >= 64 && H * W >= 1024) ? 1 : 0;
     // start delay of the second resident workgroup set in units of ~8k cycles (policy bits 20..23; default 0 = none): in
@@ -607,8 +608,8 @@ bool try_launch_bf16_v2(const dawn_conv_desc& d, long M, hipStream_t s, bool nin
 
 }  // namespace
 
-bool dawn_conv3x3_v2_try(const dawn_conv_desc& d, long M, hipStream_t s, bool nine, bool narrow) {
-    return narrow ? try_launch_bf16_v2<1>(d, M, s, nine) : try_launch_bf16_v2<2>(d, M, s, nine);
+bool dawn_conv3x3_v2_try(const dawn_conv_desc& d, long M, hipStream_t s, bool nine, bool narrow, bool dry) {
+    return narrow ? try_launch_bf16_v2<1>(d, M, s, nine, dry) : try_launch_bf16_v2<2>(d, M, s, nine, dry);
 }
 
 #ifdef DAWN_ABLATION

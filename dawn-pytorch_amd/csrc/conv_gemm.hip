@@ -1098,7 +1098,7 @@ __global__ __launch_bounds__(256) void conv3x3_halo_bf16_kernel(const dawn_conv_
 }
 
 template <int BN, int WN>
-bool try_launch_halo_bf16(const dawn_conv_desc& d, long M, hipStream_t s, bool nine) {
+bool try_launch_halo_bf16(const dawn_conv_desc& d, long M, hipStream_t s, bool nine, bool dry /* decide only, launch nothing */) {
     constexpr int BM = 64 * (4 / WN);
     const int H = d.Hi, W = d.Wi;
     if (M % BM != 0 || W > BM || BM % W != 0 || d.C0 % 16 != 0 || d.C1 % 16 != 0) return false;
@@ -1110,6 +1110,7 @@ bool try_launch_halo_bf16(const dawn_conv_desc& d, long M, hipStream_t s, bool n
     if (P16 / 16 > 7 * 4) return false;
     const size_t lds = (size_t)P16 * 64 + (size_t)6 * (P16 * 16 + 128) + (size_t)2 * 3 * BN * 32;
     if (lds > 160 * 1024) return false;
+    if (dry) return true;
     const int nwg = (int)(M / BM) * dawn_cdiv(d.N, BN);
     const int remap = ((policy_of(d) & 4) && nwg >= 64 && H * W >= 1024) ? 1 : 0;
     if (d.gn_rows) *d.gn_rows = nwg;   // rows of gn_part this launch writes
@@ -1328,6 +1329,45 @@ extern "C" int dawn_conv3x3_form(const dawn_conv_desc* dp) {
     return 0;
 }
 
+/* The direct split-operand 3x3 kernels, in dawn_conv_gemm's order: conv3x3_bf16_v2_kernel with 256 x 64 or 256 x 128 tiles, then the v1 halo
+ * kernel.  Launches the first that takes the descriptor (dry: launches nothing) and answers which (DAWN_DIRECT3X3_* of include/dawn_hip.h;
+ * NONE: the fp32 kernels are next).  THE routing of dawn_conv_gemm and of dawn_conv3x3_direct_form. */
+static int conv3x3_direct(const dawn_conv_desc& d, long M, hipStream_t s, bool nine, bool dry) {
+    if (policy_of(d) & 0x4000) {           // v2 structure (row-of-taps weight stages, register-prefetched patch)
+        // 256 x 128 tiles run one 8-wave workgroup per CU: when they occupy at most half of the 256 CUs (M = 12,800 rows,
+        // N = 256: 100 tiles), 256 x 64 tiles put one 4-wave workgroup on twice as many CUs and the launch takes
+        // 0.67x the time (measured 520 -> 349 us at K = 9216, 142 -> 97 us at K = 2304; with 129..256 tiles the same
+        // CUs stay busy either way and nothing is gained)
+        // ... and at N = 128 with many tiles (level 1: 1600 narrow tiles): two 4-wave workgroups per CU (76 KB of LDS each)
+        // overlap each other's prologue / epilogue, the 8-wave 128-column workgroup (108 KB) holds its CU alone:
+        // 356 -> 314 us at M = 204,800, K = 1152 (no difference at N = 256 / 512 with 800 / 400 narrow tiles)
+        const bool narrow = d.N <= 64 || (d.N % 64 == 0 && M % 256 == 0 && ((M / 256) * ((d.N + 127) / 128) <= 128 ||
+                                                                          (d.N == 128 && (M / 256) * 2 >= 1536)));
+        if (dawn_conv3x3_v2_try(d, M, s, nine, narrow, dry)) return narrow ? DAWN_DIRECT3X3_V2_WN1 : DAWN_DIRECT3X3_V2_WN2;
+        if (narrow && d.N > 64 && dawn_conv3x3_v2_try(d, M, s, nine, false, dry)) return DAWN_DIRECT3X3_V2_WN2;
+    }
+    const bool ok = d.N <= 64 ? try_launch_halo_bf16<64, 1>(d, M, s, nine, dry) : try_launch_halo_bf16<128, 2>(d, M, s, nine, dry);
+    return ok ? DAWN_DIRECT3X3_HALO : DAWN_DIRECT3X3_NONE;
+}
+
+/* Which direct split-operand 3x3 kernel dawn_conv_gemm would run for this descriptor (host code, launches nothing): DAWN_DIRECT3X3_HALO =
+ * conv3x3_halo_bf16_kernel, _V2_WN1 / _V2_WN2 = conv3x3_bf16_v2_kernel with 256 x 64 (four waves) / 256 x 128 (eight waves) tiles, NONE when
+ * the descriptor does not reach them: a split 1x1 / resample kernel or a Winograd form takes it, or it falls to the fp32 kernels.  The
+ * launch's own decision code (conv3x3_direct), as dawn_conv3x3_form. */
+extern "C" int dawn_conv3x3_direct_form(const dawn_conv_desc* dp) {
+    if (!dp) return DAWN_DIRECT3X3_NONE;
+    const dawn_conv_desc& d = *dp;
+    if (d.C0 % 16 != 0 || d.C1 % 16 != 0 || d.C0 + d.C1 == 0 || (d.ld0 % 4) || (d.in1 && (d.ld1 % 4)) || d.border)
+        return DAWN_DIRECT3X3_NONE;   // dawn_conv_gemm rejects these
+    const long M = (long)d.F * d.Ho * d.Wo;
+    if (M <= 0 || d.N <= 0 || !conv3x3_split_path(d) || split1x1_form(d, M) != DAWN_SPLIT1X1_NONE || dawn_conv3x3_form(dp) != 0)
+        return DAWN_DIRECT3X3_NONE;
+#ifdef DAWN_WITH_STREAMK
+    if ((policy_of(d) & 0x400) && !(policy_of(d) & 0x2000) && d.sk_ws) return DAWN_DIRECT3X3_NONE;   // (experimental build: the stream-K kernel may take it)
+#endif
+    return conv3x3_direct(d, M, nullptr, (policy_of(d) & 0x2000) != 0, true);
+}
+
 /* Which split-operand kernel dawn_conv_gemm runs a 1x1 projection / 4x4 resample descriptor on (host code, launches nothing): the
  * launch's own decision code, as dawn_conv3x3_form for the 3x3 convs. */
 extern "C" int dawn_gemm1x1_form(const dawn_conv_desc* dp) {
@@ -1366,7 +1406,6 @@ extern "C" int dawn_conv_gemm(const dawn_conv_desc* dp, void* stream) {
     }
     if (conv3x3_split_path(d)) {
         const bool nine = (policy_of(d) & 0x2000) != 0;
-        bool ok = false;
         if ((policy_of(d) & 0x8000000) && !nine && d.w_wino4) {  // Winograd F(4x4,3x3) form (conv3x3_wino4.hip; opt-in)
             int rows = 0;
             if (dawn_conv3x3_wino4_try(d, M, policy_of(d), s, &rows, 0)) {
@@ -1393,20 +1432,7 @@ extern "C" int dawn_conv_gemm(const dawn_conv_desc* dp, void* stream) {
             }
         }
 #endif
-        if (policy_of(d) & 0x4000) {           // v2 structure (row-of-taps weight stages, register-prefetched patch)
-            // 256 x 128 tiles run one 8-wave workgroup per CU: when they occupy at most half of the 256 CUs (M = 12,800 rows,
-            // N = 256: 100 tiles), 256 x 64 tiles put one 4-wave workgroup on twice as many CUs and the launch takes
-            // 0.67x the time (measured 520 -> 349 us at K = 9216, 142 -> 97 us at K = 2304; with 129..256 tiles the same
-            // CUs stay busy either way and nothing is gained)
-            // ... and at N = 128 with many tiles (level 1: 1600 narrow tiles): two 4-wave workgroups per CU (76 KB of LDS each)
-            // overlap each other's prologue / epilogue, the 8-wave 128-column workgroup (108 KB) holds its CU alone:
-            // 356 -> 314 us at M = 204,800, K = 1152 (no difference at N = 256 / 512 with 800 / 400 narrow tiles)
-            const bool narrow = d.N <= 64 || (d.N % 64 == 0 && M % 256 == 0 && ((M / 256) * ((d.N + 127) / 128) <= 128 ||
-                                                                              (d.N == 128 && (M / 256) * 2 >= 1536)));
-            ok = dawn_conv3x3_v2_try(d, M, s, nine, narrow);
-            if (!ok && narrow && d.N > 64) ok = dawn_conv3x3_v2_try(d, M, s, nine, false);
-        }
-        if (!ok) ok = d.N <= 64 ? try_launch_halo_bf16<64, 1>(d, M, s, nine) : try_launch_halo_bf16<128, 2>(d, M, s, nine);
+        const bool ok = conv3x3_direct(d, M, s, nine, false) != DAWN_DIRECT3X3_NONE;
         if (ok) {
             DAWN_LAUNCH_CHECK();
             return 0;

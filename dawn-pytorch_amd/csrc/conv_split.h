@@ -50,7 +50,8 @@ __device__ __forceinline__ void split3(const f32x4 v, uint2& p1, uint2& p2, uint
 int dawn_ncu();                                            // CUs of the current device (conv_gemm.hip)
 int gemm1x1_split_plan(long M, int N, int C0, int C1);     // tile plan of the tiled split 1x1 GEMM (conv_gemm.hip)
 // conv3x3_bf16_v2_kernel with 256 x 64 (narrow) or 256 x 128 tiles; false when the geometry does not fit (conv3x3_split.hip)
-bool dawn_conv3x3_v2_try(const dawn_conv_desc& d, long M, hipStream_t s, bool nine, bool narrow);
+// dry: decide only -- the answer of the launch's own geometry checks, before any hipFuncSetAttribute, launch or write to *d.gn_rows
+bool dawn_conv3x3_v2_try(const dawn_conv_desc& d, long M, hipStream_t s, bool nine, bool narrow, bool dry);
 void dawn_gemm1x1_tiled_launch(const dawn_conv_desc& d, long M, hipStream_t s);              // gemm1x1_tiled.hip
 void dawn_gemm1x1_rowreg_launch(const dawn_conv_desc& d, long M, hipStream_t s);             // gemm1x1_rows.hip
 // mode 0: 1x1 projection, 1: 4x4 / stride-2 Downsample, 2: transposed 4x4 Upsample as four phases (gemm1x1_rows.hip)

@@ -148,7 +148,8 @@ class HipOps:
                   form_only: bool = False, border: int = 0) -> Tensor:
         """gn_fin = (gamma, beta, film or None, total_rows[, eps]) with gn_part: ask the launch to finish the GroupNorm itself (the
         Winograd 3x3 kernel's last workgroup reduces and finalises); gn_coeffs(part=...) then returns its coefficients without a launch.
-        form_only: launch nothing and return (dawn_conv3x3_form, dawn_gemm1x1_form) of exactly this call's descriptor.
+        form_only: launch nothing and return (dawn_conv3x3_form, dawn_gemm1x1_form) of exactly this call's descriptor; form_only="direct":
+        its dawn_conv3x3_direct_form (0 none, 1 the v1 halo kernel, 2 / 3 conv3x3_bf16_v2_kernel with 256 x 64 / 256 x 128 tiles).
         border (mode 1): what a phase tap outside the input reads -- 0 zero, 1 the edge pixel, 2 the opposite edge (pack.up_border)."""
         Ho = Hi if Ho is None else Ho
         Wo = Wi if Wo is None else Wo
@@ -182,6 +183,8 @@ class HipOps:
         d.ln_eps = ln_eps
         if self.sk_ws is not None and w_bf3 is not None and KH == 3 and KW == 3 and stride == 1 and mode == 0:
             d.sk_ws, d.sk_ws_bytes = _p(self.sk_ws), self.sk_ws.numel()        # (ignored by the shipped library)
+        if form_only == "direct":
+            return int(self.L.dawn_conv3x3_direct_form(C.byref(d)))
         if form_only:
             return self.conv3x3_form(d), int(self.L.dawn_gemm1x1_form(C.byref(d)))
         nrows = C.c_int(0)

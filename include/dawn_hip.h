@@ -112,6 +112,13 @@ int dawn_conv3x3_wino4_ok(int F, int H, int W, int C0, int C1, int N);
 /* Which form of the 3x3 conv dawn_conv_gemm would run for this descriptor (host code, launches nothing; the launch's own decision
  * code): 2 = Winograd F(4x4,3x3), 1 = Winograd F(2x2,3x3), 0 = anything else. */
 int dawn_conv3x3_form(const dawn_conv_desc* d);
+/* Which DIRECT split-operand 3x3 kernel dawn_conv_gemm would run for this descriptor (host code, launches nothing; the launch's own
+ * decision code, tile width included -- it depends on the number of rows, so fewer frames can land on another kernel): */
+#define DAWN_DIRECT3X3_NONE 0     /* none: a Winograd form or a split 1x1 / resample kernel takes it, or it falls to the fp32 kernels */
+#define DAWN_DIRECT3X3_HALO 1     /* conv3x3_halo_bf16_kernel (v1) */
+#define DAWN_DIRECT3X3_V2_WN1 2   /* conv3x3_bf16_v2_kernel, 256 x 64 tiles (four waves) */
+#define DAWN_DIRECT3X3_V2_WN2 3   /* conv3x3_bf16_v2_kernel, 256 x 128 tiles (eight waves) */
+int dawn_conv3x3_direct_form(const dawn_conv_desc* d);
 /* Which split-operand kernel dawn_conv_gemm would run a 1x1 projection or a 4x4 / stride-2 resample descriptor on (host code, launches
  * nothing; the launch's own decision code): */
 #define DAWN_SPLIT1X1_NONE 0      /* none of them: the 3x3 paths or the fp32 kernels */
