@@ -146,6 +146,15 @@ SIGNATURES = {
     "dawn_add_act": [c_f, c_f, _i, _l, c_f, c_f],
     "dawn_attn64": [c_f, _i, _i, c_f, c_f],
     "dawn_interp_linear": [c_f, _l, _i, c_f, _l, c_f, c_f],
+    "dawn_hubert_pos_conv": [c_f, _i, _i, _i, _i, c_f, c_f, c_f, c_f],
+    # whole-path HuBERT stage (csrc/dawn_hubert.hip; the handle, the cfg struct and the named-pointer table travel as void*: ctx.py)
+    "dawn_hubert_create": [c_f, c_f, _i, c_f],
+    "dawn_hubert_destroy": [c_f],
+    "dawn_hubert_conv_frames": [c_f, _l],
+    "dawn_hubert_segments": [c_f, _l, C.POINTER(C.c_long), _i, C.POINTER(C.c_long), C.POINTER(C.c_long)],
+    "dawn_hubert_workspace_bytes": [c_f, _l],
+    "dawn_hubert_encode": [c_f, c_f, _l, c_f, c_f, C.c_size_t, c_f],
+    "dawn_hubert_features": [c_f, c_f, _l, c_f, c_f, c_f, C.c_size_t, c_f],
 }
 # device helpers of the C-side evaluator (csrc/dawn_ctx.hip calls them; from Python only the op tests do)
 CTX_HELPER_SIGNATURES = {
@@ -160,7 +169,8 @@ class DawnHipError(RuntimeError):
     pass
 
 
-LONG_RESULT = {"dawn_sla_ws_floats", "dawn_workspace_bytes_guided", "dawn_decoder_skip_bytes", "dawn_decoder_workspace_bytes"}       # entry points that return a size (long), not a status
+LONG_RESULT = {"dawn_sla_ws_floats", "dawn_workspace_bytes_guided", "dawn_decoder_skip_bytes", "dawn_decoder_workspace_bytes",
+               "dawn_hubert_conv_frames", "dawn_hubert_workspace_bytes"}       # entry points that return a size (long), not a status
 
 
 def lib() -> C.CDLL:

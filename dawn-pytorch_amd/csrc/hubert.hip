@@ -203,6 +203,110 @@ __global__ __launch_bounds__(256) void interp_linear_kernel(const float* __restr
     out[idx] = (float)(slope * (x - (double)lo) + (double)ylo);
 }
 
+
+// ---- HubertPositionalConvEmbedding + the residual that follows it, one launch (hubert.py encode; transformers: Conv1d(E, E, k,
+// padding = k / 2, groups) -> SamePad drop for even k -> GELU; hidden + that):
+//   out[t][g gw + n] = hid[t][g gw + n] + gelu(bias[g gw + n] + sum_{j < k} sum_{c < gw} w[g][j][c][n] hid[t + j - k/2][g gw + c])
+// One workgroup = one group x 64 output columns x 64 rows; grid (groups * column chunks, row tiles): the linear id puts a group's row
+// tiles on one XCD (id % 8 = group % 8 for 16 groups), so its weights cross that L2 once.  The 64 + k - 1 input rows every tap of the
+// tile reads are staged once in LDS (row pitch gw + 2 floats: the 32 rows of a ds_read_b64 fall on 32 different bank pairs); the K
+// loop then streams nothing but the pack_kn weight image.  Four waves = 2 column halves x 2 halves of K (16-k units, in order); each
+// holds two 32 x 32 accumulators (rows 0-31 / 32-63) that share its B operand.  A 4-k quad q of the image feeds two MFMAs: lane half
+// h supplies k = 4q + 2h, then 4q + 2h + 1 (one 8-byte load per operand).  Sum order = fixed: each half of K in fp32 MFMA chains of
+// 256 products added in order, lower half + upper half (through LDS), + bias; no atomics, bit-identical run to run.
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+#define POS_BM 64
+
+__global__ __launch_bounds__(256) void pos_conv_kernel(const float* __restrict__ hid, int T, int E, int gw, int k,
+                                                       const float* __restrict__ w, const float* __restrict__ bias,
+                                                       float* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int nch = (gw + 63) / 64;
+    const int g = blockIdx.x / nch, chunk = blockIdx.x - g * nch;
+    const int t0 = blockIdx.y * POS_BM;
+    const int ldw = gw + 2, wrows = POS_BM + k - 1, c4n = gw / 4;
+    // window row r = hid row t0 - k/2 + r, zero outside [0, T)
+    for (int i = threadIdx.x; i < wrows * c4n; i += 256) {
+        const int r = i / c4n, c = (i - r * c4n) * 4;
+        const int t = t0 - k / 2 + r;
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        if (t >= 0 && t < T) v = *reinterpret_cast<const f32x4*>(hid + (long)t * E + g * gw + c);
+        *reinterpret_cast<f32x2*>(sm + r * ldw + c) = f32x2{v.x, v.y};
+        *reinterpret_cast<f32x2*>(sm + r * ldw + c + 2) = f32x2{v.z, v.w};
+    }
+    __syncthreads();
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, l31 = lane & 31, half = lane >> 5;
+    const int ch = wave & 1, kh = wave >> 1;
+    const int n0 = chunk * 64 + ch * 32;                   // first of this wave's 32 columns, within the group
+    const bool live = n0 < gw;                             // wave-uniform (gw = 16 / 32 leave the second column half empty)
+    const int n = min(n0 + l31, gw - 1);                   // columns past gw (gw % 32 == 16) load the last one and store nothing
+    const int upt = gw / 16, nu = k * upt;                 // 16-k units: per tap, in all
+    const int ua = kh ? (nu + 1) / 2 : 0, ub = kh ? nu : (nu + 1) / 2;
+    // two levels of sums: the MFMA chains run over 16 units (256 products), then join the wave's totals -- a single chain of K / 2 =
+    // 4096 fp32 additions measured 7.5x the rounding error of CPU fp32 GEMM at T = 1000
+    f32x16 acc0, acc1, tot0, tot1;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { acc0[r] = 0.f; acc1[r] = 0.f; tot0[r] = 0.f; tot1[r] = 0.f; }
+    if (live && ua < ub) {
+        // image of group g: [k gw / 4][gw][4]; unit u = quads 4u .. 4u + 3, 16 gw floats apart
+        const float* wp = w + (long)g * k * gw * gw + (long)n * 4 + 2 * half;
+        const long us = 16L * gw;
+        f32x2 b0[4], b1[4], b2[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            b0[q] = *reinterpret_cast<const f32x2*>(wp + ua * us + q * 4 * gw);
+            b1[q] = b2[q] = f32x2{0.f, 0.f};
+            if (ua + 1 < ub) b1[q] = *reinterpret_cast<const f32x2*>(wp + (ua + 1) * us + q * 4 * gw);
+            if (ua + 2 < ub) b2[q] = *reinterpret_cast<const f32x2*>(wp + (ua + 2) * us + q * 4 * gw);
+        }
+        int j = ua / upt, cu = ua - j * upt;
+        for (int u = ua; u < ub; ++u) {
+            const float* ap = sm + (l31 + j) * ldw + 16 * cu + 2 * half;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const f32x2 a0 = *reinterpret_cast<const f32x2*>(ap + 4 * q);
+                const f32x2 a1 = *reinterpret_cast<const f32x2*>(ap + 32 * ldw + 4 * q);
+                acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.x, b0[q].x, acc0, 0, 0, 0);
+                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.x, b0[q].x, acc1, 0, 0, 0);
+                acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.y, b0[q].y, acc0, 0, 0, 0);
+                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.y, b0[q].y, acc1, 0, 0, 0);
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {                  // three units of weights in flight
+                b0[q] = b1[q];
+                b1[q] = b2[q];
+                if (u + 3 < ub) b2[q] = *reinterpret_cast<const f32x2*>(wp + (u + 3) * us + q * 4 * gw);
+            }
+            if (++cu == upt) { cu = 0; ++j; }
+            if (((u - ua) & 15) == 15 || u + 1 == ub) {
+                tot0 += acc0;
+                tot1 += acc1;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) { acc0[r] = 0.f; acc1[r] = 0.f; }
+            }
+        }
+    }
+    __syncthreads();                                       // the window is dead: its memory takes the upper half's partial sums
+    float* red = sm + ch * 2048 + lane;                    // [column half][accumulator][register][lane]
+    if (kh == 1) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) { red[r * 64] = tot0[r]; red[1024 + r * 64] = tot1[r]; }
+    }
+    __syncthreads();
+    if (kh == 0 && n0 + l31 < gw) {
+        // accumulators: lane = column l31, registers = rows (r&3) + 8 (r>>2) + 4 half
+        const int col = g * gw + n0 + l31;
+        const float bv = bias[col];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int t = t0 + (r & 3) + 8 * (r >> 2) + 4 * half;
+            if (t < T) out[(long)t * E + col] = hid[(long)t * E + col] + gelu_erf((tot0[r] + red[r * 64]) + bv);
+            if (t + 32 < T)
+                out[(long)(t + 32) * E + col] = hid[(long)(t + 32) * E + col] + gelu_erf((tot1[r] + red[1024 + r * 64]) + bv);
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" int dawn_wave_normalize(const float* x, long n, double* stats2, float* out, void* stream) {
@@ -250,6 +354,24 @@ extern "C" int dawn_interp_linear(const float* y, long n, int C, const double* x
     if (n < 2) return dawn_set_error_msg(-83, "dawn_interp_linear: needs at least two samples");
     if (m <= 0) return 0;
     hipLaunchKernelGGL(interp_linear_kernel, dim3(dawn_cdiv(m * C, 256)), dim3(256), 0, (hipStream_t)stream, y, n, C, xi, m, out);
+    DAWN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int dawn_hubert_pos_conv(const float* hid, int T, int E, int groups, int k, const float* w, const float* bias, float* out,
+                                    void* stream) {
+    if (groups <= 0 || k <= 0 || E <= 0 || E % groups != 0 || (E / groups) % 16 != 0)
+        return dawn_set_error_msg(-84, "dawn_hubert_pos_conv: E = groups * gw with gw % 16 == 0, k >= 1");
+    if (T <= 0) return 0;
+    const int gw = E / groups;
+    const size_t lds = (size_t)(POS_BM + k - 1) * (gw + 2) * 4;
+    if (lds > 65536) return dawn_set_error_msg(-84, "dawn_hubert_pos_conv: (63 + k) * (gw + 2) floats must fit 64 KB of LDS");
+    if (!hid || !w || !bias || !out || (((uintptr_t)hid | (uintptr_t)w | (uintptr_t)out) & 15) != 0)
+        return dawn_set_error_msg(-84, "dawn_hubert_pos_conv: NULL or not 16-byte aligned pointer");
+    const float *he = hid + (long)T * E, *oe = out + (long)T * E;
+    if (out < he && hid < oe) return dawn_set_error_msg(-85, "dawn_hubert_pos_conv: out overlaps hid (neighbouring rows are read)");
+    hipLaunchKernelGGL(pos_conv_kernel, dim3(groups * ((gw + 63) / 64), dawn_cdiv(T, POS_BM)), dim3(256), lds < 16384 ? 16384 : lds,
+                       (hipStream_t)stream, hid, T, E, gw, k, w, bias, out);
     DAWN_LAUNCH_CHECK();
     return 0;
 }

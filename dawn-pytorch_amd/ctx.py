@@ -602,3 +602,131 @@ class DecoderEvaluator:
         else:
             check(self.L.dawn_decode_clip_conf(self.h, H, W, T, h, w, img.data_ptr(), skip_mem.data_ptr(), grid.data_ptr(),
                                                grid.stride(0), conf.data_ptr(), *tail), "dawn_decode_clip_conf")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# C-side HuBERT audio-feature stage (include/dawn_hip.h: dawn_hubert_*; csrc/dawn_hubert.hip)
+class HubertCfg(C.Structure):
+    """Mirror of ``dawn_hubert_cfg``."""
+    _fields_ = [("n_conv", C.c_int), ("conv_k", C.c_int * 8), ("conv_stride", C.c_int * 8), ("conv_dim", C.c_int), ("hidden", C.c_int),
+                ("heads", C.c_int), ("intermediate", C.c_int), ("n_layers", C.c_int), ("pos_k", C.c_int), ("pos_groups", C.c_int),
+                ("eps", C.c_float)]
+
+
+def hubert_cfg(hf) -> HubertCfg:
+    """hubert.HubertFeatures -> its ``dawn_hubert_cfg``."""
+    if len(hf.conv) > 8 or len({c["Cout"] for c in hf.conv}) != 1:
+        raise _lib.DawnHipError("dawn_hubert_cfg: at most 8 feature-extractor conv layers, all of one width")
+    if len({ly["I"] for ly in hf.layers}) > 1:
+        raise _lib.DawnHipError("dawn_hubert_cfg: every encoder layer must have the same intermediate width")
+    cfg = HubertCfg()
+    cfg.n_conv = len(hf.conv)
+    for i, (c, st) in enumerate(zip(hf.conv, hf.conv_stride)):
+        cfg.conv_k[i], cfg.conv_stride[i] = c["k"], st
+    cfg.conv_dim, cfg.hidden, cfg.heads = hf.conv[0]["Cout"], hf.E, hf.heads
+    cfg.intermediate = hf.layers[0]["I"] if hf.layers else 4
+    cfg.n_layers, cfg.pos_k, cfg.pos_groups, cfg.eps = len(hf.layers), hf.pos_k, hf.pos_groups, hf.eps
+    return cfg
+
+
+def hubert_named_weights(hf) -> Dict[str, Tensor]:
+    """hubert.HubertFeatures -> {name: device tensor} in the naming scheme of include/dawn_hip.h (HuBERT section)."""
+    out: Dict[str, Tensor] = {}
+    for i, c in enumerate(hf.conv):
+        out[f"conv.{i}.w"], out[f"conv.{i}.g"], out[f"conv.{i}.be"] = c["w"], c["g"], c["be"]
+        if c["b"] is not None:
+            out[f"conv.{i}.b"] = c["b"]
+    out.update({"fp.g": hf.fp_g, "fp.b": hf.fp_b, "fp.w": hf.fp_w, "fp.bias": hf.fp_bias, "pos.w": hf.pos_w_all, "pos.b": hf.pos_b,
+                "enc_ln.g": hf.enc_ln[0], "enc_ln.b": hf.enc_ln[1]})
+    for i, ly in enumerate(hf.layers):
+        p = f"layers.{i}."
+        out[p + "ln1.g"], out[p + "ln1.b"], out[p + "ln2.g"], out[p + "ln2.b"] = ly["ln1"][0], ly["ln1"][1], ly["ln2"][0], ly["ln2"][1]
+        for k in ("wqkv", "bqkv", "wo", "bo", "w1", "b1", "w2", "b2"):
+            out[p + k] = ly[k]
+    return out
+
+
+class HubertEvaluator:
+    """One `dawn_hubert` for one `HubertFeatures` on one device: what a non-Python host would call to turn 16 kHz samples into the
+    audio rows of `cond`.  PyTorch provides the device memory (packed weights, workspace, outputs) and the stream.  `weights` lets a
+    test hand in an edited table (a missing name must be an error)."""
+
+    MAX_SEGMENTS = 4096
+
+    def __init__(self, hf, weights: Optional[Dict[str, Tensor]] = None):
+        self.L = _lib.lib()
+        self.device = hf.fp_w.device
+        self.weights = hubert_named_weights(hf) if weights is None else dict(weights)      # keeps every tensor alive
+        self.cfg = hubert_cfg(hf)
+        arr = (NamedPtr * max(1, len(self.weights)))()
+        self._names = [k.encode() for k in self.weights]
+        for i, (k, t) in enumerate(self.weights.items()):
+            if not t.is_cuda or not t.is_contiguous() or t.dtype != torch.float32:
+                raise _lib.DawnHipError(f"packed weight {k} must be a contiguous fp32 GPU tensor")
+            arr[i].name, arr[i].ptr = self._names[i], t.data_ptr()
+        h = C.c_void_p()
+        check(self.L.dawn_hubert_create(C.addressof(self.cfg), C.addressof(arr), len(self.weights), C.addressof(h)), "dawn_hubert_create")
+        self.h = h
+        self._ws: Optional[Tensor] = None
+
+    def __del__(self):
+        h, self.h = getattr(self, "h", None), None
+        if h:
+            self.L.dawn_hubert_destroy(h)
+
+    @staticmethod
+    def _stream() -> int:
+        return torch.cuda.current_stream().cuda_stream
+
+    def conv_frames(self, n: int) -> int:
+        return int(self.L.dawn_hubert_conv_frames(self.h, n))
+
+    def segments(self, n: int):
+        """([(first sample, samples, rows)], expected_T, num_frames) of n samples."""
+        buf, eT, nf = (C.c_long * (3 * self.MAX_SEGMENTS))(), C.c_long(0), C.c_long(0)
+        ns = int(self.L.dawn_hubert_segments(self.h, n, buf, self.MAX_SEGMENTS, C.byref(eT), C.byref(nf)))
+        if ns < 0:
+            check(ns, "dawn_hubert_segments")
+        return [tuple(buf[3 * i:3 * i + 3]) for i in range(ns)], int(eT.value), int(nf.value)
+
+    def workspace_bytes(self, n: int) -> int:
+        return int(self.L.dawn_hubert_workspace_bytes(self.h, n))
+
+    def workspace(self, n: int) -> Tensor:
+        need = self.workspace_bytes(n)
+        if need == 0:
+            raise _lib.DawnHipError(f"dawn_hubert_workspace_bytes: {self.L.dawn_last_error().decode()}")
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = None
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self._ws
+
+    def _samples(self, x: Tensor, who: str) -> None:
+        if not (x.is_cuda and x.is_contiguous() and x.dtype == torch.float32 and x.dim() == 1):
+            raise _lib.DawnHipError(f"HubertEvaluator.{who}: samples must be a contiguous 1-D fp32 GPU tensor")
+
+    def encode(self, x: Tensor, workspace: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+        """x (n,) normalised samples of one segment -> last_hidden_state (T', E)."""
+        self._samples(x, "encode")
+        n = x.numel()
+        ws = workspace if workspace is not None else self.workspace(n)
+        if out is None:
+            out = torch.empty(self.conv_frames(n), self.cfg.hidden, device=self.device)
+        check(self.L.dawn_hubert_encode(self.h, x.data_ptr(), n, out.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()),
+              "dawn_hubert_encode")
+        return out
+
+    def features(self, speech: Tensor, workspace: Optional[Tensor] = None, hidden: Optional[Tensor] = None,
+                 target: Optional[Tensor] = None, want_hidden: bool = True):
+        """speech (n,) raw fp32 samples -> (hidden (expected_T, E) or None, target (num_frames, E)): all of process_audio."""
+        self._samples(speech, "features")
+        n = speech.numel()
+        _, eT, nf = self.segments(n)
+        ws = workspace if workspace is not None else self.workspace(n)
+        if hidden is None and want_hidden:
+            hidden = torch.empty(eT, self.cfg.hidden, device=self.device)
+        if target is None:
+            target = torch.empty(nf, self.cfg.hidden, device=self.device)
+        check(self.L.dawn_hubert_features(self.h, speech.data_ptr(), n, None if hidden is None else hidden.data_ptr(), target.data_ptr(),
+                                          ws.data_ptr(), ws.numel(), self._stream()), "dawn_hubert_features")
+        return hidden, target

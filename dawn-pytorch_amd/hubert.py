@@ -72,7 +72,9 @@ class HubertFeatures:
         gw = self.E // pos_groups
         if not (wpos.shape[1] == gw and gw % 16 == 0):
             raise ValueError("wpos.shape[1] == gw and gw % 16 == 0")
-        self.pos_w = [dev(pack_kn(wpos[g * gw:(g + 1) * gw].permute(2, 1, 0).reshape(-1, gw))) for g in range(pos_groups)]
+        # the per-group pack_kn images in one (groups, k * gw / 4, gw, 4) tensor (dawn_hubert_pos_conv); pos_w = its per-group views
+        self.pos_w_all = dev(torch.stack([pack_kn(wpos[g * gw:(g + 1) * gw].permute(2, 1, 0).reshape(-1, gw)) for g in range(pos_groups)]))
+        self.pos_w = [self.pos_w_all[g] for g in range(pos_groups)]
         self.pos_b = dev(sd[q + "bias"])
         # ---- encoder layers (stable layer norm: pre-LN)
         if "encoder.layer_norm.weight" not in sd:
@@ -95,6 +97,7 @@ class HubertFeatures:
                 "I": sd[p + "feed_forward.intermediate_dense.weight"].shape[0]})
             i += 1
         self.enc_ln = (dev(sd["encoder.layer_norm.weight"]), dev(sd["encoder.layer_norm.bias"]))
+        self._evaluator = None
 
     @classmethod
     def from_model(cls, model, device, ops=None) -> "HubertFeatures":
@@ -143,19 +146,31 @@ class HubertFeatures:
             hid = ops.conv_gemm(f, ly["w2"], E, F=1, Hi=1, Wi=T, bias=ly["b2"], res=hid)
         return self._ln(hid, self.enc_ln)
 
+    def evaluator(self):
+        """The C-side evaluator of this model (ctx.HubertEvaluator over dawn_hubert_*), created on first use."""
+        if self._evaluator is None:
+            from .ctx import HubertEvaluator
+            self._evaluator = HubertEvaluator(self)
+        return self._evaluator
+
+    def _speech_device(self, speech: np.ndarray) -> Tensor:
+        if speech.ndim == 2:
+            speech = speech[:, 0]                                        # [T, 2] ==> [T,]  (UVG:455-456)
+        return torch.from_numpy(np.ascontiguousarray(speech, dtype=np.float32)).to(self.device)
+
     # ------------------------------------------------------------------ reference call surface
     def normalize(self, speech: np.ndarray) -> Tensor:
         """`Wav2Vec2FeatureExtractor(speech, sampling_rate=16000).input_values` (do_normalize=True): float32 waveform,
         zero mean / unit variance over the utterance."""
-        if speech.ndim == 2:
-            speech = speech[:, 0]                                        # [T, 2] ==> [T,]  (UVG:455-456)
-        x = torch.from_numpy(np.ascontiguousarray(speech, dtype=np.float32)).to(self.device)
-        return self.ops.wave_normalize(x)
+        return self.ops.wave_normalize(self._speech_device(speech))
 
     @torch.no_grad()
-    def get_hubert_from_16k_speech(self, speech: np.ndarray) -> Tensor:
+    def get_hubert_from_16k_speech(self, speech: np.ndarray, via_c: bool = False) -> Tensor:
         """`VideoGenerator._get_hubert_from_16k_speech` (UVG:433-501): 320000-sample segments (+ 80 samples of right
-        context), the last one if it holds at least one kernel; concatenated, then padded / cut to the expected length."""
+        context), the last one if it holds at least one kernel; concatenated, then padded / cut to the expected length.
+        via_c: the same through dawn_hubert_features (segments encoded straight to their rows, one-launch positional conv)."""
+        if via_c:
+            return self.evaluator().features(self._speech_device(speech))[0]
         iv = self.normalize(speech)
         kernel, stride = 400, 320
         clip_length = stride * 1000
@@ -186,7 +201,10 @@ class HubertFeatures:
         xi = torch.from_numpy(np.linspace(0, hidden.shape[0] - 1, num_frames)).to(self.device)
         return self.ops.interp_linear(hidden.contiguous(), xi)
 
-    def process_audio(self, speech_16k: np.ndarray) -> np.ndarray:
-        """speech (16 kHz, as `soundfile.read` returns it) -> the `target_audio.npy` array (num_frames, E) float32."""
+    def process_audio(self, speech_16k: np.ndarray, via_c: bool = False) -> np.ndarray:
+        """speech (16 kHz, as `soundfile.read` returns it) -> the `target_audio.npy` array (num_frames, E) float32.
+        via_c: the whole stage as the one dawn_hubert_features call a C host makes (ctx.HubertEvaluator)."""
+        if via_c:
+            return self.evaluator().features(self._speech_device(speech_16k), want_hidden=False)[1].cpu().numpy()
         hid = self.get_hubert_from_16k_speech(speech_16k)
         return self.interpolate_25fps(hid, speech_16k.shape[0]).cpu().numpy()

@@ -859,6 +859,20 @@ class HipOps:
         check(self.L.dawn_add_act(_p(a), _p(b), act, b.numel(), _p(out), self._stream()), "dawn_add_act")
         return out
 
+    def hubert_pos_conv(self, hid: Tensor, w: Tensor, bias: Tensor, groups: int, k: int, out: Optional[Tensor] = None) -> Tensor:
+        """hid + gelu(grouped Conv1d(E, E, k, padding = k // 2, groups)(hid)[:T] + bias) in one launch: hid (T, E), w the per-group
+        pack_kn images stacked, contiguous (groups, k * gw / 4, gw, 4), gw = E // groups.  `out` may not overlap hid."""
+        T, E = hid.shape
+        gw = E // groups
+        _need(hid.is_contiguous() and w.is_contiguous() and bias.is_contiguous() and gw * groups == E
+              and w.numel() == groups * k * gw * gw and bias.numel() == E,
+              "hubert_pos_conv: hid (T, E), w (groups, k * gw / 4, gw, 4) and bias (E) contiguous, gw = E // groups")
+        self._require(hid, w, bias, out)
+        out = torch.empty_like(hid) if out is None else out
+        _need(out.is_contiguous() and out.shape == hid.shape and out.dtype == hid.dtype, "hubert_pos_conv: out like hid, contiguous")
+        check(self.L.dawn_hubert_pos_conv(_p(hid), T, E, groups, k, _p(w), _p(bias), _p(out), self._stream()), "dawn_hubert_pos_conv")
+        return out
+
     def attn64(self, qkv: Tensor, heads: int) -> Tensor:
         """qkv (T, 3*heads*64) = [q | k | v] -> softmax(q k^T / 8) v per head, (T, heads*64)."""
         T = qkv.shape[0]

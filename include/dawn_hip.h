@@ -424,7 +424,8 @@ int dawn_final_conv_blend_yuv420(const float* x, int T, int H, int W, int C, con
 
 /* ---- HuBERT audio features + 25 fps interpolation (UVG:202-250, 433-501; transformers.HubertModel with
  * feat_extract_norm = "layer", do_stable_layer_norm = True = hubert-large-ls960-ft).  Activations are (time, channels)
- * rows; the conv layers 1..6, the grouped positional conv and every Linear run through dawn_conv_gemm. */
+ * rows; the conv layers 1..6 and every Linear run through dawn_conv_gemm, the grouped positional conv through dawn_conv_gemm (one launch
+ * per group on a zero-padded copy: the Python default) or dawn_hubert_pos_conv (one launch: the C-side stage further down). */
 /* Wav2Vec2FeatureExtractor(do_normalize): out = (x - mean) / sqrt(var + 1e-7) over the utterance; stats2 = 2 doubles scratch */
 int dawn_wave_normalize(const float* x, long n, double* stats2, float* out, void* stream);
 /* conv_layers[0]: Conv1d(1, C, k, stride) (+ bias) of the waveform -> ((n - k) / stride + 1, C); w (C, k) */
@@ -439,6 +440,16 @@ int dawn_add_act(const float* a, const float* b, int act, long n, float* out, vo
 int dawn_attn64(const float* qkv, int T, int heads, float* out, void* stream);
 /* scipy interp1d(arange(n), y (n, C) fp32, kind="linear", axis=0)(xi) -> out (m, C) fp32; xi (m) doubles on the device */
 int dawn_interp_linear(const float* y, long n, int C, const double* xi, long m, float* out, void* stream);
+/* HubertPositionalConvEmbedding + the residual add that follows it, in one launch (grouped Conv1d(E, E, k, padding = k / 2, groups),
+ * SamePad drop for even k, exact GELU, hidden + that):
+ *   out[t][g gw + n] = hid[t][g gw + n] + gelu(bias[g gw + n] + sum_{j < k} sum_{c < gw} w[g][j][c][n] hid[t + j - k/2][g gw + c])
+ * for t in [0, T); rows outside [0, T) read as zero; gw = E / groups, gw % 16 == 0, (63 + k) * (gw + 2) floats within 64 KB of LDS.
+ * w = the per-group pack_kn images one after the other, contiguous as [groups][k gw / 4][gw][4]: element [g][q][n][e] is the weight of
+ * input channel c = (4q + e) % gw at tap j = (4q + e) / gw (k index = tap * gw + c) for output channel n of group g.  hid, out (T, E)
+ * dense, 16-byte aligned.  Exact fp32 on the matrix pipe; the sum order is fixed (no atomics): bit-identical run to run.  out may not
+ * overlap hid (neighbouring rows are read): error, nothing launched. */
+int dawn_hubert_pos_conv(const float* hid, int T, int E, int groups, int k, const float* w, const float* bias, float* out,
+                         void* stream);
 
 /* ---- PBnet pose / blink decoder (PBnet/src/models/architectures/transformerdecoder5.py:40-98, 120-166).
  * Attention core for heads of 32: out[i][h] = softmax_j(scale * rot(q_i,h) . rot(k_j,h) + bias[h][i][j]) v_j,h -- q / k / v rows with
@@ -668,6 +679,58 @@ int dawn_decode_clip_yuv420(dawn_decoder* dec, int H, int W, int T, int h, int w
 int dawn_decode_clip_conf_yuv420(dawn_decoder* dec, int H, int W, int T, int h, int w, const float* img3, const void* skip_mem,
                                  const float* grid, long grid_plane, const float* conf, int chunk, unsigned char* frames_yuv420,
                                  const double* mean3, void* workspace, size_t workspace_bytes, void* stream);
+/* ---- SURVEY 8(f) N3 as a whole path: the HuBERT audio-feature stage from raw 16 kHz samples to the 25 fps feature rows of `cond`
+ * (csrc/dawn_hubert.hip).  The launch sequence of dawn-pytorch_amd/hubert.py (HubertFeatures.encode / get_hubert_from_16k_speech /
+ * interpolate_25fps = VideoGenerator.process_audio, UVG:202-250, 433-501) through the per-op entries of this library, with the
+ * positional block as the one dawn_hubert_pos_conv launch.  Same contract as dawn_decoder: opaque handle, device pointers by name,
+ * caller-owned workspace, every launch on `stream`, no allocation, no synchronisation; an error return comes with a dawn_last_error
+ * message and nothing launched.  The handle is immutable after creation (the size queries are pure functions).
+ * Weight names = the fields HubertFeatures.__init__ builds (i = layer index; every matrix a pack_kn image):
+ *   "conv.0.w" (conv_dim, conv_k[0])   "conv.i.w" [conv_k[i] conv_dim / 4][conv_dim][4] (i >= 1)   "conv.i.b" (optional: conv_bias)
+ *   "conv.i.g" "conv.i.be"                                      feature-extractor conv i and the LayerNorm after it
+ *   "fp.g" "fp.b" (conv_dim)   "fp.w" [conv_dim / 4][hidden][4]   "fp.bias"                       feature projection
+ *   "pos.w" [pos_groups][pos_k gw / 4][gw][4]   "pos.b" (hidden)                                  positional conv (weight norm folded)
+ *   "layers.i.ln1.g" "layers.i.ln1.b" "layers.i.wqkv" [hidden / 4][3 hidden][4] "layers.i.bqkv" "layers.i.wo" "layers.i.bo"
+ *   "layers.i.ln2.g" "layers.i.ln2.b" "layers.i.w1" "layers.i.b1" (intermediate) "layers.i.w2" "layers.i.b2"   encoder layer i (pre-LN)
+ *   "enc_ln.g" "enc_ln.b"                                                                         final LayerNorm */
+typedef struct dawn_hubert dawn_hubert;
+typedef struct dawn_hubert_cfg {
+    int n_conv;                          /* feature-extractor conv layers (7), at most 8 */
+    int conv_k[8], conv_stride[8];       /* (10,3,3,3,3,2,2) / (5,2,2,2,2,2,2) */
+    int conv_dim;                        /* their width (512), a multiple of 4 */
+    int hidden;                          /* E (1024) = 64 * heads */
+    int heads;                           /* 16 */
+    int intermediate;                    /* FFN width (4096) */
+    int n_layers;                        /* encoder layers (24) */
+    int pos_k, pos_groups;               /* positional conv: taps (128), groups (16); gw = hidden / pos_groups, gw % 16 == 0 */
+    float eps;                           /* layer_norm_eps (1e-5) */
+} dawn_hubert_cfg;
+/* a missing name, hidden != 64 * heads, gw % 16 != 0 or any other unusable size: error return with a message, *out untouched */
+int dawn_hubert_create(const dawn_hubert_cfg* cfg, const dawn_named_ptr* weights, int n_weights, dawn_hubert** out);
+void dawn_hubert_destroy(dawn_hubert* hub);
+/* rows the conv stack makes of n_samples samples (host code; 0 when they are fewer than the stack needs) */
+long dawn_hubert_conv_frames(const dawn_hubert* hub, long n_samples);
+/* the segment plan of UVG:466-501 + 229-236 (host code): segments of 320000 samples plus 80 of right context, clamped to n_samples, the
+ * last one if it holds at least 400.  Returns the number of segments (> 0) and writes three numbers per segment -- first sample, samples,
+ * rows it encodes to (segment s starts at the sum of the rows before it) -- plus expected_T = (n_samples - 80) / 320 and
+ * num_frames = (long)((double)n_samples / 16000.0 * 25.0) (either pointer may be NULL).  Returns a negative error code with a message
+ * for n_samples < 400, more than max_segments segments, or a row total that differs from expected_T by more than one. */
+int dawn_hubert_segments(const dawn_hubert* hub, long n_samples, long* start_len_rows, int max_segments, long* expected_T,
+                         long* num_frames);
+/* bytes of the workspace that covers dawn_hubert_features of n_samples samples and dawn_hubert_encode of min(n_samples, 320080) */
+size_t dawn_hubert_workspace_bytes(const dawn_hubert* hub, long n_samples);
+/* HubertModel.forward on one segment: input_values = n normalised samples (n <= 320080: one segment of the plan above) ->
+ * last_hidden_state, hidden_out (dawn_hubert_conv_frames(n), hidden) */
+int dawn_hubert_encode(dawn_hubert* hub, const float* input_values, long n, float* hidden_out, void* workspace,
+                       size_t workspace_bytes, void* stream);
+/* all of process_audio: speech = n raw fp32 samples on the device -> dawn_wave_normalize -> every segment of the plan encoded straight to
+ * its row offset of the hidden block (no concatenation; a surplus row is not computed, a missing one is a zero row) ->
+ * dawn_interp_linear at numpy's linspace(0, expected_T - 1, num_frames) (filled on the device: xi[i] = (double)i * step,
+ * step = (double)(expected_T - 1) / (num_frames - 1), the last entry expected_T - 1 exactly; num_frames == 1: xi = {0}).
+ * hidden_out optional (expected_T, hidden): NULL keeps the block in the workspace; features_out (num_frames, hidden) = the audio rows
+ * of `cond`.  n < 400, num_frames == 0, expected_T < 2, a short workspace: error return with a message, nothing launched. */
+int dawn_hubert_features(dawn_hubert* hub, const float* speech, long n, float* hidden_out, float* features_out, void* workspace,
+                         size_t workspace_bytes, void* stream);
 /* after a stream synchronise: (kind, algorithmic flops, algorithmic bytes, ms) per conv launch recorded under
  * DAWN_OPT_PROFILE; kind 0 = split 3x3, 1 = split 1x1, 2 = fp32 MFMA; returns the number of entries (and clears them) */
 int dawn_ctx_profile_read(dawn_ctx* ctx, double* out4, int max_entries);
