@@ -101,6 +101,7 @@ SIGNATURES = {
     "dawn_select_finalize": [c_f, c_f, _f, c_f, c_f],
     "dawn_select_ws_reset": [c_f, c_f],
     "dawn_attn_bias32": [c_f, _i, c_f, _i, c_f, _i, _i, _i, _i, c_f, c_f, c_f, _i, _f, c_f, _i, c_f],
+    "dawn_attn_win32": [c_f, _i, c_f, _i, c_f, _i, _i, _i, _i, _i, c_f, c_f, c_f, _i, _f, c_f, _i, c_f],
     "dawn_ubench_mfma_bf16": [_i, _i, c_f, c_f, C.POINTER(C.c_float), c_f],
     "dawn_ddim_update": [c_f, c_f, c_f, c_f, _f, _f, _f, _l, c_f, c_f],
     "dawn_cfg_combine": [c_f, c_f, _f, _l, c_f, c_f],
@@ -155,6 +156,14 @@ SIGNATURES = {
     "dawn_hubert_workspace_bytes": [c_f, _l],
     "dawn_hubert_encode": [c_f, c_f, _l, c_f, c_f, C.c_size_t, c_f],
     "dawn_hubert_features": [c_f, c_f, _l, c_f, c_f, c_f, C.c_size_t, c_f],
+    # whole-path PBnet pose / blink stage (csrc/dawn_pbnet.hip; handles, the cfg struct and the named-pointer table travel as void*: ctx.py)
+    "dawn_pbnet_create": [c_f, c_f, _i, c_f],
+    "dawn_pbnet_destroy": [c_f],
+    "dawn_pbnet_workspace_bytes": [c_f, _l],
+    "dawn_pbnet_generate": [c_f, c_f, c_f, _i, c_f, _l, c_f, _i, c_f, C.c_size_t, c_f],
+    "dawn_pose_blink_workspace_bytes": [c_f, c_f, _l],
+    "dawn_pose_blink_stage": [c_f, c_f, c_f, _i, _l, C.POINTER(C.c_float), C.POINTER(C.c_float), c_f, c_f, c_f, _i, c_f, _i, c_f,
+                              C.c_size_t, c_f],
 }
 # device helpers of the C-side evaluator (csrc/dawn_ctx.hip calls them; from Python only the op tests do)
 CTX_HELPER_SIGNATURES = {
@@ -170,7 +179,8 @@ class DawnHipError(RuntimeError):
 
 
 LONG_RESULT = {"dawn_sla_ws_floats", "dawn_workspace_bytes_guided", "dawn_decoder_skip_bytes", "dawn_decoder_workspace_bytes",
-               "dawn_hubert_conv_frames", "dawn_hubert_workspace_bytes"}       # entry points that return a size (long), not a status
+               "dawn_hubert_conv_frames", "dawn_hubert_workspace_bytes", "dawn_pbnet_workspace_bytes",
+               "dawn_pose_blink_workspace_bytes"}       # entry points that return a size (long), not a status
 
 
 def lib() -> C.CDLL:

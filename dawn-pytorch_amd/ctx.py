@@ -730,3 +730,156 @@ class HubertEvaluator:
         check(self.L.dawn_hubert_features(self.h, speech.data_ptr(), n, None if hidden is None else hidden.data_ptr(), target.data_ptr(),
                                           ws.data_ptr(), ws.numel(), self._stream()), "dawn_hubert_features")
         return hidden, target
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# C-side PBnet pose / blink stage (include/dawn_hip.h: dawn_pbnet_*, dawn_pose_blink_stage; csrc/dawn_pbnet.hip)
+class PbnetCfg(C.Structure):
+    """Mirror of ``dawn_pbnet_cfg``."""
+    _fields_ = [("in_dim", C.c_int), ("audio_dim", C.c_int), ("latent_dim", C.c_int), ("d", C.c_int), ("heads", C.c_int), ("ff", C.c_int),
+                ("n_layers", C.c_int), ("win", C.c_int), ("nrot", C.c_int), ("eps", C.c_float)]
+
+
+_PB_FREQS = "init_temporal_attn.fn.fn.rotary_emb.freqs"
+
+
+def pbnet_cfg(gen) -> PbnetCfg:
+    """pbnet.PoseBlinkGenerator -> its ``dawn_pbnet_cfg``."""
+    w = gen.w
+    if w["audioEmbedding.weight"].shape[0] != gen.latent_dim:
+        raise _lib.DawnHipError("dawn_pbnet_cfg: 'audioEmbedding.weight' must be as wide as the latent (ztimelinear reads d + 2 * latent_dim)")
+    ffs = {w[f"seqTransDecoder.decoder_layers.{i}.ffn.linear1.weight"].shape[0] for i in range(gen.n_layers)}
+    if len(ffs) > 1:
+        raise _lib.DawnHipError("dawn_pbnet_cfg: every decoder layer must have the same FFN width")
+    cfg = PbnetCfg()
+    cfg.in_dim, cfg.audio_dim, cfg.latent_dim, cfg.d, cfg.heads = gen.in_dim, gen.audio_dim, gen.latent_dim, gen.d, gen.heads
+    cfg.ff, cfg.n_layers, cfg.win, cfg.nrot, cfg.eps = (ffs.pop() if ffs else 4), gen.n_layers, gen.window, w[_PB_FREQS].numel(), 1e-5
+    return cfg
+
+
+def pbnet_named_weights(gen) -> Dict[str, Tensor]:
+    """pbnet.PoseBlinkGenerator -> {name: device tensor} in the naming scheme of include/dawn_hip.h (PBnet section): the decoder's own
+    state_dict keys plus the three tables built here -- the two O(window) bias tables and every layer's [to_k ; to_v] in one image.
+    Only pointers reach the C side, so the shapes it relies on are checked here, by name."""
+    w, d, hd, dev = gen.w, gen.d, gen.heads * 32, gen.device
+    layers = [f"seqTransDecoder.decoder_layers.{i}." for i in range(gen.n_layers)]
+    ff = w[layers[0] + "ffn.linear1.weight"].shape[0] if layers else 4
+    want = {"firstposeEmbedding.weight": (d, gen.in_dim), "firstposeEmbedding.bias": (d,),
+            "audioEmbedding.weight": (gen.latent_dim, gen.audio_dim), "audioEmbedding.bias": (gen.latent_dim,),
+            "ztimelinear.weight": (d, d + 2 * gen.latent_dim), "ztimelinear.bias": (d,), "init_proj.bias": (d,),
+            "init_temporal_attn.fn.norm.gamma": (d,), "init_temporal_attn.fn.norm.beta": (d,),
+            "init_temporal_attn.fn.fn.to_qkv.weight": (3 * hd, d), "init_temporal_attn.fn.fn.to_out.weight": (d, hd),
+            _PB_FREQS: (w[_PB_FREQS].numel(),), "finallayer.weight": (gen.in_dim, d), "finallayer.bias": (gen.in_dim,)}
+    for p in layers:
+        want.update({p + "self_attn.to_qkv.weight": (3 * hd, d), p + "self_attn.to_out.weight": (d, hd),
+                     p + "multihead_attn.to_q.weight": (hd, d), p + "multihead_attn.to_out.weight": (d, hd),
+                     p + "ffn.linear1.weight": (ff, d), p + "ffn.linear1.bias": (ff,), p + "ffn.linear2.weight": (d, ff),
+                     p + "ffn.linear2.bias": (d,)})
+        for n in (1, 2, 3):
+            want.update({p + f"layer_norm{n}.weight": (d,), p + f"layer_norm{n}.bias": (d,)})
+    out: Dict[str, Tensor] = {}
+    for k, shape in want.items():
+        if k not in w:
+            raise _lib.DawnHipError(f"pbnet_named_weights: the decoder lacks '{k}'")
+        if tuple(w[k].shape) != shape:
+            raise _lib.DawnHipError(f"pbnet_named_weights: '{k}' is {tuple(w[k].shape)}, {shape} expected (heads of 32, d = {d})")
+        out[k] = w[k]
+    kv = []
+    for p in layers:
+        for n in ("multihead_attn.to_k.weight", "multihead_attn.to_v.weight"):
+            if p + n not in w or tuple(w[p + n].shape) != (hd, d):
+                raise _lib.DawnHipError(f"pbnet_named_weights: '{p + n}' missing or not {(hd, d)}")
+            kv.append(w[p + n])
+    if kv:
+        out["mem_kv.w"] = torch.cat(kv, 0).contiguous()
+    out["bias_tgt.rel"] = gen.rel_bias("tgt").to(dev)
+    out["bias_mem.rel"] = gen.rel_bias("mem").to(dev)
+    return out
+
+
+class PbnetEvaluator:
+    """One `dawn_pbnet` for one `PoseBlinkGenerator` on one device: what a non-Python host would call to produce the pose or blink
+    columns of `cond`.  PyTorch provides the device memory (weights, workspace, outputs) and the stream.  `weights` lets a test hand in
+    an edited table (a missing name must be an error)."""
+
+    def __init__(self, gen, weights: Optional[Dict[str, Tensor]] = None):
+        self.L = _lib.lib()
+        self.device = gen.device
+        self.weights = pbnet_named_weights(gen) if weights is None else dict(weights)      # keeps every tensor alive
+        self.cfg = pbnet_cfg(gen)
+        arr = (NamedPtr * max(1, len(self.weights)))()
+        self._names = [k.encode() for k in self.weights]
+        for i, (k, t) in enumerate(self.weights.items()):
+            if not t.is_cuda or not t.is_contiguous() or t.dtype != torch.float32:
+                raise _lib.DawnHipError(f"weight {k} must be a contiguous fp32 GPU tensor")
+            arr[i].name, arr[i].ptr = self._names[i], t.data_ptr()
+        h = C.c_void_p()
+        check(self.L.dawn_pbnet_create(C.addressof(self.cfg), C.addressof(arr), len(self.weights), C.addressof(h)), "dawn_pbnet_create")
+        self.h = h
+        self._ws: Optional[Tensor] = None
+
+    def __del__(self):
+        h, self.h = getattr(self, "h", None), None
+        if h:
+            self.L.dawn_pbnet_destroy(h)
+
+    @staticmethod
+    def _stream() -> int:
+        return torch.cuda.current_stream().cuda_stream
+
+    def workspace_bytes(self, T: int) -> int:
+        return int(self.L.dawn_pbnet_workspace_bytes(self.h, T))
+
+    def workspace(self, nbytes: int) -> Tensor:
+        if self._ws is None or self._ws.numel() < nbytes:
+            self._ws = None
+            self._ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=self.device)
+        return self._ws
+
+    def generate(self, x0: Tensor, audio: Tensor, z: Tensor, workspace: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+        """x0 (in_dim) first pose, audio (T, audio_dim) (rows may be strided), z (T, latent_dim) -> (T, in_dim): `_decode_one`.
+        `out`: a (T, in_dim) view with unit column stride (a column slice of a wider buffer is fine)."""
+        T = audio.shape[0]
+        for t, shape, name in ((x0, (self.cfg.in_dim,), "x0"), (audio, (T, self.cfg.audio_dim), "audio"), (z, (T, self.cfg.latent_dim), "z")):
+            if not (t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == shape and t.stride(-1) == 1):
+                raise _lib.DawnHipError(f"PbnetEvaluator.generate: {name} must be an fp32 GPU tensor of shape {shape}")
+        if not z.is_contiguous():
+            raise _lib.DawnHipError("PbnetEvaluator.generate: z must be contiguous")
+        ws = workspace if workspace is not None else self.workspace(self.workspace_bytes(T))
+        if out is None:
+            out = torch.empty(T, self.cfg.in_dim, device=self.device)
+        if not (out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (T, self.cfg.in_dim) and out.stride(1) == 1):
+            raise _lib.DawnHipError("PbnetEvaluator.generate: out must be an fp32 GPU (T, in_dim) view with unit column stride")
+        check(self.L.dawn_pbnet_generate(self.h, x0.data_ptr(), audio.data_ptr(), audio.stride(0) if T > 1 else self.cfg.audio_dim,
+                                         z.data_ptr(), T, out.data_ptr(), out.stride(0) if T > 1 else self.cfg.in_dim, ws.data_ptr(),
+                                         ws.numel(), self._stream()), "dawn_pbnet_generate")
+        return out
+
+
+def pose_blink_stage_c(ev_pose: PbnetEvaluator, ev_blink: PbnetEvaluator, audio: Tensor, init_pose6, init_blink2, z_pose: Tensor,
+                       z_blink: Tensor, dri_pose: Optional[Tensor] = None, dri_blink: Optional[Tensor] = None,
+                       workspace: Optional[Tensor] = None):
+    """dawn_pose_blink_stage: audio (T, audio_dim) and the latents (T, latent_dim) on the device, the two initial rows as host numbers
+    -> (dri_pose (T, 6), dri_blink (T, 2)) on the device; `dri_pose` / `dri_blink` may be column slices of wider buffers."""
+    L, T = ev_pose.L, audio.shape[0]
+    for t, w, name in ((audio, ev_pose.cfg.audio_dim, "audio"), (z_pose, ev_pose.cfg.latent_dim, "z_pose"),
+                       (z_blink, ev_blink.cfg.latent_dim, "z_blink")):
+        if not (t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == (T, w) and t.stride(1) == 1) or \
+                (name != "audio" and not t.is_contiguous()):
+            raise _lib.DawnHipError(f"pose_blink_stage_c: {name} must be an fp32 GPU tensor of shape {(T, w)}")
+    ip = (C.c_float * 6)(*[float(v) for v in init_pose6])
+    ib = (C.c_float * 2)(*[float(v) for v in init_blink2])
+    if dri_pose is None:
+        dri_pose = torch.empty(T, 6, device=audio.device)
+    if dri_blink is None:
+        dri_blink = torch.empty(T, 2, device=audio.device)
+    for t, w in ((dri_pose, 6), (dri_blink, 2)):
+        if not (t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == (T, w) and t.stride(1) == 1):
+            raise _lib.DawnHipError(f"pose_blink_stage_c: outputs must be fp32 GPU (T, {w}) views with unit column stride")
+    need = int(L.dawn_pose_blink_workspace_bytes(ev_pose.h, ev_blink.h, T))
+    ws = workspace if workspace is not None else ev_pose.workspace(need)
+    ld = lambda t, w: t.stride(0) if T > 1 else w                                             # noqa: E731
+    check(L.dawn_pose_blink_stage(ev_pose.h, ev_blink.h, audio.data_ptr(), ld(audio, ev_pose.cfg.audio_dim), T, ip, ib, z_pose.data_ptr(),
+                                  z_blink.data_ptr(), dri_pose.data_ptr(), ld(dri_pose, 6), dri_blink.data_ptr(), ld(dri_blink, 2),
+                                  ws.data_ptr(), ws.numel(), PbnetEvaluator._stream()), "dawn_pose_blink_stage")
+    return dri_pose, dri_blink

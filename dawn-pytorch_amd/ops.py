@@ -898,6 +898,25 @@ class HipOps:
                                       _p(rsin), nrot, float(scale), _p(out), heads * 32, self._stream()), "dawn_attn_bias32")
         return out
 
+    def attn_win32(self, q: Tensor, k: Tensor, v: Tensor, heads: int, win: int, bias_rel: Optional[Tensor], rcos: Optional[Tensor],
+                   rsin: Optional[Tensor], scale: float, out: Optional[Tensor] = None) -> Tensor:
+        """`attn_bias32` with the window as the key range: query i sees the keys |j - i| <= win, bias_rel (heads, 2*win + 1) holds the
+        additive bias of rel = j - i at [h][rel + win] (or None).  No operand grows with Tq * Tk."""
+        Tq, Tk = q.shape[0], k.shape[0]
+        for t in (q, k, v):
+            _need(t.stride(1) == 1 and t.shape[1] == heads * 32, "attn_win32: t.stride(1) == 1 and t.shape[1] == heads * 32")
+        self._require(q, k, v, bias_rel, rcos, rsin, out)
+        _need(bias_rel is None or (win >= 0 and bias_rel.is_contiguous() and tuple(bias_rel.shape) == (heads, 2 * win + 1)),
+              "attn_win32: bias_rel is None or (bias_rel.is_contiguous() and tuple(bias_rel.shape) == (heads, 2 * win + 1))")
+        nrot = 0 if rcos is None else rcos.shape[1]
+        _need(rcos is None or (rcos.is_contiguous() and rsin.is_contiguous() and rcos.shape[0] >= max(Tq, Tk)), "attn_win32: rcos is None or (rcos.is_contiguous() and rsin.is_contiguous() and rcos.shape[0] >= max(Tq, Tk))")
+        if out is None:
+            out = self.empty(Tq, heads * 32, like=q)
+        _need(out.stride(1) == 1 and tuple(out.shape) == (Tq, heads * 32), "attn_win32: out (Tq, heads * 32) with unit column stride")
+        check(self.L.dawn_attn_win32(_p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), Tq, Tk, heads, int(win), _p(bias_rel),
+                                     _p(rcos), _p(rsin), nrot, float(scale), _p(out), out.stride(0), self._stream()), "dawn_attn_win32")
+        return out
+
     def interp_linear(self, y: Tensor, xi: Tensor) -> Tensor:
         """scipy interp1d(arange(n), y, kind='linear', axis=0)(xi) as float32; xi float64 positions on the device."""
         _need(y.is_contiguous() and xi.dtype == torch.float64 and xi.is_contiguous(), "interp_linear: y.is_contiguous() and xi.dtype == torch.float64 and xi.is_contiguous()")

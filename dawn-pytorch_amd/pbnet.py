@@ -14,7 +14,11 @@ Architectures: the decoder families that exist in the reference, selected by `ar
 NotImplementedError.  `pose_blink_stage` is the arithmetic of `VideoGenerator.generate_pose_blink` (UVG:252-302).
 
 Every tensor op goes through `ops` (HipOps: dawn_linear, dawn_ln_affine_act, dawn_add_act, dawn_attn_bias32; the torch op set of
-oracle/ops_ref.py only in CPU tests).  Once per clip and ~0.1 GFLOP: a latency-bound stage, not a throughput path."""
+oracle/ops_ref.py only in CPU tests).  Once per clip and ~0.1 GFLOP: a latency-bound stage, not a throughput path.
+
+`via_c=True` (on `generate` and `pose_blink_stage`) hands the same work to the C-side stage (csrc/dawn_pbnet.hip through
+ctx.PbnetEvaluator: dawn_pbnet_generate / dawn_pose_blink_stage), which attends through dawn_attn_win32 and the O(window) table of
+`rel_bias`: no (heads, T, T) table is built, so it runs at any clip length.  The default path is unchanged."""
 from __future__ import annotations
 
 import math
@@ -81,6 +85,7 @@ class PoseBlinkGenerator:
         self.w["init_temporal_attn.fn.norm.beta"] = torch.zeros(self.d, device=dev)
         self.w["init_temporal_attn.fn.norm.gamma"] = self.w["init_temporal_attn.fn.norm.gamma"].reshape(-1).contiguous()
         self._tables: Dict[int, Tuple[Tensor, ...]] = {}
+        self._c_eval = None
 
     @classmethod
     def from_model(cls, model, archiname: Optional[str] = None, device=None, ops=None) -> "PoseBlinkGenerator":
@@ -108,6 +113,22 @@ class PoseBlinkGenerator:
                  ang.cos().contiguous().to(self.device), ang.sin().contiguous().to(self.device))
             self._tables[T] = t
         return t
+
+    def rel_bias(self, which: str) -> Tensor:
+        """The relative-position bias inside the eval-mode window, on the host: (heads, 2 * window + 1), the value for
+        rel = key - query at [h][rel + window].  `which`: "tgt" (self-attention) or "mem" (cross-attention).  Independent of T."""
+        if which not in ("tgt", "mem"):
+            raise ValueError(f"rel_bias: which = {which!r}, 'tgt' or 'mem' expected")
+        emb = self.w[f"time_rel_pos_bias_{which}.relative_attention_bias.weight"].cpu()
+        rel = torch.arange(-self.window, self.window + 1)
+        return emb[_rel_pos_bucket(rel, self.num_buckets, self.max_distance)].t().contiguous()
+
+    def c_evaluator(self):
+        """The C-side stage of this generator (ctx.PbnetEvaluator), created on first use."""
+        if self._c_eval is None:
+            from .ctx import PbnetEvaluator
+            self._c_eval = PbnetEvaluator(self)
+        return self._c_eval
 
     # ------------------------------------------------------------------ decoder blocks
     def _self_attn(self, p: str, x: Tensor, bias: Tensor, rc: Tensor, rs: Tensor) -> Tensor:
@@ -146,9 +167,9 @@ class PoseBlinkGenerator:
     # ------------------------------------------------------------------ CAE.generate
     @torch.no_grad()
     def generate(self, pose: Tensor, audio: Tensor, durations: Tensor, noise_same_action="random", noise_diff_action="random",
-                 fact=1, z: Optional[Tensor] = None) -> dict:
+                 fact=1, z: Optional[Tensor] = None, via_c: bool = False) -> dict:
         """cae.py:112-175.  pose (bs, >= 1, in_dim) first frame(s), audio (bs, T, audio_dim), durations (bs,).  `z` (T, bs, latent)
-        injects the latent that cae.py:133 draws with torch.randn."""
+        injects the latent that cae.py:133 draws with torch.randn.  via_c: every sample through dawn_pbnet_generate."""
         bs, T = len(audio), audio[0].shape[0]
         lengths = durations.reshape(-1).to(torch.long)
         if len(lengths) != bs or int(lengths.max()) != T:
@@ -161,7 +182,11 @@ class PoseBlinkGenerator:
         x, y = pose.to(self.device, torch.float32), audio.to(self.device, torch.float32)
         if x.shape[2] != self.in_dim or y.shape[2] != self.audio_dim:
             raise ValueError(f"pose / audio widths {x.shape[2]} / {y.shape[2]} != the checkpoint's {self.in_dim} / {self.audio_dim}")
-        out = torch.stack([self._decode_one(x[b, 0], (fact * z[:, b]).contiguous(), y[b]) for b in range(bs)], 0)
+        if via_c:
+            ev = self.c_evaluator()
+            out = torch.stack([ev.generate(x[b, 0].contiguous(), y[b].contiguous(), (fact * z[:, b]).contiguous()) for b in range(bs)], 0)
+        else:
+            out = torch.stack([self._decode_one(x[b, 0], (fact * z[:, b]).contiguous(), y[b]) for b in range(bs)], 0)
         out = out * mask[..., None].to(out.dtype)                                            # output[~mask] = 0 (:372)
         return {"x": x, "z": fact * z, "y": y, "mask": mask, "lengths": lengths.to(self.device), "output": out}
 
@@ -185,11 +210,23 @@ def load_pbnet(pose_ckpt: str, blink_ckpt: str, device=None, ops=None) -> Tuple[
 
 @torch.no_grad()
 def pose_blink_stage(gen_pose: PoseBlinkGenerator, gen_blink: PoseBlinkGenerator, audio: Tensor, init_pose: Tensor, init_blink: Tensor,
-                     z_pose: Optional[Tensor] = None, z_blink: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+                     z_pose: Optional[Tensor] = None, z_blink: Optional[Tensor] = None, via_c: bool = False) -> Tuple[Tensor, Tensor]:
     """`VideoGenerator.generate_pose_blink` UVG:252-302 between its file reads and writes: audio (T, 1024) interpolated HuBERT
     features, init_pose (1, >= 6) / init_blink (1, >= 2) rows of init_pose.npy / init_eye_bbox.npy -> (dri_pose (T, 6), dri_blink (T, 2))
-    on the CPU, as np.save expects them."""
+    on the CPU, as np.save expects them.  via_c: the whole stage is one dawn_pose_blink_stage call (the latents are drawn as the two
+    `generate` calls draw them: pose first)."""
     dev = gen_pose.device
+    if via_c:
+        from .ctx import pose_blink_stage_c
+        T = audio.shape[0]
+        zs = []
+        for gen, z in ((gen_pose, z_pose), (gen_blink, z_blink)):
+            if z is None:
+                z = torch.randn(T, 1, gen.latent_dim, device=gen.device)                      # cae.py:133
+            zs.append(z.to(dev, torch.float32).reshape(T, gen.latent_dim).contiguous())
+        pose, blink = pose_blink_stage_c(gen_pose.c_evaluator(), gen_blink.c_evaluator(), audio.to(dev, torch.float32).contiguous(),
+                                         init_pose[0, :6], init_blink[0, :2], zs[0], zs[1])
+        return pose.cpu(), blink.cpu()
     ip = init_pose[:, :6].unsqueeze(0).to(torch.float32)                                     # UVG:272
     ib = init_blink[:, :2].unsqueeze(0).to(torch.float32)                                    # UVG:273
     au = audio.unsqueeze(0).to(torch.float32)

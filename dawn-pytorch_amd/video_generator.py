@@ -50,7 +50,7 @@ class _LastOutput(dict):
 class VideoGenerator:
     def __init__(self, args, *, generator=None, frontend=None, config: Optional[dict] = None, device=None,
                  allow_random_weights: bool = False, deterministic: bool = True, hubert=None, pbnet=None,
-                 video_egress: str = "png", encoder_cmd=None):
+                 video_egress: str = "png", encoder_cmd=None, pbnet_via_c: bool = False):
         """`allow_random_weights`: explicit opt-in (benches, tests) to run with the deterministic random-init denoiser
         when the configured checkpoint is absent; without it a missing checkpoint raises, as the reference's
         `torch.load` does (UVG:527).  `deterministic`: seed the sampler's counter-based noise with the config's
@@ -61,12 +61,15 @@ class VideoGenerator:
         decoder writes planar YUV 4:2:0 frames, which stream into an encoder process's stdin chunk by chunk, and no PNG is written.
         `encoder_cmd` (yuv420p only): the encoder's argv (list, or a string split like a shell would), to which the output path
         `<output>/<name>/video/<name>.mp4` is appended; it reads raw I420 frames of the clip's size at 25 fps from stdin.  None: ffmpeg
-        when there is one on PATH, else the frames go to `<name>.y4m` in the same directory."""
+        when there is one on PATH, else the frames go to `<name>.y4m` in the same directory.
+        `pbnet_via_c`: stage 3 through the C-side stage (dawn_pose_blink_stage: windowed attention, any clip length) instead of the Python
+        orchestration of pbnet.py."""
         if video_egress not in ("png", "yuv420p"):
             raise ValueError(f"video_egress must be 'png' or 'yuv420p', not {video_egress!r}")
         self.video_egress = video_egress
         self.encoder_cmd = shlex.split(encoder_cmd) if isinstance(encoder_cmd, str) else (list(encoder_cmd) if encoder_cmd else None)
         self.hubert = hubert              # hubert.HubertFeatures: stage 2 (process_audio, UVG:202-250) on the GPU (SURVEY 8f N3)
+        self.pbnet_via_c = bool(pbnet_via_c)
         self.pbnet = pbnet                # (pose, blink) pbnet.PoseBlinkGenerator pair: stage 3 (generate_pose_blink, UVG:252-302; N4)
         self.allow_random_weights = bool(allow_random_weights) or bool(getattr(args, "allow_random_weights", False))
         self.deterministic = deterministic
@@ -143,7 +146,7 @@ class VideoGenerator:
             init_pose = torch.from_numpy(np.array([[0, 0, 0, 4.79e-04, 5.65e+01, 6.49e+01]]))
             init_blink = torch.from_numpy(np.array([[0.3, 0.3]]))
         audio = torch.from_numpy(np.load(self.audio_emb_path))
-        pose, blink = pose_blink_stage(self.pbnet[0], self.pbnet[1], audio, init_pose, init_blink)
+        pose, blink = pose_blink_stage(self.pbnet[0], self.pbnet[1], audio, init_pose, init_blink, via_c=self.pbnet_via_c)
         np.save(osp.join(self.cache_path, 'dri_pose.npy'), pose.numpy())
         np.save(osp.join(self.cache_path, 'dri_blink.npy'), blink.numpy())
 

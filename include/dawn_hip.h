@@ -459,6 +459,14 @@ int dawn_hubert_pos_conv(const float* hid, int T, int E, int groups, int k, cons
 int dawn_attn_bias32(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, int Tq, int Tk, int heads,
                      const float* bias, const float* rot_cos, const float* rot_sin, int nrot, float scale, float* out, int ld_out,
                      void* stream);
+/* The same attention with the eval-mode window as the key range instead of a -1e8 in the table: dawn_attn_bias32 with
+ * bias[h][i][j] = bias_rel[h][j - i + win] for |j - i| <= win, and the keys with |j - i| > win absent for query i (in the dense form their
+ * exp(-1e8 - max) is exactly 0 in fp32, so both compute the same function).  bias_rel (heads, 2*win + 1) or NULL.  O(Tq * win) time, no
+ * table that grows with T; per-query key order ascending.  win < 0, Tq > Tk + win (a query row without a key), or the stride / nrot
+ * conditions of dawn_attn_bias32: error return with a message, nothing launched. */
+int dawn_attn_win32(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, int Tq, int Tk, int heads, int win,
+                    const float* bias_rel, const float* rot_cos, const float* rot_sin, int nrot, float scale, float* out, int ld_out,
+                    void* stream);
 
 /* ---- whole-path entry points (C-side evaluator, csrc/dawn_ctx.hip) ----------------------------------
  * A host in any language runs the denoiser with these five calls (create, prepare, forward or sampler_run, destroy, plus the two
@@ -731,6 +739,60 @@ int dawn_hubert_encode(dawn_hubert* hub, const float* input_values, long n, floa
  * of `cond`.  n < 400, num_frames == 0, expected_T < 2, a short workspace: error return with a message, nothing launched. */
 int dawn_hubert_features(dawn_hubert* hub, const float* speech, long n, float* hidden_out, float* features_out, void* workspace,
                          size_t workspace_bytes, void* stream);
+/* ---- SURVEY 8(f) N4 as a whole path: the PBnet pose / blink stage (csrc/dawn_pbnet.hip).  The launch sequence of
+ * dawn-pytorch_amd/pbnet.py (PoseBlinkGenerator._decode_one = Decoder.forward for one sample with all frames valid; pose_blink_stage =
+ * UVG:252-302) through the per-op entries of this library, with dawn_attn_win32 as the attention: no table grows faster than T.  Same
+ * contract as dawn_hubert: opaque handle, device pointers by name, caller-owned workspace, every launch on `stream`, no allocation, no
+ * synchronisation; an error return comes with a dawn_last_error message and nothing launched.  The handle is immutable after creation.
+ * Weight names = the decoder's state_dict keys as PoseBlinkGenerator holds them (fp32, row-major (out, in), L = layer index):
+ *   "firstposeEmbedding.weight|bias" (d, in_dim)   "audioEmbedding.weight|bias" (latent_dim, audio_dim)
+ *   "ztimelinear.weight|bias" (d, d + 2 latent_dim)   "init_proj.bias" (d)   "finallayer.weight|bias" (in_dim, d)
+ *   "init_temporal_attn.fn.norm.gamma|beta" (d)   "init_temporal_attn.fn.fn.to_qkv.weight" (3 heads 32, d)   "...fn.fn.to_out.weight"
+ *   "init_temporal_attn.fn.fn.rotary_emb.freqs" (nrot; every module holds the same; not read when nrot = 0)
+ *   "seqTransDecoder.decoder_layers.L.<self_attn.to_qkv.weight|self_attn.to_out.weight|multihead_attn.to_q.weight|
+ *    multihead_attn.to_out.weight|ffn.linear1.weight|ffn.linear1.bias|ffn.linear2.weight|ffn.linear2.bias|layer_norm{1,2,3}.weight|bias>"
+ * and three tables built at pack time (ctx.pbnet_named_weights):
+ *   "bias_tgt.rel" "bias_mem.rel" (heads, 2 win + 1)  the relative-position bias of rel = key - query at [h][rel + win]
+ *   "mem_kv.w" (n_layers * 2 * heads 32, d)            [to_k ; to_v] of every layer's multihead_attn one after the other: the decoder
+ *                                                      memory is projected to all of them in one dawn_linear
+ * Only pointers travel, so the shapes are the caller's to guarantee (ctx.pbnet_named_weights checks them). */
+typedef struct dawn_pbnet dawn_pbnet;
+typedef struct dawn_pbnet_cfg {
+    int in_dim;                          /* pose 6 / blink 2 */
+    int audio_dim;                       /* 1024 */
+    int latent_dim;                      /* 256: width of z and of the audio embedding */
+    int d;                               /* model width (64) */
+    int heads;                           /* 4, of 32 */
+    int ff;                              /* FFN width (1024) */
+    int n_layers;                        /* decoder layers (4) */
+    int win;                             /* eval-mode attention window in frames: 100 (transformerreemb6) / 200 (transformerreemb5) */
+    int nrot;                            /* rotary pairs per head (2), at most 16 */
+    float eps;                           /* LayerNorm eps (1e-5) */
+} dawn_pbnet_cfg;
+/* a missing name (named in the message), nrot > 16, or a width that is not positive: error return with a message, *out untouched */
+int dawn_pbnet_create(const dawn_pbnet_cfg* cfg, const dawn_named_ptr* weights, int n_weights, dawn_pbnet** out);
+void dawn_pbnet_destroy(dawn_pbnet* pb);
+/* host code, exactly linear in T: a header of d floats rounded up to 256 bytes, then T rows each of (widths rounded up to 4 floats)
+ *   d + 2 latent_dim  ztimelinear input [x_ref | z | audio embedding]      d  decoder memory      n_layers * 2 * heads 32  all layers' K | V
+ *   3 x d  residual stream and two temporaries      3 heads 32  self-attention q | k | v      heads 32  cross-attention q
+ *   heads 32  attention output      ff  FFN hidden      2 x nrot  rotary cos / sin
+ * = 3,528 floats = 14,112 bytes per frame at the shipped widths.  0 for T < 1 or a NULL handle. */
+size_t dawn_pbnet_workspace_bytes(const dawn_pbnet* pb, long T);
+/* Decoder.forward for one sample: x0 (in_dim) first pose, audio (T, audio_dim) rows ld_audio apart, z (T, latent_dim) dense, all on the
+ * device -> out (T, in_dim) rows ld_out apart.  T < 1, a NULL pointer, ld_audio < audio_dim, ld_out < in_dim, a short workspace or `out`
+ * overlapping the workspace: error return with a message, nothing launched. */
+int dawn_pbnet_generate(dawn_pbnet* pb, const float* x0, const float* audio, int ld_audio, const float* z, long T, float* out, int ld_out,
+                        void* workspace, size_t workspace_bytes, void* stream);
+/* VideoGenerator.generate_pose_blink between its file reads and writes (UVG:252-302): init_pose6 / init_blink2 = the first 6 / 2 values
+ * of the rows of init_pose.npy / init_eye_bbox.npy in HOST memory; the pose row is min-max normalised with (-90, -90, -90, 0, 0, 0) /
+ * (90, 90, 90, 1, 720, 1080), both decoders run (pose: in_dim 6, blink: in_dim 2, latents z_pose / z_blink (T, latent_dim)), and
+ * dri_pose = (out + ip) * (max - min) + min (every operation rounded on its own), dri_blink = out + ib, written at the caller's strides
+ * ld_pose >= 6 / ld_blink >= 2 (other columns untouched).  Workspace: dawn_pose_blink_workspace_bytes = 256 bytes + the larger of the
+ * two decoders' workspaces.  Refusals as dawn_pbnet_generate. */
+size_t dawn_pose_blink_workspace_bytes(const dawn_pbnet* pose, const dawn_pbnet* blink, long T);
+int dawn_pose_blink_stage(dawn_pbnet* pose, dawn_pbnet* blink, const float* audio, int ld_audio, long T, const float* init_pose6,
+                          const float* init_blink2, const float* z_pose, const float* z_blink, float* dri_pose, int ld_pose,
+                          float* dri_blink, int ld_blink, void* workspace, size_t workspace_bytes, void* stream);
 /* after a stream synchronise: (kind, algorithmic flops, algorithmic bytes, ms) per conv launch recorded under
  * DAWN_OPT_PROFILE; kind 0 = split 3x3, 1 = split 1x1, 2 = fp32 MFMA; returns the number of entries (and clears them) */
 int dawn_ctx_profile_read(dawn_ctx* ctx, double* out4, int max_entries);
