@@ -170,6 +170,24 @@ CTX_HELPER_SIGNATURES = {
     "dawn_chw_to_hwc": [c_f, _i, _l, c_f, c_f],
     "dawn_rotary_tables": [c_f, _i, _i, c_f, c_f, c_f],
 }
+# whole-path UNet entries (csrc/dawn_ctx.hip; the handle, the cfg / step / dawn_shard_comm structs and the tables travel as void*: ctx.py)
+_fwd = [c_f, _i, _i, _i, c_f, c_f, _f, c_f, c_f, C.c_size_t]                               # ctx, F, h, w, clip, x3, t, eps, workspace, bytes
+_run = [c_f, _i, _i, _i, c_f, c_f, _i, c_f, C.c_uint64, c_f, c_f, c_f, c_f, C.c_size_t]   # .. clip, x_init, S, steps, seed, noises, x_out, thr, ..
+CTX_SIGNATURES = {
+    "dawn_ctx_create": [c_f, c_f, _i, c_f],
+    "dawn_ctx_destroy": [c_f],
+    "dawn_ctx_set_option": [c_f, _i, _i],
+    "dawn_clip_bytes": [c_f, _i, _i, _i],
+    "dawn_workspace_bytes": [c_f, _i, _i, _i],
+    "dawn_workspace_bytes_sharded": [c_f, _i, _i, _i, _i, _i],
+    "dawn_clip_prepare": [c_f, _i, _i, _i, c_f, c_f, _i, c_f, c_f, c_f, C.c_size_t, c_f, C.c_size_t, c_f],
+    "dawn_unet_forward": _fwd + [c_f],
+    "dawn_unet_forward_sharded": _fwd + [c_f, c_f],
+    "dawn_sampler_run": _run + [c_f],
+    "dawn_sampler_run_sharded": _run + [c_f, c_f],
+    "dawn_ctx_profile_read": [c_f, c_f, _i],
+    "dawn_rel_pos_bucket": [_i],
+}
 
 _lib = None
 
@@ -180,7 +198,8 @@ class DawnHipError(RuntimeError):
 
 LONG_RESULT = {"dawn_sla_ws_floats", "dawn_workspace_bytes_guided", "dawn_decoder_skip_bytes", "dawn_decoder_workspace_bytes",
                "dawn_hubert_conv_frames", "dawn_hubert_workspace_bytes", "dawn_pbnet_workspace_bytes",
-               "dawn_pose_blink_workspace_bytes"}       # entry points that return a size (long), not a status
+               "dawn_pose_blink_workspace_bytes", "dawn_clip_bytes", "dawn_workspace_bytes",
+               "dawn_workspace_bytes_sharded"}          # entry points that return a size (long), not a status
 
 
 def lib() -> C.CDLL:
@@ -194,7 +213,7 @@ def lib() -> C.CDLL:
         L = C.CDLL(str(LIB_PATH))
         L.dawn_last_error.restype = C.c_char_p
         L.dawn_abi_version.restype = _i
-        for name, args in {**SIGNATURES, **CTX_HELPER_SIGNATURES}.items():
+        for name, args in {**SIGNATURES, **CTX_HELPER_SIGNATURES, **CTX_SIGNATURES}.items():
             fn = getattr(L, name)
             fn.argtypes = args
             fn.restype = _l if name in LONG_RESULT else _i

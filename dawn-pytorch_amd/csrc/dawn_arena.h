@@ -1,4 +1,4 @@
-// Host-side sub-allocator shared by the C-side evaluators (dawn_ctx.hip, dawn_decoder.hip).
+// Host-side sub-allocator shared by the C-side stage hosts (dawn_ctx.hip, dawn_decoder.hip, dawn_hubert.hip, dawn_pbnet.hip).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>

@@ -11,15 +11,11 @@
 // (dawn_clip_bytes) and the activation workspace (dawn_workspace_bytes); every launch goes to the caller's stream plus
 // one internal side stream that is forked / joined with events (cross-attention || conv1 of each ResBlock); tuning
 // state lives in the ctx, never in globals; int return codes + dawn_last_error().
-#include "dawn_common.h"
-#include "dawn_arena.h"
-#include "../../include/dawn_hip.h"
+#include "dawn_host.h"
 
 #include <math.h>
 #include <string.h>
 #include <iterator>
-#include <map>
-#include <string>
 #include <vector>
 
 extern "C" int dawn_gemm1x1_split_ok(long M, int N, int C0, int C1);
@@ -27,11 +23,6 @@ extern "C" int dawn_gemm1x1_ln_inline_ok(long M, int N, int C0, int C1);
 
 namespace {
 
-#define CK(expr)                              \
-    do {                                      \
-        const int rc__ = (expr);              \
-        if (rc__ != 0) return rc__;           \
-    } while (0)
 #define HCK(expr)                                                     \
     do {                                                              \
         const hipError_t e__ = (expr);                                \
@@ -71,7 +62,6 @@ struct ProfEntry { hipEvent_t e0, e1; double flops, bytes; int kind; };
 struct dawn_ctx {
     dawn_unet_cfg cfg;
     int dims[10];
-    std::map<std::string, const void*> W;
     const float *w3, *wfea, *b_init, *sin_freqs, *t_w1, *t_b1, *t_w2, *t_b2, *film_w, *film_b, *wg, *bg, *wo, *bo;
     AT init_tattn;
     std::vector<Level> downs, ups;
@@ -98,23 +88,9 @@ struct dawn_ctx {
 
 namespace {
 
-const void* getw(const dawn_ctx* c, const std::string& k, bool required, bool* ok) {
-    auto it = c->W.find(k);
-    if (it == c->W.end() || it->second == nullptr) {
-        if (required) {
-            *ok = false;
-            std::string m = "dawn_ctx_create: missing packed weight '" + k + "'";
-            dawn_set_error_msg(-200, m.c_str());
-        }
-        return nullptr;
-    }
-    return it->second;
-}
-
-bool load_rb(dawn_ctx* c, const std::string& p, int Cin, int Co, bool conditioned, RB& rb, int& film_off) {
-    bool ok = true;
-    auto F = [&](const char* n, bool req = true) { return (const float*)getw(c, p + n, req, &ok); };
-    auto V = [&](const char* n) { return getw(c, p + n, false, &ok); };
+void load_rb(dawn_ctx* c, DawnWeights& Wt, const std::string& p, int Cin, int Co, bool conditioned, RB& rb, int& film_off) {
+    auto F = [&](const std::string& n) { return Wt.getf(p + n); };
+    auto V = [&](const std::string& n) { return Wt.opt(p + n); };
     rb.Cin = Cin; rb.Co = Co; rb.conditioned = conditioned;
     rb.w1 = F("w1"); rb.b1 = F("b1"); rb.g1 = F("g1"); rb.be1 = F("be1");
     rb.w2 = F("w2"); rb.b2 = F("b2"); rb.g2 = F("g2"); rb.be2 = F("be2");
@@ -127,28 +103,25 @@ bool load_rb(dawn_ctx* c, const std::string& p, int Cin, int Co, bool conditione
         rb.wq = F("wq"); rb.wqs = V("wqs"); rb.q_scale = F("q_scale"); rb.g3 = F("g3");
         for (int b = 0; b < 3; ++b) {
             const std::string s = std::to_string(b);
-            rb.wo[b] = F(("wo." + s).c_str());
-            rb.wos[b] = V(("wos." + s).c_str());
-            rb.mlp_w[b] = F(("mlp_w." + s).c_str());
-            rb.mlp_b[b] = F(("mlp_b." + s).c_str());
-            rb.kv_w[b] = F(("kv_w." + s).c_str());
-            rb.k_scale[b] = F(("k_scale." + s).c_str());
-            rb.null_kv[b] = F(("null_kv." + s).c_str());
+            rb.wo[b] = F("wo." + s);
+            rb.wos[b] = V("wos." + s);
+            rb.mlp_w[b] = F("mlp_w." + s);
+            rb.mlp_b[b] = F("mlp_b." + s);
+            rb.kv_w[b] = F("kv_w." + s);
+            rb.k_scale[b] = F("k_scale." + s);
+            rb.null_kv[b] = F("null_kv." + s);
         }
     }
-    return ok;
 }
 
-bool load_at(dawn_ctx* c, const std::string& p, int C, bool bias, AT& a) {
-    bool ok = true;
+void load_at(DawnWeights& Wt, const std::string& p, int C, bool bias, AT& a) {
     a.C = C;
-    a.wqkv = (const float*)getw(c, p + "wqkv", true, &ok);
-    a.wout = (const float*)getw(c, p + "wout", true, &ok);
-    if (bias) a.bout = (const float*)getw(c, p + "bout", true, &ok);
-    a.wqkv_s = getw(c, p + "wqkv_s", false, &ok);
-    a.wout_s = getw(c, p + "wout_s", false, &ok);
-    a.wout_sp = getw(c, p + "wout_sp", false, &ok);
-    return ok;
+    a.wqkv = Wt.getf(p + "wqkv");
+    a.wout = Wt.getf(p + "wout");
+    if (bias) a.bout = Wt.getf(p + "bout");
+    a.wqkv_s = Wt.opt(p + "wqkv_s");
+    a.wout_s = Wt.opt(p + "wout_s");
+    a.wout_sp = Wt.opt(p + "wout_sp");
 }
 
 // RelativePositionBias._relative_position_bucket (MT:92-109), rel = k_pos - q_pos, num_buckets 32, max_distance 32,
@@ -873,53 +846,50 @@ struct Eval {
     }
 };
 
-int build_levels(dawn_ctx* c) {
+void build_levels(dawn_ctx* c, DawnWeights& Wt) {
     const dawn_unet_cfg& g = c->cfg;
     int film_off = 0;
-    bool ok = true;
-    ok &= load_at(c, "init_tattn.", g.dim, false, c->init_tattn);
+    load_at(Wt, "init_tattn.", g.dim, false, c->init_tattn);
     c->downs.resize(g.n_levels);
     c->ups.resize(g.n_levels);
     for (int l = 0; l < g.n_levels; ++l) {
         const int din = c->dims[l], dout = c->dims[l + 1];
         const std::string p = "downs." + std::to_string(l) + ".";
         Level& lv = c->downs[l];
-        ok &= load_rb(c, p + "rb1.", din, dout, true, lv.rb1, film_off);
-        ok &= load_rb(c, p + "rb2.", dout, dout, true, lv.rb2, film_off);
-        ok &= load_at(c, p + "sla.", dout, true, lv.sla);
-        ok &= load_at(c, p + "tattn.", dout, false, lv.tattn);
+        load_rb(c, Wt, p + "rb1.", din, dout, true, lv.rb1, film_off);
+        load_rb(c, Wt, p + "rb2.", dout, dout, true, lv.rb2, film_off);
+        load_at(Wt, p + "sla.", dout, true, lv.sla);
+        load_at(Wt, p + "tattn.", dout, false, lv.tattn);
         if (l + 1 < g.n_levels) {
-            lv.rs_w = (const float*)getw(c, p + "down.w", true, &ok);
-            lv.rs_b = (const float*)getw(c, p + "down.b", true, &ok);
-            lv.rs_ws = getw(c, p + "down.ws", false, &ok);
+            lv.rs_w = Wt.getf(p + "down.w");
+            lv.rs_b = Wt.getf(p + "down.b");
+            lv.rs_ws = Wt.opt(p + "down.ws");
         }
     }
     const int dm = c->dims[g.n_levels];
-    ok &= load_rb(c, "mid.rb1.", dm, dm, true, c->mid1, film_off);
-    ok &= load_at(c, "mid.sattn.", dm, false, c->mid_sattn);
-    ok &= load_at(c, "mid.tattn.", dm, false, c->mid_tattn);
-    ok &= load_rb(c, "mid.rb2.", dm, dm, true, c->mid2, film_off);
+    load_rb(c, Wt, "mid.rb1.", dm, dm, true, c->mid1, film_off);
+    load_at(Wt, "mid.sattn.", dm, false, c->mid_sattn);
+    load_at(Wt, "mid.tattn.", dm, false, c->mid_tattn);
+    load_rb(c, Wt, "mid.rb2.", dm, dm, true, c->mid2, film_off);
     for (int l = 0; l < g.n_levels; ++l) {
         const int li = g.n_levels - 1 - l;                 // reversed(in_out) (MT:826)
         const int din = c->dims[li], dout = c->dims[li + 1];
         const std::string p = "ups." + std::to_string(l) + ".";
         Level& lv = c->ups[l];
-        ok &= load_rb(c, p + "rb1.", 2 * dout, din, true, lv.rb1, film_off);
-        ok &= load_rb(c, p + "rb2.", din, din, true, lv.rb2, film_off);
-        ok &= load_at(c, p + "sla.", din, true, lv.sla);
-        ok &= load_at(c, p + "tattn.", din, false, lv.tattn);
+        load_rb(c, Wt, p + "rb1.", 2 * dout, din, true, lv.rb1, film_off);
+        load_rb(c, Wt, p + "rb2.", din, din, true, lv.rb2, film_off);
+        load_at(Wt, p + "sla.", din, true, lv.sla);
+        load_at(Wt, p + "tattn.", din, false, lv.tattn);
         if (l + 1 < g.n_levels) {
-            lv.rs_w = (const float*)getw(c, p + "up.w", true, &ok);
-            lv.rs_b = (const float*)getw(c, p + "up.b", true, &ok);
-            lv.rs_ws = getw(c, p + "up.ws", false, &ok);
+            lv.rs_w = Wt.getf(p + "up.w");
+            lv.rs_b = Wt.getf(p + "up.b");
+            lv.rs_ws = Wt.opt(p + "up.ws");
         }
     }
     int dummy = 0;
-    ok &= load_rb(c, "head_g.", 2 * g.dim, g.dim, false, c->head_g, dummy);
-    ok &= load_rb(c, "head_o.", 2 * g.dim, g.dim, false, c->head_o, dummy);
+    load_rb(c, Wt, "head_g.", 2 * g.dim, g.dim, false, c->head_g, dummy);
+    load_rb(c, Wt, "head_o.", 2 * g.dim, g.dim, false, c->head_o, dummy);
     c->film_total = film_off;
-    if (!ok) return -200;
-    return 0;
 }
 
 // The heads' res_conv folded into the output projection (dawn_fold_heads: the one implementation, the Python packer calls it too), once
@@ -961,17 +931,16 @@ extern "C" int dawn_ctx_create(const dawn_unet_cfg* cfg, const dawn_named_ptr* w
     c->dims[0] = cfg->dim;
     for (int l = 0; l < cfg->n_levels; ++l) c->dims[l + 1] = cfg->dim * cfg->dim_mults[l];
     c->time_dim = 4 * cfg->dim;
-    for (int i = 0; i < n_weights; ++i)
-        if (weights[i].name) c->W[weights[i].name] = weights[i].ptr;
-    bool ok = true;
-    auto F = [&](const char* n) { return (const float*)getw(c, n, true, &ok); };
+    DawnWeights Wt(weights, n_weights, "dawn_ctx_create: missing packed weight", -200);
+    auto F = [&](const char* n) { return Wt.getf(n); };
     c->w3 = F("w3"); c->wfea = F("wfea"); c->b_init = F("b_init"); c->sin_freqs = F("sin_freqs");
     c->t_w1 = F("t_w1"); c->t_b1 = F("t_b1"); c->t_w2 = F("t_w2"); c->t_b2 = F("t_b2");
     c->film_w = F("film_w"); c->film_b = F("film_b");
     c->wg = F("wg"); c->bg = F("bg"); c->wo = F("wo"); c->bo = F("bo");
     const float* rel = F("rel_emb");
     c->rot_freqs_dev = F("rot_freqs");
-    int rc = ok ? build_levels(c) : -200;
+    build_levels(c, Wt);
+    int rc = Wt.ok() ? 0 : Wt.code();
     if (rc == 0) {
         hipError_t e = hipMemcpy(c->rel_emb, rel, sizeof(c->rel_emb), hipMemcpyDeviceToHost);
         if (e == hipSuccess) e = hipMemcpy(c->rot_freqs, c->rot_freqs_dev, sizeof(c->rot_freqs), hipMemcpyDeviceToHost);

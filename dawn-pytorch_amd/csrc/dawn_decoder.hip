@@ -8,22 +8,11 @@
 // sized by a dry pass of the same code), every launch on the caller's stream, no synchronisation, int return codes +
 // dawn_last_error().  Three copy / elementwise kernels live here: the bias rows of the first convolution, the (C,h,w) transpose of
 // `fea`, and the occlusion map (p + 1) * 0.5 of a latent chunk.
-#include "dawn_common.h"
-#include "dawn_arena.h"
-#include "../../include/dawn_hip.h"
+#include "dawn_host.h"
 
-#include <stdio.h>
-#include <map>
-#include <string>
 #include <vector>
 
 namespace {
-
-#define CK(expr)                              \
-    do {                                      \
-        const int rc__ = (expr);              \
-        if (rc__ != 0) return rc__;           \
-    } while (0)
 
 struct Conv3 {                    // flow_decoder._Conv: 3x3 conv (pack_kn image, optional pack_bf3 image, bias), BatchNorm that follows
     const float *w = nullptr, *bias = nullptr, *a = nullptr, *b = nullptr;
@@ -62,7 +51,6 @@ int grid_for(long total) {
 
 struct dawn_decoder {
     dawn_decoder_cfg cfg;
-    std::map<std::string, const void*> W;
     const float *first_w3 = nullptr, *first_bias = nullptr, *first_a = nullptr, *first_b = nullptr, *final_w7 = nullptr,
                 *final_bias = nullptr;
     std::vector<Conv3> downs, ups;
@@ -71,33 +59,17 @@ struct dawn_decoder {
 
 namespace {
 
-const void* getw(const dawn_decoder* d, const std::string& k, bool required, bool* ok) {
-    auto it = d->W.find(k);
-    if (it == d->W.end() || it->second == nullptr) {
-        if (required && *ok) {
-            *ok = false;
-            const std::string m = "dawn_decoder_create: missing packed weight '" + k + "'";
-            dawn_set_error_msg(-230, m.c_str());
-        }
-        return nullptr;
-    }
-    return it->second;
-}
-
-bool load_conv(const dawn_decoder* d, const std::string& p, int Cin, int N, bool norm, const std::string& np, Conv3& c) {
-    bool ok = true;
+// the conv under prefix p; norm: with the scale / shift of the BatchNorm that follows it
+void load_conv(DawnWeights& Wt, const std::string& p, int Cin, int N, bool norm, Conv3& c) {
     c.Cin = Cin; c.N = N;
-    c.w = (const float*)getw(d, p + "w", true, &ok);
-    c.bias = (const float*)getw(d, p + "bias", true, &ok);
-    c.ws = getw(d, p + "ws", false, &ok);
+    c.w = Wt.getf(p + "w");
+    c.bias = Wt.getf(p + "bias");
+    c.ws = Wt.opt(p + "ws");
     if (norm) {
-        c.a = (const float*)getw(d, np + "a", true, &ok);
-        c.b = (const float*)getw(d, np + "b", true, &ok);
+        c.a = Wt.getf(p + "a");
+        c.b = Wt.getf(p + "b");
     }
-    return ok;
 }
-
-size_t a256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 size_t skip_floats(const dawn_decoder* d, int lvl, int H, int W) { return (size_t)(H >> lvl) * (W >> lvl) * d->cfg.widths[lvl]; }
 
@@ -132,9 +104,7 @@ int conv3(const Conv3& c, const float* x, int F, int H, int W, const float* res,
     return dawn_conv_gemm(&d, stream);
 }
 
-#define ALLOC(ptr, floats)                                                                                  \
-    float* ptr = (float*)A.alloc((size_t)(floats) * 4);                                                     \
-    if (!ptr) return dawn_set_error_msg(-232, "dawn_decoder: workspace too small (dawn_decoder_workspace_bytes)")
+#define ALLOC(ptr, floats) DAWN_ALLOC(A, ptr, floats, -232, "dawn_decoder: workspace too small (dawn_decoder_workspace_bytes)")
 
 // FlowDecoder.encode (+ compute_fea's transpose).  dry: sizes the workspace, launches nothing.
 int encode(const dawn_decoder* d, DawnArena& A, int H, int W, const float* img3, void* skip_mem, float* fea_out, bool dry,
@@ -189,8 +159,8 @@ int decode_chunk(const dawn_decoder* d, DawnArena& A, int H, int W, int n, int t
     const int nd = d->cfg.n_down;
     float* cfbuf = nullptr;
     if (!cf) {
-        cfbuf = (float*)A.alloc((size_t)n * h * w * 4);
-        if (!cfbuf) return dawn_set_error_msg(-232, "dawn_decoder: workspace too small (dawn_decoder_workspace_bytes)");
+        ALLOC(buf, (size_t)n * h * w);
+        cfbuf = buf;
         if (!dry) {
             hipLaunchKernelGGL(conf_of_latent_kernel, dim3(grid_for((long)n * h * w)), dim3(256), 0, st, lat2, (long)n * h * w, cfbuf);
             DAWN_LAUNCH_CHECK();
@@ -284,10 +254,7 @@ int decode_clip(dawn_decoder* d, const char* who, int H, int W, int T, int h, in
         return dawn_set_error_msg(-237, m);
     }
     const size_t need = dawn_decoder_workspace_bytes(d, H, W, chunk < T ? chunk : (T > 0 ? T : 1));
-    if (workspace_bytes < need || !workspace) {
-        snprintf(m, sizeof m, "%s: workspace of %zu bytes, %zu needed (dawn_decoder_workspace_bytes)", who, workspace_bytes, need);
-        return dawn_set_error_msg(-232, m);
-    }
+    if (workspace_bytes < need || !workspace) return refuse_workspace(-232, who, workspace_bytes, need, "dawn_decoder_workspace_bytes");
     Outputs o = {out_vid, warped_vid, out_plane, frames_u8, {0.0, 0.0, 0.0}, bgr ? 1 : 0, frames_yuv};
     if (mean3) { o.m[0] = mean3[0]; o.m[1] = mean3[1]; o.m[2] = mean3[2]; }
     for (int t0 = 0; t0 < T; t0 += chunk) {
@@ -315,29 +282,28 @@ extern "C" int dawn_decoder_create(const dawn_decoder_cfg* cfg, const dawn_named
         }
     dawn_decoder* d = new dawn_decoder();
     d->cfg = *cfg;
-    for (int i = 0; i < n_weights; ++i)
-        if (weights[i].name) d->W[weights[i].name] = weights[i].ptr;
-    bool ok = true;
-    auto F = [&](const char* n) { return (const float*)getw(d, n, true, &ok); };
+    DawnWeights Wt(weights, n_weights, "dawn_decoder_create: missing packed weight", -230);
+    auto F = [&](const std::string& n) { return Wt.getf(n); };
     d->first_w3 = F("first_w3"); d->first_bias = F("first_bias"); d->first_a = F("first.a"); d->first_b = F("first.b");
     d->final_w7 = F("final_w7"); d->final_bias = F("final_bias");
     const int n = cfg->n_down;
     d->downs.resize(n); d->ups.resize(n); d->bott.resize(cfg->n_bottleneck);
-    for (int i = 0; i < n && ok; ++i) {
+    for (int i = 0; i < n; ++i) {
         const std::string s = std::to_string(i);
-        ok = load_conv(d, "downs." + s + ".", cfg->widths[i], cfg->widths[i + 1], true, "downs." + s + ".", d->downs[i]) &&
-             load_conv(d, "ups." + s + ".", cfg->widths[n - i], cfg->widths[n - i - 1], true, "ups." + s + ".", d->ups[i]);
+        load_conv(Wt, "downs." + s + ".", cfg->widths[i], cfg->widths[i + 1], true, d->downs[i]);
+        load_conv(Wt, "ups." + s + ".", cfg->widths[n - i], cfg->widths[n - i - 1], true, d->ups[i]);
     }
     const int Cb = cfg->widths[n];
-    for (int i = 0; i < cfg->n_bottleneck && ok; ++i) {
+    for (int i = 0; i < cfg->n_bottleneck; ++i) {
         const std::string p = "bott." + std::to_string(i) + ".";
         Bott& b = d->bott[i];
-        b.a1 = F((p + "a1").c_str()); b.b1 = F((p + "b1").c_str()); b.a2 = F((p + "a2").c_str()); b.b2 = F((p + "b2").c_str());
-        ok = ok && load_conv(d, p + "c1.", Cb, Cb, false, "", b.c1) && load_conv(d, p + "c2.", Cb, Cb, false, "", b.c2);
+        b.a1 = F(p + "a1"); b.b1 = F(p + "b1"); b.a2 = F(p + "a2"); b.b2 = F(p + "b2");
+        load_conv(Wt, p + "c1.", Cb, Cb, false, b.c1);
+        load_conv(Wt, p + "c2.", Cb, Cb, false, b.c2);
     }
-    if (!ok) {
+    if (!Wt.ok()) {
         delete d;
-        return -230;
+        return Wt.code();
     }
     *out = d;
     return 0;

@@ -8,22 +8,11 @@
 // Conventions as in dawn_decoder.hip: no allocation on the device (the caller provides the workspace, sized by a dry pass of the same
 // code), every launch on the caller's stream, no synchronisation, int return codes + dawn_last_error().  One kernel lives here: the
 // interpolation positions (numpy's linspace).
-#include "dawn_common.h"
-#include "dawn_arena.h"
-#include "../../include/dawn_hip.h"
+#include "dawn_host.h"
 
-#include <stdio.h>
-#include <map>
-#include <string>
 #include <vector>
 
 namespace {
-
-#define CK(expr)                              \
-    do {                                      \
-        const int rc__ = (expr);              \
-        if (rc__ != 0) return rc__;           \
-    } while (0)
 
 const long SEG = 320000, SEG_CTX = 80, KERNEL = 400, STRIDE = 320;     // UVG:466-470: clip_length, kernel - stride, kernel, stride
 
@@ -40,7 +29,6 @@ struct Layer { const float *ln1g, *ln1b, *wqkv, *bqkv, *wo, *bo, *ln2g, *ln2b, *
 
 struct dawn_hubert {
     dawn_hubert_cfg cfg;
-    std::map<std::string, const void*> W;
     std::vector<ConvL> conv;
     const float *fp_g = nullptr, *fp_b = nullptr, *fp_w = nullptr, *fp_bias = nullptr, *pos_w = nullptr, *pos_b = nullptr,
                 *enc_g = nullptr, *enc_b = nullptr;
@@ -48,21 +36,6 @@ struct dawn_hubert {
 };                                // immutable after dawn_hubert_create: every call sub-allocates its workspace with an arena of its own
 
 namespace {
-
-const float* getw(const dawn_hubert* h, const std::string& k, bool required, bool* ok) {
-    auto it = h->W.find(k);
-    if (it == h->W.end() || it->second == nullptr) {
-        if (required && *ok) {
-            *ok = false;
-            const std::string m = "dawn_hubert_create: missing packed weight '" + k + "'";
-            dawn_set_error_msg(-250, m.c_str());
-        }
-        return nullptr;
-    }
-    return (const float*)it->second;
-}
-
-size_t a256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // a Linear / 1-D conv over (time, channel) rows through dawn_conv_gemm, as HipOps.conv_gemm fills the descriptor
 int gemm(const float* x, int Cin, long Ti, long To, int KW, int stride, const float* w, const float* bias, int N, const float* res,
@@ -77,9 +50,7 @@ int gemm(const float* x, int Cin, long Ti, long To, int KW, int stride, const fl
     return dawn_conv_gemm(&d, stream);
 }
 
-#define ALLOC(ptr, floats)                                                                                  \
-    float* ptr = (float*)A.alloc((size_t)(floats) * 4);                                                     \
-    if (!ptr) return dawn_set_error_msg(-252, "dawn_hubert: workspace too small (dawn_hubert_workspace_bytes)")
+#define ALLOC(ptr, floats) DAWN_ALLOC(A, ptr, floats, -252, "dawn_hubert: workspace too small (dawn_hubert_workspace_bytes)")
 
 long conv_frames(const dawn_hubert_cfg& c, long n) {
     long T = n;
@@ -240,14 +211,12 @@ extern "C" int dawn_hubert_create(const dawn_hubert_cfg* cfg, const dawn_named_p
     }
     dawn_hubert* h = new dawn_hubert();
     h->cfg = *cfg;
-    for (int i = 0; i < n_weights; ++i)
-        if (weights[i].name) h->W[weights[i].name] = weights[i].ptr;
-    bool ok = true;
-    auto F = [&](const std::string& n) { return getw(h, n, true, &ok); };
+    DawnWeights Wt(weights, n_weights, "dawn_hubert_create: missing packed weight", -250);
+    auto F = [&](const std::string& n) { return Wt.getf(n); };
     h->conv.resize(cfg->n_conv);
     for (int i = 0; i < cfg->n_conv; ++i) {
         const std::string p = "conv." + std::to_string(i) + ".";
-        h->conv[i] = {F(p + "w"), getw(h, p + "b", false, &ok), F(p + "g"), F(p + "be")};
+        h->conv[i] = {F(p + "w"), (const float*)Wt.opt(p + "b"), F(p + "g"), F(p + "be")};
     }
     h->fp_g = F("fp.g"); h->fp_b = F("fp.b"); h->fp_w = F("fp.w"); h->fp_bias = F("fp.bias");
     h->pos_w = F("pos.w"); h->pos_b = F("pos.b");
@@ -258,9 +227,9 @@ extern "C" int dawn_hubert_create(const dawn_hubert_cfg* cfg, const dawn_named_p
                         F(p + "ln2.g"), F(p + "ln2.b"), F(p + "w1"), F(p + "b1"), F(p + "w2"), F(p + "b2")};
     }
     h->enc_g = F("enc_ln.g"); h->enc_b = F("enc_ln.b");
-    if (!ok) {
+    if (!Wt.ok()) {
         delete h;
-        return -250;
+        return Wt.code();
     }
     *out = h;
     return 0;
@@ -308,10 +277,8 @@ extern "C" int dawn_hubert_encode(dawn_hubert* hub, const float* input_values, l
         return dawn_set_error_msg(-253, m);
     }
     const size_t need = encode_bytes(hub, n);
-    if (!workspace || workspace_bytes < need || need == 0) {
-        snprintf(m, sizeof m, "dawn_hubert_encode: workspace of %zu bytes, %zu needed (dawn_hubert_workspace_bytes)", workspace_bytes, need);
-        return dawn_set_error_msg(-252, m);
-    }
+    if (!workspace || workspace_bytes < need || need == 0)
+        return refuse_workspace(-252, "dawn_hubert_encode", workspace_bytes, need, "dawn_hubert_workspace_bytes");
     DawnArena A;
     A.reset(workspace, workspace_bytes, false);
     return encode(hub, A, input_values, n, hidden_out, conv_frames(hub->cfg, n), false, stream);
@@ -330,11 +297,8 @@ extern "C" int dawn_hubert_features(dawn_hubert* hub, const float* speech, long 
         return dawn_set_error_msg(-253, m);
     }
     CK(feat_layout(hub, n, p, L));
-    if (!workspace || workspace_bytes < L.total) {
-        snprintf(m, sizeof m, "dawn_hubert_features: workspace of %zu bytes, %zu needed (dawn_hubert_workspace_bytes)", workspace_bytes,
-                 L.total);
-        return dawn_set_error_msg(-252, m);
-    }
+    if (!workspace || workspace_bytes < L.total)
+        return refuse_workspace(-252, "dawn_hubert_features", workspace_bytes, L.total, "dawn_hubert_workspace_bytes");
     const hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
     const int E = hub->cfg.hidden;

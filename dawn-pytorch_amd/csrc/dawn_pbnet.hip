@@ -11,21 +11,11 @@
 //
 // Conventions as in dawn_hubert.hip: no allocation on the device, every launch on the caller's stream, no synchronisation, int return
 // codes + dawn_last_error().  The workspace is a fixed list of per-frame buffers, so its size is exactly linear in T.
-#include "dawn_common.h"
-#include "../../include/dawn_hip.h"
+#include "dawn_host.h"
 
-#include <stdio.h>
-#include <map>
-#include <string>
 #include <vector>
 
 namespace {
-
-#define CK(expr)                              \
-    do {                                      \
-        const int rc__ = (expr);              \
-        if (rc__ != 0) return rc__;           \
-    } while (0)
 
 // normalisation of the pose rows (UVG:95-98): yaw, pitch, roll in degrees, scale, tx, ty
 const float POSE_MAX[6] = {90.f, 90.f, 90.f, 1.f, 720.f, 1080.f};
@@ -81,7 +71,6 @@ __global__ __launch_bounds__(256) void pb_finish_kernel(Fin f, long T, float* __
 
 struct dawn_pbnet {
     dawn_pbnet_cfg cfg;
-    std::map<std::string, const void*> W;
     const float *fpe_w = nullptr, *fpe_b = nullptr, *ae_w = nullptr, *ae_b = nullptr, *zt_w = nullptr, *zt_b = nullptr, *ip_b = nullptr,
                 *in_g = nullptr, *in_be = nullptr, *in_qkv = nullptr, *in_out = nullptr, *fin_w = nullptr, *fin_b = nullptr,
                 *bias_tgt = nullptr, *bias_mem = nullptr, *mem_kv = nullptr, *freqs = nullptr;
@@ -89,19 +78,6 @@ struct dawn_pbnet {
 };                                // immutable after dawn_pbnet_create
 
 namespace {
-
-const float* getw(const dawn_pbnet* h, const std::string& k, bool* ok) {
-    auto it = h->W.find(k);
-    if (it == h->W.end() || it->second == nullptr) {
-        if (*ok) {
-            *ok = false;
-            const std::string m = "dawn_pbnet_create: missing weight '" + k + "'";
-            dawn_set_error_msg(-260, m.c_str());
-        }
-        return nullptr;
-    }
-    return (const float*)it->second;
-}
 
 int up4(int n) { return (n + 3) & ~3; }
 
@@ -141,11 +117,6 @@ Layout layout(const dawn_pbnet_cfg& c, long T) {
 
 const size_t STAGE_HEADER = 256;            // dawn_pose_blink_stage: the two normalised first rows in front of the decoder's workspace
 
-bool overlaps(const void* a, size_t an, const void* b, size_t bn) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + bn && y < x + an;
-}
-
 int attn(const dawn_pbnet* h, const float* q, int ldq, const float* k, const float* v, int ldkv, long T, const float* bias,
          const float* rc, const float* rs, float* out, void* stream) {
     const dawn_pbnet_cfg& c = h->cfg;
@@ -170,10 +141,7 @@ int check_generate(const dawn_pbnet* h, const float* x0, const float* audio, int
         return dawn_set_error_msg(-263, m);
     }
     const size_t need = layout(h->cfg, T).total;
-    if (!ws || bytes < need) {
-        snprintf(m, sizeof m, "%s: workspace of %zu bytes, %zu needed (dawn_pbnet_workspace_bytes)", who, ws ? bytes : (size_t)0, need);
-        return dawn_set_error_msg(-262, m);
-    }
+    if (!ws || bytes < need) return refuse_workspace(-262, who, ws ? bytes : 0, need, "dawn_pbnet_workspace_bytes");
     if (overlaps(out, ((size_t)(T - 1) * ld_out + h->cfg.in_dim) * 4, ws, bytes)) {
         snprintf(m, sizeof m, "%s: out overlaps the workspace", who);
         return dawn_set_error_msg(-264, m);
@@ -250,10 +218,8 @@ extern "C" int dawn_pbnet_create(const dawn_pbnet_cfg* cfg, const dawn_named_ptr
     }
     dawn_pbnet* h = new dawn_pbnet();
     h->cfg = *cfg;
-    for (int i = 0; i < n_weights; ++i)
-        if (weights[i].name) h->W[weights[i].name] = weights[i].ptr;
-    bool ok = true;
-    auto F = [&](const std::string& n) { return getw(h, n, &ok); };
+    DawnWeights Wt(weights, n_weights, "dawn_pbnet_create: missing weight", -260);
+    auto F = [&](const std::string& n) { return Wt.getf(n); };
     h->fpe_w = F("firstposeEmbedding.weight"); h->fpe_b = F("firstposeEmbedding.bias");
     h->ae_w = F("audioEmbedding.weight"); h->ae_b = F("audioEmbedding.bias");
     h->zt_w = F("ztimelinear.weight"); h->zt_b = F("ztimelinear.bias");
@@ -272,9 +238,9 @@ extern "C" int dawn_pbnet_create(const dawn_pbnet_cfg* cfg, const dawn_named_ptr
                         F(p + "ffn.linear2.weight"), F(p + "ffn.linear2.bias"), F(p + "layer_norm3.weight"), F(p + "layer_norm3.bias")};
     }
     h->fin_w = F("finallayer.weight"); h->fin_b = F("finallayer.bias");
-    if (!ok) {
+    if (!Wt.ok()) {
         delete h;
-        return -260;
+        return Wt.code();
     }
     *out = h;
     return 0;
@@ -311,12 +277,9 @@ extern "C" int dawn_pose_blink_stage(dawn_pbnet* pose, dawn_pbnet* blink, const 
                  blink->cfg.in_dim, pose->cfg.audio_dim, blink->cfg.audio_dim);
         return dawn_set_error_msg(-263, m);
     }
-    if (!workspace || workspace_bytes < STAGE_HEADER) {
-        char m[200];
-        snprintf(m, sizeof m, "%s: workspace of %zu bytes, %zu needed (dawn_pose_blink_workspace_bytes)", who,
-                 workspace ? workspace_bytes : (size_t)0, dawn_pose_blink_workspace_bytes(pose, blink, T));
-        return dawn_set_error_msg(-262, m);
-    }
+    if (!workspace || workspace_bytes < STAGE_HEADER)
+        return refuse_workspace(-262, who, workspace ? workspace_bytes : 0, dawn_pose_blink_workspace_bytes(pose, blink, T),
+                                "dawn_pose_blink_workspace_bytes");
     char* ws = (char*)workspace;
     float *x0p = (float*)ws, *x0b = (float*)(ws + 64);
     void* gws = ws + STAGE_HEADER;

@@ -1,7 +1,8 @@
 """Python binding of the C-side evaluator (include/dawn_hip.h: dawn_ctx_* / dawn_clip_prepare / dawn_unet_forward /
 dawn_sampler_run(_ancestral); csrc/dawn_ctx.hip) -- what a non-Python host would call, used here by the tests (bit-identical to the
-Python orchestration of unet_forward.py / sampler.py) and optionally by the sampler (`GaussianDiffusion.use_ctx`).  `DecoderEvaluator` at
-the end of the file binds the C-side flow decoder the same way (dawn_decoder_* / dawn_decode_clip; `FlowDecoder.use_ctx`).
+Python orchestration of unet_forward.py / sampler.py) and optionally by the sampler (`GaussianDiffusion.use_ctx`).  `DecoderEvaluator`,
+`HubertEvaluator` and `PbnetEvaluator` below bind the flow decoder, the HuBERT stage and the PBnet pose / blink stage the same way; the
+four share `_Evaluator` (weight table, handle, stream, workspace).  Every entry is bound once, in _lib.lib().
 
 PyTorch only provides device memory (the packed weights, the per-clip table memory, the workspace) and the stream."""
 from __future__ import annotations
@@ -176,39 +177,50 @@ def named_weights(P: PackedUNet) -> Dict[str, Tensor]:
     return out
 
 
-class CtxEvaluator:
-    """One `dawn_ctx` for one packed model on one device.  Keeps the packed tensors alive (the ctx holds raw pointers)."""
+class _Evaluator:
+    """What the four C-side handles share: the library, the named-pointer table of `weights` (kept alive: the handle holds raw
+    pointers), creation and destruction, the caller's stream and one grow-only workspace."""
+
+    def __init__(self, create_name: str, destroy_name: str, cfg: C.Structure, weights: Dict[str, Tensor], device, fp32_only: bool):
+        """fp32_only: every table entry must be fp32 (the UNet and decoder tables carry split bf16 images as well)."""
+        self.L = _lib.lib()
+        self.device, self.cfg, self.weights, self._destroy = device, cfg, weights, destroy_name
+        arr = (NamedPtr * max(1, len(weights)))()
+        self._names = [k.encode() for k in weights]
+        for i, (k, t) in enumerate(weights.items()):
+            if not t.is_cuda or not t.is_contiguous() or (fp32_only and t.dtype != torch.float32):
+                raise _lib.DawnHipError(f"packed weight {k} must be a contiguous {'fp32 ' if fp32_only else ''}GPU tensor")
+            arr[i].name, arr[i].ptr = self._names[i], t.data_ptr()
+        h = C.c_void_p()
+        with torch.cuda.device(device):
+            check(getattr(self.L, create_name)(C.addressof(cfg), C.addressof(arr), len(weights), C.addressof(h)), create_name)
+        self.h = h
+        self._ws: Optional[Tensor] = None
+
+    def __del__(self):
+        h, self.h = getattr(self, "h", None), None
+        if h:
+            getattr(self.L, self._destroy)(h)
+
+    @staticmethod
+    def _stream() -> int:
+        return torch.cuda.current_stream().cuda_stream
+
+    def _grown(self, nbytes: int) -> Tensor:
+        """The evaluator's own workspace, at least `nbytes` long; it only ever grows.  0 is a size query's refusal."""
+        if nbytes <= 0:
+            raise _lib.DawnHipError(f"no workspace size: {self.L.dawn_last_error().decode()}")
+        if self._ws is None or self._ws.numel() < nbytes:
+            self._ws = None              # (the old one goes first)
+            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        return self._ws
+
+
+class CtxEvaluator(_Evaluator):
+    """One `dawn_ctx` for one packed model on one device."""
 
     def __init__(self, P: PackedUNet):
-        self.L = _lib.lib()
-        L = self.L
-        L.dawn_ctx_create.argtypes = [C.POINTER(UnetCfg), C.POINTER(NamedPtr), C.c_int, C.POINTER(C.c_void_p)]
-        L.dawn_ctx_create.restype = C.c_int
-        L.dawn_ctx_destroy.argtypes = [C.c_void_p]
-        L.dawn_ctx_destroy.restype = None
-        L.dawn_ctx_set_option.argtypes = [C.c_void_p, C.c_int, C.c_int]
-        L.dawn_clip_bytes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
-        L.dawn_clip_bytes.restype = C.c_size_t
-        L.dawn_workspace_bytes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
-        L.dawn_workspace_bytes.restype = C.c_size_t
-        L.dawn_clip_prepare.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
-                                        C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
-        L.dawn_unet_forward.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
-                                        C.c_void_p, C.c_size_t, C.c_void_p]
-        L.dawn_sampler_run.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
-                                       C.POINTER(DdimStep), C.c_uint64, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p,
-                                       C.c_void_p, C.c_size_t, C.c_void_p]
-        L.dawn_ctx_profile_read.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int]
-        L.dawn_workspace_bytes_sharded.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
-        L.dawn_workspace_bytes_sharded.restype = C.c_size_t
-        L.dawn_unet_forward_sharded.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
-                                                C.c_void_p, C.c_size_t, C.POINTER(ShardCommC), C.c_void_p]
-        L.dawn_sampler_run_sharded.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
-                                               C.POINTER(DdimStep), C.c_uint64, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p,
-                                               C.c_void_p, C.c_size_t, C.POINTER(ShardCommC), C.c_void_p]
         self.P = P
-        self.device = P.rel_emb.device
-        self.weights = named_weights(P)                      # keeps every tensor alive
         cfg = UnetCfg()
         cfg.dim, cfg.n_levels = P.dim, P.n_levels
         for i in range(P.n_levels):
@@ -216,17 +228,7 @@ class CtxEvaluator:
         cfg.fea_ch = P.fea_ch
         cfg.cond_aud, cfg.cond_pose, cfg.cond_eye = P.cond_dims
         cfg.win = P.win
-        arr = (NamedPtr * len(self.weights))()
-        self._names = [k.encode() for k in self.weights]
-        for i, (k, t) in enumerate(self.weights.items()):
-            if not t.is_cuda or not t.is_contiguous():
-                raise _lib.DawnHipError(f"packed weight {k} must be a contiguous GPU tensor")
-            arr[i].name, arr[i].ptr = self._names[i], t.data_ptr()
-        h = C.c_void_p()
-        with torch.cuda.device(self.device):
-            check(L.dawn_ctx_create(C.byref(cfg), arr, len(self.weights), C.byref(h)), "dawn_ctx_create")
-        self.h = h
-        self._ws: Optional[Tensor] = None
+        super().__init__("dawn_ctx_create", "dawn_ctx_destroy", cfg, named_weights(P), P.rel_emb.device, fp32_only=False)
         self._need = {}              # (F, h, w, conv policy) -> dawn_workspace_bytes (a dry evaluation on the host: cached)
         self._policy = 0
         if P.up_border:              # folded up convs (use_deconv=False): what their outside taps read
@@ -234,21 +236,12 @@ class CtxEvaluator:
         if os.environ.get("DAWN_FOLD_HEADS", "1") == "0":      # (the A/B switch HipOps.fold_heads reads: both hosts follow it)
             self.set_option(OPT_FOLD_HEADS, 0)
 
-    def __del__(self):
-        h, self.h = getattr(self, "h", None), None
-        if h:
-            self.L.dawn_ctx_destroy(h)
-
     def set_option(self, option: int, value: int) -> None:
         check(self.L.dawn_ctx_set_option(self.h, option, int(value)), "dawn_ctx_set_option")
         if option == OPT_CONV_POLICY:
             self._policy = int(value)
         if option != OPT_PROFILE:
             self._need.clear()              # kernel-family options change the launch sequence, hence the requirement
-
-    @staticmethod
-    def _stream() -> int:
-        return torch.cuda.current_stream().cuda_stream
 
     def workspace(self, F: int, h: int, w: int, shard: Optional[ShardCallbacks] = None, guided: bool = False) -> Tensor:
         key = (F, h, w, self._policy, None if shard is None else (shard.rank, shard.world))
@@ -262,9 +255,7 @@ class CtxEvaluator:
             else:
                 need = self._need[key] = int(self.L.dawn_workspace_bytes(self.h, F, h, w) if shard is None else
                                              self.L.dawn_workspace_bytes_sharded(self.h, F, h, w, shard.rank, shard.world))
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return self._ws
+        return self._grown(need)
 
     def prepare_clip(self, fea272: Tensor, cond: Tensor, rcos: Optional[Tensor] = None, rsin: Optional[Tensor] = None) -> dict:
         """fea272 (fea_ch, h, w), cond (F, cond_dim) -> the per-clip table memory (a dict holding the buffer + shape)."""
@@ -302,7 +293,7 @@ class CtxEvaluator:
         if shard is not None:
             shard.ws = ws
             self._shard_call(shard, self.L.dawn_unet_forward_sharded(self.h, F, h, w, clip["mem"].data_ptr(), x3.data_ptr(), float(t),
-                                                                     out.data_ptr(), ws.data_ptr(), ws.numel(), C.byref(shard.c),
+                                                                     out.data_ptr(), ws.data_ptr(), ws.numel(), C.addressof(shard.c),
                                                                      self._stream()), "dawn_unet_forward_sharded")
             return out
         check(self.L.dawn_unet_forward(self.h, F, h, w, clip["mem"].data_ptr(), x3.data_ptr(), float(t), out.data_ptr(),
@@ -392,7 +383,7 @@ class CtxEvaluator:
             shard.ws = ws
             self._shard_call(shard, self.L.dawn_sampler_run_sharded(self.h, F, h, w, clip["mem"].data_ptr(), x_init.data_ptr(), S, arr,
                                                                     int(seed), nz, out.data_ptr(), None if thr is None else thr.data_ptr(),
-                                                                    ws.data_ptr(), ws.numel(), C.byref(shard.c), self._stream()),
+                                                                    ws.data_ptr(), ws.numel(), C.addressof(shard.c), self._stream()),
                              "dawn_sampler_run_sharded")
             return (out, thr) if want_thresholds else out
         check(self.L.dawn_sampler_run(self.h, F, h, w, clip["mem"].data_ptr(), x_init.data_ptr(), S, arr, int(seed), nz,
@@ -488,52 +479,25 @@ def decoder_named_weights(dec) -> Dict[str, Tensor]:
     return out
 
 
-class DecoderEvaluator:
+class DecoderEvaluator(_Evaluator):
     """One `dawn_decoder` for one `FlowDecoder` on one device: what a non-Python host would call to turn the sampler's latent into
     frames.  PyTorch provides the device memory (packed weights, skip memory, workspace, outputs) and the stream.  `weights` lets a
     test hand in an edited table (a missing name must be an error)."""
 
     def __init__(self, dec, weights: Optional[Dict[str, Tensor]] = None):
-        self.L = _lib.lib()
-        self.device = dec.first_w3.device
-        self.weights = decoder_named_weights(dec) if weights is None else dict(weights)      # keeps every tensor alive
         cfg = DecoderCfg()
         cfg.n_down, cfg.n_bottleneck = len(dec.downs), len(dec.bott)
         cfg.widths[0] = dec.C0
         for i, c in enumerate(dec.downs):
             cfg.widths[i + 1] = c.N
-        self.cfg = cfg
-        arr = (NamedPtr * max(1, len(self.weights)))()
-        self._names = [k.encode() for k in self.weights]
-        for i, (k, t) in enumerate(self.weights.items()):
-            if not t.is_cuda or not t.is_contiguous():
-                raise _lib.DawnHipError(f"packed weight {k} must be a contiguous GPU tensor")
-            arr[i].name, arr[i].ptr = self._names[i], t.data_ptr()
-        h = C.c_void_p()
-        check(self.L.dawn_decoder_create(C.addressof(cfg), C.addressof(arr), len(self.weights), C.addressof(h)), "dawn_decoder_create")
-        self.h = h
-        self._ws: Optional[Tensor] = None
-
-    def __del__(self):
-        h, self.h = getattr(self, "h", None), None
-        if h:
-            self.L.dawn_decoder_destroy(h)
-
-    @staticmethod
-    def _stream() -> int:
-        return torch.cuda.current_stream().cuda_stream
+        super().__init__("dawn_decoder_create", "dawn_decoder_destroy", cfg, decoder_named_weights(dec) if weights is None else dict(weights),
+                         dec.first_w3.device, fp32_only=False)
 
     def workspace_bytes(self, H: int, W: int, chunk: int) -> int:
         return int(self.L.dawn_decoder_workspace_bytes(self.h, H, W, chunk))
 
     def workspace(self, H: int, W: int, chunk: int) -> Tensor:
-        need = self.workspace_bytes(H, W, chunk)
-        if need == 0:
-            raise _lib.DawnHipError(f"dawn_decoder_workspace_bytes: {self.L.dawn_last_error().decode()}")
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = None
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return self._ws
+        return self._grown(self.workspace_bytes(H, W, chunk))
 
     def encode(self, img: Tensor, want_fea: bool = False):
         """img (3,H,W) fp32 contiguous -> (skip memory, fea (Cb,H/k,W/k) or None)."""
@@ -646,7 +610,7 @@ def hubert_named_weights(hf) -> Dict[str, Tensor]:
     return out
 
 
-class HubertEvaluator:
+class HubertEvaluator(_Evaluator):
     """One `dawn_hubert` for one `HubertFeatures` on one device: what a non-Python host would call to turn 16 kHz samples into the
     audio rows of `cond`.  PyTorch provides the device memory (packed weights, workspace, outputs) and the stream.  `weights` lets a
     test hand in an edited table (a missing name must be an error)."""
@@ -654,29 +618,8 @@ class HubertEvaluator:
     MAX_SEGMENTS = 4096
 
     def __init__(self, hf, weights: Optional[Dict[str, Tensor]] = None):
-        self.L = _lib.lib()
-        self.device = hf.fp_w.device
-        self.weights = hubert_named_weights(hf) if weights is None else dict(weights)      # keeps every tensor alive
-        self.cfg = hubert_cfg(hf)
-        arr = (NamedPtr * max(1, len(self.weights)))()
-        self._names = [k.encode() for k in self.weights]
-        for i, (k, t) in enumerate(self.weights.items()):
-            if not t.is_cuda or not t.is_contiguous() or t.dtype != torch.float32:
-                raise _lib.DawnHipError(f"packed weight {k} must be a contiguous fp32 GPU tensor")
-            arr[i].name, arr[i].ptr = self._names[i], t.data_ptr()
-        h = C.c_void_p()
-        check(self.L.dawn_hubert_create(C.addressof(self.cfg), C.addressof(arr), len(self.weights), C.addressof(h)), "dawn_hubert_create")
-        self.h = h
-        self._ws: Optional[Tensor] = None
-
-    def __del__(self):
-        h, self.h = getattr(self, "h", None), None
-        if h:
-            self.L.dawn_hubert_destroy(h)
-
-    @staticmethod
-    def _stream() -> int:
-        return torch.cuda.current_stream().cuda_stream
+        super().__init__("dawn_hubert_create", "dawn_hubert_destroy", hubert_cfg(hf), hubert_named_weights(hf) if weights is None else dict(weights),
+                         hf.fp_w.device, fp32_only=True)
 
     def conv_frames(self, n: int) -> int:
         return int(self.L.dawn_hubert_conv_frames(self.h, n))
@@ -693,13 +636,7 @@ class HubertEvaluator:
         return int(self.L.dawn_hubert_workspace_bytes(self.h, n))
 
     def workspace(self, n: int) -> Tensor:
-        need = self.workspace_bytes(n)
-        if need == 0:
-            raise _lib.DawnHipError(f"dawn_hubert_workspace_bytes: {self.L.dawn_last_error().decode()}")
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = None
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return self._ws
+        return self._grown(self.workspace_bytes(n))
 
     def _samples(self, x: Tensor, who: str) -> None:
         if not (x.is_cuda and x.is_contiguous() and x.dtype == torch.float32 and x.dim() == 1):
@@ -797,44 +734,20 @@ def pbnet_named_weights(gen) -> Dict[str, Tensor]:
     return out
 
 
-class PbnetEvaluator:
+class PbnetEvaluator(_Evaluator):
     """One `dawn_pbnet` for one `PoseBlinkGenerator` on one device: what a non-Python host would call to produce the pose or blink
     columns of `cond`.  PyTorch provides the device memory (weights, workspace, outputs) and the stream.  `weights` lets a test hand in
     an edited table (a missing name must be an error)."""
 
     def __init__(self, gen, weights: Optional[Dict[str, Tensor]] = None):
-        self.L = _lib.lib()
-        self.device = gen.device
-        self.weights = pbnet_named_weights(gen) if weights is None else dict(weights)      # keeps every tensor alive
-        self.cfg = pbnet_cfg(gen)
-        arr = (NamedPtr * max(1, len(self.weights)))()
-        self._names = [k.encode() for k in self.weights]
-        for i, (k, t) in enumerate(self.weights.items()):
-            if not t.is_cuda or not t.is_contiguous() or t.dtype != torch.float32:
-                raise _lib.DawnHipError(f"weight {k} must be a contiguous fp32 GPU tensor")
-            arr[i].name, arr[i].ptr = self._names[i], t.data_ptr()
-        h = C.c_void_p()
-        check(self.L.dawn_pbnet_create(C.addressof(self.cfg), C.addressof(arr), len(self.weights), C.addressof(h)), "dawn_pbnet_create")
-        self.h = h
-        self._ws: Optional[Tensor] = None
-
-    def __del__(self):
-        h, self.h = getattr(self, "h", None), None
-        if h:
-            self.L.dawn_pbnet_destroy(h)
-
-    @staticmethod
-    def _stream() -> int:
-        return torch.cuda.current_stream().cuda_stream
+        super().__init__("dawn_pbnet_create", "dawn_pbnet_destroy", pbnet_cfg(gen), pbnet_named_weights(gen) if weights is None else dict(weights),
+                         gen.device, fp32_only=True)
 
     def workspace_bytes(self, T: int) -> int:
         return int(self.L.dawn_pbnet_workspace_bytes(self.h, T))
 
-    def workspace(self, nbytes: int) -> Tensor:
-        if self._ws is None or self._ws.numel() < nbytes:
-            self._ws = None
-            self._ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=self.device)
-        return self._ws
+    def workspace(self, T: int) -> Tensor:
+        return self._grown(self.workspace_bytes(T))
 
     def generate(self, x0: Tensor, audio: Tensor, z: Tensor, workspace: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
         """x0 (in_dim) first pose, audio (T, audio_dim) (rows may be strided), z (T, latent_dim) -> (T, in_dim): `_decode_one`.
@@ -845,7 +758,7 @@ class PbnetEvaluator:
                 raise _lib.DawnHipError(f"PbnetEvaluator.generate: {name} must be an fp32 GPU tensor of shape {shape}")
         if not z.is_contiguous():
             raise _lib.DawnHipError("PbnetEvaluator.generate: z must be contiguous")
-        ws = workspace if workspace is not None else self.workspace(self.workspace_bytes(T))
+        ws = workspace if workspace is not None else self.workspace(T)
         if out is None:
             out = torch.empty(T, self.cfg.in_dim, device=self.device)
         if not (out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (T, self.cfg.in_dim) and out.stride(1) == 1):
@@ -877,9 +790,9 @@ def pose_blink_stage_c(ev_pose: PbnetEvaluator, ev_blink: PbnetEvaluator, audio:
         if not (t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == (T, w) and t.stride(1) == 1):
             raise _lib.DawnHipError(f"pose_blink_stage_c: outputs must be fp32 GPU (T, {w}) views with unit column stride")
     need = int(L.dawn_pose_blink_workspace_bytes(ev_pose.h, ev_blink.h, T))
-    ws = workspace if workspace is not None else ev_pose.workspace(need)
+    ws = workspace if workspace is not None else ev_pose._grown(need)
     ld = lambda t, w: t.stride(0) if T > 1 else w                                             # noqa: E731
     check(L.dawn_pose_blink_stage(ev_pose.h, ev_blink.h, audio.data_ptr(), ld(audio, ev_pose.cfg.audio_dim), T, ip, ib, z_pose.data_ptr(),
                                   z_blink.data_ptr(), dri_pose.data_ptr(), ld(dri_pose, 6), dri_blink.data_ptr(), ld(dri_blink, 2),
-                                  ws.data_ptr(), ws.numel(), PbnetEvaluator._stream()), "dawn_pose_blink_stage")
+                                  ws.data_ptr(), ws.numel(), ev_pose._stream()), "dawn_pose_blink_stage")
     return dri_pose, dri_blink

@@ -231,6 +231,4 @@ def test_border_errors_launch_nothing(hip):
     # ... and the C evaluator's option takes 0 / 1 / 2 only
     from dawn_pytorch_amd.ctx import OPT_UP_BORDER
     L = _lib.lib()
-    import ctypes
-    L.dawn_ctx_set_option.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
     assert L.dawn_ctx_set_option(None, OPT_UP_BORDER, 3) != 0

@@ -160,7 +160,6 @@ def test_abi_is_additive():
     assert _lib.ConvDesc().border == 0
     L = _lib.lib()
     assert L.dawn_abi_version() == 8
-    L.dawn_ctx_set_option.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
     # the value is checked before anything else: no ctx (and so no GPU) is needed to see it rejected
     for bad in (3, -1):
         assert L.dawn_ctx_set_option(None, 6, bad) != 0
