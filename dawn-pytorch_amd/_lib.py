@@ -164,6 +164,17 @@ SIGNATURES = {
     "dawn_pose_blink_workspace_bytes": [c_f, c_f, _l],
     "dawn_pose_blink_stage": [c_f, c_f, c_f, _i, _l, C.POINTER(C.c_float), C.POINTER(C.c_float), c_f, c_f, c_f, _i, c_f, _i, c_f,
                               C.c_size_t, c_f],
+    # clip inputs (csrc/clip_inputs.hip: bbox6 / init_pose / init_eye are HOST floats), their stage host and the one-call pipeline
+    # (csrc/dawn_inputs.hip; the handle, the cfg / args structs and the named-pointer table travel as void*: ctx.py)
+    "dawn_face_loc_embed": [C.POINTER(C.c_float), _i, c_f, c_f, c_f, c_f, c_f, _l, c_f],
+    "dawn_bbox_mask_bounds": [C.POINTER(C.c_float), _i, C.POINTER(C.c_int)],
+    "dawn_cond_rows": [c_f, _i, _i, c_f, _i, _i, c_f, _i, C.POINTER(C.c_float), _i, C.POINTER(C.c_float), _l, c_f, _i, c_f],
+    "dawn_inputs_create": [c_f, c_f, _i, c_f],
+    "dawn_inputs_destroy": [c_f],
+    "dawn_clip_inputs": [c_f, C.POINTER(C.c_float), _i, c_f, _i, c_f, _i, c_f, _i, _i, c_f, _i, C.POINTER(C.c_float), _i,
+                         C.POINTER(C.c_float), _l, c_f, _i, c_f],
+    "dawn_generate_bytes": [c_f, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)],
+    "dawn_generate_clip": [c_f, c_f, C.c_size_t, c_f],
 }
 # device helpers of the C-side evaluator (csrc/dawn_ctx.hip calls them; from Python only the op tests do)
 CTX_HELPER_SIGNATURES = {

@@ -1,8 +1,8 @@
 """Python binding of the C-side evaluator (include/dawn_hip.h: dawn_ctx_* / dawn_clip_prepare / dawn_unet_forward /
 dawn_sampler_run(_ancestral); csrc/dawn_ctx.hip) -- what a non-Python host would call, used here by the tests (bit-identical to the
 Python orchestration of unet_forward.py / sampler.py) and optionally by the sampler (`GaussianDiffusion.use_ctx`).  `DecoderEvaluator`,
-`HubertEvaluator` and `PbnetEvaluator` below bind the flow decoder, the HuBERT stage and the PBnet pose / blink stage the same way; the
-four share `_Evaluator` (weight table, handle, stream, workspace).  Every entry is bound once, in _lib.lib().
+`HubertEvaluator`, `PbnetEvaluator` and `InputsEvaluator` below bind the flow decoder, the HuBERT stage, the PBnet pose / blink stage and
+the clip-input stage the same way; the five share `_Evaluator` (weight table, handle, stream, workspace).  Every entry is bound once, in _lib.lib().
 
 PyTorch only provides device memory (the packed weights, the per-clip table memory, the workspace) and the stream."""
 from __future__ import annotations
@@ -178,7 +178,7 @@ def named_weights(P: PackedUNet) -> Dict[str, Tensor]:
 
 
 class _Evaluator:
-    """What the four C-side handles share: the library, the named-pointer table of `weights` (kept alive: the handle holds raw
+    """What the five C-side handles share: the library, the named-pointer table of `weights` (kept alive: the handle holds raw
     pointers), creation and destruction, the caller's stream and one grow-only workspace."""
 
     def __init__(self, create_name: str, destroy_name: str, cfg: C.Structure, weights: Dict[str, Tensor], device, fp32_only: bool):
@@ -796,3 +796,178 @@ def pose_blink_stage_c(ev_pose: PbnetEvaluator, ev_blink: PbnetEvaluator, audio:
                                   z_blink.data_ptr(), dri_pose.data_ptr(), ld(dri_pose, 6), dri_blink.data_ptr(), ld(dri_blink, 2),
                                   ws.data_ptr(), ws.numel(), ev_pose._stream()), "dawn_pose_blink_stage")
     return dri_pose, dri_blink
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# C-side clip-input stage (include/dawn_hip.h: dawn_inputs_*, dawn_clip_inputs; csrc/dawn_inputs.hip)
+class InputsCfg(C.Structure):
+    """Mirror of ``dawn_inputs_cfg``."""
+    _fields_ = [("n_aud", C.c_int), ("pose_dim", C.c_int), ("eye_dim", C.c_int)]
+
+
+_FACE_LOC = {"face_loc_emb.conv1.weight": (8, 1, 3, 3), "face_loc_emb.conv1.bias": (8,), "face_loc_emb.conv2.weight": (16, 8, 3, 3),
+             "face_loc_emb.conv2.bias": (16,)}
+
+
+def inputs_named_weights(flow_diffusion) -> Dict[str, Tensor]:
+    """flow_diffusion.FlowDiffusion -> {state_dict key: device tensor} of its Face_loc_Encoder (the reference never saves it:
+    whatever the module holds).  Only pointers reach the C side, so the shapes are checked here."""
+    sd = flow_diffusion.state_dict()
+    out: Dict[str, Tensor] = {}
+    for k, shape in _FACE_LOC.items():
+        if k not in sd or tuple(sd[k].shape) != shape:
+            raise _lib.DawnHipError(f"inputs_named_weights: '{k}' missing or not {shape}")
+        out[k] = sd[k].detach()
+    return out
+
+
+def _host_floats(v, n: Optional[int] = None):
+    if v is None:
+        return None
+    v = [float(x) for x in v]
+    if n is not None and len(v) != n:
+        raise _lib.DawnHipError(f"{n} host numbers expected, {len(v)} given")
+    return (C.c_float * len(v))(*v)
+
+
+class InputsEvaluator(_Evaluator):
+    """One `dawn_inputs` for one `FlowDiffusion` on one device: what a non-Python host would call for the face-location channels of
+    fea272 and the condition rows.  PyTorch provides the device memory and the stream.  `weights` lets a test hand in an edited table."""
+
+    def __init__(self, flow_diffusion, n_aud: int = 1024, weights: Optional[Dict[str, Tensor]] = None, pose_dim: Optional[int] = None):
+        cfg = InputsCfg(int(n_aud), int(flow_diffusion.pose_dim if pose_dim is None else pose_dim), 2)
+        w = inputs_named_weights(flow_diffusion) if weights is None else dict(weights)
+        dev = next(iter(w.values())).device if w else torch.device("cuda")
+        super().__init__("dawn_inputs_create", "dawn_inputs_destroy", cfg, w, dev, fp32_only=True)
+
+    def clip_inputs(self, bbox6, size: int, fea: Tensor, audio: Tensor, pose: Tensor, eye: Tensor, init_pose=None, init_eye=None,
+                    cond: Optional[Tensor] = None) -> Tensor:
+        """dawn_clip_inputs: `fea` = fea272 (fea_ch, size/4, size/4) contiguous -- or just its last 16 planes --, whose last 16 planes are
+        written; audio (T, n_aud), pose (T, n_pose), eye (T, 2) rows with unit column stride (they may be the column views of `cond`
+        they land in); init_pose / init_eye host numbers or None -> cond (T, n_aud + pose_dim + 2) (allocated when None)."""
+        T, P = audio.shape[0], self.cfg.pose_dim
+        width = self.cfg.n_aud + P + 2
+        if cond is None:
+            cond = torch.empty(T, width, device=self.device)
+        for t, w_, name in ((audio, self.cfg.n_aud, "audio"), (pose, pose.shape[1], "pose"), (eye, 2, "eye"), (cond, cond.shape[1], "cond")):
+            if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and tuple(t.shape) == (T, w_) and t.stride(1) == 1):
+                raise _lib.DawnHipError(f"InputsEvaluator.clip_inputs: {name} must be an fp32 GPU tensor of shape {(T, w_)} with unit column stride")
+        if not (fea.is_cuda and fea.dtype == torch.float32 and fea.is_contiguous() and fea.dim() == 3 and fea.shape[0] >= 16
+                and tuple(fea.shape[1:]) == (size // 4, size // 4)):
+            raise _lib.DawnHipError("InputsEvaluator.clip_inputs: fea must be a contiguous fp32 GPU tensor (>= 16, size/4, size/4)")
+        ld = lambda t: t.stride(0) if T > 1 else max(t.stride(0), t.shape[1])                    # noqa: E731
+        ip = _host_floats(init_pose)
+        check(self.L.dawn_clip_inputs(self.h, _host_floats(bbox6, 6), int(size), fea.data_ptr(), fea.shape[0], audio.data_ptr(), ld(audio),
+                                      pose.data_ptr(), pose.shape[1], ld(pose), eye.data_ptr(), ld(eye), ip, 0 if ip is None else len(ip),
+                                      _host_floats(init_eye, 2), T, cond.data_ptr(), ld(cond), self._stream()), "dawn_clip_inputs")
+        return cond
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# one call from samples and a source image to frame bytes (include/dawn_hip.h: dawn_generate_bytes / dawn_generate_clip)
+class GenerateArgs(C.Structure):
+    """Mirror of ``dawn_generate_args``."""
+    _fields_ = [("hubert", C.c_void_p), ("pose", C.c_void_p), ("blink", C.c_void_p), ("decoder", C.c_void_p), ("inputs", C.c_void_p),
+                ("unet", C.c_void_p), ("samples", C.c_void_p), ("n_samples", C.c_long), ("img3", C.c_void_p), ("H", C.c_int),
+                ("fea_ch", C.c_int), ("bbox6", C.POINTER(C.c_float)), ("init_pose", C.POINTER(C.c_float)),
+                ("init_eye", C.POINTER(C.c_float)), ("n_init", C.c_int), ("latent_dim", C.c_int), ("init_pose6", C.POINTER(C.c_float)),
+                ("init_blink2", C.POINTER(C.c_float)), ("T", C.c_long), ("S", C.c_int), ("cond_scale", C.c_float),
+                ("ddim_steps", C.POINTER(DdimStep)), ("ancestral_steps", C.POINTER(AncestralStep)), ("clip", C.POINTER(ClipMode)),
+                ("seed", C.c_uint64), ("format", C.c_int), ("bgr", C.c_int), ("chunk", C.c_int), ("mean3", C.POINTER(C.c_double)),
+                ("frames_out", C.c_void_p), ("latent_out", C.c_void_p), ("cond_out", C.c_void_p)]
+
+
+FRAMES_RGB, FRAMES_YUV420 = 0, 1
+Z_POSE_STREAM, Z_BLINK_STREAM = 0xFFFFFFFE, 0xFFFFFFFF      # Philox stream ids of the PBnet latents; x_init is stream 0, sampler steps 1..
+
+
+class PipelineEvaluator:
+    """dawn_generate_clip over the five stage evaluators (they own the handles and keep the weights alive): samples + image -> frame
+    bytes in one C call.  PyTorch provides the device memory (inputs, outputs, one grow-only workspace) and the stream."""
+
+    def __init__(self, hubert: HubertEvaluator, pose: PbnetEvaluator, blink: PbnetEvaluator, decoder: DecoderEvaluator,
+                 inputs: InputsEvaluator, unet: CtxEvaluator):
+        self.L = _lib.lib()
+        self.ev = (hubert, pose, blink, decoder, inputs, unet)
+        self.device = unet.device
+        self._ws: Optional[Tensor] = None
+
+    def args(self, samples: Tensor, img: Tensor, bbox6, init_pose6, init_blink2, T: int, steps: Sequence[dict], *, ancestral: bool = False,
+             init_pose=None, init_eye=None, cond_scale: float = 1.0, x0_clip=None, seed: int = 0, fmt: str = "rgb", mean=(0.0, 0.0, 0.0),
+             bgr: bool = False, chunk: int = 16) -> GenerateArgs:
+        """The filled struct; every host array it points to is kept alive on it (`_keep`)."""
+        hub, pose, blink, dec, inp, unet = self.ev
+        if not (samples.is_cuda and samples.is_contiguous() and samples.dtype == torch.float32 and samples.dim() == 1):
+            raise _lib.DawnHipError("PipelineEvaluator: samples must be a contiguous 1-D fp32 GPU tensor")
+        if not (img.is_cuda and img.is_contiguous() and img.dtype == torch.float32 and img.dim() == 3 and img.shape[0] == 3
+                and img.shape[1] == img.shape[2]):
+            raise _lib.DawnHipError("PipelineEvaluator: img must be a contiguous fp32 GPU tensor (3, H, H)")
+        if fmt not in ("rgb", "yuv420p"):
+            raise _lib.DawnHipError(f"PipelineEvaluator: format must be 'rgb' or 'yuv420p', not {fmt!r}")
+        a = GenerateArgs()
+        a.hubert, a.pose, a.blink, a.decoder, a.inputs, a.unet = hub.h, pose.h, blink.h, dec.h, inp.h, unet.h
+        a.samples, a.n_samples, a.img3, a.H, a.fea_ch = samples.data_ptr(), samples.numel(), img.data_ptr(), img.shape[1], unet.cfg.fea_ch
+        S = len(steps)
+        if ancestral:
+            arr = (AncestralStep * max(S, 1))()
+            for i, st in enumerate(steps):
+                arr[i].t, arr[i].recip, arr[i].recipm1 = int(st["t"]), st["recip"], st["recipm1"]
+                arr[i].c1, arr[i].c2, arr[i].std = st["c1"], st["c2"], st["std"]
+            a.ancestral_steps = arr
+        else:
+            arr = (DdimStep * max(S, 1))()
+            for i, st in enumerate(steps):
+                arr[i].t, arr[i].t_next = int(st["t"]), int(st["t_next"])
+                arr[i].recip, arr[i].recipm1 = st["recip"], st["recipm1"]
+                arr[i].sqrt_alpha_next, arr[i].c, arr[i].sigma = st["sqrt_alpha_next"], st["c"], st["sigma"]
+            a.ddim_steps = arr
+        keep = [arr, _host_floats(bbox6, 6), _host_floats(init_pose), _host_floats(init_eye, 2), _host_floats(init_pose6, 6),
+                _host_floats(init_blink2, 2), (C.c_double * 3)(*[float(v) / 255.0 for v in mean])]
+        if keep[1] is not None:
+            a.bbox6 = keep[1]
+        if keep[2] is not None:
+            a.init_pose, a.n_init = keep[2], len(keep[2])
+        if keep[3] is not None:
+            a.init_eye = keep[3]
+        a.init_pose6, a.init_blink2, a.mean3 = keep[4], keep[5], keep[6]
+        if x0_clip is not None:
+            keep.append(_clip_struct(x0_clip, ancestral))
+            a.clip = C.pointer(keep[-1])
+        a.latent_dim, a.T, a.S, a.cond_scale, a.seed = pose.cfg.latent_dim, int(T), S, float(cond_scale), int(seed)
+        a.format, a.bgr, a.chunk = (FRAMES_YUV420 if fmt == "yuv420p" else FRAMES_RGB), int(bool(bgr)), int(chunk)
+        a._keep = keep
+        return a
+
+    def sizes(self, a: GenerateArgs):
+        """(bytes of the frames, bytes of the workspace) of dawn_generate_bytes."""
+        cb, wb = C.c_size_t(0), C.c_size_t(0)
+        check(self.L.dawn_generate_bytes(C.addressof(a), C.byref(cb), C.byref(wb)), "dawn_generate_bytes")
+        return int(cb.value), int(wb.value)
+
+    def generate(self, a: GenerateArgs, want_latent: bool = False, want_cond: bool = False, workspace: Optional[Tensor] = None,
+                 frames: Optional[Tensor] = None) -> dict:
+        """Run dawn_generate_clip on the struct of `args(...)` -> {"frames": uint8 (T,H,H,3) or (T, 3HH/2), "latent", "cond"}."""
+        hub, pose, blink, dec, inp, unet = self.ev
+        cb, wb = self.sizes(a)
+        T, H, h = int(a.T), int(a.H), int(a.H) // 4
+        if frames is None:
+            frames = torch.empty((T, H * H * 3 // 2) if a.format == FRAMES_YUV420 else (T, H, H, 3), dtype=torch.uint8, device=self.device)
+        if not (frames.is_cuda and frames.dtype == torch.uint8 and frames.is_contiguous() and frames.numel() == cb):
+            raise _lib.DawnHipError(f"PipelineEvaluator.generate: frames must be a contiguous uint8 GPU tensor of {cb} bytes")
+        out = {"frames": frames}
+        a.frames_out = frames.data_ptr()
+        if want_latent:
+            out["latent"] = torch.empty(3, T, h, h, device=self.device)
+            a.latent_out = out["latent"].data_ptr()
+        if want_cond:
+            out["cond"] = torch.empty(T, inp.cfg.n_aud + inp.cfg.pose_dim + 2, device=self.device)
+            a.cond_out = out["cond"].data_ptr()
+        if want_latent or want_cond:
+            cb, wb = self.sizes(a)                          # (outputs the caller takes leave the workspace)
+        if workspace is None:
+            if self._ws is None or self._ws.numel() < wb:
+                self._ws = None
+                self._ws = torch.empty(wb, dtype=torch.uint8, device=self.device)
+            workspace = self._ws
+        check(self.L.dawn_generate_clip(C.addressof(a), workspace.data_ptr(), workspace.numel(), _Evaluator._stream()), "dawn_generate_clip")
+        return out

@@ -7,7 +7,9 @@ FD:96-201, 325-406): owns `.generator` (the LFG flow generator, injected: the re
 `flow_decoder.FlowDecoder`, built from the injected generator's state_dict, replaces the reference's per-frame
 `forward_with_flow` loop FD:372-385 when the clip lives on the GPU).  The few lines of tensor algebra around them
 (condition assembly, bbox rasterisation, the 2-conv `Face_loc_Encoder`) are once-per-clip host-side plumbing and
-stay in torch, device-agnostic (the reference hard-codes `.cuda()`).
+stay in torch by default, device-agnostic (the reference hard-codes `.cuda()`); with `inputs_via_c = True` a GPU clip of
+one sample takes them from the C-side clip-input stage instead (`ctx.InputsEvaluator`: dawn_clip_inputs, what a host
+without Python calls).
 """
 from __future__ import annotations
 
@@ -86,6 +88,8 @@ class FlowDiffusion(nn.Module):
                                                     ddim_sampling_eta=ddim_sampling_eta)
         self.face_loc_emb = Face_loc_Encoder()
         self.is_train = is_train        # kept for signature parity; this build is inference-only
+        self.inputs_via_c = False       # True: bbox_mask and cond of a GPU clip with B == 1 from dawn_clip_inputs (ctx.InputsEvaluator)
+        self._inputs_ev = None
 
     def update_num_frames(self, new_num_frames):
         """FD:177-180."""
@@ -135,6 +139,25 @@ class FlowDiffusion(nn.Module):
             ref_pose = torch.cat([ref_pose, ip[:, :, -1].unsqueeze(-1)], dim=-1)
         return torch.cat([sample_audio_hubert, ref_pose - ip, ref_eye - ie], dim=-1)
 
+    def clip_inputs(self, sample_img, sample_audio_hubert, sample_pose, sample_eye, sample_bbox, init_pose=None, init_eye=None):
+        """(bbox_mask (B,16,h,w), cond (B,T,cond_dim)) of FD:327-350: the torch plumbing, or -- `inputs_via_c`, a GPU clip, B == 1 --
+        the C-side stage.  The evaluator holds pointers into `face_loc_emb`'s parameters: it is rebuilt when they moved."""
+        if not (self.inputs_via_c and sample_img.is_cuda and sample_img.shape[0] == 1):
+            return (self.face_loc_emb(self.generate_bbox_mask(sample_bbox, size=sample_img.shape[-1])),
+                    self.assemble_cond(sample_audio_hubert, sample_pose, sample_eye, init_pose, init_eye))
+        from .ctx import InputsEvaluator
+        key = tuple(p.data_ptr() for p in self.face_loc_emb.parameters())
+        if self._inputs_ev is None or self._inputs_ev[0] != key:
+            self._inputs_ev = (key, InputsEvaluator(self, n_aud=sample_audio_hubert.shape[-1]))
+        pose = sample_pose[0, :self.pose_dim].t().float().contiguous()      # (T, n_pose) rows, as assemble_cond permutes them
+        eye = sample_eye[0].t().float().contiguous()
+        size = sample_img.shape[-1]
+        fea16 = torch.empty(16, size // 4, size // 4, device=sample_img.device)
+        cond = self._inputs_ev[1].clip_inputs(sample_bbox[0, :, 0].tolist(), size, fea16, sample_audio_hubert[0].float().contiguous(), pose, eye,
+                                             None if init_pose is None else init_pose[0, :self.pose_dim].tolist(),
+                                             None if init_eye is None else init_eye[0].tolist())
+        return fea16.unsqueeze(0), cond.unsqueeze(0)
+
     @torch.no_grad()
     def sample_one_video(self, sample_img, sample_audio_hubert, sample_pose, sample_eye, sample_bbox, cond_scale,
                          init_pose=None, init_eye=None, real_vid=None, frames_u8: Optional[dict] = None):
@@ -146,8 +169,7 @@ class FlowDiffusion(nn.Module):
         (B,T,3HW/2) uint8 tensor of FlowDecoder.decode_clip_yuv420, or the generator of stream_frames_yuv420; it has no bgr."""
         out = {}
         fea = self.generator.compute_fea(sample_img)                                   # (B,256,h,w)  GEN:132-136
-        bbox_mask = self.face_loc_emb(self.generate_bbox_mask(sample_bbox, size=sample_img.shape[-1]))
-        cond = self.assemble_cond(sample_audio_hubert, sample_pose, sample_eye, init_pose, init_eye)
+        bbox_mask, cond = self.clip_inputs(sample_img, sample_audio_hubert, sample_pose, sample_eye, sample_bbox, init_pose, init_eye)
         t0 = time.time()
         pred = self.diffusion.sample(fea, bbox_mask, cond=cond, batch_size=fea.size(0), cond_scale=cond_scale)
         out["sample_vid_grid"] = pred[:, :2]

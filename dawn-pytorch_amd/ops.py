@@ -925,3 +925,48 @@ class HipOps:
         check(self.L.dawn_interp_linear(_p(y), y.shape[0], y.shape[1], _p(xi), xi.numel(), _p(out), self._stream()),
               "dawn_interp_linear")
         return out
+
+    # ------------------------------------------------------------------ clip inputs (FD:327-350; csrc/clip_inputs.hip)
+    def bbox_mask_bounds(self, bbox6, size: int):
+        """(lt_x, lt_y, rb_x, rb_y) of FlowDiffusion.generate_bbox_mask's rectangle (host code, no GPU)."""
+        import ctypes as C
+        b, out = (C.c_float * 6)(*[float(v) for v in bbox6]), (C.c_int * 4)()
+        check(self.L.dawn_bbox_mask_bounds(b, int(size), out), "dawn_bbox_mask_bounds")
+        return tuple(out)
+
+    def face_loc_embed(self, bbox6, size: int, w1: Tensor, b1: Tensor, w2: Tensor, b2: Tensor, out: Optional[Tensor] = None) -> Tensor:
+        """Face_loc_Encoder(generate_bbox_mask(bbox)) for one sample in one launch: bbox6 = six host numbers, w1 (8,1,3,3) b1 (8)
+        w2 (16,8,3,3) b2 (16) -> (16, size/4, size/4).  `out`: 16 dense planes with a common stride (e.g. fea272[256:272])."""
+        import ctypes as C
+        for t, shape in ((w1, (8, 1, 3, 3)), (b1, (8,)), (w2, (16, 8, 3, 3)), (b2, (16,))):
+            _need(t.is_contiguous() and tuple(t.shape) == shape and t.dtype == torch.float32, f"face_loc_embed: contiguous fp32 weight of shape {shape}")
+        self._require(w1, b1, w2, b2, out)
+        s4 = size // 4
+        if out is None:
+            out = self.empty(16, s4, s4, like=w1)
+        _need(out.dtype == torch.float32 and tuple(out.shape) == (16, s4, s4) and out.stride(2) == 1 and out.stride(1) == s4,
+              "face_loc_embed: out (16, size/4, size/4) fp32 with dense planes")
+        b = (C.c_float * 6)(*[float(v) for v in bbox6])
+        check(self.L.dawn_face_loc_embed(b, int(size), _p(w1), _p(b1), _p(w2), _p(b2), _p(out), out.stride(0), self._stream()),
+              "dawn_face_loc_embed")
+        return out
+
+    def cond_rows(self, audio: Tensor, pose: Tensor, eye: Tensor, init_pose=None, init_eye=None, out: Optional[Tensor] = None) -> Tensor:
+        """FlowDiffusion.assemble_cond for one sample: audio (T, n_aud), pose (T, n_pose), eye (T, 2) rows (unit column stride; they
+        may be the column views of `out` they land in), init_pose / init_eye = host numbers or None (row 0) -> (T, n_aud + P + 2)."""
+        import ctypes as C
+        T, n_aud, n_pose = audio.shape[0], audio.shape[1], pose.shape[1]
+        for t, w in ((audio, n_aud), (pose, n_pose), (eye, 2)):
+            _need(t.dim() == 2 and tuple(t.shape) == (T, w) and t.dtype == torch.float32, "cond_rows: audio / pose / eye are fp32 (T, width) rows")
+        self._require(audio, pose, eye, out)
+        ip = None if init_pose is None else (C.c_float * len(init_pose))(*[float(v) for v in init_pose])
+        ie = None if init_eye is None else (C.c_float * 2)(*[float(v) for v in init_eye])
+        P = n_pose if init_pose is None else len(init_pose)
+        if out is None:
+            out = self.empty(T, n_aud + P + 2, like=audio)
+        _need(out.dtype == torch.float32 and out.dim() == 2 and out.shape[0] == T and out.shape[1] >= n_aud + P + 2 and out.stride(1) == 1,
+              "cond_rows: out fp32 (T, >= n_aud + P + 2) with unit column stride")
+        ld = lambda t: t.stride(0) if T > 1 else max(t.stride(0), t.shape[1])                   # noqa: E731
+        check(self.L.dawn_cond_rows(_p(audio), n_aud, ld(audio), _p(pose), n_pose, ld(pose), _p(eye), ld(eye), ip,
+                                    0 if init_pose is None else len(init_pose), ie, T, _p(out), ld(out), self._stream()), "dawn_cond_rows")
+        return out

@@ -50,7 +50,7 @@ class _LastOutput(dict):
 class VideoGenerator:
     def __init__(self, args, *, generator=None, frontend=None, config: Optional[dict] = None, device=None,
                  allow_random_weights: bool = False, deterministic: bool = True, hubert=None, pbnet=None,
-                 video_egress: str = "png", encoder_cmd=None, pbnet_via_c: bool = False):
+                 video_egress: str = "png", encoder_cmd=None, pbnet_via_c: bool = False, inputs_via_c: bool = False):
         """`allow_random_weights`: explicit opt-in (benches, tests) to run with the deterministic random-init denoiser
         when the configured checkpoint is absent; without it a missing checkpoint raises, as the reference's
         `torch.load` does (UVG:527).  `deterministic`: seed the sampler's counter-based noise with the config's
@@ -63,13 +63,16 @@ class VideoGenerator:
         `<output>/<name>/video/<name>.mp4` is appended; it reads raw I420 frames of the clip's size at 25 fps from stdin.  None: ffmpeg
         when there is one on PATH, else the frames go to `<name>.y4m` in the same directory.
         `pbnet_via_c`: stage 3 through the C-side stage (dawn_pose_blink_stage: windowed attention, any clip length) instead of the Python
-        orchestration of pbnet.py."""
+        orchestration of pbnet.py.
+        `inputs_via_c`: passed on as `FlowDiffusion.inputs_via_c` -- the face-location channels and the condition rows of a GPU clip from
+        the C-side clip-input stage (dawn_clip_inputs) instead of the torch plumbing."""
         if video_egress not in ("png", "yuv420p"):
             raise ValueError(f"video_egress must be 'png' or 'yuv420p', not {video_egress!r}")
         self.video_egress = video_egress
         self.encoder_cmd = shlex.split(encoder_cmd) if isinstance(encoder_cmd, str) else (list(encoder_cmd) if encoder_cmd else None)
         self.hubert = hubert              # hubert.HubertFeatures: stage 2 (process_audio, UVG:202-250) on the GPU (SURVEY 8f N3)
         self.pbnet_via_c = bool(pbnet_via_c)
+        self.inputs_via_c = bool(inputs_via_c)
         self.pbnet = pbnet                # (pose, blink) pbnet.PoseBlinkGenerator pair: stage 3 (generate_pose_blink, UVG:252-302; N4)
         self.allow_random_weights = bool(allow_random_weights) or bool(getattr(args, "allow_random_weights", False))
         self.deterministic = deterministic
@@ -114,6 +117,7 @@ class VideoGenerator:
         seed = self.video_config.get('random_seed')
         if seed is not None and self.deterministic:
             model.diffusion.noise_seed = int(seed)   # the reference never seeds torch; we can
+        model.inputs_via_c = self.inputs_via_c
         model.eval()
         return model
 

@@ -793,6 +793,92 @@ size_t dawn_pose_blink_workspace_bytes(const dawn_pbnet* pose, const dawn_pbnet*
 int dawn_pose_blink_stage(dawn_pbnet* pose, dawn_pbnet* blink, const float* audio, int ld_audio, long T, const float* init_pose6,
                           const float* init_blink2, const float* z_pose, const float* z_blink, float* dri_pose, int ld_pose,
                           float* dri_blink, int ld_blink, void* workspace, size_t workspace_bytes, void* stream);
+/* ---- the clip inputs of FlowDiffusion.sample_one_video (FD:327-350) that no other stage makes (csrc/clip_inputs.hip): the 16
+ * face-location channels of fea272 and the condition rows.  Once per clip, plain fp32, fixed summation order (bit-identical run to run).
+ * FD:182-201 + FD:39-50.  bbox6 = HOST floats [x_min, x_max, y_min, y_max, H_src, W_src] (one sample); size = the square image side
+ * (multiple of 4); w1 (8,1,3,3) b1 (8) w2 (16,8,3,3) b2 (16): the state_dict tensors as they are, on the device;
+ * out = 16 planes of (size/4, size/4), `plane` floats apart (so it can be rows 256..271 of fea272).
+ * The rectangle (FlowDiffusion.generate_bbox_mask, FD:187-193) is host arithmetic in fp32, every operation rounded on its own:
+ * b[0:2] = b[0:2] / b[4] * size, b[2:4] = b[2:4] / b[5] * size, lt = trunc(b[0]), trunc(b[2]), rb = trunc(b[1] + 1), trunc(b[3] + 1),
+ * truncation toward zero; a pixel is 1 where lt_y <= row <= rb_y and lt_x <= col <= rb_x (bounds outside the image are no error).
+ * The kernel takes the four ints by value and evaluates the mask analytically: mask, conv1 (3x3 / stride 2 / pad 1) + ReLU and conv2
+ * (the same) + ReLU in ONE launch, no mask and no intermediate tensor in memory; both convolutions pad with zeros; sums in the order
+ * (channel, ky, kx).  size < 4 or size % 4 != 0, a NULL pointer, plane < (size/4)^2, a non-finite bbox6 or bbox6[4] / bbox6[5] == 0:
+ * error return with a message, nothing launched. */
+int dawn_face_loc_embed(const float* bbox6, int size, const float* w1, const float* b1, const float* w2, const float* b2,
+                        float* out, long plane, void* stream);
+/* the four mask bounds alone, host code, for bindings and tests: lt_x, lt_y, rb_x, rb_y */
+int dawn_bbox_mask_bounds(const float* bbox6, int size, int* bounds4);
+/* FD:332-350.  audio (T, n_aud) rows ld_audio apart; pose (T, n_pose) rows ld_pose apart; eye (T, 2) rows ld_eye apart; all device.
+ * init_pose = n_init HOST floats or NULL (n_init = 0: row 0 of `pose`); init_eye = 2 HOST floats or NULL (row 0 of `eye`).
+ * P = n_init if init_pose else n_pose; n_pose must be P or P - 1 (then column P - 1 of the pose is init_pose[P - 1], FD:348-349).
+ * cond (T, n_aud + P + 2) rows ld_cond apart = [audio | pose - init_pose | eye - init_eye], each a single fp32 subtraction.
+ * Each input may be exactly the columns of `cond` it lands in (same address, ld == ld_cond: what dawn_hubert_features /
+ * dawn_pose_blink_stage leave when they wrote into `cond`; audio columns are then not touched at all); otherwise it must not overlap
+ * `cond`.  With a NULL init the rows after the first go in one launch and row 0 in a second one, so that in place no row reads a
+ * row 0 that was overwritten.  T < 1, a NULL pointer, a stride smaller than its width, n_pose not in {P, P - 1}, n_init > 16,
+ * non-finite host init values, any other overlap: error return with a message, nothing launched. */
+int dawn_cond_rows(const float* audio, int n_aud, int ld_audio, const float* pose, int n_pose, int ld_pose, const float* eye, int ld_eye,
+                   const float* init_pose, int n_init, const float* init_eye, long T, float* cond, int ld_cond, void* stream);
+/* ---- the same as a stage host (csrc/dawn_inputs.hip), the fifth beside dawn_ctx / dawn_decoder / dawn_hubert / dawn_pbnet and with
+ * their contract: opaque handle, device pointers by name, every launch on `stream`, no allocation, no synchronisation; an error return
+ * comes with a dawn_last_error message and nothing launched.  Weight names = FlowDiffusion's own state_dict keys:
+ *   "face_loc_emb.conv1.weight" (8,1,3,3)  "face_loc_emb.conv1.bias" (8)  "face_loc_emb.conv2.weight" (16,8,3,3)  "face_loc_emb.conv2.bias" (16)
+ * Reference quirk, kept: the reference never saves face_loc_emb (video_generator.py:58 stores the unet and the diffusion only), so no
+ * checkpoint holds these four tensors; the host supplies whatever its FlowDiffusion holds. */
+typedef struct dawn_inputs dawn_inputs;
+typedef struct dawn_inputs_cfg { int n_aud; int pose_dim; int eye_dim; } dawn_inputs_cfg;     /* 1024, 6 or 7, 2 */
+int  dawn_inputs_create(const dawn_inputs_cfg* cfg, const dawn_named_ptr* weights, int n_weights, dawn_inputs** out);
+void dawn_inputs_destroy(dawn_inputs* in);
+/* fea272 rows fea_ch - 16 .. fea_ch - 1 (256..271) from the bbox (dawn_face_loc_embed), and the cond rows (dawn_cond_rows with n_aud
+ * and P = pose_dim of the handle); fea272 = (fea_ch, size/4, size/4), whose first fea_ch - 16 planes dawn_decoder_encode writes.  Both
+ * calls are checked before the first launch. */
+int  dawn_clip_inputs(dawn_inputs* in, const float* bbox6, int size, float* fea272, int fea_ch,
+                      const float* audio, int ld_audio, const float* pose, int n_pose, int ld_pose, const float* eye, int ld_eye,
+                      const float* init_pose, int n_init, const float* init_eye, long T, float* cond, int ld_cond, void* stream);
+/* ---- one call from 16 kHz samples and a source image to frame bytes (VideoGenerator.generate UVG:304-399 without its files), built
+ * only from the entry points above, in this order: dawn_hubert_features -> two dawn_philox_normal draws (z_pose, z_blink) ->
+ * dawn_pose_blink_stage into the pose / eye columns of cond -> dawn_decoder_encode (fea_out = planes 0 .. fea_ch - 17 of fea272) ->
+ * dawn_clip_inputs in place on cond -> dawn_clip_prepare (and the null clip when cond_scale != 1) -> dawn_philox_normal (x_init) ->
+ * dawn_sampler_run_clip / dawn_sampler_run_ancestral_clip -> dawn_decode_clip / dawn_decode_clip_yuv420.
+ * Random draws, so that a host running the stages itself gets the same bits: x_init = dawn_philox_normal(3, T, 0, T, h w, seed, stream
+ * id 0); the sampler's steps use stream ids from 1 (dawn_sampler_run); z_pose = (1, T, 0, T, latent_dim, seed, 0xFFFFFFFE) and z_blink
+ * the same with 0xFFFFFFFF: (1, T, latent_dim) each.
+ * T is the caller's: min(max_n_frames, num_frames) as UVG:329 with num_frames from dawn_hubert_segments; T above num_frames is refused.
+ * All pointers are device pointers except the ones marked HOST.  The five handles must belong together (the caller's to guarantee:
+ * only pointers travel): hubert hidden = pbnet audio_dim = inputs n_aud; unet cond columns = [n_aud | pose_dim | 2], unet fea_ch =
+ * decoder bottleneck width + 16; decoder n_down = 2 (h = w = H / 4). */
+enum { DAWN_FRAMES_RGB = 0, DAWN_FRAMES_YUV420 = 1 };
+typedef struct dawn_generate_args {
+    dawn_hubert* hubert; dawn_pbnet* pose; dawn_pbnet* blink; dawn_decoder* decoder; dawn_inputs* inputs; dawn_ctx* unet;
+    const float* samples; long n_samples;            /* raw fp32 16 kHz samples */
+    const float* img3; int H;                        /* source image (3, H, H) planar in [0, 1] */
+    int fea_ch;                                      /* the unet's fea_ch (272) */
+    const float* bbox6;                              /* HOST, as dawn_face_loc_embed */
+    const float* init_pose; const float* init_eye;   /* HOST or NULL, as dawn_cond_rows (n_init values / 2 values) */
+    int n_init;
+    int latent_dim;                                  /* the PBnets' latent width (256), a multiple of 4 */
+    const float* init_pose6; const float* init_blink2;   /* HOST, as dawn_pose_blink_stage */
+    long T; int S;                                   /* frames; sampler steps */
+    float cond_scale;
+    const dawn_ddim_step* ddim_steps;                /* HOST, S entries: DDIM -- or */
+    const dawn_ancestral_step* ancestral_steps;      /* HOST, S entries: ancestral; exactly one of the two tables */
+    const dawn_clip_mode* clip;                      /* HOST or NULL = {DAWN_CLIP_DYNAMIC, 0.9} */
+    uint64_t seed;
+    int format; int bgr; int chunk;                  /* DAWN_FRAMES_*; bgr: RGB frames only; frames decoded `chunk` at a time */
+    const double* mean3;                             /* HOST or NULL, as dawn_decode_clip */
+    unsigned char* frames_out;                       /* (T,H,H,3) or (T, 3 H H / 2) uint8: clip_bytes of dawn_generate_bytes */
+    float* latent_out;                               /* optional (3,T,h,w): the sampler's latent */
+    float* cond_out;                                 /* optional (T, n_aud + pose_dim + 2) dense: the condition rows */
+} dawn_generate_args;
+/* host code: *clip_bytes = the bytes of frames_out, *workspace_bytes = cond, a zero row (guided), fea272, the audio rows, z_pose /
+ * z_blink, x_init and the latent, the decoder skips, the clip tables (twice when guided) -- each rounded up to 256 bytes; cond and the
+ * latent only where cond_out / latent_out are NULL -- plus the LARGEST of the stages' own workspaces (the stages run one after the
+ * other).  An argument dawn_generate_clip would refuse: the same error return, both sizes untouched. */
+int dawn_generate_bytes(const dawn_generate_args* args, size_t* clip_bytes, size_t* workspace_bytes);
+/* every argument is checked before the first launch: a refusal (NULL handle or pointer, T above what the audio yields, a short
+ * workspace, ...) comes with a message and nothing launched.  latent_out / cond_out / frames_out must not overlap the workspace. */
+int dawn_generate_clip(const dawn_generate_args* args, void* workspace, size_t workspace_bytes, void* stream);
 /* after a stream synchronise: (kind, algorithmic flops, algorithmic bytes, ms) per conv launch recorded under
  * DAWN_OPT_PROFILE; kind 0 = split 3x3, 1 = split 1x1, 2 = fp32 MFMA; returns the number of entries (and clears them) */
 int dawn_ctx_profile_read(dawn_ctx* ctx, double* out4, int max_entries);
