@@ -560,8 +560,8 @@ bool try_launch_bf16_v2(const dawn_conv_desc& d, long M, hipStream_t s, bool nin
     else { if (WT != W || TR % H != 0) return false; nf = TR / H; TR = H; if (d.F % nf != 0) return false; }
     const int P = nf * (TR + 2) * (WT + 2);
     const int P16 = (P + 15) / 16 * 16;
-    const bool timing = ((policy_of(d) >> 16) & 15) == 8;
-    const bool k32 = !nine && (policy_of(d) & 0x1000000);
+    const bool timing = policy_variant(d) == 8;
+    const bool k32 = !nine && (policy_of(d) & DAWN_POLICY_MFMA_K32);
     // (the 36-segment instantiation exists for the shipped form only: 16 x 16 x 32, six cross terms)
     const bool big_patch = P16 > 448;
     if (P16 > 576 || (big_patch && !k32)) return false;
@@ -569,11 +569,11 @@ bool try_launch_bf16_v2(const dawn_conv_desc& d, long M, hipStream_t s, bool nin
     if (lds > 160 * 1024) return false;
     if (dry) return true;
     const int nwg = (int)(M / BM) * (d.N / BN);
-    const int remap = ((policy_of(d) & 4) && nwg >= 64 && H * W >= 1024) ? 1 : 0;
-    // start delay of the second resident workgroup set in units of ~8k cycles (policy bits 20..23; default 0 = none): in
+    const int remap = ((policy_of(d) & DAWN_POLICY_XCD_ORDER) && nwg >= 64 && H * W >= 1024) ? 1 : 0;
+    // start delay of the second resident workgroup set in units of ~8k cycles (DAWN_POLICY_STAGGER; default 0 = none): in
     // isolation it takes 8..11 % off the 64-input-channel launches (354 -> 316..328 us, profiles/r2_conv_stagger.txt) and nothing
     // off deeper K; inside an evaluation, next to the side stream's kernels, it changes nothing (385.4 vs 384.5 us): off
-    const int stagger = nwg >= 1024 ? ((policy_of(d) >> 20) & 15) : 0;
+    const int stagger = nwg >= 1024 ? policy_stagger(policy_of(d)) : 0;
 #define LAUNCH_V2K(NTV, ABLV, K32V)                                                                                   \
     do {                                                                                                              \
         (void)hipFuncSetAttribute((const void*)conv3x3_bf16_v2_kernel<WN, NTV, ABLV, K32V>,                           \
@@ -592,13 +592,13 @@ bool try_launch_bf16_v2(const dawn_conv_desc& d, long M, hipStream_t s, bool nin
         (void)hipFuncSetAttribute((const void*)conv3x3_bf16_v2_kernel<WN, 6, 0, true, 36>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         hipLaunchKernelGGL((conv3x3_bf16_v2_kernel<WN, 6, 0, true, 36>), dim3(nwg), dim3(256 * WN), lds, s, d, remap, TR, nf, P16, WT, stagger);
     }
-    else if (policy_of(d) & 0x1000000) LAUNCH_V2K(6, 0, true);
+    else if (policy_of(d) & DAWN_POLICY_MFMA_K32) LAUNCH_V2K(6, 0, true);
 #ifdef DAWN_ABLATION
     else if (timing) LAUNCH_V2(6, 8);
-    else if (((policy_of(d) >> 16) & 15) == 1) LAUNCH_V2(6, 1);
-    else if (((policy_of(d) >> 16) & 15) == 2) LAUNCH_V2(6, 2);
-    else if (((policy_of(d) >> 16) & 15) == 4) LAUNCH_V2(6, 4);
-    else if (((policy_of(d) >> 16) & 15) == 7) LAUNCH_V2(6, 7);
+    else if (policy_variant(d) == 1) LAUNCH_V2(6, 1);
+    else if (policy_variant(d) == 2) LAUNCH_V2(6, 2);
+    else if (policy_variant(d) == 4) LAUNCH_V2(6, 4);
+    else if (policy_variant(d) == 7) LAUNCH_V2(6, 7);
 #endif
     else LAUNCH_V2(6, 0);
 #undef LAUNCH_V2

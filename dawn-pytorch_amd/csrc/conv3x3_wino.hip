@@ -222,10 +222,10 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wino_kernel(const dawn_conv_de
     }
     const int t_end = ntiles;
     if (t_begin >= t_end) return;
-    // start delay (policy bits 20..23, A/B; conv3x3_wino4.hip): `stagger` units of ~1 us times ((workgroup / 8) & 3) de-phase the
+    // start delay (DAWN_POLICY_STAGGER, A/B; conv3x3_wino4.hip): `stagger` units of ~1 us times ((workgroup / 8) & 3) de-phase the
     // workgroups of the persistent launch, whose patch fetches and output stores otherwise hit HBM in lockstep bursts
     for (int i = 0; i < (stagger & 0xff) * ((blockIdx.x >> 3) & 3); ++i) __builtin_amdgcn_s_sleep(32);
-    // bit 8 (policy bit 0x20000000): the tiles in REVERSE order -- last frame first.  The kernel that wrote this conv's input wrote it front to
+    // bit 8 (DAWN_POLICY_WINO_REVERSE): the tiles in REVERSE order -- last frame first.  The kernel that wrote this conv's input wrote it front to
     // back, so its END is what the memory-side cache still holds: read back to front, the most recently written part comes first
     const bool rev = (stagger & 0x100) != 0;
 
@@ -639,7 +639,7 @@ static bool wino_geometry(int F, int H, int W, int C0, int C1, int N, wino_geom&
 }
 
 /* 1 when a 3x3 / stride 1 / pad 1 conv of this shape (F frames of H x W pixels, C0 + C1 input channels, N output channels) runs in the
- * Winograd form once dawn_conv_desc.w_wino is supplied and policy bit 0x2000000 is set (the shipped default has it) */
+ * Winograd form once dawn_conv_desc.w_wino is supplied and DAWN_POLICY_WINO2 is set (the shipped default has it) */
 extern "C" int dawn_conv3x3_wino_ok(int F, int H, int W, int C0, int C1, int N) {
     wino_geom g;
     return wino_geometry(F, H, W, C0, C1, N, g) ? 1 : 0;
@@ -648,7 +648,7 @@ extern "C" int dawn_conv3x3_wino_ok(int F, int H, int W, int C0, int C1, int N) 
 // host-side geometry test + launch; 0 = the shape does not fit (the caller falls back to the direct split kernel)
 int dawn_conv3x3_wino_try(const dawn_conv_desc& d, long M, int policy, hipStream_t s, int* nrows, int dry /* 1: decide only, launch nothing */) {
     (void)M;
-    if ((policy & 0x4000000) && d.C0 + d.C1 < 128) return 0;      // per-shape policy bit: short-K convs on the direct kernel
+    if ((policy & DAWN_POLICY_WINO2_DEEP_ONLY) && d.C0 + d.C1 < 128) return 0;      // per-shape policy bit: short-K convs on the direct kernel
     if (!d.w_wino || d.tr || d.KH != 3 || d.KW != 3 || d.stride != 1 || d.pad != 1 || d.mode != 0) return 0;
     if ((d.ld0 & 3) || (d.in1 && (d.ld1 & 3)) || (d.ld_out & 3) || (d.res && (d.ld_res & 3))) return 0;
     wino_geom g;
@@ -659,9 +659,9 @@ int dawn_conv3x3_wino_try(const dawn_conv_desc& d, long M, int policy, hipStream
     const int ntiles = g.ntiles, TR = g.TR, nf = g.nf, PI = g.PI, RAWB = g.RAWB;
     const size_t lds = g.lds;
     const int grid = ntiles < wino_ncu() ? ntiles : wino_ncu();
-    const int sbits = (policy >> 20) & 15;
+    const int sbits = (policy & DAWN_POLICY_STAGGER_MASK) / DAWN_POLICY_STAGGER(1);
     const int stagger = (ntiles >= 4 * grid ? (sbits == 15 ? 0 : sbits) : 0)   // (A/B knob, default none)
-                        | ((policy & 0x20000000) ? 0x100 : 0);                  // reverse tile order (see the kernel)
+                        | ((policy & DAWN_POLICY_WINO_REVERSE) ? 0x100 : 0);                  // reverse tile order (see the kernel)
 #define WINO_LAUNCH(A)                                                                                                      \
     do {                                                                                                                    \
         (void)hipFuncSetAttribute((const void*)conv3x3_wino_kernel<A>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \

@@ -165,10 +165,10 @@ __global__ __launch_bounds__(NT4, 1) void conv3x3_wino4_kernel(const dawn_conv_d
     }
     const int t_end = ntiles;
     if (t_begin >= t_end) return;
-    // start delay (policy bits 20..23, A/B): the workgroups of a persistent launch run in lockstep, so their patch fetches and epilogue
+    // start delay (DAWN_POLICY_STAGGER, A/B): the workgroups of a persistent launch run in lockstep, so their patch fetches and epilogue
     // stores hit HBM in bursts; `stagger` units of ~1 us times ((workgroup / 8) & 3) de-phase them in four groups per XCD
     for (int i = 0; i < (stagger & 7) * ((blockIdx.x >> 3) & ((stagger & 8) ? 7 : 3)); ++i) __builtin_amdgcn_s_sleep(32);   // (bit 3: eight phases)
-    // bit 8 (policy bit 0x20000000): the tiles in REVERSE order -- last frame first.  The kernel that wrote this conv's input wrote it front to
+    // bit 8 (DAWN_POLICY_WINO_REVERSE): the tiles in REVERSE order -- last frame first.  The kernel that wrote this conv's input wrote it front to
     // back, so its END is what the memory-side cache still holds: read back to front, the most recently written part comes first
     const bool rev = (stagger & 0x100) != 0;
 
@@ -606,7 +606,7 @@ int dawn_conv3x3_wino4_try(const dawn_conv_desc& d, long M, int policy, hipStrea
     // most -- 64 input channels at the 64-pixel-wide latent (-9 %), up to 128 at the 32-pixel-wide one (-3.5..-7 %); slower at 128 / 256 input
     // channels there (+7 / +10 %).  Policy bit 0x10000000 (tests, A/B) takes it wherever the geometry fits
     const int cin_ = d.C0 + d.C1;
-    if (!(policy & 0x10000000) && !((d.Wi == 64 && cin_ == 64) || (d.Wi == 32 && cin_ <= 128))) return 0;
+    if (!(policy & DAWN_POLICY_WINO4_ALL_SHAPES) && !((d.Wi == 64 && cin_ == 64) || (d.Wi == 32 && cin_ <= 128))) return 0;
     if (!d.w_wino4 || d.tr || d.KH != 3 || d.KW != 3 || d.stride != 1 || d.pad != 1 || d.mode != 0) return 0;
     if ((d.ld0 & 3) || (d.in1 && (d.ld1 & 3)) || (d.ld_out & 3) || (d.res && (d.ld_res & 3))) return 0;
     if (!wino4_geometry(d.F, d.Hi, d.Wi, d.C0, d.C1, d.N)) return 0;
@@ -614,10 +614,10 @@ int dawn_conv3x3_wino4_try(const dawn_conv_desc& d, long M, int policy, hipStrea
     const int ntiles = (int)(M / 256) * (d.N / 64);
     const int grid = ntiles < wino4_ncu() ? ntiles : wino4_ncu();
     // start stagger: 4 units by default where a workgroup walks >= 4 tiles (-5 % at the shipped shape, profiles/r5_wino4_stagger.txt);
-    // policy bits 20..23 override it (15 = none)
-    const int sbits = (policy >> 20) & 15;
+    // DAWN_POLICY_STAGGER overrides it (15 = none)
+    const int sbits = (policy & DAWN_POLICY_STAGGER_MASK) / DAWN_POLICY_STAGGER(1);
     const int stagger = ntiles >= 4 * grid ? (sbits == 15 ? 0 : (sbits ? sbits : 4)) : 0;
-    const int rev8 = (policy & 0x20000000) ? 0x100 : 0;                        // reverse tile order (see the kernel)
+    const int rev8 = (policy & DAWN_POLICY_WINO_REVERSE) ? 0x100 : 0;                        // reverse tile order (see the kernel)
     const int W = d.Wi, RAWB = (256 / W + 2) * (W * 64 + 128);
     const size_t lds = (size_t)2 * DT4 + (size_t)2 * RAWB + 1024 + 256;
 #define W4_LAUNCH(WV, A)                                                                                                      \

@@ -27,42 +27,8 @@
 
 namespace {
 
-// Tuning policy (measured on MI355X, profiles/r1_d_conv_variants.txt, r1_j_conv_glds.txt): bit0 BK=32 tiles for
-// deep-K GEMMs on the register-staged path (K >= 4096, N > 64: +6 %), bit1 256x64 tile for N <= 64 (no gain:
-// off), bit2 XCD-contiguous tile order for multi-tap convs on >= 32x32 frames (+7..17 %; hurts pure streaming
-// 1x1 GEMMs, so not used there), bit3 direct-to-LDS staging for prologue-free GEMMs (+5..15 %; BK=32 there when
-// K >= 2304 and N >= 256), 0x80 force BK=32 on that path, 0x100 its 3-stage counted-vmcnt pipeline (no gain:
-// the loop is bound by the per-CU fetch rate, not by load latency), 0x800 LDS-halo kernel for prologue-free
-// 3x3/s1/p1 convs whose tile geometry fits (+5..19 %, profiles/r1_l_conv_halo.txt), 0x1000 split-operand bf16
-// MFMA version of that kernel when the caller supplies w_bf3 (6 cross terms; 0x2000: all 9), 0x4000 its second
-// generation (conv3x3_bf16_v2_kernel: +5..20 %, profiles/r1_n_conv_bf16.txt), 0x10/0x20 fp32-kernel perf ablations,
-// (8 << 16) the s_memtime build of the split kernel, 0x400 -- ONLY in the experimental build of hipbuild.py sktiming (-DDAWN_WITH_STREAMK; the
-// shipped library ignores the bit since round 4) -- the persistent stream-K 3x3 kernel (tools/ubench/conv3x3_sk.hip) when the caller
-// supplies dawn_conv_desc.sk_ws (0x200: without the half-tile offset between co-resident workgroups; 0x40 + bits 16..17: issue-priority
-// alternation between them; bits 20..23 there: leave n/16 of the resident slots to a concurrent stream).  NOT in the shipped
-// default: in isolation it takes 6..16 % off the 128..512-channel levels, inside the benchmark it is 3..5 % slower end to end --
-// the chip is power-limited in these kernels (profiles/r3_conv_power_by_data.txt, r3_mfma_power_ubench.txt), so cycles saved by
-// the schedule come back as a lower clock for everything that follows.
-// 0x1000000 (shipped): conv3x3_bf16_v2_kernel on v_mfma_f32_16x16x32_bf16 (two cross terms per instruction).
-// 0x2000000: the Winograd F(2x2,3x3) form of the split 3x3 conv (conv3x3_wino.hip) where the caller supplies dawn_conv_desc.w_wino and
-// the geometry fits (image width <= 64, even sides): 2.25x fewer matrix-pipe flops.
-// 0x4000000 (A/B, round 5): per-shape choice -- with it, convs of fewer than 128 input channels (K = 576: 4 chunks per tile, the Winograd
-// epilogue is a fifth of such a tile) take the direct split kernel even where the Winograd form fits.
-// 0x8000000 (opt-in, round 5): the Winograd F(4x4,3x3) form (conv3x3_wino4.hip) where dawn_conv_desc.w_wino4 is supplied and the geometry
-// fits (image width 64 / 32): 4x fewer matrix-pipe flops than the direct form, weights streamed at 2.25x the F(2x2) rate.  By itself the bit
-// takes the F(4x4) form only for the shapes it measured faster on (64 input channels at the 64-pixel-wide latent, up to 128 at the 32-pixel-wide one); with 0x10000000 wherever it fits.
-// 0x20000000 (shipped, round 5): both Winograd kernels walk their tiles back to front (last frame first).  Every kernel of an evaluation writes
-// its output front to back, so the END of a conv's input is what the memory-side cache still holds when the conv starts; front to back the
-// conv's own traffic evicts that part before reaching it.  Bit-identical outputs (tests: test_conv_wino_reverse_tile_order); +0.3..0.6 %
-// frames/s in the benchmark, alternating on one box (profiles/r5_ab_wino_reverse_order.txt).
-// The policy travels in dawn_conv_desc.policy (0 = the shipped default): there is no process-global tuning state.  The
-// perf-ablation kernels (0x10 / 0x20: wrong results by design; (n << 16): ablated / s_memtime-instrumented builds of the
-// split 3x3 kernel; 0x40000000, read from dawn_conv_desc.policy directly: the row-stationary GEMM kernels fetch their rows in a
-// line-coalesced pattern -- the right bytes in the wrong lanes, profiles/r5_row_fetch_pattern_ablation.txt) exist only in
-// -DDAWN_ABLATION builds (hipbuild.py ablation), never in the shipped library.
-// 0x80000 (A/B, round 6; read from dawn_conv_desc.policy directly, same bits out): the split 1x1 tile GEMM deals its tiles to the XCDs in
-// launch order instead of one contiguous range of row panels per XCD (see gemm1x1_bf16_kernel).
-// (the constants and policy_of: conv_split.h)
+// Which kernel runs is decided per call by dawn_conv_desc.policy (0 = the shipped default; no process-global tuning state): the DAWN_POLICY_*
+// table of include/dawn_hip.h, read through policy_of() and its companions in conv_split.h (measurements beyond the table's line: DESIGN.md).
 
 struct RowInfo {
     long rowoff;  // (f*Hi + yb)*Wi + xb : input pixel index of tap (0,0) (may point outside; bounds via yb/xb)
@@ -864,7 +830,7 @@ bool try_launch_halo(const dawn_conv_desc& d, long M, hipStream_t s) {
     const size_t lds = ((size_t)2 * P16 * 16 + (size_t)2 * 4 * BN * 4) * sizeof(float);
     if (lds > 160 * 1024) return false;
     const int nwg = (int)(M / BM) * dawn_cdiv(d.N, BN);
-    const int remap = ((policy_of(d) & 4) && nwg >= 64 && H * W >= 1024) ? 1 : 0;
+    const int remap = ((policy_of(d) & DAWN_POLICY_XCD_ORDER) && nwg >= 64 && H * W >= 1024) ? 1 : 0;
     if (lds > 65536)
         (void)hipFuncSetAttribute((const void*)conv3x3_halo_kernel<BN, WN>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)lds);
@@ -1112,7 +1078,7 @@ bool try_launch_halo_bf16(const dawn_conv_desc& d, long M, hipStream_t s, bool n
     if (lds > 160 * 1024) return false;
     if (dry) return true;
     const int nwg = (int)(M / BM) * dawn_cdiv(d.N, BN);
-    const int remap = ((policy_of(d) & 4) && nwg >= 64 && H * W >= 1024) ? 1 : 0;
+    const int remap = ((policy_of(d) & DAWN_POLICY_XCD_ORDER) && nwg >= 64 && H * W >= 1024) ? 1 : 0;
     if (d.gn_rows) *d.gn_rows = nwg;   // rows of gn_part this launch writes
     if (nine) {
         (void)hipFuncSetAttribute((const void*)conv3x3_halo_bf16_kernel<BN, WN, 9>, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1131,7 +1097,7 @@ void launch_pro(const dawn_conv_desc& d, long M, hipStream_t s) {
     const int nMt = dawn_cdiv(M, BM), nNt = dawn_cdiv(d.N, BN);
     const int z = d.mode == 1 ? 4 : 1;
     const int nwg = nMt * nNt;
-    const int remap = ((policy_of(d) & 4) && nwg >= 64 && d.KH * d.KW > 1 && d.Hi * d.Wi >= 1024) ? 1 : 0;
+    const int remap = ((policy_of(d) & DAWN_POLICY_XCD_ORDER) && nwg >= 64 && d.KH * d.KW > 1 && d.Hi * d.Wi >= 1024) ? 1 : 0;
     if (d.gn_rows) *d.gn_rows = nwg;   // rows of gn_part this launch writes
     hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, BK, WM, WN, PRO>), dim3(nwg, 1, z), dim3(256), 0, s, d, remap);
 }
@@ -1139,24 +1105,25 @@ void launch_pro(const dawn_conv_desc& d, long M, hipStream_t s) {
 template <int BM, int BN, int BK, int WM, int WN>
 void launch(const dawn_conv_desc& d, long M, hipStream_t s) {
 #ifdef DAWN_ABLATION
-    if (policy_of(d) & 0x30) {   // perf ablations only (wrong results): 0x10 no re-staging, 0x20 also no barrier
+    if (policy_of(d) & (DAWN_POLICY_ABL_NO_RESTAGE | DAWN_POLICY_ABL_NO_BARRIER)) {   // perf ablations only (wrong results)
         const int nMt = dawn_cdiv(M, BM), nNt = dawn_cdiv(d.N, BN);
         const int nwg = nMt * nNt;
         if (d.gn_rows) *d.gn_rows = nwg;   // rows of gn_part this launch writes
-        if (policy_of(d) & 0x20)
+        if (policy_of(d) & DAWN_POLICY_ABL_NO_BARRIER)
             hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, BK, WM, WN, 0, 2>), dim3(nwg, 1, 1), dim3(256), 0, s, d, 0);
         else
             hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, BK, WM, WN, 0, 1>), dim3(nwg, 1, 1), dim3(256), 0, s, d, 0);
         return;
     }
 #endif
-    if ((policy_of(d) & 8) && BM == 128 && !d.ch_a && !d.pro_act && !d.pro_add && !d.row_mean) {
+    if ((policy_of(d) & DAWN_POLICY_GLDS) && BM == 128 && !d.ch_a && !d.pro_act && !d.pro_add && !d.row_mean) {
         const int nMt = dawn_cdiv(M, BM), nNt = dawn_cdiv(d.N, BN);
         const int nwg = nMt * nNt;
-        const int remap = ((policy_of(d) & 4) && nwg >= 64 && d.KH * d.KW > 1 && d.Hi * d.Wi >= 1024) ? 1 : 0;
+        const int remap = ((policy_of(d) & DAWN_POLICY_XCD_ORDER) && nwg >= 64 && d.KH * d.KW > 1 && d.Hi * d.Wi >= 1024) ? 1 : 0;
         const dim3 grid(nwg, 1, d.mode == 1 ? 4 : 1);
         const bool deep = d.KH * d.KW * (d.C0 + d.C1) >= 2304 && d.N >= 256;
-        if (BN == 64 && M >= 65536 && ((policy_of(d) & 0x200) || (d.KH * d.KW > 1 && d.C0 + d.C1 <= 64 && !(policy_of(d) & 0x400)))) {
+        if (BN == 64 && M >= 65536 && ((policy_of(d) & DAWN_POLICY_GLDS_TILE256) ||
+                                       (d.KH * d.KW > 1 && d.C0 + d.C1 <= 64 && !(policy_of(d) & DAWN_POLICY_GLDS_NO_TILE256)))) {
             // 256 x 64 tile (weights amortised over 2x the rows): +7 % on the K=576 3x3 convs, not on 1x1 / K>=1152
             const int nwg2 = dawn_cdiv(M, 256);
             if (d.gn_rows) *d.gn_rows = nwg2;   // rows of gn_part this launch writes
@@ -1166,10 +1133,10 @@ void launch(const dawn_conv_desc& d, long M, hipStream_t s) {
         }
         if (d.gn_rows) *d.gn_rows = nwg;   // rows of gn_part this launch writes
         const bool fold = d.KH * d.KW * (d.C0 + d.C1) >= GLDS_FOLD_MIN_K;     // two-level K accumulation (see the kernel)
-        if (((policy_of(d) & 0x80) || deep) && d.C0 % 32 == 0 && d.C1 % 32 == 0) {
+        if (((policy_of(d) & DAWN_POLICY_GLDS_BK32) || deep) && d.C0 % 32 == 0 && d.C1 % 32 == 0) {
             if (fold) hipLaunchKernelGGL((conv_gemm_glds_kernel<BN, 2, 32, 2, true>), grid, dim3(256), 0, s, d, remap);
             else hipLaunchKernelGGL((conv_gemm_glds_kernel<BN, 2, 32>), grid, dim3(256), 0, s, d, remap);
-        } else if (policy_of(d) & 0x100) {
+        } else if (policy_of(d) & DAWN_POLICY_GLDS_STAGES3) {
             hipLaunchKernelGGL((conv_gemm_glds_kernel<BN, 3, 16>), grid, dim3(256), 0, s, d, remap);
         } else if (fold) {
             hipLaunchKernelGGL((conv_gemm_glds_kernel<BN, 2, 16, 2, true>), grid, dim3(256), 0, s, d, remap);
@@ -1272,8 +1239,8 @@ static bool gemm1x1_split_layout_ok(const dawn_conv_desc& d) {
 // dawn_gemm1x1_form.  With ln_eps > 0 only the row-stationary / row-accumulator kernels qualify (they hold whole rows).
 static int split1x1_form(const dawn_conv_desc& d, long M) {
     const int p = policy_of(d);
-    if (!(p & 0x1000) || !d.w_bf3) return DAWN_SPLIT1X1_NONE;
-    const bool rows_ok = !(p & 0x20000);             // policy bit 0x20000 (A/B only): the tiled kernel for every 1x1 shape
+    if (!(p & DAWN_POLICY_SPLIT) || !d.w_bf3) return DAWN_SPLIT1X1_NONE;
+    const bool rows_ok = !(p & DAWN_POLICY_NO_ROW_KERNELS);   // (A/B only: the tiled kernel for every 1x1 shape)
     const bool proj = d.mode == 0 && d.KH == 1 && d.KW == 1 && d.stride == 1 && d.pad == 0 && !d.ch_a && !d.pro_act && !d.pro_add;
     if (d.ln_eps > 0.f) {
         if (!proj || d.row_mean || d.row_rstd || !gemm1x1_split_layout_ok(d) || !rows_ok) return DAWN_SPLIT1X1_NONE;
@@ -1312,28 +1279,40 @@ extern "C" int dawn_conv_gemm_nblocks(long M, int N) {
 
 // the split-operand 3x3 family serves this descriptor (the condition dawn_conv_gemm dispatches on)
 static bool conv3x3_split_path(const dawn_conv_desc& d) {
-    return (policy_of(d) & 0x1000) && d.w_bf3 && d.mode == 0 && d.KH == 3 && d.KW == 3 && d.stride == 1 && d.pad == 1 && d.Ho == d.Hi &&
+    return (policy_of(d) & DAWN_POLICY_SPLIT) && d.w_bf3 && d.mode == 0 && d.KH == 3 && d.KW == 3 && d.stride == 1 && d.pad == 1 && d.Ho == d.Hi &&
            d.Wo == d.Wi && !d.ch_a && !d.pro_act && !d.pro_add && !d.row_mean;
 }
 
-/* Which form of the 3x3 conv dawn_conv_gemm would run for this descriptor (host code, launches nothing): 2 = Winograd F(4x4,3x3),
- * 1 = Winograd F(2x2,3x3), 0 = anything else (direct split kernel, fp32 kernels, not a 3x3 conv).  The SAME decision code as the
- * launch -- for profiling labels and tests, instead of mirroring the policy bits and per-shape gates in the caller. */
-extern "C" int dawn_conv3x3_form(const dawn_conv_desc* dp) {
-    if (!dp) return 0;
-    const dawn_conv_desc& d = *dp;
-    if (!conv3x3_split_path(d) || (policy_of(d) & 0x2000)) return 0;
-    const long M = (long)d.F * d.Ho * d.Wo;
-    if ((policy_of(d) & 0x8000000) && d.w_wino4 && dawn_conv3x3_wino4_try(d, M, policy_of(d), nullptr, nullptr, 1)) return 2;
-    if ((policy_of(d) & 0x2000000) && d.w_wino && dawn_conv3x3_wino_try(d, M, policy_of(d), nullptr, nullptr, 1)) return 1;
+/* The transformed forms of the split 3x3 conv, in dawn_conv_gemm's order: Winograd F(4x4,3x3), Winograd F(2x2,3x3) and -- in the
+ * experimental stream-K build only -- the persistent kernel.  Launches the first that takes the descriptor (dry: launches nothing) and
+ * answers which: 2 = F(4x4), 1 = F(2x2), 3 = stream-K, 0 = none of them (nine cross terms exist in the direct kernels only).
+ * *nrows receives the gn_part rows of the launch.  THE routing of dawn_conv_gemm, dawn_conv3x3_form and dawn_conv3x3_direct_form. */
+static int conv3x3_transformed(const dawn_conv_desc& d, long M, hipStream_t s, int* nrows, bool dry) {
+    const int p = policy_of(d);
+    if (p & DAWN_POLICY_NINE_TERMS) return 0;
+    if ((p & DAWN_POLICY_WINO4) && d.w_wino4 && dawn_conv3x3_wino4_try(d, M, p, s, nrows, dry)) return 2;
+    if ((p & DAWN_POLICY_WINO2) && d.w_wino && dawn_conv3x3_wino_try(d, M, p, s, nrows, dry)) return 1;
+#ifdef DAWN_WITH_STREAMK
+    // (the stream-K kernel has no dry form: asked dry, 3 says that it MAY take the descriptor)
+    if ((p & DAWN_POLICY_STREAMK) && d.sk_ws && (dry || dawn_conv3x3_sk_try(d, M, p, s, nrows))) return 3;
+#endif
     return 0;
+}
+
+/* Which form of the 3x3 conv dawn_conv_gemm would run for this descriptor (host code, launches nothing): 2 = Winograd F(4x4,3x3),
+ * 1 = Winograd F(2x2,3x3), 0 = anything else (direct split kernel, fp32 kernels, not a 3x3 conv).  The launch's own decision code
+ * (conv3x3_transformed) -- for profiling labels and tests, instead of mirroring the policy bits and per-shape gates in the caller. */
+extern "C" int dawn_conv3x3_form(const dawn_conv_desc* dp) {
+    if (!dp || !conv3x3_split_path(*dp)) return 0;
+    const int form = conv3x3_transformed(*dp, (long)dp->F * dp->Ho * dp->Wo, nullptr, nullptr, true);
+    return form <= 2 ? form : 0;
 }
 
 /* The direct split-operand 3x3 kernels, in dawn_conv_gemm's order: conv3x3_bf16_v2_kernel with 256 x 64 or 256 x 128 tiles, then the v1 halo
  * kernel.  Launches the first that takes the descriptor (dry: launches nothing) and answers which (DAWN_DIRECT3X3_* of include/dawn_hip.h;
  * NONE: the fp32 kernels are next).  THE routing of dawn_conv_gemm and of dawn_conv3x3_direct_form. */
 static int conv3x3_direct(const dawn_conv_desc& d, long M, hipStream_t s, bool nine, bool dry) {
-    if (policy_of(d) & 0x4000) {           // v2 structure (row-of-taps weight stages, register-prefetched patch)
+    if (policy_of(d) & DAWN_POLICY_SPLIT_V2) {   // v2 structure (row-of-taps weight stages, register-prefetched patch)
         // 256 x 128 tiles run one 8-wave workgroup per CU: when they occupy at most half of the 256 CUs (M = 12,800 rows,
         // N = 256: 100 tiles), 256 x 64 tiles put one 4-wave workgroup on twice as many CUs and the launch takes
         // 0.67x the time (measured 520 -> 349 us at K = 9216, 142 -> 97 us at K = 2304; with 129..256 tiles the same
@@ -1360,12 +1339,10 @@ extern "C" int dawn_conv3x3_direct_form(const dawn_conv_desc* dp) {
     if (d.C0 % 16 != 0 || d.C1 % 16 != 0 || d.C0 + d.C1 == 0 || (d.ld0 % 4) || (d.in1 && (d.ld1 % 4)) || d.border)
         return DAWN_DIRECT3X3_NONE;   // dawn_conv_gemm rejects these
     const long M = (long)d.F * d.Ho * d.Wo;
-    if (M <= 0 || d.N <= 0 || !conv3x3_split_path(d) || split1x1_form(d, M) != DAWN_SPLIT1X1_NONE || dawn_conv3x3_form(dp) != 0)
+    if (M <= 0 || d.N <= 0 || !conv3x3_split_path(d) || split1x1_form(d, M) != DAWN_SPLIT1X1_NONE ||
+        conv3x3_transformed(d, M, nullptr, nullptr, true) != 0)
         return DAWN_DIRECT3X3_NONE;
-#ifdef DAWN_WITH_STREAMK
-    if ((policy_of(d) & 0x400) && !(policy_of(d) & 0x2000) && d.sk_ws) return DAWN_DIRECT3X3_NONE;   // (experimental build: the stream-K kernel may take it)
-#endif
-    return conv3x3_direct(d, M, nullptr, (policy_of(d) & 0x2000) != 0, true);
+    return conv3x3_direct(d, M, nullptr, (policy_of(d) & DAWN_POLICY_NINE_TERMS) != 0, true);
 }
 
 /* Which split-operand kernel dawn_conv_gemm runs a 1x1 projection / 4x4 resample descriptor on (host code, launches nothing): the
@@ -1395,7 +1372,7 @@ extern "C" int dawn_conv_gemm(const dawn_conv_desc* dp, void* stream) {
     const int form1 = split1x1_form(d, M);
     if (d.ln_eps > 0.f && form1 == DAWN_SPLIT1X1_NONE)    // LayerNorm inside the GEMM: only the row-stationary kernels hold whole rows
         return dawn_set_error_msg(-14, "dawn_conv_gemm: ln_eps needs a split 1x1 projection with dawn_gemm1x1_ln_inline_ok, 16-byte aligned "
-                                       "row strides and the split-kernel policy bits (0x1000 set, 0x20000 clear)");
+                                       "row strides and the split-kernel policy bits (DAWN_POLICY_SPLIT (0x1000) set, DAWN_POLICY_NO_ROW_KERNELS (0x20000) clear)");
     if (form1 != DAWN_SPLIT1X1_NONE) {
         if (form1 == DAWN_SPLIT1X1_ROWREG) dawn_gemm1x1_rowreg_launch(d, M, s);
         else if (form1 == DAWN_SPLIT1X1_ROWACC) dawn_gemm1x1_rowacc_launch(d, M, 0, s);
@@ -1405,40 +1382,15 @@ extern "C" int dawn_conv_gemm(const dawn_conv_desc* dp, void* stream) {
         return 0;
     }
     if (conv3x3_split_path(d)) {
-        const bool nine = (policy_of(d) & 0x2000) != 0;
-        if ((policy_of(d) & 0x8000000) && !nine && d.w_wino4) {  // Winograd F(4x4,3x3) form (conv3x3_wino4.hip; opt-in)
-            int rows = 0;
-            if (dawn_conv3x3_wino4_try(d, M, policy_of(d), s, &rows, 0)) {
-                if (d.gn_rows) *d.gn_rows = rows;
-                DAWN_LAUNCH_CHECK();
-                return 0;
-            }
-        }
-        if ((policy_of(d) & 0x2000000) && !nine && d.w_wino) {   // Winograd F(2x2,3x3) form (conv3x3_wino.hip)
-            int rows = 0;
-            if (dawn_conv3x3_wino_try(d, M, policy_of(d), s, &rows, 0)) {
-                if (d.gn_rows) *d.gn_rows = rows;
-                DAWN_LAUNCH_CHECK();
-                return 0;
-            }
-        }
-#ifdef DAWN_WITH_STREAMK
-        if ((policy_of(d) & 0x400) && !nine && d.sk_ws) {   // persistent stream-K kernel (experimental build only)
-            int rows = 0;
-            if (dawn_conv3x3_sk_try(d, M, policy_of(d), s, &rows)) {
-                if (d.gn_rows) *d.gn_rows = rows;
-                DAWN_LAUNCH_CHECK();
-                return 0;
-            }
-        }
-#endif
-        const bool ok = conv3x3_direct(d, M, s, nine, false) != DAWN_DIRECT3X3_NONE;
-        if (ok) {
+        int rows = 0;
+        const bool transformed = conv3x3_transformed(d, M, s, &rows, false) != 0;
+        if (transformed && d.gn_rows) *d.gn_rows = rows;      // (the direct kernels write it themselves)
+        if (transformed || conv3x3_direct(d, M, s, (policy_of(d) & DAWN_POLICY_NINE_TERMS) != 0, false) != DAWN_DIRECT3X3_NONE) {
             DAWN_LAUNCH_CHECK();
             return 0;
         }
     }
-    if ((policy_of(d) & 0x800) && d.mode == 0 && d.KH == 3 && d.KW == 3 && d.stride == 1 && d.pad == 1 && d.Ho == d.Hi &&
+    if ((policy_of(d) & DAWN_POLICY_HALO) && d.mode == 0 && d.KH == 3 && d.KW == 3 && d.stride == 1 && d.pad == 1 && d.Ho == d.Hi &&
         d.Wo == d.Wi && !d.ch_a && !d.pro_act && !d.pro_add && !d.row_mean) {
         const bool ok = d.N <= 64 ? try_launch_halo<64, 1>(d, M, s) : try_launch_halo<128, 2>(d, M, s);
         if (ok) {
@@ -1446,9 +1398,9 @@ extern "C" int dawn_conv_gemm(const dawn_conv_desc* dp, void* stream) {
             return 0;
         }
     }
-    const bool k32 = (policy_of(d) & 1) && (d.C0 % 32 == 0) && (d.C1 % 32 == 0) && (d.KH * d.KW * Cin >= 4096);
+    const bool k32 = (policy_of(d) & DAWN_POLICY_BK32) && (d.C0 % 32 == 0) && (d.C1 % 32 == 0) && (d.KH * d.KW * Cin >= 4096);
     if (d.N <= 64) {
-        if ((policy_of(d) & 2) && M >= 256 * 256) launch<256, 64, 16, 4, 1>(d, M, s);
+        if ((policy_of(d) & DAWN_POLICY_TILE256) && M >= 256 * 256) launch<256, 64, 16, 4, 1>(d, M, s);
         else launch<128, 64, 16, 2, 2>(d, M, s);
     } else {
         if (k32) launch<128, 128, 32, 2, 2>(d, M, s);

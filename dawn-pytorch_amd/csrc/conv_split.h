@@ -8,14 +8,33 @@
 #include "dawn_common.h"
 #include "../../include/dawn_hip.h"
 
-// the policy bits are described in conv_gemm.hip
-constexpr int DAWN_CONV_POLICY_DEFAULT = 0x2B00580D;
+// dawn_conv_desc.policy: the bits are the DAWN_POLICY_* table of include/dawn_hip.h; the library reads them through the functions
+// below and nowhere as a number.  A build honours the bits of its mask, policy_of() drops the rest.
+constexpr int DAWN_CONV_POLICY_MASK_COMMON =
+    DAWN_POLICY_BK32 | DAWN_POLICY_TILE256 | DAWN_POLICY_XCD_ORDER | DAWN_POLICY_GLDS | DAWN_POLICY_SK_PRIO_ALT | DAWN_POLICY_GLDS_BK32 |
+    DAWN_POLICY_GLDS_STAGES3 | DAWN_POLICY_GLDS_TILE256 | DAWN_POLICY_GLDS_NO_TILE256 | DAWN_POLICY_HALO | DAWN_POLICY_SPLIT |
+    DAWN_POLICY_NINE_TERMS | DAWN_POLICY_SPLIT_V2 | DAWN_POLICY_TILE128_ALWAYS | DAWN_POLICY_TILE128_NEVER | DAWN_POLICY_NO_ROW_KERNELS |
+    DAWN_POLICY_MFMA_K32 | DAWN_POLICY_WINO2 | DAWN_POLICY_WINO2_DEEP_ONLY | DAWN_POLICY_WINO4 | DAWN_POLICY_WINO4_ALL_SHAPES |
+    DAWN_POLICY_WINO_REVERSE;
+constexpr int DAWN_CONV_POLICY_MASK_SHIPPED = DAWN_CONV_POLICY_MASK_COMMON | DAWN_POLICY_STAGGER_MASK;
+// the whole variant field (TILE128_NEVER, TILED_ONLY and XCD_LAUNCH_ORDER lie inside it: the overlap the table states) and the
+// fp32 ablations, without the stagger field
+constexpr int DAWN_CONV_POLICY_MASK_ABLATION =
+    DAWN_CONV_POLICY_MASK_COMMON | DAWN_POLICY_VARIANT_MASK | DAWN_POLICY_ABL_NO_RESTAGE | DAWN_POLICY_ABL_NO_BARRIER;
 #ifdef DAWN_ABLATION
-constexpr int DAWN_CONV_POLICY_MASK = 0x3F0FFFFF;
+constexpr int DAWN_CONV_POLICY_MASK = DAWN_CONV_POLICY_MASK_ABLATION;
 #else
-constexpr int DAWN_CONV_POLICY_MASK = 0x3FF3FFCF;
+constexpr int DAWN_CONV_POLICY_MASK = DAWN_CONV_POLICY_MASK_SHIPPED;
 #endif
+static_assert(DAWN_CONV_POLICY_DEFAULT == 0x2B00580D, "the shipped policy moved");
+static_assert(DAWN_CONV_POLICY_MASK_SHIPPED == 0x3FF3FFCF && DAWN_CONV_POLICY_MASK_ABLATION == 0x3F0FFFFF, "a policy mask moved");
+static_assert((DAWN_CONV_POLICY_DEFAULT & ~DAWN_CONV_POLICY_MASK_SHIPPED) == 0, "the shipped policy has a bit the shipped library drops");
 static inline int policy_of(const dawn_conv_desc& d) { return (d.policy ? d.policy : DAWN_CONV_POLICY_DEFAULT) & DAWN_CONV_POLICY_MASK; }
+static inline int policy_variant(const dawn_conv_desc& d) { return (policy_of(d) & DAWN_POLICY_VARIANT_MASK) / DAWN_POLICY_VARIANT(1); }
+static inline int policy_stagger(int policy) { return (policy & DAWN_POLICY_STAGGER_MASK) / DAWN_POLICY_STAGGER(1); }
+// DAWN_POLICY_XCD_LAUNCH_ORDER and DAWN_POLICY_ABL_ROW_FETCH lie outside both masks and are read from the descriptor as the caller
+// wrote it: no default, no mask (a kernel may call this).  Moving them into policy_of() would change which builds honour them.
+__host__ __device__ static inline bool policy_raw_bit(const dawn_conv_desc& d, int bit) { return (d.policy & bit) != 0; }
 
 // dawn_conv_desc.border (mode 1): where a 2x2 phase tap that falls outside the H x W input reads.  0 leaves the coordinate alone
 // (the callers' bounds test then reads zero), 1 clamps it to the edge pixel, 2 wraps it to the opposite edge.  A tap is at most one

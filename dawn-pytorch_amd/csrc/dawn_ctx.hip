@@ -314,7 +314,7 @@ struct Eval {
         ConvArgs a;
         a.w = w; a.w_bf3 = w_bf3; a.N = N; a.Fr = Fr; a.Hi = Hi; a.Wi = Wi; a.out = o.p; a.ld_out = N;
         const int pol = c->conv_policy;     // (A/B policies without the row-stationary split kernels take the statistics pass)
-        if (w_bf3 && !(pol && (!(pol & 0x1000) || (pol & 0x20000))) && dawn_gemm1x1_ln_inline_ok(x.rows, N, x.C, C1)) {
+        if (w_bf3 && !(pol && (!(pol & DAWN_POLICY_SPLIT) || (pol & DAWN_POLICY_NO_ROW_KERNELS))) && dawn_gemm1x1_ln_inline_ok(x.rows, N, x.C, C1)) {
             a.in0 = x.p; a.C0 = x.C; a.ld0 = x.C; a.in1 = x2 ? x2->p : nullptr; a.C1 = C1; a.ld1 = C1;
             a.ln_eps = 1e-5f;
             conv(a);

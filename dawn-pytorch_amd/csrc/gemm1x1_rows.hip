@@ -1,7 +1,7 @@
 // The row-stationary split-operand GEMMs: gemm1x1_rowreg_kernel (short K, rows held in registers) and gemm1x1_rowacc_kernel (deep K /
 // narrow N, and the 4x4 stride-2 resampling convs as implicit GEMMs).  Reached from dawn_conv_gemm's router (conv_gemm.hip) through
 // dawn_gemm1x1_rowreg_launch / dawn_gemm1x1_rowacc_launch; which shapes they serve is decided there (gemm1x1_row*_fits,
-// conv_resample_rowacc_ok).  The fetch-pattern ablation (policy 0x40000000) exists only in -DDAWN_ABLATION builds.
+// conv_resample_rowacc_ok).  The fetch-pattern ablation (DAWN_POLICY_ABL_ROW_FETCH) exists only in -DDAWN_ABLATION builds.
 #include "conv_split.h"
 
 namespace {
@@ -56,7 +56,7 @@ __global__ __launch_bounds__(512) void gemm1x1_rowreg_kernel(const dawn_conv_des
         const unsigned vo0 = (unsigned)((l31 * d.ld0 + 8 * half) * 4), vo1 = (unsigned)((l31 * ld1 + 8 * half) * 4);
 #ifdef DAWN_ABLATION
         // perf ablation (wrong results: the right bytes in the wrong lanes): 8 rows x 128 contiguous bytes per instruction instead of 32 rows x 32 bytes
-        if (d.policy & 0x40000000) {
+        if (policy_raw_bit(d, DAWN_POLICY_ABL_ROW_FETCH)) {
 #pragma unroll
             for (int kc = 0; kc < KS; ++kc)
 #pragma unroll
@@ -272,7 +272,7 @@ __global__ __launch_bounds__(512) void gemm1x1_rowacc_kernel(const dawn_conv_des
 #ifdef DAWN_ABLATION
             // perf ablation (wrong results: the right bytes in the wrong lanes): the same 32 rows x 64 channels, fetched as 8 rows x 128 contiguous
             // bytes per instruction (8 line touches instead of 32) -- what would a coalesced fetch + a free transpose buy?
-            if (d.policy & 0x40000000) {
+            if (policy_raw_bit(d, DAWN_POLICY_ABL_ROW_FETCH)) {
 #pragma unroll
                 for (int kc = 0; kc < KS; ++kc)
 #pragma unroll
@@ -316,7 +316,7 @@ __global__ __launch_bounds__(512) void gemm1x1_rowacc_kernel(const dawn_conv_des
 #ifdef DAWN_ABLATION
             // perf ablation (wrong results by design): every lane gathers the pixel of lane 0 -- one cache line per instruction instead of 32:
             // what do the scattered line touches of the gather cost?
-            if (d.policy & 0x40000000) {
+            if (policy_raw_bit(d, DAWN_POLICY_ABL_ROW_FETCH)) {
                 // ... as MODE 0: 8 pixels x 128 contiguous bytes per instruction; the pixel's offset comes from the lane that owns it
                 const unsigned pbase = inb ? off - (unsigned)(8 * half * 4) : 0xffffff00u;
 #pragma unroll

@@ -50,7 +50,7 @@ __global__ __launch_bounds__(256 * (CFG ? 1 : WN)) void gemm1x1_bf16_kernel(cons
     // the same A rows) go to ONE XCD -- XCD x walks the contiguous tile range [x q + min(x, r), ...) of the row-major tile order
     // (q = tiles / 8, r = tiles % 8), so a row panel comes over the fabric once instead of once per XCD that holds a column tile
     int tile = blockIdx.x;
-    if (!(d.policy & 0x80000)) {
+    if (!policy_raw_bit(d, DAWN_POLICY_XCD_LAUNCH_ORDER)) {
         const int nT = gridDim.x, q = nT >> 3, r = nT & 7, x = tile & 7, j = tile >> 3;
         tile = x * q + (x < r ? x : r) + j;
     }
@@ -264,7 +264,7 @@ void launch_gemm1x1_bf16(const dawn_conv_desc& d, long M, hipStream_t s) {
     const size_t lds = (size_t)2 * 2 * (6 * (256 * 16 + 128) + 64) + (size_t)2 * 2 * 6 * BN * 16;
     const int nwg = (int)(M / 256) * (d.N / BN);
     if (d.gn_rows) *d.gn_rows = nwg;   // rows of gn_part this launch writes
-    if (policy_of(d) & 0x2000) {
+    if (policy_of(d) & DAWN_POLICY_NINE_TERMS) {
         (void)hipFuncSetAttribute((const void*)gemm1x1_bf16_kernel<9, WN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         hipLaunchKernelGGL((gemm1x1_bf16_kernel<9, WN>), dim3(nwg), dim3(256 * WN), lds, s, d, M);
     } else {
@@ -286,9 +286,8 @@ void launch_gemm1x1_bf16_small(const dawn_conv_desc& d, long M, hipStream_t s) {
 // the tiled split kernel (gemm1x1_bf16_kernel) for a descriptor split1x1_form() routed to it
 void dawn_gemm1x1_tiled_launch(const dawn_conv_desc& d, long M, hipStream_t s) {
     const int plan = gemm1x1_split_plan(M, d.N, d.C0, d.C1);
-    // policy bit 0x8000: 128 x 64 tiles for every eligible shape; 0x10000 (A/B only): never (the round-1 tile policy)
-    if (plan != 0 && ((policy_of(d) & 0x8000) || (plan == 3 && !(policy_of(d) & 0x10000)))) launch_gemm1x1_bf16_small(d, M, s);
-    else if (plan == 3) {                            // 0x10000: the round-1 choice for these shapes
+    if (plan != 0 && ((policy_of(d) & DAWN_POLICY_TILE128_ALWAYS) || (plan == 3 && !(policy_of(d) & DAWN_POLICY_TILE128_NEVER)))) launch_gemm1x1_bf16_small(d, M, s);
+    else if (plan == 3) {                            // TILE128_NEVER: the round-1 choice for these shapes
         if (d.N % 128 == 0 && (M / 256) * (d.N / 128) >= 128) launch_gemm1x1_bf16<2>(d, M, s);
         else launch_gemm1x1_bf16<1>(d, M, s);
     }

@@ -1249,22 +1249,22 @@ extern "C" int dawn_temporal_layer_c64_ex(const float* x, int Fext, int HW, int 
     const int nkt = (32 + 2 * win + 31) / 32;
     const int nrt = (Fext + 31) / 32;
     if (nkt > 4) return dawn_set_error_msg(-35, "dawn_temporal_layer_c64: win > 48 not supported (use the unfused path)");
-    const int force = flags & 7;                       // 0 = automatic, m + 1 = WMODE m (A/B measurements, tests)
+    const int force = flags & DAWN_TL_FORCE_MASK;      // 0 = automatic, DAWN_TL_FORCE_WMODE(m) = WMODE m (A/B measurements, tests)
     // WMODE 4 (round 6): the window-tiled 16-query kernel of temporal_layer16.hip wherever its instantiation covers the shape
     // WMODE 5 (round 6): the window-tiled kernel with ONE query tile per wave (13 waves) wherever the query range is at most 13 tiles
-    if ((force == 0 && !(flags & 256)) || force == 6) {
+    if ((force == 0 && !(flags & DAWN_TL_KEEP_32X32)) || force == DAWN_TL_FORCE_WMODE(5)) {
         if (dawn_temporal_layer13_try(x, Fext, HW, q0, Fq, win, wqkv_bf3, wout_bf3p, rot_cos, rot_sin, band, eps, out, (hipStream_t)stream)) {
             DAWN_LAUNCH_CHECK();
             return 0;
         }
-        if (force == 6) return dawn_set_error_msg(-38, "dawn_temporal_layer_c64: WMODE 5 does not cover this shape (win <= 40, Fext <= 208, <= 13 query tiles, both split weight images)");
+        if (force == DAWN_TL_FORCE_WMODE(5)) return dawn_set_error_msg(-38, "dawn_temporal_layer_c64: WMODE 5 does not cover this shape (win <= 40, Fext <= 208, <= 13 query tiles, both split weight images)");
     }
-    if ((force == 0 && !(flags & 256)) || force == 5) {
+    if ((force == 0 && !(flags & DAWN_TL_KEEP_32X32)) || force == DAWN_TL_FORCE_WMODE(4)) {
         if (dawn_temporal_layer16_try(x, Fext, HW, q0, Fq, win, wqkv_bf3, wout_bf3p, rot_cos, rot_sin, band, eps, out, (hipStream_t)stream)) {
             DAWN_LAUNCH_CHECK();
             return 0;
         }
-        if (force == 5) return dawn_set_error_msg(-37, "dawn_temporal_layer_c64: WMODE 4 does not cover this shape (win <= 40, Fext <= 208, both split weight images)");
+        if (force == DAWN_TL_FORCE_WMODE(4)) return dawn_set_error_msg(-37, "dawn_temporal_layer_c64: WMODE 4 does not cover this shape (win <= 40, Fext <= 208, both split weight images)");
     }
     const size_t band_floats = (size_t)HEADS * (32 * nkt + 32);
     const size_t base = ((size_t)32 * nrt * (XLD + KLD + DH) + band_floats) * sizeof(float);
@@ -1272,13 +1272,13 @@ extern "C" int dawn_temporal_layer_c64_ex(const float* x, int Fext, int HW, int 
     const size_t base2 = ((size_t)32 * nrt * (96 + KLD + DH) + band_floats) * sizeof(float);
     // WMODE 3 (also S and P.V on the bf16 pipe): X + K planes for Fext rows, V^T for 32 nrt keys
     const int delta = (((q0 - win) % 16) + 16) % 16;
-    const bool fac200 = Fext <= 200 && !(flags & 64) &&
+    const bool fac200 = Fext <= 200 && !(flags & DAWN_TL_NO_FIXED200) &&
                         (size_t)200 * 576 + (size_t)nrt * 6144 + band_floats * sizeof(float) <= 163840;
     const size_t base3 = (size_t)(fac200 ? 200 : Fext) * 576 + (size_t)nrt * 6144 + band_floats * sizeof(float);
-    bool mode3 = wqkv_bf3 != nullptr && base3 <= 163840 && Fq + delta <= 256 && (force == 0 || force == 4);
-    if (force == 4 && !mode3) return dawn_set_error_msg(-36, "dawn_temporal_layer_c64: WMODE 3 does not fit this shape");
-    const bool split = !mode3 && wqkv_bf3 != nullptr && base2 <= 163840 && (force == 0 || force == 3);
-    const bool wlds = !mode3 && !split && base + 32768 <= 163840 && force != 1;
+    bool mode3 = wqkv_bf3 != nullptr && base3 <= 163840 && Fq + delta <= 256 && (force == 0 || force == DAWN_TL_FORCE_WMODE(3));
+    if (force == DAWN_TL_FORCE_WMODE(3) && !mode3) return dawn_set_error_msg(-36, "dawn_temporal_layer_c64: WMODE 3 does not fit this shape");
+    const bool split = !mode3 && wqkv_bf3 != nullptr && base2 <= 163840 && (force == 0 || force == DAWN_TL_FORCE_WMODE(2));
+    const bool wlds = !mode3 && !split && base + 32768 <= 163840 && force != DAWN_TL_FORCE_WMODE(0);
 #ifdef DAWN_TL_TIMING
     const size_t lds = 163840;                 // instrumented build: stamps live at byte 160000
     if (mode3 && base3 > 160000) mode3 = false;
@@ -1290,7 +1290,7 @@ extern "C" int dawn_temporal_layer_c64_ex(const float* x, int Fext, int HW, int 
     hipStream_t s = (hipStream_t)stream;
     const unsigned short* wsp = (const unsigned short*)wout_bf3p;
     const bool hl = 32 + 2 * win <= 32 * nkt - 16;       // the upper 16 keys of the last key tile are never in a window
-    const bool ob = wout_bf3p != nullptr && !(flags & 32);
+    const bool ob = wout_bf3p != nullptr && !(flags & DAWN_TL_OUT_FP32);
 #define LAUNCH_TL3D(N, SC, HLV, OBV, FACV, KVIV)                                                               \
     do {                                                                                                       \
         (void)hipFuncSetAttribute((const void*)temporal_layer_c64_bf16_kernel<N, SC, HLV, OBV, FACV, KVIV>,    \
@@ -1301,7 +1301,7 @@ extern "C" int dawn_temporal_layer_c64_ex(const float* x, int Fext, int HW, int 
     } while (0)
 #define LAUNCH_TL3C(N, SC, HLV, OBV, FACV)                                                                     \
     do {                                                                                                       \
-        if (flags & 128) LAUNCH_TL3D(N, SC, HLV, OBV, FACV, false); else LAUNCH_TL3D(N, SC, HLV, OBV, FACV, true); \
+        if (flags & DAWN_TL_NO_KVI) LAUNCH_TL3D(N, SC, HLV, OBV, FACV, false); else LAUNCH_TL3D(N, SC, HLV, OBV, FACV, true); \
     } while (0)
 #define LAUNCH_TL3B(N, SC, HLV, OBV)                                                                           \
     do {                                                                                                       \
@@ -1317,7 +1317,7 @@ extern "C" int dawn_temporal_layer_c64_ex(const float* x, int Fext, int HW, int 
 #define LAUNCH_TL(N)                                                                                           \
     do {                                                                                                       \
         if (mode3) {                                                                                           \
-            if (flags & 16) LAUNCH_TL3(N, 1); else LAUNCH_TL3(N, 0);                                           \
+            if (flags & DAWN_TL_SCHED_HINTS) LAUNCH_TL3(N, 1); else LAUNCH_TL3(N, 0);                          \
         } else if (split) {                                                                                    \
             (void)hipFuncSetAttribute((const void*)temporal_layer_c64_kernel<N, 2>,                            \
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                   \

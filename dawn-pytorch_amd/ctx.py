@@ -56,6 +56,7 @@ def _clip_struct(clip, ancestral: bool) -> ClipMode:
     return ClipMode(CLIP_KINDS[kind], 0.0 if q is None else q)
 
 
+# (values of OPT_CONV_POLICY / OPT_TEMPORAL_FLAGS: policy.ConvPolicy / policy.TemporalFlags)
 OPT_CONV_POLICY, OPT_TEMPORAL_FLAGS, OPT_OVERLAP, OPT_PROFILE, OPT_LONG_CLIP_FRAMES, OPT_UP_BORDER, OPT_FOLD_HEADS = 1, 2, 3, 4, 5, 6, 7
 
 # ---- T-shard callbacks (include/dawn_hip.h: dawn_shard_comm)

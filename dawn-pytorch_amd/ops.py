@@ -18,6 +18,7 @@ import torch
 
 from . import _lib
 from ._lib import ConvDesc, check
+from .policy import ConvPolicy
 
 Tensor = torch.Tensor
 
@@ -51,9 +52,9 @@ class HipOps:
         self.overlap = True          # two-stream overlap of independent branches (fork_join)
         self._side_stream = None
         self.graph_error = None      # set when a HIP-graph capture failed and the sampler fell back to eager
-        self.conv_policy = 0         # dawn_conv_desc.policy of every conv_gemm launch (0 = shipped kernel policy)
-        self.temporal_flags = 0      # kernel-family selector of the fused temporal layer (0 = automatic; A/B and tests)
-        self.temporal_attn_flags = 0  # dawn_temporal_attn_ex flags (1 = the fp32-MFMA attention core; A/B and tests)
+        self.conv_policy = 0         # dawn_conv_desc.policy of every conv_gemm launch (0 = shipped kernel policy; policy.ConvPolicy names the bits)
+        self.temporal_flags = 0      # kernel-family selector of the fused temporal layer (0 = automatic; policy.TemporalFlags; A/B and tests)
+        self.temporal_attn_flags = 0  # dawn_temporal_attn_ex flags (policy.TemporalAttnFlags, FP32 = the fp32-MFMA attention core; A/B and tests)
         self.sk_ws = None            # experimental library only (hipbuild.py sktiming): scratch tensor handed to dawn_conv_desc.sk_ws
         self.fuse_h1 = True          # cross-attention kernels write h1 = SiLU(GN(c1)) + h_cond themselves (False: A/B, two-stream form)
         # the heads' res_conv folded into the output projection: both head blocks end in one heads_eps launch (False, or DAWN_FOLD_HEADS=0
@@ -246,8 +247,8 @@ class HipOps:
     def ln_inline_ok(self, rows: int, N: int, C0: int, C1: int = 0) -> bool:
         """May the projection compute the LayerNorm of its input rows itself (conv_gemm(ln_eps=...): the row-stationary
         split GEMM holds whole rows in registers), so that no statistics pass reads them first?"""
-        pol = self.conv_policy          # 0 = shipped policy; A/B policies without the split kernels (0x1000 clear) or with the
-        if pol and (not (pol & 0x1000) or (pol & 0x20000)):          # row-stationary ones disabled (0x20000) take the statistics pass
+        pol = self.conv_policy          # 0 = shipped policy; A/B policies without the split kernels (SPLIT clear) or with the
+        if pol and (not (pol & ConvPolicy.SPLIT) or (pol & ConvPolicy.NO_ROW_KERNELS)):   # row-stationary ones disabled take the statistics pass
             return False
         return bool(self.L.dawn_gemm1x1_ln_inline_ok(rows, N, C0, C1))
 

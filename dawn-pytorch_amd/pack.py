@@ -263,7 +263,7 @@ class PackedResBlock:
     w2s: Optional[Tensor] = None
     w1w: Optional[Tensor] = None          # pack_wino_bf3 images of w1 / w2 (Winograd F(2x2,3x3) form of the split-operand conv)
     w2w: Optional[Tensor] = None
-    w1w4: Optional[Tensor] = None         # pack_wino4_bf3 images (F(4x4,3x3) form; 64-channel convs only; used under policy bit 0x8000000)
+    w1w4: Optional[Tensor] = None         # pack_wino4_bf3 images (F(4x4,3x3) form; 64-channel convs only; used under ConvPolicy.WINO4)
     w2w4: Optional[Tensor] = None
     wrs: Optional[Tensor] = None          # ... of the 1x1 res_conv, of to_q and of the three to_out projections
     wqs: Optional[Tensor] = None
@@ -425,7 +425,7 @@ def pack_unet(sd: Dict[str, Tensor], win: int, device, prefix: str = "denoise_fn
             rb.w1w = pack_wino_bf3(w1).to(device)
         if Co % 64 == 0:
             rb.w2w = pack_wino_bf3(g(p + "block2.proj.weight")).to(device)
-        # F(4x4,3x3) images (policy bit 0x8000000): only for the convs the library's per-shape gate can select (up to 128 input channels;
+        # F(4x4,3x3) images (ConvPolicy.WINO4): only for the convs the library's per-shape gate can select (up to 128 input channels;
         # 36 x 6 bytes per (cin, cout) pair: 0.9 .. 3.5 MB each)
         if Cin % 32 == 0 and Cin <= 128 and Co % 64 == 0 and Co <= 128:
             rb.w1w4 = pack_wino4_bf3(w1).to(device)

@@ -57,7 +57,7 @@ typedef struct dawn_conv_desc {
                                                       the split-operand bf16-MFMA kernel; NULL = fp32 MFMA */
     int* gn_rows;                                  /* optional HOST pointer: receives the number of gn_part rows this launch
                                                       writes (<= dawn_conv_gemm_nblocks); negative = the launch also finalised (gn_a below) */
-    int policy;                                    /* kernel-selection policy bits (see below); 0 = shipped default */
+    int policy;                                    /* kernel-selection bits (DAWN_POLICY_* below); 0 = shipped default */
     float ln_eps;                                  /* > 0: LayerNorm (no gain) over the C0+C1 channels of every input row, computed by the
                                                       GEMM itself -- no statistics pass (instead of row_mean / row_rstd).  <= 128 channels: from the
                                                       rows it holds in registers; deeper narrow projections: one shifted one-pass statistics sweep
@@ -68,8 +68,8 @@ typedef struct dawn_conv_desc {
                                                       the hipbuild.py sktiming preset.  The shipped library ignores both fields */
     const void* w_wino;                            /* optional (3x3/s1/p1 convs): the Winograd F(2x2,3x3) image of the weights, U = G g G^T computed in
                                                       fp64 and split into three bf16 planes, in the fragment order of conv3x3_wino_kernel:
-                                                      [(C0+C1)/16][16 positions][N/16][2][64 lanes][8] (pack.pack_wino_bf3).  With policy bit
-                                                      0x2000000 such convs run in the Winograd form (2.25x fewer matrix-pipe flops, fp32 results to
+                                                      [(C0+C1)/16][16 positions][N/16][2][64 lanes][8] (pack.pack_wino_bf3).  With
+                                                      DAWN_POLICY_WINO2 such convs run in the Winograd form (2.25x fewer matrix-pipe flops, fp32 results to
                                                       fp32-Winograd accuracy); NULL or other shapes = the direct split kernel */
     /* optional, with gn_part: finish the GroupNorm in the conv launch itself (dawn_gn_reduce_finalize's arguments: MT:230-248) -- the
      * workgroup that finishes last reduces the partial rows in fixed order and writes a[c] / b[c].  Honoured by the Winograd kernel
@@ -87,9 +87,8 @@ typedef struct dawn_conv_desc {
     unsigned* gn_ticket;
     /* round 5 (ABI 7), optional: the Winograd F(4x4,3x3) image of a 3x3 / stride-1 / pad-1 conv (pack.pack_wino4_bf3: [(C0+C1)/16][36
      * positions][N/16][768 bf16 = the fragment [u1|u2] in lane order, then u3 of the k-groups 0, 1] of U = G g G^T on the points 0, +-3/4,
-     * +-3/2, inf: every plane once, 8 of the 9 cross terms).  With policy bit 0x8000000 (in the
-     * shipped default: it selects the form only for the shapes it measured faster on, 64 input channels at image width 64 and up to 128 at image width 32; 0x10000000 adds
-     * every shape dawn_conv3x3_wino4_ok accepts) the conv runs as conv3x3_wino4_kernel (4x fewer
+     * +-3/2, inf: every plane once, 8 of the 9 cross terms).  With DAWN_POLICY_WINO4 (in the shipped default: the form only for
+     * the shapes it measured faster on; DAWN_POLICY_WINO4_ALL_SHAPES adds every shape dawn_conv3x3_wino4_ok accepts) the conv runs as conv3x3_wino4_kernel (4x fewer
      * matrix-pipe flops than the direct form, fp32 results to fp32-F(4x4) accuracy: ~2x the direct form's rounding error); the gn_* fields
      * above are honoured exactly as by the F(2x2) kernel */
     const void* w_wino4;
@@ -103,10 +102,10 @@ typedef struct dawn_conv_desc {
 } dawn_conv_desc;
 int dawn_conv_gemm(const dawn_conv_desc* d, void* stream);
 /* 1 when a 3x3 / stride 1 / pad 1 conv of this shape (F frames of H x W pixels, C0 + C1 input channels, N output channels) runs in the
- * Winograd F(2x2,3x3) form once dawn_conv_desc.w_wino is supplied (policy bit 0x2000000, in the shipped default): image width a power
+ * Winograd F(2x2,3x3) form once dawn_conv_desc.w_wino is supplied (DAWN_POLICY_WINO2, in the shipped default): image width a power
  * of two <= 64, even height, 256-pixel tiles, an even number of 16-channel chunks, N a multiple of 64 */
 int dawn_conv3x3_wino_ok(int F, int H, int W, int C0, int C1, int N);
-/* the same question for the F(4x4,3x3) form (dawn_conv_desc.w_wino4, policy bit 0x8000000): image width 64 or 32, H a multiple of
+/* the same question for the F(4x4,3x3) form (dawn_conv_desc.w_wino4, DAWN_POLICY_WINO4): image width 64 or 32, H a multiple of
  * 256 / W, an even number of 16-channel chunks, N a multiple of 64 */
 int dawn_conv3x3_wino4_ok(int F, int H, int W, int C0, int C1, int N);
 /* Which form of the 3x3 conv dawn_conv_gemm would run for this descriptor (host code, launches nothing; the launch's own decision
@@ -130,12 +129,44 @@ int dawn_gemm1x1_form(const dawn_conv_desc* d);
 /* upper bound on the thread blocks (= rows of gn_part) dawn_conv_gemm launches for an (M rows, N columns) output;
  * the launch reports the exact count through dawn_conv_desc.gn_rows */
 int dawn_conv_gemm_nblocks(long M, int N);
-/* dawn_conv_desc.policy bits (0 = shipped policy 0x2B00580D; per call, no process-global state): bit0 BK=32 tiles,
- * bit1 256x64 tile for N<=64, bit2 XCD-contiguous tile order, bit3 direct-to-LDS staging, 0x800 LDS-halo 3x3 kernel,
- * 0x1000 split-operand (bf16 pipe) kernels when w_bf3 is supplied, 0x2000 all 9 cross terms instead of 6, 0x4000
- * second-generation split 3x3 kernel, 0x1000000 that kernel on v_mfma_f32_16x16x32_bf16 (two cross terms per instruction: less energy per
- * flop on a power-limited chip), 0x2000000 the Winograd F(2x2,3x3) form of that conv where w_wino is supplied and the shape fits (2.25x fewer matrix-pipe flops); 0x4000000 (A/B) the direct kernel for convs of fewer than 128 input channels even where the Winograd form fits (measured slower, not shipped); 0x8000000 (shipped) the Winograd F(4x4,3x3) form where w_wino4 is supplied, dawn_conv3x3_wino4_ok and the shape is one it measured faster on (64 input channels at image width 64, up to 128 at image width 32) -- with 0x10000000 wherever it fits; 0x20000000 (shipped) both Winograd kernels walk their tiles back to front -- last frame first: the end of the input, written last by the producer, is what the memory-side cache still holds (bit-identical outputs); 0x400 is ignored (round 3's opt-in stream-K variant: experimental builds only).  Every combination computes the same function (tests run the kernel families
- * against each other); perf-ablation / s_memtime builds exist only under -DDAWN_ABLATION (hipbuild.py presets). */
+/* ---- dawn_conv_desc.policy: THE table of its bits (0 = DAWN_CONV_POLICY_DEFAULT; per call, no process-global state; read through policy_of() of
+ * csrc/conv_split.h, which drops what the build does not honour; measurement history longer than a line: DESIGN.md).  Status: shipped = in the default;
+ * A/B = honoured by the shipped library, measured, not in the default (every such combination computes the same function: the tests run the kernel families
+ * against each other); ablation = -DDAWN_ABLATION builds only (hipbuild.py presets; wrong results by design); sktiming = the experimental stream-K build only. */
+#define DAWN_POLICY_BK32               0x1         /* fp32 kernel: BK = 32 tiles for deep-K GEMMs (K >= 4096, N > 64).  shipped (profiles/r1_d_conv_variants.txt) */
+#define DAWN_POLICY_TILE256            0x2         /* fp32 kernel: 256 x 64 tiles for N <= 64.  A/B: no gain (profiles/r1_d_conv_variants.txt) */
+#define DAWN_POLICY_XCD_ORDER          0x4         /* XCD-contiguous tile order for multi-tap convs on >= 32 x 32 frames.  shipped (profiles/r1_d_conv_variants.txt) */
+#define DAWN_POLICY_GLDS               0x8         /* direct-to-LDS staging for prologue-free fp32 GEMMs.  shipped (profiles/r1_j_conv_glds.txt) */
+#define DAWN_POLICY_ABL_NO_RESTAGE     0x10        /* fp32 kernel without re-staging.  ablation */
+#define DAWN_POLICY_ABL_NO_BARRIER     0x20        /* ... and without its barrier.  ablation */
+#define DAWN_POLICY_SK_PRIO_ALT        0x40        /* stream-K kernel: issue-priority alternation (period in DAWN_POLICY_VARIANT).  sktiming; ignored by the shipped library */
+#define DAWN_POLICY_GLDS_BK32          0x80        /* direct-to-LDS path: BK = 32 for every shape.  A/B */
+#define DAWN_POLICY_GLDS_STAGES3       0x100       /* direct-to-LDS path: 3-stage counted-vmcnt pipeline.  A/B: no gain (profiles/r1_j_conv_glds.txt) */
+#define DAWN_POLICY_GLDS_TILE256       0x200       /* direct-to-LDS path: its 256 x 64 tile for every N <= 64 GEMM of >= 65536 rows.  A/B */
+#define DAWN_POLICY_SK_NO_PAIR_OFFSET  0x200       /* (same bit) stream-K kernel: no half-tile offset between co-resident workgroups.  sktiming */
+#define DAWN_POLICY_GLDS_NO_TILE256    0x400       /* direct-to-LDS path: never that tile (automatic for 3x3 convs of <= 64 channels).  A/B */
+#define DAWN_POLICY_STREAMK            0x400       /* (same bit) the persistent stream-K 3x3 kernel where sk_ws is supplied.  sktiming (profiles/r3_conv_sk_vs_v2_in_benchmark.txt) */
+#define DAWN_POLICY_HALO               0x800       /* LDS-halo fp32 kernel for prologue-free 3x3 / s1 / p1 convs.  shipped (profiles/r1_l_conv_halo.txt) */
+#define DAWN_POLICY_SPLIT              0x1000      /* split-operand (bf16 pipe) kernels where w_bf3 is supplied.  shipped (profiles/r1_n_conv_bf16.txt) */
+#define DAWN_POLICY_NINE_TERMS         0x2000      /* all 9 cross terms instead of 6, direct kernels only (no Winograd form).  A/B: the accuracy yardstick of the tests */
+#define DAWN_POLICY_SPLIT_V2           0x4000      /* second-generation split 3x3 kernel (conv3x3_bf16_v2_kernel).  shipped (profiles/r1_n_conv_bf16.txt) */
+#define DAWN_POLICY_TILE128_ALWAYS     0x8000      /* tiled split 1x1 GEMM: 128 x 64 tiles for every eligible shape.  A/B (profiles/r2_gemm1x1_tiles_128x64.txt) */
+#define DAWN_POLICY_TILE128_NEVER      0x10000     /* tiled split 1x1 GEMM: never 128 x 64 tiles (the round-1 tile policy).  A/B (profiles/r2_gemm1x1_tiles_128x64.txt) */
+#define DAWN_POLICY_NO_ROW_KERNELS     0x20000     /* the tiled kernel for every split 1x1 shape: no row-stationary / resample kernels.  A/B */
+#define DAWN_POLICY_XCD_LAUNCH_ORDER   0x80000     /* tiled split 1x1 GEMM: tiles dealt to the XCDs in launch order.  A/B; read RAW (policy_raw_bit): outside both masks */
+#define DAWN_POLICY_VARIANT(n)         ((n) << 16) /* field, shift 16 width 4.  ablation: build n of the split 3x3 kernel (1, 2, 4, 7 ablated, 8 = s_memtime stamps); sktiming: priority period */
+#define DAWN_POLICY_VARIANT_MASK       0xF0000     /* OVERLAP, only under -DDAWN_ABLATION: its values 1, 2, 8 ARE TILE128_NEVER, NO_ROW_KERNELS, XCD_LAUNCH_ORDER; the shipped mask keeps the first two, drops the rest */
+#define DAWN_POLICY_STAGGER(n)         ((n) << 20) /* field, shift 20 width 4: start delay of workgroup sets (split v2, Winograd; sktiming: slots left free).  A/B (profiles/r5_wino4_stagger.txt); DROPPED by the -DDAWN_ABLATION mask although both Winograd units read it */
+#define DAWN_POLICY_STAGGER_MASK       0xF00000    /* the bits of that field */
+#define DAWN_POLICY_MFMA_K32           0x1000000   /* split v2 kernel on v_mfma_f32_16x16x32_bf16 (two cross terms per instruction).  shipped (profiles/r3_k32_shapes.txt) */
+#define DAWN_POLICY_WINO2              0x2000000   /* Winograd F(2x2,3x3) form where w_wino is supplied and dawn_conv3x3_wino_ok.  shipped (profiles/r4_wino_insitu_per_shape.txt) */
+#define DAWN_POLICY_WINO2_DEEP_ONLY    0x4000000   /* ... but the direct kernel for convs of fewer than 128 input channels.  A/B: slower (profiles/r5_ab_gn_sums_and_per_shape_policy.txt) */
+#define DAWN_POLICY_WINO4              0x8000000   /* Winograd F(4x4,3x3) form where w_wino4 is supplied, dawn_conv3x3_wino4_ok and the shape measured faster (64 channels at width 64, <= 128 at width 32).  shipped (profiles/r5_ab_wino4_policy_in_benchmark.txt) */
+#define DAWN_POLICY_WINO4_ALL_SHAPES   0x10000000  /* with WINO4: wherever the form fits.  A/B (profiles/r5_insitu_shapes_wino4_everywhere_vs_gated.txt) */
+#define DAWN_POLICY_WINO_REVERSE       0x20000000  /* both Winograd kernels walk their tiles last frame first (bit-identical outputs).  shipped (profiles/r5_ab_wino_reverse_order.txt) */
+#define DAWN_POLICY_ABL_ROW_FETCH      0x40000000  /* row-stationary GEMMs fetch rows line-coalesced into the wrong lanes.  ablation (profiles/r5_row_fetch_pattern_ablation.txt); read RAW (policy_raw_bit): outside both masks */
+#define DAWN_CONV_POLICY_DEFAULT /* = 0x2B00580D */ (DAWN_POLICY_BK32 | DAWN_POLICY_XCD_ORDER | DAWN_POLICY_GLDS | DAWN_POLICY_HALO | DAWN_POLICY_SPLIT | \
+                                  DAWN_POLICY_SPLIT_V2 | DAWN_POLICY_MFMA_K32 | DAWN_POLICY_WINO2 | DAWN_POLICY_WINO4 | DAWN_POLICY_WINO_REVERSE)
 
 /* ---- A3 GroupNorm(8) statistics over (C/8, F, H, W) (MT:230,235; nn.GroupNorm on a 5-D tensor) --
  * partial: per-block fp64 (sum, sumsq) per group -> part[nblk][16]; reduce: fixed-order sum ->
@@ -212,10 +243,12 @@ int dawn_temporal_attn(const float* qkv, int Fext, int HW, int q0, int Fq, int w
                        const float* rot_cos, const float* rot_sin, const float* band,
                        float* out, void* stream);
 /* the same with flags: 0 = automatic (S and P.V on the bf16 matrix pipe with exactly split operands where the shape is covered:
- * win <= 48, at most 256 queries, K / V planes of the buffer in LDS, >= 128 pixel columns; the fp32-MFMA kernel otherwise), bit 0 = the
- * fp32-MFMA kernel, bit 1 = the split-operand 32 x 32 kernel whatever the number of pixel columns.  Round 6: bit 2 = the window-tiled 13-wave kernel
- * (16-query tiles, csrc/temporal_layer16.hip: temporal_attn13_kernel; win <= 40, Fext <= 208, at most 13 query tiles: error -39 outside).  Opt-in:
- * 4..9 % faster than the 32 x 32 kernel in isolation, 0.3 % slower inside the benchmark (the core is bound by its reads of the (rows, 768) tensor) */
+ * win <= 48, at most 256 queries, K / V planes of the buffer in LDS, >= 128 pixel columns; the fp32-MFMA kernel otherwise) */
+#define DAWN_TA_FP32          1   /* the fp32-MFMA kernel even where the split-operand kernel covers the shape.  A/B, tests */
+#define DAWN_TA_SPLIT_ALWAYS  2   /* the split-operand 32 x 32 kernel whatever the number of pixel columns.  A/B, tests */
+#define DAWN_TA_WAVE13        4   /* the window-tiled 13-wave kernel (16-query tiles, temporal_attn13_kernel; win <= 40, Fext <= 208, at most 13 query
+                                     tiles: error -39 outside).  A/B: +4..9 % isolated, -0.3 % in the benchmark (profiles/r6_temporal_attn13_ab.txt) */
+#define DAWN_TA_PIXEL_HEAD_MAJOR 16  /* with WAVE13 only: qkv is [pixel][head][q | k | v][buffer row][32] (the layout experiment of DESIGN 8).  A/B */
 int dawn_temporal_attn_ex(const float* qkv, int Fext, int HW, int q0, int Fq, int win,
                           const float* rot_cos, const float* rot_sin, const float* band,
                           float* out, int flags, void* stream);
@@ -228,12 +261,11 @@ int dawn_temporal_attn_ex(const float* qkv, int Fext, int HW, int q0, int Fq, in
 int dawn_temporal_layer_c64(const float* x, int Fext, int HW, int q0, int Fq, int win, const float* wqkv,
                             const void* wqkv_bf3, const float* wout, const float* rot_cos, const float* rot_sin,
                             const float* band, float eps, float* out, void* stream);
-/* same, with a kernel-family selector for A/B measurements and tests: flags & 7 = 0 automatic (what the entry point above
- * does), m + 1 forces WMODE m: 0 fp32 MFMA with weights from L2, 1 fp32 MFMA with per-head weight slices in LDS, 2 Q/K/V
+/* same, with a kernel-family selector for A/B measurements and tests (DAWN_TL_* below): force field 0 = automatic (what the entry
+ * point above does), DAWN_TL_FORCE_WMODE(m) forces WMODE m: 0 fp32 MFMA with weights from L2, 1 fp32 MFMA with per-head weight slices in LDS, 2 Q/K/V
  * projections on the bf16 pipe (exact 3-way operand split), 3 additionally S = K.Q^T and O = V^T.P^T on the bf16 pipe
  * (K / V split once per head into bf16 planes in LDS, Q / P split from the accumulators; fits up to Fext ~ 200 rows:
- * the benchmark clip); flags & 16 adds explicit sched_group_barrier MFMA/VALU interleave hints to WMODE 3 (measured: within noise, 1550 vs 1513 us); flags & 32 keeps
- * the out-projection of WMODE 3 on the fp32 MFMA even when wout_bf3p is given.  wout_bf3p (optional, WMODE 3): the exact
+ * the benchmark clip).  wout_bf3p (optional, WMODE 3): the exact
  * 3-way bf16 split of to_out with the rows of every head permuted to the accumulator order of O^T, [256/16][3][2][64][8]
  * (pack.pack_bf3_temporal_out).  All families compute the same function to fp32 round-off.
  * `out` MAY BE `x` when the layer covers its whole frame buffer (q0 == 0, Fq == Fext): a workgroup reads the rows of its pixel
@@ -241,11 +273,17 @@ int dawn_temporal_layer_c64(const float* x, int Fext, int HW, int q0, int Fq, in
  * one tensor less through the caches).
  * Round 6 (ABI 8): WMODE 4 = the WINDOW-tiled kernel (csrc/temporal_layer16.hip): 16-query tiles against the 16 + 2 win <= 96 keys
  * of their window (only the key blocks that exist at the clip ends) on v_mfma_f32_16x16x32_bf16, 12 waves, the head's work split
- * into two SIMD-balanced phases by dawn_tl16_schedule.  Automatic (flags & 7 == 0) whenever both split weight images are given,
- * win <= 40 and Fext <= 208; flags & 7 == 5 forces it (error if the shape is outside), flags & 256 keeps the 32 x 32 kernel.
+ * into two SIMD-balanced phases by dawn_tl16_schedule.  Automatic whenever both split weight images are given,
+ * win <= 40 and Fext <= 208; forced: error if the shape is outside; DAWN_TL_KEEP_32X32 keeps the 32 x 32 kernel.
  * WMODE 5 = the same window tiling with ONE query tile per wave (13 waves of 128 registers instead of 8 of 256: no wave runs two tiles one
- * after the other): taken first by the automatic choice whenever the query range has at most 13 tiles (208 - delta frames); flags & 7 == 6
- * forces it. */
+ * after the other): taken first by the automatic choice whenever the query range has at most 13 tiles (208 - delta frames). */
+#define DAWN_TL_FORCE_MASK     7            /* the force field: 0 = automatic */
+#define DAWN_TL_FORCE_WMODE(m) ((m) + 1)    /* its value that forces WMODE m (0..5); error -36 / -37 / -38 where WMODE 3 / 4 / 5 does not cover the shape */
+#define DAWN_TL_SCHED_HINTS    16           /* WMODE 3 with explicit sched_group_barrier MFMA / VALU interleave hints.  A/B: within noise (1550 vs 1513 us) */
+#define DAWN_TL_OUT_FP32       32           /* WMODE 3 keeps its out-projection on the fp32 MFMA even when wout_bf3p is given.  A/B, tests */
+#define DAWN_TL_NO_FIXED200    64           /* WMODE 3 without the fixed 200-row LDS layout of clips of <= 200 buffer rows.  A/B, tests */
+#define DAWN_TL_NO_KVI         128          /* WMODE 3 projects K / V one wave per 32-row tile, not as 2 nrt (tile, K | V) items dealt over the waves (KVI).  A/B, tests */
+#define DAWN_TL_KEEP_32X32     256          /* automatic choice without the window-tiled kernels (WMODE 4 / 5).  A/B, tests */
 int dawn_temporal_layer_c64_ex(const float* x, int Fext, int HW, int q0, int Fq, int win, const float* wqkv,
                                const void* wqkv_bf3, const float* wout, const void* wout_bf3p, const float* rot_cos,
                                const float* rot_sin, const float* band, float eps, float* out, int flags, void* stream);

@@ -36,12 +36,13 @@ import warnings
 
 import torch
 
+from dawn_pytorch_amd.policy import ConvPolicy
 from test_hip_ops import LOG      # the op-error log every GPU op test appends to (test_hip_ops.check)
 
 C_GATE = 2.0          # the factor of the whole file; a case widens it only with a measured reason stated beside it
 FLOOR = 1e-7          # relative to max|want64|: ~1 ulp of fp32 at the output's scale
-DEFAULT_POLICY = 0x2B00580D
-TILED_ONLY = DEFAULT_POLICY | 0x20000     # policy bit 0x20000: the tiled split kernel for every 1x1 shape (reaches its nS = 2 corner)
+DEFAULT_POLICY = ConvPolicy.DEFAULT
+TILED_ONLY = ConvPolicy.TILED_ONLY        # DEFAULT | NO_ROW_KERNELS: the tiled split kernel for every 1x1 shape (reaches its nS = 2 corner)
 
 
 # ---------------------------------------------------------------------------------------------- the gate

@@ -304,7 +304,7 @@ class Case:
 
 
 def _hconv(name, **p):
-    # BK of the generic kernel's K loop: 32 where K >= 2304 and N >= 256 (conv_gemm.hip `deep`, and policy bit 0 at K >= 4096), else 16
+    # BK of the generic kernel's K loop: 32 where K >= 2304 and N >= 256 (conv_gemm.hip `deep`, and ConvPolicy.BK32 at K >= 4096), else 16
     K = p.get("KW", 1) * p["C0"]
     return Case(f"hubert_conv/{name}", "hconv", bk=32 if K >= 2304 and p["N"] >= 256 else 16, **p)
 

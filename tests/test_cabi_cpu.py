@@ -82,3 +82,46 @@ def test_ctx_structs_match_header():
     # dawn_shard_comm: void* user; int rank, world; five function pointers
     assert ctypes.sizeof(ctx.ShardCommC) == 8 + 4 + 4 + 5 * 8
     assert ctx.ShardCommC.halo_begin.offset == 16 and ctx.ShardCommC.allreduce_min_u32.offset == 48
+
+
+def header_constants(prefix):
+    """({NAME: value}, {NAME: function}) of include/dawn_hip.h's object-like `#define <prefix>NAME value` (and anonymous-enum
+    `<prefix>NAME = value`) and function-like `#define <prefix>NAME(x) (expression in x)` constants, names without the prefix."""
+    src = open(os.path.join(ROOT, "include", "dawn_hip.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S).replace("\\\n", " ")
+    env = {}            # every DAWN_* constant: a body may name earlier ones (an OR of names, FIELD(15))
+    for name, arg, body in re.findall(r"^#define (DAWN_[A-Z0-9_]+)(\(\w+\))?[ \t]+(.+)$", src, flags=re.M):
+        env[name] = eval(f"lambda {arg[1:-1]}: {body}" if arg else body, env)          # ((n) << 16), a | b: C and Python agree
+    for name, value in re.findall(r"\b(DAWN_[A-Z0-9_]+) *= *(\w+)", src):
+        env[name] = eval(value, env)
+    mine = {n[len(prefix):]: v for n, v in env.items() if n.startswith(prefix)}
+    return ({n: v for n, v in mine.items() if not callable(v)}, {n: v for n, v in mine.items() if callable(v)})
+
+
+def test_python_names_equal_header_values():
+    """policy.ConvPolicy / TemporalFlags / TemporalAttnFlags and ctx.OPT_* are the header's table, name for name and value for value,
+    and every named composition is the literal the tests and tools used to spell."""
+    from dawn_pytorch_amd import ctx, policy
+    CP = policy.ConvPolicy
+    compositions = {"FP32_TILES": 0xD, "EXACT_FP32": 0x80D, "HALO_V1": 0x180D, "HALO_V1_NINE": 0x380D, "DIRECT_V2": 0x580D,
+                    "DIRECT_V2_NINE": 0x780D, "DIRECT_V2_K32": 0x100580D, "DIRECT_V2_TILE128": 0xD80D, "WINO": 0x300580D,
+                    "WINO4_EVERYWHERE": 0x1B00580D, "DEFAULT": 0x2B00580D, "TILED_ONLY": 0x2B02580D}
+    for name, value in compositions.items():
+        assert int(CP[name]) == value, name
+    assert int(CP.DEFAULT) == 0x2B00580D
+    default, _ = header_constants("DAWN_CONV_POLICY_")
+    assert default == {"DEFAULT": 0x2B00580D}
+    for prefix, cls, extra in (("DAWN_POLICY_", CP, set(compositions)), ("DAWN_TL_", policy.TemporalFlags, set()),
+                               ("DAWN_TA_", policy.TemporalAttnFlags, set())):
+        consts, funcs = header_constants(prefix)
+        assert len(consts) >= 4, prefix
+        members = {n: int(m) for n, m in cls.__members__.items()}            # (aliases of one bit included)
+        assert set(members) - extra == set(consts), (prefix, set(members) - extra ^ set(consts))
+        for name, value in consts.items():
+            assert members[name] == value, (prefix, name)
+        for name, f in funcs.items():                                        # DAWN_POLICY_VARIANT(n) == ConvPolicy.variant(n), ...
+            for n in range(6):
+                assert int(getattr(cls, name.lower())(n)) == f(n), (prefix, name, n)
+    assert set(header_constants("DAWN_POLICY_")[1]) == {"VARIANT", "STAGGER"} and set(header_constants("DAWN_TL_")[1]) == {"FORCE_WMODE"}
+    opts, _ = header_constants("DAWN_OPT_")
+    assert opts == {n[4:]: getattr(ctx, n) for n in dir(ctx) if n.startswith("OPT_")} and len(opts) == 7

@@ -6,6 +6,7 @@ import ctypes as C
 import pytest
 
 from dawn_pytorch_amd import _lib
+from dawn_pytorch_amd.policy import ConvPolicy as CP
 
 DEFAULT, FAKE = 0, 0x1000          # policy 0 = the shipped default; FAKE = any non-null 16-byte aligned "device pointer"
 
@@ -39,7 +40,7 @@ def form(d):
     (dict(), 2),                                                    # level 0, 64 -> 64 channels: the F(4x4) form (shipped per-shape gate)
     (dict(wino4=False), 1),                                         # no F(4x4) image: F(2x2)
     (dict(C0=64, C1=64), 1),                                        # 128 input channels at width 64: F(2x2) (F(4x4) measured slower there)
-    (dict(C0=64, C1=64, policy=0x2B00580D | 0x10000000), 2),        # ... unless the policy takes F(4x4) wherever it fits
+    (dict(C0=64, C1=64, policy=CP.DEFAULT | CP.WINO4_ALL_SHAPES), 2),   # ... unless the policy takes F(4x4) wherever it fits
     (dict(H=32, W=32, C0=128, N=128), 2),                           # level 1, up to 128 input channels: F(4x4)
     (dict(H=32, W=32, C0=128, C1=128, N=128), 1),                   # level 1, 256 input channels: F(2x2)
     (dict(H=8, W=8, C0=512, N=512), 1),                             # deepest level: F(2x2)
@@ -49,9 +50,9 @@ def form(d):
     (dict(stride=2), 0),
     (dict(tr=True), 0),                                             # the `+ SiLU(GN(c2))` epilogue exists in the GEMM kernels only
     (dict(C0=64, C1=64, wino4=False, ld1=128), 0),                  # two sources with different row strides: the F(2x2) kernel's one offset table cannot serve them
-    (dict(policy=0x2B00580D & ~0x2000000 & ~0x8000000), 0),         # both Winograd bits off
-    (dict(policy=0x2B00580D & ~0x8000000), 1),                      # F(4x4) bit off
-    (dict(policy=0x2B00580D | 0x2000), 0),                          # all nine cross terms: the direct kernel only
+    (dict(policy=CP.DEFAULT & ~CP.WINO2 & ~CP.WINO4), 0),           # both Winograd bits off
+    (dict(policy=CP.DEFAULT & ~CP.WINO4), 1),                       # F(4x4) bit off
+    (dict(policy=CP.DEFAULT | CP.NINE_TERMS), 0),                   # all nine cross terms: the direct kernel only
     (dict(H=4, W=4, F=400, C0=512, N=512), 0),                      # 4 x 4-pixel frames (configs[1]'s deepest level): the 36-segment direct kernel
 ])
 def test_conv3x3_form(kw, want):

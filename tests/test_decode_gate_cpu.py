@@ -13,6 +13,7 @@ import torch
 
 import decode_gate as D
 from dawn_pytorch_amd import _lib
+from dawn_pytorch_amd.policy import ConvPolicy as CP
 
 IDS = [c.name for c in D.CASES]
 
@@ -123,7 +124,7 @@ def test_direct_form_answers():
     assert direct_form(**dict(base, F=3, H=5, W=64)) == 0                    # M % 64 != 0: neither v2 nor v1, the fp32 kernels
     assert _lib.lib().dawn_conv3x3_direct_form(None) == 0
     FAKE = 0x1000
-    for change, want in (({}, D.V2_WN1), ({"w_bf3": 0}, 0), ({"policy": 0x2B00580D & ~0x4000}, D.HALO), ({"KH": 1, "KW": 1, "pad": 0}, 0),
+    for change, want in (({}, D.V2_WN1), ({"w_bf3": 0}, 0), ({"policy": CP.DEFAULT & ~CP.SPLIT_V2}, D.HALO), ({"KH": 1, "KW": 1, "pad": 0}, 0),
                          ({"stride": 2}, 0), ({"w_wino": FAKE}, 0)):
         d = _lib.ConvDesc()
         d.in0, d.C0, d.ld0 = FAKE, 64, 64

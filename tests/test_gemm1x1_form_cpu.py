@@ -6,6 +6,7 @@ import ctypes as C
 import pytest
 
 from dawn_pytorch_amd import _lib
+from dawn_pytorch_amd.policy import ConvPolicy as CP
 
 NONE, TILED, ROWREG, ROWACC, RESAMPLE = 0, 1, 2, 3, 4
 DEFAULT, FAKE = 0, 0x1000          # policy 0 = the shipped default; FAKE = any non-null 16-byte aligned "device pointer"
@@ -66,9 +67,9 @@ def form(d):
     (dict(M=51200, N=768, C0=128, ld0=130), NONE),                  # a row stride that is no multiple of 16 bytes
     (dict(M=51200, N=768, C0=128, gn=True), NONE),                  # fused GroupNorm statistics: not in these kernels
     (dict(M=51200, N=128, C0=128, down=True, tr=True), NONE),       # resample with an epilogue it does not have
-    (dict(M=51200, N=768, C0=128, policy=0x2B00580D | 0x20000), TILED),     # policy bit 0x20000: the tiled kernel for every shape
-    (dict(M=51200, N=128, C0=128, down=True, policy=0x2B00580D | 0x20000), NONE),
-    (dict(M=51200, N=768, C0=128, policy=0x2B00580D & ~0x1000), NONE),      # split kernels off
+    (dict(M=51200, N=768, C0=128, policy=CP.TILED_ONLY), TILED),     # NO_ROW_KERNELS: the tiled kernel for every shape
+    (dict(M=51200, N=128, C0=128, down=True, policy=CP.TILED_ONLY), NONE),
+    (dict(M=51200, N=768, C0=128, policy=CP.DEFAULT & ~CP.SPLIT), NONE),      # split kernels off
 ])
 def test_gemm1x1_form(kw, want):
     assert form(desc(**kw)) == want

@@ -12,6 +12,7 @@ import torch
 from conftest import ROOT, load_golden, golden_sd
 from oracle import dawn_oracle as O
 import dawn_pytorch_amd as D
+from dawn_pytorch_amd.policy import ConvPolicy
 
 pytestmark = pytest.mark.gpu
 T = torch.from_numpy
@@ -187,7 +188,7 @@ def test_benchmark_size_kernel_families_agree(Tn, res):
     """At BASELINE's full size (256x256, 200 frames, DAWN_256 architecture) the CPU oracle takes minutes, so parity is
     checked through a size-independent property: one denoiser evaluation computed with the shipped kernel policy
     (split-operand bf16-pipe convs / GEMMs, LayerNorm in the GEMM loader, 256x64 / 256x128 tile policy, XCD remap) must
-    agree with the same evaluation on the exact-fp32-MFMA kernels (policy 0x80D: a different kernel family for every
+    agree with the same evaluation on the exact-fp32-MFMA kernels (ConvPolicy.EXACT_FP32: a different kernel family for every
     conv and projection; both families are checked against the oracle at small sizes).  Tolerance: 3e-5 x max|y| (measured 3.9e-6) --
     ~300 chained fp32 ops whose summation orders differ."""
     import sys
@@ -204,7 +205,7 @@ def test_benchmark_size_kernel_families_agree(Tn, res):
     x = torch.randn(3, Tn, h, h, generator=torch.Generator().manual_seed(9)).to(dev)
     try:
         y_split = unet_forward(ops, P, cs, x, 500)
-        ops.conv_policy = 0x80D
+        ops.conv_policy = ConvPolicy.EXACT_FP32
         y_fp32 = unet_forward(ops, P, cs, x, 500)
     finally:
         ops.conv_policy = 0                       # shipped policy

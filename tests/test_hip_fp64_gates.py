@@ -13,6 +13,7 @@ import pytest
 import torch
 
 import split_gate as G
+from dawn_pytorch_amd.policy import TemporalAttnFlags as TA, TemporalFlags as TF
 from oracle.ops_ref import RefOps
 
 pytestmark = pytest.mark.gpu
@@ -89,20 +90,21 @@ def test_conv_split_fp64_gate(hip, case):
 
 
 # ---------------------------------------------------------------------------------------------- attention layers
-# temporal_flags: m + 1 forces WMODE m (4: the window-tiled kernel, 5: its tile-per-wave form); 256 = automatic without WMODE 4
-TEMPORAL_FLAGS = (0, 1, 2, 3, 4, 5, 6, 256)
+# temporal_flags: automatic, every forced WMODE (4: the window-tiled kernel, 5: its tile-per-wave form), automatic without WMODE 4 / 5
+WMODE = TF.force_wmode
+TEMPORAL_FLAGS = (0, WMODE(0), WMODE(1), WMODE(2), WMODE(3), WMODE(4), WMODE(5), TF.KEEP_32X32)
 
 
 def temporal_fits(flags, Fext, q0, Fq, win=40):
     """The shapes each forced WMODE instantiates (the same exclusions as test_hip_ops.test_temporal_layer_c64)."""
-    if flags in (5, 6) and (win > 40 or Fext > 208):
+    if flags in (WMODE(4), WMODE(5)) and (win > 40 or Fext > 208):
         return False
-    if flags == 6 and (Fq + (q0 - win) % 16 + 15) // 16 > 13:
+    if flags == WMODE(5) and (Fq + (q0 - win) % 16 + 15) // 16 > 13:
         return False
-    if flags & 7 == 4 and (Fext * 576 + ((Fext + 31) // 32) * 6144 + 8 * (32 * ((32 + 2 * win + 31) // 32) + 32) * 4 > 163840
+    if flags & TF.FORCE_MASK == WMODE(3) and (Fext * 576 + ((Fext + 31) // 32) * 6144 + 8 * (32 * ((32 + 2 * win + 31) // 32) + 32) * 4 > 163840
                            or Fq + (q0 - win) % 16 > 256):
         return False
-    return not (flags == 2 and Fext > 192)
+    return not (flags == WMODE(1) and Fext > 192)
 
 
 def attention_call(hip, case, T, Wkn):
@@ -141,7 +143,7 @@ def test_temporal_layer_fp64_gate(hip, case):
             ran.append(flags)
     finally:
         hip.temporal_flags = 0
-    assert 0 in ran and len(ran) >= 4, ran           # (at Fext 280 flags 2, 4, 5 and 6 do not fit: 0, 1, 3 and 256 run)
+    assert 0 in ran and len(ran) >= 4, ran           # (at Fext 280 WMODE 1, 3, 4 and 5 do not fit: automatic, WMODE 0, 2 and KEEP_32X32 run)
 
 
 OTHER_ATTN = [c for c in G.CASES if c.kind in ("temporal_seg", "sla", "xattn")]
@@ -158,9 +160,9 @@ def test_attention_layer_fp64_gate(hip, case):
 
 
 # ---------------------------------------------------------------------------------------------- attention cores of the unfused levels
-# temporal_attn_flags (dawn_temporal_attn_ex): 0 automatic, 1 the fp32-MFMA kernel, 2 the split-operand EXT core on any grid, 4 the opt-in
+# temporal_attn_flags (dawn_temporal_attn_ex): automatic, the fp32-MFMA kernel, the split-operand EXT core on any grid, the opt-in
 # window-tiled 13-wave core
-TATTN_FLAGS = (0, 1, 2, 4)
+TATTN_FLAGS = (0, TA.FP32, TA.SPLIT_ALWAYS, TA.WAVE13)
 TATTN_CASES = [c for c in G.CASES if c.kind == "tattn"]
 
 
@@ -190,7 +192,7 @@ def test_temporal_attn_fp64_gate(hip, case):
     ran = []
     try:
         for flags in TATTN_FLAGS:
-            if flags == 4 and not attn13_fits(p["F"], p.get("q0", 0), p.get("Fq", p["F"])):
+            if flags == TA.WAVE13 and not attn13_fits(p["F"], p.get("q0", 0), p.get("Fq", p["F"])):
                 continue
             hip.temporal_attn_flags = flags
             got = core_call(hip, case, T)

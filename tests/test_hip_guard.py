@@ -11,6 +11,7 @@ import torch
 
 import test_hip_ops as T
 import test_hip_upconv as UP
+from dawn_pytorch_amd.policy import ConvPolicy as CP, TemporalAttnFlags as TA_, TemporalFlags as TF
 from guarded import GuardedOps
 from oracle.ops_ref import RefOps
 from test_hip_fp64_gates import TEMPORAL_FLAGS, temporal_fits
@@ -121,11 +122,11 @@ CONV3 = {c[0]: c for c in (
 )}
 
 # form name -> (policy, weight images handed over, (dawn_conv3x3_form, dawn_gemm1x1_form) of a 3x3 conv)
-FORMS3 = {f"fp32_v{p}": (p, (), (0, 0)) for p in (0, 7, 141, 269, 525, 1037, 13, 2061)}          # the eight policies of test_conv_gemm
+FORMS3 = {f"fp32_v{int(p)}": (p, (), (0, 0)) for p in T.FP32_POLICIES}          # the eight policies of test_conv_gemm
 FORMS3.update({
-    "split_v1": (6157, ("w_bf3",), (0, 0)),
-    "split_v2": (22541, ("w_bf3",), (0, 0)),
-    "split_v2_16x16x32": (22541 | 0x1000000, ("w_bf3",), (0, 0)),
+    "split_v1": (CP.HALO_V1, ("w_bf3",), (0, 0)),
+    "split_v2": (CP.DIRECT_V2, ("w_bf3",), (0, 0)),
+    "split_v2_16x16x32": (CP.DIRECT_V2_K32, ("w_bf3",), (0, 0)),
     "wino2": (T.WINO, ("w_bf3", "w_wino"), (1, 0)),
     "wino4": (T.WINO4, ("w_bf3", "w_wino", "w_wino4"), (2, 0)),
 })
@@ -141,7 +142,7 @@ WINO_FALLBACK = {("c3x3_ragged_M", "wino2"): (0, 0), ("c3x3_ragged_M", "wino4"):
 
 # dawn_conv3x3_form / dawn_gemm1x1_form answer (0, 0) for the fp32 kernels, the direct split kernel v1 (conv3x3_halo_bf16_kernel) and v2
 # (conv3x3_bf16_v2_kernel) alike, so form_only cannot tell these apart.  What does: the bits (the split kernels round differently from the fp32
-# ones; a launch that fell through to the fp32 kernel is bit-identical to policy 2061, whose fp32 bits the split policies share) and, where the
+# ones; a launch that fell through to the fp32 kernel is bit-identical to ConvPolicy.EXACT_FP32, whose fp32 bits the split policies share) and, where the
 # grids differ, gn_part.dawn_rows (the launch's workgroup count).  Every multi-frame kernel of the 3x3 family -- both split kernels, the fp32 halo
 # kernel, Winograd F(2x2) -- takes whole tiles only (M a multiple of its row tile AND F a multiple of the frames per tile): no kernel ever
 # receives a ragged multi-frame tile, the ragged-F shapes run conv_gemm_glds_kernel / conv_gemm_kernel on 128-row tiles with a ragged last
@@ -202,10 +203,10 @@ def test_conv3x3(g, case, form):
         return
     # which kernel ran (form_only cannot say: see DIRECT)
     kernel = DIRECT.get((case, form), "v1" if form == "split_v1" else "v2")
-    f32, f32_rows = cached(("fp32_bits", case), lambda: run_conv(g, c, "fp32_v2061", 2061, (0, 0)))
+    f32, f32_rows = cached(("fp32_bits", case), lambda: run_conv(g, c, "fp32_exact", CP.EXACT_FP32, (0, 0)))
     M = c.rows_out
     if kernel == "fp32":
-        assert torch.equal(got, f32), f"{case}/{form}: expected to fall through to the fp32 kernel, but the bits differ from policy 2061"
+        assert torch.equal(got, f32), f"{case}/{form}: expected to fall through to the fp32 kernel, but the bits differ from ConvPolicy.EXACT_FP32"
         assert rows == f32_rows
     else:
         assert not torch.equal(got, f32), f"{case}/{form}: bit-identical to the fp32 kernel: the split kernel did not run"
@@ -248,10 +249,10 @@ def test_gemm1x1_split_forms(g, p):
     c = gemm_case(*p)
     run_conv(g, c, "shipped", 0, (0, GEMM_FORM[p]), ("w_bf3",))
     if GEMM_FORM[p] == TILED:
-        run_conv(g, c, "tiles128x64", 22541 | 0x8000, (0, TILED), ("w_bf3",))
-        run_conv(g, c, "nine_terms", 30733, (0, TILED), ("w_bf3",))
+        run_conv(g, c, "tiles128x64", CP.DIRECT_V2_TILE128, (0, TILED), ("w_bf3",))
+        run_conv(g, c, "nine_terms", CP.DIRECT_V2_NINE, (0, TILED), ("w_bf3",))
     elif GEMM_FORM[p] != NONE:
-        run_conv(g, c, "tiled_for_every_shape", 0x2B00580D | 0x20000, (0, TILED if p[3] != 64 else NONE), ("w_bf3",))       # (N = 64 tiles stay on the fp32 kernel)
+        run_conv(g, c, "tiled_for_every_shape", CP.TILED_ONLY, (0, TILED if p[3] != 64 else NONE), ("w_bf3",))       # (N = 64 tiles stay on the fp32 kernel)
 
 
 @pytest.mark.parametrize("p,ln", [((6400, 64, 64, 64, ""), True), ((6400, 256, 0, 128, ""), True)], ids=["rowreg", "rowacc"])
@@ -266,9 +267,9 @@ def test_gemm1x1_layernorm_inside(g, p, ln):
 @pytest.mark.parametrize("p,form", [((6400, 96, 0, 256, "tr"), TILED), ((6400, 64, 64, 64, "tr"), ROWREG), ((6400, 256, 0, 128, "res"), ROWACC)],
                          ids=["tiled", "rowreg", "rowacc"])
 def test_gemm1x1_split_forms_accept_no_ragged_M(g, p, form):
-    """Every split 1x1 form takes whole 256-row panels only (the 128 x 64-tile configuration of the tiled kernel, policy bit 0x8000, too: its
+    """Every split 1x1 form takes whole 256-row panels only (the 128 x 64-tile configuration of the tiled kernel, ConvPolicy.TILE128_ALWAYS, too: its
     plan asks M % 256 == 0 although it steps in 128 rows): from the smallest M on, dawn_gemm1x1_form of the same descriptor answers NONE for
-    every M that is no multiple of 256, under the shipped policy and under 0x8000 -- nothing is there to find, which is what is asserted -- and
+    every M that is no multiple of 256, under the shipped policy and under TILE128_ALWAYS -- nothing is there to find, which is what is asserted -- and
     the fp32 kernel that serves such an M instead is guarded."""
     import ctypes
     from dawn_pytorch_amd import _lib
@@ -287,13 +288,13 @@ def test_gemm1x1_split_forms_accept_no_ragged_M(g, p, form):
         if "tr" in extra:
             d.tr, d.ld_tr, d.tr_a, d.tr_b = FAKE, N, FAKE, FAKE
         return g.L.dawn_gemm1x1_form(ctypes.byref(d))
-    for policy in (0, 22541 | 0x8000):
-        assert form_of(M, policy) == form, policy          # (the row kernels keep their shapes under 0x8000)
+    for policy in (0, CP.DIRECT_V2_TILE128):
+        assert form_of(M, policy) == form, policy          # (the row kernels keep their shapes under TILE128_ALWAYS)
         for m in list(range(M - 255, M)) + list(range(M + 1, M + 256)) + [2 * M + 128, 8 * M - 1, 204800 + 128]:
             assert form_of(m, policy) == NONE, (m, policy)
     c = gemm_case(M + 128, C0, C1, N, extra)
     run_conv(g, c, "ragged_M_on_fp32", 0, (0, NONE), ("w_bf3",))
-    run_conv(g, c, "ragged_M_on_fp32_tiles128x64", 22541 | 0x8000, (0, NONE), ("w_bf3",))
+    run_conv(g, c, "ragged_M_on_fp32_tiles128x64", CP.DIRECT_V2_TILE128, (0, NONE), ("w_bf3",))
 
 
 def resample_case(kind, F, H, W, Cc):
@@ -340,7 +341,7 @@ def test_upconv_phase_kernels(g, key, border, form):
     kw = {k: (v.cpu() if torch.is_tensor(v) else v) for k, v in u.kw.items()}
     c = Conv("upconv_F%d_%dx%d_C%d_N%d" % key, u.x, None, u.wp.cpu(), u.N, kw, u.want(border),
              dict(w_bf3=None if u.ws is None else u.ws.cpu()), chk=UP.check)
-    policy = UP.SHIPPED_POLICY & ~8 if form == "reg" else 0
+    policy = CP.DEFAULT & ~CP.GLDS if form == "reg" else 0
     run_conv(g, c, f"{form}/border{border}", policy, (0, RESAMPLE if form == "split" else NONE), ("w_bf3",) if form == "split" else (),
              border=border)
 
@@ -376,8 +377,8 @@ def test_conv_epilogue_operands(g, name):
             kw["tr"] = (rnd(F * Ho * Wo, N, seed=9), rnd(N, seed=10) * 0.3 + 1.0, rnd(N, seed=11) * 0.3)
         return Conv(name, in0, in1, w, N, kw, ref.conv_gemm(in0, w, N, in1=in1, **kw))
     c = cached(("epi", name), make)
-    for policy in (0, 2061, UP.SHIPPED_POLICY & ~8):
-        run_conv(g, c, f"v{policy}", policy, (0, 0))
+    for policy in (0, CP.EXACT_FP32, CP.DEFAULT & ~CP.GLDS):
+        run_conv(g, c, f"v{int(policy)}", policy, (0, 0))
 
 
 # ---------------------------------------------------------------------------------------------- fused 64-channel layers, attention cores
@@ -408,7 +409,7 @@ def temporal_args(g, c):
 # HW = 64 case (and the HW >= 64 cases of test_temporal_attn below) is left to that test for run time; so that more than a few pixel columns, and a
 # count that is no multiple of 4 (nor of the 16 / 32-column tiles), are guarded, one short clip at HW = 130 is added to both
 TL_SHAPES = [tuple(s) for s in params(T.test_temporal_layer_c64) if s[0] * s[1] <= 600] + [(12, 130, 0, 12, 3), (20, 130, 3, 14, 5)]
-TL = [(s, fl) for s in TL_SHAPES for fl in TEMPORAL_FLAGS + (4 | 16, 4 | 32) if temporal_fits(fl, s[0], s[2], s[3], s[4])]
+TL = [(s, fl) for s in TL_SHAPES for fl in TEMPORAL_FLAGS + (TF.force_wmode(3) | TF.SCHED_HINTS, TF.force_wmode(3) | TF.OUT_FP32) if temporal_fits(fl, s[0], s[2], s[3], s[4])]
 
 
 @pytest.mark.parametrize("shape,flags", TL, ids=["F%d_HW%d_q%d_%d_w%d" % s + f"_flags{fl}" for s, fl in TL])
@@ -435,8 +436,8 @@ def test_temporal_layer_c64_segmented(g, Fext, HW, q0, Fq):
 TA_SHAPES = [tuple(s) for s in params(T.test_temporal_attn) if s[0] * s[1] <= 400] + [(12, 130, 0, 12, 3), (20, 130, 3, 14, 5)]
 
 
-TA = [(s, fl) for s in TA_SHAPES for fl in (0, 1, 2, 4)
-      if fl != 4 or (s[4] <= 40 and s[0] <= 208 and (s[3] + (s[2] - s[4]) % 16 + 15) // 16 <= 13)]          # (the 13-wave kernel's instantiation)
+TA = [(s, fl) for s in TA_SHAPES for fl in (0, TA_.FP32, TA_.SPLIT_ALWAYS, TA_.WAVE13)
+      if fl != TA_.WAVE13 or (s[4] <= 40 and s[0] <= 208 and (s[3] + (s[2] - s[4]) % 16 + 15) // 16 <= 13)]          # (the 13-wave kernel's instantiation)
 
 
 @pytest.mark.parametrize("shape,flags", TA, ids=["F%d_HW%d_q%d_%d_w%d" % s + f"_flags{fl}" for s, fl in TA])
@@ -591,7 +592,7 @@ def test_c64_attention_layers_in_place(g, F, HW):
         g.verify()
         g.inputs_intact(overwritten=("x",))
 
-    for split, flags in ((False, 0), (True, 0), (True, 4)):
+    for split, flags in ((False, 0), (True, 0), (True, TF.force_wmode(3))):
         g.temporal_flags = flags
         both(lambda xg, out: g.temporal_layer_c64(
             xg, F, HW, 0, F, win, *[gin(g, t, n) for t, n in ((wqkv, "wqkv"), (wout, "wout"), (rc, "rcos"), (rs, "rsin"), (band, "band"))],

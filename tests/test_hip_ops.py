@@ -12,9 +12,16 @@ import pytest
 import torch
 
 from conftest import ROOT
+from dawn_pytorch_amd.policy import ConvPolicy as CP, TemporalAttnFlags as TA, TemporalFlags as TF
 from oracle.ops_ref import RefOps
 
 pytestmark = pytest.mark.gpu
+
+WMODE = TF.force_wmode             # temporal_flags that force WMODE m
+# every fp32-MFMA tile configuration: automatic, 256 x 64 tiles, the direct-to-LDS path with BK = 32 / three stages / with and without its
+# 256 x 64 tile, the shipped fp32 tiles, and those with the LDS-halo 3x3 kernel
+FP32_POLICIES = (0, CP.BK32 | CP.TILE256 | CP.XCD_ORDER, CP.FP32_TILES | CP.GLDS_BK32, CP.FP32_TILES | CP.GLDS_STAGES3,
+                 CP.FP32_TILES | CP.GLDS_TILE256, CP.FP32_TILES | CP.GLDS_NO_TILE256, CP.FP32_TILES, CP.EXACT_FP32)
 
 LOG = os.path.join(ROOT, "gpurun_out", "op_errors.jsonl")
 
@@ -114,13 +121,13 @@ def test_conv_gemm(hip, ref, case):
     if ex.get("tr"):
         kw["tr"] = (rnd(F * Ho * Wo, N, seed=9), rnd(N, seed=10) * 0.3 + 1.0, rnd(N, seed=11) * 0.3)
     want = ref.conv_gemm(in0, w, N, in1=in1, **kw)
-    for variant in (0, 7, 141, 269, 525, 1037, 13, 2061):   # every fp32-MFMA tile configuration
+    for variant in FP32_POLICIES:
         hip.conv_policy = variant
         _conv_case(hip, name + f"/v{variant}", in0, in1, w, N, kw, want)
     if k == 3 and C0 % 16 == 0 and C1 % 16 == 0:
         from dawn_pytorch_amd.pack import pack_bf3, unpack_kn
         kw["w_bf3"] = pack_bf3(unpack_kn(w)).cuda()
-        for variant in (14349, 30733, 6157, 22541, 22541 | 0x1000000):   # split-operand bf16 MFMA: 9 / 6 terms, v1 / v2 kernels, v2 on 16x16x32
+        for variant in (CP.HALO_V1_NINE, CP.DIRECT_V2_NINE, CP.HALO_V1, CP.DIRECT_V2, CP.DIRECT_V2_K32):   # split-operand bf16 MFMA: 9 / 6 terms, v1 / v2 kernels, v2 on 16x16x32
             hip.conv_policy = variant
             _conv_case(hip, name + f"/v{variant}", in0, in1, w, N, kw, want)
     hip.conv_policy = 0                            # shipped policy (left active)
@@ -135,7 +142,7 @@ def _conv_case(hip, name, in0, in1, w, N, kw, want):
 
 
 # ---------------------------------------------------------------------------------------------- Winograd F(2x2,3x3) split conv
-WINO = 0x580D | 0x1000000 | 0x2000000              # shipped policy + the Winograd form where w_wino is supplied
+WINO = CP.WINO                                     # shipped policy + the Winograd form where w_wino is supplied
 WINO_CASES = [
     # name, F, H, W, C0, C1, N, extras
     ("L0_64x64_4rows", 3, 64, 64, 64, 0, 64, {"bias": True, "gn": True}),                  # tile = 4 rows: 2 x 32 Winograd tiles
@@ -184,7 +191,7 @@ def test_conv3x3_winograd(hip, ref, case):
     x0g, x1g, wg = in0.cuda(), None if in1 is None else in1.cuda(), w.cuda()
     try:
         outs = []
-        for variant in (WINO, 0x580D | 0x1000000):
+        for variant in (WINO, CP.DIRECT_V2_K32):
             hip.conv_policy = variant
             part = hip.conv_gn_part(rows, N, x0g) if ex.get("gn") else None
             got = hip.conv_gemm(x0g, wg, N, in1=x1g, gn_part=part, **gkw)
@@ -277,7 +284,7 @@ def test_conv_wino_is_fp32_accurate(hip, ref):
         w4 = wkn.reshape(3, 3, Cc, N).permute(3, 2, 0, 1)
         want = F_.conv2d(x.double().reshape(F, H, W, Cc).permute(0, 3, 1, 2), w4, padding=1).permute(0, 2, 3, 1).reshape(rows, N)
         ws, ww = pack_bf3(unpack_kn(w)).cuda(), pack_wino_bf3(_w5_from_packed(w, Cc, N)).cuda()
-        for variant in (2061, 0x580D | 0x1000000, WINO):
+        for variant in (CP.EXACT_FP32, CP.DIRECT_V2_K32, WINO):
             hip.conv_policy = variant
             got = hip.conv_gemm(x.cuda(), w.cuda(), N, F=F, Hi=H, Wi=W, KH=3, KW=3, pad=1, w_bf3=ws, w_wino=ww)
             torch.cuda.synchronize()
@@ -286,12 +293,12 @@ def test_conv_wino_is_fp32_accurate(hip, ref):
     with open(LOG, "a") as f:
         f.write(json.dumps({"op": "conv_wino/rel_err_vs_fp64", **{f"{t}/{v:#x}": e for (t, v), e in errs.items()}}) + "\n")
     for tag in ("n01", "spread"):
-        assert errs[(tag, WINO)] <= 3.0 * errs[(tag, 0x580D | 0x1000000)] + 1e-7, errs
+        assert errs[(tag, WINO)] <= 3.0 * errs[(tag, CP.DIRECT_V2_K32)] + 1e-7, errs
 
 
 
 # ---------------------------------------------------------------------------------------------- Winograd F(4x4,3x3) split conv (opt-in)
-WINO4 = WINO | 0x8000000 | 0x10000000          # the F(4x4) form wherever its geometry fits (0x8000000 alone: only the shapes it wins on)
+WINO4 = CP.WINO4_EVERYWHERE                    # the F(4x4) form wherever its geometry fits (CP.WINO4 alone: only the shapes it wins on)
 WINO4_CASES = [
     # name, F, H, W, C0, C1, N, extras
     ("L0_64x64", 3, 64, 64, 64, 0, 64, {"bias": True, "gn": True}),                         # tile = 4 rows x 64 columns: 1 x 16 Winograd tiles
@@ -364,7 +371,7 @@ REV_CASES = [WINO_CASES[i] for i in (0, 1, 4, 6, 8, 11, 12, 13)] + [("F4:" + c[0
 
 @pytest.mark.parametrize("case", REV_CASES, ids=[c[0] for c in REV_CASES])
 def test_conv_wino_reverse_tile_order(hip, case):
-    """Policy bit 0x20000000: both Winograd kernels walk their tiles back to front (last frame first).  A tile's arithmetic does not depend
+    """ConvPolicy.WINO_REVERSE: both Winograd kernels walk their tiles back to front (last frame first).  A tile's arithmetic does not depend
     on the order: the outputs must be BIT-identical to the front-to-back launch; the GroupNorm partial sums of a workgroup add the
     same tiles in the opposite order (fp64): fused coefficients equal to summation rounding."""
     from dawn_pytorch_amd.pack import pack_bf3, pack_wino_bf3, pack_wino4_bf3, unpack_kn
@@ -383,7 +390,7 @@ def test_conv_wino_reverse_tile_order(hip, case):
     try:
         hip.begin_evaluation(in0)
         res = []
-        for pol in (base, base | 0x20000000):
+        for pol in (base, base | CP.WINO_REVERSE):
             hip.conv_policy = pol
             part = hip.conv_gn_part(rows, N, in0)
             got = hip.conv_gemm(in0, w.cuda(), N, in1=in1, gn_part=part, gn_fin=(gamma, beta, None, rows), **kw)
@@ -399,7 +406,7 @@ def test_conv_wino_reverse_tile_order(hip, case):
 
 def test_conv_wino4_is_fp32_accurate(hip, ref):
     """VERDICT r4 #1b's gate: against an fp64 convolution the F(4x4,3x3) kernel's error stays within 5x the exact-fp32-MFMA kernel's
-    (policy 2061) on N(0,1) data and on data spread over 10 decades (measured ~2x: the points 0, +-3/4, +-3/2 -- tools/wino4_points.py)."""
+    (ConvPolicy.EXACT_FP32) on N(0,1) data and on data spread over 10 decades (measured ~2x: the points 0, +-3/4, +-3/2 -- tools/wino4_points.py)."""
     import torch.nn.functional as F_
     from dawn_pytorch_amd.pack import pack_bf3, pack_wino_bf3, pack_wino4_bf3, unpack_kn
     F, H, W, Cc, N = 4, 32, 32, 128, 128
@@ -414,7 +421,7 @@ def test_conv_wino4_is_fp32_accurate(hip, ref):
         want = F_.conv2d(x.double().reshape(F, H, W, Cc).permute(0, 3, 1, 2), w4, padding=1).permute(0, 2, 3, 1).reshape(rows, N)
         w5 = _w5_from_packed(w, Cc, N)
         ws, ww, ww4 = pack_bf3(unpack_kn(w)).cuda(), pack_wino_bf3(w5).cuda(), pack_wino4_bf3(w5).cuda()
-        for variant in (2061, 0x580D | 0x1000000, WINO, WINO4):
+        for variant in (CP.EXACT_FP32, CP.DIRECT_V2_K32, WINO, WINO4):
             hip.conv_policy = variant
             got = hip.conv_gemm(x.cuda(), w.cuda(), N, F=F, Hi=H, Wi=W, KH=3, KW=3, pad=1, w_bf3=ws, w_wino=ww, w_wino4=ww4)
             torch.cuda.synchronize()
@@ -423,7 +430,7 @@ def test_conv_wino4_is_fp32_accurate(hip, ref):
     with open(LOG, "a") as f:
         f.write(json.dumps({"op": "conv_wino4/rel_err_vs_fp64", **{f"{t}/{v:#x}": e for (t, v), e in errs.items()}}) + "\n")
     for tag in ("n01", "spread"):
-        assert errs[(tag, WINO4)] <= 5.0 * errs[(tag, 2061)] + 1e-7, errs
+        assert errs[(tag, WINO4)] <= 5.0 * errs[(tag, CP.EXACT_FP32)] + 1e-7, errs
 
 
 @pytest.mark.parametrize("F,H,W,C0,N", [(3, 16, 16, 64, 64), (2, 8, 8, 128, 256), (5, 8, 8, 16, 16), (1, 40, 37, 32, 128),
@@ -435,7 +442,8 @@ def test_conv_gemm_fused_gn_stats(hip, ref, F, H, W, C0, N):
     gamma, beta = rnd(N, seed=4) * 0.2 + 1, rnd(N, seed=5) * 0.2
     from dawn_pytorch_amd.pack import pack_bf3, unpack_kn
     ws = pack_bf3(unpack_kn(w)).cuda() if C0 % 16 == 0 else None
-    for variant in (5, 525, 13, 2061, 6157, 22541, 22541 | 0x1000000):
+    for variant in (CP.BK32 | CP.XCD_ORDER, CP.FP32_TILES | CP.GLDS_TILE256, CP.FP32_TILES, CP.EXACT_FP32, CP.HALO_V1, CP.DIRECT_V2,
+                    CP.DIRECT_V2_K32):
         hip.conv_policy = variant
         xg = x.cuda()
         part = hip.conv_gn_part(rows, N, xg)
@@ -461,21 +469,21 @@ def test_conv_bf16_split_is_fp32_accurate(hip, ref):
     w4 = wkn.reshape(3, 3, Cc, N).permute(3, 2, 0, 1)
     want = F_.conv2d(x.double().reshape(F, H, W, Cc).permute(0, 3, 1, 2), w4, padding=1).permute(0, 2, 3, 1).reshape(rows, N)
     errs = {}
-    K32 = 22541 | 0x1000000
-    for variant, ws in ((2061, None), (6157, pack_bf3(unpack_kn(w)).cuda()), (14349, pack_bf3(unpack_kn(w)).cuda()),
-                        (22541, pack_bf3(unpack_kn(w)).cuda()), (K32, pack_bf3(unpack_kn(w)).cuda())):
+    FP32, V1, V1_NINE, V2, K32 = CP.EXACT_FP32, CP.HALO_V1, CP.HALO_V1_NINE, CP.DIRECT_V2, CP.DIRECT_V2_K32
+    for variant, ws in ((FP32, None), (V1, pack_bf3(unpack_kn(w)).cuda()), (V1_NINE, pack_bf3(unpack_kn(w)).cuda()),
+                        (V2, pack_bf3(unpack_kn(w)).cuda()), (K32, pack_bf3(unpack_kn(w)).cuda())):
         hip.conv_policy = variant
         got = hip.conv_gemm(x.cuda(), w.cuda(), N, F=F, Hi=H, Wi=W, KH=3, KW=3, pad=1, w_bf3=ws)
         torch.cuda.synchronize()
         errs[variant] = float((got.cpu().double() - want).abs().max() / want.abs().max())
     with open(LOG, "a") as f:
-        f.write(json.dumps({"op": "conv_bf16_split/rel_err_vs_fp64", "fp32_mfma": errs[2061], "bf16x6": errs[6157],
-                            "bf16x9": errs[14349], "bf16x6_v2": errs[22541], "bf16x6_v2_16x16x32": errs[K32]}) + "\n")
+        f.write(json.dumps({"op": "conv_bf16_split/rel_err_vs_fp64", "fp32_mfma": errs[FP32], "bf16x6": errs[V1],
+                            "bf16x9": errs[V1_NINE], "bf16x6_v2": errs[V2], "bf16x6_v2_16x16x32": errs[K32]}) + "\n")
     hip.conv_policy = 0
-    assert errs[6157] <= 2.0 * errs[2061] + 1e-7, errs
-    assert errs[22541] <= 2.0 * errs[2061] + 1e-7, errs
-    assert errs[K32] <= 2.0 * errs[2061] + 1e-7, errs
-    assert errs[14349] <= 2.0 * errs[2061] + 1e-7, errs
+    assert errs[V1] <= 2.0 * errs[FP32] + 1e-7, errs
+    assert errs[V2] <= 2.0 * errs[FP32] + 1e-7, errs
+    assert errs[K32] <= 2.0 * errs[FP32] + 1e-7, errs
+    assert errs[V1_NINE] <= 2.0 * errs[FP32] + 1e-7, errs
 
 
 @pytest.mark.parametrize("M,K,N,res,bias", [(51200, 128, 768, False, False), (51200, 256, 128, True, True),
@@ -491,7 +499,7 @@ def test_gemm1x1_split(hip, ref, M, K, N, res, bias):
         kw["bias"] = rnd(N, seed=4)
     want = ref.conv_gemm(x, w, N, **kw)
     gkw = {k_: (v.cuda() if torch.is_tensor(v) else v) for k_, v in kw.items()}
-    for variant in (22541, 30733, 22541 | 0x8000):           # shipped policy, 9 cross terms, 128 x 64 tiles (2 WG / CU)
+    for variant in (CP.DIRECT_V2, CP.DIRECT_V2_NINE, CP.DIRECT_V2_TILE128):   # shipped policy, 9 cross terms, 128 x 64 tiles (2 WG / CU)
         hip.conv_policy = variant
         got = hip.conv_gemm(x.cuda(), w.cuda(), N, w_bf3=pack_bf3(unpack_kn(w)).cuda(), **gkw)
         torch.cuda.synchronize()
@@ -567,7 +575,7 @@ def test_gemm1x1_split_variants(hip, ref, M, C0, C1, N, extra):
     got = hip.conv_gemm(x0g, w.cuda(), N, in1=None if x1 is None else x1.cuda(), w_bf3=pack_bf3(unpack_kn(w)).cuda(), out=out, **gkw)
     torch.cuda.synchronize()
     check(f"gemm1x1_split_variants/M{M}_C{C0}+{C1}_N{N}_{extra}", got, want)
-    hip.conv_policy = 22541 | 0x8000                          # the 128 x 64-tile configuration of the same kernel
+    hip.conv_policy = CP.DIRECT_V2_TILE128                    # the 128 x 64-tile configuration of the same kernel
     got_small = hip.conv_gemm(x0g, w.cuda(), N, in1=None if x1 is None else x1.cuda(), w_bf3=pack_bf3(unpack_kn(w)).cuda(),
                               out=None if out is None else torch.empty_like(out), **gkw)
     hip.conv_policy = 0
@@ -580,7 +588,7 @@ def test_gemm1x1_split_variants(hip, ref, M, C0, C1, N, extra):
     if out is not None:
         assert float(big[:, :N].min()) == 7.0 and float(big[:, 2 * N:].max()) == 7.0       # neighbours untouched
     # and it is the split kernel's accuracy class: no worse than the fp32 MFMA path against fp64
-    hip.conv_policy = 2061
+    hip.conv_policy = CP.EXACT_FP32
     got32 = hip.conv_gemm(x0.cuda(), w.cuda(), N, in1=None if x1 is None else x1.cuda(), **gkw)
     hip.conv_policy = 0
     e_split, e_f32 = float((got.cpu() - want).abs().max()), float((got32.cpu() - want).abs().max())
@@ -851,9 +859,9 @@ def test_temporal_attn(hip, ref, Fext, HW, q0, Fq, win):
     got = hip.temporal_attn(qkv.cuda(), Fext, HW, q0, Fq, win, rc.cuda(), rs.cuda(), band.cuda())
     check(f"temporal_attn/F{Fext}_q{q0}_{Fq}_w{win}", got, want, 2e-5)
     try:                                                        # both kernels explicitly: fp32 MFMA / split operands on any grid
-        hip.temporal_attn_flags = 1
+        hip.temporal_attn_flags = TA.FP32
         got32 = hip.temporal_attn(qkv.cuda(), Fext, HW, q0, Fq, win, rc.cuda(), rs.cuda(), band.cuda())
-        hip.temporal_attn_flags = 2
+        hip.temporal_attn_flags = TA.SPLIT_ALWAYS
         got16 = hip.temporal_attn(qkv.cuda(), Fext, HW, q0, Fq, win, rc.cuda(), rs.cuda(), band.cuda())
     finally:
         hip.temporal_attn_flags = 0
@@ -861,7 +869,7 @@ def test_temporal_attn(hip, ref, Fext, HW, q0, Fq, win):
     check(f"temporal_attn_split/F{Fext}_q{q0}_{Fq}_w{win}", got16, want, 2e-5)
     if win <= 40 and Fext <= 208 and (Fq + (q0 - win) % 16 + 15) // 16 <= 13:      # the window-tiled 13-wave kernel, on any grid
         try:
-            hip.temporal_attn_flags = 4
+            hip.temporal_attn_flags = TA.WAVE13
             got13 = hip.temporal_attn(qkv.cuda(), Fext, HW, q0, Fq, win, rc.cuda(), rs.cuda(), band.cuda())
         finally:
             hip.temporal_attn_flags = 0
@@ -871,7 +879,7 @@ def test_temporal_attn(hip, ref, Fext, HW, q0, Fq, win):
 @pytest.mark.parametrize("Fext,HW,q0,Fq,win", [(200, 256, 0, 200, 40), (200, 130, 47, 120, 40), (184, 128, 0, 184, 40), (120, 128, 31, 70, 24),
                                                  (208, 128, 8, 200, 40), (200, 128, 40, 120, 40)])
 def test_temporal_attn_13wave_at_chip_filling_grids(hip, ref, Fext, HW, q0, Fq, win):
-    """temporal_attn13_kernel (opt-in, flags bit 2) at chip-filling grids (>= 128 pixel columns: the 128- / 256-channel levels of the benchmark,
+    """temporal_attn13_kernel (opt-in, TemporalAttnFlags.WAVE13) at chip-filling grids (>= 128 pixel columns: the 128- / 256-channel levels of the benchmark,
     the 120-query segments of longer clips and T-shard ranks): against the oracle and the 32 x 32 kernel, and eight runs bit-identical (the kernel
     keeps the fused layer's load / compute regions: a load that lands in the registers of an MFMA still in flight shows up as a different tile
     every run)."""
@@ -883,14 +891,14 @@ def test_temporal_attn_13wave_at_chip_filling_grids(hip, ref, Fext, HW, q0, Fq, 
     args = (qkv.cuda(), Fext, HW, q0, Fq, win, rc.cuda(), rs.cuda(), band.cuda())
     old = hip.temporal_attn(*args)                                   # automatic: the 32 x 32 split kernel
     try:
-        hip.temporal_attn_flags = 4
+        hip.temporal_attn_flags = TA.WAVE13
         got = hip.temporal_attn(*args)
         check(f"temporal_attn_13wave/F{Fext}_HW{HW}_q{q0}_{Fq}_w{win}", got, want, 2e-5)
         check(f"temporal_attn_13wave_vs_32x32/F{Fext}_HW{HW}", got, old, 2e-5)
         for _ in range(7):
             assert torch.equal(hip.temporal_attn(*args), got)
-        # the layout experiment (flags bit 4): the same rows in the (pixel, head)-major layout [pixel][head][q | k | v][buffer row][32]
-        hip.temporal_attn_flags = 4 | 16
+        # the layout experiment (TemporalAttnFlags.PIXEL_HEAD_MAJOR): the same rows in the (pixel, head)-major layout [pixel][head][q | k | v][buffer row][32]
+        hip.temporal_attn_flags = TA.WAVE13 | TA.PIXEL_HEAD_MAJOR
         ph = qkv.view(Fext, HW, 3, 8, 32).permute(1, 3, 2, 0, 4).contiguous().view(Fext * HW, 768).cuda()
         assert torch.equal(hip.temporal_attn(ph, *args[1:]), got)
     finally:
@@ -918,18 +926,19 @@ def test_temporal_layer_c64(hip, ref, Fext, HW, q0, Fq, win):
     wosp = pack_bf3_temporal_out(unpack_kn(wout)).cuda()
     got = hip.temporal_layer_c64(*gpu(x), Fext, HW, q0, Fq, win, *gpu(wqkv, wout, rc, rs, band), wqkv_bf3=wsplit)
     check(f"temporal_layer_c64_split/F{Fext}_q{q0}_{Fq}_w{win}", got, want, 3e-5)
-    # every kernel family explicitly (flags: m + 1 forces WMODE m; 16 = WMODE 3 without the interleave hints)
+    # every kernel family explicitly
     try:
-        for flags, name in ((1, "wmode0"), (2, "wmode1"), (3, "wmode2"), (4, "wmode3"), (4 | 16, "wmode3_hints"),
-                            (4 | 32, "wmode3_out_fp32"), (5, "wmode4_window_tiled"), (6, "wmode5_tile_per_wave"), (256, "auto_without_wmode4")):
-            if flags in (5, 6) and (win > 40 or Fext > 208):
+        for flags, name in ((WMODE(0), "wmode0"), (WMODE(1), "wmode1"), (WMODE(2), "wmode2"), (WMODE(3), "wmode3"),
+                            (WMODE(3) | TF.SCHED_HINTS, "wmode3_hints"), (WMODE(3) | TF.OUT_FP32, "wmode3_out_fp32"), (WMODE(4), "wmode4_window_tiled"),
+                            (WMODE(5), "wmode5_tile_per_wave"), (TF.KEEP_32X32, "auto_without_wmode4")):
+            if flags in (WMODE(4), WMODE(5)) and (win > 40 or Fext > 208):
                 continue                                         # outside the window-tiled kernels' instantiation
-            if flags == 6 and (Fq + (q0 - win) % 16 + 15) // 16 > 13:
+            if flags == WMODE(5) and (Fq + (q0 - win) % 16 + 15) // 16 > 13:
                 continue                                         # more than 13 query tiles
-            if flags & 7 == 4 and (Fext * 576 + ((Fext + 31) // 32) * 6144 + 8 * (32 * ((32 + 2 * win + 31) // 32) + 32) * 4 > 163840
+            if flags & TF.FORCE_MASK == WMODE(3) and (Fext * 576 + ((Fext + 31) // 32) * 6144 + 8 * (32 * ((32 + 2 * win + 31) // 32) + 32) * 4 > 163840
                                    or Fq + (q0 - win) % 16 > 256):
                 continue                                         # WMODE 3 does not fit this shape (LDS)
-            if flags == 2 and Fext > 192:
+            if flags == WMODE(1) and Fext > 192:
                 continue                                         # weight slices in LDS need the room
             hip.temporal_flags = flags
             got = hip.temporal_layer_c64(*gpu(x), Fext, HW, q0, Fq, win, *gpu(wqkv, wout, rc, rs, band), wqkv_bf3=wsplit,
@@ -955,7 +964,8 @@ def test_temporal_attention_trained_weight_like_range(hip, ref):
     want = ref.temporal_layer_c64(x, Fext, HW, q0, Fq, win, wqkv, wout, rc, rs, band)
     wsplit, wosp = pack_bf3(unpack_kn(wqkv)).cuda(), pack_bf3_temporal_out(unpack_kn(wout)).cuda()
     try:
-        for flags, name in ((0, "default"), (1, "wmode0"), (3, "wmode2"), (4, "wmode3"), (5, "wmode4_window_tiled"), (6, "wmode5_tile_per_wave")):
+        for flags, name in ((0, "default"), (WMODE(0), "wmode0"), (WMODE(2), "wmode2"), (WMODE(3), "wmode3"), (WMODE(4), "wmode4_window_tiled"),
+                            (WMODE(5), "wmode5_tile_per_wave")):
             hip.temporal_flags = flags
             got = hip.temporal_layer_c64(*gpu(x), Fext, HW, q0, Fq, win, *gpu(wqkv, wout, rc, rs, band), wqkv_bf3=wsplit,
                                          wout_bf3p=wosp)
@@ -983,9 +993,9 @@ def test_temporal_layer16_is_run_to_run_deterministic(hip, F):
     rc, rs, band = ang.cos().contiguous().cuda(), ang.sin().contiguous().cuda(), rnd(2 * win + 1, 8, seed=5).cuda()
     kw = dict(wqkv_bf3=pack_bf3(unpack_kn(wqkv)).cuda(), wout_bf3p=pack_bf3_temporal_out(unpack_kn(wout)).cuda())
     try:
-        hip.temporal_flags = 4
+        hip.temporal_flags = WMODE(3)
         want = hip.temporal_layer_c64(x, F, HW, 0, F, win, *gpu(wqkv, wout), rc, rs, band, **kw)
-        for flags in (5, 6):
+        for flags in (WMODE(4), WMODE(5)):
             hip.temporal_flags = flags
             first = hip.temporal_layer_c64(x, F, HW, 0, F, win, *gpu(wqkv, wout), rc, rs, band, **kw)
             check(f"temporal_layer16_vs_wmode3/F{F}_flags{flags}", first, want.cpu(), 3e-5)
@@ -1052,8 +1062,8 @@ def test_c64_attention_layers_in_place(hip, F, HW):
     rc, rs, band = ang.cos().contiguous().cuda(), ang.sin().contiguous().cuda(), rnd(2 * win + 1, 8, seed=5).cuda()
     wsplit, wosp = pack_bf3(unpack_kn(wqkv)).cuda(), pack_bf3_temporal_out(unpack_kn(wout)).cuda()
     try:
-        for kw, flags in (({}, 0), ({"wqkv_bf3": wsplit, "wout_bf3p": wosp}, 0), ({"wqkv_bf3": wsplit, "wout_bf3p": wosp}, 4)):
-            hip.temporal_flags = flags                                # 0 with both images: the window-tiled kernel; 4: the 32 x 32 one
+        for kw, flags in (({}, 0), ({"wqkv_bf3": wsplit, "wout_bf3p": wosp}, 0), ({"wqkv_bf3": wsplit, "wout_bf3p": wosp}, WMODE(3))):
+            hip.temporal_flags = flags                                # 0 with both images: the window-tiled kernel; WMODE 3: the 32 x 32 one
             want = hip.temporal_layer_c64(x, F, HW, 0, F, win, *gpu(wqkv, wout), rc, rs, band, **kw)
             xin = x.clone()
             got = hip.temporal_layer_c64(xin, F, HW, 0, F, win, *gpu(wqkv, wout), rc, rs, band, out=xin, **kw)

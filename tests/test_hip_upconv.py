@@ -14,11 +14,12 @@ from fullsize_cases import KW, build_inputs, checksum
 from upconv_cases import BORDER_MODE, TINY_KW, literal_rows, tiny_upconv_sd
 import dawn_pytorch_amd as D
 from dawn_pytorch_amd import _lib
+from dawn_pytorch_amd.policy import ConvPolicy
 from dawn_pytorch_amd.pack import pack_bf3, pack_kn, upconv_w_kn_phases
 
 pytestmark = pytest.mark.gpu
 T = torch.from_numpy
-SHIPPED_POLICY = 0x2B00580D
+SHIPPED_POLICY = ConvPolicy.DEFAULT
 DAWN_SPLIT1X1_RESAMPLE = 4
 
 
@@ -90,9 +91,9 @@ SPLIT_SHAPES = [(50, 16, 16, 64), (25, 16, 32, 64), (50, 16, 16, 128), (200, 8, 
 @pytest.mark.parametrize("glds", [True, False], ids=["shipped_policy", "no_direct_to_lds"])
 @pytest.mark.parametrize("F,H,W,C,N", FP32_SHAPES)
 def test_fp32_kernels_every_border(hip, F, H, W, C, N, glds):
-    """Both fp32 kernels gather a border: conv_gemm_glds_kernel under the shipped policy, conv_gemm_kernel with policy bit 3 cleared."""
+    """Both fp32 kernels gather a border: conv_gemm_glds_kernel under the shipped policy, conv_gemm_kernel with ConvPolicy.GLDS cleared."""
     c = case(F, H, W, C, N)
-    hip.conv_policy = 0 if glds else SHIPPED_POLICY & ~8
+    hip.conv_policy = 0 if glds else SHIPPED_POLICY & ~ConvPolicy.GLDS
     try:
         assert hip.conv_gemm(c.xg, c.wp, N, border=1, form_only=True, **c.kw)[1] == 0          # no split kernel here
         for border in (0, 1, 2):
@@ -118,7 +119,7 @@ def test_split_kernel_every_border(hip, F, H, W, C):
 @pytest.mark.parametrize("key,split", [((50, 16, 16, 64, 64), True), ((3, 4, 16, 64, 64), False)], ids=["split_50x16x16", "fp32_3x4x16"])
 def test_border_is_confined_to_the_outer_ring(hip, key, split):
     c = case(*key)
-    policies = [0] if split else [0, SHIPPED_POLICY & ~8]
+    policies = [0] if split else [0, SHIPPED_POLICY & ~ConvPolicy.GLDS]
     try:
         for pol in policies:
             hip.conv_policy = pol

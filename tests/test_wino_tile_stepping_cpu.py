@@ -1,6 +1,6 @@
 """Index contract of the Winograd kernels' tile bookkeeping (conv3x3_wino.hip / conv3x3_wino4.hip, round 5): a workgroup's tiles are G apart,
 so (column tile, first image row, frame) advance by constants -- two integer divisions per launch instead of two per tile -- and the same
-stepping runs backwards for the back-to-front tile order (policy bit 0x20000000).  The stepping restated here (same formulas, same carries)
+stepping runs backwards for the back-to-front tile order (ConvPolicy.WINO_REVERSE).  The stepping restated here (same formulas, same carries)
 must reproduce the direct decomposition of every tile index the kernel's setup() computes, for every geometry the launchers accept."""
 import itertools
 

@@ -1,6 +1,6 @@
 #!/bin/bash
 # GPU box: whole-benchmark A/B of bench.py argument sets, alternating inside ONE gpurun call.
-#   bash tools/ab_flags.sh 3 "" "--temporal-attn-flags 1"
+#   bash tools/ab_flags.sh 3 "" "--temporal-attn-flags 1"      (1 = TemporalAttnFlags.FP32)
 cd "$(dirname "$0")/.."
 R=$1; shift
 mkdir -p gpurun_out

@@ -2,7 +2,7 @@
 cd "$(dirname "$0")/.."
 O=gpurun_out
 for r in 1 2; do
-  for p in 0x580D 0x100580D; do
+  for p in 0x580D 0x100580D; do      # ConvPolicy.DIRECT_V2, DIRECT_V2_K32
     python tools/profile_conv_shapes.py --no-overlap --policy $p 2>/dev/null | grep "k=3x3" | sed "s/^/r$r $p /" >> $O/r3_k32_shapes.txt
   done
 done

@@ -1,6 +1,7 @@
 #!/bin/bash
 # GPU box: A/B of conv kernel policies inside the whole benchmark, alternating within ONE gpurun call (boxes and power /
 # thermal state differ between calls).   bash tools/ab_policy.sh "0x580D 0x5C0D 0x5C4D" [rounds] [extra bench.py args]
+# (ConvPolicy.DIRECT_V2, | STREAMK, | STREAMK | SK_PRIO_ALT: dawn-pytorch_amd/policy.py names the bits)
 cd "$(dirname "$0")/.."
 POL=${1:-"0x580D 0x5C0D"}; R=${2:-2}; shift; shift
 mkdir -p gpurun_out

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """GPU tool: interleaved A/B of temporal-layer kernel variants (flags) in ONE process -- run-to-run / box-to-box noise on the
 shared pool is +-3 %, so variants are alternated and the per-variant minimum and median over the repeats are printed.
-    python tools/ab_temporal.py 4 4|16 4|128 ..."""
+    python tools/ab_temporal.py 4 '4|16' '4|128' ...      (integers: TemporalFlags.force_wmode(3), | SCHED_HINTS, | NO_KVI)"""
 import os, sys
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

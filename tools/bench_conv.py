@@ -7,6 +7,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from dawn_pytorch_amd.ops import HipOps
+from dawn_pytorch_amd.policy import ConvPolicy
 from dawn_pytorch_amd.pack import pack_kn, pack_bf3
 
 CASES = {   # name: (F, H, W, C0, C1, N, k, stride, pad, rowstats)
@@ -26,7 +27,7 @@ CASES = {   # name: (F, H, W, C0, C1, N, k, stride, pad, rowstats)
 ap = argparse.ArgumentParser()
 ap.add_argument("--cases", default=",".join(CASES))
 ap.add_argument("--iters", type=int, default=10)
-ap.add_argument("--variants", default="7")
+ap.add_argument("--variants", default=str(int(ConvPolicy.BK32 | ConvPolicy.TILE256 | ConvPolicy.XCD_ORDER)), help="conv policies, comma separated integers")
 ap.add_argument("--data", default="randn", choices=["randn", "zero", "const"], help="operand values (the chip clocks to its power budget: zeros run faster than random data)")
 ap.add_argument("--gn", action="store_true", help="emit GroupNorm partial sums from the conv epilogue (as the ResBlock convs do)")
 a = ap.parse_args()
@@ -52,7 +53,7 @@ for variant, name in itertools.product([int(v, 0) for v in a.variants.split(",")
     w = pack_kn(w_kn).to(dev)
     b = torch.randn(N, device=dev)
     kw = dict(F=F, Hi=H, Wi=W, KH=k, KW=k, stride=st, pad=pad, in1=x1, bias=b)
-    if k == 3 and (variant & 0x1000):
+    if k == 3 and (variant & ConvPolicy.SPLIT):
         kw["w_bf3"] = pack_bf3(w_kn).to(dev)
     if rs:
         kw["row_stats"] = (torch.randn(rows, device=dev) * 0.1, torch.rand(rows, device=dev) + 0.5)

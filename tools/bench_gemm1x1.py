@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """GPU microbenchmark of the split-operand 1x1 GEMMs (dawn_conv_gemm with w_bf3) at the benchmark's projection shapes.
-    python tools/bench_gemm1x1.py [--policy 0x580D,0x2580D] [--iters 20]"""
+    python tools/bench_gemm1x1.py [--policy 0x580D,0x2580D] [--iters 20]      (integers: ConvPolicy.DIRECT_V2, DIRECT_V2 | NO_ROW_KERNELS)"""
 import argparse, os, sys
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

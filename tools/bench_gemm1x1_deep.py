@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """GPU microbenchmark of the split-operand 1x1 GEMMs at the row counts of the deeper levels (M = 12,800 / 51,200):
-    python tools/bench_gemm1x1_deep.py [--iters 20] [--policy 0x2B08580D]
+    python tools/bench_gemm1x1_deep.py [--iters 20] [--policy 0x2B08580D]      (ConvPolicy.DEFAULT | XCD_LAUNCH_ORDER)
 Back-to-back launches of one shape (operands warm in L2 / the memory-side cache) and launches separated by a 1 GB fill (cold)."""
 import argparse, os, sys
 import torch
@@ -17,7 +17,7 @@ CASES = [  # (M, N, K, LayerNorm prologue)
 ap = argparse.ArgumentParser()
 ap.add_argument("--iters", type=int, default=20)
 ap.add_argument("--first", type=int, default=0, help="only the first N shapes")
-ap.add_argument("--policy", type=lambda v: int(v, 0), default=0, help="dawn_conv_desc.policy (0 = shipped; 0x2B08580D = launch-order tiles)")
+ap.add_argument("--policy", type=lambda v: int(v, 0), default=0, help="dawn_conv_desc.policy (0 = shipped; 0x2B08580D = ConvPolicy.DEFAULT | XCD_LAUNCH_ORDER: launch-order tiles)")
 a = ap.parse_args()
 ops = HipOps()
 ops.conv_policy = a.policy

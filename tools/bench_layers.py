@@ -6,6 +6,8 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from dawn_pytorch_amd.ops import HipOps
+from dawn_pytorch_amd.policy import TemporalFlags
+WMODE = TemporalFlags.force_wmode
 from dawn_pytorch_amd.pack import pack_kn, pack_bf3, pack_bf3_temporal_out, rel_pos_bucket
 
 ops = HipOps()
@@ -39,8 +41,9 @@ def timeit(fn, n=5):
 for name, s in (("fp32", None), ("split", wqkv_s)):
     t = timeit(lambda: ops.temporal_layer_c64(x, F, HW, 0, F, win, wqkv, wout, rc, rs, band, wqkv_bf3=s))
     print(f"temporal_layer_c64 {name:6s}: {t:8.1f} us")
-for flags, name in ((3, "WMODE 2 (projections on the bf16 pipe)"), (4, "WMODE 3 (+ S, P.V, out-proj on the bf16 pipe)"),
-                    (4 | 32, "WMODE 3 with the out-projection on fp32 MFMA"), (4 | 16, "WMODE 3 with interleave hints")):
+for flags, name in ((WMODE(2), "WMODE 2 (projections on the bf16 pipe)"), (WMODE(3), "WMODE 3 (+ S, P.V, out-proj on the bf16 pipe)"),
+                    (WMODE(3) | TemporalFlags.OUT_FP32, "WMODE 3 with the out-projection on fp32 MFMA"),
+                    (WMODE(3) | TemporalFlags.SCHED_HINTS, "WMODE 3 with interleave hints")):
     ops.temporal_flags = flags
     t = timeit(lambda: ops.temporal_layer_c64(x, F, HW, 0, F, win, wqkv, wout, rc, rs, band, wqkv_bf3=wqkv_s, wout_bf3p=wout_sp))
     print(f"temporal_layer_c64 {name}: {t:8.1f} us")

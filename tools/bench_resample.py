@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """GPU box: the six resampling convs of the denoiser (Downsample 4x4 / stride 2, Upsample transposed 4x4 as 2x2 phases; gemm1x1_rowacc_kernel MODE 1 / 2)
-at the benchmark's shapes, and the use_deconv=False upsampler (nearest x2 + 3x3 conv: folded 2x2 phase taps, border 1) at the `up` shapes, HIP events.   python tools/bench_resample.py [--iters 10] [--policies 0 0x40000000]
+at the benchmark's shapes, and the use_deconv=False upsampler (nearest x2 + 3x3 conv: folded 2x2 phase taps, border 1) at the `up` shapes, HIP events.   python tools/bench_resample.py [--iters 10] [--policies 0 0x40000000]   (ConvPolicy.ABL_ROW_FETCH: the `ablation` build)
 (0x40000000: instrumented builds only -- `python3 hipbuild.py ablation`, DAWN_HIP_LIB=tools/ubench/libdawn_hip_ablation.bin --, every lane gathers lane 0's pixel: the cost of the gather's scattered line touches)"""
 import argparse, os, sys
 import torch

@@ -4,6 +4,8 @@ import os, sys
 import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from dawn_pytorch_amd.ops import HipOps
+from dawn_pytorch_amd.policy import TemporalFlags
+WMODE = TemporalFlags.force_wmode
 from dawn_pytorch_amd.pack import pack_kn, pack_bf3, pack_bf3_temporal_out
 ops = HipOps()
 F, win = 200, 40
@@ -13,12 +15,12 @@ wqkv, wout = pack_kn(wqkv_kn).cuda(), pack_kn(wout_kn).cuda()
 ws, wo = pack_bf3(wqkv_kn).cuda(), pack_bf3_temporal_out(wout_kn).cuda()
 ang = torch.arange(F).float()[:, None] * (1.0 / (10000 ** (torch.arange(0, 32, 2).float() / 32)))[None]
 rc, rs, band = ang.cos().contiguous().cuda(), ang.sin().contiguous().cuda(), torch.randn(2 * win + 1, 8, generator=g).cuda()
-# flags: 4 = the 32 x 32-tile kernel (WMODE 3), 5 = the window-tiled 16-query kernel (WMODE 4, round 6), alternating
+# the 32 x 32-tile kernel (WMODE 3), the window-tiled 16-query kernel (WMODE 4, round 6) and its tile-per-wave form (WMODE 5), alternating
 for HW in (4096, 1024):
     x = torch.randn(F * HW, 64, generator=g).cuda()
     out = torch.empty_like(x)
     for rep in range(3):
-        for flags, name in ((4, "wmode3 32x32 tiles"), (5, "wmode4 window-tiled"), (6, "wmode5 tile per wave")):
+        for flags, name in ((WMODE(3), "wmode3 32x32 tiles"), (WMODE(4), "wmode4 window-tiled"), (WMODE(5), "wmode5 tile per wave")):
             ops.temporal_flags = flags
             for _ in range(2):
                 ops.temporal_layer_c64(x, F, HW, 0, F, win, wqkv, wout, rc, rs, band, wqkv_bf3=ws, wout_bf3p=wo, out=out)
@@ -33,7 +35,7 @@ for HW in (4096, 1024):
 HW = 1024
 x = torch.randn(F * HW, 64, generator=g).cuda()
 out = torch.empty(120 * HW, 64, device="cuda")
-for flags, name in ((4, "wmode3 32x32 tiles"), (5, "wmode4 window-tiled"), (6, "wmode5 tile per wave")):
+for flags, name in ((WMODE(3), "wmode3 32x32 tiles"), (WMODE(4), "wmode4 window-tiled"), (WMODE(5), "wmode5 tile per wave")):
     ops.temporal_flags = flags
     for _ in range(2):
         ops.temporal_layer_c64(x, F, HW, 40, 120, win, wqkv, wout, rc, rs, band, wqkv_bf3=ws, wout_bf3p=wo, out=out)

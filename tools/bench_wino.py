@@ -8,6 +8,7 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from dawn_pytorch_amd.ops import HipOps                                      # noqa: E402
+from dawn_pytorch_amd.policy import ConvPolicy                               # noqa: E402
 from dawn_pytorch_amd.pack import pack_bf3, pack_kn, pack_wino_bf3, pack_wino4_bf3, conv_w_kn  # noqa: E402
 
 SHAPES = [  # F, H, W, C0, C1, N      (BASELINE configs[2]: T = 200, 64 x 64 latent)
@@ -26,14 +27,14 @@ def main():
     ap.add_argument("--wino-only", action="store_true")
     ap.add_argument("--extra-policy", type=lambda v: int(v, 0), default=0, help="a third policy to time (A/B of kernel variants)")
     ap.add_argument("--check", action="store_true", help="compare the extra policy's output with the Winograd one (bit-identical expected)")
-    ap.add_argument("--stagger", type=int, nargs="*", default=[], help="with --wino4: also time start-stagger units (policy bits 20..23)")
-    ap.add_argument("--wino4", action="store_true", help="also time the F(4x4,3x3) kernel (policy bit 0x8000000) where its geometry fits")
+    ap.add_argument("--stagger", type=int, nargs="*", default=[], help="with --wino4: also time start-stagger units (ConvPolicy.stagger)")
+    ap.add_argument("--wino4", action="store_true", help="also time the F(4x4,3x3) kernel (ConvPolicy.WINO4) where its geometry fits")
     ap.add_argument("--stamps4", action="store_true", help="F(4x4) instrumented build (hipbuild.py wino4timing, DAWN_WINO4_ABL=64): per-wave s_memtime timeline")
     ap.add_argument("--stamps", action="store_true", help="instrumented build (DAWN_WINO_ABL=64): print the s_memtime timeline of a few workgroups")
     a = ap.parse_args()
     ops = HipOps()
     dev = torch.device("cuda")
-    DIRECT, WINO = 0x580D | 0x1000000, 0x580D | 0x1000000 | 0x2000000
+    DIRECT, WINO, WINO4 = ConvPolicy.DIRECT_V2_K32, ConvPolicy.WINO, ConvPolicy.WINO4_EVERYWHERE
     for si, (F, H, W, C0, C1, N) in enumerate(SHAPES):
         if a.only is not None and si not in a.only:
             continue
@@ -53,7 +54,7 @@ def main():
         if a.stamps4:
             import numpy as np
             ww4s = pack_wino4_bf3(w5).to(dev)
-            ops.conv_policy = WINO | 0x18000000
+            ops.conv_policy = WINO4
             for _ in range(3):
                 out.zero_()
                 ops.conv_gemm(x0, w, N, in1=x1, F=F, Hi=H, Wi=W, KH=3, KW=3, pad=1, bias=bias, w_bf3=ws, w_wino=ww, w_wino4=ww4s, out=out)
@@ -106,9 +107,9 @@ def main():
             for sg in a.stagger:
                 pols.append((f"wino+stagger{sg}", WINO | (sg << 20)))
             if w4ok:
-                pols.append(("wino4", WINO | 0x18000000))
+                pols.append(("wino4", WINO4))
                 for sg in a.stagger:
-                    pols.append((f"wino4+stagger{sg}", WINO | 0x18000000 | (sg << 20)))
+                    pols.append((f"wino4+stagger{sg}", WINO4 | ConvPolicy.stagger(sg)))
             for name, pol in pols:
                 ops.conv_policy = pol
                 part = ops.conv_gn_part(rows, N, x0)
@@ -145,7 +146,7 @@ def main():
             o1, o2 = torch.empty_like(out), torch.empty_like(out)
             ops.conv_policy = WINO
             ops.conv_gemm(x0, w, N, in1=x1, F=F, Hi=H, Wi=W, KH=3, KW=3, pad=1, bias=bias, w_bf3=ws, w_wino=ww, out=o1)
-            ops.conv_policy = WINO | 0x18000000
+            ops.conv_policy = WINO4
             ops.conv_gemm(x0, w, N, in1=x1, F=F, Hi=H, Wi=W, KH=3, KW=3, pad=1, bias=bias, w_bf3=ws, w_wino=ww, w_wino4=ww4, out=o2)
             torch.cuda.synchronize()
             print(f"   F(4x4): {w4t:8.1f} us ({fl / w4t / 1e6:6.1f} alg TF/s)  {(w4t / wn - 1) * 100:+.1f} % vs F(2x2)   max|F4 - F2| {float((o1 - o2).abs().max()):.2e} "

@@ -8,6 +8,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from dawn_pytorch_amd.ops import HipOps
+from dawn_pytorch_amd.policy import ConvPolicy
 from dawn_pytorch_amd.pack import pack_kn, pack_bf3
 
 ap = argparse.ArgumentParser()
@@ -16,7 +17,7 @@ ap.add_argument("--C1", type=int, default=64)
 ap.add_argument("--N", type=int, default=64)
 ap.add_argument("--hw", type=int, default=64)
 ap.add_argument("--frames", type=int, default=200)
-ap.add_argument("--variant", type=lambda v: int(v, 0), default=0x580D | (8 << 16))
+ap.add_argument("--variant", type=lambda v: int(v, 0), default=ConvPolicy.DIRECT_V2 | ConvPolicy.variant(8))
 a = ap.parse_args()
 ops = HipOps()
 F, H, W, C0, C1, N = a.frames, a.hw, a.hw, a.C0, a.C1, a.N

@@ -11,6 +11,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from dawn_pytorch_amd.ops import HipOps
+from dawn_pytorch_amd.policy import ConvPolicy
 from dawn_pytorch_amd.pack import pack_kn, pack_bf3
 
 ap = argparse.ArgumentParser()
@@ -18,8 +19,8 @@ ap.add_argument("--C0", type=int, default=64)
 ap.add_argument("--C1", type=int, default=0)
 ap.add_argument("--N", type=int, default=64)
 ap.add_argument("--frames", type=int, default=200)
-ap.add_argument("--policy", type=lambda v: int(v, 0), default=0x5C0D)
-ap.add_argument("--leave", type=int, default=0, help="policy bits 20..23: grid = (16 - n)/16 of the resident slots")
+ap.add_argument("--policy", type=lambda v: int(v, 0), default=ConvPolicy.DIRECT_V2 | ConvPolicy.STREAMK)
+ap.add_argument("--leave", type=int, default=0, help="ConvPolicy.stagger(n): grid = (16 - n)/16 of the resident slots")
 a = ap.parse_args()
 ops = HipOps()
 F, H, W, C0, C1, N = a.frames, 64, 64, a.C0, a.C1, a.N
@@ -38,7 +39,7 @@ ops.L.dawn_conv_sk_workspace_init.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
 ops.sk_ws = torch.empty(int(ops.L.dawn_conv_sk_workspace_bytes()), dtype=torch.uint8, device="cuda")
 assert ops.L.dawn_conv_sk_workspace_init(ops.sk_ws.data_ptr(), torch.cuda.current_stream().cuda_stream) == 0
 part = ops.conv_gn_part(rows, N, x0)
-ops.conv_policy = a.policy | (a.leave << 20)
+ops.conv_policy = a.policy | ConvPolicy.stagger(a.leave)
 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 for it in range(3):
     dbg.zero_()

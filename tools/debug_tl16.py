@@ -4,6 +4,7 @@ import os, sys
 import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from dawn_pytorch_amd.ops import HipOps
+from dawn_pytorch_amd.policy import TemporalFlags
 from dawn_pytorch_amd.pack import pack_kn, pack_bf3, pack_bf3_temporal_out
 ops = HipOps()
 F, win = int(os.environ.get("F", 200)), 40
@@ -15,9 +16,9 @@ ang = torch.arange(F).float()[:, None] * (1.0 / (10000 ** (torch.arange(0, 32, 2
 rc, rs, band = ang.cos().contiguous().cuda(), ang.sin().contiguous().cuda(), torch.randn(2 * win + 1, 8, generator=g).cuda()
 for HW in (64, 256):
     x = torch.randn(F * HW, 64, generator=g).cuda()
-    ops.temporal_flags = 4
+    ops.temporal_flags = TemporalFlags.force_wmode(3)
     a = ops.temporal_layer_c64(x, F, HW, 0, F, win, wqkv, wout, rc, rs, band, wqkv_bf3=ws, wout_bf3p=wo)
-    ops.temporal_flags = 5
+    ops.temporal_flags = TemporalFlags.force_wmode(4)
     for rep in range(4):
         b = ops.temporal_layer_c64(x, F, HW, 0, F, win, wqkv, wout, rc, rs, band, wqkv_bf3=ws, wout_bf3p=wo)
         d = (a - b).abs().view(F, HW, 64)

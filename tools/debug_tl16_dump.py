@@ -5,6 +5,7 @@ import ctypes, os, sys
 import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from dawn_pytorch_amd.ops import HipOps
+from dawn_pytorch_amd.policy import TemporalFlags
 from dawn_pytorch_amd import _lib
 from dawn_pytorch_amd.pack import pack_kn, pack_bf3, pack_bf3_temporal_out
 ops = HipOps()
@@ -17,7 +18,7 @@ ws, wo = pack_bf3(wqkv_kn).cuda(), pack_bf3_temporal_out(wout_kn).cuda()
 ang = torch.arange(F).float()[:, None] * (1.0 / (10000 ** (torch.arange(0, 32, 2).float() / 32)))[None]
 rc, rs, band = ang.cos().contiguous().cuda(), ang.sin().contiguous().cuda(), torch.randn(2 * win + 1, 8, generator=g).cuda()
 x = torch.randn(F * HW, 64, generator=g).cuda()
-ops.temporal_flags = 5
+ops.temporal_flags = TemporalFlags.force_wmode(4)
 dumps = []
 for rep in range(12):
     d = torch.zeros(HW, 8, 16, 64, 12, device="cuda")

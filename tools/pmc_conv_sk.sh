@@ -1,5 +1,5 @@
 #!/bin/bash
-# GPU box: cycles, matrix-pipe busy and wave-state counters of the 3x3 split conv kernels (v2 = policy 0x580D, stream-K = 0x5C0D),
+# GPU box: cycles, matrix-pipe busy and wave-state counters of the 3x3 split conv kernels (v2 = policy 0x580D = ConvPolicy.DIRECT_V2, stream-K = 0x5C0D = DIRECT_V2 | STREAMK),
 # one --pmc set per pass, kernel-trace only.   bash tools/pmc_conv_sk.sh [outdir] [cases] [variants]
 # GRBM_GUI_ACTIVE / 8 = shader-clock cycles of a launch (the chip clocks to its power budget: wall time alone hides whether a
 # change saved cycles or cost clock); SQ_VALU_MFMA_BUSY_CYCLES / (cycles x 1024 SIMDs) = matrix-pipe busy; SQ_WAIT_* in quad-cycles.

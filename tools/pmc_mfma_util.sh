@@ -7,6 +7,7 @@
 # 290 us launch = 8 x 586k cycles at 2.02 GHz).  utilisation = BUSY / (GUI_ACTIVE / 8 * 1024 SIMDs).
 OUT=${1:-/root/repo/gpurun_out/pmc_mfma}; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
+# --variants 0x100580D,0x580D = ConvPolicy.DIRECT_V2_K32, DIRECT_V2
 timeout 300 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_INSTS_VALU SQ_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace \
   -d $OUT/run -o p -- python /root/repo/tools/bench_conv.py --cases l0_3x3,l0_3x3_cat,l1_3x3,l2_3x3,l3_3x3 --iters 3 --variants 0x100580D,0x580D > $OUT/run.log 2>&1
 cd /root/repo

@@ -6,6 +6,8 @@ import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from dawn_pytorch_amd.ops import HipOps
+from dawn_pytorch_amd.policy import TemporalFlags
+WMODE3 = TemporalFlags.force_wmode(3)
 from dawn_pytorch_amd.pack import pack_kn, pack_bf3, pack_bf3_temporal_out
 ops = HipOps()
 dev = "cuda"
@@ -28,7 +30,7 @@ assert ops.L.dawn_temporal_set_debug(dbg.data_ptr()) == 0
 names = ["start", "phase0+setup", "h0 start", "h0 KV proj", "h0 barrier", "h0 Q proj", "h0 S(A)", "h0 S(B)+smA", "h0 PV(A)+smB", "h0 PV(B)", "h0 out",
          "h1 start", "h1 KV proj", "h1 barrier", "h1 Q proj", "h1 S(A)", "h1 S(B)+smA", "h1 PV(A)+smB", "h1 PV(B)", "h1 out", "end (6 more heads + store)"]
 for label, s, flags in (
-                        ("all-bf16-pipe (WMODE 3, runtime row stride)", wqkv_s, 4 | 64), ("WMODE 3 with interleave hints", wqkv_s, 4 | 64 | 16)):
+                        ("all-bf16-pipe (WMODE 3, runtime row stride)", wqkv_s, WMODE3 | TemporalFlags.NO_FIXED200), ("WMODE 3 with interleave hints", wqkv_s, WMODE3 | TemporalFlags.NO_FIXED200 | TemporalFlags.SCHED_HINTS)):
     ops.temporal_flags = flags
     for _ in range(2):
         dbg.zero_()

@@ -7,6 +7,7 @@ import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from dawn_pytorch_amd.ops import HipOps
+from dawn_pytorch_amd.policy import TemporalFlags
 from dawn_pytorch_amd.pack import pack_kn, pack_bf3, pack_bf3_temporal_out
 ops = HipOps()
 dev = "cuda"
@@ -27,7 +28,7 @@ assert ops.L.dawn_temporal16_set_debug(dbg.data_ptr()) == 0
 names = ["start", "phase 0", "h0 start", "h0 Q proj", "h0 K/V group", "h0 barrier A", "h0 S+softmax (tile 0)", "h0 P.V (tile 0)", "h0 out-proj (tile 0)",
          "h0 phase B end", "h1 start", "h1 Q proj", "h1 K/V group", "h1 barrier A", "h1 S+softmax (tile 0)", "h1 P.V (tile 0)", "h1 out-proj (tile 0)",
          "h1 phase B end", "end (6 more heads + store)"]
-ops.temporal_flags = 5
+ops.temporal_flags = TemporalFlags.force_wmode(4)
 for _ in range(2):
     dbg.zero_()
     ops.temporal_layer_c64(x, F, HW, 0, F, win, wqkv, wout, rc, rs, band, wqkv_bf3=wqkv_s, wout_bf3p=wout_sp)

@@ -21,7 +21,7 @@
 #include "../../dawn-pytorch_amd/csrc/dawn_common.h"
 #include "../../include/dawn_hip.h"
 // (round 4: not part of the shipped library any more -- built into the experimental library by `hipbuild.py sktiming`, which
-//  compiles conv_gemm.hip with -DDAWN_WITH_STREAMK so that policy bit 0x400 + dawn_conv_desc.sk_ws reach dawn_conv3x3_sk_try)
+//  compiles conv_gemm.hip with -DDAWN_WITH_STREAMK so that DAWN_POLICY_STREAMK + dawn_conv_desc.sk_ws reach dawn_conv3x3_sk_try)
 extern "C" size_t dawn_conv_sk_workspace_bytes(void);
 extern "C" int dawn_conv_sk_workspace_init(void* ws, void* stream);
 extern "C" int dawn_conv_sk_check(const void* ws, void* stream);
@@ -583,14 +583,14 @@ int dawn_conv3x3_sk_try(const dawn_conv_desc& d, long M, int policy, hipStream_t
     if (ntiles * a.nC >= (1L << 30)) return 0;
     a.U = (int)(ntiles * a.nC);
     int G = 2 * sk_ncu();
-    // (policy bits 20..23: grid = (16 - n)/16 of the resident slots -- leaves CUs to a concurrent stream; 0 = all)
-    const int leave = (policy >> 20) & 15;
+    // (DAWN_POLICY_STAGGER field: grid = (16 - n)/16 of the resident slots -- leaves CUs to a concurrent stream; 0 = all)
+    const int leave = (policy & DAWN_POLICY_STAGGER_MASK) / DAWN_POLICY_STAGGER(1);
     if (leave) G = G * (16 - leave) / 16 / 8 * 8;
     if (G > a.U) G = a.U;
     if (G <= 0) return 0;
     a.G = G;
-    a.pair_xor = ((policy & 0x200) || (G % 64)) ? 0 : 2;
-    a.prio_alt = (policy & 0x40) ? 1 + ((policy >> 16) & 3) : 0;   // (idx ^ 2 is a permutation of [G/16, G/8) only then)
+    a.pair_xor = ((policy & DAWN_POLICY_SK_NO_PAIR_OFFSET) || (G % 64)) ? 0 : 2;
+    a.prio_alt = (policy & DAWN_POLICY_SK_PRIO_ALT) ? 1 + ((policy / DAWN_POLICY_VARIANT(1)) & 3) : 0;   // (idx ^ 2 is a permutation of [G/16, G/8) only then)
     unsigned char* ws = static_cast<unsigned char*>(d.sk_ws);
     a.flag = reinterpret_cast<unsigned*>(ws);
     a.err = reinterpret_cast<unsigned*>(ws + 4096);
