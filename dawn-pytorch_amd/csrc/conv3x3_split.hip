@@ -1,4 +1,4 @@
-// The shipped direct 3x3 / stride 1 / pad 1 convolution: fp32 on the bf16 matrix pipe by exact operand splitting (split3, conv_split.h),
+// The shipped direct 3x3 / stride 1 / pad 1 convolution: fp32 on the bf16 matrix pipe by exact operand splitting (dawn_split3_rne_quad, dawn_common.h),
 // second generation of conv3x3_halo_bf16_kernel (conv_gemm.hip).  Reached from dawn_conv_gemm's router through dawn_conv3x3_v2_try;
 // the s_memtime stamps (TSTAMP, ABL bit 3) and the other ABL instantiations exist only in -DDAWN_ABLATION builds (hipbuild.py ablation).
 #include "conv_split.h"
@@ -7,13 +7,10 @@ namespace {
 
 __device__ unsigned long long* g_dbg = nullptr;   // s_memtime stamps of the instrumented build (ABL bit 3)
 
-// sums over lanes 0..31 and over lanes 32..63 of a wave, valid in lanes 16..31 / 48..63: four DPP adds inside each row of 16
-// (quad xor 1, quad xor 2, half-row mirror, row mirror), then row_bcast15 into rows 1 and 3 -- no LDS round trips
+// sums over lanes 0..31 and over lanes 32..63 of a wave, valid in lanes 16..31 / 48..63: the sum inside each row of 16
+// (row16_sum), then row_bcast15 into rows 1 and 3 -- no LDS round trips
 __device__ __forceinline__ float half_wave_sum_dpp(float v) {
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, true));
+    v = row16_sum(v);
     v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x142, 0xA, 0xF, false));
     return v;
 }
@@ -105,12 +102,9 @@ __global__ __launch_bounds__(256 * WN, (K32 && PSEG == 28) ? 2 / WN : 1) void co
     // ---- buffer descriptors: the patch window of each source (first pixel = row y0-1 of frame f0), the weights
     const long pb = ((long)f0 * H + y0 - 1) * W;
     const int ext = nf * H * W + (nf > 1 ? 2 * W : (TR + 2) * W - H * W);    // pixels spanned by the window
-    const __amdgpu_buffer_rsrc_t rs0 =
-        __builtin_amdgcn_make_buffer_rsrc((void*)(d.in0 + pb * d.ld0), 0, ext * d.ld0 * 4, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs1 = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)((d.in1 ? d.in1 : d.in0) + pb * (d.in1 ? d.ld1 : d.ld0)), 0, ext * (d.in1 ? d.ld1 : d.ld0) * 4, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsw =
-        __builtin_amdgcn_make_buffer_rsrc((void*)d.w_bf3, 0, 9 * nC * 6 * d.N * 16, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs0 = DAWN_BUFFER(d.in0 + pb * d.ld0, ext * d.ld0 * 4);
+    const __amdgpu_buffer_rsrc_t rs1 = DAWN_BUFFER((d.in1 ? d.in1 : d.in0) + pb * (d.in1 ? d.ld1 : d.ld0), ext * (d.in1 ? d.ld1 : d.ld0) * 4);
+    const __amdgpu_buffer_rsrc_t rsw = DAWN_BUFFER(d.w_bf3, 9 * nC * 6 * d.N * 16);
 
     // ---- this thread's patch quads: q = tid + NTHR*i -> (pos = q>>2, 4-channel slot = q&3); rel = window pixel
     const int nq = P16 * 4;
@@ -177,12 +171,11 @@ __global__ __launch_bounds__(256 * WN, (K32 && PSEG == 28) ? 2 / WN : 1) void co
         const int ldb = (src1 ? d.ld1 : d.ld0) * 4;
         const int soff = (src1 ? cbase - d.C0 : cbase) * 4;
         const unsigned voff = rel[i] < 0 ? OOB : (unsigned)(rel[i] * ldb + (tid & 3) * 16);
-        typedef int i32x4 __attribute__((ext_vector_type(4)));
         const i32x4 v = src1 ? __builtin_amdgcn_raw_buffer_load_b128(rs1, voff, soff, 0)
                              : __builtin_amdgcn_raw_buffer_load_b128(rs0, voff, soff, 0);
         araw[i] = __builtin_bit_cast(f32x4, v);
     };
-    auto convA = [&](int i) { split3(araw[i], ap[i][0], ap[i][1], ap[i][2]); };
+    auto convA = [&](int i) { dawn_split3_rne_quad(araw[i], ap[i][0], ap[i][1], ap[i][2]); };
     auto writeA = [&]() {
 #pragma unroll
         for (int i = 0; i < MAXQ; ++i) {
@@ -319,15 +312,13 @@ __global__ __launch_bounds__(256 * WN, (K32 && PSEG == 28) ? 2 / WN : 1) void co
                         fb[j][RB[g]] = *reinterpret_cast<const bf16x8*>(
                             Bb + ((size_t)((kx * 6 + RB[g] * 2 + half) * BN + wn * 64 + j * 32 + l31)) * 16);
                 }
-                constexpr int PA9[9] = {2, 2, 1, 2, 0, 1, 1, 0, 0};
-                constexpr int PB9[9] = {2, 1, 2, 0, 2, 1, 0, 1, 0};
 #pragma unroll
                 for (int t = 9 - NT; t < 9; ++t)
 #pragma unroll
                     for (int i = 0; i < TM; ++i)
 #pragma unroll
                         for (int j = 0; j < TN; ++j)
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[j][PB9[t]], fa[i][PA9[t]], acc[i][j], 0, 0, 0);
+                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[j][DAWN_SPLIT9_B[t]], fa[i][DAWN_SPLIT9_A[t]], acc[i][j], 0, 0, 0);
                 // split the quads that landed during the previous stage, in the shadow of the MFMAs above
                 if (more && ky > 0) {
 #pragma unroll

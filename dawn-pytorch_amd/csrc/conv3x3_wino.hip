@@ -44,32 +44,10 @@
 
 namespace {
 
-typedef dawn_bf16x8 bf16x8;
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int DTG = 8 * 6 * 1024;            // bytes of one D~ region: [nu_l 2][xi 4][plane 3][k-half 2][tile 64][16 B]
 constexpr int EXROW = 32 * 4 + 16;           // exchange row of the epilogue: 32 channels fp32 + 16 B (bank rotation)
 constexpr int EXHALF = 8 * 64 * EXROW;       // one 32-channel half of the exchange: [xi 4][zb 2][tile 64][EXROW]
 constexpr unsigned OOB = 0x80000000u;
-
-// exact truncation split of 4 fp32 values into three bf16 quads (dawn_split3_oct's scheme, see dawn_common.h)
-__device__ __forceinline__ void split3q(const f32x4 v, uint2& p1, uint2& p2, uint2& p3) {
-    unsigned q1[2], q2[2], q3[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const float a = v[2 * i], b = v[2 * i + 1];
-        const unsigned a1 = __float_as_uint(a) & 0xffff0000u, b1 = __float_as_uint(b) & 0xffff0000u;
-        const float ra = a - __uint_as_float(a1), rb = b - __uint_as_float(b1);
-        const unsigned a2 = __float_as_uint(ra) & 0xffff0000u, b2 = __float_as_uint(rb) & 0xffff0000u;
-        const float sa = ra - __uint_as_float(a2), sb = rb - __uint_as_float(b2);
-        q1[i] = __builtin_amdgcn_perm(b1, a1, 0x07060302u);          // [hi16(a) | hi16(b) << 16]
-        q2[i] = __builtin_amdgcn_perm(b2, a2, 0x07060302u);
-        q3[i] = __builtin_amdgcn_perm(__float_as_uint(sb), __float_as_uint(sa), 0x07060302u);
-    }
-    p1 = make_uint2(q1[0], q1[1]);
-    p2 = make_uint2(q2[0], q2[1]);
-    p3 = make_uint2(q3[0], q3[1]);
-}
 
 struct wino_thread {
     // transform role
@@ -96,7 +74,7 @@ __device__ __forceinline__ void wino_transform(const wino_thread& t, const unsig
 #pragma unroll
     for (int xi = 0; xi < 4; ++xi) {
         uint2 p1, p2, p3;
-        split3q(D[xi], p1, p2, p3);
+        dawn_split3_trunc_quad(D[xi], p1, p2, p3);
         unsigned char* dst = dt + t.wbase + xi * 6 * 1024;
         *reinterpret_cast<uint2*>(dst) = p1;
         *reinterpret_cast<uint2*>(dst + 2048) = p2;
@@ -161,7 +139,7 @@ __device__ __forceinline__ void wino_phase(const wino_thread& t, const unsigned 
         } else if (blk < 6) {
             const int xi = blk - 2;
             uint2 p1, p2, p3;
-            split3q(D[xi], p1, p2, p3);
+            dawn_split3_trunc_quad(D[xi], p1, p2, p3);
             unsigned char* dst = dtw + t.wbase + xi * 6 * 1024;
             *reinterpret_cast<uint2*>(dst) = p1;
             *reinterpret_cast<uint2*>(dst + 2048) = p2;
@@ -257,8 +235,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wino_kernel(const dawn_conv_de
         dtab[i * 512 + tid] = v;
         ddst[i] = s < PI ? s * 1024 : -1;
     }
-    const __amdgpu_buffer_rsrc_t rsw =
-        __builtin_amdgcn_make_buffer_rsrc((void*)d.w_wino, 0, nC * 16 * nCB * 2 * 1024, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsw = DAWN_BUFFER(d.w_wino, nC * 16 * nCB * 2 * 1024);
 
     struct tile_t { int f0, y0, n0, valid; };          // scalars only: descriptors and lane offsets are rebuilt at issue time
     auto setup = [&](int tile, bool valid, tile_t& T) {
@@ -304,7 +281,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wino_kernel(const dawn_conv_de
         const bool src1 = cbase >= d.C0;
         const float* src = src1 ? d.in1 : d.in0;
         // the descriptor covers the tile's frame(s), rows 0 .. H - 1: the window's rows -1 / H fall outside it
-        Fd.rs = __builtin_amdgcn_make_buffer_rsrc((void*)(src + (long)T.f0 * frame_fl), 0, range_b, 0x00020000);
+        Fd.rs = DAWN_BUFFER(src + (long)T.f0 * frame_fl, range_b);
         Fd.soff = (src1 ? cbase - d.C0 : cbase) * 4;
         // the window's first pixel relative to the frame's; a tile past the end (a copy of a real one) fetches nothing: every lane out of range
         // (through the OFFSET, not a zero-sized descriptor: a descriptor word that depends on the flag ends up in vector registers and
@@ -472,9 +449,8 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wino_kernel(const dawn_conv_de
         // outputs leave through a buffer descriptor of the tile: the lane's share of the address (vo_out, fixed at launch) in the vector
         // offset, row / column / channel half of the instruction in the scalar offset -- no 64-bit vector arithmetic per store
         const long tb = ((long)cur.f0 * H + cur.y0) * W;                       // the tile's first pixel
-        const __amdgpu_buffer_rsrc_t rso = __builtin_amdgcn_make_buffer_rsrc((void*)(d.out + tb * d.ld_out + cur.n0), 0, (255 * d.ld_out + 64) * 4, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rsr =
-            __builtin_amdgcn_make_buffer_rsrc((void*)((d.res ? d.res : d.out) + tb * d.ld_res + cur.n0), 0, d.res ? (255 * d.ld_res + 64) * 4 : 0, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rso = DAWN_BUFFER(d.out + tb * d.ld_out + cur.n0, (255 * d.ld_out + 64) * 4);
+        const __amdgpu_buffer_rsrc_t rsr = DAWN_BUFFER((d.res ? d.res : d.out) + tb * d.ld_res + cur.n0, d.res ? (255 * d.ld_res + 64) * 4 : 0);
         const bool never = d.F < 0;                    // (ablation builds: work kept alive behind a condition that is never true)
         if ((ABL & 1) && never) {
             f32x4 sa = {0.f, 0.f, 0.f, 0.f};

@@ -48,27 +48,12 @@
 
 namespace {
 
-typedef dawn_bf16x8 bf16x8;
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
 constexpr int NW4 = 12;                      // waves per workgroup
 constexpr int NT4 = NW4 * 64;
 constexpr int DT4 = 36 * 6 * 256;            // bytes of one D~ buffer: [position 36][plane 3][k-half 2][tile 16][16 B]
 constexpr int EXROW4 = 144;                  // exchange row: 32 channels fp32 + 16 B (bank rotation)
 constexpr unsigned OOB4 = 0x80000000u;
 constexpr int WD4 = 2;                       // weight-fetch lookahead in positions (ring of WD4 + 1 fragment sets: 16 registers each)
-
-// exact truncation split of two fp32 values into three packed bf16 pairs (dawn_split3_oct's scheme)
-__device__ __forceinline__ void split3p(const float a, const float b, unsigned& q1, unsigned& q2, unsigned& q3) {
-    const unsigned a1 = __float_as_uint(a) & 0xffff0000u, b1 = __float_as_uint(b) & 0xffff0000u;
-    const float ra = a - __uint_as_float(a1), rb = b - __uint_as_float(b1);
-    const unsigned a2 = __float_as_uint(ra) & 0xffff0000u, b2 = __float_as_uint(rb) & 0xffff0000u;
-    const float sa = ra - __uint_as_float(a2), sb = rb - __uint_as_float(b2);
-    q1 = __builtin_amdgcn_perm(b1, a1, 0x07060302u);                  // [hi16(a) | hi16(b) << 16]
-    q2 = __builtin_amdgcn_perm(b2, a2, 0x07060302u);
-    q3 = __builtin_amdgcn_perm(__float_as_uint(sb), __float_as_uint(sa), 0x07060302u);
-}
 
 // B^T on the points (0, +-3/4, +-3/2, inf), row nu over the patch columns x0..x5:
 //   0: 81/64 x0 - 45/16 x2 + x4      1/2: -/+ 27/16 x1 - 9/4 x2 +/- 3/4 x3 + x4      3/4: -/+ 27/32 x1 - 9/16 x2 +/- 3/2 x3 + x4      5: 81/64 x1 - 45/16 x3 + x5
@@ -115,7 +100,7 @@ __device__ __forceinline__ void w4_cols(const f32x2 (&tr)[6], f32x2 (&v)[6]) {
 }
 __device__ __forceinline__ void w4_store(unsigned char* dtw, const w4_thread& t, const int xi, const f32x2 v) {
     unsigned q1, q2, q3;
-    split3p(v.x, v.y, q1, q2, q3);
+    dawn_split3_trunc_pair(v.x, v.y, q1, q2, q3);
     unsigned char* dst = dtw + t.wbase + xi * (6 * 6 * 256);
     *reinterpret_cast<unsigned*>(dst) = q1;
     *reinterpret_cast<unsigned*>(dst + 512) = q2;
@@ -214,7 +199,7 @@ __global__ __launch_bounds__(NT4, 1) void conv3x3_wino4_kernel(const dawn_conv_d
         const int q = i & 15, side = (i >> 4) & 1, r = (i >> 5) % (TR + 2), b = (i >> 5) / (TR + 2);
         *reinterpret_cast<unsigned*>(raw0 + b * RAWB + r * ROWB + side * (ROWB - 64) + q * 4) = 0u;
     }
-    const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc((void*)d.w_wino4, 0, nC * 36 * nCB * 1536, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsw = DAWN_BUFFER(d.w_wino4, nC * 36 * nCB * 1536);
 
     struct tile_t { int f0, y0, n0, valid; };
     auto setup = [&](int tile, bool valid, tile_t& T) {
@@ -261,7 +246,7 @@ __global__ __launch_bounds__(NT4, 1) void conv3x3_wino4_kernel(const dawn_conv_d
         const float* src = src1 ? d.in1 : d.in0;
         const int ld = src1 ? d.ld1 : d.ld0;
         const long pb = ((long)T.f0 * H + T.y0 - 1) * W;                     // first pixel of the window = row y0 - 1 of frame f0
-        D.rs = __builtin_amdgcn_make_buffer_rsrc((void*)(src + pb * ld), 0, live ? (TR + 2) * W * ld * 4 : 0, 0x00020000);
+        D.rs = DAWN_BUFFER(src + pb * ld, live ? (TR + 2) * W * ld * 4 : 0);
         D.ldb = ld * 4;
         D.soff = (src1 ? cbase - d.C0 : cbase) * 4;
         D.y0 = T.y0;
@@ -297,7 +282,7 @@ __global__ __launch_bounds__(NT4, 1) void conv3x3_wino4_kernel(const dawn_conv_d
             const float* src = src1 ? d.in1 : d.in0;
             const int ld = src1 ? d.ld1 : d.ld0;
             const long pb = ((long)T.f0 * H + T.y0 - 1) * W;
-            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(src + pb * ld), 0, (TR + 2) * W * ld * 4, 0x00020000);
+            const __amdgpu_buffer_rsrc_t rs = DAWN_BUFFER(src + pb * ld, (TR + 2) * W * ld * 4);
             const int r = i * RPI + (RPI == 2 ? (lane >> 5) : 0);
             const unsigned row = (unsigned)(T.y0 + r - 1);
             const unsigned voff = (unsigned)((r * W + (lane & (W - 1))) * (ld * 4));
@@ -455,9 +440,8 @@ __global__ __launch_bounds__(NT4, 1) void conv3x3_wino4_kernel(const dawn_conv_d
         // outputs leave through a buffer descriptor of the tile: the lane's share of the address (vo_out, fixed at launch) in the vector
         // offset, the row / column of the instruction in the scalar offset -- no 64-bit vector arithmetic per store
         const long tb = ((long)cur.f0 * H + cur.y0) * W;                       // the tile's first pixel
-        const __amdgpu_buffer_rsrc_t rso = __builtin_amdgcn_make_buffer_rsrc((void*)(d.out + tb * d.ld_out + cur.n0), 0, (255 * d.ld_out + 64) * 4, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rsr =
-            __builtin_amdgcn_make_buffer_rsrc((void*)((d.res ? d.res : d.out) + tb * d.ld_res + cur.n0), 0, d.res ? (255 * d.ld_res + 64) * 4 : 0, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rso = DAWN_BUFFER(d.out + tb * d.ld_out + cur.n0, (255 * d.ld_out + 64) * 4);
+        const __amdgpu_buffer_rsrc_t rsr = DAWN_BUFFER((d.res ? d.res : d.out) + tb * d.ld_res + cur.n0, d.res ? (255 * d.ld_res + 64) * 4 : 0);
         f32x4 bv = {0.f, 0.f, 0.f, 0.f};
         if (d.bias && tid < 512) bv = *reinterpret_cast<const f32x4*>(d.bias + cur.n0 + nrl);
         float gs1 = 0.f, gs2 = 0.f;

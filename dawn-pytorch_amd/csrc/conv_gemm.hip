@@ -952,7 +952,7 @@ __global__ __launch_bounds__(256) void conv3x3_halo_bf16_kernel(const dawn_conv_
         for (int q = tid; q < nq; q += 256) {
             const f32x4 v = *reinterpret_cast<const f32x4*>(raw + q * 4);
             uint2 p1, p2, p3;
-            split3(v, p1, p2, p3);
+            dawn_split3_rne_quad(v, p1, p2, p3);
             const int pos = q >> 2, slot = q & 3;
             unsigned char* dst = planes + (size_t)(slot >> 1) * HPS + pos * 16 + (slot & 1) * 8;
             *reinterpret_cast<uint2*>(dst) = p1;
@@ -1001,16 +1001,13 @@ __global__ __launch_bounds__(256) void conv3x3_halo_bf16_kernel(const dawn_conv_
                 for (int j = 0; j < TN; ++j)
                     b[j][pl] = *reinterpret_cast<const bf16x8*>(Bb + ((size_t)((pl * 2 + half) * BN + wn * WTN + j * 32 + l31)) * 16);
             }
-            // smallest terms first
-            constexpr int PA9[9] = {2, 2, 1, 2, 0, 1, 1, 0, 0};
-            constexpr int PB9[9] = {2, 1, 2, 0, 2, 1, 0, 1, 0};
 #pragma unroll
-            for (int t = 9 - NT; t < 9; ++t)
+            for (int t = 9 - NT; t < 9; ++t)                   // (six terms: the last six of the nine)
 #pragma unroll
                 for (int i = 0; i < TM; ++i)
 #pragma unroll
                     for (int j = 0; j < TN; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][PA9[t]], b[j][PB9[t]], acc[i][j], 0, 0, 0);
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][DAWN_SPLIT9_A[t]], b[j][DAWN_SPLIT9_B[t]], acc[i][j], 0, 0, 0);
             if (tap < 8) {
                 if (issuedA) asm volatile("s_waitcnt vmcnt(1) lgkmcnt(0)" ::: "memory");
                 else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");

@@ -3,7 +3,9 @@
 //   conv3x3_split.hip  conv3x3_bf16_v2_kernel (the shipped direct 3x3 kernel)
 //   gemm1x1_tiled.hip  gemm1x1_bf16_kernel (the tiled split 1x1 GEMM)
 //   gemm1x1_rows.hip   gemm1x1_rowreg_kernel / gemm1x1_rowacc_kernel (the row-stationary split GEMMs)
-// Only what two or more of them need lives here.  The library links without relocatable device code: no __device__ variable here.
+// Only what two or more of them need lives here: the policy bits, the border rule and the host functions that cross the units.  The
+// operand splits (dawn_split3_rne_quad for the activations of these kernels), the cross-term orders and the vector types are
+// dawn_common.h's, shared with the attention kernels.  The library links without relocatable device code: no __device__ variable here.
 #pragma once
 #include "dawn_common.h"
 #include "../../include/dawn_hip.h"
@@ -43,24 +45,6 @@ __device__ __forceinline__ int dawn_border_coord(int i, int n, int border) {
     if (border == 1) return i < 0 ? 0 : (i >= n ? n - 1 : i);
     if (border == 2) return i < 0 ? i + n : (i >= n ? i - n : i);
     return i;
-}
-
-typedef dawn_bf16x8 bf16x8;
-
-// exact fp32 -> 3 x bf16 operand split (round to nearest even; see conv3x3_halo_bf16_kernel in conv_gemm.hip)
-__device__ __forceinline__ void split3(const f32x4 v, uint2& p1, uint2& p2, uint2& p3) {
-    typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-    bf16x4 h1, h2, h3;
-    f32x4 r;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { h1[i] = (__bf16)v[i]; r[i] = v[i] - (float)h1[i]; }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { h2[i] = (__bf16)r[i]; r[i] = r[i] - (float)h2[i]; }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) h3[i] = (__bf16)r[i];
-    p1 = *reinterpret_cast<uint2*>(&h1);
-    p2 = *reinterpret_cast<uint2*>(&h2);
-    p3 = *reinterpret_cast<uint2*>(&h3);
 }
 
 // ---- host functions that cross the units.  The router (dawn_conv_gemm, conv_gemm.hip) decides; these launch what it chose.

@@ -34,7 +34,7 @@ __global__ __launch_bounds__(512) void gemm1x1_rowreg_kernel(const dawn_conv_des
     const long u1 = u0 + units_per_wg < nunits ? u0 + units_per_wg : nunits;
     if (u0 >= u1) return;
     const int ld1 = d.in1 ? d.ld1 : d.ld0;
-    const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc((void*)d.w_bf3, 0, KS * 6 * d.N * 16, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsw = DAWN_BUFFER(d.w_bf3, KS * 6 * d.N * 16);
     auto issueB = [&](long u, int buf) __attribute__((always_inline)) {
         const int n0 = (int)(u % nCh) * BNC;
 #pragma unroll
@@ -47,9 +47,8 @@ __global__ __launch_bounds__(512) void gemm1x1_rowreg_kernel(const dawn_conv_des
     bf16x8 xs[KS][3];
     auto load_panel = [&](long panel) __attribute__((always_inline)) {
         const long r0 = panel * BM + wave * 32;            // wave-uniform first row
-        const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc((void*)(d.in0 + r0 * d.ld0), 0, 32 * d.ld0 * 4, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rb =
-            __builtin_amdgcn_make_buffer_rsrc((void*)((d.in1 ? d.in1 : d.in0) + r0 * ld1), 0, 32 * ld1 * 4, 0x00020000);
+        const __amdgpu_buffer_rsrc_t ra = DAWN_BUFFER(d.in0 + r0 * d.ld0, 32 * d.ld0 * 4);
+        const __amdgpu_buffer_rsrc_t rb = DAWN_BUFFER((d.in1 ? d.in1 : d.in0) + r0 * ld1, 32 * ld1 * 4);
         f32x4 raw[KS][2];
         // one per-lane byte offset per source (row l31, k-half); the channel chunk goes into the scalar / immediate offset (16 separate
         // offset registers otherwise, hoisted out of the unit loop)
@@ -152,12 +151,12 @@ __global__ __launch_bounds__(512) void gemm1x1_rowreg_kernel(const dawn_conv_des
         for (int kc = 0; kc < KS; ++kc) {
             if (kc + 1 < KS) read_frags(kc + 1, (kc + 1) & 1);
             __builtin_amdgcn_sched_barrier(0);            // keep the requests above this step's MFMAs
-            constexpr int PW[6] = {0, 2, 1, 0, 1, 0}, PX[6] = {2, 0, 1, 1, 0, 0};     // smallest cross terms first
+            // (the cross-term tables with their roles swapped, here and in the row-accumulating kernel: _B picks the weight plane)
 #pragma unroll
             for (int t = 0; t < 6; ++t)
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
-                    acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[kc & 1][j][PW[t]], xs[kc][PX[t]], acc[j], 0, 0, 0);
+                    acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[kc & 1][j][DAWN_SPLIT6_B[t]], xs[kc][DAWN_SPLIT6_A[t]], acc[j], 0, 0, 0);
                 }
         }
         // ---- epilogue.  The accumulators hold lane = row, registers 4g..4g+3 = columns 8g + 4*half + {0..3}: stored directly,
@@ -231,7 +230,7 @@ __global__ __launch_bounds__(512) void gemm1x1_rowacc_kernel(const dawn_conv_des
     const long p1 = p0 + panels_per_wg < npanels ? p0 + panels_per_wg : npanels;
     if (p0 >= p1) return;
     const int ld1 = d.in1 ? d.ld1 : d.ld0;
-    const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc((void*)d.w_bf3, 0, (MODE == 2 ? 4 : 1) * (Ktot / 16) * 6 * d.N * 16, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsw = DAWN_BUFFER(d.w_bf3, (MODE == 2 ? 4 : 1) * (Ktot / 16) * 6 * d.N * 16);
     auto issueB = [&](long unit, int kb, int c, int buf) __attribute__((always_inline)) {
         const long panel = unit / ngrp;
         const int cg = (int)(unit - panel * ngrp) * NCH;       // first column chunk of the unit's group
@@ -264,9 +263,8 @@ __global__ __launch_bounds__(512) void gemm1x1_rowacc_kernel(const dawn_conv_des
     auto fetch_rows = [&](long panel, int kb) __attribute__((always_inline)) {
         if (MODE == 0) {
             const long r0 = panel * BM + wave * 32;
-            const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc((void*)(d.in0 + r0 * d.ld0), 0, 32 * d.ld0 * 4, 0x00020000);
-            const __amdgpu_buffer_rsrc_t rb =
-                __builtin_amdgcn_make_buffer_rsrc((void*)((d.in1 ? d.in1 : d.in0) + r0 * ld1), 0, 32 * ld1 * 4, 0x00020000);
+            const __amdgpu_buffer_rsrc_t ra = DAWN_BUFFER(d.in0 + r0 * d.ld0, 32 * d.ld0 * 4);
+            const __amdgpu_buffer_rsrc_t rb = DAWN_BUFFER((d.in1 ? d.in1 : d.in0) + r0 * ld1, 32 * ld1 * 4);
             if (kb == 0 && d.row_mean) { mu = d.row_mean[r0 + l31]; rs = d.row_rstd[r0 + l31]; }
             const int lrow = l31;
 #ifdef DAWN_ABLATION
@@ -297,8 +295,7 @@ __global__ __launch_bounds__(512) void gemm1x1_rowacc_kernel(const dawn_conv_des
         } else {
             // a 32-pixel tile lies in one frame (host check): frame-sized descriptor, the lane's offset = its tap pixel
             const int fr = __builtin_amdgcn_readfirstlane(pf);
-            const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc((void*)(d.in0 + (long)fr * d.Hi * d.Wi * d.ld0), 0,
-                                                                                d.Hi * d.Wi * d.ld0 * 4, 0x00020000);
+            const __amdgpu_buffer_rsrc_t ra = DAWN_BUFFER(d.in0 + (long)fr * d.Hi * d.Wi * d.ld0, d.Hi * d.Wi * d.ld0 * 4);
             const int tap = kb / cpb, c0 = (kb - tap * cpb) * KBC;
             int iy, ix;
             if (MODE == 1) { iy = py_ + (tap >> 2); ix = px_ + (tap & 3); }
@@ -357,9 +354,8 @@ __global__ __launch_bounds__(512) void gemm1x1_rowacc_kernel(const dawn_conv_des
     // so that E[d^2] - E[d]^2 does not cancel), both halves of a row combined by one xor-32 exchange
     auto ln_stats = [&](long panel) __attribute__((always_inline)) {
         const long r0 = panel * BM + wave * 32;
-        const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc((void*)(d.in0 + r0 * d.ld0), 0, 32 * d.ld0 * 4, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rb =
-            __builtin_amdgcn_make_buffer_rsrc((void*)((d.in1 ? d.in1 : d.in0) + r0 * ld1), 0, 32 * ld1 * 4, 0x00020000);
+        const __amdgpu_buffer_rsrc_t ra = DAWN_BUFFER(d.in0 + r0 * d.ld0, 32 * d.ld0 * 4);
+        const __amdgpu_buffer_rsrc_t rb = DAWN_BUFFER((d.in1 ? d.in1 : d.in0) + r0 * ld1, 32 * ld1 * 4);
         const float shift = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ra, (unsigned)(l31 * d.ld0 * 4), 0, 0));
         float s1 = 0.f, s2 = 0.f;
         for (int kb = 0; kb < nKB; ++kb) {
@@ -465,12 +461,11 @@ __global__ __launch_bounds__(512) void gemm1x1_rowacc_kernel(const dawn_conv_des
                     } else {
                         read_frags(kc, 0);
                     }
-                    constexpr int PW[6] = {0, 2, 1, 0, 1, 0}, PX[6] = {2, 0, 1, 1, 0, 0};
 #pragma unroll
                     for (int t = 0; t < 6; ++t)
 #pragma unroll
                         for (int j = 0; j < 2; ++j)
-                            acc[c][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[NFB == 2 ? (kc & 1) : 0][j][PW[t]], xs[kc][PX[t]], acc[c][j], 0, 0, 0);
+                            acc[c][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[NFB == 2 ? (kc & 1) : 0][j][DAWN_SPLIT6_B[t]], xs[kc][DAWN_SPLIT6_A[t]], acc[c][j], 0, 0, 0);
                 }
                 buf ^= 1;
                 if (last_kb) {

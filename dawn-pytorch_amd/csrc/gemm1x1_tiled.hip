@@ -58,11 +58,9 @@ __global__ __launch_bounds__(256 * (CFG ? 1 : WN)) void gemm1x1_bf16_kernel(cons
     const long m0 = (long)mt * BM;
     const int n0 = nt * BN;
     const int ld1 = d.in1 ? d.ld1 : d.ld0;
-    const __amdgpu_buffer_rsrc_t rsa =
-        __builtin_amdgcn_make_buffer_rsrc((void*)(d.in0 + m0 * d.ld0), 0, BM * d.ld0 * 4, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsa1 = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)((d.in1 ? d.in1 : d.in0) + m0 * ld1), 0, BM * ld1 * 4, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc((void*)d.w_bf3, 0, (K / 16) * 6 * d.N * 16, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsa = DAWN_BUFFER(d.in0 + m0 * d.ld0, BM * d.ld0 * 4);
+    const __amdgpu_buffer_rsrc_t rsa1 = DAWN_BUFFER((d.in1 ? d.in1 : d.in0) + m0 * ld1, BM * ld1 * 4);
+    const __amdgpu_buffer_rsrc_t rsw = DAWN_BUFFER(d.w_bf3, (K / 16) * 6 * d.N * 16);
     // A quads of a stage: BM rows x 8 quads -> NQ per thread: q = tid + NTHR i -> row = q >> 3, quad = q & 7
     const int row0 = tid >> 3, qoff = (tid & 7) * 16;
     unsigned voffB[3];
@@ -73,7 +71,6 @@ __global__ __launch_bounds__(256 * (CFG ? 1 : WN)) void gemm1x1_bf16_kernel(cons
         const int ph = rem / BN, n = rem - ph * BN;
         voffB[j] = (unsigned)((((sub * 6 + ph) * d.N) + n0 + n) * 16);
     }
-    typedef int i32x4 __attribute__((ext_vector_type(4)));
     f32x4 araw[2][NQ];
     uint2 ap[NQ][3];
     // optional LayerNorm prologue (PreNorm / LayerNorm_img with the gain folded into the weights): A = (x - mean[row]) *
@@ -91,8 +88,8 @@ __global__ __launch_bounds__(256 * (CFG ? 1 : WN)) void gemm1x1_bf16_kernel(cons
 #pragma clang fp contract(off)          // the normalised value is ROUNDED before its split (as dawn_ln_rows stores it)
         f32x4 v = slot ? araw[1][qi] : araw[0][qi];
         v = (v - rmu[qi]) * rrs[qi];                           // (without a prologue: mean 0, rstd 1 -- exact)
-        asm volatile("" : "+v"(v));                         // (split3's first residual must not fuse with the product either)
-        split3(v, ap[qi][0], ap[qi][1], ap[qi][2]);
+        asm volatile("" : "+v"(v));                         // (the split's first residual must not fuse with the product either)
+        dawn_split3_rne_quad(v, ap[qi][0], ap[qi][1], ap[qi][2]);
     };
     auto loadA = [&](int s, int slot) {
         const bool src1 = s >= nS0;                            // wave-uniform
@@ -178,10 +175,10 @@ __global__ __launch_bounds__(256 * (CFG ? 1 : WN)) void gemm1x1_bf16_kernel(cons
                         Bb + ((size_t)((sub * 6 + RB[g] * 2 + half) * BN + wn * (32 * TN) + j * 32 + l31)) * 16);
             }
         };
-        // the split of one PAIR of A values in three steps of 5 / 5 / 3 vector instructions (the arithmetic of split3, in its order):
+        // the split of one PAIR of A values in three steps of 5 / 5 / 3 vector instructions (the arithmetic of
+        // dawn_split3_rne_quad, dawn_common.h, in its order; staged by hand because a call cannot be cut into steps):
         // one step goes behind each MFMA, so the vector ALU works while the matrix pipe runs that MFMA (8 issue slots)
         constexpr int NMF = NT * TM * TN, NSTEP = 3 * NQ;       // per half stage: MFMAs; split steps (NQ pairs: NQ / 2 quads)
-        typedef float f32x2 __attribute__((ext_vector_type(2)));
         f32x2 px[NQ], pe[NQ];
         auto split_step = [&](const int sub, const int k) {
 #pragma clang fp contract(off)      // the normalised value is ROUNDED before its split (as dawn_ln_rows stores it): no fma of the product into the residual
@@ -208,8 +205,6 @@ __global__ __launch_bounds__(256 * (CFG ? 1 : WN)) void gemm1x1_bf16_kernel(cons
             const unsigned hb = __builtin_bit_cast(unsigned, h);
             if (e == 0) ap[qi][st].x = hb; else ap[qi][st].y = hb;
         };
-        constexpr int PA9[9] = {2, 2, 1, 2, 0, 1, 1, 0, 0};
-        constexpr int PB9[9] = {2, 1, 2, 0, 2, 1, 0, 1, 0};
         // fences: MFMA and vector ALU instructions keep the order written here; LDS / global / scalar instructions may cross
         constexpr int FENCE = 0x4 | 0x10 | 0x20 | 0x40 | 0x80 | 0x100 | 0x200;
         read_frags(0);
@@ -218,7 +213,7 @@ __global__ __launch_bounds__(256 * (CFG ? 1 : WN)) void gemm1x1_bf16_kernel(cons
 #pragma unroll
             for (int m = 0; m < NMF; ++m) {
                 const int t = 9 - NT + m / (TM * TN), i = (m / TN) % TM, j = m % TN;
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[sub][j][PB9[t]], fa[sub][i][PA9[t]], acc[i][j], 0, 0, 0);
+                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[sub][j][DAWN_SPLIT9_B[t]], fa[sub][i][DAWN_SPLIT9_A[t]], acc[i][j], 0, 0, 0);
 #pragma unroll
                 for (int k = 0; k < NSTEP; ++k)
                     if (k * NMF / NSTEP == m) split_step(sub, k);

@@ -214,7 +214,6 @@ __global__ __launch_bounds__(256) void interp_linear_kernel(const float* __restr
 // holds two 32 x 32 accumulators (rows 0-31 / 32-63) that share its B operand.  A 4-k quad q of the image feeds two MFMAs: lane half
 // h supplies k = 4q + 2h, then 4q + 2h + 1 (one 8-byte load per operand).  Sum order = fixed: each half of K in fp32 MFMA chains of
 // 256 products added in order, lower half + upper half (through LDS), + bias; no atomics, bit-identical run to run.
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 #define POS_BM 64
 
 __global__ __launch_bounds__(256) void pos_conv_kernel(const float* __restrict__ hid, int T, int E, int gw, int k,

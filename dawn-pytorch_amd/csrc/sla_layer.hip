@@ -24,13 +24,6 @@ constexpr int DH = 32;
 constexpr int XLD = 68;
 constexpr int QKVN = 3 * HEADS * DH;
 
-__device__ __forceinline__ f32x16 z16() {
-    f32x16 z;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) z[r] = 0.f;
-    return z;
-}
-
 // stage one 32-pixel tile of LayerNorm'ed rows into LDS: thread t -> pixel t>>4, float4 t&15 (512 threads)
 __device__ __forceinline__ void stage_tile(const float* __restrict__ xf, int n0, int HW, float eps, float* Xt, int tid) {
     const int px = tid >> 4, sub = tid & 15;
@@ -51,7 +44,7 @@ __device__ __forceinline__ void stage_tile(const float* __restrict__ xf, int n0,
 
 // normal-form projection tile: D[px][feat] = sum_c X[px][c] W[c][feat]; A = X rows (LDS), B = weight frags (regs)
 __device__ __forceinline__ f32x16 proj_N(const float* Xt, int l31, int half, const f32x4* w) {
-    f32x16 acc = z16();
+    f32x16 acc = zero16();
     const float* xr = Xt + l31 * XLD + 4 * half;
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
@@ -100,7 +93,7 @@ __global__ __launch_bounds__(512) void sla_c64_context_kernel(const float* __res
     mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
 
     // ---- sweep 2: ctx[d][e] += exp(K - max)[n][d] * V[n][e], den[d] += exp(K - max)[n][d]
-    f32x16 ctx = z16();
+    f32x16 ctx = zero16();
     float den = 0.f;
     stage_tile(xf, 0, HW, eps, Xs[0], tid);
     __syncthreads();
@@ -135,7 +128,7 @@ __global__ __launch_bounds__(512) void sla_c64_context_kernel(const float* __res
     // ---- M_h[d][n] = sum_e ctxn[d][e] Wout[h*32+e][n] : A = ctxn rows d (LDS float4 over e), B = Wout frags
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) {
-        f32x16 m = z16();
+        f32x16 m = zero16();
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             const f32x4 a4 = *reinterpret_cast<const f32x4*>(ct + l31 * 36 + 8 * c + 4 * half);
@@ -161,21 +154,6 @@ __global__ __launch_bounds__(512) void sla_c64_context_kernel(const float* __res
 //    grows) instead of a first sweep that recomputes K only to find the max: softmax is shift-invariant, so
 //    the result differs from the two-sweep kernel by rounding only.
 
-__device__ __forceinline__ void split3_quad(const f32x4 v, uint2& p1, uint2& p2, uint2& p3) {
-    typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-    bf16x4 h1, h2, h3;
-    f32x4 r;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { h1[i] = (__bf16)v[i]; r[i] = v[i] - (float)h1[i]; }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { h2[i] = (__bf16)r[i]; r[i] = r[i] - (float)h2[i]; }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) h3[i] = (__bf16)r[i];
-    p1 = *reinterpret_cast<uint2*>(&h1);
-    p2 = *reinterpret_cast<uint2*>(&h2);
-    p3 = *reinterpret_cast<uint2*>(&h3);
-}
-
 // planes of one 32-pixel tile: [plane 3][chunk 4][k-half 2][px 32] x 16 B (8 channels) = 12 KB.  The tile is requested one
 // iteration ahead (stage_load: thread t -> pixel t>>4, float4 t&15) and normalised / split / written after the MFMAs of the
 // current tile were issued (stage_store), so the HBM latency of the request hides under a whole tile of matrix work.
@@ -198,7 +176,7 @@ __device__ __forceinline__ void stage_store(const f32x4 v, int n0, int HW, float
     f32x4 o = dl * rs;
     if (n >= HW) o = f32x4{0.f, 0.f, 0.f, 0.f};
     uint2 p1, p2, p3;
-    split3_quad(o, p1, p2, p3);
+    dawn_split3_rne_quad(o, p1, p2, p3);
     const int kc = sub >> 2, qd = sub & 3;
     unsigned char* dst = Pt + ((size_t)((kc * 2 + (qd >> 1)) * 32 + px)) * 16 + (qd & 1) * 8;
     *reinterpret_cast<uint2*>(dst) = p1;
@@ -258,11 +236,11 @@ __global__ __launch_bounds__(512) void sla_c64_apply_kernel(const float* x /* ma
         for (int c = 0; c < 8; ++c) xn[c] = (xb[c] - mu) * rs;
 
         f32x16 oT[2];
-        oT[0] = z16();
-        oT[1] = z16();
+        oT[0] = zero16();
+        oT[1] = zero16();
         for (int h = 0; h < HEADS; ++h) {
             // Q^T (32 d x 32 px): A = Wq_h frags (LDS), B = xn
-            f32x16 qT = z16();
+            f32x16 qT = zero16();
 #pragma unroll
             for (int c = 0; c < 8; ++c) {
                 const f32x4 w4 = *reinterpret_cast<const f32x4*>(Wq + ((2 * c + half) * 256 + h * DH + l31) * 4);
@@ -325,7 +303,6 @@ __global__ __launch_bounds__(512) void sla_c64_apply_kernel(const float* x /* ma
 // registers 8j..8j+7 (k-step j; the k order is a free permutation): 24 MFMAs of 32 cycles per head.  LDS: the M planes take 96 KB, so only the
 // two upper planes of Wq stay in LDS (64 KB) and the third -- used by one cross term of six -- is fetched from global memory (32 KB for all heads:
 // L1 / L2 hits), a head ahead.  Exact as before: q (fp32) and M are split into three bf16 each without loss, six cross terms, fp32 accumulation.
-typedef dawn_bf16x8 bf16x8a;
 
 template <bool OUTB>
 __global__ __launch_bounds__(512) void sla_c64_apply_bf16_kernel(const float* x /* may alias `out` */, int HW, int F,
@@ -365,12 +342,12 @@ __global__ __launch_bounds__(512) void sla_c64_apply_bf16_kernel(const float* x 
                 const f32x4 a = *reinterpret_cast<const f32x4*>(mf + ((size_t)(h * 8 + 4 * j + hf) * C + ch) * 4);
                 const f32x4 b = *reinterpret_cast<const f32x4*>(mf + ((size_t)(h * 8 + 4 * j + hf + 2) * C + ch) * 4);
                 const float m8[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-                bf16x8a p0, p1, p2;
+                bf16x8 p0, p1, p2;
                 dawn_split3_oct(m8, p0, p1, p2);
                 unsigned char* dst = Mp + ((size_t)(((h * 2 + j) * 3) * 2 + hf) * C + ch) * 16;
-                *reinterpret_cast<bf16x8a*>(dst) = p0;
-                *reinterpret_cast<bf16x8a*>(dst + 2 * C * 16) = p1;
-                *reinterpret_cast<bf16x8a*>(dst + 4 * C * 16) = p2;
+                *reinterpret_cast<bf16x8*>(dst) = p0;
+                *reinterpret_cast<bf16x8*>(dst + 2 * C * 16) = p1;
+                *reinterpret_cast<bf16x8*>(dst + 4 * C * 16) = p2;
             }
         } else {
             for (int i = tid; i < 64 * 64; i += 512)
@@ -412,7 +389,7 @@ __global__ __launch_bounds__(512) void sla_c64_apply_bf16_kernel(const float* x 
                 for (int e = 0; e < 8; ++e) { const float dl = xv[kc][e] - mu; ss += dl * dl; }
             ss += __shfl_xor(ss, 32, 64);
             const float rs = 1.0f / sqrtf(ss * (1.0f / C) + eps);
-            bf16x8a xs[4][3];
+            bf16x8 xs[4][3];
 #pragma unroll
             for (int kc = 0; kc < 4; ++kc) {
                 float xn[8];
@@ -422,22 +399,21 @@ __global__ __launch_bounds__(512) void sla_c64_apply_bf16_kernel(const float* x 
             }
 
             f32x16 oT[2];
-            oT[0] = z16();
-            oT[1] = z16();
+            oT[0] = zero16();
+            oT[1] = zero16();
             // (OUTB) the third Wq plane of a head straight from global memory, a head ahead
-            bf16x8a wg[4];
+            bf16x8 wg[4];
             auto request_w = [&](int h) {
 #pragma unroll
                 for (int kc = 0; kc < 4; ++kc)
-                    wg[kc] = *reinterpret_cast<const bf16x8a*>(wqkv_s + ((size_t)((kc * 3 + 2) * 2 + half) * QKVN + h * DH + l31) * 8);
+                    wg[kc] = *reinterpret_cast<const bf16x8*>(wqkv_s + ((size_t)((kc * 3 + 2) * 2 + half) * QKVN + h * DH + l31) * 8);
             };
             if constexpr (OUTB) request_w(0);
 #pragma unroll 1
             for (int h = 0; h < HEADS; ++h) {
                 // Q^T (32 d x 32 px): A = Wq_h plane fragments (LDS, lane = feature d), B = the pixel's split channels
-                f32x16 qT = z16();
-                constexpr int PW[6] = {2, 0, 1, 1, 0, 0}, PX[6] = {0, 2, 1, 0, 1, 0};   // smallest cross terms first
-                bf16x8a wc[4];
+                f32x16 qT = zero16();
+                bf16x8 wc[4];
                 if constexpr (OUTB) {
 #pragma unroll
                     for (int kc = 0; kc < 4; ++kc) wc[kc] = wg[kc];
@@ -445,14 +421,14 @@ __global__ __launch_bounds__(512) void sla_c64_apply_bf16_kernel(const float* x 
                 }
 #pragma unroll
                 for (int kc = 0; kc < 4; ++kc) {
-                    bf16x8a wa[3];
+                    bf16x8 wa[3];
 #pragma unroll
                     for (int pl = 0; pl < NPL; ++pl)
-                        wa[pl] = *reinterpret_cast<const bf16x8a*>(Wq + ((size_t)(((kc * NPL + pl) * 2 + half) * 256 + h * DH + l31)) * 16);
+                        wa[pl] = *reinterpret_cast<const bf16x8*>(Wq + ((size_t)(((kc * NPL + pl) * 2 + half) * 256 + h * DH + l31)) * 16);
                     if constexpr (OUTB) wa[2] = wc[kc];
 #pragma unroll
                     for (int u = 0; u < 6; ++u)
-                        qT = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[PW[u]], xs[kc][PX[u]], qT, 0, 0, 0);
+                        qT = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[DAWN_SPLIT6_A[u]], xs[kc][DAWN_SPLIT6_B[u]], qT, 0, 0, 0);
                 }
                 float m = qT[0];
 #pragma unroll
@@ -472,17 +448,17 @@ __global__ __launch_bounds__(512) void sla_c64_apply_bf16_kernel(const float* x 
                         float q8[8];
 #pragma unroll
                         for (int i = 0; i < 8; ++i) q8[i] = qT[8 * j + i] * inv;
-                        bf16x8a qb[3];
+                        bf16x8 qb[3];
                         dawn_split3_oct(q8, qb[0], qb[1], qb[2]);
 #pragma unroll
                         for (int nt = 0; nt < 2; ++nt) {
-                            bf16x8a ma[3];
+                            bf16x8 ma[3];
 #pragma unroll
                             for (int pl = 0; pl < 3; ++pl)
-                                ma[pl] = *reinterpret_cast<const bf16x8a*>(Mp + ((size_t)((((h * 2 + j) * 3 + pl) * 2 + half) * C + 32 * nt + l31)) * 16);
+                                ma[pl] = *reinterpret_cast<const bf16x8*>(Mp + ((size_t)((((h * 2 + j) * 3 + pl) * 2 + half) * C + 32 * nt + l31)) * 16);
 #pragma unroll
                             for (int u = 0; u < 6; ++u)
-                                oT[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ma[PW[u]], qb[PX[u]], oT[nt], 0, 0, 0);
+                                oT[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ma[DAWN_SPLIT6_A[u]], qb[DAWN_SPLIT6_B[u]], oT[nt], 0, 0, 0);
                         }
                     }
                 } else {
@@ -526,21 +502,20 @@ __global__ __launch_bounds__(512) void sla_c64_apply_bf16_kernel(const float* x 
 constexpr int SLA_PART = HEADS * (DH * DH + 2 * DH);       // floats per (frame, slice) partial
 
 // K / V projection of one 32-pixel tile for one head: 48 bf16 MFMAs, the only LDS reads of a tile
-__device__ __forceinline__ void sla_ctx_proj(const unsigned char* Pt, int l31, int half, const bf16x8a (&wk)[4][3],
-                                             const bf16x8a (&wv)[4][3], f32x16& kt, f32x16& vt) {
-    kt = z16();
-    vt = z16();
-    constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};   // smallest cross terms first
+__device__ __forceinline__ void sla_ctx_proj(const unsigned char* Pt, int l31, int half, const bf16x8 (&wk)[4][3],
+                                             const bf16x8 (&wv)[4][3], f32x16& kt, f32x16& vt) {
+    kt = zero16();
+    vt = zero16();
 #pragma unroll
     for (int kc = 0; kc < 4; ++kc) {
-        bf16x8a xa[3];
+        bf16x8 xa[3];
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl)
-            xa[pl] = *reinterpret_cast<const bf16x8a*>(Pt + pl * 4096 + ((size_t)((kc * 2 + half) * 32 + l31)) * 16);
+            xa[pl] = *reinterpret_cast<const bf16x8*>(Pt + pl * 4096 + ((size_t)((kc * 2 + half) * 32 + l31)) * 16);
 #pragma unroll
         for (int u = 0; u < 6; ++u) {
-            kt = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xa[PA[u]], wk[kc][PB[u]], kt, 0, 0, 0);
-            vt = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xa[PA[u]], wv[kc][PB[u]], vt, 0, 0, 0);
+            kt = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xa[DAWN_SPLIT6_A[u]], wk[kc][DAWN_SPLIT6_B[u]], kt, 0, 0, 0);
+            vt = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xa[DAWN_SPLIT6_A[u]], wv[kc][DAWN_SPLIT6_B[u]], vt, 0, 0, 0);
         }
     }
 }
@@ -549,7 +524,6 @@ __device__ __forceinline__ void sla_ctx_proj(const unsigned char* Pt, int l31, i
 template <bool FULL>
 __device__ __forceinline__ void sla_ctx_post(f32x16& kt, const f32x16& vt, int t, int HW, int half, f32x16& ctx, float& den,
                                              float& mx) {
-    constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};
     // `mx` is the softmax reference of column d in log2 units (any reference gives the same quotient; it only has to keep
     // 2^(k - mx) in range): it is raised to the running maximum only when that exceeds it by more than 2^8, so that the
     // rescale of ctx / den is rare even in a short slice.  Numerators stay <= 2^8 (den <= 2^20 per slice): no overflow.
@@ -587,11 +561,11 @@ __device__ __forceinline__ void sla_ctx_post(f32x16& kt, const f32x16& vt, int t
         float ek[8], vv[8];
 #pragma unroll
         for (int i = 0; i < 8; ++i) { ek[i] = kt[8 * j + i]; vv[i] = vt[8 * j + i]; }
-        bf16x8a e3[3], v3[3];
+        bf16x8 e3[3], v3[3];
         dawn_split3_oct(ek, e3[0], e3[1], e3[2]);
         dawn_split3_oct(vv, v3[0], v3[1], v3[2]);
 #pragma unroll
-        for (int u = 0; u < 6; ++u) ctx = __builtin_amdgcn_mfma_f32_32x32x16_bf16(e3[PA[u]], v3[PB[u]], ctx, 0, 0, 0);
+        for (int u = 0; u < 6; ++u) ctx = __builtin_amdgcn_mfma_f32_32x32x16_bf16(e3[DAWN_SPLIT6_A[u]], v3[DAWN_SPLIT6_B[u]], ctx, 0, 0, 0);
     }
 }
 
@@ -607,17 +581,17 @@ __global__ __launch_bounds__(512) void sla_c64_context_part_kernel(const float* 
     const int ntiles = (HW + 31) >> 5;
     const int tA = sl * per, tB = min(ntiles, tA + per);
 
-    bf16x8a wk[4][3], wv[4][3];
+    bf16x8 wk[4][3], wv[4][3];
 #pragma unroll
     for (int kc = 0; kc < 4; ++kc)
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl) {
             const size_t base = ((size_t)((kc * 3 + pl) * 2 + half) * QKVN) * 8;
-            wk[kc][pl] = *reinterpret_cast<const bf16x8a*>(wqkv_s + base + (size_t)(HEADS * DH + h * DH + l31) * 8);
-            wv[kc][pl] = *reinterpret_cast<const bf16x8a*>(wqkv_s + base + (size_t)(2 * HEADS * DH + h * DH + l31) * 8);
+            wk[kc][pl] = *reinterpret_cast<const bf16x8*>(wqkv_s + base + (size_t)(HEADS * DH + h * DH + l31) * 8);
+            wv[kc][pl] = *reinterpret_cast<const bf16x8*>(wqkv_s + base + (size_t)(2 * HEADS * DH + h * DH + l31) * 8);
         }
 
-    f32x16 ctx = z16();
+    f32x16 ctx = zero16();
     float den = 0.f, mx = -3.0e38f;
     f32x4 vnext = {0.f, 0.f, 0.f, 0.f};
     if (tA < tB) stage_store(stage_load(xf, 32 * tA, HW, tid), 32 * tA, HW, eps, Ps[0], tid);
@@ -700,7 +674,7 @@ __global__ __launch_bounds__(512) void sla_c64_context_merge_kernel(const float*
     __syncthreads();
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) {
-        f32x16 m = z16();
+        f32x16 m = zero16();
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             const f32x4 a4 = *reinterpret_cast<const f32x4*>(ct + l31 * 36 + 8 * c + 4 * half);

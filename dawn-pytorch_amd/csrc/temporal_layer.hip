@@ -34,13 +34,6 @@ constexpr int XLD = 68;   // Xs row stride (floats): conflict-free ds_read_b128
 constexpr int KLD = 36;   // Ks row stride
 constexpr float NEG = -1.0e30f;
 
-__device__ __forceinline__ f32x16 zero16() {
-    f32x16 z;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) z[r] = 0.f;
-    return z;
-}
-
 // D^T(32 feat x 32 rows) = W^T . X^T : A = weight fragments (global, packed [K/4][N][4], column n0 + l31),
 // B = row fragments from LDS.  xr points at Xs[row][4*half].
 __device__ __forceinline__ f32x16 proj_T(const float* wp, int Nw, int n, int half, const float* xr) {
@@ -60,22 +53,6 @@ __device__ __forceinline__ f32x16 proj_T(const float* wp, int Nw, int n, int hal
 // ([plane 3][chunk 4][k-half 2][row][8 channels], shared by all 8 heads x {q,k,v}), the pre-split weight fragments
 // (pack_bf3 image [4][3][2][768][8]) are read straight from L2 one chunk ahead: 24 bf16 MFMAs (768 cycles) replace
 // 32 fp32 MFMAs (2048 cycles) per 32x32 projection tile, and the per-head weight staging + its barrier disappear.
-typedef dawn_bf16x8 bf16x8t;
-
-__device__ __forceinline__ void split3_quad_t(const f32x4 v, uint2& p1, uint2& p2, uint2& p3) {
-    typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-    bf16x4 h1, h2, h3;
-    f32x4 r;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { h1[i] = (__bf16)v[i]; r[i] = v[i] - (float)h1[i]; }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { h2[i] = (__bf16)r[i]; r[i] = r[i] - (float)h2[i]; }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) h3[i] = (__bf16)r[i];
-    p1 = *reinterpret_cast<uint2*>(&h1);
-    p2 = *reinterpret_cast<uint2*>(&h2);
-    p3 = *reinterpret_cast<uint2*>(&h3);
-}
 
 // one (TWO = false) or two 32-feature tiles of D^T = W^T . X^T for 32 rows.  Weight fragments come through a buffer
 // descriptor (SGPRs) + one per-lane byte offset + scalar offsets (feature column, chunk, plane): no 64-bit address
@@ -83,16 +60,14 @@ __device__ __forceinline__ void split3_quad_t(const f32x4 v, uint2& p1, uint2& p
 template <bool TWO>
 __device__ __forceinline__ void proj_T_split(const __amdgpu_buffer_rsrc_t rw, unsigned wvoff, int col0, int col1,
                                              const unsigned char* xp, int FP, f32x16& d0, f32x16& d1) {
-    constexpr int PW[6] = {2, 0, 1, 1, 0, 0}, PX[6] = {0, 2, 1, 0, 1, 0};   // smallest cross terms first
     constexpr int WS = 2 * 768 * 16;                 // bytes between (chunk, plane) groups of the weight image
-    typedef int i32x4 __attribute__((ext_vector_type(4)));
     d0 = zero16();
     if (TWO) d1 = zero16();
-    bf16x8t w0[2][3], w1[2][3];
+    bf16x8 w0[2][3], w1[2][3];
 #pragma unroll
     for (int pl = 0; pl < 3; ++pl) {
-        w0[0][pl] = __builtin_bit_cast(bf16x8t, __builtin_amdgcn_raw_buffer_load_b128(rw, wvoff, col0 * 16 + pl * WS, 0));
-        if (TWO) w1[0][pl] = __builtin_bit_cast(bf16x8t, __builtin_amdgcn_raw_buffer_load_b128(rw, wvoff, col1 * 16 + pl * WS, 0));
+        w0[0][pl] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rw, wvoff, col0 * 16 + pl * WS, 0));
+        if (TWO) w1[0][pl] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rw, wvoff, col1 * 16 + pl * WS, 0));
     }
 #pragma unroll
     for (int kc = 0; kc < 4; ++kc) {
@@ -100,20 +75,20 @@ __device__ __forceinline__ void proj_T_split(const __amdgpu_buffer_rsrc_t rw, un
 #pragma unroll
             for (int pl = 0; pl < 3; ++pl) {
                 w0[(kc + 1) & 1][pl] = __builtin_bit_cast(
-                    bf16x8t, __builtin_amdgcn_raw_buffer_load_b128(rw, wvoff, col0 * 16 + ((kc + 1) * 3 + pl) * WS, 0));
+                    bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rw, wvoff, col0 * 16 + ((kc + 1) * 3 + pl) * WS, 0));
                 if (TWO)
                     w1[(kc + 1) & 1][pl] = __builtin_bit_cast(
-                        bf16x8t, __builtin_amdgcn_raw_buffer_load_b128(rw, wvoff, col1 * 16 + ((kc + 1) * 3 + pl) * WS, 0));
+                        bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rw, wvoff, col1 * 16 + ((kc + 1) * 3 + pl) * WS, 0));
             }
         }
-        bf16x8t xs[3];
+        bf16x8 xs[3];
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl)
-            xs[pl] = *reinterpret_cast<const bf16x8t*>(xp + (size_t)((pl * 4 + kc) * 2) * FP * 16);
+            xs[pl] = *reinterpret_cast<const bf16x8*>(xp + (size_t)((pl * 4 + kc) * 2) * FP * 16);
 #pragma unroll
         for (int u = 0; u < 6; ++u) {
-            d0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0[kc & 1][PW[u]], xs[PX[u]], d0, 0, 0, 0);
-            if (TWO) d1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w1[kc & 1][PW[u]], xs[PX[u]], d1, 0, 0, 0);
+            d0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0[kc & 1][DAWN_SPLIT6_A[u]], xs[DAWN_SPLIT6_B[u]], d0, 0, 0, 0);
+            if (TWO) d1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w1[kc & 1][DAWN_SPLIT6_A[u]], xs[DAWN_SPLIT6_B[u]], d1, 0, 0, 0);
         }
     }
 }
@@ -175,7 +150,7 @@ __global__ __launch_bounds__(512) void temporal_layer_c64_kernel(
             if (j >= Fext) o = f32x4{0.f, 0.f, 0.f, 0.f};
             if (SPLIT) {
                 uint2 p1, p2, p3;
-                split3_quad_t(o, p1, p2, p3);
+                dawn_split3_rne_quad(o, p1, p2, p3);
                 const int kc = sub >> 2, qd = sub & 3;
                 unsigned char* dst = reinterpret_cast<unsigned char*>(Xs) + ((size_t)(kc * 2 + (qd >> 1)) * FP + j) * 16 + (qd & 1) * 8;
                 *reinterpret_cast<uint2*>(dst) = p1;
@@ -189,7 +164,7 @@ __global__ __launch_bounds__(512) void temporal_layer_c64_kernel(
     __syncthreads();
 
     // WMODE 2: descriptor of the split weight image + this lane's byte offset (k-half, feature column l31)
-    const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc((void*)wqkv_s, 0, 4 * 3 * 2 * 768 * 16, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsw = DAWN_BUFFER(wqkv_s, 4 * 3 * 2 * 768 * 16);
     const unsigned wvoff = (unsigned)((half * 768 + l31) * 16);
     const int nqt = (Fq + 31) >> 5;
     const bool has_q = wave < nqt;           // this wave's query tile (8 waves => Fq <= 256)
@@ -504,59 +479,43 @@ __global__ __launch_bounds__(512) void temporal_layer_c64_kernel(
 //     start `delta` = (q0 - win) mod 16 rows before q0 (dummy queries in front are computed and not stored).
 // LDS: X planes 384 B + K planes 192 B per frame row (rows = Fext, no padding: reads clamp) + V^T 192 B per key of
 // 32*nrt + the bias table: 163,328 B at Fext = 200 (the benchmark clip); longer buffers (T-shard interior shards) use
-// WMODE 2 / 1.
-// Exact 3-way split of 8 fp32 values into bf16 pieces by TRUNCATION: p1 = top 16 bits of x, r = x - p1 (exact), p2 = top 16
-// bits of r, r2 = r - p2 (exact, <= 8 significant bits left) = p3.  p1 + p2 + p3 == x bit for bit, every piece is a valid
-// bf16, and the instruction mix is the cheap one on gfx950 (tools/ubench/valu_rate.hip: v_and / v_sub issue at ~2.4 cycles
-// with two waves per SIMD, v_cvt_pk_bf16_f32 / v_lshlrev / v_perm at ~4.3): per pair 4 v_and + 4 v_sub + 3 v_perm.
-// (dawn_split3_oct, dawn_common.h)
-
-// Sum over the 16 lanes of a DPP row, result in every lane, as four v_add_f32_dpp (quad xor 1, quad xor 2, half-row mirror,
-// row mirror): same pairing tree as the xor butterfly (bit-identical), without its ds_bpermute round trips.
-__device__ __forceinline__ float row16_sum(float v) {
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, true));
-    return v;
-}
+// WMODE 2 / 1.  The in-kernel operand splits are the truncation split (dawn_split3_oct, dawn_common.h).
 
 // K^T (transposed: lane = row, registers = features) and V (lane = feature, registers = rows) of one 32-row tile for one
 // head, sharing the X plane fragments; weights through the buffer descriptor as in proj_T_split.
 __device__ __forceinline__ void proj_KV_split(const __amdgpu_buffer_rsrc_t rw, unsigned wvoff, int colk, int colv,
                                               const unsigned char* xp, int FA, f32x16& kT, f32x16& v) {
-    constexpr int PW[6] = {2, 0, 1, 1, 0, 0}, PX[6] = {0, 2, 1, 0, 1, 0};
     constexpr int WS = 2 * 768 * 16;
     kT = zero16();
     v = zero16();
     // all 24 weight fragments of the head's K / V slices are requested before the first MFMA (96 VGPRs): one exposed L2
     // round trip per row tile instead of one per 16-channel chunk (a chunk's 12 MFMAs are shorter than the L2 latency)
-    bf16x8t wk[4][3], wv[4][3];
+    bf16x8 wk[4][3], wv[4][3];
 #pragma unroll
     for (int kc = 0; kc < 4; ++kc)
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl) {
-            wk[kc][pl] = __builtin_bit_cast(bf16x8t, __builtin_amdgcn_raw_buffer_load_b128(rw, wvoff, colk * 16 + (kc * 3 + pl) * WS, 0));
-            wv[kc][pl] = __builtin_bit_cast(bf16x8t, __builtin_amdgcn_raw_buffer_load_b128(rw, wvoff, colv * 16 + (kc * 3 + pl) * WS, 0));
+            wk[kc][pl] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rw, wvoff, colk * 16 + (kc * 3 + pl) * WS, 0));
+            wv[kc][pl] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rw, wvoff, colv * 16 + (kc * 3 + pl) * WS, 0));
         }
     __builtin_amdgcn_sched_barrier(0);          // keep the requests in front (the scheduler sinks them to save registers)
 #pragma unroll
     for (int kc = 0; kc < 4; ++kc) {
-        bf16x8t xs[3];
+        bf16x8 xs[3];
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl)
-            xs[pl] = *reinterpret_cast<const bf16x8t*>(xp + (size_t)((pl * 4 + kc) * 2) * FA * 16);
+            xs[pl] = *reinterpret_cast<const bf16x8*>(xp + (size_t)((pl * 4 + kc) * 2) * FA * 16);
 #pragma unroll
         for (int u = 0; u < 6; ++u) {
-            kT = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wk[kc][PW[u]], xs[PX[u]], kT, 0, 0, 0);   // D^T = W^T . X^T
-            v = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xs[PX[u]], wv[kc][PW[u]], v, 0, 0, 0);     // D   = X . W
+            kT = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wk[kc][DAWN_SPLIT6_A[u]], xs[DAWN_SPLIT6_B[u]], kT, 0, 0, 0);   // D^T = W^T . X^T
+            v = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xs[DAWN_SPLIT6_B[u]], wv[kc][DAWN_SPLIT6_A[u]], v, 0, 0, 0);     // D   = X . W
         }
     }
 }
 
 // the same, as two passes: K^T first (returned early so that the caller's rotary + split of K runs in the shadow of the V
 // pass) -- the V pass is `proj_V_pass`; weight fragments of both are requested up front by the caller
-struct KVWeights { bf16x8t w[4][3]; };
+struct KVWeights { bf16x8 w[4][3]; };
 template <bool VPASS>
 __device__ __forceinline__ void kv_weights_request(const __amdgpu_buffer_rsrc_t rw, unsigned wvoff, int col, KVWeights& w) {
     constexpr int WS = 2 * 768 * 16;
@@ -564,23 +523,22 @@ __device__ __forceinline__ void kv_weights_request(const __amdgpu_buffer_rsrc_t 
     for (int kc = 0; kc < 4; ++kc)
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl)
-            w.w[kc][pl] = __builtin_bit_cast(bf16x8t, __builtin_amdgcn_raw_buffer_load_b128(rw, wvoff, col * 16 + (kc * 3 + pl) * WS, 0));
+            w.w[kc][pl] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rw, wvoff, col * 16 + (kc * 3 + pl) * WS, 0));
     __builtin_amdgcn_sched_barrier(0);
 }
 template <bool VPASS>
 __device__ __forceinline__ f32x16 proj_pass(const KVWeights& w, const unsigned char* xp, int FA) {
-    constexpr int PW[6] = {2, 0, 1, 1, 0, 0}, PX[6] = {0, 2, 1, 0, 1, 0};
     f32x16 d = zero16();
 #pragma unroll
     for (int kc = 0; kc < 4; ++kc) {
-        bf16x8t xs[3];
+        bf16x8 xs[3];
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl)
-            xs[pl] = *reinterpret_cast<const bf16x8t*>(xp + (size_t)((pl * 4 + kc) * 2) * FA * 16);
+            xs[pl] = *reinterpret_cast<const bf16x8*>(xp + (size_t)((pl * 4 + kc) * 2) * FA * 16);
 #pragma unroll
         for (int u = 0; u < 6; ++u) {
-            if (VPASS) d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xs[PX[u]], w.w[kc][PW[u]], d, 0, 0, 0);     // D   = X . W
-            else d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.w[kc][PW[u]], xs[PX[u]], d, 0, 0, 0);           // D^T = W^T . X^T
+            if (VPASS) d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xs[DAWN_SPLIT6_B[u]], w.w[kc][DAWN_SPLIT6_A[u]], d, 0, 0, 0);     // D   = X . W
+            else d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.w[kc][DAWN_SPLIT6_A[u]], xs[DAWN_SPLIT6_B[u]], d, 0, 0, 0);           // D^T = W^T . X^T
         }
     }
     return d;
@@ -589,24 +547,23 @@ __device__ __forceinline__ f32x16 proj_pass(const KVWeights& w, const unsigned c
 // Q^T of one 32-row tile for one head, all 12 weight fragments requested up front (see proj_KV_split)
 __device__ __forceinline__ f32x16 proj_Q_split(const __amdgpu_buffer_rsrc_t rw, unsigned wvoff, int col,
                                                const unsigned char* xp, int FA) {
-    constexpr int PW[6] = {2, 0, 1, 1, 0, 0}, PX[6] = {0, 2, 1, 0, 1, 0};
     constexpr int WS = 2 * 768 * 16;
     f32x16 d = zero16();
-    bf16x8t w[4][3];
+    bf16x8 w[4][3];
 #pragma unroll
     for (int kc = 0; kc < 4; ++kc)
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl)
-            w[kc][pl] = __builtin_bit_cast(bf16x8t, __builtin_amdgcn_raw_buffer_load_b128(rw, wvoff, col * 16 + (kc * 3 + pl) * WS, 0));
+            w[kc][pl] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rw, wvoff, col * 16 + (kc * 3 + pl) * WS, 0));
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int kc = 0; kc < 4; ++kc) {
-        bf16x8t xs[3];
+        bf16x8 xs[3];
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl)
-            xs[pl] = *reinterpret_cast<const bf16x8t*>(xp + (size_t)((pl * 4 + kc) * 2) * FA * 16);
+            xs[pl] = *reinterpret_cast<const bf16x8*>(xp + (size_t)((pl * 4 + kc) * 2) * FA * 16);
 #pragma unroll
-        for (int u = 0; u < 6; ++u) d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w[kc][PW[u]], xs[PX[u]], d, 0, 0, 0);
+        for (int u = 0; u < 6; ++u) d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w[kc][DAWN_SPLIT6_A[u]], xs[DAWN_SPLIT6_B[u]], d, 0, 0, 0);
     }
     return d;
 }
@@ -681,7 +638,7 @@ __global__ __launch_bounds__(512) void temporal_layer_c64_bf16_kernel(
             const float rs = 1.0f / sqrtf(ss * (1.0f / C) + eps);
             const f32x4 o = dl * rs;
             uint2 p1, p2, p3;
-            split3_quad_t(o, p1, p2, p3);
+            dawn_split3_rne_quad(o, p1, p2, p3);
             const int kc = sub >> 2, qd = sub & 3;
             if (j < Fext) {
                 unsigned char* dst = Xp + ((size_t)(kc * 2 + (qd >> 1)) * FA + j) * 16 + (qd & 1) * 8;
@@ -693,7 +650,7 @@ __global__ __launch_bounds__(512) void temporal_layer_c64_bf16_kernel(
     }
     __syncthreads();
 
-    const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc((void*)wqkv_s, 0, 4 * 3 * 2 * 768 * 16, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsw = DAWN_BUFFER(wqkv_s, 4 * 3 * 2 * 768 * 16);
     const unsigned wvoff = (unsigned)((half * 768 + l31) * 16);
     const int nqt = (Fq + delta + 31) >> 5;
     const bool has_q = wave < nqt;
@@ -712,7 +669,6 @@ __global__ __launch_bounds__(512) void temporal_layer_c64_bf16_kernel(
             qcs[c].x *= sl; qcs[c].y *= sl; qsn[c].x *= sl; qsn[c].y *= sl;
         }
     }
-    constexpr int PA6[6] = {2, 0, 1, 1, 0, 0}, PB6[6] = {0, 2, 1, 0, 1, 0};      // smallest cross terms first
     f32x16 outT[2];
     outT[0] = zero16();
     outT[1] = zero16();
@@ -722,8 +678,7 @@ __global__ __launch_bounds__(512) void temporal_layer_c64_bf16_kernel(
     // Buffer loads: one per-lane byte offset for K / Q and one for V plus scalar row / head offsets -- no 64-bit address registers
     float kvr[2][16], qreg[16];
     const int wv = __builtin_amdgcn_readfirstlane(wave);      // (scalar: the row-tile / key / head offsets below stay in SGPRs)
-    typedef int i32x4_t __attribute__((ext_vector_type(4)));
-    const __amdgpu_buffer_rsrc_t rsx = __builtin_amdgcn_make_buffer_rsrc((void*)x, 0, EXT ? Fext * HW * (QKV * 4) : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsx = DAWN_BUFFER(x, EXT ? Fext * HW * (QKV * 4) : 0);
     const unsigned kvoff = (unsigned)((l31 * HW + (int)p) * (QKV * 4) + half * 16);            // row l31 of a row tile, k-half
     const unsigned vvoff = (unsigned)((4 * half * HW + (int)p) * (QKV * 4) + l31 * 4);         // key 4 half of a 16-key group, feature
     const unsigned qvoff = (unsigned)((iqc * HW + (int)p) * (QKV * 4) + half * 16);
@@ -736,7 +691,7 @@ __global__ __launch_bounds__(512) void temporal_layer_c64_bf16_kernel(
             const int so = (HEADS * DH + hh * DH) * 4;
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
-                const f32x4 v = __builtin_bit_cast(f32x4, (i32x4_t)__builtin_amdgcn_raw_buffer_load_b128(rsx, vo, so + 32 * c, 0));
+                const f32x4 v = __builtin_bit_cast(f32x4, (i32x4)__builtin_amdgcn_raw_buffer_load_b128(rsx, vo, so + 32 * c, 0));
 #pragma unroll
                 for (int e = 0; e < 4; ++e) reg[4 * c + e] = v[e];
             }
@@ -772,13 +727,13 @@ __global__ __launch_bounds__(512) void temporal_layer_c64_bf16_kernel(
                     kr[4 * cc + 2] = reg[4 * c + 2] * cs.y - reg[4 * c + 3] * sn.y;
                     kr[4 * cc + 3] = reg[4 * c + 3] * cs.y + reg[4 * c + 2] * sn.y;
                 }
-                bf16x8t k1, k2, k3;
+                bf16x8 k1, k2, k3;
                 dawn_split3_oct(kr, k1, k2, k3);
                 if (j < Fext) {
                     unsigned char* dst = Kp + ((size_t)(kc * 2 + half) * FA + j) * 16;
-                    *reinterpret_cast<bf16x8t*>(dst) = k1;
-                    *reinterpret_cast<bf16x8t*>(dst + (size_t)4 * FA * 16) = k2;
-                    *reinterpret_cast<bf16x8t*>(dst + (size_t)8 * FA * 16) = k3;
+                    *reinterpret_cast<bf16x8*>(dst) = k1;
+                    *reinterpret_cast<bf16x8*>(dst + (size_t)4 * FA * 16) = k2;
+                    *reinterpret_cast<bf16x8*>(dst + (size_t)8 * FA * 16) = k3;
                 }
             }
         } else {
@@ -790,19 +745,19 @@ __global__ __launch_bounds__(512) void temporal_layer_c64_bf16_kernel(
                     const int key = 32 * rt + 16 * g + 4 * half + (i & 3) + 8 * (i >> 2);
                     vr[i] = key < Fext ? reg[8 * g + i] : 0.f;                 // finite zeros for the padded keys (their P is exactly 0)
                 }
-                bf16x8t v1, v2, v3;
+                bf16x8 v1, v2, v3;
                 dawn_split3_oct(vr, v1, v2, v3);
                 unsigned char* dst = Vt + ((size_t)((2 * rt + g) * 2 + half) * 32 + l31) * 16;
-                *reinterpret_cast<bf16x8t*>(dst) = v1;
-                *reinterpret_cast<bf16x8t*>(dst + (size_t)NBV * 64 * 16) = v2;
-                *reinterpret_cast<bf16x8t*>(dst + (size_t)2 * NBV * 64 * 16) = v3;
+                *reinterpret_cast<bf16x8*>(dst) = v1;
+                *reinterpret_cast<bf16x8*>(dst + (size_t)NBV * 64 * 16) = v2;
+                *reinterpret_cast<bf16x8*>(dst + (size_t)2 * NBV * 64 * 16) = v3;
             }
         }
     };
     auto q_request = [&](int hh) {
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-            const f32x4 v = __builtin_bit_cast(f32x4, (i32x4_t)__builtin_amdgcn_raw_buffer_load_b128(rsx, qvoff, hh * DH * 4 + 32 * c, 0));
+            const f32x4 v = __builtin_bit_cast(f32x4, (i32x4)__builtin_amdgcn_raw_buffer_load_b128(rsx, qvoff, hh * DH * 4 + 32 * c, 0));
 #pragma unroll
             for (int e = 0; e < 4; ++e) qreg[4 * c + e] = v[e];
         }
@@ -860,13 +815,13 @@ __global__ __launch_bounds__(512) void temporal_layer_c64_bf16_kernel(
                         kr[4 * cc + 2] = kT[4 * c + 2] * cs.y - kT[4 * c + 3] * sn.y;
                         kr[4 * cc + 3] = kT[4 * c + 3] * cs.y + kT[4 * c + 2] * sn.y;
                     }
-                    bf16x8t k1, k2, k3;
+                    bf16x8 k1, k2, k3;
                     dawn_split3_oct(kr, k1, k2, k3);
                     if (j < Fext) {
                         unsigned char* dst = Kp + ((size_t)(kc * 2 + half) * FA + j) * 16;
-                        *reinterpret_cast<bf16x8t*>(dst) = k1;
-                        *reinterpret_cast<bf16x8t*>(dst + (size_t)4 * FA * 16) = k2;
-                        *reinterpret_cast<bf16x8t*>(dst + (size_t)8 * FA * 16) = k3;
+                        *reinterpret_cast<bf16x8*>(dst) = k1;
+                        *reinterpret_cast<bf16x8*>(dst + (size_t)4 * FA * 16) = k2;
+                        *reinterpret_cast<bf16x8*>(dst + (size_t)8 * FA * 16) = k3;
                     }
                 }
             } else {
@@ -885,12 +840,12 @@ __global__ __launch_bounds__(512) void temporal_layer_c64_bf16_kernel(
                             vr[i] = key < Fext ? vr[i] : 0.f;           // finite zeros (their P is exactly 0)
                         }
                     }
-                    bf16x8t v1, v2, v3;
+                    bf16x8 v1, v2, v3;
                     dawn_split3_oct(vr, v1, v2, v3);
                     unsigned char* dst = Vt + ((size_t)((2 * rt + g) * 2 + half) * 32 + l31) * 16;
-                    *reinterpret_cast<bf16x8t*>(dst) = v1;
-                    *reinterpret_cast<bf16x8t*>(dst + (size_t)NBV * 64 * 16) = v2;
-                    *reinterpret_cast<bf16x8t*>(dst + (size_t)2 * NBV * 64 * 16) = v3;
+                    *reinterpret_cast<bf16x8*>(dst) = v1;
+                    *reinterpret_cast<bf16x8*>(dst + (size_t)NBV * 64 * 16) = v2;
+                    *reinterpret_cast<bf16x8*>(dst + (size_t)2 * NBV * 64 * 16) = v3;
                 }
             }
         }
@@ -922,13 +877,13 @@ __global__ __launch_bounds__(512) void temporal_layer_c64_bf16_kernel(
                     kr[4 * cc + 2] = kT[4 * c + 2] * cs.y - kT[4 * c + 3] * sn.y;
                     kr[4 * cc + 3] = kT[4 * c + 3] * cs.y + kT[4 * c + 2] * sn.y;
                 }
-                bf16x8t k1, k2, k3;
+                bf16x8 k1, k2, k3;
                 dawn_split3_oct(kr, k1, k2, k3);
                 if (j < Fext) {
                     unsigned char* dst = Kp + ((size_t)(kc * 2 + half) * FA + j) * 16;
-                    *reinterpret_cast<bf16x8t*>(dst) = k1;
-                    *reinterpret_cast<bf16x8t*>(dst + (size_t)4 * FA * 16) = k2;
-                    *reinterpret_cast<bf16x8t*>(dst + (size_t)8 * FA * 16) = k3;
+                    *reinterpret_cast<bf16x8*>(dst) = k1;
+                    *reinterpret_cast<bf16x8*>(dst + (size_t)4 * FA * 16) = k2;
+                    *reinterpret_cast<bf16x8*>(dst + (size_t)8 * FA * 16) = k3;
                 }
             }
             // V: lane = feature d = l31, registers 8g..8g+7 = keys 32 rt + 16 g + 4 half + (i & 3) + 8 (i >> 2)
@@ -944,12 +899,12 @@ __global__ __launch_bounds__(512) void temporal_layer_c64_bf16_kernel(
                         vr[i] = key < Fext ? vr[i] : 0.f;               // finite zeros (their P is exactly 0)
                     }
                 }
-                bf16x8t v1, v2, v3;
+                bf16x8 v1, v2, v3;
                 dawn_split3_oct(vr, v1, v2, v3);
                 unsigned char* dst = Vt + ((size_t)((2 * rt + g) * 2 + half) * 32 + l31) * 16;
-                *reinterpret_cast<bf16x8t*>(dst) = v1;
-                *reinterpret_cast<bf16x8t*>(dst + (size_t)NBV * 64 * 16) = v2;
-                *reinterpret_cast<bf16x8t*>(dst + (size_t)2 * NBV * 64 * 16) = v3;
+                *reinterpret_cast<bf16x8*>(dst) = v1;
+                *reinterpret_cast<bf16x8*>(dst + (size_t)NBV * 64 * 16) = v2;
+                *reinterpret_cast<bf16x8*>(dst + (size_t)2 * NBV * 64 * 16) = v3;
             }
         }
         }
@@ -968,7 +923,7 @@ __global__ __launch_bounds__(512) void temporal_layer_c64_bf16_kernel(
 
         if (has_q) {
             // ---- Q^T (registers = B fragments): scale + rotary (lane-local), split into three bf16 pieces per d-chunk
-            bf16x8t qp[3][2];
+            bf16x8 qp[3][2];
             {
                 f32x16 qT;
                 if constexpr (EXT) {
@@ -1023,17 +978,17 @@ __global__ __launch_bounds__(512) void temporal_layer_c64_bf16_kernel(
                     if (r < nreg(t)) st[t][r] = bb[32 * t + (r & 3) + 8 * (r >> 2)];
                 const int j = max(0, min(j0 + 32 * t + l31, Fext - 1));
                 const unsigned char* kr = Kp + ((size_t)half * FA + j) * 16;
-                bf16x8t kf[3][2];
+                bf16x8 kf[3][2];
 #pragma unroll
                 for (int pl = 0; pl < 3; ++pl)
 #pragma unroll
                     for (int kc = 0; kc < 2; ++kc)
-                        kf[pl][kc] = *reinterpret_cast<const bf16x8t*>(kr + (size_t)((pl * 2 + kc) * 2) * FA * 16);
+                        kf[pl][kc] = *reinterpret_cast<const bf16x8*>(kr + (size_t)((pl * 2 + kc) * 2) * FA * 16);
 #pragma unroll
                 for (int kc = 0; kc < 2; ++kc)
 #pragma unroll
                     for (int u = 0; u < 6; ++u)
-                        st[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[PA6[u]][kc], qp[PB6[u]][kc], st[t], 0, 0, 0);
+                        st[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[DAWN_SPLIT6_A[u]][kc], qp[DAWN_SPLIT6_B[u]][kc], st[t], 0, 0, 0);
             };
             const int lo = j0 < 0 ? -j0 : 0;
             const int hi = Fext - j0 < 32 * NKT ? Fext - j0 : 32 * NKT;
@@ -1069,16 +1024,16 @@ __global__ __launch_bounds__(512) void temporal_layer_c64_bf16_kernel(
                     if (8 * g >= nreg(t)) continue;
                     const int b = max(0, min((j0m >> 4) + 2 * t + g, NBV - 1));    // clamped blocks hold masked keys only (P = 0)
                     const unsigned char* vr = Vt + ((size_t)(b * 2 + half) * 32 + l31) * 16;
-                    bf16x8t vf[3];
+                    bf16x8 vf[3];
 #pragma unroll
-                    for (int pl = 0; pl < 3; ++pl) vf[pl] = *reinterpret_cast<const bf16x8t*>(vr + (size_t)pl * NBV * 64 * 16);
+                    for (int pl = 0; pl < 3; ++pl) vf[pl] = *reinterpret_cast<const bf16x8*>(vr + (size_t)pl * NBV * 64 * 16);
                     float pr[8];
 #pragma unroll
                     for (int i = 0; i < 8; ++i) pr[i] = st[t][8 * g + i];
-                    bf16x8t pp[3];
+                    bf16x8 pp[3];
                     dawn_split3_oct(pr, pp[0], pp[1], pp[2]);
 #pragma unroll
-                    for (int u = 0; u < 6; ++u) o = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[PA6[u]], pp[PB6[u]], o, 0, 0, 0);
+                    for (int u = 0; u < 6; ++u) o = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[DAWN_SPLIT6_A[u]], pp[DAWN_SPLIT6_B[u]], o, 0, 0, 0);
                 }
             };
 #pragma unroll
@@ -1140,7 +1095,7 @@ __global__ __launch_bounds__(512) void temporal_layer_c64_bf16_kernel(
             l += __shfl_xor(l, 32, 64);
             if (h < 2) TSTAMP();   // PV(A) issued + softmax(B)
             // to_out fragments of this head (bf16 pipe): requested here, consumed after P.V of half B
-            bf16x8t wf[2][3][2];
+            bf16x8 wf[2][3][2];
             if (OB) {
                 const unsigned char* wb = reinterpret_cast<const unsigned char*>(wout_sp) + ((size_t)half * C + l31) * 16;
 #pragma unroll
@@ -1149,7 +1104,7 @@ __global__ __launch_bounds__(512) void temporal_layer_c64_bf16_kernel(
                     for (int kc = 0; kc < 2; ++kc)
 #pragma unroll
                         for (int pl = 0; pl < 3; ++pl)
-                            wf[nt][pl][kc] = *reinterpret_cast<const bf16x8t*>(
+                            wf[nt][pl][kc] = *reinterpret_cast<const bf16x8*>(
                                 wb + ((size_t)(((2 * h + kc) * 3 + pl) * 2) * C + 32 * nt) * 16);
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -1176,7 +1131,7 @@ __global__ __launch_bounds__(512) void temporal_layer_c64_bf16_kernel(
                 // ---- out^T += Wout_h^T . O^T on the bf16 pipe: O^T split from the accumulators (registers 8kc..8kc+7 = the
                 // B fragment of d-chunk kc), to_out as the k-permuted 3-way split image wout_sp (pack.pack_bf3_temporal_out:
                 // slot (kc, k-half, i) of head h holds row h*32 + 16 kc + 8 (i >> 2) + 4 k-half + (i & 3))
-                bf16x8t op[3][2];
+                bf16x8 op[3][2];
 #pragma unroll
                 for (int kc = 0; kc < 2; ++kc) {
                     float orr[8];
@@ -1190,7 +1145,7 @@ __global__ __launch_bounds__(512) void temporal_layer_c64_bf16_kernel(
                     for (int kc = 0; kc < 2; ++kc)
 #pragma unroll
                         for (int u = 0; u < 6; ++u)
-                            outT[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[nt][PA6[u]][kc], op[PB6[u]][kc], outT[nt], 0, 0, 0);
+                            outT[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[nt][DAWN_SPLIT6_A[u]][kc], op[DAWN_SPLIT6_B[u]][kc], outT[nt], 0, 0, 0);
             } else {
                 // ---- out^T += Wout_h^T . O^T   (fp32 MFMA; A = to_out rows h*32 + d, columns n)
 #pragma unroll

@@ -65,53 +65,19 @@ constexpr int BAND_BYTES = 4 * BLD * 4;
 constexpr int LDS_BYTES = XP_BYTES + KP_BYTES + VP_BYTES + BAND_BYTES;
 static_assert(LDS_BYTES == TL16_LDS_BYTES, "LDS layout");
 
-typedef dawn_bf16x8 bf16x8t;
-typedef int i32x4_t __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ f32x4 zero4() { return f32x4{0.f, 0.f, 0.f, 0.f}; }
-
-// Sum over the 16 lanes of a DPP row (temporal_layer.hip's: same pairing tree as the xor butterfly)
-__device__ __forceinline__ float row16_sum(float v) {
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, true));
-    return v;
-}
-
-// truncation split of four fp32 values into three 4 x bf16 pieces (dawn_split3_oct's arithmetic on a quad)
-__device__ __forceinline__ void split3_quad(const f32x4 v, uint2& p1, uint2& p2, uint2& p3) {
-    unsigned q1[2], q2[2], q3[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const float a = v[2 * i], b = v[2 * i + 1];
-        const unsigned a1 = __float_as_uint(a) & 0xffff0000u, b1 = __float_as_uint(b) & 0xffff0000u;
-        const float ra = a - __uint_as_float(a1), rb = b - __uint_as_float(b1);
-        const unsigned a2 = __float_as_uint(ra) & 0xffff0000u, b2 = __float_as_uint(rb) & 0xffff0000u;
-        const float sa = ra - __uint_as_float(a2), sb = rb - __uint_as_float(b2);
-        q1[i] = __builtin_amdgcn_perm(b1, a1, 0x07060302u);
-        q2[i] = __builtin_amdgcn_perm(b2, a2, 0x07060302u);
-        q3[i] = __builtin_amdgcn_perm(__float_as_uint(sb), __float_as_uint(sa), 0x07060302u);
-    }
-    p1 = uint2{q1[0], q1[1]};
-    p2 = uint2{q2[0], q2[1]};
-    p3 = uint2{q3[0], q3[1]};
-}
-
 // The result registers must not be the A / B operand registers.  hipcc (ROCm 7.2) allows that overlap for the 4-register results of
 // the 16 x 16 shapes -- once a fragment's last use is an MFMA whose accumulator starts elsewhere (0, or a value that stays live) it
 // emits e.g. `v_mfma_f32_16x16x32_bf16 v[4:7], v[4:7], v[16:19], 0` -- and on gfx950 that instruction then occasionally (1 workgroup
 // in ~100, timing dependent) returns rows 12..15 of the tile (lanes 48..63) computed from clobbered operands: found with
 // tools/debug_tl16_dump.py (sum(q) differed in lanes 48..63 only).  The empty asm keeps both operands live across the MFMA.
-__device__ __forceinline__ f32x4 mfma16(const bf16x8t a, const bf16x8t b, const f32x4 c) {
+__device__ __forceinline__ f32x4 mfma16(const bf16x8 a, const bf16x8 b, const f32x4 c) {
     f32x4 d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
     asm("" : "+v"(d) : "v"(a), "v"(b));
     return d;
 }
 
-__device__ __forceinline__ bf16x8t join8(const uint2 lo, const uint2 hi) {
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    return __builtin_bit_cast(bf16x8t, u32x4{lo.x, lo.y, hi.x, hi.y});
+__device__ __forceinline__ bf16x8 join8(const uint2 lo, const uint2 hi) {
+    return __builtin_bit_cast(bf16x8, u32x4{lo.x, lo.y, hi.x, hi.y});
 }
 
 // v_max3_f32 on values that are never NaN (fmaxf would first quiet each operand with a v_max x, x: two extra instructions per call)
@@ -143,8 +109,6 @@ __device__ __forceinline__ float rows4_sum(float v) {
     return __uint_as_float(r[0]) + __uint_as_float(r[1]);
 }
 
-// the six cross terms of the 3-way split, smallest first: (a3 b1) (a1 b3) (a2 b2) (a2 b1) (a1 b2) (a1 b1)
-constexpr int PA6[6] = {2, 0, 1, 1, 0, 0}, PB6[6] = {0, 2, 1, 0, 1, 0};
 
 template <int NTILE>
 __global__ __launch_bounds__(NT) void temporal_layer16_kernel(
@@ -196,7 +160,8 @@ __global__ __launch_bounds__(NT) void temporal_layer16_kernel(
             ss = row16_sum(ss);
             const float rs = 1.0f / sqrtf(ss * (1.0f / C) + eps);
             const f32x4 o = dl * rs;
-            // round-to-nearest split (the planes the 32 x 32 kernel builds: identical X operands)
+            // dawn_split3_rne_quad (dawn_common.h) written out: the planes the 32 x 32 kernel builds, identical X operands.  (A call
+            // here changes this kernel's instruction order -- the split sinks into the branch below differently; the 13-frame kernel calls it)
             typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
             bf16x4 h1, h2, h3;
             f32x4 r;
@@ -223,15 +188,15 @@ __global__ __launch_bounds__(NT) void temporal_layer16_kernel(
     const int nblk = (Fext + 15) >> 4;
     const int nkb = (16 + 2 * win + 15) >> 4;
 
-    const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc((void*)wqkv_s, 0, 4 * 3 * 2 * 768 * 16, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsw = DAWN_BUFFER(wqkv_s, 4 * 3 * 2 * 768 * 16);
     // weight image [chunk kc][plane][k-half][768 columns] x 16 B; k-group g of k-step s = chunk 2 s + (g >> 1), k-half g & 1
     const unsigned wlane = (unsigned)(((6 * (g >> 1) + (g & 1)) * 768 + n) * 16);
     const unsigned wlane_v = (unsigned)(((6 * (g >> 1) + (g & 1)) * 768 + 16 * (n >> 3) + (n & 7)) * 16);
-    const __amdgpu_buffer_rsrc_t rso = __builtin_amdgcn_make_buffer_rsrc((void*)wout_sp, 0, 16 * 3 * 2 * C * 16, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rso = DAWN_BUFFER(wout_sp, 16 * 3 * 2 * C * 16);
     const unsigned wolane = (unsigned)(((6 * (g >> 1) + (g & 1)) * C + n) * 16);
     // rotary tables through descriptors too: 32-bit lane offsets (row . 64 + 8 . (2 g) bytes) instead of 64-bit addresses
-    const __amdgpu_buffer_rsrc_t rsc = __builtin_amdgcn_make_buffer_rsrc((void*)rcos, 0, Fext * 64, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rss = __builtin_amdgcn_make_buffer_rsrc((void*)rsin, 0, Fext * 64, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsc = DAWN_BUFFER(rcos, Fext * 64);
+    const __amdgpu_buffer_rsrc_t rss = DAWN_BUFFER(rsin, Fext * 64);
     typedef int i32x2_t __attribute__((ext_vector_type(2)));
     auto rot_load = [&](const __amdgpu_buffer_rsrc_t r, int row, int mb) {
         return __builtin_bit_cast(float2, (i32x2_t)__builtin_amdgcn_raw_buffer_load_b64(r, (unsigned)(row * 64 + 8 * g), 32 * mb, 0));
@@ -251,7 +216,7 @@ __global__ __launch_bounds__(NT) void temporal_layer16_kernel(
     for (int k = 0; k < NTILE; ++k)
 #pragma unroll
         for (int cm = 0; cm < 4; ++cm) outT[k][cm] = zero4();
-    bf16x8t qp[NTILE][3];
+    bf16x8 qp[NTILE][3];
 
     // REGIONS.  The loop body is a sequence of regions separated by sched_barrier(0) (nothing crosses): LOAD regions (LDS reads,
     // weight / table fetches) and COMPUTE regions (MFMAs + the vector work on their results), and every compute region ends with a
@@ -268,8 +233,8 @@ __global__ __launch_bounds__(NT) void temporal_layer16_kernel(
 #define REGION() __builtin_amdgcn_sched_barrier(0)
     const bool isV = (kvc & 2) != 0;
     const int kmb = kvc & 1;
-    bf16x8t wkv[2][3];          // the K / V group's fragments of the head (6 x 1 KB per wave)
-    bf16x8t wq[2][2][3];        // Wq fragments [feature half][k-step][plane]
+    bf16x8 wkv[2][3];          // the K / V group's fragments of the head (6 x 1 KB per wave)
+    bf16x8 wq[2][2][3];        // Wq fragments [feature half][k-step][plane]
     float2 qcs[NTILE][2], qsn[NTILE][2];   // rotary rows of the own query tiles
     float bandv;                // this thread's entry of the head's bias table
     // (unconditional -- a wave without a group / tile fetches fragments it does not use: a conditional definition would keep the
@@ -283,13 +248,13 @@ __global__ __launch_bounds__(NT) void temporal_layer16_kernel(
             for (int s = 0; s < 2; ++s)
 #pragma unroll
                 for (int pl = 0; pl < 3; ++pl)
-                    wq[mb][s][pl] = __builtin_bit_cast(bf16x8t, __builtin_amdgcn_raw_buffer_load_b128(
+                    wq[mb][s][pl] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(
                                                                     rsw, wlane, ((12 * s + 2 * pl) * 768 + 32 * hh + 16 * mb) * 16, 0));
 #pragma unroll
         for (int s = 0; s < 2; ++s)
 #pragma unroll
             for (int pl = 0; pl < 3; ++pl)
-                wkv[s][pl] = __builtin_bit_cast(bf16x8t, __builtin_amdgcn_raw_buffer_load_b128(rsw, lo, ((12 * s + 2 * pl) * 768 + col0) * 16, 0));
+                wkv[s][pl] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rsw, lo, ((12 * s + 2 * pl) * 768 + col0) * 16, 0));
 #pragma unroll
         for (int k = 0; k < NTILE; ++k)
 #pragma unroll
@@ -304,7 +269,7 @@ __global__ __launch_bounds__(NT) void temporal_layer16_kernel(
     const int bidx = (tid & 127) + (tid >> 7) - 15;
     const bool bok = bidx >= 0 && bidx <= 2 * win;
     // X fragments + rotary row of a 16-row tile for the K / V projection (tiles past the group's end are fetched and dropped)
-    auto kv_fetch = [&](int rt, bf16x8t (&xf)[2][3], float2& cs, float2& sn) {
+    auto kv_fetch = [&](int rt, bf16x8 (&xf)[2][3], float2& cs, float2& sn) {
         const int row = 16 * min(rt, NB - 1) + n;
         const int rc_ = min(row, Fext - 1);
         cs = rot_load(rsc, rc_, kmb);
@@ -314,11 +279,11 @@ __global__ __launch_bounds__(NT) void temporal_layer16_kernel(
         for (int s = 0; s < 2; ++s)
 #pragma unroll
             for (int pl = 0; pl < 3; ++pl)
-                xf[s][pl] = *reinterpret_cast<const bf16x8t*>(xr + (size_t)((pl * 8 + 4 * s) * FA) * 16);
+                xf[s][pl] = *reinterpret_cast<const bf16x8*>(xr + (size_t)((pl * 8 + 4 * s) * FA) * 16);
     };
     // NR (1 or 2) 16-row tiles of the group per compute region: 12 MFMAs each, one chain per (tile, k-step); rotary (K), split, planes
     // into LDS
-    auto kv_tiles = [&](auto nr_, int rt, const bf16x8t (&xf)[2][2][3], const float2 (&cs)[2], const float2 (&sn)[2]) {
+    auto kv_tiles = [&](auto nr_, int rt, const bf16x8 (&xf)[2][2][3], const float2 (&cs)[2], const float2 (&sn)[2]) {
         constexpr int NR = decltype(nr_)::value;
         f32x4 d2[NR][2];
 #pragma unroll
@@ -329,14 +294,14 @@ __global__ __launch_bounds__(NT) void temporal_layer16_kernel(
 #pragma unroll
                 for (int s = 0; s < 2; ++s)
 #pragma unroll
-                    for (int t = 0; t < NR; ++t) d2[t][s] = mfma16(wkv[s][PA6[u]], xf[t][s][PB6[u]], d2[t][s]);      // K^T = Wk^T . X^T
+                    for (int t = 0; t < NR; ++t) d2[t][s] = mfma16(wkv[s][DAWN_SPLIT6_A[u]], xf[t][s][DAWN_SPLIT6_B[u]], d2[t][s]);      // K^T = Wk^T . X^T
 #pragma unroll
             for (int t = 0; t < NR; ++t) {
                 const f32x4 d = d2[t][0] + d2[t][1];
                 const f32x4 kr = {d[0] * cs[t].x - d[1] * sn[t].x, d[1] * cs[t].x + d[0] * sn[t].x, d[2] * cs[t].y - d[3] * sn[t].y,
                                   d[3] * cs[t].y + d[2] * sn[t].y};
                 uint2 p1, p2, p3;
-                split3_quad(kr, p1, p2, p3);
+                dawn_split3_trunc_quad(kr, p1, p2, p3);
                 unsigned char* dst = Kp + ((size_t)g * FA + 16 * (rt + t) + n) * 16 + kmb * 8;
                 *reinterpret_cast<uint2*>(dst) = p1;
                 *reinterpret_cast<uint2*>(dst + (size_t)4 * FA * 16) = p2;
@@ -348,11 +313,11 @@ __global__ __launch_bounds__(NT) void temporal_layer16_kernel(
 #pragma unroll
                 for (int s = 0; s < 2; ++s)
 #pragma unroll
-                    for (int t = 0; t < NR; ++t) d2[t][s] = mfma16(xf[t][s][PB6[u]], wkv[s][PA6[u]], d2[t][s]);      // V = X . Wv
+                    for (int t = 0; t < NR; ++t) d2[t][s] = mfma16(xf[t][s][DAWN_SPLIT6_B[u]], wkv[s][DAWN_SPLIT6_A[u]], d2[t][s]);      // V = X . Wv
 #pragma unroll
             for (int t = 0; t < NR; ++t) {
                 uint2 p1, p2, p3;
-                split3_quad(d2[t][0] + d2[t][1], p1, p2, p3);
+                dawn_split3_trunc_quad(d2[t][0] + d2[t][1], p1, p2, p3);
                 unsigned char* dst = Vp + ((size_t)(kmb * 64 + lane) * NB + rt + t) * 8;
                 *reinterpret_cast<uint2*>(dst) = p1;
                 *reinterpret_cast<uint2*>(dst + (size_t)NB * 2 * 512) = p2;
@@ -360,7 +325,7 @@ __global__ __launch_bounds__(NT) void temporal_layer16_kernel(
             }
         }
     };
-    auto kv_step = [&](int rt, const bf16x8t (&xf)[2][2][3], const float2 (&cs)[2], const float2 (&sn)[2]) {
+    auto kv_step = [&](int rt, const bf16x8 (&xf)[2][2][3], const float2 (&cs)[2], const float2 (&sn)[2]) {
         if (rt + 1 < kt1) kv_tiles(std::integral_constant<int, 2>{}, rt, xf, cs, sn);
         else kv_tiles(std::integral_constant<int, 1>{}, rt, xf, cs, sn);
     };
@@ -382,7 +347,7 @@ __global__ __launch_bounds__(NT) void temporal_layer16_kernel(
         // reads float4 at copy[(15 - n) & 3][((15 - n) & ~3) + 4 g + 16 b] = entries 15 - n + 4 g + 16 b + r), the X fragments of the
         // own query rows and of the group's first row tile
         band4[(tid >> 7) * BLD + (tid & 127)] = bok ? bandv * LOG2E : NEG;
-        bf16x8t xfq[NTILE][2][3];
+        bf16x8 xfq[NTILE][2][3];
 #pragma unroll
         for (int k = 0; k < NTILE; ++k) {
             const unsigned char* xr = Xp + ((size_t)g * FA + iqc[k]) * 16;
@@ -390,9 +355,9 @@ __global__ __launch_bounds__(NT) void temporal_layer16_kernel(
             for (int s = 0; s < 2; ++s)
 #pragma unroll
                 for (int pl = 0; pl < 3; ++pl)
-                    xfq[k][s][pl] = *reinterpret_cast<const bf16x8t*>(xr + (size_t)((pl * 8 + 4 * s) * FA) * 16);
+                    xfq[k][s][pl] = *reinterpret_cast<const bf16x8*>(xr + (size_t)((pl * 8 + 4 * s) * FA) * 16);
         }
-        bf16x8t xfa[2][2][3], xfb[2][2][3];                          // two pairs of row tiles: one being multiplied, one in flight
+        bf16x8 xfa[2][2][3], xfb[2][2][3];                          // two pairs of row tiles: one being multiplied, one in flight
         float2 csa[2], sna[2], csb[2], snb[2];
         if constexpr (NTILE == 1) {                                  // (two query tiles: 56 registers too many beside 2 x 24 X fragments)
             kv_fetch(kt0, xfa[0], csa[0], sna[0]);
@@ -412,7 +377,7 @@ __global__ __launch_bounds__(NT) void temporal_layer16_kernel(
 #pragma unroll
                     for (int k = 0; k < NTILE; ++k)
 #pragma unroll
-                        for (int mb = 0; mb < 2; ++mb) d[k][mb] = mfma16(wq[mb][s][PA6[u]], xfq[k][s][PB6[u]], d[k][mb]);
+                        for (int mb = 0; mb < 2; ++mb) d[k][mb] = mfma16(wq[mb][s][DAWN_SPLIT6_A[u]], xfq[k][s][DAWN_SPLIT6_B[u]], d[k][mb]);
 #pragma unroll
             for (int k = 0; k < NTILE; ++k) {
                 float qr[8];
@@ -457,13 +422,13 @@ __global__ __launch_bounds__(NT) void temporal_layer16_kernel(
         if (h < 2) TSTAMP();   // K / V group done
         // to_out fragments of the head [16-channel block][plane]: LOAD region here with one query tile per wave, behind the first tile's
         // S stage with two (into the registers the K fragments leave: 48 registers less across that stage)
-        bf16x8t wo[4][3];
+        bf16x8 wo[4][3];
         auto request_wo = [&]() {
 #pragma unroll
             for (int cm = 0; cm < 4; ++cm)
 #pragma unroll
                 for (int pl = 0; pl < 3; ++pl)
-                    wo[cm][pl] = __builtin_bit_cast(bf16x8t, __builtin_amdgcn_raw_buffer_load_b128(rso, wolane, ((12 * h + 2 * pl) * C + 16 * cm) * 16, 0));
+                    wo[cm][pl] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rso, wolane, ((12 * h + 2 * pl) * C + 16 * cm) * 16, 0));
         };
         REGION();
         if constexpr (NTILE == 1) request_wo();
@@ -493,21 +458,21 @@ __global__ __launch_bounds__(NT) void temporal_layer16_kernel(
                     constexpr int NP = (NV + 1) / 2;
                     // LOAD: K fragments; the S^T accumulators START from the bias (NEG + anything = NEG keeps the window mask)
                     f32x4 st[NV];
-                    bf16x8t kf[NV][3];
+                    bf16x8 kf[NV][3];
                     REGION();
 #pragma unroll
                     for (int j = 0; j < NV; ++j) {
                         st[j] = *reinterpret_cast<const f32x4*>(bb + 16 * j);
 #pragma unroll
                         for (int pl = 0; pl < 3; ++pl)
-                            kf[j][pl] = *reinterpret_cast<const bf16x8t*>(kbase + (size_t)j * 256 + (size_t)pl * 4 * FA * 16);
+                            kf[j][pl] = *reinterpret_cast<const bf16x8*>(kbase + (size_t)j * 256 + (size_t)pl * 4 * FA * 16);
                     }
                     REGION();
                     // COMPUTE: S^T slot = bias + K_b . Q^T (NV chains), mask of the slots past the buffer, row maximum
 #pragma unroll
                     for (int u = 0; u < 6; ++u)
 #pragma unroll
-                        for (int j = 0; j < NV; ++j) st[j] = mfma16(kf[j][PA6[u]], qp[k][PB6[u]], st[j]);
+                        for (int j = 0; j < NV; ++j) st[j] = mfma16(kf[j][DAWN_SPLIT6_A[u]], qp[k][DAWN_SPLIT6_B[u]], st[j]);
 #pragma unroll
                     for (int r = 0; r < 4; ++r) st[NV - 1][r] = r < klast ? st[NV - 1][r] : NEG;
                     float m = NEG;
@@ -522,8 +487,8 @@ __global__ __launch_bounds__(NT) void temporal_layer16_kernel(
                     // LOAD: V^T fragments of the block pairs (they land under the softmax) [+ the to_out fragments].  Waves with two query
                     // tiles hold two pairs at a time (24 registers less where the stage peaks): the third follows in a region of its own
                     constexpr int NP1 = (NTILE == 2 && NP == 3) ? 2 : NP;
-                    bf16x8t vf[NP1][2][3];
-                    auto v_fetch = [&](int kk, bf16x8t (&v)[2][3]) {
+                    bf16x8 vf[NP1][2][3];
+                    auto v_fetch = [&](int kk, bf16x8 (&v)[2][3]) {
                         const int jb = 2 * kk + 1 < NV ? 2 * kk + 1 : 2 * kk;      // an odd count: the pair's second half re-reads the first (P = 0)
 #pragma unroll
                         for (int mb = 0; mb < 2; ++mb)
@@ -541,7 +506,7 @@ __global__ __launch_bounds__(NT) void temporal_layer16_kernel(
                     m = rows4_max(m);
                     REGION();
                     // vector work: P = 2^(S - m), row sums (their cross-lane part is needed at the very end only), split of P
-                    bf16x8t pp[NP][3];
+                    bf16x8 pp[NP][3];
 #pragma unroll
                     for (int j = 0; j < NV; ++j)
 #pragma unroll
@@ -566,19 +531,19 @@ __global__ __launch_bounds__(NT) void temporal_layer16_kernel(
 #pragma unroll
                         for (int u = 0; u < 6; ++u)
 #pragma unroll
-                            for (int mb = 0; mb < 2; ++mb) o[kk & 1][mb] = mfma16(vf[kk][mb][PA6[u]], pp[kk][PB6[u]], o[kk & 1][mb]);
+                            for (int mb = 0; mb < 2; ++mb) o[kk & 1][mb] = mfma16(vf[kk][mb][DAWN_SPLIT6_A[u]], pp[kk][DAWN_SPLIT6_B[u]], o[kk & 1][mb]);
                     if constexpr (NP1 < NP) {
                         // closing read of the first two pairs' chains, then the third pair: LOAD, COMPUTE
                         float cl = (o[0][0][0] + o[0][1][0]) + (o[1][0][0] + o[1][1][0]);
                         asm volatile("" :: "v"(cl));
                         REGION();
-                        bf16x8t v2[2][3];
+                        bf16x8 v2[2][3];
                         v_fetch(2, v2);
                         REGION();
 #pragma unroll
                         for (int u = 0; u < 6; ++u)
 #pragma unroll
-                            for (int mb = 0; mb < 2; ++mb) o[0][mb] = mfma16(v2[mb][PA6[u]], pp[2][PB6[u]], o[0][mb]);
+                            for (int mb = 0; mb < 2; ++mb) o[0][mb] = mfma16(v2[mb][DAWN_SPLIT6_A[u]], pp[2][DAWN_SPLIT6_B[u]], o[0][mb]);
                     }
 #ifdef DAWN_TL16_DUMP
                     if (dawn_tl16_dump) {
@@ -609,12 +574,12 @@ __global__ __launch_bounds__(NT) void temporal_layer16_kernel(
                     float orr[8];
 #pragma unroll
                     for (int r = 0; r < 4; ++r) { orr[r] = (o[0][0][r] + o[1][0][r]) * inv; orr[4 + r] = (o[0][1][r] + o[1][1][r]) * inv; }
-                    bf16x8t op[3];
+                    bf16x8 op[3];
                     dawn_split3_oct(orr, op[0], op[1], op[2]);
 #pragma unroll
                     for (int u = 0; u < 6; ++u)
 #pragma unroll
-                        for (int cm = 0; cm < 4; ++cm) outT[k][cm] = mfma16(wo[cm][PA6[u]], op[PB6[u]], outT[k][cm]);
+                        for (int cm = 0; cm < 4; ++cm) outT[k][cm] = mfma16(wo[cm][DAWN_SPLIT6_A[u]], op[DAWN_SPLIT6_B[u]], outT[k][cm]);
                     float sink = (outT[k][0][0] + outT[k][1][0]) + (outT[k][2][0] + outT[k][3][0]);
                     asm volatile("" :: "v"(sink));
                 }
@@ -655,7 +620,6 @@ __global__ __launch_bounds__(NT) void temporal_layer16_kernel(
 #endif
 #endif
 }
-
 
 // =====================================================================================================================================
 // ONE TILE PER WAVE (round 6, second form): 13 waves (832 threads: 4 / 3 / 3 / 3 per SIMD, 128 registers each).  In the 8-wave kernel above
@@ -708,19 +672,12 @@ __global__ __launch_bounds__(NT13) void temporal_layer13_kernel(
             ss = row16_sum(ss);
             const float rs = 1.0f / sqrtf(ss * (1.0f / C) + eps);
             const f32x4 o = dl * rs;
-            typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-            bf16x4 h1, h2, h3;
-            f32x4 r;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { h1[e] = (__bf16)o[e]; r[e] = o[e] - (float)h1[e]; }
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { h2[e] = (__bf16)r[e]; r[e] = r[e] - (float)h2[e]; }
-#pragma unroll
-            for (int e = 0; e < 4; ++e) h3[e] = (__bf16)r[e];
+            uint2 p1, p2, p3;
+            dawn_split3_rne_quad(o, p1, p2, p3);
             unsigned char* dst = Xp + ((size_t)(sub >> 1) * FA + j) * 16 + (sub & 1) * 8;
-            *reinterpret_cast<uint2*>(dst) = __builtin_bit_cast(uint2, h1);
-            *reinterpret_cast<uint2*>(dst + (size_t)8 * FA * 16) = __builtin_bit_cast(uint2, h2);
-            *reinterpret_cast<uint2*>(dst + (size_t)16 * FA * 16) = __builtin_bit_cast(uint2, h3);
+            *reinterpret_cast<uint2*>(dst) = p1;
+            *reinterpret_cast<uint2*>(dst + (size_t)8 * FA * 16) = p2;
+            *reinterpret_cast<uint2*>(dst + (size_t)16 * FA * 16) = p3;
         }
     }
 
@@ -734,23 +691,23 @@ __global__ __launch_bounds__(NT13) void temporal_layer13_kernel(
     const bool isV = (kvc & 2) != 0;
     const int kmb = kvc & 1;
 
-    const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc((void*)wqkv_s, 0, 4 * 3 * 2 * 768 * 16, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsw = DAWN_BUFFER(wqkv_s, 4 * 3 * 2 * 768 * 16);
     const unsigned wlane = (unsigned)(((6 * (g >> 1) + (g & 1)) * 768 + n) * 16);
     const unsigned wlane_v = (unsigned)(((6 * (g >> 1) + (g & 1)) * 768 + 16 * (n >> 3) + (n & 7)) * 16);
-    const __amdgpu_buffer_rsrc_t rso = __builtin_amdgcn_make_buffer_rsrc((void*)wout_sp, 0, 16 * 3 * 2 * C * 16, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rso = DAWN_BUFFER(wout_sp, 16 * 3 * 2 * C * 16);
     const unsigned wolane = (unsigned)(((6 * (g >> 1) + (g & 1)) * C + n) * 16);
-    const __amdgpu_buffer_rsrc_t rsc = __builtin_amdgcn_make_buffer_rsrc((void*)rcos, 0, Fext * 64, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rss = __builtin_amdgcn_make_buffer_rsrc((void*)rsin, 0, Fext * 64, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsc = DAWN_BUFFER(rcos, Fext * 64);
+    const __amdgpu_buffer_rsrc_t rss = DAWN_BUFFER(rsin, Fext * 64);
     typedef int i32x2_t __attribute__((ext_vector_type(2)));
     auto rot_load = [&](const __amdgpu_buffer_rsrc_t r, int row, int mb) {
         return __builtin_bit_cast(float2, (i32x2_t)__builtin_amdgcn_raw_buffer_load_b64(r, (unsigned)(row * 64 + 8 * g), 32 * mb, 0));
     };
-    auto wq_load = [&](int hh, int mb, bf16x8t (&w)[2][3]) {
+    auto wq_load = [&](int hh, int mb, bf16x8 (&w)[2][3]) {
 #pragma unroll
         for (int s = 0; s < 2; ++s)
 #pragma unroll
             for (int pl = 0; pl < 3; ++pl)
-                w[s][pl] = __builtin_bit_cast(bf16x8t, __builtin_amdgcn_raw_buffer_load_b128(rsw, wlane, ((12 * s + 2 * pl) * 768 + 32 * hh + 16 * mb) * 16, 0));
+                w[s][pl] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rsw, wlane, ((12 * s + 2 * pl) * 768 + 32 * hh + 16 * mb) * 16, 0));
     };
 
     const int i0 = q0 - delta + 16 * qt;
@@ -759,11 +716,11 @@ __global__ __launch_bounds__(NT13) void temporal_layer13_kernel(
     f32x4 outT[4];
 #pragma unroll
     for (int cm = 0; cm < 4; ++cm) outT[cm] = zero4();
-    bf16x8t qp[3];
+    bf16x8 qp[3];
 
     const int bidx = (tid & 127) + (tid >> 7) - 15;
     const bool bok = bidx >= 0 && bidx <= 2 * win;
-    bf16x8t wq0[2][3];          // Wq fragments of feature half 0, requested across the closing barrier
+    bf16x8 wq0[2][3];          // Wq fragments of feature half 0, requested across the closing barrier
     float2 qcs[2], qsn[2];
     float bandv;
     auto request_next = [&](int hh) {
@@ -783,30 +740,30 @@ __global__ __launch_bounds__(NT13) void temporal_layer13_kernel(
         // ---- phase A
         if (tid < 512) band4[(tid >> 7) * BLD + (tid & 127)] = bok ? bandv * LOG2E : NEG;
         if (has_q) {
-            bf16x8t xfq[2][3];
+            bf16x8 xfq[2][3];
             const unsigned char* xr = Xp + ((size_t)g * FA + iqc) * 16;
 #pragma unroll
             for (int s = 0; s < 2; ++s)
 #pragma unroll
                 for (int pl = 0; pl < 3; ++pl)
-                    xfq[s][pl] = *reinterpret_cast<const bf16x8t*>(xr + (size_t)((pl * 8 + 4 * s) * FA) * 16);
+                    xfq[s][pl] = *reinterpret_cast<const bf16x8*>(xr + (size_t)((pl * 8 + 4 * s) * FA) * 16);
             REGION();
             f32x4 d2[2] = {zero4(), zero4()};
 #pragma unroll
             for (int u = 0; u < 6; ++u)
 #pragma unroll
-                for (int s = 0; s < 2; ++s) d2[s] = mfma16(wq0[s][PA6[u]], xfq[s][PB6[u]], d2[s]);
+                for (int s = 0; s < 2; ++s) d2[s] = mfma16(wq0[s][DAWN_SPLIT6_A[u]], xfq[s][DAWN_SPLIT6_B[u]], d2[s]);
             const f32x4 d0 = d2[0] + d2[1];
             asm volatile("" :: "v"(d0[0]), "v"(d0[1]), "v"(d0[2]), "v"(d0[3]));
             REGION();
-            bf16x8t wq1[2][3];
+            bf16x8 wq1[2][3];
             wq_load(h, 1, wq1);
             REGION();
             f32x4 e2[2] = {zero4(), zero4()};
 #pragma unroll
             for (int u = 0; u < 6; ++u)
 #pragma unroll
-                for (int s = 0; s < 2; ++s) e2[s] = mfma16(wq1[s][PA6[u]], xfq[s][PB6[u]], e2[s]);
+                for (int s = 0; s < 2; ++s) e2[s] = mfma16(wq1[s][DAWN_SPLIT6_A[u]], xfq[s][DAWN_SPLIT6_B[u]], e2[s]);
             const f32x4 d1 = e2[0] + e2[1];
             const float sl = 0.17677669529663687f * LOG2E;
             float qr[8];
@@ -825,7 +782,7 @@ __global__ __launch_bounds__(NT13) void temporal_layer13_kernel(
         }
         REGION();
         if (kvc < 4) {
-            bf16x8t wkv[2][3];
+            bf16x8 wkv[2][3];
             {
                 const unsigned lo = isV ? wlane_v : wlane;
                 const int col0 = isV ? (512 + 32 * h + 8 * kmb) : (256 + 32 * h + 16 * kmb);
@@ -833,7 +790,7 @@ __global__ __launch_bounds__(NT13) void temporal_layer13_kernel(
                 for (int s = 0; s < 2; ++s)
 #pragma unroll
                     for (int pl = 0; pl < 3; ++pl)
-                        wkv[s][pl] = __builtin_bit_cast(bf16x8t, __builtin_amdgcn_raw_buffer_load_b128(rsw, lo, ((12 * s + 2 * pl) * 768 + col0) * 16, 0));
+                        wkv[s][pl] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rsw, lo, ((12 * s + 2 * pl) * 768 + col0) * 16, 0));
             }
             for (int rt = kt0; rt < kt1; ++rt) {
                 REGION();
@@ -841,12 +798,12 @@ __global__ __launch_bounds__(NT13) void temporal_layer13_kernel(
                 const int rc_ = min(row, Fext - 1);
                 const float2 cs = rot_load(rsc, rc_, kmb), sn = rot_load(rss, rc_, kmb);
                 const unsigned char* xr = Xp + ((size_t)g * FA + row) * 16;
-                bf16x8t xf[2][3];
+                bf16x8 xf[2][3];
 #pragma unroll
                 for (int s = 0; s < 2; ++s)
 #pragma unroll
                     for (int pl = 0; pl < 3; ++pl)
-                        xf[s][pl] = *reinterpret_cast<const bf16x8t*>(xr + (size_t)((pl * 8 + 4 * s) * FA) * 16);
+                        xf[s][pl] = *reinterpret_cast<const bf16x8*>(xr + (size_t)((pl * 8 + 4 * s) * FA) * 16);
                 REGION();
                 f32x4 d2[2] = {zero4(), zero4()};
                 uint2 p1, p2, p3;
@@ -854,10 +811,10 @@ __global__ __launch_bounds__(NT13) void temporal_layer13_kernel(
 #pragma unroll
                     for (int u = 0; u < 6; ++u)
 #pragma unroll
-                        for (int s = 0; s < 2; ++s) d2[s] = mfma16(wkv[s][PA6[u]], xf[s][PB6[u]], d2[s]);
+                        for (int s = 0; s < 2; ++s) d2[s] = mfma16(wkv[s][DAWN_SPLIT6_A[u]], xf[s][DAWN_SPLIT6_B[u]], d2[s]);
                     const f32x4 d = d2[0] + d2[1];
                     const f32x4 kr = {d[0] * cs.x - d[1] * sn.x, d[1] * cs.x + d[0] * sn.x, d[2] * cs.y - d[3] * sn.y, d[3] * cs.y + d[2] * sn.y};
-                    split3_quad(kr, p1, p2, p3);
+                    dawn_split3_trunc_quad(kr, p1, p2, p3);
                     unsigned char* dst = Kp + ((size_t)g * FA + row) * 16 + kmb * 8;
                     *reinterpret_cast<uint2*>(dst) = p1;
                     *reinterpret_cast<uint2*>(dst + (size_t)4 * FA * 16) = p2;
@@ -866,8 +823,8 @@ __global__ __launch_bounds__(NT13) void temporal_layer13_kernel(
 #pragma unroll
                     for (int u = 0; u < 6; ++u)
 #pragma unroll
-                        for (int s = 0; s < 2; ++s) d2[s] = mfma16(xf[s][PB6[u]], wkv[s][PA6[u]], d2[s]);
-                    split3_quad(d2[0] + d2[1], p1, p2, p3);
+                        for (int s = 0; s < 2; ++s) d2[s] = mfma16(xf[s][DAWN_SPLIT6_B[u]], wkv[s][DAWN_SPLIT6_A[u]], d2[s]);
+                    dawn_split3_trunc_quad(d2[0] + d2[1], p1, p2, p3);
                     unsigned char* dst = Vp + ((size_t)(kmb * 64 + lane) * NB + rt) * 8;
                     *reinterpret_cast<uint2*>(dst) = p1;
                     *reinterpret_cast<uint2*>(dst + (size_t)NB * 2 * 512) = p2;
@@ -897,19 +854,19 @@ __global__ __launch_bounds__(NT13) void temporal_layer13_kernel(
                 f32x4 st[NV];
                 REGION();
                 {
-                    bf16x8t kf[H1][3];
+                    bf16x8 kf[H1][3];
 #pragma unroll
                     for (int j = 0; j < NV; ++j) st[j] = *reinterpret_cast<const f32x4*>(bb + 16 * j);
 #pragma unroll
                     for (int j = 0; j < H1; ++j)
 #pragma unroll
                         for (int pl = 0; pl < 3; ++pl)
-                            kf[j][pl] = *reinterpret_cast<const bf16x8t*>(kbase + (size_t)j * 256 + (size_t)pl * 4 * FA * 16);
+                            kf[j][pl] = *reinterpret_cast<const bf16x8*>(kbase + (size_t)j * 256 + (size_t)pl * 4 * FA * 16);
                     REGION();
 #pragma unroll
                     for (int u = 0; u < 6; ++u)
 #pragma unroll
-                        for (int j = 0; j < H1; ++j) st[j] = mfma16(kf[j][PA6[u]], qp[PB6[u]], st[j]);
+                        for (int j = 0; j < H1; ++j) st[j] = mfma16(kf[j][DAWN_SPLIT6_A[u]], qp[DAWN_SPLIT6_B[u]], st[j]);
                 }
                 float m = NEG;
                 if constexpr (H1 == 3) mfma_settle(st[0], st[1], st[2]);
@@ -921,17 +878,17 @@ __global__ __launch_bounds__(NT13) void temporal_layer13_kernel(
                 asm volatile("" :: "v"(m));
                 REGION();
                 if constexpr (NV > H1) {
-                    bf16x8t kf[NV - H1][3];
+                    bf16x8 kf[NV - H1][3];
 #pragma unroll
                     for (int j = H1; j < NV; ++j)
 #pragma unroll
                         for (int pl = 0; pl < 3; ++pl)
-                            kf[j - H1][pl] = *reinterpret_cast<const bf16x8t*>(kbase + (size_t)j * 256 + (size_t)pl * 4 * FA * 16);
+                            kf[j - H1][pl] = *reinterpret_cast<const bf16x8*>(kbase + (size_t)j * 256 + (size_t)pl * 4 * FA * 16);
                     REGION();
 #pragma unroll
                     for (int u = 0; u < 6; ++u)
 #pragma unroll
-                        for (int j = H1; j < NV; ++j) st[j] = mfma16(kf[j - H1][PA6[u]], qp[PB6[u]], st[j]);
+                        for (int j = H1; j < NV; ++j) st[j] = mfma16(kf[j - H1][DAWN_SPLIT6_A[u]], qp[DAWN_SPLIT6_B[u]], st[j]);
                 }
                 if constexpr (NV - H1 == 3) mfma_settle(st[H1], st[H1 + 1], st[NV - 1]);
                 else if constexpr (NV - H1 == 2) mfma_settle(st[H1], st[NV - 1]);
@@ -943,7 +900,7 @@ __global__ __launch_bounds__(NT13) void temporal_layer13_kernel(
                     if (j >= H1 || j == NV - 1) m = max3_nc(max3_nc(m, st[j][0], st[j][1]), st[j][2], st[j][3]);
                 asm volatile("" :: "v"(m));
                 REGION();
-                auto v_fetch = [&](int kk, bf16x8t (&v)[2][3]) {
+                auto v_fetch = [&](int kk, bf16x8 (&v)[2][3]) {
                     const int jb = 2 * kk + 1 < NV ? 2 * kk + 1 : 2 * kk;
 #pragma unroll
                     for (int mb = 0; mb < 2; ++mb)
@@ -954,7 +911,7 @@ __global__ __launch_bounds__(NT13) void temporal_layer13_kernel(
                             v[mb][pl] = join8(lo, hi);
                         }
                 };
-                bf16x8t vf[2][3];
+                bf16x8 vf[2][3];
                 v_fetch(0, vf);
                 m = rows4_max(m);
                 REGION();
@@ -971,13 +928,13 @@ __global__ __launch_bounds__(NT13) void temporal_layer13_kernel(
                     float pr[8];
 #pragma unroll
                     for (int r = 0; r < 4; ++r) { pr[r] = st[2 * kk][r]; pr[4 + r] = 2 * kk + 1 < NV ? st[2 * kk + 1 < NV ? 2 * kk + 1 : 0][r] : 0.f; }
-                    bf16x8t pp[3];
+                    bf16x8 pp[3];
                     dawn_split3_oct(pr, pp[0], pp[1], pp[2]);
                     REGION();
 #pragma unroll
                     for (int u = 0; u < 6; ++u)
 #pragma unroll
-                        for (int mb = 0; mb < 2; ++mb) o[mb] = mfma16(vf[mb][PA6[u]], pp[PB6[u]], o[mb]);
+                        for (int mb = 0; mb < 2; ++mb) o[mb] = mfma16(vf[mb][DAWN_SPLIT6_A[u]], pp[DAWN_SPLIT6_B[u]], o[mb]);
                     float cl = o[0][0] + o[1][0];
                     asm volatile("" :: "v"(cl));
                     REGION();
@@ -997,22 +954,22 @@ __global__ __launch_bounds__(NT13) void temporal_layer13_kernel(
             float orr[8];
 #pragma unroll
             for (int r = 0; r < 4; ++r) { orr[r] = o[0][r] * inv; orr[4 + r] = o[1][r] * inv; }
-            bf16x8t op[3];
+            bf16x8 op[3];
             dawn_split3_oct(orr, op[0], op[1], op[2]);
 #pragma unroll
             for (int hf = 0; hf < 2; ++hf) {
                 REGION();
-                bf16x8t wo[2][3];
+                bf16x8 wo[2][3];
 #pragma unroll
                 for (int c2 = 0; c2 < 2; ++c2)
 #pragma unroll
                     for (int pl = 0; pl < 3; ++pl)
-                        wo[c2][pl] = __builtin_bit_cast(bf16x8t, __builtin_amdgcn_raw_buffer_load_b128(rso, wolane, ((12 * h + 2 * pl) * C + 16 * (2 * hf + c2)) * 16, 0));
+                        wo[c2][pl] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rso, wolane, ((12 * h + 2 * pl) * C + 16 * (2 * hf + c2)) * 16, 0));
                 REGION();
 #pragma unroll
                 for (int u = 0; u < 6; ++u)
 #pragma unroll
-                    for (int c2 = 0; c2 < 2; ++c2) outT[2 * hf + c2] = mfma16(wo[c2][PA6[u]], op[PB6[u]], outT[2 * hf + c2]);
+                    for (int c2 = 0; c2 < 2; ++c2) outT[2 * hf + c2] = mfma16(wo[c2][DAWN_SPLIT6_A[u]], op[DAWN_SPLIT6_B[u]], outT[2 * hf + c2]);
                 float sink = outT[2 * hf][0] + outT[2 * hf + 1][0];
                 asm volatile("" :: "v"(sink));
             }
@@ -1035,7 +992,6 @@ __global__ __launch_bounds__(NT13) void temporal_layer13_kernel(
     }
 #endif
 }
-
 
 // =====================================================================================================================================
 // THE ATTENTION CORE ALONE in the 13-wave form (round 6): dawn_temporal_attn for the levels whose to_qkv / to_out projections are separate
@@ -1097,7 +1053,7 @@ __global__ __launch_bounds__(NT13) void temporal_attn13_kernel(
     }
     // rows past the buffer (the tail of the last 16-row tile) are out of the descriptor's range: the hardware returns zeros -- the K / V of the
     // fused kernel's zero rows.  One vector offset per role; the row tile, the head and the feature half travel in the scalar offset.
-    const __amdgpu_buffer_rsrc_t rsq = __builtin_amdgcn_make_buffer_rsrc((void*)qkv, 0, Fext * HW * 3072, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsq = DAWN_BUFFER(qkv, Fext * HW * 3072);
     const unsigned rowb = PH ? 128u : (unsigned)HW * 3072u;               // bytes between consecutive buffer rows of one (pixel, head, operand)
     const unsigned pcol = PH ? 0u : (unsigned)(p * 3072);
     const unsigned vo_q = (unsigned)iqc * rowb + pcol + (unsigned)(16 * g);
@@ -1128,7 +1084,7 @@ __global__ __launch_bounds__(NT13) void temporal_attn13_kernel(
         bandv = band[max(0, min(bidx, 2 * win)) * HEADS + hh];
     };
     request_next(0);
-    bf16x8t qp[3];
+    bf16x8 qp[3];
     REGION();
     __syncthreads();
 
@@ -1154,7 +1110,7 @@ __global__ __launch_bounds__(NT13) void temporal_attn13_kernel(
         for (int i = 0; i < 4; ++i) {
             uint2 p1, p2, p3;
             if (uV[i]) {
-                split3_quad(kvraw[i], p1, p2, p3);
+                dawn_split3_trunc_quad(kvraw[i], p1, p2, p3);
                 if (uok[i]) {
                     unsigned char* dst = Vp + ((size_t)(ukmb[i] * 64 + lane) * NB + urt[i]) * 8;
                     *reinterpret_cast<uint2*>(dst) = p1;
@@ -1167,7 +1123,7 @@ __global__ __launch_bounds__(NT13) void temporal_attn13_kernel(
                 const float2 cs = *reinterpret_cast<const float2*>(rr), sn = *reinterpret_cast<const float2*>(rr + 16);
                 const f32x4 d = kvraw[i];
                 const f32x4 kr = {d[0] * cs.x - d[1] * sn.x, d[1] * cs.x + d[0] * sn.x, d[2] * cs.y - d[3] * sn.y, d[3] * cs.y + d[2] * sn.y};
-                split3_quad(kr, p1, p2, p3);
+                dawn_split3_trunc_quad(kr, p1, p2, p3);
                 if (uok[i]) {
                     unsigned char* dst = Kp + ((size_t)g * FA + row) * 16 + ukmb[i] * 8;
                     *reinterpret_cast<uint2*>(dst) = p1;
@@ -1201,19 +1157,19 @@ __global__ __launch_bounds__(NT13) void temporal_attn13_kernel(
                 f32x4 st[NV];
                 REGION();
                 {
-                    bf16x8t kf[H1][3];
+                    bf16x8 kf[H1][3];
 #pragma unroll
                     for (int j = 0; j < NV; ++j) st[j] = *reinterpret_cast<const f32x4*>(bb + 16 * j);
 #pragma unroll
                     for (int j = 0; j < H1; ++j)
 #pragma unroll
                         for (int pl = 0; pl < 3; ++pl)
-                            kf[j][pl] = *reinterpret_cast<const bf16x8t*>(kbase + (size_t)j * 256 + (size_t)pl * 4 * FA * 16);
+                            kf[j][pl] = *reinterpret_cast<const bf16x8*>(kbase + (size_t)j * 256 + (size_t)pl * 4 * FA * 16);
                     REGION();
 #pragma unroll
                     for (int u = 0; u < 6; ++u)
 #pragma unroll
-                        for (int j = 0; j < H1; ++j) st[j] = mfma16(kf[j][PA6[u]], qp[PB6[u]], st[j]);
+                        for (int j = 0; j < H1; ++j) st[j] = mfma16(kf[j][DAWN_SPLIT6_A[u]], qp[DAWN_SPLIT6_B[u]], st[j]);
                 }
                 float m = NEG;
                 if constexpr (H1 == 3) mfma_settle(st[0], st[1], st[2]);
@@ -1225,17 +1181,17 @@ __global__ __launch_bounds__(NT13) void temporal_attn13_kernel(
                 asm volatile("" :: "v"(m));
                 REGION();
                 if constexpr (NV > H1) {
-                    bf16x8t kf[NV - H1][3];
+                    bf16x8 kf[NV - H1][3];
 #pragma unroll
                     for (int j = H1; j < NV; ++j)
 #pragma unroll
                         for (int pl = 0; pl < 3; ++pl)
-                            kf[j - H1][pl] = *reinterpret_cast<const bf16x8t*>(kbase + (size_t)j * 256 + (size_t)pl * 4 * FA * 16);
+                            kf[j - H1][pl] = *reinterpret_cast<const bf16x8*>(kbase + (size_t)j * 256 + (size_t)pl * 4 * FA * 16);
                     REGION();
 #pragma unroll
                     for (int u = 0; u < 6; ++u)
 #pragma unroll
-                        for (int j = H1; j < NV; ++j) st[j] = mfma16(kf[j - H1][PA6[u]], qp[PB6[u]], st[j]);
+                        for (int j = H1; j < NV; ++j) st[j] = mfma16(kf[j - H1][DAWN_SPLIT6_A[u]], qp[DAWN_SPLIT6_B[u]], st[j]);
                 }
                 if constexpr (NV - H1 == 3) mfma_settle(st[H1], st[H1 + 1], st[NV - 1]);
                 else if constexpr (NV - H1 == 2) mfma_settle(st[H1], st[NV - 1]);
@@ -1247,7 +1203,7 @@ __global__ __launch_bounds__(NT13) void temporal_attn13_kernel(
                     if (j >= H1 || j == NV - 1) m = max3_nc(max3_nc(m, st[j][0], st[j][1]), st[j][2], st[j][3]);
                 asm volatile("" :: "v"(m));
                 REGION();
-                auto v_fetch = [&](int kk, bf16x8t (&v)[2][3]) {
+                auto v_fetch = [&](int kk, bf16x8 (&v)[2][3]) {
                     const int jb = 2 * kk + 1 < NV ? 2 * kk + 1 : 2 * kk;
 #pragma unroll
                     for (int mb = 0; mb < 2; ++mb)
@@ -1258,7 +1214,7 @@ __global__ __launch_bounds__(NT13) void temporal_attn13_kernel(
                             v[mb][pl] = join8(lo, hi);
                         }
                 };
-                bf16x8t vf[2][3];
+                bf16x8 vf[2][3];
                 v_fetch(0, vf);
                 m = rows4_max(m);
                 REGION();
@@ -1275,13 +1231,13 @@ __global__ __launch_bounds__(NT13) void temporal_attn13_kernel(
                     float pr[8];
 #pragma unroll
                     for (int r = 0; r < 4; ++r) { pr[r] = st[2 * kk][r]; pr[4 + r] = 2 * kk + 1 < NV ? st[2 * kk + 1 < NV ? 2 * kk + 1 : 0][r] : 0.f; }
-                    bf16x8t pp[3];
+                    bf16x8 pp[3];
                     dawn_split3_oct(pr, pp[0], pp[1], pp[2]);
                     REGION();
 #pragma unroll
                     for (int u = 0; u < 6; ++u)
 #pragma unroll
-                        for (int mb = 0; mb < 2; ++mb) o[mb] = mfma16(vf[mb][PA6[u]], pp[PB6[u]], o[mb]);
+                        for (int mb = 0; mb < 2; ++mb) o[mb] = mfma16(vf[mb][DAWN_SPLIT6_A[u]], pp[DAWN_SPLIT6_B[u]], o[mb]);
                     float cl = o[0][0] + o[1][0];
                     asm volatile("" :: "v"(cl));
                     REGION();

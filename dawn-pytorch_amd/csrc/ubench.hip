@@ -10,7 +10,6 @@
 #include "../../include/dawn_hip.h"
 
 namespace {
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 template <int MODE>
 __global__ __launch_bounds__(256, 2) void mfma_power_kernel(const u32x4* __restrict__ src, float* out, int iters) {

@@ -73,7 +73,8 @@ def gate_rejects(got, want64, base32, c=C_GATE, floor=FLOOR):
 
 # ---------------------------------------------------------------------------------------------- the plane defects
 def planes3(w):
-    """The exact split w = w1 + w2 + w3 of dawn_pytorch_amd.pack.pack_bf3, as float32 tensors."""
+    """The exact split w = w1 + w2 + w3 of dawn_pytorch_amd.pack.pack_bf3, as float32 tensors.
+    In the kernels: dawn_split3_rne_quad (csrc/dawn_common.h), round to nearest even."""
     w = w.float()
     w1 = w.to(torch.bfloat16).float()
     r1 = w - w1
@@ -134,7 +135,7 @@ def _hook(defect, name, t, split, axis):
 
 
 def attn_core64(qkv, Fext, HW, q0, Fq, win, rcos, rsin, band, defect=None):
-    """RefOps.temporal_attn in float64 with hooks on Q, K, V and P (all split by dawn_split3_oct / split3_quad: trunc_planes3)."""
+    """RefOps.temporal_attn in float64 with hooks on Q, K, V and P (all split by dawn_split3_oct / dawn_split3_trunc_quad: trunc_planes3)."""
     x = qkv.double().reshape(Fext, HW, 3, 8, 32)
     rcos, rsin, band = rcos.double(), rsin.double(), band.double()
     q = x[:, :, 0].permute(1, 2, 0, 3) * 32 ** -0.5          # (HW, 8, Fext, 32): axis 1 = head
@@ -180,8 +181,8 @@ def temporal_layer64(x, Fext, HW, q0, Fq, win, wqkv, wout, rcos, rsin, band, eps
     x = x.double()
     stats = ops.ln_rowstats(x, None, eps)
     if defect and "X" in defect:
-        # X: the LayerNorm'ed rows, split by ROUNDING (split3_quad_t's bf16 conversions: planes3, not dawn_split3_oct) --
-        # temporal_layer.hip:684, temporal_layer16.hip:200-208 / :711-719; stale = the third plane of the previous frame row
+        # X: the LayerNorm'ed rows, split by ROUNDING (dawn_split3_rne_quad's bf16 conversions: planes3, not dawn_split3_oct) --
+        # the LayerNorm prologues of temporal_layer.hip and temporal_layer16.hip; stale = the third plane of the previous frame row
         xn = ((x - stats[0][:, None]) * stats[1][:, None]).view(Fext, HW, 64)
         xn = _hook(defect, "X", xn, planes3, 0).view(Fext * HW, 64)
         qkv = ops.conv_gemm(xn, wqkv.double(), 768, F=Fext, Hi=1, Wi=HW)

@@ -125,3 +125,23 @@ def test_python_names_equal_header_values():
     assert set(header_constants("DAWN_POLICY_")[1]) == {"VARIANT", "STAGGER"} and set(header_constants("DAWN_TL_")[1]) == {"FORCE_WMODE"}
     opts, _ = header_constants("DAWN_OPT_")
     assert opts == {n[4:]: getattr(ctx, n) for n in dir(ctx) if n.startswith("OPT_")} and len(opts) == 7
+
+
+# (file, token) pairs allowed outside dawn_common.h: sites where sharing the definition would have changed device code.  Empty.
+SHARED_IDIOM_ALLOW = set()
+
+
+def test_shared_kernel_idioms_have_one_definition():
+    """The truncation mask, the cross-term orders, the buffer-descriptor builtin and the row-sum DPP control are spelled in
+    csrc/dawn_common.h and nowhere else in the kernel sources: a change to a split scheme reaches every kernel or none."""
+    csrc = os.path.join(ROOT, "dawn-pytorch_amd", "csrc")
+    files = sorted(os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".h", ".hip")))
+    files.append(os.path.join(ROOT, "tools", "ubench", "conv3x3_sk.hip"))
+    tokens = ("0xffff0000u", "{2, 0, 1, 1, 0, 0}", "{2, 2, 1, 2, 0, 1, 1, 0, 0}", "make_buffer_rsrc", "0x141")
+    assert len(files) > 30
+    found = set()
+    for path in files:
+        text = open(path).read()
+        found |= {(os.path.basename(path), t) for t in tokens if t in text}
+    assert {t for f, t in found if f == "dawn_common.h"} == set(tokens)
+    assert {(f, t) for f, t in found if f != "dawn_common.h"} == SHARED_IDIOM_ALLOW

@@ -81,7 +81,7 @@ def breakdown(region, epilogue=False):
     for l in region:
         if is_inst(l):
             c[classify(l, epilogue)] += 1
-    # the split's residual subtractions: one v_sub_f32 per v_and (8 and 8 per split3q) -- move them from "fp" to "split"
+    # the split's residual subtractions: one v_sub_f32 per v_and (8 and 8 per dawn_split3_trunc_quad) -- move them from "fp" to "split"
     n_and = sum(1 for l in region if is_inst(l) and l.strip().startswith("v_and_b32") and ("0xffff0000" in l or "-65536" in l))
     if not epilogue:
         mv = min(n_and, c["fp"])

@@ -28,9 +28,6 @@ extern "C" int dawn_conv_sk_check(const void* ws, void* stream);
 
 namespace {
 
-typedef dawn_bf16x8 bf16x8;
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-
 struct sk_args {
     int nC, nNt, ncx, G;         // 16-channel chunks per tile, 64*WN-column tiles, column tiles per row band, grid
     int U;                       // ntiles * nC work units
@@ -42,32 +39,10 @@ struct sk_args {
     unsigned long long* dbg;     // instrumented build only: [G][64] s_memtime stamps
 };
 
-// exact truncation split of 4 fp32 values into three bf16 quads (dawn_split3_oct's scheme, see dawn_common.h)
-__device__ __forceinline__ void split3q(const f32x4 v, uint2& p1, uint2& p2, uint2& p3) {
-    unsigned q1[2], q2[2], q3[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const float a = v[2 * i], b = v[2 * i + 1];
-        const unsigned a1 = __float_as_uint(a) & 0xffff0000u, b1 = __float_as_uint(b) & 0xffff0000u;
-        const float ra = a - __uint_as_float(a1), rb = b - __uint_as_float(b1);
-        const unsigned a2 = __float_as_uint(ra) & 0xffff0000u, b2 = __float_as_uint(rb) & 0xffff0000u;
-        const float sa = ra - __uint_as_float(a2), sb = rb - __uint_as_float(b2);
-        q1[i] = __builtin_amdgcn_perm(b1, a1, 0x07060302u);          // [hi16(a) | hi16(b) << 16]
-        q2[i] = __builtin_amdgcn_perm(b2, a2, 0x07060302u);
-        q3[i] = __builtin_amdgcn_perm(__float_as_uint(sb), __float_as_uint(sa), 0x07060302u);
-    }
-    p1 = make_uint2(q1[0], q1[1]);
-    p2 = make_uint2(q2[0], q2[1]);
-    p3 = make_uint2(q3[0], q3[1]);
-}
-
-// sum over the 64 lanes of a wave, result in lanes 48..63 (only): four DPP adds inside each row of 16 (quad xor 1, quad xor 2,
-// half-row mirror, row mirror), then row_bcast15 into rows 1 / 3 and row_bcast31 into rows 2 / 3 -- no LDS round trips
+// sum over the 64 lanes of a wave, result in lanes 48..63 (only): the sum inside each row of 16 (row16_sum), then row_bcast15
+// into rows 1 / 3 and row_bcast31 into rows 2 / 3 -- no LDS round trips
 __device__ __forceinline__ float wave_sum64_dpp(float v) {
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, true));
+    v = row16_sum(v);
     v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x142, 0xA, 0xF, false));
     v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x143, 0xC, 0xF, false));
     return v;
@@ -171,10 +146,8 @@ __global__ __launch_bounds__(256 * WN, 2 / WN) void conv3x3_sk_kernel(const dawn
         const int ph = rem / BN, n = rem - ph * BN;
         voffB[j] = q < NBI ? (unsigned)(((tp * nC * 6 + ph) * d.N + n) * 16) : OOB;
     }
-    const __amdgpu_buffer_rsrc_t rsw =
-        __builtin_amdgcn_make_buffer_rsrc((void*)d.w_bf3, 0, 9 * nC * 6 * d.N * 16, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsp = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(a.part + (size_t)v * (256 * BN)), 0, 256 * BN * 4, 0x00020000);      // this workgroup's partial slot
+    const __amdgpu_buffer_rsrc_t rsw = DAWN_BUFFER(d.w_bf3, 9 * nC * 6 * d.N * 16);
+    const __amdgpu_buffer_rsrc_t rsp = DAWN_BUFFER(a.part + (size_t)v * (256 * BN), 256 * BN * 4);      // this workgroup's partial slot
 
     // ---- tile bookkeeping (wave-uniform)
     auto tile_of = [&](int t) {
@@ -208,8 +181,8 @@ __global__ __launch_bounds__(256 * WN, 2 / WN) void conv3x3_sk_kernel(const dawn
         const int ext = (NF - 1) * H * W + (TR + 1) * W + PW;                  //  those quads are masked, never fetched)
         const float* b1 = d.in1 ? d.in1 : d.in0;
         const int l1 = d.in1 ? d.ld1 : d.ld0;
-        rs0 = __builtin_amdgcn_make_buffer_rsrc((void*)(d.in0 + pb * d.ld0), 0, ext * d.ld0 * 4, 0x00020000);
-        rs1 = __builtin_amdgcn_make_buffer_rsrc((void*)(b1 + pb * l1), 0, ext * l1 * 4, 0x00020000);
+        rs0 = DAWN_BUFFER(d.in0 + pb * d.ld0, ext * d.ld0 * 4);
+        rs1 = DAWN_BUFFER(b1 + pb * l1, ext * l1 * 4);
         Linv = mnone | (L.y0 == 0 ? mtop : 0u) | (L.y0 + TR >= H ? mbot : 0u) | (x0 == 0 ? mleft : 0u) |
                (x0 + WT >= W ? mright : 0u);
     };
@@ -235,7 +208,7 @@ __global__ __launch_bounds__(256 * WN, 2 / WN) void conv3x3_sk_kernel(const dawn
         for (int i = 0; i < MAXQ; ++i) {
             if (tid + NTHR * i < NQ) {
                 uint2 p1, p2, p3;
-                split3q(araw[i], p1, p2, p3);
+                dawn_split3_trunc_quad(araw[i], p1, p2, p3);
                 unsigned char* dst = planes + dbase + i * (NTHR * 4);
                 *reinterpret_cast<uint2*>(dst) = p1;
                 *reinterpret_cast<uint2*>(dst + 2 * HPS) = p2;
@@ -327,15 +300,13 @@ __global__ __launch_bounds__(256 * WN, 2 / WN) void conv3x3_sk_kernel(const dawn
                         for (int j = 0; j < TN; ++j)
                             fb[j][RB[g]] = *reinterpret_cast<const bf16x8*>(Bb + ((kx * 6 + RB[g] * 2) * BN * 16 + j * 512));
                     }
-                    constexpr int PA6[6] = {2, 0, 1, 1, 0, 0};
-                    constexpr int PB6[6] = {0, 2, 1, 0, 1, 0};
 #pragma unroll
                     for (int t = 0; t < 6; ++t)
 #pragma unroll
                         for (int i = 0; i < TM; ++i)
 #pragma unroll
                             for (int j = 0; j < TN; ++j)
-                                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[j][PB6[t]], fa[i][PA6[t]], acc[i][j], 0, 0, 0);
+                                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[j][DAWN_SPLIT6_B[t]], fa[i][DAWN_SPLIT6_A[t]], acc[i][j], 0, 0, 0);
                     __builtin_amdgcn_sched_group_barrier(0x100, 12, 0);           // the 12 fragment reads first,
                     __builtin_amdgcn_sched_group_barrier(0x008, 24, 0);           // then the 24 MFMAs
                 }
@@ -396,8 +367,7 @@ __global__ __launch_bounds__(256 * WN, 2 / WN) void conv3x3_sk_kernel(const dawn
                                 }
                             }
                             __builtin_amdgcn_s_barrier();
-                            const __amdgpu_buffer_rsrc_t rsq = __builtin_amdgcn_make_buffer_rsrc(
-                                (void*)(a.part + (size_t)w * (256 * BN)), 0, 256 * BN * 4, 0x00020000);
+                            const __amdgpu_buffer_rsrc_t rsq = DAWN_BUFFER(a.part + (size_t)w * (256 * BN), 256 * BN * 4);
 #pragma unroll
                             for (int i = 0; i < TM; ++i)
 #pragma unroll
