@@ -114,8 +114,9 @@ class HipOps:
     def _stream() -> int:
         return torch.cuda.current_stream().cuda_stream
 
-    def empty(self, *shape, like: Tensor, dtype=torch.float32) -> Tensor:
-        return torch.empty(*shape, device=like.device, dtype=dtype)
+    def empty(self, *shape, like: Optional[Tensor] = None, dtype=torch.float32, device=None) -> Tensor:
+        """Every result an op allocates comes from here (tests substitute a guarded allocation); `device=` where no tensor is there to be like."""
+        return torch.empty(*shape, device=like.device if like is not None else device, dtype=dtype)
 
     def fork_join(self, side, main):
         """Run `side()` on a second HIP stream concurrently with `main()` on the current stream; both see all
@@ -573,7 +574,7 @@ class HipOps:
     def ddim_x0(self, x: Tensor, eps: Tensor, recip: float, recipm1: float) -> Tuple[Tensor, Tensor]:
         n = x.numel()
         _need(x.is_contiguous() and eps.is_contiguous(), "ddim_x0: x.is_contiguous() and eps.is_contiguous()")
-        x0 = torch.empty_like(x)
+        x0 = self.empty(x.shape, like=x)
         # selection scratch [hist1 2048 | hist2 1024 | hist3 1024 | state 4 | hmin 4]: ONE buffer per (device, stream), reset by two
         # stream-ordered fills per step (no allocation, no torch fill kernels inside the DDIM loop)
         key = (x.device.index, self._stream())
@@ -609,7 +610,7 @@ class HipOps:
         n = x0.numel()
         ws = self._sel_ws.get((x0.device.index, s))
         if ws is None or hist1.data_ptr() != ws.data_ptr():          # histogram from elsewhere (tests): private scratch
-            ws = torch.empty(2048 + 1024 + 1024 + 8, device=x0.device, dtype=torch.int32)
+            ws = self.empty(2048 + 1024 + 1024 + 8, like=x0, dtype=torch.int32)
             check(self.L.dawn_select_ws_reset(_p(ws), s), "dawn_select_ws_reset")
         state = ws[4096:4100]
         if self.comm is not None:
@@ -625,15 +626,17 @@ class HipOps:
         check(self.L.dawn_select_hist(_p(x0), n, _p(state), 4, _p(hmin), s), "dawn_select_hist")
         if self.comm is not None:
             self.comm.all_reduce_min(hmin)
-        out = torch.empty(2, device=x0.device, dtype=torch.float32)
+        out = self.empty(2, like=x0)
         check(self.L.dawn_select_finalize(_p(state), _p(hmin), weight, _p(out), s), "dawn_select_finalize")
         return out
 
     def ddim_update(self, x0: Tensor, eps: Tensor, s: Tensor, noise: Optional[Tensor], sqrt_alpha_next: float,
                     c: float, sigma: float) -> Tensor:
-        x = torch.empty_like(x0)
-        _need(noise is None or noise.is_contiguous(), "ddim_update: noise is None or noise.is_contiguous()")
-        check(self.L.dawn_ddim_update(_p(x0), _p(eps), _p(s), _p(noise), sqrt_alpha_next, c, sigma, x0.numel(),
+        n = x0.numel()
+        _need(x0.is_contiguous() and eps.is_contiguous() and eps.numel() == n and (noise is None or (noise.is_contiguous() and noise.numel() == n)),
+              "ddim_update: contiguous x0 / eps / noise of one size")
+        x = self.empty(x0.shape, like=x0)
+        check(self.L.dawn_ddim_update(_p(x0), _p(eps), _p(s), _p(noise), sqrt_alpha_next, c, sigma, n,
                                       _p(x), self._stream()), "dawn_ddim_update")
         return x
 
@@ -644,7 +647,7 @@ class HipOps:
         _need(x0.is_contiguous() and x_t.is_contiguous() and x_t.numel() == n and (noise is None or (noise.is_contiguous() and noise.numel() == n)),
               "ancestral_update: contiguous x0 / x_t / noise of one size")
         if out is None:
-            out = torch.empty_like(x0)
+            out = self.empty(x0.shape, like=x0)
         _need(out.is_contiguous() and out.numel() == n, "ancestral_update: out contiguous of x0's size")
         check(self.L.dawn_ancestral_update(_p(x0), _p(x_t), _p(s), _p(noise), float(c1), float(c2), float(std), n, _p(out),
                                            self._stream()), "dawn_ancestral_update")
@@ -657,9 +660,11 @@ class HipOps:
               f"{name}: contiguous x / eps / noise of one size")
         self._require(x, eps, noise, out)
         if out is None:
-            out = torch.empty_like(x)
+            out = self.empty(x.shape, like=x)
         _need(out.is_contiguous() and out.numel() == n, f"{name}: out contiguous of x's size")
-        x0 = torch.empty_like(x) if want_x0 else None
+        x0 = None
+        if want_x0:
+            x0 = self.empty(x.shape, like=x)
         check(fn(_p(x), _p(eps), _p(noise), float(recip), float(recipm1), float(a), float(b), float(sg), int(bool(clamp)), n, _p(x0),
                  _p(out), self._stream()), name)
         return (out, x0) if want_x0 else out
@@ -682,8 +687,10 @@ class HipOps:
                                 std, clamp, want_x0, out)
 
     def cfg_combine(self, e_null: Tensor, e_cond: Tensor, scale: float) -> Tensor:
-        out = torch.empty_like(e_cond)
-        check(self.L.dawn_cfg_combine(_p(e_null), _p(e_cond), float(scale), e_cond.numel(), _p(out), self._stream()),
+        n = e_cond.numel()
+        _need(e_null.is_contiguous() and e_cond.is_contiguous() and e_null.numel() == n, "cfg_combine: contiguous e_null / e_cond of one size")
+        out = self.empty(e_cond.shape, like=e_cond)
+        check(self.L.dawn_cfg_combine(_p(e_null), _p(e_cond), float(scale), n, _p(out), self._stream()),
               "dawn_cfg_combine")
         return out
 
@@ -693,8 +700,8 @@ class HipOps:
         n = x.numel()
         _need(x.is_contiguous() and e_null.is_contiguous() and e_cond.is_contiguous() and e_null.numel() == n and e_cond.numel() == n,
               "cfg_x0: contiguous e_null / e_cond / x of one size")
-        eps = torch.empty_like(e_cond)
-        x0 = torch.empty_like(x)
+        eps = self.empty(e_cond.shape, like=e_cond)
+        x0 = self.empty(x.shape, like=x)
         key = (x.device.index, self._stream())
         ws = self._sel_ws.get(key)
         if ws is None:
@@ -707,7 +714,7 @@ class HipOps:
 
     def philox_normal(self, Cc: int, F: int, f0: int, Ftotal: int, hw: int, seed: int, stream_id: int,
                       device) -> Tensor:
-        out = torch.empty(Cc, F, hw, device=device, dtype=torch.float32)
+        out = self.empty(Cc, F, hw, device=device)
         check(self.L.dawn_philox_normal(_p(out), Cc, F, f0, Ftotal, hw, seed, stream_id, self._stream()),
               "dawn_philox_normal")
         return out
@@ -802,7 +809,7 @@ class HipOps:
         _, T, H, W = vid.shape
         _need(vid.shape[0] == 3 and vid.stride(3) == 1 and vid.stride(2) == W and vid.stride(1) == H * W, "frames_to_u8: vid.shape[0] == 3 and vid.stride(3) == 1 and vid.stride(2) == W and vid.stride(1) == H * W")
         self._require(vid)
-        out = torch.empty(T, H, W, 3, device=vid.device, dtype=torch.uint8)
+        out = self.empty(T, H, W, 3, like=vid, dtype=torch.uint8)
         m = [float(x) / 255.0 for x in mean]
         check(self.L.dawn_frames_to_u8(_p(vid), vid.stride(0), T * H * W, m[0], m[1], m[2], 1 if bgr else 0, _p(out),
                                        self._stream()), "dawn_frames_to_u8")
@@ -815,7 +822,7 @@ class HipOps:
         _need(vid.shape[0] == 3 and vid.stride(3) == 1 and vid.stride(2) == W and vid.stride(1) == H * W, "frames_to_yuv420: vid.shape[0] == 3 and vid.stride(3) == 1 and vid.stride(2) == W and vid.stride(1) == H * W")
         self._require(vid)
         if out is None:
-            out = torch.empty(T, H * W * 3 // 2, device=vid.device, dtype=torch.uint8)
+            out = self.empty(T, H * W * 3 // 2, like=vid, dtype=torch.uint8)
         _need(out.dtype == torch.uint8 and out.shape == (T, H * W * 3 // 2) and out.is_contiguous(), "frames_to_yuv420: out.dtype == torch.uint8 and out.shape == (T, H * W * 3 // 2) and out.is_contiguous()")
         m = [float(x) / 255.0 for x in mean]
         check(self.L.dawn_frames_to_yuv420(_p(vid), vid.stride(0), T, H, W, m[0], m[1], m[2], _p(out), self._stream()),
@@ -827,8 +834,8 @@ class HipOps:
         """Wav2Vec2FeatureExtractor(do_normalize): (x - mean) / sqrt(var + 1e-7) over the utterance."""
         _need(x.is_contiguous() and x.dim() == 1, "wave_normalize: x.is_contiguous() and x.dim() == 1")
         self._require(x)
-        st = torch.empty(2, dtype=torch.float64, device=x.device)
-        out = torch.empty_like(x)
+        st = self.empty(2, like=x, dtype=torch.float64)
+        out = self.empty(x.shape, like=x)
         check(self.L.dawn_wave_normalize(_p(x), x.numel(), _p(st), _p(out), self._stream()), "dawn_wave_normalize")
         return out
 
@@ -847,7 +854,7 @@ class HipOps:
         """LayerNorm over the channels of every row, affine, act 0 none / 2 exact GELU."""
         _need(x.is_contiguous(), "ln_affine_act: x.is_contiguous()")
         self._require(x, gamma, beta)
-        out = torch.empty_like(x)
+        out = self.empty(x.shape, like=x)
         check(self.L.dawn_ln_affine_act(_p(x), x.shape[0], x.shape[1], _p(gamma), _p(beta), eps, act, _p(out), self._stream()),
               "dawn_ln_affine_act")
         return out
@@ -856,7 +863,8 @@ class HipOps:
         """out = a + act(b) (a may be None); act 2 = exact GELU."""
         _need(b.is_contiguous() and (a is None or a.is_contiguous()), "add_act: b.is_contiguous() and (a is None or a.is_contiguous())")
         self._require(a, b)
-        out = torch.empty_like(b) if out is None else out
+        if out is None:
+            out = self.empty(b.shape, like=b)
         check(self.L.dawn_add_act(_p(a), _p(b), act, b.numel(), _p(out), self._stream()), "dawn_add_act")
         return out
 
@@ -869,7 +877,8 @@ class HipOps:
               and w.numel() == groups * k * gw * gw and bias.numel() == E,
               "hubert_pos_conv: hid (T, E), w (groups, k * gw / 4, gw, 4) and bias (E) contiguous, gw = E // groups")
         self._require(hid, w, bias, out)
-        out = torch.empty_like(hid) if out is None else out
+        if out is None:
+            out = self.empty(hid.shape, like=hid)
         _need(out.is_contiguous() and out.shape == hid.shape and out.dtype == hid.dtype, "hubert_pos_conv: out like hid, contiguous")
         check(self.L.dawn_hubert_pos_conv(_p(hid), T, E, groups, k, _p(w), _p(bias), _p(out), self._stream()), "dawn_hubert_pos_conv")
         return out

@@ -1,5 +1,5 @@
-"""Guard bands and poison around the buffers of the UNet evaluation's kernels, for GPU op tests; shown to catch each defect on
-CPU tensors by tests/test_guarded_cpu.py.  A max-norm comparison of values cannot see three kinds of error:
+"""Guard bands and poison around the buffers of the UNet evaluation's kernels and of the stage and sampler kernels around it (flow decoder,
+HuBERT, PBnet, sampler steps), for GPU op tests; shown to catch each defect on CPU tensors by tests/test_guarded_cpu.py.  A max-norm comparison of values cannot see three kinds of error:
 
   * an output element the kernel never wrote -- the results come from `torch.empty`, and the caching allocator hands the block
     of the previous, correct, call back: `GuardedOps.empty` fills every result with NaN first;
@@ -10,13 +10,32 @@ CPU tensors by tests/test_guarded_cpu.py.  A max-norm comparison of values canno
 Every band is part of ONE torch allocation that the helper owns: a stray access lands in owned memory and becomes an assertion.
 Nothing here depends on the device: the same code carves CPU tensors.
 
-What is guarded: what an op asks `HipOps.empty` / `conv_gn_part` for, and what the test hands in through `guarded_out` / `guarded_in`.
-NOT guarded: the few buffers ops.py takes from torch directly -- the per-clip table of `xattn_tables`, the GroupNorm hand-off ticket and
-the selection scratch (cached per stream), and everything the sampler ops allocate.
+What is guarded: what an op asks `HipOps.empty` / `conv_gn_part` for -- every result of every op of ops.py, the sampler ops, the frame
+egress and the HuBERT ops included, and the private scratch `quantile_threshold.ws` that a histogram from elsewhere makes it allocate --
+and what the test hands in through `guarded_out` / `guarded_in`.
+NOT guarded: the three buffers ops.py still takes from torch directly, each cached for the life of the HipOps object and shared between calls,
+so that no single call owns (or completely writes) it:
+  * the per-clip table of `xattn_tables` (written once per clip, read by every evaluation);
+  * the GroupNorm hand-off ticket of `_gn_ticket` (four words per (device, stream), zeroed by a stream-ordered fill);
+  * the selection scratch `_sel_ws` of `ddim_x0` / `cfg_x0` / `quantile_threshold` (4104 words per (device, stream)) and the `hist` slice of
+    it that `ddim_x0` and `cfg_x0` return: its contents are checked by value (the histogram is compared bin for bin with a bincount).
+
+Byte outputs.  Poison is 0xFF and 255 is a legal RGB byte, so an integer payload is unambiguous only where the EXPECTED bytes hold no 255:
+every guarded byte test first asserts that on its CPU reference (`assert_no_255`).  For I420 it holds by definition (Y <= 235, U and
+V <= 240); for RGB the test draws its inputs so that the clipped value stays below 255/255 and keeps the mean at zero (the 255 level is pinned
+by the byte-boundary tests of the egress, which are not guarded).  Under that condition the integer rule of `_poisoned` (== 255: never
+written) is exact.
+
+Outputs into a frame range of a longer clip (PARTIAL, below): the test guards the WHOLE clip, hands the op the frame-range view and states the
+written rows, verify(written=...); every other row must still be poison.  For the fp32 clips (3, Ttot, H, W) the rows are the (channel,
+frame) pairs: the clip is carved as (3 * Ttot, H * W).  A strided plane view as an INPUT (`grid`, a frame range of a (2, Ttot, h, w) clip) is
+guarded as the whole clip too: the frames outside the range are ordinary in-buffer data that the value references would expose if read,
+the bands around the whole clip are NaN.
 
 Names.  A result is named `<HipOps method>.<variable it is assigned to>`, read off the calling line; a line that does not have that shape
 is an error here, not a silent other name.  The names PARTIAL is keyed by are pinned twice: tests/test_guarded_cpu.py finds each in the
-source of ops.py, and the GPU tests of those ops (tests/test_hip_guard.py) assert that the buffer of that name was allocated."""
+source of ops.py, and the GPU tests of those ops (tests/test_hip_guard.py, tests/test_hip_guard_stages.py) assert that the buffer of that
+name was allocated.  A PARTIAL key whose variable is a parameter of its method names an output that only a caller supplies."""
 import linecache
 import re
 import sys
@@ -43,7 +62,28 @@ PARTIAL = {
     "head_out.out": ("one head at a time (hg or ho is None) writes that head's rows of the caller's `out` only",
                      lambda r: torch.ones(r.payload.shape[0], dtype=torch.bool)),     # all three, unless the caller states the rows:
     # verify(written={"head_out.out": ...}); the rows it does not state must then still be poison
+    # ---- outputs that a caller aims at a frame range of a longer clip: all rows, unless the caller states the frames it handed over
+    "final_conv_blend.out_vid": ("a (3, T, H, W) frame-range view of a (3, Ttot, H, W) clip, carved as (3 * Ttot, H * W): only the (channel, frame) "
+                                 "rows of the range are written", lambda r: torch.ones(r.payload.shape[0], dtype=torch.bool)),
+    "final_conv_blend.warped_vid": ("as final_conv_blend.out_vid", lambda r: torch.ones(r.payload.shape[0], dtype=torch.bool)),
+    "final_conv_blend_u8.frames": ("frames [t0, t1) of a (Ttot, H * W * 3) byte clip: only those frames are written",
+                                   lambda r: torch.ones(r.payload.shape[0], dtype=torch.bool)),
+    "final_conv_blend_yuv420.frames": ("frames [t0, t1) of a (Ttot, 3 * H * W / 2) I420 clip: only those frames are written",
+                                       lambda r: torch.ones(r.payload.shape[0], dtype=torch.bool)),
+    "frames_to_yuv420.out": ("the op's own allocation is written completely; a caller's `out` may be frames [t0, t1) of a longer I420 clip",
+                             lambda r: torch.ones(r.payload.shape[0], dtype=torch.bool)),
 }
+
+
+# Every result that the stage and sampler ops of ops.py allocate (`<method>.<variable>`; the two step-tail entries share `_step_fixed`).
+# tests/test_guarded_cpu.py finds each in the source of ops.py, tests/test_hip_guard_stages.py asserts that its launches allocated each.
+STAGE_BUFFERS = (
+    "affine_act.out", "bn_relu_pool2.out", "warp_blend.out", "frames_to_u8.out", "frames_to_yuv420.out",
+    "wave_normalize.st", "wave_normalize.out", "hubert_conv0.out", "ln_affine_act.out", "add_act.out", "hubert_pos_conv.out", "attn64.out",
+    "interp_linear.out", "attn_bias32.out",
+    "ddim_x0.x0", "cfg_x0.eps", "cfg_x0.x0", "quantile_threshold.out", "quantile_threshold.ws", "ddim_update.x", "ancestral_update.out",
+    "_step_fixed.out", "_step_fixed.x0", "cfg_combine.out", "philox_normal.out",
+)
 
 
 class GuardError(AssertionError):
@@ -106,7 +146,8 @@ def _carve(name, shape, dtype, device, fill, col_pad=0):
 
 
 def _poisoned(t):
-    """bool tensor like t: the element still holds poison (float: any NaN -- also what a NaN that was read turns a result into)."""
+    """bool tensor like t: the element still holds poison (float: any NaN -- also what a NaN that was read turns a result into; integer:
+    all-ones, which for bytes is exact only under the condition of the module docstring: the expected bytes hold no 255)."""
     return torch.isnan(t) if t.dtype.is_floating_point else t == torch.tensor(POISON).to(t.dtype)
 
 
@@ -121,6 +162,12 @@ def _call_site():
     return f"{f.f_code.co_name}.{m.group(1)}"
 
 
+def assert_no_255(want):
+    """The precondition of every guarded byte test (module docstring), on the CPU reference: no expected byte equals the poison."""
+    want = torch.as_tensor(want)
+    assert want.dtype == torch.uint8 and not bool((want == 255).any()), "a guarded byte test needs expected bytes below 255 (255 is the poison)"
+
+
 class GuardedOps(HipOps):
     """HipOps whose every result is carved out of a guarded, poisoned allocation; see the module docstring."""
 
@@ -131,10 +178,10 @@ class GuardedOps(HipOps):
         self.ins = []           # guarded inputs
 
     # ------------------------------------------------------------------ allocation
-    def empty(self, *shape, like, dtype=torch.float32):
+    def empty(self, *shape, like=None, dtype=torch.float32, device=None):
         if len(shape) == 1 and isinstance(shape[0], (tuple, list)):
             shape = tuple(shape[0])
-        r = _carve(_call_site(), shape, dtype, like.device, PATTERN)
+        r = _carve(_call_site(), shape, dtype, like.device if like is not None else device, PATTERN)
         self.outs.append(r)
         return r.payload
 

@@ -222,6 +222,36 @@ def test_launch_preconditions_raise_not_assert():
         ops._need(False, "x.is_contiguous()")
 
 
+def _refused(call):
+    """The call raises through `_need` before anything is allocated or launched (the operands are CPU tensors: a launch would not even
+    get this far with them, and `_require` would name the device, not the precondition)."""
+    from dawn_pytorch_amd import _lib
+    with pytest.raises(_lib.DawnHipError, match="HipOps precondition failed"):
+        call()
+
+
+def test_ddim_update_preconditions():
+    """ddim_update launches over x0.numel() elements: a shorter or strided eps / noise would be read past its end."""
+    from dawn_pytorch_amd.ops import HipOps
+    ops = HipOps()
+    x0, s = torch.zeros(3, 4), torch.ones(2)
+    wide = torch.zeros(3, 8)
+    _refused(lambda: ops.ddim_update(x0, torch.zeros(11), s, None, 1.0, 0.0, 0.0))                  # eps one element short
+    _refused(lambda: ops.ddim_update(x0, wide[:, :4], s, None, 1.0, 0.0, 0.0))                      # eps strided
+    _refused(lambda: ops.ddim_update(wide[:, :4], torch.zeros(3, 4), s, None, 1.0, 0.0, 0.0))       # x0 strided
+    _refused(lambda: ops.ddim_update(x0, torch.zeros(3, 4), s, torch.zeros(11), 1.0, 0.0, 0.0))     # noise one element short
+    _refused(lambda: ops.ddim_update(x0, torch.zeros(3, 4), s, wide[:, :4], 1.0, 0.0, 0.0))         # noise strided
+
+
+def test_cfg_combine_preconditions():
+    from dawn_pytorch_amd.ops import HipOps
+    ops = HipOps()
+    e, wide = torch.zeros(3, 4), torch.zeros(3, 8)
+    _refused(lambda: ops.cfg_combine(torch.zeros(11), e, 2.0))                                     # e_null one element short
+    _refused(lambda: ops.cfg_combine(wide[:, :4], e, 2.0))                                         # e_null strided
+    _refused(lambda: ops.cfg_combine(e, wide[:, :4], 2.0))                                         # e_cond strided
+
+
 def test_band_and_rotary_tables_under_inference_mode_with_fp16_checkpoint(tiny):
     """packing runs lazily inside GaussianDiffusion.sample(), i.e. under torch.inference_mode(); with a checkpoint that needs
     a conversion (fp16 weights) the packed tables are inference tensors, which have no version counter -- band() must not ask for one.
