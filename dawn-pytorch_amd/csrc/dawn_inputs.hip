@@ -1,8 +1,10 @@
 // C-side host of the clip-input stage (include/dawn_hip.h: dawn_inputs_*, dawn_clip_inputs) and of the one-call pipeline that
-// chains the five stage hosts (dawn_generate_bytes, dawn_generate_clip).  Same contract as the other four: opaque handle, device
+// chains the five stage hosts (dawn_generate_bytes, dawn_generate_clip; from decoded media, with the two conversions of
+// media_ingest.hip in front: dawn_generate_media_bytes, dawn_generate_clip_media).  Same contract as the other four: opaque handle, device
 // pointers by name, every launch on the caller's stream, no allocation, no synchronisation, errors by return code + dawn_last_error
 // with nothing launched.  The pipeline calls nothing but the public entry points of the stages.
 #include "clip_inputs.h"
+#include "media_ingest.h"
 
 #include <math.h>
 #include <stddef.h>
@@ -188,14 +190,14 @@ extern "C" int dawn_generate_bytes(const dawn_generate_args* args, size_t* clip_
     return 0;
 }
 
-extern "C" int dawn_generate_clip(const dawn_generate_args* args, void* workspace, size_t workspace_bytes, void* stream) {
-    const char* who = "dawn_generate_clip";
-    Plan p;
-    CK(make_plan(args, who, p));
-    const dawn_generate_args& a = *args;
-    if (!a.frames_out) return refuse(-301, who, "NULL frames_out");
-    if (!workspace || workspace_bytes < p.total)
-        return refuse_workspace(-305, who, workspace ? workspace_bytes : 0, p.total, "dawn_generate_bytes");
+namespace {
+
+// The pipeline on a plan that make_plan accepted: its remaining checks, then `before_first_launch` (the conversions of
+// dawn_generate_clip_media, which write a.img3 / a.samples; it launches, so it comes after the last refusal), then the stages.
+// `workspace` is the pipeline's own part: p.total bytes.
+template <class Pre>
+int run_pipeline(const dawn_generate_args& a, const Plan& p, void* workspace, size_t workspace_bytes, void* stream, const char* who,
+                 Pre&& before_first_launch) {
     const dawn_inputs_cfg& ic = a.inputs->cfg;
     const long T = a.T;
     const int h = p.h, H = a.H, ldc = p.ld_cond;
@@ -212,6 +214,7 @@ extern "C" int dawn_generate_clip(const dawn_generate_args* args, void* workspac
     // the pose stage writes 6 pose columns; a 7th comes from init_pose (FD:348-349)
     CK(check_clip_inputs(a.inputs, a.bbox6, H, fea, a.fea_ch, audio, ic.n_aud, pose, 6, ldc, eye, ldc, a.init_pose, a.n_init, a.init_eye, T,
                          cond, ldc, who));
+    CK(before_first_launch());
     void* sws = ws + p.stage;
     const size_t sbytes = p.stage_bytes;
     const hipStream_t st = (hipStream_t)stream;
@@ -249,4 +252,91 @@ extern "C" int dawn_generate_clip(const dawn_generate_args* args, void* workspac
                                        sbytes, stream);
     return dawn_decode_clip(a.decoder, H, H, (int)T, h, h, a.img3, ws + p.skip, latent, plane, a.chunk, nullptr, nullptr, 0, a.frames_out,
                             a.mean3, a.bgr, sws, sbytes, stream);
+}
+
+// ---- the same from decoded media: the front of the workspace holds what the two conversions make
+struct MediaPlan {
+    dawn_generate_args gen;                 // the caller's, with img3 / samples / n_samples replaced where media are given
+    Plan plan;
+    size_t img3, samples, ingest, ingest_bytes, front;      // offsets; front = where the pipeline's own workspace starts
+};
+
+int make_media_plan(const dawn_media_args* m, const char* who, MediaPlan& q) {
+    if (!m || !m->gen) return refuse(-321, who, "NULL args or NULL gen");
+    q.gen = *m->gen;
+    dawn_generate_args& g = q.gen;
+    if (!m->image && !g.img3) return refuse(-321, who, "image is NULL and so is gen->img3: one of the two is the source image");
+    if (!m->pcm && !g.samples) return refuse(-321, who, "pcm is NULL and so is gen->samples: one of the two is the audio");
+    // placeholders that only have to be non-NULL until the workspace is known: no check below reads through them
+    static const float dummy_f = 0.0f;
+    if (m->pcm) {
+        CK(media_pcm_check(m->pcm, m->n_frames, m->channels, &dummy_f, who));
+        g.samples = &dummy_f;
+        g.n_samples = m->n_frames;
+    }
+    if (m->image) g.img3 = &dummy_f;
+    CK(make_plan(&g, who, q.plan));
+    size_t o = 0;
+    auto take = [&](size_t bytes) { const size_t at = o; o += a256(bytes); return at; };
+    q.ingest_bytes = 0;
+    if (m->image) {
+        // out3 and the ingest workspace are this entry's own, carved below: only the source and the shapes can be wrong
+        CK(media_image_check(m->image, m->Hs, m->Ws, m->row_bytes, m->pix_bytes, m->order, g.H, g.H, (long)g.H * g.H, who));
+        q.ingest_bytes = dawn_image_ingest_workspace_bytes(m->Hs, m->Ws, g.H, g.H);
+    }
+    q.img3 = take(m->image ? (size_t)3 * g.H * g.H * 4 : 0);
+    q.samples = take(m->pcm ? (size_t)m->n_frames * 4 : 0);
+    q.ingest = take(q.ingest_bytes);
+    q.front = o;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int dawn_generate_clip(const dawn_generate_args* args, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* who = "dawn_generate_clip";
+    Plan p;
+    CK(make_plan(args, who, p));
+    if (!args->frames_out) return refuse(-301, who, "NULL frames_out");
+    if (!workspace || workspace_bytes < p.total)
+        return refuse_workspace(-305, who, workspace ? workspace_bytes : 0, p.total, "dawn_generate_bytes");
+    return run_pipeline(*args, p, workspace, workspace_bytes, stream, who, [] { return 0; });
+}
+
+extern "C" int dawn_generate_media_bytes(const dawn_media_args* args, size_t* clip_bytes, size_t* workspace_bytes) {
+    MediaPlan q;
+    CK(make_media_plan(args, "dawn_generate_media_bytes", q));
+    if (clip_bytes) *clip_bytes = q.plan.frames_bytes;
+    if (workspace_bytes) *workspace_bytes = q.front + q.plan.total;
+    return 0;
+}
+
+extern "C" int dawn_generate_clip_media(const dawn_media_args* args, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* who = "dawn_generate_clip_media";
+    MediaPlan q;
+    CK(make_media_plan(args, who, q));
+    const dawn_media_args& m = *args;
+    dawn_generate_args& g = q.gen;
+    if (!g.frames_out) return refuse(-301, who, "NULL frames_out");
+    const size_t total = q.front + q.plan.total;
+    if (!workspace || workspace_bytes < total)
+        return refuse_workspace(-305, who, workspace ? workspace_bytes : 0, total, "dawn_generate_media_bytes");
+    char* ws = (char*)workspace;
+    float* img3 = (float*)(ws + q.img3);
+    float* samples = (float*)(ws + q.samples);
+    if (m.image) g.img3 = img3;
+    if (m.pcm) g.samples = samples;
+    // the conversions' pieces are workspace too (run_pipeline checks the outputs against its own part)
+    if (overlaps(g.frames_out, q.plan.frames_bytes, ws, q.front) ||
+        (g.cond_out && overlaps(g.cond_out, (size_t)g.T * q.plan.ld_cond * 4, ws, q.front)) ||
+        (g.latent_out && overlaps(g.latent_out, (size_t)3 * g.T * q.plan.h * q.plan.h * 4, ws, q.front)))
+        return refuse(-306, who, "frames_out / latent_out / cond_out overlaps the workspace");
+    const long HH = (long)g.H * g.H;
+    return run_pipeline(g, q.plan, ws + q.front, workspace_bytes - q.front, stream, who, [&] {
+        if (m.image)
+            CK(dawn_image_ingest(m.image, m.Hs, m.Ws, m.row_bytes, m.pix_bytes, m.order, g.H, g.H, img3, HH, ws + q.ingest, q.ingest_bytes,
+                                 stream));
+        if (m.pcm) CK(dawn_pcm16_to_samples(m.pcm, m.n_frames, m.channels, samples, stream));
+        return 0;
+    });
 }

@@ -878,7 +878,14 @@ class GenerateArgs(C.Structure):
                 ("frames_out", C.c_void_p), ("latent_out", C.c_void_p), ("cond_out", C.c_void_p)]
 
 
+class MediaArgs(C.Structure):
+    """Mirror of ``dawn_media_args``."""
+    _fields_ = [("gen", C.POINTER(GenerateArgs)), ("image", C.c_void_p), ("Hs", C.c_int), ("Ws", C.c_int), ("row_bytes", C.c_long),
+                ("pix_bytes", C.c_int), ("order", C.c_int), ("pcm", C.c_void_p), ("n_frames", C.c_long), ("channels", C.c_int)]
+
+
 FRAMES_RGB, FRAMES_YUV420 = 0, 1
+PIXELS_RGB, PIXELS_BGR = 0, 1
 Z_POSE_STREAM, Z_BLINK_STREAM = 0xFFFFFFFE, 0xFFFFFFFF      # Philox stream ids of the PBnet latents; x_init is stream 0, sampler steps 1..
 
 
@@ -895,19 +902,26 @@ class PipelineEvaluator:
 
     def args(self, samples: Tensor, img: Tensor, bbox6, init_pose6, init_blink2, T: int, steps: Sequence[dict], *, ancestral: bool = False,
              init_pose=None, init_eye=None, cond_scale: float = 1.0, x0_clip=None, seed: int = 0, fmt: str = "rgb", mean=(0.0, 0.0, 0.0),
-             bgr: bool = False, chunk: int = 16) -> GenerateArgs:
-        """The filled struct; every host array it points to is kept alive on it (`_keep`)."""
+             bgr: bool = False, chunk: int = 16, H: Optional[int] = None) -> GenerateArgs:
+        """The filled struct; every host array it points to is kept alive on it (`_keep`).  samples / img may be None where
+        `from_media` supplies PCM / image bytes instead; without an img the model's image side is `H`."""
         hub, pose, blink, dec, inp, unet = self.ev
-        if not (samples.is_cuda and samples.is_contiguous() and samples.dtype == torch.float32 and samples.dim() == 1):
+        if samples is not None and not (samples.is_cuda and samples.is_contiguous() and samples.dtype == torch.float32 and samples.dim() == 1):
             raise _lib.DawnHipError("PipelineEvaluator: samples must be a contiguous 1-D fp32 GPU tensor")
-        if not (img.is_cuda and img.is_contiguous() and img.dtype == torch.float32 and img.dim() == 3 and img.shape[0] == 3
-                and img.shape[1] == img.shape[2]):
+        if img is None and H is None:
+            raise _lib.DawnHipError("PipelineEvaluator: without an img the image side H must be given")
+        if img is not None and not (img.is_cuda and img.is_contiguous() and img.dtype == torch.float32 and img.dim() == 3 and img.shape[0] == 3
+                                    and img.shape[1] == img.shape[2] and H in (None, img.shape[1])):
             raise _lib.DawnHipError("PipelineEvaluator: img must be a contiguous fp32 GPU tensor (3, H, H)")
         if fmt not in ("rgb", "yuv420p"):
             raise _lib.DawnHipError(f"PipelineEvaluator: format must be 'rgb' or 'yuv420p', not {fmt!r}")
         a = GenerateArgs()
         a.hubert, a.pose, a.blink, a.decoder, a.inputs, a.unet = hub.h, pose.h, blink.h, dec.h, inp.h, unet.h
-        a.samples, a.n_samples, a.img3, a.H, a.fea_ch = samples.data_ptr(), samples.numel(), img.data_ptr(), img.shape[1], unet.cfg.fea_ch
+        if samples is not None:
+            a.samples, a.n_samples = samples.data_ptr(), samples.numel()
+        if img is not None:
+            a.img3 = img.data_ptr()
+        a.H, a.fea_ch = int(H if img is None else img.shape[1]), unet.cfg.fea_ch
         S = len(steps)
         if ancestral:
             arr = (AncestralStep * max(S, 1))()
@@ -971,4 +985,67 @@ class PipelineEvaluator:
                 self._ws = torch.empty(wb, dtype=torch.uint8, device=self.device)
             workspace = self._ws
         check(self.L.dawn_generate_clip(C.addressof(a), workspace.data_ptr(), workspace.numel(), _Evaluator._stream()), "dawn_generate_clip")
+        return out
+
+    # ---- the same from decoded media (dawn_generate_media_bytes / dawn_generate_clip_media)
+    def from_media(self, a: GenerateArgs, image: Optional[Tensor] = None, pcm: Optional[Tensor] = None, order: str = "rgb") -> MediaArgs:
+        """`a` = the struct of `args(...)` (its img / samples are placeholders for whatever is given here) -> the dawn_media_args that
+        replaces them: image = uint8 GPU tensor (Hs, Ws, C) or (Hs, Ws) with unit pixel and channel strides and any row stride, C in
+        {1, 3, 4}; pcm = int16 GPU tensor (n_frames, channels) or (n_frames,), contiguous.  None keeps the input of `a`."""
+        m = MediaArgs()
+        m.gen = C.pointer(a)
+        keep = [a]
+        if image is not None:
+            pb = 1 if image.dim() == 2 else int(image.shape[2])
+            if not (image.is_cuda and image.dtype == torch.uint8 and image.dim() in (2, 3) and image.stride(1) == pb
+                    and (image.dim() == 2 or image.stride(2) == 1)):
+                raise _lib.DawnHipError("PipelineEvaluator.from_media: image must be a uint8 GPU tensor (Hs, Ws[, C]) with dense pixels")
+            if order not in ("rgb", "bgr"):
+                raise _lib.DawnHipError(f"PipelineEvaluator.from_media: order must be 'rgb' or 'bgr', not {order!r}")
+            m.image, m.Hs, m.Ws, m.pix_bytes = image.data_ptr(), int(image.shape[0]), int(image.shape[1]), pb
+            m.row_bytes = int(image.stride(0)) if image.shape[0] > 1 else max(int(image.stride(0)), int(image.shape[1]) * pb)
+            m.order = PIXELS_BGR if order == "bgr" else PIXELS_RGB
+            keep.append(image)
+        if pcm is not None:
+            if not (pcm.is_cuda and pcm.dtype == torch.int16 and pcm.dim() in (1, 2) and pcm.is_contiguous()):
+                raise _lib.DawnHipError("PipelineEvaluator.from_media: pcm must be a contiguous int16 GPU tensor (n_frames[, channels])")
+            m.pcm, m.n_frames, m.channels = pcm.data_ptr(), int(pcm.shape[0]), 1 if pcm.dim() == 1 else int(pcm.shape[1])
+            keep.append(pcm)
+        m._keep = keep
+        return m
+
+    def media_sizes(self, m: MediaArgs):
+        """(bytes of the frames, bytes of the workspace) of dawn_generate_media_bytes."""
+        cb, wb = C.c_size_t(0), C.c_size_t(0)
+        check(self.L.dawn_generate_media_bytes(C.addressof(m), C.byref(cb), C.byref(wb)), "dawn_generate_media_bytes")
+        return int(cb.value), int(wb.value)
+
+    def generate_media(self, m: MediaArgs, want_latent: bool = False, want_cond: bool = False, workspace: Optional[Tensor] = None,
+                       frames: Optional[Tensor] = None) -> dict:
+        """`generate` through dawn_generate_clip_media on the struct of `from_media(...)`: the same outputs."""
+        hub, pose, blink, dec, inp, unet = self.ev
+        a = m.gen.contents
+        cb, wb = self.media_sizes(m)
+        T, H, h = int(a.T), int(a.H), int(a.H) // 4
+        if frames is None:
+            frames = torch.empty((T, H * H * 3 // 2) if a.format == FRAMES_YUV420 else (T, H, H, 3), dtype=torch.uint8, device=self.device)
+        if not (frames.is_cuda and frames.dtype == torch.uint8 and frames.is_contiguous() and frames.numel() == cb):
+            raise _lib.DawnHipError(f"PipelineEvaluator.generate_media: frames must be a contiguous uint8 GPU tensor of {cb} bytes")
+        out = {"frames": frames}
+        a.frames_out = frames.data_ptr()
+        if want_latent:
+            out["latent"] = torch.empty(3, T, h, h, device=self.device)
+            a.latent_out = out["latent"].data_ptr()
+        if want_cond:
+            out["cond"] = torch.empty(T, inp.cfg.n_aud + inp.cfg.pose_dim + 2, device=self.device)
+            a.cond_out = out["cond"].data_ptr()
+        if want_latent or want_cond:
+            cb, wb = self.media_sizes(m)
+        if workspace is None:
+            if self._ws is None or self._ws.numel() < wb:
+                self._ws = None
+                self._ws = torch.empty(wb, dtype=torch.uint8, device=self.device)
+            workspace = self._ws
+        check(self.L.dawn_generate_clip_media(C.addressof(m), workspace.data_ptr(), workspace.numel(), _Evaluator._stream()),
+              "dawn_generate_clip_media")
         return out

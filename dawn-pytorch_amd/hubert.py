@@ -153,7 +153,11 @@ class HubertFeatures:
             self._evaluator = HubertEvaluator(self)
         return self._evaluator
 
-    def _speech_device(self, speech: np.ndarray) -> Tensor:
+    def _speech_device(self, speech) -> Tensor:
+        if isinstance(speech, torch.Tensor):                             # fp32 mono on the device already (ops.pcm16_to_samples)
+            if not (speech.dim() == 1 and speech.dtype == torch.float32):
+                raise ValueError("speech as a tensor: 1-D float32")
+            return speech.contiguous().to(self.device)
         if speech.ndim == 2:
             speech = speech[:, 0]                                        # [T, 2] ==> [T,]  (UVG:455-456)
         return torch.from_numpy(np.ascontiguousarray(speech, dtype=np.float32)).to(self.device)

@@ -980,3 +980,35 @@ class HipOps:
         check(self.L.dawn_cond_rows(_p(audio), n_aud, ld(audio), _p(pose), n_pose, ld(pose), _p(eye), ld(eye), ip,
                                     0 if init_pose is None else len(init_pose), ie, T, _p(out), ld(out), self._stream()), "dawn_cond_rows")
         return out
+
+    # ------------------------------------------------------------------ media ingest (csrc/media_ingest.hip)
+    def image_ingest(self, src_u8: Tensor, Ho: int, Wo: int, order: str = "rgb", out: Optional[Tensor] = None) -> Tensor:
+        """Decoded image bytes -> the (3, Ho, Wo) fp32 planes in [0, 1] of `Image.convert("RGB")` + Pillow's 8-bit bilinear resize +
+        ToTensor(), bit for bit (dawn_image_ingest).  src_u8 = (Hs, Ws, C) with C in {1, 3, 4} or (Hs, Ws) uint8, dense pixels, any row
+        stride; order "rgb" / "bgr" = the byte order of a colour source.  `out`: three dense planes with a common stride."""
+        _need(src_u8.is_cuda and src_u8.dtype == torch.uint8 and src_u8.dim() in (2, 3), "image_ingest: a uint8 GPU tensor (Hs, Ws[, C])")
+        pb = 1 if src_u8.dim() == 2 else int(src_u8.shape[2])
+        _need(src_u8.stride(1) == pb and (src_u8.dim() == 2 or src_u8.stride(2) == 1), "image_ingest: pixels and channels must be dense")
+        _need(order in ("rgb", "bgr"), "image_ingest: order is 'rgb' or 'bgr'")
+        Hs, Ws = int(src_u8.shape[0]), int(src_u8.shape[1])
+        row_bytes = int(src_u8.stride(0)) if Hs > 1 else max(int(src_u8.stride(0)), Ws * pb)
+        self._require(out)
+        if out is None:
+            out = self.empty(3, Ho, Wo, like=src_u8)
+        _need(out.dtype == torch.float32 and tuple(out.shape) == (3, Ho, Wo) and out.stride(2) == 1 and out.stride(1) == Wo,
+              "image_ingest: out (3, Ho, Wo) fp32 with dense planes")
+        nbytes = int(self.L.dawn_image_ingest_workspace_bytes(Hs, Ws, int(Ho), int(Wo)))
+        ws = self.empty(max(nbytes, 1), like=src_u8, dtype=torch.uint8)
+        check(self.L.dawn_image_ingest(_p(src_u8), Hs, Ws, row_bytes, pb, 1 if order == "bgr" else 0, int(Ho), int(Wo), _p(out), out.stride(0),
+                                       _p(ws), nbytes, self._stream()), "dawn_image_ingest")
+        return out
+
+    def pcm16_to_samples(self, pcm_i16: Tensor) -> Tensor:
+        """Interleaved 16-bit PCM (n_frames, channels) or (n_frames,) int16, contiguous -> channel 0 as fp32 / 32768 (n_frames,): what
+        `soundfile.read(...)[0][:, 0]` holds, exactly (dawn_pcm16_to_samples)."""
+        _need(pcm_i16.is_cuda and pcm_i16.dtype == torch.int16 and pcm_i16.dim() in (1, 2) and pcm_i16.is_contiguous(),
+              "pcm16_to_samples: a contiguous int16 GPU tensor (n_frames[, channels])")
+        n, ch = int(pcm_i16.shape[0]), 1 if pcm_i16.dim() == 1 else int(pcm_i16.shape[1])
+        out = self.empty(n, like=pcm_i16)
+        check(self.L.dawn_pcm16_to_samples(_p(pcm_i16), n, ch, _p(out), self._stream()), "dawn_pcm16_to_samples")
+        return out

@@ -48,9 +48,12 @@ class _LastOutput(dict):
 
 
 class VideoGenerator:
+    image_via_c = False               # (class default: the opt-in of __init__'s keyword)
+
     def __init__(self, args, *, generator=None, frontend=None, config: Optional[dict] = None, device=None,
                  allow_random_weights: bool = False, deterministic: bool = True, hubert=None, pbnet=None,
-                 video_egress: str = "png", encoder_cmd=None, pbnet_via_c: bool = False, inputs_via_c: bool = False):
+                 video_egress: str = "png", encoder_cmd=None, pbnet_via_c: bool = False, inputs_via_c: bool = False,
+                 image_via_c: bool = False):
         """`allow_random_weights`: explicit opt-in (benches, tests) to run with the deterministic random-init denoiser
         when the configured checkpoint is absent; without it a missing checkpoint raises, as the reference's
         `torch.load` does (UVG:527).  `deterministic`: seed the sampler's counter-based noise with the config's
@@ -65,7 +68,11 @@ class VideoGenerator:
         `pbnet_via_c`: stage 3 through the C-side stage (dawn_pose_blink_stage: windowed attention, any clip length) instead of the Python
         orchestration of pbnet.py.
         `inputs_via_c`: passed on as `FlowDiffusion.inputs_via_c` -- the face-location channels and the condition rows of a GPU clip from
-        the C-side clip-input stage (dawn_clip_inputs) instead of the torch plumbing."""
+        the C-side clip-input stage (dawn_clip_inputs) instead of the torch plumbing.
+        `image_via_c` (GPU only): the decoded source image goes to the device as bytes and dawn_image_ingest resizes and scales it there
+        (Pillow's 8-bit bilinear resample restated in integers: the same bytes as the host resize, and from there the same
+        arithmetic as the default path, so the same frames); with `hubert` set, a 16 kHz 16-bit
+        PCM file's frames go to the device as int16 and dawn_pcm16_to_samples makes the fp32 samples (the same values)."""
         if video_egress not in ("png", "yuv420p"):
             raise ValueError(f"video_egress must be 'png' or 'yuv420p', not {video_egress!r}")
         self.video_egress = video_egress
@@ -73,6 +80,7 @@ class VideoGenerator:
         self.hubert = hubert              # hubert.HubertFeatures: stage 2 (process_audio, UVG:202-250) on the GPU
         self.pbnet_via_c = bool(pbnet_via_c)
         self.inputs_via_c = bool(inputs_via_c)
+        self.image_via_c = bool(image_via_c)
         self.pbnet = pbnet                # (pose, blink) pbnet.PoseBlinkGenerator pair: stage 3 (generate_pose_blink, UVG:252-302; N4)
         self.allow_random_weights = bool(allow_random_weights) or bool(getattr(args, "allow_random_weights", False))
         self.deterministic = deterministic
@@ -131,7 +139,11 @@ class VideoGenerator:
         `target_audio.npy`.  Otherwise it is delegated to `frontend` / the cache like the other upstream stages."""
         if self.hubert is None or not (self.audio_path and osp.exists(self.audio_path)):
             return self._front("process_audio")
-        speech = load_wav_16k(self.audio_path)
+        pcm = read_pcm16_16k(self.audio_path) if self.image_via_c and self.device.type == "cuda" else None
+        if pcm is not None:
+            speech = self.video_model.unet._ops().pcm16_to_samples(torch.from_numpy(pcm).to(self.device))
+        else:
+            speech = load_wav_16k(self.audio_path)
         feats = self.hubert.process_audio(speech)
         print(f'Frame count: {feats.shape[0]}')
         np.save(self.audio_emb_path, feats)
@@ -176,8 +188,15 @@ class VideoGenerator:
         if not yuv:
             os.makedirs(img_dir, exist_ok=True)
         size = cfg['input_size']
-        image = Image.open(self.image_path).convert("RGB").resize((size, size), Image.BILINEAR)
-        image_tensor = torch.from_numpy(np.array(image)).permute(2, 0, 1).float()        # 0..255, like ToTensor()*255
+        image = Image.open(self.image_path).convert("RGB")
+        if self.image_via_c and self.device.type == "cuda":
+            # the decoded bytes as they are; resize, planes and ToTensor() on the device (dawn_image_ingest), then the reference's * 255
+            # (UVG:325): byte / 255 * 255 is the byte again for all 256 values, so this is the tensor of the branch below, bit for bit
+            planes = self.video_model.unet._ops().image_ingest(torch.from_numpy(np.array(image)).to(self.device), size, size)
+            image_tensor = planes * 255
+        else:
+            image = image.resize((size, size), Image.BILINEAR)
+            image_tensor = torch.from_numpy(np.array(image)).permute(2, 0, 1).float()    # 0..255, like ToTensor()*255
         hubert = np.load(self.audio_emb_path)
         T = min(cfg['max_n_frames'], hubert.shape[0])
         ref_hubert = torch.from_numpy(hubert[:T]).float()
@@ -307,6 +326,20 @@ class VideoGenerator:
         self.generate_pose_blink()
         print("4. Generating final video...")
         return self.generate_final_video()
+
+
+def read_pcm16_16k(path: str) -> Optional[np.ndarray]:
+    """The frames of a 16 kHz 16-bit PCM WAV as int16 (n_frames, channels), read with the stdlib; None for any other file."""
+    import wave
+    try:
+        with wave.open(path, "rb") as f:
+            sr, nch, sw, n = f.getframerate(), f.getnchannels(), f.getsampwidth(), f.getnframes()
+            raw = f.readframes(n)
+    except (wave.Error, EOFError):
+        return None
+    if sr != 16000 or sw != 2 or not 1 <= nch <= 8 or len(raw) < 2 * nch:
+        return None
+    return np.frombuffer(raw, dtype="<i2").reshape(-1, nch).copy()
 
 
 def load_wav_16k(path: str) -> np.ndarray:

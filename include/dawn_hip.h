@@ -917,6 +917,56 @@ int dawn_generate_bytes(const dawn_generate_args* args, size_t* clip_bytes, size
 /* every argument is checked before the first launch: a refusal (NULL handle or pointer, T above what the audio yields, a short
  * workspace, ...) comes with a message and nothing launched.  latent_out / cond_out / frames_out must not overlap the workspace. */
 int dawn_generate_clip(const dawn_generate_args* args, void* workspace, size_t workspace_bytes, void* stream);
+/* ---- media ingest (csrc/media_ingest.hip): from what a host holds after decoding to what dawn_generate_clip takes.  Contract as the
+ * stage entry points: every launch on `stream`, no allocation, no synchronisation, every argument checked before the first launch; a
+ * refusal returns non-zero with a dawn_last_error message that names the argument, and launches nothing.
+ * UVG:320-325 (Image.open(...).convert("RGB") -> transforms.Resize((size, size)) -> ToTensor()): Pillow's 8-bit antialiased bilinear
+ * resample, restated in integers and bit-identical to it.  src = Hs rows of Ws interleaved pixels, device bytes, rows row_bytes >=
+ * Ws * pix_bytes apart, no alignment asked of the pointer or of row_bytes.  pix_bytes 1 = grey, replicated to the three planes as
+ * .convert("RGB") does for mode "L"; 3 = RGB / BGR; 4 = the same with a fourth byte that is never read (.convert("RGB") drops alpha).
+ * order = DAWN_PIXELS_RGB / DAWN_PIXELS_BGR (ignored for pix_bytes 1).  out3 = three planes of Ho * Wo floats, `plane` floats apart,
+ * in R, G, B order whatever `order` is; a value = (float)byte / 255.0f, one correctly rounded fp32 division (= ToTensor()'s value, and
+ * for all 256 bytes = (ToTensor(x) * 255) / 255. as the generator forms it).
+ * Per axis with input length n and output length m, in fp64 with every operation rounded on its own (no fused multiply-add):
+ *   scale = n / m; fs = max(scale, 1); support = fs; ss = 1 / fs
+ *   center = (i + 0.5) * scale; lo = max((int)(center - support + 0.5), 0); hi = min((int)(center + support + 0.5), n)
+ *   w[j] = max(1 - |(j + lo - center + 0.5) * ss|, 0), j < hi - lo; ww = w[0] + w[1] + ... left to right
+ *   k[j] = (int)(0.5 + (w[j] / ww) * 4194304.0); out = clip to 0..255 of ((1 << 21) + sum_j in[lo + j] * k[j]) >> 22, the sum in int32
+ * (Pillow's precompute_coeffs with the bilinear filter and normalize_coeffs_8bpc; the tables are made on the device).
+ * PASS ORDER: the horizontal pass (Ws -> Wo) runs first and stores BYTES, the vertical pass runs on those bytes -- always.  A pass whose
+ * input and output lengths are equal is skipped, not run with unit weights; with both skipped the call is the layout conversion and the
+ * division alone.  The horizontal pass touches only the source rows that a vertical tap reads.  Horizontal-first is the classic Pillow
+ * order; Pillow 12.2.0 was seen to run the vertical pass first on some tall and narrow shapes (1023 x 3 -> 8 x 8, 4000 x 6 -> 4 x 4) and
+ * then differs from this entry point by one level, while it agrees bit for bit on 2160 x 3840 -> 8 x 8, 1080 x 1920 -> 12 x 12,
+ * 777 x 1333 -> 8 x 16, 257 x 255 -> 256 x 256 and small shapes of every kind (tests/ingest_cases.py).
+ * The source is read through aligned 32-bit loads: up to three bytes in front of a row and behind it are fetched (bytes of an aligned word
+ * that also holds a byte of the row) and never used.
+ * Refused: a NULL pointer, a side below 1 or above 65535, pix_bytes not in {1, 3, 4}, an unknown order, row_bytes < Ws * pix_bytes,
+ * plane < Ho * Wo, a workspace below dawn_image_ingest_workspace_bytes (the message states both sizes), out3 overlapping the workspace. */
+enum { DAWN_PIXELS_RGB = 0, DAWN_PIXELS_BGR = 1 };
+/* host code: both coefficient tables with their (lo, taps) pairs and the byte image between the two passes, each piece rounded up to 256
+ * bytes and sized whether or not its pass runs, so that the size grows with every argument; 0 for a side outside 1 .. 65535 */
+size_t dawn_image_ingest_workspace_bytes(int Hs, int Ws, int Ho, int Wo);
+int dawn_image_ingest(const unsigned char* src, int Hs, int Ws, long row_bytes, int pix_bytes, int order, int Ho, int Wo, float* out3,
+                      long plane, void* workspace, size_t workspace_bytes, void* stream);
+/* UVG:226, 451-452 (soundfile.read, then speech[:, 0]): out[i] = (float)pcm[i * channels] / 32768.0f for i < n_frames -- channel 0 of
+ * interleaved 16-bit PCM with soundfile's int16 scaling, exact in fp32.  pcm needs 2-byte alignment only.  Refused: a NULL or odd
+ * pointer, n_frames < 1, channels outside 1 .. 8. */
+int dawn_pcm16_to_samples(const int16_t* pcm, long n_frames, int channels, float* out, void* stream);
+/* ---- dawn_generate_clip from decoded media: the two conversions above, then the pipeline.  `gen` is a HOST struct filled as for
+ * dawn_generate_clip; with `image` set its img3 is ignored and the image is ingested to (3, gen->H, gen->H); with `pcm` set its samples /
+ * n_samples are ignored and channel 0 of the n_frames PCM frames is the audio (T above what n_frames yields is refused exactly as there).
+ * A NULL image / pcm keeps gen->img3 / gen->samples; with both NULL the call IS dawn_generate_clip.  The workspace holds, in front of
+ * what dawn_generate_bytes asks for, img3 (3 H H floats), the fp32 samples and the ingest workspace -- each rounded up to 256 bytes and
+ * only for the input that is given: dawn_generate_media_bytes is dawn_generate_bytes plus those pieces.  Everything is checked before the
+ * first launch: what dawn_generate_clip, dawn_image_ingest and dawn_pcm16_to_samples refuse is refused here, under this entry's name. */
+typedef struct dawn_media_args {
+    const dawn_generate_args* gen;     /* HOST; its img3 / samples / n_samples are ignored when the fields below replace them */
+    const unsigned char* image; int Hs, Ws; long row_bytes; int pix_bytes, order;   /* NULL image: gen->img3 is used */
+    const int16_t* pcm; long n_frames; int channels;                                /* NULL pcm: gen->samples is used */
+} dawn_media_args;
+int dawn_generate_media_bytes(const dawn_media_args* args, size_t* clip_bytes, size_t* workspace_bytes);
+int dawn_generate_clip_media(const dawn_media_args* args, void* workspace, size_t workspace_bytes, void* stream);
 /* after a stream synchronise: (kind, algorithmic flops, algorithmic bytes, ms) per conv launch recorded under
  * DAWN_OPT_PROFILE; kind 0 = split 3x3, 1 = split 1x1, 2 = fp32 MFMA; returns the number of entries (and clears them) */
 int dawn_ctx_profile_read(dawn_ctx* ctx, double* out4, int max_entries);
