@@ -181,6 +181,13 @@ SIGNATURES = {
     "dawn_pcm16_to_samples": [c_f, _l, _i, c_f, c_f],
     "dawn_generate_media_bytes": [c_f, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)],
     "dawn_generate_clip_media": [c_f, c_f, C.c_size_t, c_f],
+    # audio at any sample rate (csrc/audio_resample.hip) and the pipeline from PCM at that rate (csrc/dawn_inputs.hip)
+    "dawn_resample16k_len": [_l, _i],
+    "dawn_resample16k_workspace_bytes": [_i],
+    "dawn_resample16k_pcm16": [c_f, _l, _i, _i, c_f, _l, c_f, C.c_size_t, c_f],
+    "dawn_resample16k_f32": [c_f, _l, _i, c_f, _l, c_f, C.c_size_t, c_f],
+    "dawn_generate_media_rate_bytes": [c_f, _i, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)],
+    "dawn_generate_clip_media_rate": [c_f, _i, c_f, C.c_size_t, c_f],
 }
 # device helpers of the C-side evaluator (csrc/dawn_ctx.hip calls them; from Python only the op tests do)
 CTX_HELPER_SIGNATURES = {
@@ -216,7 +223,8 @@ class DawnHipError(RuntimeError):
 LONG_RESULT = {"dawn_sla_ws_floats", "dawn_workspace_bytes_guided", "dawn_decoder_skip_bytes", "dawn_decoder_workspace_bytes",
                "dawn_hubert_conv_frames", "dawn_hubert_workspace_bytes", "dawn_pbnet_workspace_bytes",
                "dawn_pose_blink_workspace_bytes", "dawn_clip_bytes", "dawn_workspace_bytes",
-               "dawn_workspace_bytes_sharded", "dawn_image_ingest_workspace_bytes"}          # entry points that return a size (long), not a status
+               "dawn_workspace_bytes_sharded", "dawn_image_ingest_workspace_bytes", "dawn_resample16k_len",
+               "dawn_resample16k_workspace_bytes"}        # entry points that return a size (long), not a status
 
 
 def lib() -> C.CDLL:

@@ -1,10 +1,12 @@
 // C-side host of the clip-input stage (include/dawn_hip.h: dawn_inputs_*, dawn_clip_inputs) and of the one-call pipeline that
 // chains the five stage hosts (dawn_generate_bytes, dawn_generate_clip; from decoded media, with the two conversions of
-// media_ingest.hip in front: dawn_generate_media_bytes, dawn_generate_clip_media).  Same contract as the other four: opaque handle, device
+// media_ingest.hip in front: dawn_generate_media_bytes, dawn_generate_clip_media; with PCM at any sample rate, through the resampler of
+// audio_resample.hip: dawn_generate_media_rate_bytes, dawn_generate_clip_media_rate).  Same contract as the other four: opaque handle, device
 // pointers by name, every launch on the caller's stream, no allocation, no synchronisation, errors by return code + dawn_last_error
 // with nothing launched.  The pipeline calls nothing but the public entry points of the stages.
 #include "clip_inputs.h"
 #include "media_ingest.h"
+#include "audio_resample.h"
 
 #include <math.h>
 #include <stddef.h>
@@ -258,21 +260,36 @@ int run_pipeline(const dawn_generate_args& a, const Plan& p, void* workspace, si
 struct MediaPlan {
     dawn_generate_args gen;                 // the caller's, with img3 / samples / n_samples replaced where media are given
     Plan plan;
-    size_t img3, samples, ingest, ingest_bytes, front;      // offsets; front = where the pipeline's own workspace starts
+    size_t img3, samples, ingest, ingest_bytes, table, table_bytes, front;      // offsets; front = where the pipeline's own workspace starts
+    long n_out;                             // the 16 kHz samples the PCM yields (= n_frames at 16 kHz)
 };
 
-int make_media_plan(const dawn_media_args* m, const char* who, MediaPlan& q) {
+// pcm_rate = the sample rate of m->pcm; 16000: the PCM is converted as it is and the plan is dawn_generate_clip_media's, byte for byte
+int make_media_plan(const dawn_media_args* m, int pcm_rate, const char* who, MediaPlan& q) {
     if (!m || !m->gen) return refuse(-321, who, "NULL args or NULL gen");
+    if (!m->pcm && pcm_rate != 16000) {
+        char e[160];
+        snprintf(e, sizeof e, "pcm is NULL with pcm_rate = %d: gen->samples are 16 kHz samples, only PCM is resampled", pcm_rate);
+        return refuse(-321, who, e);
+    }
     q.gen = *m->gen;
     dawn_generate_args& g = q.gen;
     if (!m->image && !g.img3) return refuse(-321, who, "image is NULL and so is gen->img3: one of the two is the source image");
     if (!m->pcm && !g.samples) return refuse(-321, who, "pcm is NULL and so is gen->samples: one of the two is the audio");
     // placeholders that only have to be non-NULL until the workspace is known: no check below reads through them
     static const float dummy_f = 0.0f;
+    q.n_out = 0;
+    q.table_bytes = 0;
     if (m->pcm) {
-        CK(media_pcm_check(m->pcm, m->n_frames, m->channels, &dummy_f, who));
+        if (pcm_rate == 16000) {
+            CK(media_pcm_check(m->pcm, m->n_frames, m->channels, &dummy_f, who));
+            q.n_out = m->n_frames;
+        } else {
+            CK(resample_pcm_check(m->pcm, m->n_frames, m->channels, pcm_rate, &q.n_out, who));
+            q.table_bytes = dawn_resample16k_workspace_bytes(pcm_rate);
+        }
         g.samples = &dummy_f;
-        g.n_samples = m->n_frames;
+        g.n_samples = q.n_out;
     }
     if (m->image) g.img3 = &dummy_f;
     CK(make_plan(&g, who, q.plan));
@@ -285,8 +302,9 @@ int make_media_plan(const dawn_media_args* m, const char* who, MediaPlan& q) {
         q.ingest_bytes = dawn_image_ingest_workspace_bytes(m->Hs, m->Ws, g.H, g.H);
     }
     q.img3 = take(m->image ? (size_t)3 * g.H * g.H * 4 : 0);
-    q.samples = take(m->pcm ? (size_t)m->n_frames * 4 : 0);
+    q.samples = take(m->pcm ? (size_t)q.n_out * 4 : 0);
     q.ingest = take(q.ingest_bytes);
+    q.table = take(q.table_bytes);
     q.front = o;
     return 0;
 }
@@ -303,24 +321,25 @@ extern "C" int dawn_generate_clip(const dawn_generate_args* args, void* workspac
     return run_pipeline(*args, p, workspace, workspace_bytes, stream, who, [] { return 0; });
 }
 
-extern "C" int dawn_generate_media_bytes(const dawn_media_args* args, size_t* clip_bytes, size_t* workspace_bytes) {
+namespace {
+
+int media_bytes(const dawn_media_args* args, int pcm_rate, size_t* clip_bytes, size_t* workspace_bytes, const char* who) {
     MediaPlan q;
-    CK(make_media_plan(args, "dawn_generate_media_bytes", q));
+    CK(make_media_plan(args, pcm_rate, who, q));
     if (clip_bytes) *clip_bytes = q.plan.frames_bytes;
     if (workspace_bytes) *workspace_bytes = q.front + q.plan.total;
     return 0;
 }
 
-extern "C" int dawn_generate_clip_media(const dawn_media_args* args, void* workspace, size_t workspace_bytes, void* stream) {
-    const char* who = "dawn_generate_clip_media";
+int clip_media(const dawn_media_args* args, int pcm_rate, void* workspace, size_t workspace_bytes, void* stream, const char* who,
+               const char* sizer) {
     MediaPlan q;
-    CK(make_media_plan(args, who, q));
+    CK(make_media_plan(args, pcm_rate, who, q));
     const dawn_media_args& m = *args;
     dawn_generate_args& g = q.gen;
     if (!g.frames_out) return refuse(-301, who, "NULL frames_out");
     const size_t total = q.front + q.plan.total;
-    if (!workspace || workspace_bytes < total)
-        return refuse_workspace(-305, who, workspace ? workspace_bytes : 0, total, "dawn_generate_media_bytes");
+    if (!workspace || workspace_bytes < total) return refuse_workspace(-305, who, workspace ? workspace_bytes : 0, total, sizer);
     char* ws = (char*)workspace;
     float* img3 = (float*)(ws + q.img3);
     float* samples = (float*)(ws + q.samples);
@@ -336,7 +355,28 @@ extern "C" int dawn_generate_clip_media(const dawn_media_args* args, void* works
         if (m.image)
             CK(dawn_image_ingest(m.image, m.Hs, m.Ws, m.row_bytes, m.pix_bytes, m.order, g.H, g.H, img3, HH, ws + q.ingest, q.ingest_bytes,
                                  stream));
-        if (m.pcm) CK(dawn_pcm16_to_samples(m.pcm, m.n_frames, m.channels, samples, stream));
+        if (m.pcm && pcm_rate == 16000) CK(dawn_pcm16_to_samples(m.pcm, m.n_frames, m.channels, samples, stream));
+        if (m.pcm && pcm_rate != 16000)
+            CK(dawn_resample16k_pcm16(m.pcm, m.n_frames, m.channels, pcm_rate, samples, q.n_out, ws + q.table, q.table_bytes, stream));
         return 0;
     });
+}
+
+}  // namespace
+
+extern "C" int dawn_generate_media_bytes(const dawn_media_args* args, size_t* clip_bytes, size_t* workspace_bytes) {
+    return media_bytes(args, 16000, clip_bytes, workspace_bytes, "dawn_generate_media_bytes");
+}
+
+extern "C" int dawn_generate_clip_media(const dawn_media_args* args, void* workspace, size_t workspace_bytes, void* stream) {
+    return clip_media(args, 16000, workspace, workspace_bytes, stream, "dawn_generate_clip_media", "dawn_generate_media_bytes");
+}
+
+extern "C" int dawn_generate_media_rate_bytes(const dawn_media_args* args, int pcm_rate, size_t* clip_bytes, size_t* workspace_bytes) {
+    return media_bytes(args, pcm_rate, clip_bytes, workspace_bytes, "dawn_generate_media_rate_bytes");
+}
+
+extern "C" int dawn_generate_clip_media_rate(const dawn_media_args* args, int pcm_rate, void* workspace, size_t workspace_bytes,
+                                             void* stream) {
+    return clip_media(args, pcm_rate, workspace, workspace_bytes, stream, "dawn_generate_clip_media_rate", "dawn_generate_media_rate_bytes");
 }

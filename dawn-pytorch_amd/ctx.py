@@ -988,11 +988,15 @@ class PipelineEvaluator:
         return out
 
     # ---- the same from decoded media (dawn_generate_media_bytes / dawn_generate_clip_media)
-    def from_media(self, a: GenerateArgs, image: Optional[Tensor] = None, pcm: Optional[Tensor] = None, order: str = "rgb") -> MediaArgs:
+    def from_media(self, a: GenerateArgs, image: Optional[Tensor] = None, pcm: Optional[Tensor] = None, order: str = "rgb",
+                   pcm_rate: int = 16000) -> MediaArgs:
         """`a` = the struct of `args(...)` (its img / samples are placeholders for whatever is given here) -> the dawn_media_args that
         replaces them: image = uint8 GPU tensor (Hs, Ws, C) or (Hs, Ws) with unit pixel and channel strides and any row stride, C in
-        {1, 3, 4}; pcm = int16 GPU tensor (n_frames, channels) or (n_frames,), contiguous.  None keeps the input of `a`."""
+        {1, 3, 4}; pcm = int16 GPU tensor (n_frames, channels) or (n_frames,), contiguous.  None keeps the input of `a`.
+        pcm_rate = the sample rate of `pcm` (the struct has no field for it: it is kept beside it, and `media_sizes` / `generate_media`
+        hand it to the *_rate entry points; 16000 = the entry points without a rate)."""
         m = MediaArgs()
+        m._pcm_rate = int(pcm_rate)
         m.gen = C.pointer(a)
         keep = [a]
         if image is not None:
@@ -1014,18 +1018,29 @@ class PipelineEvaluator:
         m._keep = keep
         return m
 
-    def media_sizes(self, m: MediaArgs):
-        """(bytes of the frames, bytes of the workspace) of dawn_generate_media_bytes."""
+    @staticmethod
+    def _rate_of(m: MediaArgs, pcm_rate: Optional[int]) -> int:
+        return int(getattr(m, "_pcm_rate", 16000) if pcm_rate is None else pcm_rate)
+
+    def media_sizes(self, m: MediaArgs, pcm_rate: Optional[int] = None):
+        """(bytes of the frames, bytes of the workspace) of dawn_generate_media_bytes -- of dawn_generate_media_rate_bytes where the PCM is
+        not at 16 kHz.  pcm_rate None: the rate `from_media` was given (16000 unless stated)."""
         cb, wb = C.c_size_t(0), C.c_size_t(0)
-        check(self.L.dawn_generate_media_bytes(C.addressof(m), C.byref(cb), C.byref(wb)), "dawn_generate_media_bytes")
+        rate = self._rate_of(m, pcm_rate)
+        if rate == 16000:
+            check(self.L.dawn_generate_media_bytes(C.addressof(m), C.byref(cb), C.byref(wb)), "dawn_generate_media_bytes")
+        else:
+            check(self.L.dawn_generate_media_rate_bytes(C.addressof(m), rate, C.byref(cb), C.byref(wb)), "dawn_generate_media_rate_bytes")
         return int(cb.value), int(wb.value)
 
     def generate_media(self, m: MediaArgs, want_latent: bool = False, want_cond: bool = False, workspace: Optional[Tensor] = None,
-                       frames: Optional[Tensor] = None) -> dict:
-        """`generate` through dawn_generate_clip_media on the struct of `from_media(...)`: the same outputs."""
+                       frames: Optional[Tensor] = None, pcm_rate: Optional[int] = None) -> dict:
+        """`generate` through dawn_generate_clip_media on the struct of `from_media(...)`: the same outputs.  With PCM at another rate
+        than 16 kHz (pcm_rate None: the rate `from_media` was given) through dawn_generate_clip_media_rate, which resamples it first."""
         hub, pose, blink, dec, inp, unet = self.ev
         a = m.gen.contents
-        cb, wb = self.media_sizes(m)
+        rate = self._rate_of(m, pcm_rate)
+        cb, wb = self.media_sizes(m, rate)
         T, H, h = int(a.T), int(a.H), int(a.H) // 4
         if frames is None:
             frames = torch.empty((T, H * H * 3 // 2) if a.format == FRAMES_YUV420 else (T, H, H, 3), dtype=torch.uint8, device=self.device)
@@ -1040,12 +1055,16 @@ class PipelineEvaluator:
             out["cond"] = torch.empty(T, inp.cfg.n_aud + inp.cfg.pose_dim + 2, device=self.device)
             a.cond_out = out["cond"].data_ptr()
         if want_latent or want_cond:
-            cb, wb = self.media_sizes(m)
+            cb, wb = self.media_sizes(m, rate)
         if workspace is None:
             if self._ws is None or self._ws.numel() < wb:
                 self._ws = None
                 self._ws = torch.empty(wb, dtype=torch.uint8, device=self.device)
             workspace = self._ws
-        check(self.L.dawn_generate_clip_media(C.addressof(m), workspace.data_ptr(), workspace.numel(), _Evaluator._stream()),
-              "dawn_generate_clip_media")
+        if rate == 16000:
+            check(self.L.dawn_generate_clip_media(C.addressof(m), workspace.data_ptr(), workspace.numel(), _Evaluator._stream()),
+                  "dawn_generate_clip_media")
+        else:
+            check(self.L.dawn_generate_clip_media_rate(C.addressof(m), rate, workspace.data_ptr(), workspace.numel(), _Evaluator._stream()),
+                  "dawn_generate_clip_media_rate")
         return out

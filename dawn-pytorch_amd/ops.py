@@ -1012,3 +1012,25 @@ class HipOps:
         out = self.empty(n, like=pcm_i16)
         check(self.L.dawn_pcm16_to_samples(_p(pcm_i16), n, ch, _p(out), self._stream()), "dawn_pcm16_to_samples")
         return out
+
+    # ------------------------------------------------------------------ audio at any sample rate (csrc/audio_resample.hip)
+    def resample_to_16k(self, x: Tensor, rate: int, out: Optional[Tensor] = None) -> Tensor:
+        """Samples at `rate` (1000 .. 384000 Hz) -> fp32 samples at 16 kHz (n_out,), n_out = floor(n * 16000 / rate), by the windowed-sinc
+        resampler that include/dawn_hip.h defines (its values are that definition's, not ffmpeg's).  x = interleaved 16-bit PCM (n, channels)
+        or (n,) int16 -- channel 0 is taken -- or fp32 (n,), contiguous.  rate 16000 is `pcm16_to_samples` / a copy."""
+        _need(x.is_cuda and x.is_contiguous() and ((x.dtype == torch.int16 and x.dim() in (1, 2)) or (x.dtype == torch.float32 and x.dim() == 1)),
+              "resample_to_16k: a contiguous GPU tensor, int16 (n[, channels]) or fp32 (n,)")
+        n, ch, rate = int(x.shape[0]), 1 if x.dim() == 1 else int(x.shape[1]), int(rate)
+        n_out = int(self.L.dawn_resample16k_len(n, rate))
+        _need(n_out >= 1, f"resample_to_16k: n = {n} frames at rate = {rate} yield no output (rate 1000 .. 384000, n_out = floor(n * 16000 / rate) >= 1)")
+        self._require(out)
+        if out is None:
+            out = self.empty(n_out, like=x)
+        _need(out.dtype == torch.float32 and tuple(out.shape) == (n_out,) and out.is_contiguous(), f"resample_to_16k: out fp32 ({n_out},) contiguous")
+        nbytes = int(self.L.dawn_resample16k_workspace_bytes(rate))
+        ws = self.empty(max(nbytes, 8), like=x, dtype=torch.uint8)
+        if x.dtype == torch.int16:
+            check(self.L.dawn_resample16k_pcm16(_p(x), n, ch, rate, _p(out), n_out, _p(ws), nbytes, self._stream()), "dawn_resample16k_pcm16")
+        else:
+            check(self.L.dawn_resample16k_f32(_p(x), n, rate, _p(out), n_out, _p(ws), nbytes, self._stream()), "dawn_resample16k_f32")
+        return out

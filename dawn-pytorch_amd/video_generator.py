@@ -49,11 +49,12 @@ class _LastOutput(dict):
 
 class VideoGenerator:
     image_via_c = False               # (class default: the opt-in of __init__'s keyword)
+    audio_via_c = False               # (likewise)
 
     def __init__(self, args, *, generator=None, frontend=None, config: Optional[dict] = None, device=None,
                  allow_random_weights: bool = False, deterministic: bool = True, hubert=None, pbnet=None,
                  video_egress: str = "png", encoder_cmd=None, pbnet_via_c: bool = False, inputs_via_c: bool = False,
-                 image_via_c: bool = False):
+                 image_via_c: bool = False, audio_via_c: bool = False):
         """`allow_random_weights`: explicit opt-in (benches, tests) to run with the deterministic random-init denoiser
         when the configured checkpoint is absent; without it a missing checkpoint raises, as the reference's
         `torch.load` does (UVG:527).  `deterministic`: seed the sampler's counter-based noise with the config's
@@ -72,7 +73,11 @@ class VideoGenerator:
         `image_via_c` (GPU only): the decoded source image goes to the device as bytes and dawn_image_ingest resizes and scales it there
         (Pillow's 8-bit bilinear resample restated in integers: the same bytes as the host resize, and from there the same
         arithmetic as the default path, so the same frames); with `hubert` set, a 16 kHz 16-bit
-        PCM file's frames go to the device as int16 and dawn_pcm16_to_samples makes the fp32 samples (the same values)."""
+        PCM file's frames go to the device as int16 and dawn_pcm16_to_samples makes the fp32 samples (the same values).
+        `audio_via_c`: with `hubert` set, a 16-bit PCM WAV of any sample rate from 1000 to 384000 Hz never touches ffmpeg: on the GPU its
+        frames go to the device as int16 and dawn_resample16k_pcm16 makes the 16 kHz samples, on a CPU device audio.resample_to_16k does
+        (the same definition in numpy fp64).  The values are that definition's (include/dawn_hip.h), not ffmpeg's; nobody has measured
+        the difference at the HuBERT features.  Any other file takes the default path."""
         if video_egress not in ("png", "yuv420p"):
             raise ValueError(f"video_egress must be 'png' or 'yuv420p', not {video_egress!r}")
         self.video_egress = video_egress
@@ -81,7 +86,8 @@ class VideoGenerator:
         self.pbnet_via_c = bool(pbnet_via_c)
         self.inputs_via_c = bool(inputs_via_c)
         self.image_via_c = bool(image_via_c)
-        self.pbnet = pbnet                # (pose, blink) pbnet.PoseBlinkGenerator pair: stage 3 (generate_pose_blink, UVG:252-302; N4)
+        self.audio_via_c = bool(audio_via_c)
+        self.pbnet = pbnet               # (pose, blink) pbnet.PoseBlinkGenerator pair: stage 3 (generate_pose_blink, UVG:252-302; N4)
         self.allow_random_weights = bool(allow_random_weights) or bool(getattr(args, "allow_random_weights", False))
         self.deterministic = deterministic
         self.audio_path = args.audio_path
@@ -139,14 +145,31 @@ class VideoGenerator:
         `target_audio.npy`.  Otherwise it is delegated to `frontend` / the cache like the other upstream stages."""
         if self.hubert is None or not (self.audio_path and osp.exists(self.audio_path)):
             return self._front("process_audio")
-        pcm = read_pcm16_16k(self.audio_path) if self.image_via_c and self.device.type == "cuda" else None
-        if pcm is not None:
+        any_rate = self._pcm_any_rate() if self.audio_via_c else None
+        pcm = read_pcm16_16k(self.audio_path) if any_rate is None and self.image_via_c and self.device.type == "cuda" else None
+        if any_rate is not None:
+            frames, rate = any_rate
+            if self.device.type == "cuda":
+                speech = self.video_model.unet._ops().resample_to_16k(torch.from_numpy(frames).to(self.device), rate)
+            else:
+                from .audio import resample_to_16k
+                speech = resample_to_16k(frames, rate)
+        elif pcm is not None:
             speech = self.video_model.unet._ops().pcm16_to_samples(torch.from_numpy(pcm).to(self.device))
         else:
             speech = load_wav_16k(self.audio_path)
         feats = self.hubert.process_audio(speech)
         print(f'Frame count: {feats.shape[0]}')
         np.save(self.audio_emb_path, feats)
+
+    def _pcm_any_rate(self):
+        """(int16 frames (n, channels), rate) of the audio file where `audio_via_c` takes it -- 16-bit PCM, a rate the resampler takes, at
+        least one 16 kHz sample -- else None."""
+        from .audio import MAX_RATE, MIN_RATE, read_pcm16, resample_len
+        got = read_pcm16(self.audio_path)
+        if got is None or not MIN_RATE <= got[1] <= MAX_RATE or resample_len(got[0].shape[0], got[1]) < 1:
+            return None
+        return got
 
     def generate_pose_blink(self):
         """UVG:252-302.  With a (pose, blink) pair of `pbnet.PoseBlinkGenerator` (built from the decoders of the reference's own

@@ -967,6 +967,38 @@ typedef struct dawn_media_args {
 } dawn_media_args;
 int dawn_generate_media_bytes(const dawn_media_args* args, size_t* clip_bytes, size_t* workspace_bytes);
 int dawn_generate_clip_media(const dawn_media_args* args, void* workspace, size_t workspace_bytes, void* stream);
+/* ---- audio at any sample rate (csrc/audio_resample.hip): resample to the 16 kHz mono fp32 samples that the HuBERT stage takes.  It stands
+ * where the reference runs `ffmpeg -ar 16000` (UVG:223, 416-431), but its values are THIS definition's, not ffmpeg's: swresample's output
+ * depends on build and version, bit parity with it is not a goal, and nobody has measured what the difference does to the HuBERT features.
+ * Contract as the media ingest above (every launch on `stream`, no allocation, no synchronisation, everything checked before the first launch).
+ * Z = 32 (zero crossings per side), BETA = 9.0 (Kaiser), CUT = 0.92.  For an integer `rate`, 1000 <= rate <= 384000, rate != 16000:
+ *   g = gcd(16000, rate); L = 16000 / g; M = rate / g; n_out = floor(n_frames * 16000 / rate) in 64-bit integers (n_out < 1 is refused)
+ *   rho = 1 if rate <= 16000, else 16000.0 / rate; W = Z / rho is the half width in input samples (fp64); K = ceil(W)
+ *   h(u) = rho * CUT * sinc(rho * CUT * u) * I0(BETA * sqrt(1 - (u / W)^2)) / I0(BETA) for |u| < W, and 0 otherwise
+ *   sinc(t) = sin(pi t) / (pi t), sinc(0) = 1; I0(x) = sum_k ((x / 2)^k / k!)^2, summed until a term falls below 2^-60 of the sum
+ *   coef[r][j + K] = h(r / L - j) for r = 0 .. L - 1, j = -K .. K: L rows of 2 K + 1 fp64 values, made on the device in the workspace
+ *   for output i: (q, r) = divmod(i * M, L) in 64-bit integers; y[i] = sum_{j = -K .. K} x[q + j] * coef[r][j + K], j ascending
+ * with x[k] = 0 outside 0 <= k < n_frames, x exact (channel 0 of the PCM / 32768, or the fp32 sample), the sum in fp64 and ONE rounding to
+ * fp32; no clipping, |y| may exceed 1.  The position q + r / L is never formed as one floating-point number.  Bit-identical run to run.
+ * rate == 16000 is not filtered: the PCM entry is dawn_pcm16_to_samples bit for bit, the fp32 entry a copy, and no workspace is needed
+ * (it may be NULL; dawn_resample16k_workspace_bytes(16000) = 0).  The PCM pointer needs 2-byte alignment only; x and out 4-byte, the
+ * workspace 8-byte.  n_frames is at most 2^34.
+ * Refused, with a message that names the argument and nothing launched: a NULL or misaligned pointer, channels outside 1 .. 8, rate outside
+ * 1000 .. 384000, n_frames < 1, n_out != dawn_resample16k_len(n_frames, rate) (the message states both), n_out < 1, a workspace below
+ * dawn_resample16k_workspace_bytes(rate) (the message states both sizes), out overlapping the workspace. */
+long dawn_resample16k_len(long n_frames, int rate);            /* host: n_out; 0 where the call would be refused */
+size_t dawn_resample16k_workspace_bytes(int rate);             /* host: the table, rounded up to 256 bytes; 0 for a rate outside the range (and for 16000) */
+int dawn_resample16k_pcm16(const int16_t* pcm, long n_frames, int channels, int rate, float* out, long n_out, void* workspace,
+                           size_t workspace_bytes, void* stream);
+int dawn_resample16k_f32(const float* x, long n_frames, int rate, float* out, long n_out, void* workspace, size_t workspace_bytes,
+                         void* stream);
+/* dawn_generate_clip_media with PCM at `pcm_rate`: the PCM goes through dawn_resample16k_pcm16, whose n_out samples and table are carved
+ * from the front of the workspace with the other pieces (dawn_generate_media_rate_bytes counts them); "T above what the audio yields" is
+ * judged on n_out.  pcm_rate == 16000 IS dawn_generate_clip_media: the same launches, the same bits, the same sizes.  A NULL pcm with
+ * pcm_rate != 16000 is refused (gen->samples are 16 kHz samples already); what dawn_resample16k_pcm16 refuses is refused here, under this
+ * entry's name, before the first launch.  The rate is a parameter, not a field: dawn_media_args is unchanged. */
+int dawn_generate_media_rate_bytes(const dawn_media_args* args, int pcm_rate, size_t* clip_bytes, size_t* workspace_bytes);
+int dawn_generate_clip_media_rate(const dawn_media_args* args, int pcm_rate, void* workspace, size_t workspace_bytes, void* stream);
 /* after a stream synchronise: (kind, algorithmic flops, algorithmic bytes, ms) per conv launch recorded under
  * DAWN_OPT_PROFILE; kind 0 = split 3x3, 1 = split 1x1, 2 = fp32 MFMA; returns the number of entries (and clears them) */
 int dawn_ctx_profile_read(dawn_ctx* ctx, double* out4, int max_entries);
