@@ -27,11 +27,16 @@
 //     (block rt, g); the n-block's columns are features 16 (n >> 3) + 8 mb + (n & 7), so that O^T's accumulators (m = 4 g + r of
 //     m-block mb) are, as slot 4 mb + r of k-group g, d = 16 (g >> 1) + 8 mb + 4 (g & 1) + r: exactly the 16-byte piece
 //     (chunk g >> 1, k-half g & 1) of pack.pack_bf3_temporal_out's image -- the images of the 32 x 32 kernel are reused as they are.
-// LDS (FA = 208 row slots: a multiple of 16, so that the four k-groups of a fragment read fall on disjoint banks):
+// LDS (offsets: temporal_layer16.h; every access site priced with the per-instruction bank model by tools/tl16_lds_banks.cpp, the model
+// checked against SQ_LDS_BANK_CONFLICT in profiles/temporal_layer_lds_vmem.md).  FA = 208 row slots: a multiple of 16, so that a plane is
+// a multiple of 256 B and the k-groups a ds_read_b128 lane group mixes ({0-3, 12-15} of one, {4-11} of the next) fall on disjoint banks:
 //   X planes [3][8 channel octets][FA] x 16 B = 79,872; K planes [3][4 k-groups][FA] x 16 B = 39,936;
-//   V^T [3][2 m-blocks][64 lanes][13 blocks] x 8 B = 39,936 (a lane's blocks are contiguous: ONE ds_read2_b64 fetches the A fragment
-//   [block b | block b + 1] for either parity of b); the head's bias table in 4 shifted copies (16-byte aligned reads for every query
-//   column) 2,112: 161,856 B.
+//   V^T [3][2 m-blocks][64 lanes][13 blocks] x 8 B = 39,936: the A fragment [block b | block b + 1] is TWO ds_read_b64 (lds_read8 below: a
+//   lane stride of 104 B = 26 banks covers the 64 banks of a 32-lane group exactly once; as one ds_read2_b64 the same bytes take twice
+//   the LDS cycles); the head's bias table in 4 shifted copies (16-byte aligned reads for every query column), 112 floats apart, in
+//   2,112: 161,856 B.
+//   Known and left (measured, same file): the phase-0 stores of the X planes are 8-way (one row per 16 lanes = eight octets' pieces a
+//   plane apart), the K-plane stores 2-way (16 rows x 8 B at a stride of 16 B).
 #include "dawn_common.h"
 #include "../../include/dawn_hip.h"
 #include "temporal_layer16.h"
@@ -56,14 +61,23 @@ constexpr int NB = FA / 16;                   // 16-key blocks
 constexpr int NKB = TL16_KEY_BLOCKS;          // key blocks per query tile
 constexpr float NEG = -1.0e30f;
 constexpr float LOG2E = 1.4426950408889634f;
-constexpr int XP_BYTES = 3 * 8 * FA * 16;
-constexpr int KP_BYTES = 3 * 4 * FA * 16;
-constexpr int VP_BYTES = 3 * NB * 2 * 512;
-constexpr int BLD = 132;                     // floats between the shifted bias-table copies: +4 banks per copy (the four lanes of a
-                                            // query quad read four copies: 4-way conflicts at a stride of 128)
-constexpr int BAND_BYTES = 4 * BLD * 4;
+constexpr int XP_BYTES = TL16_X_BYTES;
+constexpr int KP_BYTES = TL16_K_BYTES;
+constexpr int VP_BYTES = TL16_V_BYTES;
+constexpr int BLD = TL16_BAND_STRIDE;        // floats between the shifted bias-table copies (temporal_layer16.h: conflict-free float4 reads)
+constexpr int BAND_BYTES = TL16_BAND_BYTES;
 constexpr int LDS_BYTES = XP_BYTES + KP_BYTES + VP_BYTES + BAND_BYTES;
-static_assert(LDS_BYTES == TL16_LDS_BYTES, "LDS layout");
+static_assert(LDS_BYTES == TL16_LDS_BYTES && NB == TL16_BLOCKS, "LDS layout");
+
+// Two 8-byte LDS reads that stay two ds_read_b64 (64 banks, two 32-lane groups: 2 LDS cycles each).  Plain loads of neighbouring blocks
+// are merged into one ds_read2_b64, which is banked mod 32 in 16-lane groups and takes 8 cycles for the same 1 KB: half the rate
+// (tools/tl16_lds_banks.cpp).  Volatile accesses are not merged; the compiler still counts them in its s_waitcnt.
+__device__ __forceinline__ uint2 lds_read8(const unsigned char* p) {
+    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+    // (the LDS address space spelled out: address-space inference leaves volatile accesses through generic pointers as flat loads)
+    const u32x2 v = *(const volatile __attribute__((address_space(3))) u32x2*)p;
+    return uint2{v[0], v[1]};
+}
 
 // The result registers must not be the A / B operand registers.  hipcc (ROCm 7.2) allows that overlap for the 4-register results of
 // the 16 x 16 shapes -- once a fragment's last use is an MFMA whose accumulator starts elsewhere (0, or a value that stays live) it
@@ -108,7 +122,6 @@ __device__ __forceinline__ float rows4_sum(float v) {
     r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
     return __uint_as_float(r[0]) + __uint_as_float(r[1]);
 }
-
 
 template <int NTILE>
 __global__ __launch_bounds__(NT) void temporal_layer16_kernel(
@@ -172,10 +185,10 @@ __global__ __launch_bounds__(NT) void temporal_layer16_kernel(
 #pragma unroll
             for (int e = 0; e < 4; ++e) h3[e] = (__bf16)r[e];
             if (j < FA) {
-                unsigned char* dst = Xp + ((size_t)(sub >> 1) * FA + j) * 16 + (sub & 1) * 8;
+                unsigned char* dst = Xp + tl16_x_off(0, sub >> 1, j, sub & 1);
                 *reinterpret_cast<uint2*>(dst) = __builtin_bit_cast(uint2, h1);
-                *reinterpret_cast<uint2*>(dst + (size_t)8 * FA * 16) = __builtin_bit_cast(uint2, h2);
-                *reinterpret_cast<uint2*>(dst + (size_t)16 * FA * 16) = __builtin_bit_cast(uint2, h3);
+                *reinterpret_cast<uint2*>(dst + tl16_x_off(1, 0, 0, 0)) = __builtin_bit_cast(uint2, h2);
+                *reinterpret_cast<uint2*>(dst + tl16_x_off(2, 0, 0, 0)) = __builtin_bit_cast(uint2, h3);
             }
         }
     }
@@ -235,7 +248,21 @@ __global__ __launch_bounds__(NT) void temporal_layer16_kernel(
     const int kmb = kvc & 1;
     bf16x8 wkv[2][3];          // the K / V group's fragments of the head (6 x 1 KB per wave)
     bf16x8 wq[2][2][3];        // Wq fragments [feature half][k-step][plane]
-    float2 qcs[NTILE][2], qsn[NTILE][2];   // rotary rows of the own query tiles
+    // rotary rows of the own query tiles: they depend on the row and the feature block, not on the head.  With one query tile per wave
+    // they are fetched once, here, and kept, times scale . log2(e) (a reload per head put 8 more loads in front of the next head's weight
+    // fragments).  With two tiles the 16 registers are not there across phase B (252 -> 256 + 4 spilled dwords reloaded every head): that
+    // instantiation keeps the per-head reload.
+    constexpr bool ROT_ONCE = NTILE == 1;
+    constexpr float QSCALE = 0.17677669529663687f * LOG2E;
+    float2 qcs[NTILE][2], qsn[NTILE][2];
+    if constexpr (ROT_ONCE) {
+#pragma unroll
+        for (int mb = 0; mb < 2; ++mb) {
+            const float2 c_ = rot_load(rsc, iqc[0], mb), s_ = rot_load(rss, iqc[0], mb);
+            qcs[0][mb] = float2{c_.x * QSCALE, c_.y * QSCALE};
+            qsn[0][mb] = float2{s_.x * QSCALE, s_.y * QSCALE};
+        }
+    }
     float bandv;                // this thread's entry of the head's bias table
     // (unconditional -- a wave without a group / tile fetches fragments it does not use: a conditional definition would keep the
     //  previous head's registers alive through phase B as the other arm of the merge)
@@ -255,13 +282,15 @@ __global__ __launch_bounds__(NT) void temporal_layer16_kernel(
 #pragma unroll
             for (int pl = 0; pl < 3; ++pl)
                 wkv[s][pl] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rsw, lo, ((12 * s + 2 * pl) * 768 + col0) * 16, 0));
+        if constexpr (!ROT_ONCE) {
 #pragma unroll
-        for (int k = 0; k < NTILE; ++k)
+            for (int k = 0; k < NTILE; ++k)
 #pragma unroll
-            for (int mb = 0; mb < 2; ++mb) {
-                qcs[k][mb] = rot_load(rsc, iqc[k], mb);
-                qsn[k][mb] = rot_load(rss, iqc[k], mb);
-            }
+                for (int mb = 0; mb < 2; ++mb) {
+                    qcs[k][mb] = rot_load(rsc, iqc[k], mb);
+                    qsn[k][mb] = rot_load(rss, iqc[k], mb);
+                }
+        }
         // bias table entry: copy sh = tid >> 7 starts at entry sh; entry e <-> key - query + win = e - 15 (NEG outside the window)
         const int idx = (tid & 127) + (tid >> 7) - 15;
         bandv = band[max(0, min(idx, 2 * win)) * HEADS + hh];
@@ -274,12 +303,12 @@ __global__ __launch_bounds__(NT) void temporal_layer16_kernel(
         const int rc_ = min(row, Fext - 1);
         cs = rot_load(rsc, rc_, kmb);
         sn = rot_load(rss, rc_, kmb);
-        const unsigned char* xr = Xp + ((size_t)g * FA + row) * 16;
+        const unsigned char* xr = Xp + tl16_x_off(0, g, row, 0);
 #pragma unroll
         for (int s = 0; s < 2; ++s)
 #pragma unroll
             for (int pl = 0; pl < 3; ++pl)
-                xf[s][pl] = *reinterpret_cast<const bf16x8*>(xr + (size_t)((pl * 8 + 4 * s) * FA) * 16);
+                xf[s][pl] = *reinterpret_cast<const bf16x8*>(xr + tl16_x_off(pl, 4 * s, 0, 0));
     };
     // NR (1 or 2) 16-row tiles of the group per compute region: 12 MFMAs each, one chain per (tile, k-step); rotary (K), split, planes
     // into LDS
@@ -302,10 +331,10 @@ __global__ __launch_bounds__(NT) void temporal_layer16_kernel(
                                   d[3] * cs[t].y + d[2] * sn[t].y};
                 uint2 p1, p2, p3;
                 dawn_split3_trunc_quad(kr, p1, p2, p3);
-                unsigned char* dst = Kp + ((size_t)g * FA + 16 * (rt + t) + n) * 16 + kmb * 8;
+                unsigned char* dst = Kp + tl16_k_off(0, g, 16 * (rt + t) + n, kmb);
                 *reinterpret_cast<uint2*>(dst) = p1;
-                *reinterpret_cast<uint2*>(dst + (size_t)4 * FA * 16) = p2;
-                *reinterpret_cast<uint2*>(dst + (size_t)8 * FA * 16) = p3;
+                *reinterpret_cast<uint2*>(dst + tl16_k_off(1, 0, 0, 0)) = p2;
+                *reinterpret_cast<uint2*>(dst + tl16_k_off(2, 0, 0, 0)) = p3;
             }
         } else {
 #pragma unroll
@@ -318,10 +347,10 @@ __global__ __launch_bounds__(NT) void temporal_layer16_kernel(
             for (int t = 0; t < NR; ++t) {
                 uint2 p1, p2, p3;
                 dawn_split3_trunc_quad(d2[t][0] + d2[t][1], p1, p2, p3);
-                unsigned char* dst = Vp + ((size_t)(kmb * 64 + lane) * NB + rt + t) * 8;
+                unsigned char* dst = Vp + tl16_v_off(0, kmb, lane, rt + t);
                 *reinterpret_cast<uint2*>(dst) = p1;
-                *reinterpret_cast<uint2*>(dst + (size_t)NB * 2 * 512) = p2;
-                *reinterpret_cast<uint2*>(dst + (size_t)2 * NB * 2 * 512) = p3;
+                *reinterpret_cast<uint2*>(dst + tl16_v_off(1, 0, 0, 0)) = p2;
+                *reinterpret_cast<uint2*>(dst + tl16_v_off(2, 0, 0, 0)) = p3;
             }
         }
     };
@@ -346,16 +375,16 @@ __global__ __launch_bounds__(NT) void temporal_layer16_kernel(
         // ---- phase A.  LOAD region: the head's bias table (log2 units; NEG outside the window: the lookup is the window mask; a lane
         // reads float4 at copy[(15 - n) & 3][((15 - n) & ~3) + 4 g + 16 b] = entries 15 - n + 4 g + 16 b + r), the X fragments of the
         // own query rows and of the group's first row tile
-        band4[(tid >> 7) * BLD + (tid & 127)] = bok ? bandv * LOG2E : NEG;
+        if ((tid & 127) < BLD) band4[tl16_band_idx(tid >> 7, tid & 127)] = bok ? bandv * LOG2E : NEG;
         bf16x8 xfq[NTILE][2][3];
 #pragma unroll
         for (int k = 0; k < NTILE; ++k) {
-            const unsigned char* xr = Xp + ((size_t)g * FA + iqc[k]) * 16;
+            const unsigned char* xr = Xp + tl16_x_off(0, g, iqc[k], 0);
 #pragma unroll
             for (int s = 0; s < 2; ++s)
 #pragma unroll
                 for (int pl = 0; pl < 3; ++pl)
-                    xfq[k][s][pl] = *reinterpret_cast<const bf16x8*>(xr + (size_t)((pl * 8 + 4 * s) * FA) * 16);
+                    xfq[k][s][pl] = *reinterpret_cast<const bf16x8*>(xr + tl16_x_off(pl, 4 * s, 0, 0));
         }
         bf16x8 xfa[2][2][3], xfb[2][2][3];                          // two pairs of row tiles: one being multiplied, one in flight
         float2 csa[2], sna[2], csb[2], snb[2];
@@ -383,7 +412,7 @@ __global__ __launch_bounds__(NT) void temporal_layer16_kernel(
                 float qr[8];
 #pragma unroll
                 for (int mb = 0; mb < 2; ++mb) {
-                    const float sl = 0.17677669529663687f * LOG2E;
+                    const float sl = ROT_ONCE ? 1.0f : QSCALE;      // (the kept rows are scaled already: the same products)
                     const float2 cs = {qcs[k][mb].x * sl, qcs[k][mb].y * sl}, sn = {qsn[k][mb].x * sl, qsn[k][mb].y * sl};
                     qr[4 * mb] = d[k][mb][0] * cs.x - d[k][mb][1] * sn.x;
                     qr[4 * mb + 1] = d[k][mb][1] * cs.x + d[k][mb][0] * sn.x;
@@ -446,10 +475,9 @@ __global__ __launch_bounds__(NT) void temporal_layer16_kernel(
                 const int B0 = (i0t[k] - win) >> 4;                                 // first key block (i0 - win is a multiple of 16)
                 const int blo = max(0, -B0), bhi = min(nkb, nblk - B0);             // the blocks that exist
                 const int Bf = B0 + blo;                                            // first existing block
-                const int sh = (15 - n) & 3;
-                const float* bb = band4 + sh * BLD + ((15 - n) - sh) + 4 * g + 16 * blo;
-                const unsigned char* kbase = Kp + ((size_t)g * FA + 16 * Bf + n) * 16;
-                const unsigned char* vbase = Vp + ((size_t)lane * NB + Bf) * 8;
+                const float* bb = band4 + tl16_band_read_idx(n, g, blo);
+                const unsigned char* kbase = Kp + tl16_k_off(0, g, 16 * Bf + n, 0);
+                const unsigned char* vbase = Vp + tl16_v_off(0, 0, lane, Bf);
                 const int klast = Fext - 16 * (Bf + (bhi - blo) - 1) - 4 * g;       // slots of the last block that are frames: r < klast
                 f32x4 o[2][2] = {{zero4(), zero4()}, {zero4(), zero4()}};
                 float l = 0.f;
@@ -465,7 +493,7 @@ __global__ __launch_bounds__(NT) void temporal_layer16_kernel(
                         st[j] = *reinterpret_cast<const f32x4*>(bb + 16 * j);
 #pragma unroll
                         for (int pl = 0; pl < 3; ++pl)
-                            kf[j][pl] = *reinterpret_cast<const bf16x8*>(kbase + (size_t)j * 256 + (size_t)pl * 4 * FA * 16);
+                            kf[j][pl] = *reinterpret_cast<const bf16x8*>(kbase + j * 256 + tl16_k_off(pl, 0, 0, 0));
                     }
                     REGION();
                     // COMPUTE: S^T slot = bias + K_b . Q^T (NV chains), mask of the slots past the buffer, row maximum
@@ -494,8 +522,8 @@ __global__ __launch_bounds__(NT) void temporal_layer16_kernel(
                         for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
                             for (int pl = 0; pl < 3; ++pl) {
-                                const uint2 lo = *reinterpret_cast<const uint2*>(vbase + (size_t)(2 * kk) * 8 + (size_t)(pl * 2 + mb) * NB * 512);
-                                const uint2 hi = *reinterpret_cast<const uint2*>(vbase + (size_t)jb * 8 + (size_t)(pl * 2 + mb) * NB * 512);
+                                const uint2 lo = lds_read8(vbase + tl16_v_off(pl, mb, 0, 2 * kk));
+                                const uint2 hi = lds_read8(vbase + tl16_v_off(pl, mb, 0, jb));
                                 v[mb][pl] = join8(lo, hi);
                             }
                     };
@@ -674,10 +702,10 @@ __global__ __launch_bounds__(NT13) void temporal_layer13_kernel(
             const f32x4 o = dl * rs;
             uint2 p1, p2, p3;
             dawn_split3_rne_quad(o, p1, p2, p3);
-            unsigned char* dst = Xp + ((size_t)(sub >> 1) * FA + j) * 16 + (sub & 1) * 8;
+            unsigned char* dst = Xp + tl16_x_off(0, sub >> 1, j, sub & 1);
             *reinterpret_cast<uint2*>(dst) = p1;
-            *reinterpret_cast<uint2*>(dst + (size_t)8 * FA * 16) = p2;
-            *reinterpret_cast<uint2*>(dst + (size_t)16 * FA * 16) = p3;
+            *reinterpret_cast<uint2*>(dst + tl16_x_off(1, 0, 0, 0)) = p2;
+            *reinterpret_cast<uint2*>(dst + tl16_x_off(2, 0, 0, 0)) = p3;
         }
     }
 
@@ -721,15 +749,20 @@ __global__ __launch_bounds__(NT13) void temporal_layer13_kernel(
     const int bidx = (tid & 127) + (tid >> 7) - 15;
     const bool bok = bidx >= 0 && bidx <= 2 * win;
     bf16x8 wq0[2][3];          // Wq fragments of feature half 0, requested across the closing barrier
+    // rotary rows of the own query tile, times scale . log2(e): the same for every head -- fetched once and kept (8 registers; the kernel
+    // stands at 128 of its 128 with them, so the K side's rows -- 4 registers per row tile of the group -- are still fetched per head, in
+    // the load region of their row tile, where nothing queues behind them)
     float2 qcs[2], qsn[2];
+#pragma unroll
+    for (int mb = 0; mb < 2; ++mb) {
+        const float sl = 0.17677669529663687f * LOG2E;
+        const float2 c_ = rot_load(rsc, iqc, mb), s_ = rot_load(rss, iqc, mb);
+        qcs[mb] = float2{c_.x * sl, c_.y * sl};
+        qsn[mb] = float2{s_.x * sl, s_.y * sl};
+    }
     float bandv;
     auto request_next = [&](int hh) {
         wq_load(hh, 0, wq0);
-#pragma unroll
-        for (int mb = 0; mb < 2; ++mb) {
-            qcs[mb] = rot_load(rsc, iqc, mb);
-            qsn[mb] = rot_load(rss, iqc, mb);
-        }
         bandv = band[max(0, min(bidx, 2 * win)) * HEADS + hh];
     };
     request_next(0);
@@ -738,15 +771,15 @@ __global__ __launch_bounds__(NT13) void temporal_layer13_kernel(
 
     for (int h = 0; h < HEADS; ++h) {
         // ---- phase A
-        if (tid < 512) band4[(tid >> 7) * BLD + (tid & 127)] = bok ? bandv * LOG2E : NEG;
+        if (tid < 512 && (tid & 127) < BLD) band4[tl16_band_idx(tid >> 7, tid & 127)] = bok ? bandv * LOG2E : NEG;
         if (has_q) {
             bf16x8 xfq[2][3];
-            const unsigned char* xr = Xp + ((size_t)g * FA + iqc) * 16;
+            const unsigned char* xr = Xp + tl16_x_off(0, g, iqc, 0);
 #pragma unroll
             for (int s = 0; s < 2; ++s)
 #pragma unroll
                 for (int pl = 0; pl < 3; ++pl)
-                    xfq[s][pl] = *reinterpret_cast<const bf16x8*>(xr + (size_t)((pl * 8 + 4 * s) * FA) * 16);
+                    xfq[s][pl] = *reinterpret_cast<const bf16x8*>(xr + tl16_x_off(pl, 4 * s, 0, 0));
             REGION();
             f32x4 d2[2] = {zero4(), zero4()};
 #pragma unroll
@@ -765,15 +798,14 @@ __global__ __launch_bounds__(NT13) void temporal_layer13_kernel(
 #pragma unroll
                 for (int s = 0; s < 2; ++s) e2[s] = mfma16(wq1[s][DAWN_SPLIT6_A[u]], xfq[s][DAWN_SPLIT6_B[u]], e2[s]);
             const f32x4 d1 = e2[0] + e2[1];
-            const float sl = 0.17677669529663687f * LOG2E;
             float qr[8];
             {
-                const float2 cs = {qcs[0].x * sl, qcs[0].y * sl}, sn = {qsn[0].x * sl, qsn[0].y * sl};
+                const float2 cs = qcs[0], sn = qsn[0];
                 qr[0] = d0[0] * cs.x - d0[1] * sn.x; qr[1] = d0[1] * cs.x + d0[0] * sn.x;
                 qr[2] = d0[2] * cs.y - d0[3] * sn.y; qr[3] = d0[3] * cs.y + d0[2] * sn.y;
             }
             {
-                const float2 cs = {qcs[1].x * sl, qcs[1].y * sl}, sn = {qsn[1].x * sl, qsn[1].y * sl};
+                const float2 cs = qcs[1], sn = qsn[1];
                 qr[4] = d1[0] * cs.x - d1[1] * sn.x; qr[5] = d1[1] * cs.x + d1[0] * sn.x;
                 qr[6] = d1[2] * cs.y - d1[3] * sn.y; qr[7] = d1[3] * cs.y + d1[2] * sn.y;
             }
@@ -797,13 +829,13 @@ __global__ __launch_bounds__(NT13) void temporal_layer13_kernel(
                 const int row = 16 * rt + n;
                 const int rc_ = min(row, Fext - 1);
                 const float2 cs = rot_load(rsc, rc_, kmb), sn = rot_load(rss, rc_, kmb);
-                const unsigned char* xr = Xp + ((size_t)g * FA + row) * 16;
+                const unsigned char* xr = Xp + tl16_x_off(0, g, row, 0);
                 bf16x8 xf[2][3];
 #pragma unroll
                 for (int s = 0; s < 2; ++s)
 #pragma unroll
                     for (int pl = 0; pl < 3; ++pl)
-                        xf[s][pl] = *reinterpret_cast<const bf16x8*>(xr + (size_t)((pl * 8 + 4 * s) * FA) * 16);
+                        xf[s][pl] = *reinterpret_cast<const bf16x8*>(xr + tl16_x_off(pl, 4 * s, 0, 0));
                 REGION();
                 f32x4 d2[2] = {zero4(), zero4()};
                 uint2 p1, p2, p3;
@@ -815,20 +847,20 @@ __global__ __launch_bounds__(NT13) void temporal_layer13_kernel(
                     const f32x4 d = d2[0] + d2[1];
                     const f32x4 kr = {d[0] * cs.x - d[1] * sn.x, d[1] * cs.x + d[0] * sn.x, d[2] * cs.y - d[3] * sn.y, d[3] * cs.y + d[2] * sn.y};
                     dawn_split3_trunc_quad(kr, p1, p2, p3);
-                    unsigned char* dst = Kp + ((size_t)g * FA + row) * 16 + kmb * 8;
+                    unsigned char* dst = Kp + tl16_k_off(0, g, row, kmb);
                     *reinterpret_cast<uint2*>(dst) = p1;
-                    *reinterpret_cast<uint2*>(dst + (size_t)4 * FA * 16) = p2;
-                    *reinterpret_cast<uint2*>(dst + (size_t)8 * FA * 16) = p3;
+                    *reinterpret_cast<uint2*>(dst + tl16_k_off(1, 0, 0, 0)) = p2;
+                    *reinterpret_cast<uint2*>(dst + tl16_k_off(2, 0, 0, 0)) = p3;
                 } else {
 #pragma unroll
                     for (int u = 0; u < 6; ++u)
 #pragma unroll
                         for (int s = 0; s < 2; ++s) d2[s] = mfma16(xf[s][DAWN_SPLIT6_B[u]], wkv[s][DAWN_SPLIT6_A[u]], d2[s]);
                     dawn_split3_trunc_quad(d2[0] + d2[1], p1, p2, p3);
-                    unsigned char* dst = Vp + ((size_t)(kmb * 64 + lane) * NB + rt) * 8;
+                    unsigned char* dst = Vp + tl16_v_off(0, kmb, lane, rt);
                     *reinterpret_cast<uint2*>(dst) = p1;
-                    *reinterpret_cast<uint2*>(dst + (size_t)NB * 2 * 512) = p2;
-                    *reinterpret_cast<uint2*>(dst + (size_t)2 * NB * 2 * 512) = p3;
+                    *reinterpret_cast<uint2*>(dst + tl16_v_off(1, 0, 0, 0)) = p2;
+                    *reinterpret_cast<uint2*>(dst + tl16_v_off(2, 0, 0, 0)) = p3;
                 }
             }
         }
@@ -840,10 +872,9 @@ __global__ __launch_bounds__(NT13) void temporal_layer13_kernel(
             const int B0 = (i0 - win) >> 4;
             const int blo = max(0, -B0), bhi = min(nkb, nblk - B0);
             const int Bf = B0 + blo;
-            const int sh = (15 - n) & 3;
-            const float* bb = band4 + sh * BLD + ((15 - n) - sh) + 4 * g + 16 * blo;
-            const unsigned char* kbase = Kp + ((size_t)g * FA + 16 * Bf + n) * 16;
-            const unsigned char* vbase = Vp + ((size_t)lane * NB + Bf) * 8;
+            const float* bb = band4 + tl16_band_read_idx(n, g, blo);
+            const unsigned char* kbase = Kp + tl16_k_off(0, g, 16 * Bf + n, 0);
+            const unsigned char* vbase = Vp + tl16_v_off(0, 0, lane, Bf);
             const int klast = Fext - 16 * (Bf + (bhi - blo) - 1) - 4 * g;
             f32x4 o[2] = {zero4(), zero4()};
             float l = 0.f;
@@ -861,7 +892,7 @@ __global__ __launch_bounds__(NT13) void temporal_layer13_kernel(
                     for (int j = 0; j < H1; ++j)
 #pragma unroll
                         for (int pl = 0; pl < 3; ++pl)
-                            kf[j][pl] = *reinterpret_cast<const bf16x8*>(kbase + (size_t)j * 256 + (size_t)pl * 4 * FA * 16);
+                            kf[j][pl] = *reinterpret_cast<const bf16x8*>(kbase + j * 256 + tl16_k_off(pl, 0, 0, 0));
                     REGION();
 #pragma unroll
                     for (int u = 0; u < 6; ++u)
@@ -883,7 +914,7 @@ __global__ __launch_bounds__(NT13) void temporal_layer13_kernel(
                     for (int j = H1; j < NV; ++j)
 #pragma unroll
                         for (int pl = 0; pl < 3; ++pl)
-                            kf[j - H1][pl] = *reinterpret_cast<const bf16x8*>(kbase + (size_t)j * 256 + (size_t)pl * 4 * FA * 16);
+                            kf[j - H1][pl] = *reinterpret_cast<const bf16x8*>(kbase + j * 256 + tl16_k_off(pl, 0, 0, 0));
                     REGION();
 #pragma unroll
                     for (int u = 0; u < 6; ++u)
@@ -906,8 +937,8 @@ __global__ __launch_bounds__(NT13) void temporal_layer13_kernel(
                     for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
                         for (int pl = 0; pl < 3; ++pl) {
-                            const uint2 lo = *reinterpret_cast<const uint2*>(vbase + (size_t)(2 * kk) * 8 + (size_t)(pl * 2 + mb) * NB * 512);
-                            const uint2 hi = *reinterpret_cast<const uint2*>(vbase + (size_t)jb * 8 + (size_t)(pl * 2 + mb) * NB * 512);
+                            const uint2 lo = lds_read8(vbase + tl16_v_off(pl, mb, 0, 2 * kk));
+                            const uint2 hi = lds_read8(vbase + tl16_v_off(pl, mb, 0, jb));
                             v[mb][pl] = join8(lo, hi);
                         }
                 };
@@ -1090,7 +1121,7 @@ __global__ __launch_bounds__(NT13) void temporal_attn13_kernel(
 
     for (int h = 0; h < HEADS; ++h) {
         // ---- phase A: the head's bias table, the wave's query tile, its four K / V units (all from registers requested a head ago)
-        if (tid < 512) band4[(tid >> 7) * BLD + (tid & 127)] = bok ? bandv * LOG2E : NEG;
+        if (tid < 512 && (tid & 127) < BLD) band4[tl16_band_idx(tid >> 7, tid & 127)] = bok ? bandv * LOG2E : NEG;
         {
             const float sl = 0.17677669529663687f * LOG2E;
             const float* rr = rot + iqc * 32 + 2 * g;
@@ -1112,10 +1143,10 @@ __global__ __launch_bounds__(NT13) void temporal_attn13_kernel(
             if (uV[i]) {
                 dawn_split3_trunc_quad(kvraw[i], p1, p2, p3);
                 if (uok[i]) {
-                    unsigned char* dst = Vp + ((size_t)(ukmb[i] * 64 + lane) * NB + urt[i]) * 8;
+                    unsigned char* dst = Vp + tl16_v_off(0, ukmb[i], lane, urt[i]);
                     *reinterpret_cast<uint2*>(dst) = p1;
-                    *reinterpret_cast<uint2*>(dst + (size_t)NB * 2 * 512) = p2;
-                    *reinterpret_cast<uint2*>(dst + (size_t)2 * NB * 2 * 512) = p3;
+                    *reinterpret_cast<uint2*>(dst + tl16_v_off(1, 0, 0, 0)) = p2;
+                    *reinterpret_cast<uint2*>(dst + tl16_v_off(2, 0, 0, 0)) = p3;
                 }
             } else {
                 const int row = 16 * urt[i] + n;
@@ -1125,10 +1156,10 @@ __global__ __launch_bounds__(NT13) void temporal_attn13_kernel(
                 const f32x4 kr = {d[0] * cs.x - d[1] * sn.x, d[1] * cs.x + d[0] * sn.x, d[2] * cs.y - d[3] * sn.y, d[3] * cs.y + d[2] * sn.y};
                 dawn_split3_trunc_quad(kr, p1, p2, p3);
                 if (uok[i]) {
-                    unsigned char* dst = Kp + ((size_t)g * FA + row) * 16 + ukmb[i] * 8;
+                    unsigned char* dst = Kp + tl16_k_off(0, g, row, ukmb[i]);
                     *reinterpret_cast<uint2*>(dst) = p1;
-                    *reinterpret_cast<uint2*>(dst + (size_t)4 * FA * 16) = p2;
-                    *reinterpret_cast<uint2*>(dst + (size_t)8 * FA * 16) = p3;
+                    *reinterpret_cast<uint2*>(dst + tl16_k_off(1, 0, 0, 0)) = p2;
+                    *reinterpret_cast<uint2*>(dst + tl16_k_off(2, 0, 0, 0)) = p3;
                 }
             }
         }
@@ -1143,10 +1174,9 @@ __global__ __launch_bounds__(NT13) void temporal_attn13_kernel(
             const int B0 = (i0 - win) >> 4;
             const int blo = max(0, -B0), bhi = min(nkb, nblk - B0);
             const int Bf = B0 + blo;
-            const int sh = (15 - n) & 3;
-            const float* bb = band4 + sh * BLD + ((15 - n) - sh) + 4 * g + 16 * blo;
-            const unsigned char* kbase = Kp + ((size_t)g * FA + 16 * Bf + n) * 16;
-            const unsigned char* vbase = Vp + ((size_t)lane * NB + Bf) * 8;
+            const float* bb = band4 + tl16_band_read_idx(n, g, blo);
+            const unsigned char* kbase = Kp + tl16_k_off(0, g, 16 * Bf + n, 0);
+            const unsigned char* vbase = Vp + tl16_v_off(0, 0, lane, Bf);
             const int klast = Fext - 16 * (Bf + (bhi - blo) - 1) - 4 * g;
             f32x4 o[2] = {zero4(), zero4()};
             float l = 0.f;
@@ -1164,7 +1194,7 @@ __global__ __launch_bounds__(NT13) void temporal_attn13_kernel(
                     for (int j = 0; j < H1; ++j)
 #pragma unroll
                         for (int pl = 0; pl < 3; ++pl)
-                            kf[j][pl] = *reinterpret_cast<const bf16x8*>(kbase + (size_t)j * 256 + (size_t)pl * 4 * FA * 16);
+                            kf[j][pl] = *reinterpret_cast<const bf16x8*>(kbase + j * 256 + tl16_k_off(pl, 0, 0, 0));
                     REGION();
 #pragma unroll
                     for (int u = 0; u < 6; ++u)
@@ -1186,7 +1216,7 @@ __global__ __launch_bounds__(NT13) void temporal_attn13_kernel(
                     for (int j = H1; j < NV; ++j)
 #pragma unroll
                         for (int pl = 0; pl < 3; ++pl)
-                            kf[j - H1][pl] = *reinterpret_cast<const bf16x8*>(kbase + (size_t)j * 256 + (size_t)pl * 4 * FA * 16);
+                            kf[j - H1][pl] = *reinterpret_cast<const bf16x8*>(kbase + j * 256 + tl16_k_off(pl, 0, 0, 0));
                     REGION();
 #pragma unroll
                     for (int u = 0; u < 6; ++u)
@@ -1209,8 +1239,8 @@ __global__ __launch_bounds__(NT13) void temporal_attn13_kernel(
                     for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
                         for (int pl = 0; pl < 3; ++pl) {
-                            const uint2 lo = *reinterpret_cast<const uint2*>(vbase + (size_t)(2 * kk) * 8 + (size_t)(pl * 2 + mb) * NB * 512);
-                            const uint2 hi = *reinterpret_cast<const uint2*>(vbase + (size_t)jb * 8 + (size_t)(pl * 2 + mb) * NB * 512);
+                            const uint2 lo = lds_read8(vbase + tl16_v_off(pl, mb, 0, 2 * kk));
+                            const uint2 hi = lds_read8(vbase + tl16_v_off(pl, mb, 0, jb));
                             v[mb][pl] = join8(lo, hi);
                         }
                 };
