@@ -119,6 +119,10 @@ SIGNATURES = {
     "dawn_sampler_run_clip": [c_f, _i, _i, _i, c_f, c_f, _f, c_f, _i, c_f, C.c_uint64, c_f, c_f, c_f, c_f, C.c_size_t, c_f, c_f, c_f],
     "dawn_sampler_run_ancestral_clip": [c_f, _i, _i, _i, c_f, c_f, _f, c_f, _i, c_f, C.c_uint64, c_f, c_f, c_f, c_f, C.c_size_t, c_f, c_f,
                                         c_f],
+    # DPM-Solver++(2M): the two step tails and the whole-path entry (single / guided / sharded, any clipping mode, in one)
+    "dawn_dpmpp_update": [c_f, c_f, c_f, c_f, _f, _f, _f, _l, c_f, c_f, c_f],
+    "dawn_dpmpp_step_fixed": [c_f, c_f, c_f, _f, _f, _f, _f, _f, _i, _l, c_f, c_f, c_f],
+    "dawn_sampler_run_dpmpp": [c_f, _i, _i, _i, c_f, c_f, _f, c_f, _i, c_f, c_f, c_f, c_f, C.c_size_t, c_f, c_f, c_f],
     "dawn_philox_normal": [c_f, _i, _i, _i, _i, _i, C.c_uint64, C.c_uint32, c_f],
     "dawn_affine_act": [c_f, _i, c_f, c_f, _i, c_f, _l, _i, c_f],
     "dawn_bn_relu_pool2": [c_f, c_f, c_f, c_f, _i, _i, _i, _i, c_f],

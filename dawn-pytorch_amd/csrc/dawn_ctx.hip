@@ -1137,12 +1137,14 @@ extern "C" int dawn_unet_forward(dawn_ctx* c, int F, int h, int w, const void* c
 
 // null_clip_mem != NULL and cond_scale != 1: every evaluation guided (Eval::forward_guided, whose last launch is dawn_cfg_x0).
 // Loop kind: DDIM steps (`steps`) or ancestral steps (`asteps`, exactly one of the two non-NULL); they differ in the step tail only.
+// `dsteps` instead: DPM-Solver++(2M) steps (dawn_sampler_run_dpmpp) -- deterministic, so the `noise` latent carries the history v_prev.
 // clip = NULL: dynamic thresholding at 0.9, what the entries without a mode have always run.  DAWN_CLIP_STATIC / DAWN_CLIP_NONE: the
 // evaluation (guided: ending in dawn_cfg_combine, the eps dawn_cfg_x0 forms) and ONE fused tail launch, no selection, no all-reduce.
 static int sampler_run_impl(dawn_ctx* c, int F, int h, int w, const void* clip_mem, const void* null_clip_mem, float cond_scale,
                             const float* x_init, int S, const dawn_ddim_step* steps, uint64_t seed, const float* const* noises, float* x_out,
                             float* thresholds, void* workspace, size_t workspace_bytes, const dawn_shard_comm* comm, void* stream,
-                            const dawn_ancestral_step* asteps = nullptr, const dawn_clip_mode* clip = nullptr) {
+                            const dawn_ancestral_step* asteps = nullptr, const dawn_clip_mode* clip = nullptr,
+                            const dawn_dpmpp_step* dsteps = nullptr) {
     const bool guided = null_clip_mem && cond_scale != 1.0f;
     const int kind = clip ? clip->kind : (int)DAWN_CLIP_DYNAMIC;
     const double q = clip ? clip->q : 0.9;
@@ -1153,8 +1155,10 @@ static int sampler_run_impl(dawn_ctx* c, int F, int h, int w, const void* clip_m
     if (kind == DAWN_CLIP_NONE && asteps)
         return dawn_set_error_msg(-214, "dawn_clip_mode: DAWN_CLIP_NONE does not exist for ancestral steps (p_sample always clips, MT:1113)");
     const bool dynamic = kind == DAWN_CLIP_DYNAMIC;
-    if (!c || !clip_mem || !x_init || !(steps || asteps) || !x_out || !workspace)
+    if (!c || !clip_mem || !x_init || !(steps || asteps || dsteps) || !x_out || !workspace)
         return dawn_set_error_msg(-202, "dawn_sampler_run: null argument");
+    if (dsteps && S > 0 && dsteps[0].c != 0.0f)
+        return dawn_set_error_msg(-215, "dawn_sampler_run_dpmpp: steps[0].c != 0, but the first step has no history");
     if (shard_check(comm)) return -212;
     if (comm && dynamic && (!comm->allreduce_sum_u32 || !comm->allreduce_min_u32))
         return dawn_set_error_msg(-210, "dawn_sampler_run_sharded: dawn_shard_comm.allreduce_sum_u32 / allreduce_min_u32 is NULL");
@@ -1198,8 +1202,10 @@ static int sampler_run_impl(dawn_ctx* c, int F, int h, int w, const void* clip_m
         weight = (float)(pos - fl);
     }
     for (int i = 0; i < S; ++i) {
-        const int t = asteps ? asteps[i].t : steps[i].t;
-        const float recip = asteps ? asteps[i].recip : steps[i].recip, recipm1 = asteps ? asteps[i].recipm1 : steps[i].recipm1;
+        const int t = dsteps ? dsteps[i].t : asteps ? asteps[i].t : steps[i].t;
+        const float recip = dsteps ? dsteps[i].recip : asteps ? asteps[i].recip : steps[i].recip;
+        const float recipm1 = dsteps ? dsteps[i].recipm1 : asteps ? asteps[i].recipm1 : steps[i].recipm1;
+        const float* v_prev = dsteps && dsteps[i].c != 0.0f ? noise : nullptr;      // (the history: written by step i - 1)
         c->arena.reset(ws, fwd_bytes, false);
         if (!dynamic) {
             {
@@ -1209,13 +1215,17 @@ static int sampler_run_impl(dawn_ctx* c, int F, int h, int w, const void* clip_m
                 else ev.forward(x, (float)t, eps);
                 if (ev.rc) return ev.rc;
             }
+            float* dst = (i + 1 == S) ? x_out : x;
+            const int clamp = kind == DAWN_CLIP_STATIC;
+            if (dsteps) {
+                CK(dawn_dpmpp_step_fixed(x, eps, v_prev, recip, recipm1, dsteps[i].a, dsteps[i].b, dsteps[i].c, clamp, n, noise, dst, s));
+                continue;
+            }
             const float* nz = nullptr;
             if (asteps ? t > 0 : steps[i].t_next > 0) {
                 if (noises) nz = noises[i];
                 else { CK(dawn_philox_normal(noise, 3, F, f0g, Ftot, h * w, seed, (uint32_t)(i + 1), s)); nz = noise; }
             }
-            float* dst = (i + 1 == S) ? x_out : x;
-            const int clamp = kind == DAWN_CLIP_STATIC;
             if (asteps) CK(dawn_ancestral_step_fixed(x, eps, nz, recip, recipm1, asteps[i].c1, asteps[i].c2, asteps[i].std, clamp, n, nullptr, dst, s));
             else CK(dawn_ddim_step_fixed(x, eps, nz, recip, recipm1, steps[i].sqrt_alpha_next, steps[i].c, steps[i].sigma, clamp, n, nullptr, dst, s));
             continue;
@@ -1252,6 +1262,10 @@ static int sampler_run_impl(dawn_ctx* c, int F, int h, int w, const void* clip_m
         SHARD_CB(comm->allreduce_min_u32(comm->user, hmin, 1, stream));
         CK(dawn_select_finalize(state, hmin, weight, sthr, s));
         if (thresholds) HCK(hipMemcpyAsync(thresholds + 2 * i, sthr, 8, hipMemcpyDeviceToDevice, s));
+        if (dsteps) {
+            CK(dawn_dpmpp_update(x0, sthr, x, v_prev, dsteps[i].a, dsteps[i].b, dsteps[i].c, n, noise, (i + 1 == S) ? x_out : x, s));
+            continue;
+        }
         const float* nz = nullptr;
         if (asteps ? t > 0 : steps[i].t_next > 0) {            // noise only if t_next > 0 (MT:1201) / t > 0 (MT:1120)
             if (noises) nz = noises[i];
@@ -1309,6 +1323,14 @@ extern "C" int dawn_sampler_run_ancestral_clip(dawn_ctx* c, int F, int h, int w,
     if (!steps) return dawn_set_error_msg(-202, "dawn_sampler_run_ancestral_clip: null argument");
     return sampler_run_impl(c, F, h, w, clip_mem, null_clip_mem, cond_scale, x_init, S, nullptr, seed, noises, x_out, thresholds,
                             workspace, workspace_bytes, comm, stream, steps, clip);
+}
+extern "C" int dawn_sampler_run_dpmpp(dawn_ctx* c, int F, int h, int w, const void* clip_mem, const void* null_clip_mem, float cond_scale,
+                                      const float* x_init, int S, const dawn_dpmpp_step* steps, float* x_out, float* thresholds,
+                                      void* workspace, size_t workspace_bytes, const dawn_shard_comm* comm, const dawn_clip_mode* clip,
+                                      void* stream) {
+    if (!steps) return dawn_set_error_msg(-202, "dawn_sampler_run_dpmpp: null argument");
+    return sampler_run_impl(c, F, h, w, clip_mem, null_clip_mem, cond_scale, x_init, S, nullptr, 0, nullptr, x_out, thresholds, workspace,
+                            workspace_bytes, comm, stream, nullptr, clip, steps);
 }
 extern "C" int dawn_sampler_run(dawn_ctx* c, int F, int h, int w, const void* clip_mem, const float* x_init, int S,
                                 const dawn_ddim_step* steps, uint64_t seed, const float* const* noises, float* x_out,

@@ -264,6 +264,58 @@ __global__ __launch_bounds__(256) void step_fixed_kernel(const float* x, const f
     }
 }
 
+// ---- DPM-Solver++(2M) step tails (include/dawn_hip.h has the definition): out = A*x + b*v + c*v_prev with v the clipped x0, which is also
+// stored (v_out) as the next step's history.  ONE expression for both kernels, roundings pinned: r = (A*x) + (b*v), three roundings, then
+// r = fma(c, v_prev, r) when the history term exists -- so the fused kernel equals dawn_ddim_x0 followed by dawn_dpmpp_update bit for bit
+// (static: clamp(x0,-1,1)/1 is exact), and the 128-bit body equals the scalar tail.  out may alias x and v_out may alias v_prev (every
+// thread reads its elements before it writes them): no __restrict__ on those pairs.
+__device__ __forceinline__ float dpmpp_one(float xv, float v, float pv, float A, float b, float c, bool has_prev) {
+#pragma clang fp contract(off)
+    float r = (A * xv) + (b * v);
+    if (has_prev) r = __builtin_fmaf(c, pv, r);
+    return r;
+}
+// v of the dynamic mode: clamp(x0, -s, s) / s (the expression of ddim_update_kernel)
+__device__ __forceinline__ float dpmpp_v_dynamic(float x0v, float s) { return fminf(fmaxf(x0v, -s), s) / s; }
+// v of the static / none modes from x and eps: x0 as step_fixed_one forms it, clamped to [-1, 1] or not
+__device__ __forceinline__ float dpmpp_v_fixed(float xv, float ev, float recip, float recipm1, int clamp) {
+#pragma clang fp contract(off)
+    const float x0v = __builtin_fmaf(recip, xv, -(recipm1 * ev));
+    return clamp ? fminf(fmaxf(x0v, -1.0f), 1.0f) : x0v;
+}
+
+// FIXED = false: in0 = x0, sp = the threshold; FIXED = true: in0 = eps, x0 is formed here and never goes through memory
+template <bool FIXED>
+__global__ __launch_bounds__(256) void dpmpp_kernel(const float* __restrict__ in0, const float* __restrict__ sp, const float* x,
+                                                    const float* v_prev, float recip, float recipm1, float A, float b, float c,
+                                                    int clamp, long n, int vec, float* v_out, float* out) {
+    const float s = FIXED ? 1.0f : sp[0];
+    const bool hp = v_prev != nullptr;
+    const long stride = (long)gridDim.x * 256;
+    const long n4 = vec ? (n >> 2) : 0;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
+        const f32x4 iv = reinterpret_cast<const f32x4*>(in0)[i];
+        const f32x4 xv = reinterpret_cast<const f32x4*>(x)[i];
+        f32x4 pv = {0.f, 0.f, 0.f, 0.f};
+        if (hp) pv = reinterpret_cast<const f32x4*>(v_prev)[i];
+        f32x4 r, v;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            v[k] = FIXED ? dpmpp_v_fixed(xv[k], iv[k], recip, recipm1, clamp) : dpmpp_v_dynamic(iv[k], s);
+            r[k] = dpmpp_one(xv[k], v[k], pv[k], A, b, c, hp);
+        }
+        reinterpret_cast<f32x4*>(v_out)[i] = v;
+        reinterpret_cast<f32x4*>(out)[i] = r;
+    }
+    for (long i = n4 * 4 + (long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+        const float xv = x[i], pv = hp ? v_prev[i] : 0.f;
+        const float v = FIXED ? dpmpp_v_fixed(xv, in0[i], recip, recipm1, clamp) : dpmpp_v_dynamic(in0[i], s);
+        const float r = dpmpp_one(xv, v, pv, A, b, c, hp);
+        v_out[i] = v;
+        out[i] = r;
+    }
+}
+
 int grid_for(long n) {
     long g = (n + 255) / 256;
     if (g > 2048) g = 2048;
@@ -373,6 +425,47 @@ extern "C" int dawn_ancestral_step_fixed(const float* x_t, const float* eps, con
                                          float c2, float std, int clamp, long n, float* x0_out, float* out, void* stream) {
     return step_fixed_launch(true, "dawn_ancestral_step_fixed", x_t, eps, noise, recip, recipm1, c1, c2, std, clamp, n, x0_out, out,
                              stream);
+}
+// in0 = x0 (fixed = false; s = the threshold) or eps (fixed = true; s = NULL).  Allowed aliases: out == x, v_out == v_prev.
+static int dpmpp_launch(bool fixed, const char* who, const float* in0, const float* s, const float* x, const float* v_prev, float recip,
+                        float recipm1, float A, float b, float c, int clamp, long n, float* v_out, float* out, void* stream) {
+    char msg[200];
+    if (!in0 || !x || !v_out || !out || (!fixed && !s) || n < 0) {
+        snprintf(msg, sizeof(msg), "%s: null argument", who);
+        return dawn_set_error_msg(-79, msg);
+    }
+    if (clamp != 0 && clamp != 1) {
+        snprintf(msg, sizeof(msg), "%s: clamp must be 1 (static) or 0 (none)", who);
+        return dawn_set_error_msg(-79, msg);
+    }
+    const bool bad = (out != x && ranges_overlap(out, x, n)) || (v_out != v_prev && ranges_overlap(v_out, v_prev, n)) ||
+                     ranges_overlap(out, in0, n) || ranges_overlap(out, v_prev, n) || ranges_overlap(out, v_out, n) ||
+                     ranges_overlap(v_out, in0, n) || ranges_overlap(v_out, x, n) ||
+                     (s && s >= out && s < out + n) || (s && s >= v_out && s < v_out + n);      // (s[0] is all that is read)
+    if (bad) {
+        snprintf(msg, sizeof(msg), "%s: out and v_out must not alias each other or an input (out == x and v_out == v_prev are allowed)", who);
+        return dawn_set_error_msg(-80, msg);
+    }
+    if (n == 0) return 0;
+    const uintptr_t bits = (uintptr_t)in0 | (uintptr_t)x | (uintptr_t)v_prev | (uintptr_t)v_out | (uintptr_t)out;
+    const int vec = (bits & 15) == 0 && n >= 4;
+    const int grid = grid_for(vec ? (n + 3) / 4 : n);
+    if (fixed)
+        hipLaunchKernelGGL(dpmpp_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, in0, s, x, v_prev, recip, recipm1, A, b, c,
+                           clamp, n, vec, v_out, out);
+    else
+        hipLaunchKernelGGL(dpmpp_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, in0, s, x, v_prev, recip, recipm1, A, b, c,
+                           clamp, n, vec, v_out, out);
+    DAWN_LAUNCH_CHECK();
+    return 0;
+}
+extern "C" int dawn_dpmpp_update(const float* x0, const float* s, const float* x, const float* v_prev, float A, float b, float c, long n,
+                                 float* v_out, float* out, void* stream) {
+    return dpmpp_launch(false, "dawn_dpmpp_update", x0, s, x, v_prev, 0.f, 0.f, A, b, c, 1, n, v_out, out, stream);
+}
+extern "C" int dawn_dpmpp_step_fixed(const float* x, const float* eps, const float* v_prev, float recip, float recipm1, float A, float b,
+                                     float c, int clamp, long n, float* v_out, float* out, void* stream) {
+    return dpmpp_launch(true, "dawn_dpmpp_step_fixed", eps, nullptr, x, v_prev, recip, recipm1, A, b, c, clamp, n, v_out, out, stream);
 }
 extern "C" int dawn_cfg_combine(const float* e_null, const float* e_cond, float scale, long n, float* out,
                                 void* stream) {

@@ -42,6 +42,11 @@ class AncestralStep(C.Structure):
                 ("std", C.c_float)]
 
 
+class DpmppStep(C.Structure):
+    """Mirror of ``dawn_dpmpp_step``."""
+    _fields_ = [("t", C.c_int), ("recip", C.c_float), ("recipm1", C.c_float), ("a", C.c_float), ("b", C.c_float), ("c", C.c_float)]
+
+
 class ClipMode(C.Structure):
     """Mirror of ``dawn_clip_mode``."""
     _fields_ = [("kind", C.c_int), ("q", C.c_double)]
@@ -439,6 +444,39 @@ class CtxEvaluator(_Evaluator):
             self._shard_call(shard, rc, what)
         else:
             check(rc, what)
+        return (out, thr) if want_thresholds else out
+
+    def sample_dpmpp(self, clip: dict, x_init: Tensor, steps: Sequence[dict], want_thresholds: bool = False,
+                     shard: Optional[ShardCallbacks] = None, null_clip: Optional[dict] = None, cond_scale: float = 1.0, x0_clip=None):
+        """dawn_sampler_run_dpmpp: the DPM-Solver++(2M) loop (sampler.dpmpp_step_scalars), guided when cond_scale != 1 (null_clip =
+        prepare_null_clip(...)), one T-shard rank when `shard` is given.  Deterministic: no seed, no noises.  x0_clip (sampler.clip_mode;
+        None: dynamic thresholding at 0.9): any clipping mode.  Thresholds: static [1, 1] per step, none: rows left as allocated."""
+        F, h, w = clip["F"], clip["h"], clip["w"]
+        S = len(steps)
+        arr = (DpmppStep * max(S, 1))()
+        for i, st in enumerate(steps):
+            arr[i].t, arr[i].recip, arr[i].recipm1 = int(st["t"]), st["recip"], st["recipm1"]
+            arr[i].a, arr[i].b, arr[i].c = st["a"], st["b"], st["c"]
+        guided = cond_scale != 1.0
+        if guided and null_clip is None:
+            raise _lib.DawnHipError("sample_dpmpp: cond_scale != 1 needs null_clip (prepare_null_clip)")
+        x_init = x_init.contiguous().float()
+        out = torch.empty_like(x_init)
+        thr = torch.empty(S, 2, device=self.device) if want_thresholds else None
+        mode = None if x0_clip is None else _clip_struct(x0_clip, False)
+        ws = self.workspace(F, h, w, shard, guided=guided)
+        comm = None
+        if shard is not None:
+            shard.ws = ws
+            comm = C.addressof(shard.c)
+        rc = self.L.dawn_sampler_run_dpmpp(self.h, F, h, w, clip["mem"].data_ptr(), null_clip["mem"].data_ptr() if guided else None,
+                                           float(cond_scale), x_init.data_ptr(), S, arr, out.data_ptr(),
+                                           None if thr is None else thr.data_ptr(), ws.data_ptr(), ws.numel(), comm,
+                                           None if mode is None else C.addressof(mode), self._stream())
+        if shard is not None:
+            self._shard_call(shard, rc, "dawn_sampler_run_dpmpp")
+        else:
+            check(rc, "dawn_sampler_run_dpmpp")
         return (out, thr) if want_thresholds else out
 
     def profile_read(self):

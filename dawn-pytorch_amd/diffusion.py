@@ -6,6 +6,9 @@ MT:1156-1208) on the HIP op set.  Same constructor signature and the same 12 sch
 timesteps, else the ancestral loop `p_sample_loop` (MT:1113-1135).  x0 is clipped as the reference clips it (MT:1094-1107,
 MT:1183-1196): `use_dynamic_thres=True` -> dynamic thresholding at `dynamic_thres_percentile` (the shipped pipeline: 0.9, FD:164),
 `use_dynamic_thres=False` (the constructor default) -> static clamp to [-1, 1], `ddim_sample(clip_denoised=False)` -> none.
+Not in the reference: `solver = "dpmpp2m"` (a plain attribute, default "ddim") runs DPM-Solver++(2M) on the DDIM time grid instead of
+the DDIM update, on every host; its definition is in include/dawn_hip.h.  Quality against the number of steps on a trained checkpoint
+has not been measured.
 Inference only: the training losses (MT:1226-1281) are out of scope."""
 from __future__ import annotations
 
@@ -15,7 +18,7 @@ import torch
 from torch import nn
 
 from .sampler import (CLIP_DEFAULT, ancestral_sample_clip, ancestral_step_scalars, clip_mode, cosine_schedule_buffers, ddim_sample_clip,
-                      ddim_step_scalars)
+                      ddim_step_scalars, dpmpp_sample_clip, dpmpp_step_scalars)
 
 Tensor = torch.Tensor
 
@@ -88,6 +91,11 @@ class GaussianDiffusion(nn.Module):
                                                   # the ancestral loop; dawn_sampler_run_clip / _ancestral_clip for any clipping
                                                   # mode but dynamic at 0.9); same kernels and arguments as the Python
                                                   # orchestration: bit-identical output
+        self.solver = "ddim"                      # "ddim": the reference's update; "dpmpp2m": DPM-Solver++(2M) on the same time pairs
+                                                  # (needs sampling_timesteps < timesteps; deterministic after the initial
+                                                  # latent: ddim_sampling_eta and `noises` are not read, noise_seed only seeds
+                                                  # the initial latent).  A plain attribute: neither a constructor argument
+                                                  # nor a buffer
         self.last_route: Optional[str] = None     # "ctx" or "python": which host ran the last sample()
         self.last_trace: Optional[list] = None
 
@@ -120,9 +128,14 @@ class GaussianDiffusion(nn.Module):
                                  self.clip if clip_denoised else ("none", None))
 
     def _sample_loop(self, kind, fea, shape, cond, cond_scale, x_init, noises, trace, comm, clip):
-        """One host loop for both samplers (kind "ddim" / "ancestral"): the C-side evaluator when use_ctx, else the Python
-        orchestration; they share the evaluation and differ in the step scalars and the step tail.  clip = (kind, q) of
-        sampler.clip_mode."""
+        """One host loop for every sampler (kind "ddim" / "ancestral"; solver "dpmpp2m" turns "ddim" into the DPM-Solver++(2M) steps
+        on the same time pairs): the C-side evaluator when use_ctx, else the Python orchestration; they share the evaluation and
+        differ in the step scalars and the step tail.  clip = (kind, q) of sampler.clip_mode."""
+        if self.solver not in ("ddim", "dpmpp2m"):
+            raise ValueError(f'unknown solver {self.solver!r}: "ddim" or "dpmpp2m"')
+        dpmpp = self.solver == "dpmpp2m"
+        if dpmpp and (kind != "ddim" or not self.is_ddim_sampling):
+            raise ValueError('solver = "dpmpp2m" runs on the DDIM time grid: it needs sampling_timesteps < timesteps')
         ancestral = kind == "ancestral"
         clip = clip_mode(clip, ancestral)
         unet = self.denoise_fn
@@ -136,12 +149,17 @@ class GaussianDiffusion(nn.Module):
             steps = ancestral_step_scalars({k: getattr(self, k) for k in (
                 "sqrt_recip_alphas_cumprod", "sqrt_recipm1_alphas_cumprod", "posterior_mean_coef1", "posterior_mean_coef2",
                 "posterior_log_variance_clipped")}, self.num_timesteps)
+        elif dpmpp:
+            steps = dpmpp_step_scalars({k: getattr(self, k) for k in ("alphas_cumprod_prev", "sqrt_recip_alphas_cumprod",
+                                                                       "sqrt_recipm1_alphas_cumprod")}, self.sampling_timesteps,
+                                       self.num_timesteps)
         else:
             S, eta = self.sampling_timesteps, self.ddim_sampling_eta
             steps = ddim_step_scalars({k: getattr(self, k) for k in ("alphas_cumprod_prev", "sqrt_recip_alphas_cumprod",
                                                                       "sqrt_recipm1_alphas_cumprod")}, S, eta,
                                       self.num_timesteps)
-        noisy = [st["t"] > 0 if ancestral else st["t_next"] > 0 for st in steps]    # steps that draw noise (MT:1120 / MT:1201)
+        # steps that draw noise (MT:1120 / MT:1201); DPM-Solver++(2M) draws none
+        noisy = [not dpmpp and (st["t"] > 0 if ancestral else st["t_next"] > 0) for st in steps]
         device = fea.device
         Ttotal, f0 = (T, 0) if comm is None else (comm.Ttotal, comm.f0)
         if cond is not None and cond.shape[1] != T:
@@ -164,13 +182,17 @@ class GaussianDiffusion(nn.Module):
                 if noises is not None:
                     nz = [noises[i][b].contiguous() if noisy[i] else None for i in range(len(steps))]
                 run_seed = (seed + b) if seed is not None else None
-                if nz is None and run_seed is None:
+                if nz is None and run_seed is None and not dpmpp:
                     # unseeded (MT:1201 draws from the global generator): ONE draw from it seeds the evaluator's counter-based
                     # generator -- S x 3 x T x h x w floats of pre-drawn noise would be GBs for the long clips the path supports
                     run_seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+                x0_clip = None if clip == CLIP_DEFAULT else clip
+                if dpmpp:
+                    outs.append(ev.sample_dpmpp(clip_mem, x0, steps, null_clip=null_clip, cond_scale=cond_scale, x0_clip=x0_clip))
+                    continue
                 run = ev.sample_ancestral if ancestral else ev.sample
                 outs.append(run(clip_mem, x0, steps, seed=run_seed or 0, noises=nz, null_clip=null_clip, cond_scale=cond_scale,
-                                x0_clip=None if clip == CLIP_DEFAULT else clip))
+                                x0_clip=x0_clip))
             self.last_trace = None
             self.last_route = "ctx"
             return torch.stack(outs, 0)
@@ -197,9 +219,13 @@ class GaussianDiffusion(nn.Module):
             else:
                 x0 = torch.randn(3, T, h, w, device=device)                           # MT:1166
             tr = [] if trace else None
-            outs.append((ancestral_sample_clip if ancestral else ddim_sample_clip)(
-                ops, P, cs, x0, steps, noise_fn, cond_scale, cs_null, tr, use_graph=self.use_graph, eager_every=self.eager_every,
-                clip=clip))
+            if dpmpp:
+                outs.append(dpmpp_sample_clip(ops, P, cs, x0, steps, cond_scale, cs_null, tr, use_graph=self.use_graph,
+                                              eager_every=self.eager_every, clip=clip))
+            else:
+                outs.append((ancestral_sample_clip if ancestral else ddim_sample_clip)(
+                    ops, P, cs, x0, steps, noise_fn, cond_scale, cs_null, tr, use_graph=self.use_graph, eager_every=self.eager_every,
+                    clip=clip))
             traces.append(tr)
         self.last_trace = traces if trace else None
         self.last_route = "python"

@@ -686,6 +686,39 @@ class HipOps:
         return self._step_fixed(self.L.dawn_ancestral_step_fixed, "dawn_ancestral_step_fixed", x_t, eps, noise, recip, recipm1, c1, c2,
                                 std, clamp, want_x0, out)
 
+    def _dpmpp_buffers(self, name: str, x: Tensor, other: Tensor, v_prev: Optional[Tensor], v_out: Optional[Tensor], out: Optional[Tensor]):
+        n = x.numel()
+        _need(x.is_contiguous() and other.is_contiguous() and other.numel() == n and
+              (v_prev is None or (v_prev.is_contiguous() and v_prev.numel() == n)), f"{name}: contiguous operands of one size")
+        self._require(x, other, v_prev, v_out, out)
+        if v_out is None:
+            v_out = self.empty(x.shape, like=x)
+        if out is None:
+            out = self.empty(x.shape, like=x)
+        _need(out.is_contiguous() and out.numel() == n and v_out.is_contiguous() and v_out.numel() == n,
+              f"{name}: out / v_out contiguous of x's size")
+        return n, v_out, out
+
+    def dpmpp_update(self, x0: Tensor, s: Tensor, x: Tensor, v_prev: Optional[Tensor], a: float, b: float, c: float,
+                     v_out: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+        """DPM-Solver++(2M) step tail of the dynamic mode (dawn_dpmpp_update): v = clamp(x0, -s, s) / s, a*x + b*v (+ c*v_prev) ->
+        (next latent, v).  v_prev = None drops the history term (pass it whenever c == 0).  v_out = v_prev keeps the history in place,
+        out = x updates the latent in place."""
+        n, v_out, out = self._dpmpp_buffers("dawn_dpmpp_update", x, x0, v_prev, v_out, out)
+        check(self.L.dawn_dpmpp_update(_p(x0), _p(s), _p(x), _p(v_prev), float(a), float(b), float(c), n, _p(v_out), _p(out),
+                                       self._stream()), "dawn_dpmpp_update")
+        return out, v_out
+
+    def dpmpp_step_fixed(self, x: Tensor, eps: Tensor, v_prev: Optional[Tensor], recip: float, recipm1: float, a: float, b: float,
+                         c: float, clamp: bool = True, v_out: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+        """The whole DPM-Solver++(2M) step tail of the clipping modes without a quantile in ONE launch (dawn_dpmpp_step_fixed): x0 =
+        recip*x - recipm1*eps, v = clamp(x0, -1, 1) (clamp: static) or x0 (none), a*x + b*v (+ c*v_prev) -> (next latent, v).
+        Bit-identical to ddim_x0 + dpmpp_update with s = 1."""
+        n, v_out, out = self._dpmpp_buffers("dawn_dpmpp_step_fixed", x, eps, v_prev, v_out, out)
+        check(self.L.dawn_dpmpp_step_fixed(_p(x), _p(eps), _p(v_prev), float(recip), float(recipm1), float(a), float(b), float(c),
+                                           int(bool(clamp)), n, _p(v_out), _p(out), self._stream()), "dawn_dpmpp_step_fixed")
+        return out, v_out
+
     def cfg_combine(self, e_null: Tensor, e_cond: Tensor, scale: float) -> Tensor:
         n = e_cond.numel()
         _need(e_null.is_contiguous() and e_cond.is_contiguous() and e_null.numel() == n, "cfg_combine: contiguous e_null / e_cond of one size")

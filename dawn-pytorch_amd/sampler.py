@@ -1,5 +1,6 @@
 """DDIM sampler loop for one clip on the op interface (`GaussianDiffusion.ddim_sample`, MT:1156-1208), and the ancestral loop
 (`GaussianDiffusion.p_sample_loop`, MT:1113-1135) that shares it: the two differ in the step scalars and the step tail only.
+So does DPM-Solver++(2M), which is not in the reference (defined in include/dawn_hip.h): the DDIM time pairs, other scalars, another tail.
 
 Host side: the cosine schedule tables and per-step scalars (tiny fp32/fp64 host arithmetic exactly as the
 reference computes them); device side: every tensor op of the loop goes through `ops` (HIP kernels).
@@ -84,6 +85,36 @@ def ancestral_step_scalars(bufs: Dict[str, Tensor], timesteps: int = 1000) -> Li
     return out
 
 
+def dpmpp_step_scalars(bufs: Dict[str, Tensor], S: int, total: int = 1000, order: int = 2) -> List[dict]:
+    """Per-step scalars of DPM-Solver++(2M) (Lu et al. 2022) on the DDIM time pairs; the definition is the one written in
+    include/dawn_hip.h (not in the reference).  Noise levels from the fp32 `_prev` table the DDIM loop uses, everything after that in
+    fp64; a, b, c rounded to fp32 once (`b0`: B0 rounded likewise, b + c before the rounding).  A step is first order (c = 0) at the
+    ends of the loop, where sigma_next = 0, and next to two equal times (h = 0: only for S close to `total`).  order=1: the
+    first-order solver of the same definition (c = 0 on every step)."""
+    if order not in (1, 2):
+        raise ValueError(f"dpmpp_step_scalars: order must be 1 or 2, got {order!r}")
+    acp_prev = bufs["alphas_cumprod_prev"].detach().float().cpu().double()
+    recip = bufs["sqrt_recip_alphas_cumprod"].detach().float().cpu()
+    recipm1 = bufs["sqrt_recipm1_alphas_cumprod"].detach().float().cpu()
+    f32 = lambda v: float(torch.tensor(v, dtype=torch.float64).float())          # noqa: E731
+    out, h_prev = [], None
+    for i, (t, tn) in enumerate(ddim_time_pairs(S, total)):
+        ab, abn = float(acp_prev[t]), float(acp_prev[tn])
+        al, sg, aln, sgn = math.sqrt(ab), math.sqrt(1.0 - ab), math.sqrt(abn), math.sqrt(1.0 - abn)
+        rho = (sgn * al) / (aln * sg)                                            # e^(-h); 0, not inf, at sigma_next = 0
+        A, B0 = sgn / sg, aln * (1.0 - rho)
+        h = -math.log(rho) if sgn > 0.0 else None
+        first = i == 0 or i == S - 1 or h is None or order == 1 or not (h > 0.0 and h_prev is not None and h_prev > 0.0)
+        if first:
+            b, c = B0, 0.0
+        else:
+            r = h_prev / h
+            b, c = B0 * (1.0 + 1.0 / (2.0 * r)), -B0 / (2.0 * r)
+        out.append(dict(t=t, t_next=tn, recip=float(recip[t]), recipm1=float(recipm1[t]), a=f32(A), b=f32(b), c=f32(c), b0=f32(B0)))
+        h_prev = h
+    return out
+
+
 CLIP_DEFAULT = ("dynamic", 0.9)        # the shipped pipeline's setting (FD:164)
 
 
@@ -123,6 +154,14 @@ def ancestral_sample_clip(ops, P: PackedUNet, cs: ClipState, x_init: Tensor, ste
                             clip=clip)
 
 
+def dpmpp_sample_clip(ops, P: PackedUNet, cs: ClipState, x_init: Tensor, steps: Sequence[dict], cond_scale: float = 1.0,
+                      cs_null: Optional[ClipState] = None, trace: Optional[list] = None, use_graph: bool = False,
+                      eager_every: int = 0, clip=CLIP_DEFAULT) -> Tensor:
+    """The DPM-Solver++(2M) loop (steps = dpmpp_step_scalars(...)): the evaluation, x0 and quantile of ddim_sample_clip, then
+    ops.dpmpp_update / ops.dpmpp_step_fixed.  Deterministic: no noise is drawn."""
+    return ddim_sample_clip(ops, P, cs, x_init, steps, None, cond_scale, cs_null, trace, use_graph, eager_every, kind="dpmpp", clip=clip)
+
+
 def ddim_sample_clip(ops, P: PackedUNet, cs: ClipState, x_init: Tensor, steps: Sequence[dict],
                      noise_fn: Callable[[int], Optional[Tensor]], cond_scale: float = 1.0,
                      cs_null: Optional[ClipState] = None, trace: Optional[list] = None, use_graph: bool = False,
@@ -136,11 +175,17 @@ def ddim_sample_clip(ops, P: PackedUNet, cs: ClipState, x_init: Tensor, steps: S
     clip (clip_mode): ("dynamic", q) runs the quantile selection at q; ("static",) / ("none",) need none -- the evaluation (guided:
     ending in ops.cfg_combine, the eps ops.cfg_x0 forms) is followed by ONE fused launch for the whole step tail
     (ops.ddim_step_fixed / ops.ancestral_step_fixed) and, T-sharded, by no all-reduce.  Trace entries: eps, x and s (static: a
-    constant [1, 1] tensor; none: None)."""
-    if kind not in ("ddim", "ancestral"):
+    constant [1, 1] tensor; none: None).
+    kind = "dpmpp": the step tail of DPM-Solver++(2M) (dpmpp_sample_clip; noise_fn is never called).  ONE history tensor holds the
+    clipped x0 of the previous step; the tail updates it in place and is handed it only when the step's c != 0 (it is uninitialised
+    before the first step).  Trace entries carry `x0c`, a copy of it, next to eps, s and x."""
+    if kind not in ("ddim", "ancestral", "dpmpp"):
         raise ValueError(f"unknown sampler step kind {kind!r}")
-    ancestral = kind == "ancestral"
+    ancestral, dpmpp = kind == "ancestral", kind == "dpmpp"
     clip_kind, q = clip_mode(clip, ancestral)
+    if dpmpp and steps and steps[0]["c"] != 0.0:
+        raise ValueError("dpmpp steps: steps[0]['c'] != 0, but the first step has no history")
+    hist_v = None                                # dpmpp: the clipped x0 of the previous step
     s_one = None
     x = x_init.contiguous()
     n_total = 3 * cs.Ttotal * cs.h * cs.w
@@ -172,7 +217,10 @@ def ddim_sample_clip(ops, P: PackedUNet, cs: ClipState, x_init: Tensor, steps: S
             else:
                 eps = graphed(x, st["t"]) if replay else unet_forward(ops, P, cs, x, st["t"])
             clamp = clip_kind == "static"
-            if ancestral:
+            if dpmpp:
+                x, hist_v = ops.dpmpp_step_fixed(x, eps, hist_v if st["c"] != 0.0 else None, st["recip"], st["recipm1"], st["a"], st["b"],
+                                                 st["c"], clamp, v_out=hist_v)
+            elif ancestral:
                 noise = noise_fn(i) if st["t"] > 0 else None
                 x = ops.ancestral_step_fixed(x, eps, noise, st["recip"], st["recipm1"], st["c1"], st["c2"], st["std"], clamp)
             else:
@@ -182,6 +230,8 @@ def ddim_sample_clip(ops, P: PackedUNet, cs: ClipState, x_init: Tensor, steps: S
                 if clamp and s_one is None:
                     s_one = torch.ones(2, device=x.device, dtype=torch.float32)
                 trace.append(dict(eps=eps.clone() if graphed is not None and not guided else eps, s=s_one if clamp else None, x=x))
+                if dpmpp:
+                    trace[-1]["x0c"] = hist_v.clone()
             continue
         if guided:
             eps_c, eps_null = graphed(x, st["t"]) if replay else unet_forward_guided(ops, P, cs, cs_null, x, st["t"])
@@ -191,7 +241,9 @@ def ddim_sample_clip(ops, P: PackedUNet, cs: ClipState, x_init: Tensor, steps: S
             eps = graphed(x, st["t"]) if replay else unet_forward(ops, P, cs, x, st["t"])
             x0, hist = ops.ddim_x0(x, eps, st["recip"], st["recipm1"])
         s = ops.quantile_threshold(x0, hist, n_total, q)
-        if ancestral:
+        if dpmpp:
+            x, hist_v = ops.dpmpp_update(x0, s, x, hist_v if st["c"] != 0.0 else None, st["a"], st["b"], st["c"], v_out=hist_v)
+        elif ancestral:
             noise = noise_fn(i) if st["t"] > 0 else None
             x = ops.ancestral_update(x0, x, s, noise, st["c1"], st["c2"], st["std"])
         else:
@@ -200,4 +252,6 @@ def ddim_sample_clip(ops, P: PackedUNet, cs: ClipState, x_init: Tensor, steps: S
         if trace is not None:
             # a graphed evaluation returns its static output buffer: clone, or every entry would alias the last step
             trace.append(dict(eps=eps.clone() if graphed is not None and not guided else eps, s=s, x=x))
+            if dpmpp:
+                trace[-1]["x0c"] = hist_v.clone()
     return x

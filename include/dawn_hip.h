@@ -389,6 +389,40 @@ int dawn_ddim_step_fixed(const float* x, const float* eps, const float* noise, f
                          float c, float sigma, int clamp, long n, float* x0_out, float* out, void* stream);
 int dawn_ancestral_step_fixed(const float* x_t, const float* eps, const float* noise, float recip, float recipm1, float c1, float c2,
                               float std, int clamp, long n, float* x0_out, float* out, void* stream);
+/* ---- DPM-Solver++(2M) (Lu et al. 2022, "DPM-Solver++: Fast Solver for Guided Sampling of Diffusion Probabilistic Models"): a
+ * second-order multistep solver in the data prediction, one evaluation per step like DDIM.  NOT in the reference: its values are THIS
+ * definition, checked in fp64.  Quality against the number of steps on a trained checkpoint has not been measured by anyone; nothing
+ * here says that fewer steps are as good as 50 DDIM steps.
+ *   Steps are the DDIM time pairs (t, t_next) of ddim_time_pairs(S, timesteps).  The state at time t lies at the noise level the DDIM
+ *   loop already uses, read from the fp32 table and then carried in fp64:
+ *       abar = alphas_cumprod_prev[t], abar_n = alphas_cumprod_prev[t_next]
+ *       alpha = sqrt(abar), sigma = sqrt(1 - abar), and alpha_n, sigma_n likewise.
+ *   x0 is formed as everywhere else, recip[t]*x - recipm1[t]*eps with the non-_prev tables (the guided eps when guided), and clipped by
+ *   the clip mode (dynamic at q, static, or none) as in the DDIM loop.  The clipped value v is what the solver sees and what the history
+ *   keeps.  Per step i:
+ *       rho = (sigma_n*alpha)/(alpha_n*sigma)       (= e^(-h); formed as this ratio so that sigma_n = 0 gives 0, not inf)
+ *       A   = sigma_n/sigma      B0 = alpha_n*(1 - rho)      h = -ln rho   (only when sigma_n > 0)
+ *       first order  (i = 0, or i = S-1 [lower-order final step], or sigma_n = 0, or order = 1):  b = B0,              c = 0
+ *       second order (otherwise), r = h_prev / h:                                                b = B0*(1 + 1/(2r)), c = -B0/(2r)
+ *       x_next = A*x + b*v + c*v_prev
+ *   (a step whose h or h_prev is not positive -- two equal times, which ddim_time_pairs gives only for S close to timesteps -- is first
+ *   order too: r would be 0 or infinite.)  A, b, c are rounded to fp32 once, on the host.  The last step has sigma_n = 0 (A = 0, b = 1):
+ *   it returns v itself, the clipped x0, like the other loops.  No noise is drawn; ddim_sampling_eta is not read.
+ * The two step tails.  Rounding order, the same in both and in their 128-bit and scalar paths (so every host is bit-identical):
+ *       out = fma(c, v_prev, (A*x) + (b*v))         three roundings for (A*x) + (b*v), one more for the history term
+ *   dawn_dpmpp_update      dynamic mode: v = clamp(x0,-s,s)/s with s = s[0] of dawn_select_finalize (one more rounding, the division)
+ *   dawn_dpmpp_step_fixed  static (clamp = 1) and none (clamp = 0) in ONE launch: x0 = fma(recip, x, -(recipm1*eps)), the roundings of
+ *                          dawn_ddim_x0 (as dawn_ddim_step_fixed); v = clamp(x0,-1,1) or x0; x0 does not go through memory
+ *   so dawn_dpmpp_step_fixed equals dawn_ddim_x0 followed by dawn_dpmpp_update bit for bit at s = 1 (static) and with the clamp removed
+ *   (none) -- the relation dawn_ddim_step_fixed has to dawn_ddim_x0 + dawn_ddim_update.  v_out = v (the next step's history) is always
+ *   written.  v_prev = NULL drops the history term: hosts pass NULL whenever c == 0, because the history buffer is uninitialised on
+ *   the first step and 0*NaN is NaN.  Aliasing: out == x and v_out == v_prev are allowed (each thread reads before it writes); any other
+ *   overlap between an output and an input or the other output is an error return with a message, nothing launched.  128-bit accesses
+ *   when every pointer is 16-byte aligned and n >= 4, scalar otherwise; any n >= 0. */
+int dawn_dpmpp_update(const float* x0, const float* s, const float* x, const float* v_prev, float A, float b, float c, long n,
+                      float* v_out, float* out, void* stream);
+int dawn_dpmpp_step_fixed(const float* x, const float* eps, const float* v_prev, float recip, float recipm1, float A, float b, float c,
+                          int clamp, long n, float* v_out, float* out, void* stream);
 /* classifier-free guidance (Unet3D.forward_with_cond_scale MT:889-890): out = null + (cond-null)*scale */
 int dawn_cfg_combine(const float* e_null, const float* e_cond, float scale, long n, float* out, void* stream);
 /* cfg_combine then ddim_x0 in one pass: eps_out = null + (cond-null)*scale, x0_out = recip*x - recipm1*eps_out, and the 2048-bin
@@ -516,7 +550,8 @@ int dawn_attn_win32(const float* q, int ldq, const float* k, int ldk, const floa
  *                      sigma-affine cross-attention tables, rotary + relative-position tables)   [FD:332-350, MT:1151,1167]
  *   dawn_unet_forward  one Unet3D.forward (null_cond_prob = 0) of one clip                       [MT:892-956]
  *   dawn_sampler_run   the DDIM loop: S x (forward, x0, dynamic-threshold quantile at 0.9, update)  [MT:1156-1208]
- *                      (other clipping modes / percentiles: dawn_sampler_run_clip, dawn_sampler_run_ancestral_clip below)
+ *                      (other clipping modes / percentiles: dawn_sampler_run_clip, dawn_sampler_run_ancestral_clip below;
+ *                      DPM-Solver++(2M) on the same time pairs, not in the reference: dawn_sampler_run_dpmpp)
  * No allocation, no synchronisation: the caller owns the clip memory (dawn_clip_bytes) and the workspace
  * (dawn_workspace_bytes); launches go to `stream` and to one ctx-owned side stream forked / joined with events.
  * One host thread per ctx.  Single GPU (the T-shard exchanges live in the Python host, tshard.py). */
@@ -665,6 +700,19 @@ int dawn_sampler_run_ancestral_clip(dawn_ctx* ctx, int F, int h, int w, const vo
                                     float cond_scale, const float* x_init, int S, const dawn_ancestral_step* steps, uint64_t seed,
                                     const float* const* noises, float* x_out, float* thresholds, void* workspace,
                                     size_t workspace_bytes, const dawn_shard_comm* comm, const dawn_clip_mode* clip, void* stream);
+/* ---- DPM-Solver++(2M) on the whole path (the definition stands with dawn_dpmpp_update above; host arithmetic of the steps:
+ * sampler.dpmpp_step_scalars).  a, b, c: the fp32-rounded A, b, c of the definition; c == 0 marks a first-order step. */
+typedef struct dawn_dpmpp_step { int t; float recip, recipm1; float a, b, c; } dawn_dpmpp_step;
+/* ONE entry for every form: guided when null_clip_mem != NULL and cond_scale != 1, T-sharded when comm != NULL, clip = NULL means
+ * {DAWN_CLIP_DYNAMIC, 0.9}.  Per step: the evaluation, x0, the threshold selection (dynamic only), then dawn_dpmpp_update (dynamic) or
+ * dawn_dpmpp_step_fixed (static / none) with v_prev = NULL when steps[i].c == 0.  Deterministic: no seed, no noises.  The `noise` latent
+ * of the sampler state carries the one-step history v_prev, so the existing workspace queries cover this entry (dawn_workspace_bytes,
+ * dawn_workspace_bytes_sharded, dawn_workspace_bytes_guided).  T-sharded, the dynamic mode keeps the four histogram / minimum
+ * all-reduces per step; static and none need none (allreduce_sum_u32 / allreduce_min_u32 may then be NULL).  thresholds as for
+ * dawn_sampler_run_clip.  steps[0].c != 0 (no history exists yet) is refused before the first launch. */
+int dawn_sampler_run_dpmpp(dawn_ctx* ctx, int F, int h, int w, const void* clip_mem, const void* null_clip_mem, float cond_scale,
+                           const float* x_init, int S, const dawn_dpmpp_step* steps, float* x_out, float* thresholds, void* workspace,
+                           size_t workspace_bytes, const dawn_shard_comm* comm, const dawn_clip_mode* clip, void* stream);
 /* ---- SURVEY 8(f) N1 + N2 as a whole path: the LFG flow decode of a sampled clip, down to uint8 frames (csrc/dawn_decoder.hip).
  * The same launch sequence as dawn-pytorch_amd/flow_decoder.py (FlowDecoder.encode / _decode_frames / decode_clip), results bit-identical
  * to it (tests/test_hip_decode_u8.py).  Same contract as dawn_ctx: opaque handle, device pointers by name, caller-owned memory, every
