@@ -192,6 +192,18 @@ SIGNATURES = {
     "dawn_resample16k_f32": [c_f, _l, _i, c_f, _l, c_f, C.c_size_t, c_f],
     "dawn_generate_media_rate_bytes": [c_f, _i, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)],
     "dawn_generate_clip_media_rate": [c_f, _i, c_f, C.c_size_t, c_f],
+    # model bundle (csrc/dawn_bundle.hip; the handle, the table / blob out-pointers and the dawn_generate_args travel as void*: bundle.py, ctx.py)
+    "dawn_bundle_open": [C.c_char_p, c_f],
+    "dawn_bundle_close": [c_f],
+    "dawn_bundle_device_bytes": [c_f],
+    "dawn_bundle_verify_workspace_bytes": [c_f],
+    "dawn_bundle_upload": [c_f, c_f, C.c_size_t, c_f],
+    "dawn_bundle_verify": [c_f, c_f, C.c_size_t, c_f, C.c_size_t, c_f],
+    "dawn_bundle_table": [c_f, _i, c_f, c_f, C.POINTER(C.c_int)],
+    "dawn_bundle_cfg": [c_f, _i, c_f, C.c_size_t],
+    "dawn_bundle_host": [c_f, C.c_char_p, c_f, C.POINTER(C.c_size_t)],
+    "dawn_bundle_create_handles": [c_f, c_f, c_f],
+    "dawn_bundle_destroy_handles": [c_f],
 }
 # device helpers of the C-side evaluator (csrc/dawn_ctx.hip calls them; from Python only the op tests do)
 CTX_HELPER_SIGNATURES = {
@@ -228,7 +240,8 @@ LONG_RESULT = {"dawn_sla_ws_floats", "dawn_workspace_bytes_guided", "dawn_decode
                "dawn_hubert_conv_frames", "dawn_hubert_workspace_bytes", "dawn_pbnet_workspace_bytes",
                "dawn_pose_blink_workspace_bytes", "dawn_clip_bytes", "dawn_workspace_bytes",
                "dawn_workspace_bytes_sharded", "dawn_image_ingest_workspace_bytes", "dawn_resample16k_len",
-               "dawn_resample16k_workspace_bytes"}        # entry points that return a size (long), not a status
+               "dawn_resample16k_workspace_bytes", "dawn_bundle_device_bytes",
+               "dawn_bundle_verify_workspace_bytes"}      # entry points that return a size (long), not a status
 
 
 def lib() -> C.CDLL:

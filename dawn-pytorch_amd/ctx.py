@@ -1106,3 +1106,92 @@ class PipelineEvaluator:
             check(self.L.dawn_generate_clip_media_rate(C.addressof(m), rate, workspace.data_ptr(), workspace.numel(), _Evaluator._stream()),
                   "dawn_generate_clip_media_rate")
         return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the same pipeline from a model bundle file (include/dawn_hip.h: "model bundle"; csrc/dawn_bundle.hip): what a host without Python does
+class _BundleStage:
+    """What PipelineEvaluator asks of a stage evaluator: the handle and the cfg struct (the bundle owns handles and weights)."""
+
+    def __init__(self, h, cfg, device):
+        self.h, self.cfg, self.device = h, cfg, device
+
+
+class BundleEvaluator(PipelineEvaluator):
+    """PipelineEvaluator whose six handles come from a bundle file through the C loader: dawn_bundle_open -> upload into one torch uint8
+    tensor (`mem`) -> verify on the device -> dawn_bundle_create_handles.  The same `args / sizes / generate / from_media / media_sizes /
+    generate_media` surface, plus `steps(name)`, `defaults()`, `cfg(stage)`, `table(stage)` and `tensor(stage, name)` (the uploaded
+    bytes of one entry)."""
+
+    def __init__(self, path, device="cuda:0", verify: bool = True):
+        from . import bundle
+        self.L = _lib.lib()
+        self.device = torch.device(device)
+        self.path = os.fspath(path)
+        self.b, self._args = None, None
+        b = C.c_void_p()
+        check(self.L.dawn_bundle_open(self.path.encode(), C.addressof(b)), "dawn_bundle_open")
+        self.b = b
+        self.index = bundle.read_index(self.path)
+        with torch.cuda.device(self.device):
+            self.mem = torch.empty(max(int(self.L.dawn_bundle_device_bytes(self.b)), 1), dtype=torch.uint8, device=self.device)
+            check(self.L.dawn_bundle_upload(self.b, self.mem.data_ptr(), self.mem.numel(), _Evaluator._stream()), "dawn_bundle_upload")
+            if verify:
+                self.verify()
+            a = GenerateArgs()
+            check(self.L.dawn_bundle_create_handles(self.b, self.mem.data_ptr(), C.addressof(a)), "dawn_bundle_create_handles")
+        self._args = a
+        cfgs = (HubertCfg, PbnetCfg, PbnetCfg, DecoderCfg, InputsCfg, UnetCfg)
+        handles = (a.hubert, a.pose, a.blink, a.decoder, a.inputs, a.unet)
+        self.ev = tuple(_BundleStage(h, self.cfg(s, cls), self.device) for s, (h, cls) in enumerate(zip(handles, cfgs)))
+        self._ws: Optional[Tensor] = None
+
+    def __del__(self):
+        a, self._args = getattr(self, "_args", None), None
+        if a is not None:
+            self.L.dawn_bundle_destroy_handles(C.addressof(a))
+        b, self.b = getattr(self, "b", None), None
+        if b:
+            self.L.dawn_bundle_close(b)
+
+    def verify(self, workspace: Optional[Tensor] = None) -> None:
+        """dawn_bundle_verify of `mem`; raises DawnHipError naming the first failing stage and tensor."""
+        if workspace is None:
+            workspace = torch.empty(int(self.L.dawn_bundle_verify_workspace_bytes(self.b)), dtype=torch.uint8, device=self.device)
+        check(self.L.dawn_bundle_verify(self.b, self.mem.data_ptr(), self.mem.numel(), workspace.data_ptr(), workspace.numel(),
+                                        _Evaluator._stream()), "dawn_bundle_verify")
+
+    def cfg(self, stage: int, cls):
+        out = cls()
+        check(self.L.dawn_bundle_cfg(self.b, stage, C.addressof(out), C.sizeof(out)), "dawn_bundle_cfg")
+        return out
+
+    def host(self, name: str) -> bytes:
+        p, n = C.c_void_p(), C.c_size_t(0)
+        check(self.L.dawn_bundle_host(self.b, name.encode(), C.addressof(p), C.byref(n)), "dawn_bundle_host")
+        return C.string_at(p.value, n.value)
+
+    def steps(self, name: str) -> List[dict]:
+        """The step table "steps.<name>" ("ddim.20", "ancestral.1000") as the dicts `args(...)` takes."""
+        raw = self.host(f"steps.{name}")
+        cls = AncestralStep if name.startswith("ancestral.") else DdimStep
+        arr = (cls * (len(raw) // C.sizeof(cls))).from_buffer_copy(raw)
+        return [{f: getattr(s, f) for f, _ in cls._fields_} for s in arr]
+
+    def defaults(self):
+        from .bundle import Defaults
+        return Defaults.from_buffer_copy(self.host("defaults"))
+
+    def table(self, stage: int) -> Dict[str, int]:
+        """{name: device address} of dawn_bundle_table for `mem`."""
+        t, n = C.c_void_p(), C.c_int(0)
+        check(self.L.dawn_bundle_table(self.b, stage, self.mem.data_ptr(), C.addressof(t), C.byref(n)), "dawn_bundle_table")
+        arr = C.cast(t, C.POINTER(NamedPtr))
+        return {arr[i].name.decode(): int(arr[i].ptr) for i in range(n.value)}
+
+    def tensor(self, stage: str, name: str) -> Tensor:
+        """The uploaded bytes of one device entry (its zero padding to whole words included): a view of `mem`."""
+        for e in self.index["entries"]:
+            if e["kind"] == 0 and e["stage"] == stage and e["name"] == name:
+                return self.mem[e["offset"]:e["offset"] + e["length"]]
+        raise KeyError(f"{stage}/{name}")

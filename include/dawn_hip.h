@@ -1047,6 +1047,75 @@ int dawn_resample16k_f32(const float* x, long n_frames, int rate, float* out, lo
  * entry's name, before the first launch.  The rate is a parameter, not a field: dawn_media_args is unchanged. */
 int dawn_generate_media_rate_bytes(const dawn_media_args* args, int pcm_rate, size_t* clip_bytes, size_t* workspace_bytes);
 int dawn_generate_clip_media_rate(const dawn_media_args* args, int pcm_rate, void* workspace, size_t workspace_bytes, void* stream);
+/* ---- model bundle (csrc/dawn_bundle.hip, csrc/dawn_bundle_format.h): ONE file that holds everything the six *_create calls and
+ * dawn_generate_args need besides the media -- the packed weight tables, the six cfg structs, named step tables and a defaults
+ * record -- so that a host without Python runs the pipeline (tools/dawn_generate.cpp).  Python writes it (dawn_pytorch_amd/bundle.py:
+ * the packers of pack.py / ctx.py stay the one definition of every packed layout; the loader copies bytes and never looks inside).
+ * THE FORMAT, version 1.  Little-endian, every offset and size an unsigned 64-bit number, no compression, nothing optional.
+ *   header, 64 bytes:   0 magic "DAWNBNDL"   8 u32 version = 1   12 u32 abi (dawn_abi_version() the struct blobs were written for)
+ *                       16 u64 n_entries   24 u64 index_bytes   32 u64 payload_offset (multiple of 256, at or after the index end)
+ *                       40 u64 device_bytes (multiple of 256)   48 u64 file_bytes (the whole file)   56 u64 zero
+ *   index at byte 64, index_bytes long, n_entries entries back to back, each 48 bytes + the name:
+ *                       0 u32 stage (DAWN_STAGE_*)   4 u32 kind (DAWN_BUNDLE_DEVICE / _HOST)   8 u32 dtype (informational: 0 bytes,
+ *                       1 f32, 2 bf16, 3 f16, 4 i32, 5 f64, 6 i64, 7 i16)   12 u32 name_len (1 .. 4096)   16 u64 offset from the payload
+ *                       start   24 u64 length in bytes   32 u64 s1   40 u64 s2   48 the name, zero-padded to a multiple of 8 bytes
+ *   payload at payload_offset: first the device part, bytes [0, device_bytes), then the host part up to the end of the file.
+ *     device tensor: offset a multiple of 256, length the tensor's bytes zero-padded to a multiple of 4 (a bf16 split image may hold an
+ *                    odd element count), inside the device part; the bytes between tensors are zero.  The device part goes to the GPU
+ *                    as one region and a tensor's pointer is base + offset.
+ *     host blob:     offset a multiple of 16, inside the host part (at most 64 MiB).  "cfg" of a stage = the raw bytes of its cfg struct
+ *                    (dawn_hubert_cfg, dawn_pbnet_cfg for pose and blink, dawn_decoder_cfg, dawn_inputs_cfg, dawn_unet_cfg); in the stage
+ *                    DAWN_STAGE_HOST: "defaults" = one dawn_bundle_defaults, "steps.ddim.<S>" = S dawn_ddim_step,
+ *                    "steps.ancestral.<S>" = S dawn_ancestral_step (written by sampler.ddim_step_scalars / ancestral_step_scalars:
+ *                    the schedule arithmetic keeps its single definition); other names are the host's own.
+ *   A length of 0, two entries that overlap, a name given twice within (stage, kind), a struct blob whose length is not its sizeof
+ *   (a step table: not a multiple of it): refused.
+ *   checksum of an entry: its bytes (a host blob zero-padded to whole words) as n little-endian 32-bit words w[0..n-1],
+ *     s1 = sum w[i] mod 2^64, s2 = sum (i + 1) w[i] mod 2^64.  A flipped bit changes s1, two exchanged unequal words change s2.  It is an
+ *     INTEGRITY check against truncated files, bad copies and stale bundles; it is NO protection against tampering.
+ * THE LOADER.  dawn_bundle_open is host code (no GPU call): it reads and validates header, index and host part (host blobs are checked
+ * against their checksums there) and refuses, with a message that names the field or the entry, everything the format forbids, an ABI
+ * number other than dawn_abi_version() and a file whose size is not the header's; all offset arithmetic is overflow-checked.
+ * dawn_bundle_upload copies the device part of the file into the caller's allocation (256-byte aligned, at least
+ * dawn_bundle_device_bytes): the ONE entry that does file I/O, and it BLOCKS until the copy is done (it synchronises `stream`); its
+ * staging memory is the library's own, two pinned buffers of 8 MiB whatever the file size.
+ * dawn_bundle_verify checksums every device tensor ON THE DEVICE (so the copy is covered too): the host cuts the tensors into work
+ * items (tensor, first word, at most 65536 words), ONE launch (per 2^20 items) writes one (s1, s2) pair per item into the workspace
+ * [work list | partials] of dawn_bundle_verify_workspace_bytes, the host adds the pairs per tensor in exact 64-bit integers and compares
+ * with the index.  Integer arithmetic only: the result does not depend on launch geometry or order.  It BLOCKS (it reads the pairs back)
+ * and returns non-zero naming the first failing stage and tensor.  Both refuse a short allocation before touching anything.
+ * dawn_bundle_table yields the dawn_named_ptr array of a stage for the region at device_mem, owned by the handle and valid until close
+ * (or the next call for that stage); pass it straight to dawn_*_create.  dawn_bundle_cfg copies a stage's cfg struct (out_bytes must be
+ * its sizeof); dawn_bundle_host returns a blob of DAWN_STAGE_HOST by name (pointer into the handle).
+ * dawn_bundle_create_handles creates all six handles from the region and fills the six handle fields of `args` (nothing else of it);
+ * DAWN_OPT_UP_BORDER is set from the defaults record when the bundle has one.  A stage missing from the file is an error that names it;
+ * on any error the handles made so far are destroyed and `args` is untouched.  dawn_bundle_destroy_handles destroys the six and zeroes
+ * the fields.  The region must outlive the handles. */
+typedef struct dawn_bundle dawn_bundle;
+enum { DAWN_STAGE_HUBERT = 0, DAWN_STAGE_POSE = 1, DAWN_STAGE_BLINK = 2, DAWN_STAGE_DECODER = 3, DAWN_STAGE_INPUTS = 4, DAWN_STAGE_UNET = 5,
+       DAWN_STAGE_HOST = 6 };
+enum { DAWN_BUNDLE_DEVICE = 0, DAWN_BUNDLE_HOST = 1 };
+/* what VideoGenerator takes from the yaml and its fallbacks (UVG:277-278, 329, 340-341) */
+typedef struct dawn_bundle_defaults {
+    int H, fea_ch, latent_dim, max_n_frames;         /* image side, the unet's fea_ch, the PBnets' latent width, the clip-length cap */
+    int sampling_step, ancestral;                    /* the default step table: "steps.ddim.<sampling_step>" (ancestral = 0) or "steps.ancestral.<..>" */
+    float cond_scale; int up_border;                 /* up_border: DAWN_OPT_UP_BORDER of the unet */
+    uint64_t random_seed;
+    double mean[3];                                  /* mean_c as the yaml holds it (0..255); dawn_generate_args.mean3 = mean / 255 */
+    float bbox6[6]; float init_pose6[6]; float init_blink2[2];
+    dawn_clip_mode clip;
+} dawn_bundle_defaults;
+int dawn_bundle_open(const char* path, dawn_bundle** out);
+void dawn_bundle_close(dawn_bundle* b);
+size_t dawn_bundle_device_bytes(const dawn_bundle* b);
+size_t dawn_bundle_verify_workspace_bytes(const dawn_bundle* b);
+int dawn_bundle_upload(dawn_bundle* b, void* device_mem, size_t bytes, void* stream);
+int dawn_bundle_verify(dawn_bundle* b, const void* device_mem, size_t bytes, void* workspace, size_t workspace_bytes, void* stream);
+int dawn_bundle_table(dawn_bundle* b, int stage, const void* device_mem, const dawn_named_ptr** table, int* n);
+int dawn_bundle_cfg(const dawn_bundle* b, int stage, void* out, size_t out_bytes);
+int dawn_bundle_host(const dawn_bundle* b, const char* name, const void** ptr, size_t* bytes);
+int dawn_bundle_create_handles(dawn_bundle* b, const void* device_mem, dawn_generate_args* args);
+void dawn_bundle_destroy_handles(dawn_generate_args* args);
 /* after a stream synchronise: (kind, algorithmic flops, algorithmic bytes, ms) per conv launch recorded under
  * DAWN_OPT_PROFILE; kind 0 = split 3x3, 1 = split 1x1, 2 = fp32 MFMA; returns the number of entries (and clears them) */
 int dawn_ctx_profile_read(dawn_ctx* ctx, double* out4, int max_entries);
