@@ -192,6 +192,12 @@ SIGNATURES = {
     "dawn_resample16k_f32": [c_f, _l, _i, c_f, _l, c_f, C.c_size_t, c_f],
     "dawn_generate_media_rate_bytes": [c_f, _i, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)],
     "dawn_generate_clip_media_rate": [c_f, _i, c_f, C.c_size_t, c_f],
+    # LFG motion encode (csrc/motion_encode.hip): driving video -> flow / occlusion latent (motion_encoder.py)
+    "dawn_antialias_down": [c_f, _i, _l, _l, _i, _i, _i, _i, c_f, _i, _i, c_f],
+    "dawn_region_moments": [c_f, _i, _i, _i, _i, _i, _d, c_f, c_f, c_f, c_f],
+    "dawn_bg_params": [c_f, _i, _i, _i, _i, c_f, c_f, c_f, c_f],
+    "dawn_motion_inputs": [c_f, c_f, c_f, c_f, c_f, c_f, c_f, _i, c_f, _i, _i, _i, _i, c_f, _i, _i, c_f],
+    "dawn_flow_combine": [c_f, _i, c_f, c_f, c_f, c_f, c_f, _i, _i, _i, _i, c_f, _l, c_f, _i, c_f],
     # model bundle (csrc/dawn_bundle.hip; the handle, the table / blob out-pointers and the dawn_generate_args travel as void*: bundle.py, ctx.py)
     "dawn_bundle_open": [C.c_char_p, c_f],
     "dawn_bundle_close": [c_f],

@@ -22,6 +22,7 @@ import torch.nn.functional as F_
 
 from .diffusion import DynamicNfGaussianDiffusion
 from .flow_decoder import FlowDecoder
+from .motion_encoder import MotionEncoder
 from .unet import DynamicNfUnet3D
 
 
@@ -62,8 +63,11 @@ class FlowDiffusion(nn.Module):
     def __init__(self, img_size=32, num_frames=40, sampling_timesteps=250, win_width=40, null_cond_prob=0.1,
                  ddim_sampling_eta=1., pose_dim=7, dim_mults=(1, 2, 4, 8), is_train=True, use_residual_flow=False,
                  learn_null_cond=False, use_deconv=True, padding_mode="zeros", pretrained_pth=None, config_pth=None,
-                 generator=None, device=None, native_decode: Optional[bool] = None):
-        """`native_decode`: True = decode on the HIP kernels (error without a GPU / the extension), False = call the
+                 generator=None, device=None, native_decode: Optional[bool] = None, region_predictor=None, bg_predictor=None,
+                 motion_encoder: Optional[MotionEncoder] = None):
+        """`region_predictor`, `bg_predictor` (the reference's unchanged modules, beside its `generator` module) or a ready `motion_encoder`:
+        the LFG's encode half, needed by `encode_video` / `reenact` only (FD:124-136 loads them from the same checkpoint).
+        `native_decode`: True = decode on the HIP kernels (error without a GPU / the extension), False = call the
         injected generator's `forward_with_flow` frame by frame exactly like FD:375-383, None (default) = HIP kernels
         whenever the clip is on the GPU."""
         super().__init__()
@@ -75,6 +79,7 @@ class FlowDiffusion(nn.Module):
         self.generator = generator
         self.native_decode = native_decode
         self._decoder: Optional[FlowDecoder] = generator if isinstance(generator, FlowDecoder) else None
+        self.region_predictor, self.bg_predictor, self._motion = region_predictor, bg_predictor, motion_encoder
         self.pose_dim = pose_dim
         self.unet = DynamicNfUnet3D(dim=64, cond_dim=1024 + pose_dim + 2, cond_aud=1024, cond_pose=pose_dim,
                                     cond_eye=2, num_frames=num_frames, channels=3 + 256 + 16, out_grid_dim=2,
@@ -101,6 +106,15 @@ class FlowDiffusion(nn.Module):
         if self._decoder is None:
             self._decoder = FlowDecoder.from_generator(self.generator, device)
         return self._decoder
+
+    def motion_encoder(self, device) -> MotionEncoder:
+        """The HIP encode half (weights packed once, on first use)."""
+        if self._motion is None:
+            if self.region_predictor is None or self.bg_predictor is None or not hasattr(self.generator, "state_dict"):
+                raise ValueError("encode_video / reenact need the LFG's encode half: pass motion_encoder=, or region_predictor= and "
+                                 "bg_predictor= beside the reference's generator module")
+            self._motion = MotionEncoder.from_modules(self.generator, self.region_predictor, self.bg_predictor, device)
+        return self._motion
 
     def decodes_natively(self, sample_img) -> bool:
         """Does sample_one_video decode this clip with `FlowDecoder` (rather than frame by frame through the injected generator)?"""
@@ -158,6 +172,59 @@ class FlowDiffusion(nn.Module):
                                              None if init_eye is None else init_eye[0].tolist())
         return fea16.unsqueeze(0), cond.unsqueeze(0)
 
+    def _decode_bytes(self, sample_img, grid, conf, frames_u8: dict):
+        """The `frames_u8` options of sample_one_video / reenact on a latent: -> (output key, the byte tensor or the chunk generator)."""
+        kw = dict(frames_u8)
+        stream = kw.pop("stream", False)
+        fmt = kw.pop("format", "rgb")
+        if fmt not in ("rgb", "yuv420p"):
+            raise ValueError(f"frames_u8 format must be 'rgb' or 'yuv420p', not {fmt!r}")
+        if fmt == "yuv420p" and kw.pop("bgr", False):
+            raise ValueError("frames_u8 format='yuv420p' has no channel order: bgr=True is not allowed")
+        dec = self.flow_decoder(sample_img.device)
+        if stream and sample_img.shape[0] != 1:
+            raise ValueError("frames_u8 stream=True takes one clip (B == 1)")
+        if fmt == "yuv420p":
+            fn = dec.stream_frames_yuv420 if stream else dec.decode_clip_yuv420
+            return "sample_frames_yuv420", fn(sample_img, grid, conf, **kw)
+        fn = dec.stream_frames_u8 if stream else dec.decode_clip_u8
+        return "sample_frames_u8", fn(sample_img, grid, conf, **kw)
+
+    def _encode(self, ref_img, real_vid):
+        """ref_img (B,3,H,W), real_vid (B,3,T,H,W) fp32 in [0,1] -- or, B == 1, (T,H,W,3) uint8 frames -> grid (B,2,T,h,w), conf (B,1,T,h,w)."""
+        me = self.motion_encoder(ref_img.device)
+        if real_vid.dtype == torch.uint8:
+            if ref_img.shape[0] != 1:
+                raise ValueError("uint8 driving frames (T,H,W,3) take one clip (B == 1)")
+            clips = [me.encode_clip(ref_img[0], real_vid)]
+        else:
+            clips = [me.encode_clip(ref_img[b], real_vid[b].permute(1, 0, 2, 3)) for b in range(ref_img.shape[0])]
+        return torch.cat([c["real_vid_grid"] for c in clips], 0), torch.cat([c["real_vid_conf"] for c in clips], 0)
+
+    @torch.no_grad()
+    def encode_video(self, ref_img, real_vid):
+        """What FlowDiffusion.forward computes under no_grad from a real clip (FD:248-262), with the reference's keys: real_vid_grid
+        (B,2,T,h,w), real_vid_conf (B,1,T,h,w) from the HIP encode half (`MotionEncoder`), real_out_vid / real_warped_vid (B,3,T,H,W) from
+        the batched `FlowDecoder` on that latent."""
+        grid, conf = self._encode(ref_img, real_vid)
+        dec = self.flow_decoder(ref_img.device).decode_clip(ref_img, grid, conf)
+        return {"real_vid_grid": grid, "real_vid_conf": conf, "real_out_vid": dec["sample_out_vid"], "real_warped_vid": dec["sample_warped_vid"]}
+
+    @torch.no_grad()
+    def reenact(self, sample_img, driving, frames_u8: Optional[dict] = None):
+        """Video-driven reenactment, the LFG's own use: the motion of `driving` ((B,3,T,H,W) fp32, or (T,H,W,3) uint8 frames for one
+        clip) encoded against `sample_img` (B,3,H,W) and decoded from it.  -> real_vid_grid, real_vid_conf, and sample_out_vid /
+        sample_warped_vid -- or, with `frames_u8` (the options of sample_one_video: RGB or format="yuv420p", stream or not),
+        sample_frames_u8 / sample_frames_yuv420 instead."""
+        grid, conf = self._encode(sample_img, driving)
+        out = {"real_vid_grid": grid, "real_vid_conf": conf}
+        if frames_u8 is not None:
+            key, frames = self._decode_bytes(sample_img, grid, conf, frames_u8)
+            out[key] = frames
+            return out
+        out.update(self.flow_decoder(sample_img.device).decode_clip(sample_img, grid, conf))
+        return out
+
     @torch.no_grad()
     def sample_one_video(self, sample_img, sample_audio_hubert, sample_pose, sample_eye, sample_bbox, cond_scale,
                          init_pose=None, init_eye=None, real_vid=None, frames_u8: Optional[dict] = None):
@@ -179,22 +246,8 @@ class FlowDiffusion(nn.Module):
         if frames_u8 is not None:
             if not native:
                 raise ValueError("sample_one_video(frames_u8=...) needs the native flow decode (native_decode, or a clip on the GPU)")
-            kw = dict(frames_u8)
-            stream = kw.pop("stream", False)
-            fmt = kw.pop("format", "rgb")
-            if fmt not in ("rgb", "yuv420p"):
-                raise ValueError(f"frames_u8 format must be 'rgb' or 'yuv420p', not {fmt!r}")
-            if fmt == "yuv420p" and kw.pop("bgr", False):
-                raise ValueError("frames_u8 format='yuv420p' has no channel order: bgr=True is not allowed")
-            dec = self.flow_decoder(sample_img.device)
-            if stream and sample_img.shape[0] != 1:
-                raise ValueError("frames_u8 stream=True takes one clip (B == 1)")
-            if fmt == "yuv420p":
-                fn = dec.stream_frames_yuv420 if stream else dec.decode_clip_yuv420
-                out["sample_frames_yuv420"] = fn(sample_img, out["sample_vid_grid"], out["sample_vid_conf"], **kw)
-                return out
-            fn = dec.stream_frames_u8 if stream else dec.decode_clip_u8
-            out["sample_frames_u8"] = fn(sample_img, out["sample_vid_grid"], out["sample_vid_conf"], **kw)
+            key, frames = self._decode_bytes(sample_img, out["sample_vid_grid"], out["sample_vid_conf"], frames_u8)
+            out[key] = frames
             return out
         if native:                                                                     # FD:372-385 as one batched decode
             out.update(self.flow_decoder(sample_img.device).decode_clip(sample_img, out["sample_vid_grid"],

@@ -1067,3 +1067,84 @@ class HipOps:
         else:
             check(self.L.dawn_resample16k_f32(_p(x), n, rate, _p(out), n_out, _p(ws), nbytes, self._stream()), "dawn_resample16k_f32")
         return out
+
+    # ------------------------------------------------------------------ LFG motion encode (csrc/motion_encode.hip; motion_encoder.py)
+    def antialias_down(self, frames: Tensor, s: int, c_pad: int = 16, out: Optional[Tensor] = None) -> Tensor:
+        """AntiAliasInterpolation2d at scale 1 / s (UTIL:217-264), only the kept pixels: frames fp32 (T,3,H,W) -- any frame and channel
+        stride with dense planes, so a (3,T,H,W) clip permuted to frames is taken as it is -- or uint8 (T,H,W,3) contiguous ->
+        rows (T * ceil(H/s) * ceil(W/s), c_pad): channels 0..2 the result, the rest zero (what dawn_conv_gemm's channel multiple needs)."""
+        _need(frames.is_cuda and frames.dim() == 4, "antialias_down: a GPU tensor, fp32 (T,3,H,W) or uint8 (T,H,W,3)")
+        if frames.dtype == torch.uint8:
+            _need(frames.shape[3] == 3 and frames.is_contiguous(), "antialias_down: uint8 frames are (T,H,W,3) contiguous")
+            T, H, W = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
+            kind, fs, cs = 1, H * W * 3, 1
+        else:
+            _need(frames.dtype == torch.float32 and frames.shape[1] == 3 and frames.stride(3) == 1 and frames.stride(2) == frames.shape[3],
+                  "antialias_down: fp32 frames are (T,3,H,W) with dense planes")
+            T, H, W = int(frames.shape[0]), int(frames.shape[2]), int(frames.shape[3])
+            kind, fs, cs = 0, (int(frames.stride(0)) if T > 1 else 3 * H * W), int(frames.stride(1))
+        ho, wo = -(-H // s), -(-W // s)
+        self._require(out)
+        if out is None:
+            out = self.empty(T * ho * wo, c_pad, like=frames)
+        _need(out.dtype == torch.float32 and tuple(out.shape) == (T * ho * wo, c_pad) and out.stride(1) == 1, "antialias_down: out fp32 (T*ho*wo, c_pad) rows")
+        check(self.L.dawn_antialias_down(_p(frames), kind, fs, cs, T, H, W, int(s), _p(out), _ld(out), c_pad, self._stream()), "dawn_antialias_down")
+        return out
+
+    def region_moments(self, x: Tensor, T: int, h: int, w: int, R: int, temperature: float) -> Tuple[Tensor, Tensor, Tensor]:
+        """RP:84-117 after the `regions` conv: x (T*h*w, >= R) rows -> (shift (T,R,2), covar (T,R,2,2), affine (T,R,2,2)); the sign
+        convention of affine's U is include/dawn_hip.h's (det U = -1)."""
+        _need(x.dim() == 2 and x.shape[0] == T * h * w and x.shape[1] >= R and x.stride(1) == 1, "region_moments: x (T*h*w, >= R) rows")
+        self._require(x)
+        shift = self.empty(T, R, 2, like=x)
+        covar = self.empty(T, R, 2, 2, like=x)
+        affine = self.empty(T, R, 2, 2, like=x)
+        check(self.L.dawn_region_moments(_p(x), _ld(x), T, h, w, R, float(temperature), _p(shift), _p(covar), _p(affine), self._stream()),
+              "dawn_region_moments")
+        return shift, covar, affine
+
+    def bg_params(self, x: Tensor, T: int, fc_w: Tensor, fc_b: Tensor) -> Tensor:
+        """BG:46-52 (bg_type 'affine') after the encoder: x (T*npix, C) rows = its last map -> (T,3,3)."""
+        C = x.shape[1]
+        _need(x.dim() == 2 and x.shape[0] % T == 0 and x.stride(1) == 1 and fc_w.is_contiguous() and tuple(fc_w.shape) == (6, C) and tuple(fc_b.shape) == (6,),
+              "bg_params: x (T*npix, C) rows, fc_w (6, C) contiguous, fc_b (6,)")
+        self._require(x, fc_w, fc_b)
+        out = self.empty(T, 3, 3, like=x)
+        check(self.L.dawn_bg_params(_p(x), _ld(x), T, x.shape[0] // T, C, _p(fc_w), _p(fc_b), _p(out), self._stream()), "dawn_bg_params")
+        return out
+
+    @staticmethod
+    def _region_params(name: str, p, lead: tuple, R: int):
+        shift, covar, affine = p
+        _need(tuple(shift.shape) == lead + (R, 2) and shift.is_contiguous(), f"{name}: shift {lead + (R, 2)} contiguous")
+        _need(covar is None or (tuple(covar.shape) == lead + (R, 2, 2) and covar.is_contiguous()), f"{name}: covar {lead + (R, 2, 2)} contiguous")
+        _need(tuple(affine.shape) == lead + (R, 2, 2) and affine.is_contiguous(), f"{name}: affine {lead + (R, 2, 2)} contiguous")
+
+    def motion_inputs(self, drv, src, bg: Tensor, src_rows: Tensor, T: int, h: int, w: int, c_pad: int) -> Tensor:
+        """PF:48-120: drv = (shift, covar, affine) of the T driving frames, src = the same of the source (no frame axis), bg (T,3,3),
+        src_rows (h*w, >= 3) the downsampled source -> the pixelwise hourglass's input rows (T*h*w, c_pad), channels past 4 (R+1) zero."""
+        R = int(src[0].shape[0])
+        self._region_params("motion_inputs: drv", drv, (T,), R)
+        self._region_params("motion_inputs: src", src, (), R)
+        _need(tuple(bg.shape) == (T, 3, 3) and bg.is_contiguous() and src_rows.dim() == 2 and src_rows.shape[0] == h * w and src_rows.stride(1) == 1,
+              "motion_inputs: bg (T,3,3) contiguous, src_rows (h*w, >= 3) rows")
+        self._require(*drv, *src, bg, src_rows)
+        out = self.empty(T * h * w, c_pad, like=bg)
+        check(self.L.dawn_motion_inputs(_p(drv[0]), _p(drv[1]), _p(drv[2]), _p(src[0]), _p(src[1]), _p(src[2]), _p(bg), R, _p(src_rows), _ld(src_rows),
+                                        T, h, w, _p(out), _ld(out), c_pad, self._stream()), "dawn_motion_inputs")
+        return out
+
+    def flow_combine(self, x: Tensor, drv, src, bg: Tensor, T: int, h: int, w: int, grid: Tensor, conf: Tensor, conf_x0: bool = False) -> None:
+        """PF:124-135: x (T*h*w, >= R+2) rows = the mask | occlusion conv -> grid (2,T,h,w) view (dense planes, any plane stride: a frame
+        range of a (2,Ttot,h,w) or (3,Ttot,h,w) clip) and conf (T,h,w) contiguous; conf_x0: conf receives 2 * occlusion - 1."""
+        R = int(src[0].shape[0])
+        self._region_params("flow_combine: drv", (drv[0], None, drv[2]), (T,), R)
+        self._region_params("flow_combine: src", (src[0], None, src[2]), (), R)
+        _need(x.dim() == 2 and x.shape[0] == T * h * w and x.shape[1] >= R + 2 and x.stride(1) == 1 and tuple(bg.shape) == (T, 3, 3) and bg.is_contiguous(),
+              "flow_combine: x (T*h*w, >= R+2) rows, bg (T,3,3) contiguous")
+        _need(tuple(grid.shape) == (2, T, h, w) and grid.stride(3) == 1 and grid.stride(2) == w and grid.stride(1) == h * w and grid.stride(0) >= T * h * w,
+              "flow_combine: grid (2,T,h,w) with dense planes")
+        _need(tuple(conf.shape) == (T, h, w) and conf.is_contiguous(), "flow_combine: conf (T,h,w) contiguous")
+        self._require(x, drv[0], drv[2], src[0], src[2], bg, grid, conf)
+        check(self.L.dawn_flow_combine(_p(x), _ld(x), _p(drv[0]), _p(drv[2]), _p(src[0]), _p(src[2]), _p(bg), R, T, h, w, _p(grid), grid.stride(0),
+                                       _p(conf), 1 if conf_x0 else 0, self._stream()), "dawn_flow_combine")

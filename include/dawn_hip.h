@@ -1047,6 +1047,61 @@ int dawn_resample16k_f32(const float* x, long n_frames, int rate, float* out, lo
  * entry's name, before the first launch.  The rate is a parameter, not a field: dawn_media_args is unchanged. */
 int dawn_generate_media_rate_bytes(const dawn_media_args* args, int pcm_rate, size_t* clip_bytes, size_t* workspace_bytes);
 int dawn_generate_clip_media_rate(const dawn_media_args* args, int pcm_rate, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- LFG motion encode, batched over the frames of a driving video (csrc/motion_encode.hip) -------------------------
+ * The encode half of the frozen LFG (FD:248-262): RegionPredictor (RP = LFG/modules/region_predictor.py), BGMotionPredictor (BG =
+ * bg_motion_predictor.py) and Generator.forward's PixelwiseFlowPredictor (PF = pixelwise_flow_predictor.py; UTIL = util.py), for the
+ * shipped configuration (pca_based, estimate_affine, revert_axis_swap, bg_type 'affine', use_deformed_source, use_covar_heatmap,
+ * estimate_occlusion_map).  The five entries below are everything that is not a convolution; the three conv stacks between them run on
+ * dawn_conv_gemm / dawn_affine_act / dawn_bn_relu_pool2 (dawn_pytorch_amd/motion_encoder.py).  Activations are channels-last rows.
+ * Stage contract: every launch on `stream`, no allocation, no synchronisation, every argument checked before the first launch, a refusal
+ * names the argument.  The coordinate grid is make_coordinate_grid's (UTIL:51-67), fp32, each operation rounded on its own:
+ *     g(j, n) = 2 * (j / (n - 1)) - 1        x: j = column, n = w;  y: j = row, n = h        (so h, w >= 2) */
+/* AntiAliasInterpolation2d (UTIL:217-264) at scale 1 / s, s = 1 .. 8 (s = 1: one tap of weight 1, the layout change alone), only the kept pixels: with sigma = (s - 1) / 2, K = 4 (s - 1) + 1
+ * taps (= 2 round(4 sigma) + 1: sigma 1.5 and 13 taps at s = 4), ka = K / 2 and g[i] = fp32(exp(-(i - ka)^2 / (2 sigma^2))),
+ *     out[t][yo][xo][c] = ( sum_i g[i] * ( sum_j g[j] * in[t][c][s yo - ka + i][s xo - ka + j] ) ) / S,     S = fp32 sum_ij fp32(g[i] g[j]),
+ * taps outside the H x W frame read zero (the reference's F.pad), sums in fp32 with fused multiply-adds, j inside i; ho = ceil(H / s),
+ * wo = ceil(W / s).  This is the reference's fp32 product kernel divided by its fp32 sum, factored.
+ * in_kind 0: fp32 planes, in[t][c][y][x] at in + t * frame_stride + c * chan_stride + y * W + x floats (both (T,3,H,W) and (3,T,H,W));
+ * in_kind 1: uint8 frames (T,H,W,3) as ingest and egress make them, frame t at in + t * frame_stride bytes, value = byte / 255.
+ * out: rows (T * ho * wo, ld_out) as dawn_conv_gemm reads them: channels 0 .. 2 the result, channels 3 .. c_pad - 1 written as zero. */
+int dawn_antialias_down(const void* in, int in_kind, long frame_stride, long chan_stride, int T, int H, int W, int s, float* out, int ld_out,
+                        int c_pad, void* stream);
+/* RegionPredictor after its `regions` conv (RP:84-117, RP:60-75), per frame t and region r, from x (T, h * w, R) with row stride ld:
+ *     e[p]   = exp((x[t][p][r] - max_p x[t][p][r]) / temperature)                      fp64
+ *     shift  = sum_p e[p] g[p] / sum_p e[p],    covar = sum_p e[p] g[p] g[p]^T / sum_p e[p] - shift shift^T        fp64 sums, fp32 results
+ *     affine = U diag(sqrt(s1), sqrt(s2)),  covar = U diag(s1, s2) U^T, s1 >= s2 >= 0, in closed form from the fp64 covar = [[a, b], [b, c]]:
+ *              hd = (a - c) / 2, rad = sqrt(hd^2 + b^2), s1 = (a + c) / 2 + rad, s2 = max((a c - b^2) / s1, 0);
+ *              u1 = the unit vector along (hd + rad, b) where hd >= 0, along (b, rad - hd) otherwise, (1, 0) where that vanishes;
+ * SIGN CONVENTION: u1.x > 0, or u1.x == 0 and u1.y > 0;  u2 = (u1.y, -u1.x), so det U = -1 always (torch.svd's U of such matrices has
+ * det -1 too except on exactly diagonal input; only A_s . inverse(A_d) is used downstream, and after revert_axis_swap's sign(M[0][0]) that
+ * product is the same for every convention with a fixed det U).  The heatmap (T, R, h, w) is never written: nothing at inference reads it.
+ * shift (T, R, 2) = (x, y);  covar, affine (T, R, 2, 2) row-major. */
+int dawn_region_moments(const float* x, int ld, int T, int h, int w, int R, double temperature, float* shift, float* covar, float* affine,
+                        void* stream);
+/* BGMotionPredictor after its encoder (BG:46-52, bg_type 'affine'): x (T, npix, C) with row stride ld = the encoder's last map,
+ *     v[o] = fc_b[o] + sum_c fc_w[o][c] * (sum_p x[t][p][c] / npix),  o = 0 .. 5     (fp64 sums, rounded once)
+ *     out[t] = [[v0, v1, v2], [v3, v4, v5], [0, 0, 1]]                                (T, 3, 3) */
+int dawn_bg_params(const float* x, int ld, int T, int npix, int C, const float* fc_w, const float* fc_b, float* out, void* stream);
+/* The pixelwise hourglass's input rows (PF:48-120), written directly: out (T * h * w, ld_out), channel 4 k + j of pixel p of frame t,
+ * k = 0 .. R (0 = background), from the per-frame driving parameters drv_* (T, R, ...), the per-clip source parameters src_* (R, ...),
+ * bg_params (T, 3, 3) and the downsampled source src_rows (h * w, ld_src), 3 channels:
+ *     motion_0 = (X / Z, Y / Z), (X, Y, Z) = bg[t] . (gx, gy, 1)
+ *     motion_k = M_k . (g - shift_d,k) + shift_s,k,   M_k = A_s,k . inverse(A_d,k),  M_k *= sign(M_k[0][0])   (sign(0) = 0)
+ *     j = 0:      k = 0: 0;  k >= 1: gauss(g; shift_d,k, covar_d,k) - gauss(g; shift_s,k, covar_s,k),  gauss = exp(-(d^T C^-1 d) / 2), d = g - shift
+ *     j = 1 .. 3: grid_sample(source, motion_k) -- bilinear, zeros, align_corners=False (dawn_warp_blend's corner set) -- channel j - 1
+ * M_k and the inverse covariances: fp64, closed-form 2x2 inverses, rounded to fp32; everything per pixel: fp32.  Channels 4 (R + 1) ..
+ * c_pad - 1 are written as zero (c_pad % 4 == 0, <= 64; ld_out % 4 == 0; out 16-byte aligned).  Neither the R + 1 motion grids nor the
+ * R + 1 warped images are stored. */
+int dawn_motion_inputs(const float* drv_shift, const float* drv_covar, const float* drv_affine, const float* src_shift, const float* src_covar,
+                       const float* src_affine, const float* bg_params, int R, const float* src_rows, int ld_src, int T, int h, int w,
+                       float* out, int ld_out, int c_pad, void* stream);
+/* PF:124-135 on x (T * h * w, ld): channels 0 .. R the `mask` conv, channel R + 1 the `occlusion` conv (run as one 7x7 conv):
+ *     m = softmax(x[0 .. R]);   flow = sum_k m[k] * motion_k  (k ascending, the motions of dawn_motion_inputs recomputed);   occ = sigmoid(x[R + 1])
+ * grid: the x plane of frame t at grid + t * h * w, the y plane grid_plane floats further ((2, T, h, w) slices of the latent);
+ * conf + t * h * w receives occ, or with conf_x0 = 1 the diffusion's x0 plane 2 * occ - 1 (FD:274-282). */
+int dawn_flow_combine(const float* x, int ld, const float* drv_shift, const float* drv_affine, const float* src_shift, const float* src_affine,
+                      const float* bg_params, int R, int T, int h, int w, float* grid, long grid_plane, float* conf, int conf_x0, void* stream);
 /* ---- model bundle (csrc/dawn_bundle.hip, csrc/dawn_bundle_format.h): ONE file that holds everything the six *_create calls and
  * dawn_generate_args need besides the media -- the packed weight tables, the six cfg structs, named step tables and a defaults
  * record -- so that a host without Python runs the pipeline (tools/dawn_generate.cpp).  Python writes it (dawn_pytorch_amd/bundle.py:
