@@ -210,6 +210,15 @@ SIGNATURES = {
     "dawn_bundle_host": [c_f, C.c_char_p, c_f, C.POINTER(C.c_size_t)],
     "dawn_bundle_create_handles": [c_f, c_f, c_f],
     "dawn_bundle_destroy_handles": [c_f],
+    "dawn_bundle_create_motion": [c_f, c_f, c_f],
+    # yuv420p ingest (csrc/yuv_ingest.hip) and the C-side motion-encode stage (csrc/dawn_motion.hip; handle, cfg and args structs as void*: ctx.py)
+    "dawn_yuv420_to_frames": [c_f, _l, _i, _i, _i, c_f, c_f],
+    "dawn_motion_create": [c_f, c_f, _i, c_f],
+    "dawn_motion_destroy": [c_f],
+    "dawn_motion_workspace_bytes": [c_f, _i, _i, _i],
+    "dawn_motion_encode_clip": [c_f, _i, _i, _i, c_f, _i, c_f, _i, _l, _l, _i, c_f, _l, c_f, _i, c_f, C.c_size_t, c_f],
+    "dawn_reenact_bytes": [c_f, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)],
+    "dawn_reenact_clip": [c_f, c_f, C.c_size_t, c_f],
 }
 # device helpers of the C-side evaluator (csrc/dawn_ctx.hip calls them; from Python only the op tests do)
 CTX_HELPER_SIGNATURES = {
@@ -247,7 +256,7 @@ LONG_RESULT = {"dawn_sla_ws_floats", "dawn_workspace_bytes_guided", "dawn_decode
                "dawn_pose_blink_workspace_bytes", "dawn_clip_bytes", "dawn_workspace_bytes",
                "dawn_workspace_bytes_sharded", "dawn_image_ingest_workspace_bytes", "dawn_resample16k_len",
                "dawn_resample16k_workspace_bytes", "dawn_bundle_device_bytes",
-               "dawn_bundle_verify_workspace_bytes"}      # entry points that return a size (long), not a status
+               "dawn_bundle_verify_workspace_bytes", "dawn_motion_workspace_bytes"}      # entry points that return a size (long), not a status
 
 
 def lib() -> C.CDLL:

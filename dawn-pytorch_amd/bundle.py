@@ -11,7 +11,8 @@ One file, little-endian, every offset and size an unsigned 64-bit number, no com
                         zero-padded to a multiple of 8 bytes
     payload             the device part [0, device_bytes): every tensor at a multiple of 256 bytes, zero-padded to a multiple of 4 bytes,
                         zeros between tensors -- it goes to the GPU as one region, a pointer is base + offset; then the host part:
-                        blobs at multiples of 16 bytes.  "cfg" of a stage = the raw bytes of its cfg struct; in the stage "host":
+                        blobs at multiples of 16 bytes.  "cfg" of a stage = the raw bytes of its cfg struct (the optional stage 7,
+                        "motion": ctx.MotionCfg = dawn_motion_cfg; a loader from before it refuses a file that has it); in the stage "host":
                         "defaults" (Defaults = dawn_bundle_defaults), "steps.ddim.<S>" (S x ctx.DdimStep), "steps.ancestral.<S>"
                         (S x ctx.AncestralStep), made from the dicts of sampler.ddim_step_scalars / ancestral_step_scalars.
     checksum            an entry's bytes (a host blob zero-padded to whole words) as n little-endian 32-bit words w:
@@ -31,7 +32,8 @@ import numpy as np
 MAGIC = b"DAWNBNDL"
 VERSION = 1
 HEADER_BYTES, ENTRY_FIXED_BYTES, ALIGN, HOST_ALIGN = 64, 48, 256, 16
-STAGES = ("hubert", "pose", "blink", "decoder", "inputs", "unet", "host")      # DAWN_STAGE_*: the order of PipelineEvaluator.ev, then host
+STAGES = ("hubert", "pose", "blink", "decoder", "inputs", "unet", "host", "motion")    # DAWN_STAGE_*: the order of PipelineEvaluator.ev, then host,
+MODEL_STAGES = STAGES[:6] + STAGES[7:]      # then the optional motion-encode stage (7).  MODEL_STAGES: the ones with a weight table and a cfg
 KIND_DEVICE, KIND_HOST = 0, 1
 DTYPES = {"uint8": 0, "float32": 1, "bfloat16": 2, "float16": 3, "int32": 4, "float64": 5, "int64": 6, "int16": 7}
 _M64 = (1 << 64) - 1
@@ -122,10 +124,10 @@ def write_bundle(path, tables: Mapping[str, Mapping[str, object]], cfgs: Mapping
         from . import _lib
         abi = int(_lib.lib().dawn_abi_version())
     for s in (*tables, *cfgs):
-        if s not in STAGES[:6]:
-            raise ValueError(f"bundle: unknown stage {s!r} (one of {STAGES[:6]})")
-    dev = [(STAGES.index(s), str(n), t) for s in STAGES[:6] if s in tables for n, t in tables[s].items()]
-    blobs = [(STAGES.index(s), "cfg", _blob_bytes(f"{s}/cfg", cfgs[s])) for s in STAGES[:6] if s in cfgs]
+        if s not in MODEL_STAGES:
+            raise ValueError(f"bundle: unknown stage {s!r} (one of {MODEL_STAGES})")
+    dev = [(STAGES.index(s), str(n), t) for s in MODEL_STAGES if s in tables for n, t in tables[s].items()]
+    blobs = [(STAGES.index(s), "cfg", _blob_bytes(f"{s}/cfg", cfgs[s])) for s in MODEL_STAGES if s in cfgs]
     blobs += [(6, str(n), _blob_bytes(str(n), v)) for n, v in host.items()]
     names = [(s, KIND_DEVICE, n) for s, n, _ in dev] + [(s, KIND_HOST, n) for s, n, _ in blobs]
     if len(set(names)) != len(names):
@@ -206,12 +208,21 @@ def steps_blob(name: str, steps: Sequence[dict]) -> C.Array:
 
 
 def bundle_from_pipeline(path, pipe, steps: Mapping[str, Sequence[dict]], defaults: Optional[Mapping[str, object]] = None,
-                         abi: Optional[int] = None) -> dict:
+                         abi: Optional[int] = None, motion=None) -> dict:
     """The bundle of a ctx.PipelineEvaluator: the six evaluators' `weights` and `cfg`, exactly the tables _Evaluator.__init__ hands to
     *_create.  steps = {"ddim.20": ddim_step_scalars(...), "ancestral.1000": ...}; defaults = overrides of DEFAULTS (fea_ch, latent_dim
-    and up_border are read off the evaluators)."""
+    and up_border are read off the evaluators).  motion = a motion_encoder.MotionEncoder or its ctx.MotionEvaluator: the optional
+    seventh stage "motion" (ctx.motion_named_weights / ctx.motion_cfg), for dawn_bundle_create_motion."""
     tables = {s: ev.weights for s, ev in zip(STAGES, pipe.ev)}
     cfgs = {s: ev.cfg for s, ev in zip(STAGES, pipe.ev)}
+    if motion is not None:
+        from . import ctx
+        if isinstance(motion, ctx.MotionEvaluator):
+            if not motion.weights:
+                raise ValueError("bundle: a MotionEvaluator that came from a bundle holds no weight table to write")
+            tables["motion"], cfgs["motion"] = motion.weights, motion.cfg
+        else:
+            tables["motion"], cfgs["motion"] = ctx.motion_named_weights(motion), ctx.motion_cfg(motion)
     unet, pose = pipe.ev[5], pipe.ev[1]
     d = dict(fea_ch=unet.cfg.fea_ch, latent_dim=pose.cfg.latent_dim, up_border=int(getattr(getattr(unet, "P", None), "up_border", 0) or 0))
     if steps:                                               # the default step table: the first one given, unless the caller names one

@@ -1,6 +1,7 @@
 // The model bundle loader (include/dawn_hip.h: "model bundle"): open / upload / verify / tables / handles.  The file format and every
 // refusal of it live in dawn_bundle_format.h (host code without HIP, shared with tools/); this unit adds the one kernel -- the checksum
-// of the uploaded tensors -- the upload through the library's own bounded staging, and the glue to the six *_create calls.
+// of the uploaded tensors -- the upload through the library's own bounded staging, and the glue to the six *_create calls (and to the
+// optional seventh, dawn_motion_create).
 #include "dawn_host.h"
 #include "dawn_bundle_format.h"
 
@@ -72,6 +73,9 @@ __global__ __launch_bounds__(CK_THREADS) void bundle_checksum_kernel(const unsig
 constexpr size_t STAGING_BYTES = 8u << 20;
 
 int refuse(int code, const char* who, const std::string& what) { return dawn_set_error_msg(code, (std::string(who) + ": " + what).c_str()); }
+
+// a stage with a weight table and a cfg struct: everything but the host stage
+bool model_stage(int stage) { return stage >= 0 && stage < fmt::N_STAGES && stage != fmt::STAGE_HOST; }
 
 }  // namespace
 
@@ -222,7 +226,7 @@ extern "C" int dawn_bundle_verify(dawn_bundle* b, const void* device_mem, size_t
 extern "C" int dawn_bundle_table(dawn_bundle* b, int stage, const void* device_mem, const dawn_named_ptr** table, int* n) {
     const char* who = "dawn_bundle_table";
     if (!b || !device_mem || !table || !n) return refuse(-350, who, "NULL argument");
-    if (stage < 0 || stage >= fmt::STAGE_HOST) return refuse(-358, who, "stage " + std::to_string(stage) + ": 0 .. 5");
+    if (!model_stage(stage)) return refuse(-358, who, "stage " + std::to_string(stage) + ": 0 .. 5, or 7 (motion)");
     std::vector<dawn_named_ptr>& t = b->tables[stage];
     t.clear();
     for (const fmt::Entry* e : b->tensors)
@@ -235,7 +239,7 @@ extern "C" int dawn_bundle_table(dawn_bundle* b, int stage, const void* device_m
 extern "C" int dawn_bundle_cfg(const dawn_bundle* b, int stage, void* out, size_t out_bytes) {
     const char* who = "dawn_bundle_cfg";
     if (!b || !out) return refuse(-350, who, "NULL argument");
-    if (stage < 0 || stage >= fmt::STAGE_HOST) return refuse(-358, who, "stage " + std::to_string(stage) + ": 0 .. 5");
+    if (!model_stage(stage)) return refuse(-358, who, "stage " + std::to_string(stage) + ": 0 .. 5, or 7 (motion)");
     const fmt::Entry* e = b->find((uint32_t)stage, fmt::KIND_HOST, "cfg");
     if (!e) return refuse(-359, who, std::string("stage '") + fmt::stage_name((uint32_t)stage) + "' is missing from the bundle (no cfg)");
     if (out_bytes != e->length) return refuse(-360, who, std::string("stage '") + fmt::stage_name((uint32_t)stage) + "': out_bytes = " + fmt::u64s(out_bytes) + ", the struct has " + fmt::u64s(e->length));
@@ -296,4 +300,16 @@ extern "C" int dawn_bundle_create_handles(dawn_bundle* b, const void* device_mem
     }
     args->hubert = h.hubert; args->pose = h.pose; args->blink = h.blink; args->decoder = h.decoder; args->inputs = h.inputs; args->unet = h.unet;
     return 0;
+}
+
+extern "C" int dawn_bundle_create_motion(dawn_bundle* b, const void* device_mem, dawn_motion** m) {
+    const char* who = "dawn_bundle_create_motion";
+    if (!b || !device_mem || !m) return refuse(-350, who, "NULL argument");
+    if (!b->find(fmt::STAGE_MOTION, fmt::KIND_HOST, "cfg")) return refuse(-359, who, "stage 'motion' is missing from the bundle (no cfg)");
+    dawn_motion_cfg cfg;
+    const dawn_named_ptr* tab = nullptr;
+    int n = 0;
+    CK(dawn_bundle_cfg(b, fmt::STAGE_MOTION, &cfg, sizeof cfg));
+    CK(dawn_bundle_table(b, fmt::STAGE_MOTION, device_mem, &tab, &n));
+    return dawn_motion_create(&cfg, tab, n, m);
 }

@@ -20,12 +20,14 @@ constexpr unsigned char MAGIC[8] = {'D', 'A', 'W', 'N', 'B', 'N', 'D', 'L'};
 constexpr uint32_t VERSION = 1;
 constexpr uint64_t HEADER_BYTES = 64, ENTRY_FIXED_BYTES = 48, ALIGN = 256, HOST_ALIGN = 16;
 constexpr uint64_t MAX_INDEX_BYTES = 256ull << 20, MAX_HOST_BYTES = 64ull << 20, MAX_NAME_BYTES = 4096;
-enum { STAGE_HUBERT = 0, STAGE_POSE = 1, STAGE_BLINK = 2, STAGE_DECODER = 3, STAGE_INPUTS = 4, STAGE_UNET = 5, STAGE_HOST = 6, N_STAGES = 7 };
+enum { STAGE_HUBERT = 0, STAGE_POSE = 1, STAGE_BLINK = 2, STAGE_DECODER = 3, STAGE_INPUTS = 4, STAGE_UNET = 5, STAGE_HOST = 6, STAGE_MOTION = 7, N_STAGES = 8 };
+// STAGE_MOTION is optional and came after the first release of version 1: a reader from before it refuses a file that has the stage, by
+// the stage number of the first such entry ("index entry i '<name>': stage 7"); a file without it reads as before.
 enum { KIND_DEVICE = 0, KIND_HOST = 1 };
 constexpr int N_DTYPES = 8;         // informational: 0 bytes, 1 f32, 2 bf16, 3 f16, 4 i32, 5 f64, 6 i64, 7 i16
 
 inline const char* stage_name(uint32_t s) {
-    static const char* const names[N_STAGES] = {"hubert", "pose", "blink", "decoder", "inputs", "unet", "host"};
+    static const char* const names[N_STAGES] = {"hubert", "pose", "blink", "decoder", "inputs", "unet", "host", "motion"};
     return s < N_STAGES ? names[s] : "?";
 }
 
@@ -147,6 +149,7 @@ inline uint64_t blob_struct_bytes(const Entry& e, bool* array) {
             case STAGE_DECODER: return sizeof(dawn_decoder_cfg);
             case STAGE_INPUTS: return sizeof(dawn_inputs_cfg);
             case STAGE_UNET: return sizeof(dawn_unet_cfg);
+            case STAGE_MOTION: return sizeof(dawn_motion_cfg);
             default: return 0;
         }
     }

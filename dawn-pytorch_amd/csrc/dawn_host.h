@@ -1,4 +1,4 @@
-// Host-side plumbing shared by the C-side stage hosts (dawn_ctx.hip, dawn_decoder.hip, dawn_hubert.hip, dawn_pbnet.hip): the
+// Host-side plumbing shared by the C-side stage hosts (dawn_ctx.hip, dawn_decoder.hip, dawn_hubert.hip, dawn_pbnet.hip, dawn_motion.hip): the
 // return-code macro, the workspace arithmetic and refusals, and the named-weight table a *_create reads its pointers from.
 // Header only, internal linkage throughout: the library's symbol table gains nothing from it.
 #pragma once

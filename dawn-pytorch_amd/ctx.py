@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
@@ -1109,6 +1109,205 @@ class PipelineEvaluator:
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# C-side motion-encode stage (include/dawn_hip.h: dawn_motion_*, dawn_reenact_*; csrc/dawn_motion.hip)
+MOTION_MAX_BLOCKS = 8
+
+
+class MotionCfg(C.Structure):
+    """Mirror of ``dawn_motion_cfg``."""
+    _fields_ = [("R", C.c_int), ("s", C.c_int), ("temperature", C.c_double), ("rp_blocks", C.c_int), ("bg_blocks", C.c_int), ("pf_blocks", C.c_int),
+                ("rp_down", C.c_int * MOTION_MAX_BLOCKS), ("rp_up", C.c_int * MOTION_MAX_BLOCKS), ("bg_down", C.c_int * MOTION_MAX_BLOCKS),
+                ("pf_down", C.c_int * MOTION_MAX_BLOCKS), ("pf_up", C.c_int * MOTION_MAX_BLOCKS)]
+
+
+class ReenactArgs(C.Structure):
+    """Mirror of ``dawn_reenact_args``."""
+    _fields_ = [("size", C.c_size_t), ("motion", C.c_void_p), ("decoder", C.c_void_p), ("img3", C.c_void_p), ("H", C.c_int), ("W", C.c_int),
+                ("drv", C.c_void_p), ("drv_kind", C.c_int), ("T", C.c_int), ("drv_frame_stride", C.c_long), ("drv_chan_stride", C.c_long),
+                ("motion_chunk", C.c_int), ("chunk", C.c_int), ("format", C.c_int), ("bgr", C.c_int), ("mean3", C.POINTER(C.c_double)),
+                ("frames_out", C.c_void_p), ("grid_out", C.c_void_p), ("conf_out", C.c_void_p)]
+
+
+def motion_cfg(enc) -> MotionCfg:
+    """motion_encoder.MotionEncoder -> its ``dawn_motion_cfg``: R, s, temperature and the REAL channel counts of the three conv stacks
+    (the packed images hold each rounded up to a multiple of 16; motion_encoder.pad16 is the one definition of that)."""
+    stacks = (("rp_down", enc.rp_hg.enc.reals), ("rp_up", enc.rp_hg.up_reals), ("bg_down", enc.bg_enc.reals),
+              ("pf_down", enc.pf_hg.enc.reals), ("pf_up", enc.pf_hg.up_reals))
+    cfg = MotionCfg()
+    cfg.R, cfg.s, cfg.temperature = enc.R, enc.s, enc.temperature
+    cfg.rp_blocks, cfg.bg_blocks, cfg.pf_blocks = enc.rp_hg.levels, len(enc.bg_enc.downs), enc.pf_hg.levels
+    for name, reals in stacks:
+        if not 1 <= len(reals) <= MOTION_MAX_BLOCKS:
+            raise _lib.DawnHipError(f"dawn_motion_cfg: {name} has {len(reals)} blocks, 1 .. {MOTION_MAX_BLOCKS} fit the struct")
+        arr = getattr(cfg, name)
+        for i, c in enumerate(reals):
+            arr[i] = int(c)
+    return cfg
+
+
+def motion_named_weights(enc) -> Dict[str, Tensor]:
+    """motion_encoder.MotionEncoder -> {name: device tensor} in the naming scheme of include/dawn_hip.h (motion stage): the packed _Conv
+    images as they are.  The background encoder's first conv travels as its two halves (bg.src0 with the bias, bg.drv0), its BatchNorm
+    as bg.down.0.a / b; the unsplit 6-channel image of that conv is not in the table (nothing launches it)."""
+    out: Dict[str, Tensor] = {}
+
+    def conv(p: str, c, norm: bool = True):
+        out[p + "w"] = c.w
+        if c.ws is not None:
+            out[p + "ws"] = c.ws
+        if c.bias is not None:
+            out[p + "bias"] = c.bias
+        if norm and c.a is not None:
+            out[p + "a"], out[p + "b"] = c.a, c.b
+
+    for stem, hg in (("rp.", enc.rp_hg), ("pf.", enc.pf_hg)):
+        for i, c in enumerate(hg.enc.downs):
+            conv(f"{stem}down.{i}.", c)
+        for i, c in enumerate(hg.ups):
+            conv(f"{stem}up.{i}.", c)
+    conv("rp.regions.", enc.rp_regions)
+    conv("pf.out.", enc.pf_out)
+    conv("bg.src0.", enc.bg_src0)
+    conv("bg.drv0.", enc.bg_drv0, norm=False)
+    out["bg.down.0.a"], out["bg.down.0.b"] = enc.bg_enc.downs[0].a, enc.bg_enc.downs[0].b
+    for i, c in enumerate(enc.bg_enc.downs[1:], 1):
+        conv(f"bg.down.{i}.", c)
+    out["fc.w"], out["fc.b"] = enc.fc_w, enc.fc_b
+    return out
+
+
+class MotionEvaluator(_Evaluator):
+    """One `dawn_motion` on one device: what a non-Python host would call to turn a driving video into the flow / occlusion latent.
+    Built from a `MotionEncoder` (its packed weights, kept alive here) -- or, `handle=`, around a handle that a bundle made
+    (BundleEvaluator.motion(): the bundle owns the weights).  PyTorch provides the device memory and the stream."""
+
+    def __init__(self, enc=None, weights: Optional[Dict[str, Tensor]] = None, *, handle=None, cfg: Optional[MotionCfg] = None, device=None,
+                 keep=None):
+        if handle is not None:
+            self.L = _lib.lib()
+            self.device, self.cfg, self.weights, self._destroy, self.h, self._ws, self._keep = torch.device(device), cfg, {}, "dawn_motion_destroy", handle, None, keep
+            return
+        super().__init__("dawn_motion_create", "dawn_motion_destroy", motion_cfg(enc), motion_named_weights(enc) if weights is None else dict(weights),
+                         enc.device, fp32_only=False)
+
+    def latent_size(self, H: int, W: int) -> Tuple[int, int]:
+        s = self.cfg.s
+        return -(-H // s), -(-W // s)
+
+    def workspace_bytes(self, H: int, W: int, chunk: int) -> int:
+        return int(self.L.dawn_motion_workspace_bytes(self.h, H, W, chunk))
+
+    def workspace(self, H: int, W: int, chunk: int) -> Tensor:
+        return self._grown(self.workspace_bytes(H, W, chunk))
+
+    @staticmethod
+    def _source(src: Tensor):
+        """-> (tensor kept alive, kind, H, W) of a source image: fp32 (3,H,W) / (1,3,H,W), or uint8 (1,H,W,3)."""
+        if src.dtype == torch.uint8:
+            if src.dim() != 4 or src.shape[0] != 1 or src.shape[3] != 3:
+                raise _lib.DawnHipError("MotionEvaluator: a uint8 source image is (1,H,W,3)")
+            return src.contiguous(), 1, int(src.shape[1]), int(src.shape[2])
+        src = src[0] if src.dim() == 4 and src.shape[0] == 1 else src
+        if src.dim() != 3 or src.shape[0] != 3:
+            raise _lib.DawnHipError("MotionEvaluator: an fp32 source image is (3,H,W) or (1,3,H,W)")
+        return src.float().contiguous(), 0, int(src.shape[1]), int(src.shape[2])
+
+    @staticmethod
+    def _driving(drv: Tensor, H: int, W: int):
+        """-> (tensor kept alive, kind, T, frame stride, channel stride): fp32 (T,3,H,W) with dense planes (a (3,T,H,W) clip permuted is
+        taken as it is), uint8 (T,H,W,3) contiguous, or uint8 (T, >= 3HW/2) I420 rows."""
+        if drv.dtype == torch.uint8 and drv.dim() == 2:
+            if drv.stride(1) != 1 or drv.shape[1] < H * W * 3 // 2:
+                raise _lib.DawnHipError("MotionEvaluator: I420 driving frames are uint8 (T, >= 3*H*W/2) rows")
+            T = int(drv.shape[0])
+            return drv, 2, T, (int(drv.stride(0)) if T > 1 else int(drv.shape[1])), 0
+        if drv.dtype == torch.uint8:
+            if drv.dim() != 4 or tuple(drv.shape[1:]) != (H, W, 3):
+                raise _lib.DawnHipError("MotionEvaluator: uint8 driving frames are (T,H,W,3) of the source's size")
+            return drv.contiguous(), 1, int(drv.shape[0]), H * W * 3, 1
+        if drv.dim() != 4 or tuple(drv.shape[1:]) != (3, H, W):
+            raise _lib.DawnHipError("MotionEvaluator: fp32 driving frames are (T,3,H,W) of the source's size")
+        drv = drv.float()
+        if not (drv.stride(3) == 1 and drv.stride(2) == W):
+            drv = drv.contiguous()
+        T = int(drv.shape[0])
+        return drv, 0, T, (int(drv.stride(0)) if T > 1 else 3 * H * W), int(drv.stride(1))
+
+    def encode_into(self, src: Tensor, drv: Tensor, grid: Tensor, conf: Tensor, chunk: int = 16, conf_x0: bool = False,
+                    workspace: Optional[Tensor] = None) -> None:
+        """dawn_motion_encode_clip into grid (2,T,h,w) (dense planes, any plane stride) and conf (T,h,w) contiguous."""
+        s, sk, H, W = self._source(src)
+        d, dk, T, fs, cs = self._driving(drv, H, W)
+        h, w = self.latent_size(H, W)
+        for t in (s, d, grid, conf):
+            if not t.is_cuda:
+                raise _lib.DawnHipError("MotionEvaluator needs GPU tensors; there is no CPU fallback on the product path")
+        if not (grid.dtype == torch.float32 and tuple(grid.shape) == (2, T, h, w) and grid.stride(3) == 1 and grid.stride(2) == w and grid.stride(1) == h * w):
+            raise _lib.DawnHipError(f"MotionEvaluator: grid must be fp32 (2,{T},{h},{w}) with dense planes")
+        if not (conf.dtype == torch.float32 and tuple(conf.shape) == (T, h, w) and conf.is_contiguous()):
+            raise _lib.DawnHipError(f"MotionEvaluator: conf must be fp32 ({T},{h},{w}) contiguous")
+        chunk = max(1, min(int(chunk), T))
+        ws = workspace if workspace is not None else self.workspace(H, W, chunk)
+        with torch.cuda.device(self.device):
+            check(self.L.dawn_motion_encode_clip(self.h, H, W, T, s.data_ptr(), sk, d.data_ptr(), dk, fs, cs, chunk, grid.data_ptr(), grid.stride(0),
+                                                 conf.data_ptr(), 1 if conf_x0 else 0, ws.data_ptr(), ws.numel(), self._stream()),
+                  "dawn_motion_encode_clip")
+
+    def encode_clip(self, src: Tensor, drv: Tensor, chunk: int = 16, workspace: Optional[Tensor] = None) -> Dict[str, Tensor]:
+        """MotionEncoder.encode_clip through the C stage: -> {real_vid_grid (1,2,T,h,w), real_vid_conf (1,1,T,h,w)}."""
+        _, _, H, W = self._source(src)
+        T = int(drv.shape[0])
+        h, w = self.latent_size(H, W)
+        grid = torch.empty(2, T, h, w, device=self.device, dtype=torch.float32)
+        conf = torch.empty(T, h, w, device=self.device, dtype=torch.float32)
+        self.encode_into(src, drv, grid, conf, chunk, False, workspace)
+        return {"real_vid_grid": grid.unsqueeze(0), "real_vid_conf": conf.view(1, 1, T, h, w)}
+
+    def latent(self, src: Tensor, drv: Tensor, chunk: int = 16, workspace: Optional[Tensor] = None) -> Tensor:
+        """-> (3,T,h,w): the diffusion's x0 of this clip, cat(grid, 2 * conf - 1)."""
+        _, _, H, W = self._source(src)
+        T = int(drv.shape[0])
+        h, w = self.latent_size(H, W)
+        lat = torch.empty(3, T, h, w, device=self.device, dtype=torch.float32)
+        self.encode_into(src, drv, lat[:2], lat[2], chunk, True, workspace)
+        return lat
+
+    def reenact(self, decoder, src: Tensor, drv: Tensor, *, format: str = "rgb", mean=(0.0, 0.0, 0.0), bgr: bool = False, motion_chunk: int = 16,
+                chunk: int = 64, want_motion: bool = False, workspace: Optional[Tensor] = None):
+        """dawn_reenact_clip: src fp32 (3,H,W) / (1,3,H,W), drv as encode_clip, `decoder` a DecoderEvaluator (or anything with its
+        handle as `.h`) -> (T,H,W,3) uint8 frames, or (T, 3HW/2) with format="yuv420p"; want_motion: -> (frames, grid (2,T,h,w),
+        conf (T,h,w))."""
+        if format not in ("rgb", "yuv420p"):
+            raise ValueError(f"format must be 'rgb' or 'yuv420p', not {format!r}")
+        s, sk, H, W = self._source(src)
+        if sk != 0:
+            raise _lib.DawnHipError("MotionEvaluator.reenact: the source image is fp32 (3,H,W): the decoder reads it too")
+        d, dk, T, fs, cs = self._driving(drv, H, W)
+        h, w = self.latent_size(H, W)
+        a = ReenactArgs()
+        a.size, a.motion, a.decoder, a.img3, a.H, a.W = C.sizeof(ReenactArgs), self.h, decoder.h, s.data_ptr(), H, W
+        a.drv, a.drv_kind, a.T, a.drv_frame_stride, a.drv_chan_stride = d.data_ptr(), dk, T, fs, cs
+        a.motion_chunk, a.chunk = max(1, min(int(motion_chunk), T)), max(1, min(int(chunk), T))
+        a.format, a.bgr = (1 if format == "yuv420p" else 0), (1 if bgr else 0)
+        m = (C.c_double * 3)(*[float(v) / 255.0 for v in mean])
+        a.mean3 = C.cast(m, C.POINTER(C.c_double))
+        grid = conf = None
+        if want_motion:
+            grid = torch.empty(2, T, h, w, device=self.device, dtype=torch.float32)
+            conf = torch.empty(T, h, w, device=self.device, dtype=torch.float32)
+            a.grid_out, a.conf_out = grid.data_ptr(), conf.data_ptr()
+        cb, wb = C.c_size_t(0), C.c_size_t(0)
+        check(self.L.dawn_reenact_bytes(C.addressof(a), C.byref(cb), C.byref(wb)), "dawn_reenact_bytes")
+        frames = torch.empty(cb.value, dtype=torch.uint8, device=self.device)
+        a.frames_out = frames.data_ptr()
+        ws = workspace if workspace is not None else self._grown(wb.value)
+        with torch.cuda.device(self.device):
+            check(self.L.dawn_reenact_clip(C.addressof(a), ws.data_ptr(), ws.numel(), self._stream()), "dawn_reenact_clip")
+        frames = frames.view(T, H * W * 3 // 2) if format == "yuv420p" else frames.view(T, H, W, 3)
+        return (frames, grid, conf) if want_motion else frames
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # the same pipeline from a model bundle file (include/dawn_hip.h: "model bundle"; csrc/dawn_bundle.hip): what a host without Python does
 class _BundleStage:
     """What PipelineEvaluator asks of a stage evaluator: the handle and the cfg struct (the bundle owns handles and weights)."""
@@ -1181,6 +1380,14 @@ class BundleEvaluator(PipelineEvaluator):
     def defaults(self):
         from .bundle import Defaults
         return Defaults.from_buffer_copy(self.host("defaults"))
+
+    def motion(self) -> "MotionEvaluator":
+        """The motion-encode stage of the bundle (dawn_bundle_create_motion) as a MotionEvaluator on the bundle's region; DawnHipError
+        "stage 'motion' is missing" for a bundle without it.  The evaluator owns its handle and keeps this bundle alive."""
+        m = C.c_void_p()
+        with torch.cuda.device(self.device):
+            check(self.L.dawn_bundle_create_motion(self.b, self.mem.data_ptr(), C.addressof(m)), "dawn_bundle_create_motion")
+        return MotionEvaluator(handle=m, cfg=self.cfg(7, MotionCfg), device=self.device, keep=self)
 
     def table(self, stage: int) -> Dict[str, int]:
         """{name: device address} of dawn_bundle_table for `mem`."""

@@ -95,6 +95,7 @@ class FlowDiffusion(nn.Module):
         self.is_train = is_train        # kept for signature parity; this build is inference-only
         self.inputs_via_c = False       # True: bbox_mask and cond of a GPU clip with B == 1 from dawn_clip_inputs (ctx.InputsEvaluator)
         self._inputs_ev = None
+        self.motion_via_c = False       # True: encode_video / reenact encode a GPU clip with B == 1 through dawn_motion_encode_clip (ctx.MotionEvaluator)
 
     def update_num_frames(self, new_num_frames):
         """FD:177-180."""
@@ -191,14 +192,18 @@ class FlowDiffusion(nn.Module):
         return "sample_frames_u8", fn(sample_img, grid, conf, **kw)
 
     def _encode(self, ref_img, real_vid):
-        """ref_img (B,3,H,W), real_vid (B,3,T,H,W) fp32 in [0,1] -- or, B == 1, (T,H,W,3) uint8 frames -> grid (B,2,T,h,w), conf (B,1,T,h,w)."""
+        """ref_img (B,3,H,W), real_vid (B,3,T,H,W) fp32 in [0,1] -- or, B == 1, (T,H,W,3) uint8 frames -> grid (B,2,T,h,w), conf (B,1,T,h,w).
+        `motion_via_c` (a GPU clip, B == 1): the C-side stage, which also takes I420 frames, (T, 3*H*W/2) uint8."""
         me = self.motion_encoder(ref_img.device)
+        via_c = bool(self.motion_via_c) and ref_img.is_cuda and ref_img.shape[0] == 1
+        if real_vid.dtype == torch.uint8 and real_vid.dim() == 2 and not via_c:
+            raise ValueError("I420 driving frames (T, 3*H*W/2) need motion_via_c = True, a GPU clip and B == 1")
         if real_vid.dtype == torch.uint8:
             if ref_img.shape[0] != 1:
-                raise ValueError("uint8 driving frames (T,H,W,3) take one clip (B == 1)")
-            clips = [me.encode_clip(ref_img[0], real_vid)]
+                raise ValueError("uint8 driving frames take one clip (B == 1)")
+            clips = [me.encode_clip(ref_img[0], real_vid, via_c=via_c)]
         else:
-            clips = [me.encode_clip(ref_img[b], real_vid[b].permute(1, 0, 2, 3)) for b in range(ref_img.shape[0])]
+            clips = [me.encode_clip(ref_img[b], real_vid[b].permute(1, 0, 2, 3), via_c=via_c) for b in range(ref_img.shape[0])]
         return torch.cat([c["real_vid_grid"] for c in clips], 0), torch.cat([c["real_vid_conf"] for c in clips], 0)
 
     @torch.no_grad()
@@ -213,7 +218,7 @@ class FlowDiffusion(nn.Module):
     @torch.no_grad()
     def reenact(self, sample_img, driving, frames_u8: Optional[dict] = None):
         """Video-driven reenactment, the LFG's own use: the motion of `driving` ((B,3,T,H,W) fp32, or (T,H,W,3) uint8 frames for one
-        clip) encoded against `sample_img` (B,3,H,W) and decoded from it.  -> real_vid_grid, real_vid_conf, and sample_out_vid /
+        clip, or with `motion_via_c` its I420 bytes (T, 3*H*W/2) uint8) encoded against `sample_img` (B,3,H,W) and decoded from it.  -> real_vid_grid, real_vid_conf, and sample_out_vid /
         sample_warped_vid -- or, with `frames_u8` (the options of sample_one_video: RGB or format="yuv420p", stream or not),
         sample_frames_u8 / sample_frames_yuv420 instead."""
         grid, conf = self._encode(sample_img, driving)

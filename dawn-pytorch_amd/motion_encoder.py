@@ -105,11 +105,13 @@ class _Encoder:
 
     def __init__(self, sd, stem: str, first_segs, dev, first_bias: bool = True):
         self.downs: List[_Conv] = []
+        self.reals: List[int] = []                 # real (unpadded) output channels of every block: what ctx.motion_cfg states
         segs = list(first_segs)
         for i in range(_count(sd, stem)):
             p = f"{stem}.{i}"
             self.downs.append(_pack(sd, p + ".conv", segs, dev, norm=p + ".norm", bias=first_bias or i > 0))
-            co = sd[p + ".conv.weight"].shape[0]
+            co = int(sd[p + ".conv.weight"].shape[0])
+            self.reals.append(co)
             segs = [(co, pad16(co))]
         self.out_real = segs[0][0]
 
@@ -121,6 +123,7 @@ class _Hourglass:
         self.enc = _Encoder(sd, prefix + ".encoder.down_blocks", [(in_real, pad16(in_real))], dev)
         reals = [in_real] + [sd[f"{prefix}.encoder.down_blocks.{i}.conv.weight"].shape[0] for i in range(len(self.enc.downs))]
         self.ups: List[_Conv] = []
+        self.up_reals: List[int] = []
         n = len(self.enc.downs)
         if _count(sd, prefix + ".decoder.up_blocks") != n or n == 0:
             raise ValueError(f"{prefix}: an Hourglass with as many up blocks as down blocks (at least one) is required")
@@ -130,7 +133,8 @@ class _Hourglass:
             skip = reals[n - j]
             segs = [(skip, pad16(skip))] if prev is None else [(prev, pad16(prev)), (skip, pad16(skip))]
             self.ups.append(_pack(sd, p + ".conv", segs, dev, norm=p + ".norm", up=True))
-            prev = sd[p + ".conv.weight"].shape[0]
+            prev = int(sd[p + ".conv.weight"].shape[0])
+            self.up_reals.append(prev)
         self.out_segs = [(prev, pad16(prev)), (in_real, pad16(in_real))]
         self.levels = n
 
@@ -215,6 +219,7 @@ class MotionEncoder:
                 "mo.bias": torch.cat((gen[f"{pf}.mask.bias"].float(), gen[f"{pf}.occlusion.bias"].float()), 0)}
         self.pf_out = _pack(both, "mo", self.pf_hg.out_segs, dev)
         self._bg_rep: Optional[Tensor] = None
+        self._c_eval = None
 
     @classmethod
     def from_state_dicts(cls, generator_sd, region_sd, bg_sd, device, **kw) -> "MotionEncoder":
@@ -302,9 +307,20 @@ class MotionEncoder:
     def latent_size(self, H: int, W: int) -> Tuple[int, int]:
         return -(-H // self.s), -(-W // self.s)
 
-    def encode_clip(self, source_img: Tensor, driving: Tensor, chunk: Optional[int] = None) -> Dict[str, Tensor]:
+    def c_evaluator(self):
+        """The C-side stage of this encoder (ctx.MotionEvaluator), created on first use."""
+        if self._c_eval is None:
+            from .ctx import MotionEvaluator
+            self._c_eval = MotionEvaluator(self)
+        return self._c_eval
+
+    def encode_clip(self, source_img: Tensor, driving: Tensor, chunk: Optional[int] = None, via_c: bool = False) -> Dict[str, Tensor]:
         """source_img (3,H,W) / (1,3,H,W) fp32 in [0,1] or (1,H,W,3) uint8; driving (T,3,H,W) fp32 -- a (3,T,H,W) clip permuted is taken
-        without a copy -- or (T,H,W,3) uint8 -> {real_vid_grid (1,2,T,h,w), real_vid_conf (1,1,T,h,w)}, FD:259-260."""
+        without a copy -- or (T,H,W,3) uint8 -> {real_vid_grid (1,2,T,h,w), real_vid_conf (1,1,T,h,w)}, FD:259-260.
+        via_c: the same launches from dawn_motion_encode_clip (csrc/dawn_motion.hip through ctx.MotionEvaluator), the same bits; driving
+        may then also be I420 frames, (T, 3*H*W/2) uint8, converted chunk by chunk on the device.  The default path is unchanged."""
+        if via_c:
+            return self.c_evaluator().encode_clip(source_img, driving, chunk or self.chunk)
         T = int(driving.shape[0])
         h, w = self.latent_size(*self._size(self._frames(driving, "driving")))
         grid = torch.empty(2, T, h, w, device=driving.device, dtype=torch.float32)
@@ -312,8 +328,10 @@ class MotionEncoder:
         self._encode(source_img, driving, grid, conf, chunk, False)
         return {"real_vid_grid": grid.unsqueeze(0), "real_vid_conf": conf.view(1, 1, T, h, w)}
 
-    def latent(self, source_img: Tensor, driving: Tensor, chunk: Optional[int] = None) -> Tensor:
-        """-> (3,T,h,w): the diffusion's x0 of this clip, cat(grid, 2 * conf - 1) (FD:280-282)."""
+    def latent(self, source_img: Tensor, driving: Tensor, chunk: Optional[int] = None, via_c: bool = False) -> Tensor:
+        """-> (3,T,h,w): the diffusion's x0 of this clip, cat(grid, 2 * conf - 1) (FD:280-282).  via_c: as encode_clip."""
+        if via_c:
+            return self.c_evaluator().latent(source_img, driving, chunk or self.chunk)
         T = int(driving.shape[0])
         h, w = self.latent_size(*self._size(self._frames(driving, "driving")))
         lat = torch.empty(3, T, h, w, device=driving.device, dtype=torch.float32)

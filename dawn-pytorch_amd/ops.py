@@ -862,6 +862,20 @@ class HipOps:
               "dawn_frames_to_yuv420")
         return out
 
+    def yuv420_to_frames(self, yuv: Tensor, H: int, W: int, out: Optional[Tensor] = None) -> Tensor:
+        """(T, >= 3HW/2) uint8 I420 frames (rows may be strided: the frame stride is the row stride) -> (T,H,W,3) uint8 RGB frames, the
+        definition at dawn_yuv420_to_frames: BT.601 limited range, 8-bit fixed point, chroma replicated over its 2x2 block, clamped.
+        Even H, W % 4 == 0."""
+        _need(yuv.is_cuda and yuv.dtype == torch.uint8 and yuv.dim() == 2 and yuv.stride(1) == 1 and yuv.shape[1] >= H * W * 3 // 2,
+              "yuv420_to_frames: yuv uint8 (T, >= 3*H*W/2) GPU rows")
+        T = int(yuv.shape[0])
+        if out is None:
+            out = self.empty(T, H, W, 3, like=yuv, dtype=torch.uint8)
+        _need(out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == (T, H, W, 3) and out.is_contiguous(), "yuv420_to_frames: out uint8 (T,H,W,3) contiguous")
+        check(self.L.dawn_yuv420_to_frames(_p(yuv), int(yuv.stride(0)) if T > 1 else int(yuv.shape[1]), T, H, W, _p(out), self._stream()),
+              "dawn_yuv420_to_frames")
+        return out
+
     # ------------------------------------------------------------------ HuBERT audio features (SURVEY 8f N3)
     def wave_normalize(self, x: Tensor) -> Tensor:
         """Wav2Vec2FeatureExtractor(do_normalize): (x - mean) / sqrt(var + 1e-7) over the utterance."""

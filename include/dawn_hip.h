@@ -487,6 +487,23 @@ int dawn_final_conv_blend_u8(const float* x, int T, int H, int W, int C, const f
  * dawn_frames_to_yuv420: vid = three fp32 planes (`plane` floats apart, a multiple of 4; 16-byte aligned) of a (3,T,H,W) clip. */
 int dawn_frames_to_yuv420(const float* vid, long plane, int T, int H, int W, double mean0, double mean1, double mean2,
                           unsigned char* out, void* stream);
+/* ---- yuv420p ingest (csrc/yuv_ingest.hip): the inverse of the egress above, for driving frames that arrive from a video decoder or a
+ * .y4m file.  in = T I420 frames in the layout the egress writes (Y H*W bytes, then U and V (H/2)*(W/2) bytes each), frame t at
+ * in + t*frame_stride bytes -> out (T,H,W,3) uint8 RGB frames, contiguous, as dawn_antialias_down reads them with in_kind = 1.
+ * BT.601 limited range in 8-bit fixed point, `>>` an arithmetic shift (floor), chroma replicated over its 2x2 block (the centre siting
+ * the egress assumes), clamp8(v) = min(max(v, 0), 255):
+ *   C = Y - 16, D = U - 128, E = V - 128                       (D, E of the block's one chroma sample)
+ *   R = clamp8((298*C         + 409*E + 128) >> 8)
+ *   G = clamp8((298*C - 100*D - 208*E + 128) >> 8)
+ *   B = clamp8((298*C + 516*D         + 128) >> 8)
+ * Every byte value of Y, U, V is accepted (the clamp handles what lies outside the nominal ranges).  It is not the exact inverse of the
+ * egress: that one averages chroma and rounds, so a round trip moves a byte by a few levels.
+ * A work item converts a 2 x 8 pixel block (8-byte Y loads, 4-byte chroma loads, each output row as three 8-byte stores) when W % 8 == 0
+ * and `in`, frame_stride and `out` are multiples of 8; otherwise a 2 x 4 block with loads that assume no alignment and each output row
+ * as three 4-byte stores.  The bytes are the same on both paths.
+ * Refused, with a message that names the argument and nothing launched: a NULL pointer, T < 1, H < 2 or odd, W < 4 or W % 4 != 0,
+ * frame_stride < 3*H*W/2, an `out` that is not 4-byte aligned. */
+int dawn_yuv420_to_frames(const unsigned char* in, long frame_stride, int T, int H, int W, unsigned char* out, void* stream);
 /* dawn_final_conv_blend with the yuv420p egress defined above as its store: the same kernel source as dawn_final_conv_blend_u8 up to the
  * RGB bytes (bgr = 0), which stay in LDS and are converted there; no fp32 frame and no RGB byte is written.  Frame t of the launch goes
  * to frames + t*3*H*W/2. */
@@ -1102,6 +1119,77 @@ int dawn_motion_inputs(const float* drv_shift, const float* drv_covar, const flo
  * conf + t * h * w receives occ, or with conf_x0 = 1 the diffusion's x0 plane 2 * occ - 1 (FD:274-282). */
 int dawn_flow_combine(const float* x, int ld, const float* drv_shift, const float* drv_affine, const float* src_shift, const float* src_affine,
                       const float* bg_params, int R, int T, int h, int w, float* grid, long grid_plane, float* conf, int conf_x0, void* stream);
+/* ---- SURVEY 8(f) N5 as a whole path: the motion-encode stage from a source image and driving frames to the flow / occlusion latent
+ * (csrc/dawn_motion.hip).  The launch sequence of dawn_pytorch_amd/motion_encoder.py (MotionEncoder._encode) through the per-op entries
+ * of this library with the same arguments -- dawn_antialias_down, dawn_conv_gemm, dawn_bn_relu_pool2, dawn_affine_act,
+ * dawn_region_moments, dawn_bg_params, dawn_motion_inputs, dawn_flow_combine -- so the bits are those of the Python orchestration.  The
+ * one launch Python does not have: the source half of the background encoder's first conv, which Python repeats per chunk with
+ * expand().reshape(), is repeated by a copy kernel here (no arithmetic).  Same contract as dawn_decoder: opaque handle, device pointers
+ * by name, caller-owned workspace, every launch on `stream`, no allocation, no synchronisation; an error return comes with a
+ * dawn_last_error message and nothing launched.  The handle is immutable after creation.  One clip per call (B = 1).
+ * Weight names = ctx.motion_named_weights(encoder), from the packed _Conv images of MotionEncoder (pack.py and motion_encoder.py stay
+ * the one definition of the layouts and of the zero padding of every channel count to a multiple of 16).  <conv> = "w" (pack_kn image;
+ * an up block: the four phase images), "ws" (pack_bf3 image, 3x3 convs), "bias"; "a" "b" = the BatchNorm that follows, as scale / shift:
+ *   "rp.down.i.<conv>" "rp.down.i.a|b"   "rp.up.i.<conv>" "rp.up.i.a|b"   "rp.regions.w" "rp.regions.bias"      region predictor
+ *   "bg.src0.<conv>"   "bg.drv0.w" "bg.drv0.ws"   "bg.down.0.a|b"   "bg.down.i.<conv>" "bg.down.i.a|b" (i >= 1)   "fc.w" "fc.b"
+ *                                                    background encoder, its first conv as a source half (with the bias) and a driving half
+ *   "pf.down.i.<conv>" "pf.down.i.a|b"   "pf.up.i.<conv>" "pf.up.i.a|b"   "pf.out.w" "pf.out.bias"              pixelwise flow predictor
+ *                                                    ("pf.out" = the mask and occlusion convs as one 7x7 conv of R + 2 outputs) */
+#define DAWN_MOTION_MAX_BLOCKS 8
+typedef struct dawn_motion dawn_motion;
+typedef struct dawn_motion_cfg {
+    int R;                                   /* regions, 1 .. 15 (10) */
+    int s;                                   /* 1 / scale_factor of both predictors, 1 .. 8 (4): the latent is ceil(H / s) x ceil(W / s) */
+    double temperature;                      /* RegionPredictor's softmax temperature (0.1), the double dawn_region_moments takes */
+    int rp_blocks, bg_blocks, pf_blocks;     /* down blocks of the region hourglass (= its up blocks), of the background encoder, of the
+                                                pixelwise hourglass: 1 .. DAWN_MOTION_MAX_BLOCKS each, refused beyond */
+    int rp_down[DAWN_MOTION_MAX_BLOCKS], rp_up[DAWN_MOTION_MAX_BLOCKS];     /* REAL (unpadded) output channels of every block; the */
+    int bg_down[DAWN_MOTION_MAX_BLOCKS];                                    /* buffers hold each rounded up to a multiple of 16.  The */
+    int pf_down[DAWN_MOTION_MAX_BLOCKS], pf_up[DAWN_MOTION_MAX_BLOCKS];     /* hourglass inputs are 3 and 4 (R + 1) channels */
+} dawn_motion_cfg;
+/* a missing name, a count outside its range: error return with a message that names it, *out untouched */
+int dawn_motion_create(const dawn_motion_cfg* cfg, const dawn_named_ptr* weights, int n_weights, dawn_motion** out);
+void dawn_motion_destroy(dawn_motion* m);
+/* host code: bytes of the workspace for H x W frames encoded `chunk` frames at a time (1 .. 4096) -- independent of the clip length:
+ * the per-clip source pieces, a chunk's activations and, so that driving kind 2 needs no more, a chunk of RGB bytes.  0 (with a
+ * message) for sizes the stage refuses. */
+size_t dawn_motion_workspace_bytes(const dawn_motion* m, int H, int W, int chunk);
+/* src = ONE H x W image, drv = T frames of that size.  Kinds as dawn_antialias_down: 0 = fp32 planes (src: channel c at src + c * H * W
+ * floats; drv: frame t, channel c at drv + t * drv_frame_stride + c * drv_chan_stride floats, so (T,3,H,W) and (3,T,H,W) both go),
+ * 1 = uint8 RGB frames (frame t at drv + t * drv_frame_stride bytes, drv_frame_stride >= 3 H W; drv_chan_stride ignored); driving kind
+ * 2 = I420 frames as dawn_yuv420_to_frames takes them (frame t at drv + t * drv_frame_stride bytes, >= 3 H W / 2), converted chunk by
+ * chunk into the workspace with that kernel and then read as kind 1: a full-clip RGB copy never exists.  src kind 2 is refused.
+ * The source work happens once, first (its downsampled image, its region parameters, its half of the background encoder's first
+ * conv); then the frames go `chunk` at a time (a ragged last chunk is fine; chunk above T counts as T).
+ * Outputs = dawn_flow_combine's: the x plane of frame t at grid + t * h * w, the y plane grid_plane floats further (grid_plane >= T h w),
+ * conf (T,h,w) the occlusion map -- or 2 * conf - 1 with conf_x0 = 1 (the diffusion's x0 plane); h = ceil(H / s), w = ceil(W / s).
+ * Refused before the first launch, the cause named: a NULL argument, T < 1, chunk < 1, an unknown kind, H or W not divisible by
+ * 2^bg_blocks, h or w not divisible by 2^rp_blocks and 2^pf_blocks (or below 2), short strides, a workspace below
+ * dawn_motion_workspace_bytes(m, H, W, min(chunk, T)), an output that overlaps the workspace, and what dawn_yuv420_to_frames refuses. */
+int dawn_motion_encode_clip(dawn_motion* m, int H, int W, int T, const void* src, int src_kind, const void* drv, int drv_kind,
+                            long drv_frame_stride, long drv_chan_stride, int chunk, float* grid, long grid_plane, float* conf, int conf_x0,
+                            void* workspace, size_t workspace_bytes, void* stream);
+/* ---- video-driven reenactment in one call (FlowDiffusion.reenact): source image + driving frames -> frame bytes, built from
+ * dawn_motion_encode_clip (into grid / conf) -> dawn_decoder_encode -> dawn_decode_clip_conf (DAWN_FRAMES_RGB) or
+ * dawn_decode_clip_conf_yuv420 (DAWN_FRAMES_YUV420).  No UNet, no audio.  `size` = sizeof(dawn_reenact_args) of the caller's header:
+ * another value is refused.  All pointers are device pointers except mean3. */
+typedef struct dawn_reenact_args {
+    size_t size;
+    dawn_motion* motion; dawn_decoder* decoder;
+    const float* img3; int H, W;                     /* source image (3,H,W) fp32 planar in [0,1]: both stages read it */
+    const void* drv; int drv_kind; int T;            /* as dawn_motion_encode_clip */
+    long drv_frame_stride, drv_chan_stride;
+    int motion_chunk, chunk;                         /* frames per chunk of the encode / of the decode */
+    int format, bgr;                                 /* DAWN_FRAMES_* as dawn_generate_args; bgr: RGB frames only */
+    const double* mean3;                             /* HOST or NULL, as dawn_decode_clip */
+    unsigned char* frames_out;                       /* (T,H,W,3) or (T, 3 H W / 2) uint8: clip_bytes of dawn_reenact_bytes */
+    float* grid_out; float* conf_out;                /* optional, both or neither: (2,T,h,w) dense and (T,h,w), the encoded motion */
+} dawn_reenact_args;
+/* host code: *clip_bytes = the bytes of frames_out; *workspace_bytes = grid and conf (where grid_out / conf_out are NULL), the decoder's
+ * skip memory -- each rounded up to 256 bytes -- plus the larger of the two stages' workspaces.  What dawn_reenact_clip would refuse:
+ * the same error return, both sizes untouched. */
+int dawn_reenact_bytes(const dawn_reenact_args* args, size_t* clip_bytes, size_t* workspace_bytes);
+int dawn_reenact_clip(const dawn_reenact_args* args, void* workspace, size_t workspace_bytes, void* stream);
 /* ---- model bundle (csrc/dawn_bundle.hip, csrc/dawn_bundle_format.h): ONE file that holds everything the six *_create calls and
  * dawn_generate_args need besides the media -- the packed weight tables, the six cfg structs, named step tables and a defaults
  * record -- so that a host without Python runs the pipeline (tools/dawn_generate.cpp).  Python writes it (dawn_pytorch_amd/bundle.py:
@@ -1145,10 +1233,14 @@ int dawn_flow_combine(const float* x, int ld, const float* drv_shift, const floa
  * dawn_bundle_create_handles creates all six handles from the region and fills the six handle fields of `args` (nothing else of it);
  * DAWN_OPT_UP_BORDER is set from the defaults record when the bundle has one.  A stage missing from the file is an error that names it;
  * on any error the handles made so far are destroyed and `args` is untouched.  dawn_bundle_destroy_handles destroys the six and zeroes
- * the fields.  The region must outlive the handles. */
+ * the fields.  The region must outlive the handles.
+ * DAWN_STAGE_MOTION = 7 (the motion-encode stage, dawn_motion_cfg as its "cfg") came after the format's first release and is OPTIONAL:
+ * the format version stays 1, a file without the stage is as valid as before, dawn_bundle_create_handles neither needs nor reads it,
+ * dawn_bundle_table / dawn_bundle_cfg take stage 7 like 0 .. 5.  A loader from before the stage refuses a file that has it, by the
+ * stage number of the first such index entry. */
 typedef struct dawn_bundle dawn_bundle;
 enum { DAWN_STAGE_HUBERT = 0, DAWN_STAGE_POSE = 1, DAWN_STAGE_BLINK = 2, DAWN_STAGE_DECODER = 3, DAWN_STAGE_INPUTS = 4, DAWN_STAGE_UNET = 5,
-       DAWN_STAGE_HOST = 6 };
+       DAWN_STAGE_HOST = 6, DAWN_STAGE_MOTION = 7 };
 enum { DAWN_BUNDLE_DEVICE = 0, DAWN_BUNDLE_HOST = 1 };
 /* what VideoGenerator takes from the yaml and its fallbacks (UVG:277-278, 329, 340-341) */
 typedef struct dawn_bundle_defaults {
@@ -1171,6 +1263,9 @@ int dawn_bundle_cfg(const dawn_bundle* b, int stage, void* out, size_t out_bytes
 int dawn_bundle_host(const dawn_bundle* b, const char* name, const void** ptr, size_t* bytes);
 int dawn_bundle_create_handles(dawn_bundle* b, const void* device_mem, dawn_generate_args* args);
 void dawn_bundle_destroy_handles(dawn_generate_args* args);
+/* the seventh handle: the motion-encode stage from the table and the "cfg" blob (one dawn_motion_cfg) of DAWN_STAGE_MOTION.  A bundle
+ * without the stage: error "stage 'motion' is missing", *m untouched.  The caller destroys it with dawn_motion_destroy, before the region goes. */
+int dawn_bundle_create_motion(dawn_bundle* b, const void* device_mem, dawn_motion** m);
 /* after a stream synchronise: (kind, algorithmic flops, algorithmic bytes, ms) per conv launch recorded under
  * DAWN_OPT_PROFILE; kind 0 = split 3x3, 1 = split 1x1, 2 = fp32 MFMA; returns the number of entries (and clears them) */
 int dawn_ctx_profile_read(dawn_ctx* ctx, double* out4, int max_entries);

@@ -3,14 +3,17 @@
 `MotionEncoder.latent` on the shipped architecture (config/hdtf256.yaml: region predictor and background encoder block_expansion 32,
 pixelwise predictor 64, max_features 1024, 5 blocks, 10 regions) with random weights -- the times do not depend on the values.
 
-    python tools/bench_motion_encode.py [--res 256] [--frames 200] [--chunk 16] [--repeat 3] [--out profiles/motion_encode.json]
+    python tools/bench_motion_encode.py [--res 256] [--frames 200] [--chunk 16] [--repeat 3] [--via-c] [--out profiles/motion_encode.json]
 
 Prints one JSON line: frames/s of the whole call (device events around it, after a warm-up call), and per op the device time of one
 call summed over its launches (a second, instrumented call: events around every op, so host gaps are not in it).  For the two
 reduction kernels the achieved bytes/s is the bytes each must read (its input once) over its time, against the 8.0 TB/s HBM3E
 specification of an MI355X; for the background encoder's first two convolutions the achieved FLOP/s is the algorithm's multiply-adds
 (unpadded channels) x 2 over their time, against the 2.5 PFLOP/s dense bf16 specification (the split-operand kernel issues six bf16
-products per fp32 product, so 1/6 of it is that kernel's ceiling).  A number that needs a GPU is not produced without one."""
+products per fp32 product, so 1/6 of it is that kernel's ceiling).  A number that needs a GPU is not produced without one.
+--via-c adds the same clip through the C-side stage (`latent(via_c=True)`: dawn_motion_encode_clip, the same launches from C), once from
+the uint8 RGB frames and once from I420 frames (driving kind 2), and the yuv420p ingest alone (dawn_yuv420_to_frames on the whole clip:
+1.5 bytes read and 3 written per pixel, against the same HBM specification)."""
 import argparse
 import json
 import os
@@ -96,6 +99,7 @@ def main():
     ap.add_argument("--frames", type=int, default=200)
     ap.add_argument("--chunk", type=int, default=16)
     ap.add_argument("--repeat", type=int, default=3)
+    ap.add_argument("--via-c", action="store_true", help="also time the C-side stage and the yuv420p ingest")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -120,6 +124,28 @@ def main():
         e1.record()
         torch.cuda.synchronize()
         times.append(e0.elapsed_time(e1) * 1e-3)
+    def best_of(fn):
+        fn()                                                                    # warm-up
+        torch.cuda.synchronize()
+        out = []
+        for _ in range(args.repeat):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            out.append(e0.elapsed_time(e1) * 1e-3)
+        return out
+    via_c = None
+    if args.via_c:
+        yuv = torch.randint(0, 256, (T, H * H * 3 // 2), generator=gd, dtype=torch.uint8).cuda()
+        assert torch.equal(me.latent(src, drv, via_c=True), lat), "the C-side stage must reproduce the Python path's bits"
+        t_c = best_of(lambda: me.latent(src, drv, via_c=True))
+        t_yuv = best_of(lambda: me.latent(src, yuv, via_c=True))
+        t_conv = best_of(lambda: hip.yuv420_to_frames(yuv, H, H))
+        byts = T * H * H * 4.5
+        via_c = dict(seconds=t_c, frames_per_s=T / min(t_c), i420_seconds=t_yuv, i420_frames_per_s=T / min(t_yuv),
+                     yuv420_to_frames=dict(seconds=t_conv, bytes=byts, GBps=byts / min(t_conv) / 1e9, of_hbm_spec=byts / min(t_conv) / HBM_SPEC))
     me.ops = TimedOps(hip)
     me.latent(src, drv)
     torch.cuda.synchronize()
@@ -146,6 +172,8 @@ def main():
     res = dict(bench="motion_encode", device=torch.cuda.get_device_name(0), res=H, frames=T, chunk=args.chunk, seconds=times, frames_per_s=T / best,
                op_ms_sum=sum(ms for _, ms in per_op.values()),
                per_op_ms={k: dict(launches=n, ms=round(ms, 3)) for k, (n, ms) in sorted(per_op.items(), key=lambda kv: -kv[1][1])}, achieved=achieved)
+    if via_c is not None:
+        res["via_c"] = via_c
     line = json.dumps(res)
     print(line)
     if args.out:

@@ -6,7 +6,7 @@
 //   bundle_check [--abi N] mutate FILE     FILE is a valid bundle; in memory: every truncation of its header and index, length by
 //                                          length, then every header and index field set to 0, 2^63 and 2^64 - 1 (32-bit fields: 0, 2^31,
 //                                          2^32 - 1).  One line per case class; exit 0 unless a truncation was accepted or FILE is not valid
-//   bundle_check wav FILE | pnm FILE       parse the file                                    -> exit 0 accepted, 3 refused
+//   bundle_check wav FILE | pnm FILE | y4m FILE       parse the file                         -> exit 0 accepted, 3 refused
 //
 // Build:  g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -I dawn-pytorch_amd/csrc tools/bundle_check.cpp -o bundle_check
 #include <stdio.h>
@@ -87,7 +87,7 @@ int main(int argc, char** argv) {
         i = 3;
     }
     if (argc - i != 2) {
-        fprintf(stderr, "usage: bundle_check [--abi N] bundle|mutate|wav|pnm FILE\n");
+        fprintf(stderr, "usage: bundle_check [--abi N] bundle|mutate|wav|pnm|y4m FILE\n");
         return 2;
     }
     const std::string mode = argv[i];
@@ -113,8 +113,12 @@ int main(int argc, char** argv) {
             media_files::Image im;
             rc = media_files::parse_pnm(raw.data(), raw.size(), &im, &err);
             if (rc == 0) printf("OK %d x %d x %d\n", im.width, im.height, im.channels);
+        } else if (mode == "y4m") {
+            media_files::Y4m v;
+            rc = media_files::parse_y4m(raw.data(), raw.size(), &v, &err);
+            if (rc == 0) printf("OK %ld frames of %d x %d, %zu bytes\n", v.n_frames, v.width, v.height, v.frames.size());
         } else {
-            fprintf(stderr, "usage: bundle_check [--abi N] bundle|mutate|wav|pnm FILE\n");
+            fprintf(stderr, "usage: bundle_check [--abi N] bundle|mutate|wav|pnm|y4m FILE\n");
             return 2;
         }
     }

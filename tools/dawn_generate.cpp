@@ -3,7 +3,11 @@
 //
 //   dawn_generate --bundle M.dawn --wav A.wav --image F.ppm --out clip.y4m
 //                 [--frames T] [--steps ddim.20] [--seed N] [--cond-scale X] [--format y4m|rgb] [--chunk N]
+//   dawn_generate --bundle M.dawn --driving D.y4m --image F.ppm --out clip.y4m [--frames T] [--format y4m|rgb] [--chunk N]
 //
+// With --driving (and no --wav) the clip is video-driven: the motion of the frames of D.y4m (8-bit 4:2:0, of the model's size; the
+// parser and what it refuses: tools/media_files.h) is encoded against the image and decoded from it in one dawn_reenact_clip call --
+// no audio, no sampler.  That needs a bundle with the motion stage; another one is refused with the loader's message.
 // The model comes from a bundle file (dawn_pytorch_amd/bundle.py writes it; include/dawn_hip.h, "model bundle").  The WAV is 16-bit
 // PCM, 1 .. 8 channels, at any rate the resampler takes; the image a binary PPM (P6) or PGM (P5) with maxval 255 (tools/media_files.h).
 // T = min(max_n_frames, frames the audio yields) as the Python host forms it, unless --frames states it.
@@ -42,14 +46,111 @@ size_t up256(size_t n) { return (n + 255) & ~(size_t)255; }
 
 [[noreturn]] void usage() {
     fprintf(stderr, "usage: dawn_generate --bundle M.dawn --wav A.wav --image F.ppm --out clip.y4m [--frames T] [--steps ddim.20] [--seed N]\n"
-                    "                     [--cond-scale X] [--format y4m|rgb] [--chunk N]\n");
+                    "                     [--cond-scale X] [--format y4m|rgb] [--chunk N]\n"
+                    "       dawn_generate --bundle M.dawn --driving D.y4m --image F.ppm --out clip.y4m [--frames T] [--format y4m|rgb] [--chunk N]\n");
     exit(2);
+}
+
+// the frames as a .y4m stream or as raw bytes
+void write_clip(const std::string& out_path, const std::string& format, const std::vector<unsigned char>& out, int H, long T) {
+    FILE* f = fopen(out_path.c_str(), "wb");
+    if (!f) die("cannot write '" + out_path + "'");
+    bool ok = true;
+    if (format == "y4m") {
+        const size_t frame = (size_t)H * H * 3 / 2;
+        ok = fprintf(f, "YUV4MPEG2 W%d H%d F25:1 Ip A1:1 C420jpeg\n", H, H) > 0;
+        for (long t = 0; ok && t < T; ++t) ok = fputs("FRAME\n", f) >= 0 && fwrite(out.data() + (size_t)t * frame, 1, frame, f) == frame;
+    } else {
+        ok = fwrite(out.data(), 1, out.size(), f) == out.size();
+    }
+    if (fclose(f) != 0 || !ok) die("short write to '" + out_path + "'");
+}
+
+// --driving: the frames of a .y4m file reenacted on the image, one dawn_reenact_clip call
+int reenact(const std::string& bundle, const std::string& driving_path, const std::string& image_path, const std::string& out_path,
+            const std::string& format, long frames, int chunk) {
+    std::string err;
+    std::vector<unsigned char> raw;
+    media_files::Y4m drv;
+    media_files::Image img;
+    if (media_files::read_file(driving_path.c_str(), &raw, &err) != 0 || media_files::parse_y4m(raw.data(), raw.size(), &drv, &err) != 0) die(err);
+    if (media_files::read_file(image_path.c_str(), &raw, &err) != 0 || media_files::parse_pnm(raw.data(), raw.size(), &img, &err) != 0) die(err);
+
+    hipStream_t stream = nullptr;
+    hk(hipStreamCreate(&stream), "hipStreamCreate");
+    dawn_bundle* b = nullptr;
+    ck(dawn_bundle_open(bundle.c_str(), &b), "dawn_bundle_open");
+    const size_t model_bytes = std::max<size_t>(dawn_bundle_device_bytes(b), 256), verify_bytes = dawn_bundle_verify_workspace_bytes(b);
+    void *model = nullptr, *verify_ws = nullptr;
+    hk(hipMalloc(&model, model_bytes), "hipMalloc (model)");
+    ck(dawn_bundle_upload(b, model, model_bytes, stream), "dawn_bundle_upload");
+    hk(hipMalloc(&verify_ws, verify_bytes), "hipMalloc (verify workspace)");
+    ck(dawn_bundle_verify(b, model, model_bytes, verify_ws, verify_bytes, stream), "dawn_bundle_verify");
+    hk(hipFree(verify_ws), "hipFree");
+    dawn_motion* motion = nullptr;
+    ck(dawn_bundle_create_motion(b, model, &motion), "dawn_bundle_create_motion");
+    dawn_generate_args g;
+    memset(&g, 0, sizeof g);
+    ck(dawn_bundle_create_handles(b, model, &g), "dawn_bundle_create_handles");
+    const void* blob = nullptr;
+    size_t blob_bytes = 0;
+    ck(dawn_bundle_host(b, "defaults", &blob, &blob_bytes), "dawn_bundle_host");
+    dawn_bundle_defaults def;
+    memcpy(&def, blob, sizeof def);
+    const int H = def.H;
+    if (drv.width != H || drv.height != H)
+        die("y4m: frames of " + std::to_string(drv.width) + " x " + std::to_string(drv.height) + ", the bundle's model takes " + std::to_string(H) + " x " + std::to_string(H));
+    const long T = frames > 0 ? std::min<long>(frames, drv.n_frames) : std::min<long>(def.max_n_frames, drv.n_frames);
+    const double mean3[3] = {def.mean[0] / 255.0, def.mean[1] / 255.0, def.mean[2] / 255.0};
+    const size_t frame_in = (size_t)H * H * 3 / 2;
+
+    // device memory: [image bytes | img3 | I420 frames | ingest workspace] in one allocation, then the frames and the stage workspace
+    const size_t img_bytes = up256(img.pixels.size()), img3_bytes = up256((size_t)3 * H * H * 4), drv_bytes = up256((size_t)T * frame_in);
+    const size_t ingest_bytes = up256(dawn_image_ingest_workspace_bytes(img.height, img.width, H, H));
+    if (ingest_bytes == 0) die(std::string("dawn_image_ingest_workspace_bytes: ") + dawn_last_error());
+    unsigned char* io = nullptr;
+    hk(hipMalloc((void**)&io, img_bytes + img3_bytes + drv_bytes + ingest_bytes), "hipMalloc (media)");
+    float* img3 = (float*)(io + img_bytes);
+    unsigned char* drv_dev = io + img_bytes + img3_bytes;
+    dawn_reenact_args a;
+    memset(&a, 0, sizeof a);
+    a.size = sizeof a;
+    a.motion = motion; a.decoder = g.decoder;
+    a.img3 = img3; a.H = H; a.W = H;
+    a.drv = drv_dev; a.drv_kind = 2; a.T = (int)T; a.drv_frame_stride = (long)frame_in;
+    a.motion_chunk = chunk; a.chunk = chunk;
+    a.format = format == "y4m" ? DAWN_FRAMES_YUV420 : DAWN_FRAMES_RGB;
+    a.mean3 = mean3;
+    size_t clip_bytes = 0, ws_bytes = 0;
+    ck(dawn_reenact_bytes(&a, &clip_bytes, &ws_bytes), "dawn_reenact_bytes");
+    unsigned char* frames_dev = nullptr;
+    void* ws = nullptr;
+    hk(hipMalloc((void**)&frames_dev, clip_bytes), "hipMalloc (frames)");
+    hk(hipMalloc(&ws, ws_bytes), "hipMalloc (workspace)");
+    a.frames_out = frames_dev;
+    hk(hipMemcpyAsync(io, img.pixels.data(), img.pixels.size(), hipMemcpyHostToDevice, stream), "hipMemcpyAsync (image)");
+    hk(hipMemcpyAsync(drv_dev, drv.frames.data(), (size_t)T * frame_in, hipMemcpyHostToDevice, stream), "hipMemcpyAsync (driving)");
+    ck(dawn_image_ingest(io, img.height, img.width, (long)img.width * img.channels, img.channels, DAWN_PIXELS_RGB, H, H, img3, (long)H * H,
+                         io + img_bytes + img3_bytes + drv_bytes, ingest_bytes, stream), "dawn_image_ingest");
+    ck(dawn_reenact_clip(&a, ws, ws_bytes, stream), "dawn_reenact_clip");
+    std::vector<unsigned char> out(clip_bytes);
+    hk(hipMemcpyAsync(out.data(), frames_dev, clip_bytes, hipMemcpyDeviceToHost, stream), "hipMemcpyAsync (frames)");
+    hk(hipStreamSynchronize(stream), "hipStreamSynchronize");
+    write_clip(out_path, format, out, H, T);
+    fprintf(stderr, "dawn_generate: %ld driving frames of %d x %d reenacted (%s) -> %s\n", T, H, H, format.c_str(), out_path.c_str());
+
+    dawn_motion_destroy(motion);
+    dawn_bundle_destroy_handles(&g);
+    dawn_bundle_close(b);
+    (void)hipFree(ws); (void)hipFree(frames_dev); (void)hipFree(io); (void)hipFree(model);
+    (void)hipStreamDestroy(stream);
+    return 0;
 }
 
 }  // namespace
 
 int main(int argc, char** argv) {
-    std::string bundle, wav_path, image_path, out_path, steps_name, format = "y4m";
+    std::string bundle, wav_path, driving_path, image_path, out_path, steps_name, format = "y4m";
     long frames = -1;
     int chunk = 16;
     bool have_seed = false, have_scale = false;
@@ -61,6 +162,7 @@ int main(int argc, char** argv) {
         const char* v = argv[++i];
         if (k == "--bundle") bundle = v;
         else if (k == "--wav") wav_path = v;
+        else if (k == "--driving") driving_path = v;
         else if (k == "--image") image_path = v;
         else if (k == "--out") out_path = v;
         else if (k == "--steps") steps_name = v;
@@ -71,7 +173,8 @@ int main(int argc, char** argv) {
         else if (k == "--cond-scale") { cond_scale = strtof(v, nullptr); have_scale = true; }
         else usage();
     }
-    if (bundle.empty() || wav_path.empty() || image_path.empty() || out_path.empty() || (format != "y4m" && format != "rgb")) usage();
+    if (bundle.empty() || wav_path.empty() == driving_path.empty() || image_path.empty() || out_path.empty() || (format != "y4m" && format != "rgb")) usage();
+    if (!driving_path.empty()) return reenact(bundle, driving_path, image_path, out_path, format, frames, chunk);
 
     // the media, parsed on the host
     std::string err;
@@ -169,17 +272,7 @@ int main(int argc, char** argv) {
     hk(hipMemcpyAsync(out.data(), frames_dev, clip_bytes, hipMemcpyDeviceToHost, stream), "hipMemcpyAsync (frames)");
     hk(hipStreamSynchronize(stream), "hipStreamSynchronize");
 
-    FILE* f = fopen(out_path.c_str(), "wb");
-    if (!f) die("cannot write '" + out_path + "'");
-    bool ok = true;
-    if (format == "y4m") {
-        const size_t frame = (size_t)a.H * a.H * 3 / 2;
-        ok = fprintf(f, "YUV4MPEG2 W%d H%d F25:1 Ip A1:1 C420jpeg\n", a.H, a.H) > 0;
-        for (long t = 0; ok && t < T; ++t) ok = fputs("FRAME\n", f) >= 0 && fwrite(out.data() + (size_t)t * frame, 1, frame, f) == frame;
-    } else {
-        ok = fwrite(out.data(), 1, out.size(), f) == out.size();
-    }
-    if (fclose(f) != 0 || !ok) die("short write to '" + out_path + "'");
+    write_clip(out_path, format, out, a.H, T);
     fprintf(stderr, "dawn_generate: %ld frames of %d x %d (%s, %d %s steps) -> %s\n", T, a.H, a.H, format.c_str(), a.S, ancestral ? "ancestral" : "DDIM",
             out_path.c_str());
 

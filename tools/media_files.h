@@ -1,4 +1,5 @@
-// The two file parsers of tools/dawn_generate.cpp, from memory: a RIFF/WAVE file of 16-bit PCM and a binary PPM / PGM.  Plain C++, no
+// The file parsers of tools/dawn_generate.cpp, from memory: a RIFF/WAVE file of 16-bit PCM, a binary PPM / PGM and a YUV4MPEG2 stream
+// of 8-bit 4:2:0 frames.  Plain C++, no
 // HIP; tools/bundle_check.cpp runs them under the host sanitizers.  Every size read from a file is checked against the bytes that
 // are there before it is used.
 #pragma once
@@ -107,6 +108,91 @@ inline int parse_pnm(const unsigned char* p, size_t n, Image* out, std::string* 
     out->width = (int)v[0];
     out->height = (int)v[1];
     out->pixels.assign(p + at, p + at + need);
+    return 0;
+}
+
+// A YUV4MPEG2 (.y4m) stream of 8-bit 4:2:0 frames, as tools/dawn_generate.cpp writes them and dawn_yuv420_to_frames reads them.
+//   stream header   "YUV4MPEG2" then space-separated tokens up to a newline: W<width> H<height> are required; F (rate), A (aspect) and
+//                   X (comment) tokens are accepted and ignored; I = interlacing: "Ip" and "I?" only; C = colourspace: "C420",
+//                   "C420jpeg", "C420mpeg2", "C420paldv" or none -- ALL taken as 8-bit 4:2:0 whose chroma sample is replicated over its
+//                   2 x 2 block: the siting differences between them (a shift of at most half a pixel) are ignored.
+//   frames          "FRAME", optional parameters, a newline, then W H + 2 (W/2) (H/2) bytes: Y, U, V planes (I420).
+// A header line (stream or frame) longer than 256 bytes, another colourspace or bit depth, interlaced content, a W or H that the
+// kernel does not take (W % 4, H % 2, 2 .. 65536), a truncated last frame, a stream without a frame: refused, the cause named.
+struct Y4m {
+    int width = 0, height = 0;
+    long n_frames = 0;
+    std::vector<unsigned char> frames;         // n_frames x (3 W H / 2) bytes, back to back
+};
+constexpr size_t Y4M_MAX_LINE = 256;
+
+// the line that starts at p[at]: *end = the index of its '\n'; a line without one within Y4M_MAX_LINE bytes (or the file) is refused
+inline int y4m_line(const unsigned char* p, size_t n, size_t at, const char* what, size_t* end, std::string* err) {
+    for (size_t i = at; i < n; ++i) {
+        if (i - at >= Y4M_MAX_LINE) return refuse(err, std::string("y4m: ") + what + " is longer than 256 bytes");
+        if (p[i] == '\n') {
+            *end = i;
+            return 0;
+        }
+    }
+    if (n - at >= Y4M_MAX_LINE) return refuse(err, std::string("y4m: ") + what + " is longer than 256 bytes");
+    return refuse(err, std::string("y4m: ") + what + " ends early (no newline)");
+}
+
+inline int parse_y4m(const unsigned char* p, size_t n, Y4m* out, std::string* err) {
+    if (n < 10 || memcmp(p, "YUV4MPEG2", 9) != 0 || (p[9] != ' ' && p[9] != '\n')) return refuse(err, "y4m: not a YUV4MPEG2 stream");
+    size_t end = 0;
+    if (y4m_line(p, n, 0, "the stream header", &end, err) != 0) return -1;
+    long W = -1, H = -1;
+    size_t at = 9;
+    while (at < end) {
+        if (p[at] == ' ') {
+            ++at;
+            continue;
+        }
+        size_t stop = at;
+        while (stop < end && p[stop] != ' ') ++stop;
+        const std::string tok((const char*)p + at, stop - at);
+        at = stop;
+        const std::string val = tok.substr(1);
+        if (tok[0] == 'W' || tok[0] == 'H') {
+            long v = 0;
+            if (val.empty() || val.size() > 6) return refuse(err, "y4m: bad header token '" + tok + "'");
+            for (char ch : val) {
+                if (ch < '0' || ch > '9') return refuse(err, "y4m: bad header token '" + tok + "'");
+                v = v * 10 + (ch - '0');
+            }
+            (tok[0] == 'W' ? W : H) = v;
+        } else if (tok[0] == 'C') {
+            if (val != "420" && val != "420jpeg" && val != "420mpeg2" && val != "420paldv")
+                return refuse(err, "y4m: colourspace '" + tok + "' (8-bit 4:2:0 only: C420, C420jpeg, C420mpeg2, C420paldv)");
+        } else if (tok[0] == 'I') {
+            if (val != "p" && val != "?") return refuse(err, "y4m: interlacing '" + tok + "' (progressive only: Ip or I?)");
+        } else if (tok[0] != 'F' && tok[0] != 'A' && tok[0] != 'X') {
+            return refuse(err, "y4m: unknown header token '" + tok + "'");
+        }
+    }
+    if (W < 0 || H < 0) return refuse(err, "y4m: the stream header lacks W or H");
+    if (W < 4 || W > 65536 || W % 4 != 0) return refuse(err, "y4m: W" + std::to_string(W) + " (a multiple of 4, 4 .. 65536)");
+    if (H < 2 || H > 65536 || H % 2 != 0) return refuse(err, "y4m: H" + std::to_string(H) + " (even, 2 .. 65536)");
+    const size_t frame = (size_t)W * (size_t)H / 2 * 3;           // at most 3 * 2^31: fits size_t
+    out->width = (int)W;
+    out->height = (int)H;
+    out->n_frames = 0;
+    out->frames.clear();
+    at = end + 1;
+    while (at < n) {
+        if (y4m_line(p, n, at, "a FRAME header", &end, err) != 0) return -1;
+        if (end - at < 5 || memcmp(p + at, "FRAME", 5) != 0 || (end - at > 5 && p[at + 5] != ' '))
+            return refuse(err, "y4m: no FRAME header where frame " + std::to_string(out->n_frames) + " starts");
+        at = end + 1;
+        if (n - at < frame)
+            return refuse(err, "y4m: frame " + std::to_string(out->n_frames) + " is cut: " + std::to_string(n - at) + " bytes, " + std::to_string(frame) + " needed");
+        out->frames.insert(out->frames.end(), p + at, p + at + frame);
+        at += frame;
+        ++out->n_frames;
+    }
+    if (out->n_frames < 1) return refuse(err, "y4m: no frame");
     return 0;
 }
 
