@@ -29,6 +29,8 @@ from typing import Dict, Mapping, Optional, Sequence, Tuple
 
 import numpy as np
 
+from .ctx import ClipMode
+
 MAGIC = b"DAWNBNDL"
 VERSION = 1
 HEADER_BYTES, ENTRY_FIXED_BYTES, ALIGN, HOST_ALIGN = 64, 48, 256, 16
@@ -39,16 +41,12 @@ DTYPES = {"uint8": 0, "float32": 1, "bfloat16": 2, "float16": 3, "int32": 4, "fl
 _M64 = (1 << 64) - 1
 
 
-class ClipModeC(C.Structure):
-    _fields_ = [("kind", C.c_int), ("q", C.c_double)]
-
-
 class Defaults(C.Structure):
     """Mirror of ``dawn_bundle_defaults``."""
     _fields_ = [("H", C.c_int), ("fea_ch", C.c_int), ("latent_dim", C.c_int), ("max_n_frames", C.c_int), ("sampling_step", C.c_int),
                 ("ancestral", C.c_int), ("cond_scale", C.c_float),
                 ("up_border", C.c_int), ("random_seed", C.c_uint64), ("mean", C.c_double * 3), ("bbox6", C.c_float * 6),
-                ("init_pose6", C.c_float * 6), ("init_blink2", C.c_float * 2), ("clip", ClipModeC)]
+                ("init_pose6", C.c_float * 6), ("init_blink2", C.c_float * 2), ("clip", ClipMode)]
 
 
 # VideoGenerator's fallbacks: the bbox of UVG:340-341, the init pose / blink of UVG:277-278, the yaml's shipped values

@@ -24,6 +24,9 @@
 extern "C" {
 #endif
 
+/* The ABI number of this header.  dawn_abi_version() returns the one the library was built from; the Python binding derives every
+ * argument type from this file and refuses a library whose number differs. */
+#define DAWN_ABI_VERSION 8
 const char* dawn_last_error(void);
 int dawn_abi_version(void);
 

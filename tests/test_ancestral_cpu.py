@@ -60,9 +60,6 @@ def test_ancestral_symbols_declared_exported_and_bound():
     for n in ANCESTRAL:
         assert hasattr(L, n), n
     assert L.dawn_abi_version() == 8
-    for n in ANCESTRAL:
-        decl = re.search(r"\b" + n + r"\s*\(([^;]*)\)\s*;", src, flags=re.S).group(1)
-        assert len(_lib.SIGNATURES[n]) == decl.count(",") + 1, n
     # the step struct and its ctypes mirror agree field by field
     from dawn_pytorch_amd.ctx import AncestralStep, CtxEvaluator
     body = re.search(r"typedef struct dawn_ancestral_step \{(.*?)\} dawn_ancestral_step;", src, flags=re.S).group(1)

@@ -1,11 +1,15 @@
-"""No-GPU checks of the C-ABI library: it loads, exports every symbol include/dawn_hip.h declares, and the
-ctypes mirror of `dawn_conv_desc` has the C layout (no compute calls without a GPU)."""
+"""No-GPU checks of the C-ABI library and of its binding: the header reader (dawn_pytorch_amd/abi.py) reads every declaration of
+include/dawn_hip.h and refuses what it cannot read, the library exports and binds all of them, and every hand-written ctypes struct
+mirror has the header's layout (no compute calls without a GPU)."""
 import ctypes
+import importlib.util
 import os
 import re
 
+import pytest
+
 from conftest import ROOT
-from dawn_pytorch_amd import _lib
+from dawn_pytorch_amd import _lib, abi
 
 
 def header_functions():
@@ -14,47 +18,135 @@ def header_functions():
     return sorted(set(re.findall(r"\b(dawn_[a-z0-9_]+)\s*\(", src)))
 
 
+def header_text():
+    return open(os.path.join(ROOT, "include", "dawn_hip.h")).read()
+
+
 def test_library_exports_every_declared_symbol():
+    """Every declaration is bound: the names a loose regex finds in the header, the names abi.functions() reads, and the names the
+    library exports with the derived argtypes set are one set."""
     L = _lib.lib()
     names = header_functions()
-    assert len(names) >= 25
-    for n in names:
+    assert len(names) >= 160
+    derived = abi.functions(header_text())
+    assert set(names) == set(derived) == set(_lib.SIGNATURES), set(names) ^ set(derived) ^ set(_lib.SIGNATURES)
+    for n, (restype, argtypes) in derived.items():
         assert hasattr(L, n), f"{n} declared in include/dawn_hip.h but not exported by libdawn_hip.so"
-    # whole-path entry points (bound with their own argtypes in dawn_pytorch_amd/ctx.py) + host-side helpers
-    CTX = {"dawn_ctx_create", "dawn_ctx_destroy", "dawn_ctx_set_option", "dawn_clip_bytes", "dawn_workspace_bytes",
-           "dawn_clip_prepare", "dawn_unet_forward", "dawn_sampler_run", "dawn_ctx_profile_read", "dawn_chw_to_hwc",
-           "dawn_rotary_tables", "dawn_rel_pos_bucket", "dawn_workspace_bytes_sharded", "dawn_unet_forward_sharded",
-           "dawn_sampler_run_sharded"}
-    declared = set(names) - {"dawn_last_error", "dawn_abi_version"} - CTX
-    assert CTX <= set(names)
-    assert declared == set(_lib.SIGNATURES), declared ^ set(_lib.SIGNATURES)
-    assert L.dawn_abi_version() == 8
+        fn = getattr(L, n)
+        assert fn.argtypes is not None and list(fn.argtypes) == argtypes == _lib.SIGNATURES[n] and fn.restype is restype, n
+    assert L.dawn_abi_version() == 8 == abi.defines(header_text())["DAWN_ABI_VERSION"]
     # no process-global tuning hooks / ablation entry points in the shipped library (policy travels in dawn_conv_desc)
     for gone in ("dawn_conv_set_variant", "dawn_conv_set_debug"):
         assert not hasattr(L, gone), gone
 
 
-def test_conv_desc_layout_matches_c():
-    """Offsets computed the way a C compiler lays out the struct in the header (natural alignment)."""
-    src = open(os.path.join(ROOT, "include", "dawn_hip.h")).read()
-    body = src[src.index("typedef struct dawn_conv_desc {") + 31:src.index("} dawn_conv_desc;")]
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        is_wide = "*" in decl or decl.startswith("size_t") or decl.startswith("double")
-        for name in re.sub(r"^(const\s+)?(float|int|double|void|size_t|unsigned)\s*\*?", "", decl).split(","):
-            fields.append((name.strip().lstrip("*").strip(), 8 if is_wide else 4))
-    off, expect = 0, {}
-    for name, size in fields:
-        off = (off + size - 1) // size * size
-        expect[name] = off
-        off += size
-    for name, _ in _lib.ConvDesc._fields_:
-        assert getattr(_lib.ConvDesc, name).offset == expect[name], name
-    assert ctypes.sizeof(_lib.ConvDesc) == (off + 7) // 8 * 8
+_p, _i, _l, _f, _d, _z = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_double, ctypes.c_size_t
+# written out from include/dawn_hip.h by hand: every scalar kind and every return kind appears
+PINNED = {
+    "dawn_heads_eps": (_i, [_p] * 7 + [_i, _i, _p, _i, _i, _p, _p, _p, _p, _l, _i, _p, _p]),
+    "dawn_select_scan": (_i, [_p, _i, ctypes.c_ulonglong, _p, _i, _p]),
+    "dawn_philox_normal": (_i, [_p, _i, _i, _i, _i, _i, ctypes.c_uint64, ctypes.c_uint32, _p]),
+    "dawn_frames_to_u8": (_i, [_p, _l, _l, _d, _d, _d, _i, _p, _p]),
+    "dawn_gn_finalize": (_i, [_p, _d, _p, _p, _p, _p, _i, _f, _p, _p, _p]),
+    "dawn_bundle_open": (_i, [ctypes.c_char_p, _p]),
+    "dawn_sampler_run_dpmpp": (_i, [_p, _i, _i, _i, _p, _p, _f, _p, _i, _p, _p, _p, _p, _z, _p, _p, _p]),
+    "dawn_resample16k_len": (_l, [_l, _i]),
+    "dawn_clip_bytes": (_z, [_p, _i, _i, _i]),
+    "dawn_ctx_destroy": (None, [_p]),
+    "dawn_last_error": (ctypes.c_char_p, []),
+}
+
+
+@pytest.mark.parametrize("name", sorted(PINNED))
+def test_pinned_signatures(name):
+    fn = getattr(_lib.lib(), name)
+    restype, argtypes = PINNED[name]
+    assert fn.restype is restype and list(fn.argtypes) == argtypes
+
+
+@pytest.mark.parametrize("decl,quoted", [
+    ("int dawn_ok(int a);\nint dawn_x(flaot y, void* stream);", "dawn_x(flaot y"),                      # unknown type
+    ("int dawn_x(int (*cb)(void* user), void* stream);", "dawn_x(int (*cb)"),                           # function-pointer argument
+    ("int dawn_x(int n, ...);", "dawn_x(int n, ...)"),                                                  # outside the grammar
+    ("int dawn_x(int);", "dawn_x(int)"),                                                                # unnamed argument
+    ("static inline int dawn_x(int n) { return n; }\nint dawn_y(int n);", "dawn_x(int n)"),             # a body, not a declaration
+    ("typedef struct dawn_s { int n[DAWN_NOT_DEFINED]; } dawn_s;", "DAWN_NOT_DEFINED"),
+    ("typedef struct dawn_s { dawn_other o; } dawn_s;", "dawn_other"),
+    ("int dawn_x(int n)", "dawn_x(int n)"),                                                             # no terminating semicolon
+])
+def test_reader_refuses_what_it_cannot_read(decl, quoted):
+    with pytest.raises(abi.HeaderError) as e:
+        abi.functions(decl)
+    assert quoted in str(e.value)
+
+
+def test_reader_on_header_strings():
+    text = """#define DAWN_N 3  /* a size */
+    typedef struct dawn_h dawn_h;
+    typedef struct dawn_in { int kind; double q; } dawn_in;
+    typedef struct dawn_s { const float* a, * b; int n[DAWN_N], m; dawn_in in; int (*cb)(void* user, int n); const char* name; } dawn_s;
+    enum { DAWN_A = 0, DAWN_B = 1 };
+    void dawn_f(dawn_h* h, const dawn_s* s, const float* const* rows, unsigned char* bytes, int16_t v, /* comment, with ( */ unsigned u);
+    const char* dawn_g(void);   // trailing
+    dawn_h* dawn_make(size_t n);"""
+    f, s = abi.functions(text), abi.structs(text)
+    assert f == {"dawn_f": (None, [_p, _p, _p, _p, ctypes.c_int16, ctypes.c_uint]), "dawn_g": (ctypes.c_char_p, []), "dawn_make": (_p, [_z])}
+    assert [n for n, _ in s["dawn_s"]] == ["a", "b", "n", "m", "in", "cb", "name"] and abi.defines(text) == {"DAWN_N": 3}
+    S = type("S", (ctypes.Structure,), {"_fields_": s["dawn_s"]})
+    assert (S.n.offset, S.m.offset, getattr(S, "in").offset, S.cb.offset, S.name.offset, ctypes.sizeof(S)) == (16, 28, 32, 48, 56, 64)
+    assert s["dawn_s"][6][1] is ctypes.c_char_p and s["dawn_s"][0][1] is _p
+
+
+def test_lib_refuses_a_missing_header_and_another_abi_number(tmp_path, monkeypatch):
+    monkeypatch.setattr(_lib, "_lib", None)
+    monkeypatch.setattr(_lib, "HEADER_PATH", tmp_path / "absent.h")
+    with pytest.raises(_lib.DawnHipError, match="absent.h"):
+        _lib.lib()
+    newer = tmp_path / "dawn_hip.h"
+    newer.write_text(header_text().replace("#define DAWN_ABI_VERSION 8", "#define DAWN_ABI_VERSION 9"))
+    monkeypatch.setattr(_lib, "HEADER_PATH", newer)
+    with pytest.raises(_lib.DawnHipError, match=r"ABI version 8.*DAWN_ABI_VERSION 9"):
+        _lib.lib()
+    # DAWN_HIP_HEADER names the header as DAWN_HIP_LIB names the library; importing the module never fails, lib() does
+    monkeypatch.setenv("DAWN_HIP_HEADER", str(tmp_path / "absent.h"))
+    spec = importlib.util.spec_from_file_location("dawn_pytorch_amd._lib_without_header", _lib.__file__)
+    probe = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(probe)
+    assert probe.SIGNATURES == {} and len(_lib.SIGNATURES) >= 160
+    with pytest.raises(probe.DawnHipError, match="absent.h"):
+        probe.lib()
+
+
+def struct_mirrors():
+    from dawn_pytorch_amd import bundle, ctx
+    from test_tl16_schedule_cpu import Sched
+    return {"dawn_conv_desc": _lib.ConvDesc, "dawn_tl16_sched": Sched, "dawn_unet_cfg": ctx.UnetCfg, "dawn_named_ptr": ctx.NamedPtr,
+            "dawn_ddim_step": ctx.DdimStep, "dawn_shard_comm": ctx.ShardCommC, "dawn_ancestral_step": ctx.AncestralStep,
+            "dawn_clip_mode": ctx.ClipMode, "dawn_dpmpp_step": ctx.DpmppStep, "dawn_decoder_cfg": ctx.DecoderCfg,
+            "dawn_hubert_cfg": ctx.HubertCfg, "dawn_pbnet_cfg": ctx.PbnetCfg, "dawn_inputs_cfg": ctx.InputsCfg,
+            "dawn_generate_args": ctx.GenerateArgs, "dawn_media_args": ctx.MediaArgs, "dawn_motion_cfg": ctx.MotionCfg,
+            "dawn_reenact_args": ctx.ReenactArgs, "dawn_bundle_defaults": bundle.Defaults}
+
+
+STRUCTS = sorted(abi.structs(header_text()))
+
+
+def test_every_header_struct_has_one_mirror():
+    from dawn_pytorch_amd import bundle, ctx
+    assert STRUCTS == sorted(struct_mirrors()) and len(STRUCTS) == 18
+    assert dict(bundle.Defaults._fields_)["clip"] is ctx.ClipMode and not hasattr(bundle, "ClipModeC")
+
+
+@pytest.mark.parametrize("name", STRUCTS)
+def test_struct_mirror_matches_header(name):
+    """The hand-written ctypes mirror against the header's struct in natural C layout: field names in order, every offset, every
+    field size, sizeof and alignment.  (The C side pins the same layouts with static_asserts; this is the Python side.)"""
+    mirror = struct_mirrors()[name]
+    want = type(name, (ctypes.Structure,), {"_fields_": abi.structs(header_text())[name]})
+    assert [n for n, _ in mirror._fields_] == [n for n, _ in want._fields_]
+    for n, _ in want._fields_:
+        assert (getattr(mirror, n).offset, getattr(mirror, n).size) == (getattr(want, n).offset, getattr(want, n).size), n
+    assert (ctypes.sizeof(mirror), ctypes.alignment(mirror)) == (ctypes.sizeof(want), ctypes.alignment(want))
 
 
 def test_host_side_helpers_match_python_and_reference():
@@ -71,17 +163,6 @@ def test_host_side_helpers_match_python_and_reference():
             (12801, 768, 128, 0): 0, (204800, 768, 48, 0): 0, (819200, 64, 256, 0): 1, (819200, 64, 192, 0): 0, (51200, 192, 256, 256): 1}
     for (M, N, C0, C1), ok in want.items():
         assert int(L.dawn_gemm1x1_split_ok(M, N, C0, C1)) == ok, (M, N, C0, C1)
-
-
-def test_ctx_structs_match_header():
-    """ctypes mirrors of dawn_unet_cfg / dawn_ddim_step have the sizes the C declarations imply."""
-    from dawn_pytorch_amd import ctx
-    assert ctypes.sizeof(ctx.UnetCfg) == 4 * (2 + 8 + 1 + 3 + 1)
-    assert ctypes.sizeof(ctx.DdimStep) == 4 * 7
-    assert ctypes.sizeof(ctx.NamedPtr) == 16
-    # dawn_shard_comm: void* user; int rank, world; five function pointers
-    assert ctypes.sizeof(ctx.ShardCommC) == 8 + 4 + 4 + 5 * 8
-    assert ctx.ShardCommC.halo_begin.offset == 16 and ctx.ShardCommC.allreduce_min_u32.offset == 48
 
 
 def header_constants(prefix):

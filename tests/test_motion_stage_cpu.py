@@ -8,7 +8,6 @@
   tests/test_bundle_cpu.py builds it, run as a child process: exit status 0 (accepted) or 3 (refused), no sanitizer report."""
 import ctypes as C
 import os
-import re
 import shutil
 import struct
 import subprocess
@@ -68,12 +67,9 @@ def test_exhaustive_frame_holds_every_triple_once():
 
 def test_symbols_and_signatures():
     L = _lib.lib()
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "dawn_hip.h")).read(), flags=re.S)
     for n in NEW:
         assert hasattr(L, n) and n in _lib.SIGNATURES, n
-        decl = re.search(rf"\b{n}\s*\(([^)]*)\)", src)
-        assert decl and len(_lib.SIGNATURES[n]) == len(decl.group(1).split(",")), n
-    assert L.dawn_abi_version() == 8 and "dawn_motion_workspace_bytes" in _lib.LONG_RESULT
+    assert L.dawn_abi_version() == 8 and L.dawn_motion_workspace_bytes.restype is C.c_size_t
     assert C.sizeof(ctx.MotionCfg) == 192 and ctx.MotionCfg.temperature.offset == 8 and ctx.MotionCfg.rp_down.offset == 28 and C.sizeof(ctx.ReenactArgs) == 120
     # host-side refusals of the converter: nothing is launched for them, so no GPU is needed
     buf = C.create_string_buffer(64)

@@ -82,7 +82,7 @@ def test_entries_exported_bound_and_abi_unchanged():
         assert hasattr(L, n), f"{n} not exported by libdawn_hip.so"
         assert n in _lib.SIGNATURES, f"{n} not bound in _lib.SIGNATURES"
     assert L.dawn_abi_version() == 8
-    assert L.dawn_pbnet_workspace_bytes.restype is C.c_long and L.dawn_pose_blink_workspace_bytes.restype is C.c_long
+    assert L.dawn_pbnet_workspace_bytes.restype is C.c_size_t and L.dawn_pose_blink_workspace_bytes.restype is C.c_size_t
 
 
 def test_cfg_layout_matches_header():

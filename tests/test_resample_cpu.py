@@ -3,14 +3,11 @@ signatures, the two host helpers against the Python formulas, every refusal (ref
 device), the oracle of tests/resample_cases.py against its own 80-bit evaluation, dawn_pytorch_amd/audio.py against the oracle under the
 gate, the WAV reader, the filter's pass band and stop band on the oracle, and that the gate rejects four defects."""
 import ctypes as C
-import os
-import re
 import wave
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
 from dawn_pytorch_amd import _lib, audio, ctx
 from resample_cases import (ALL_CASES, IMPULSE_AT, RATES, assert_gate, impulse, case_id, gate_excess, oracle, out_len, pcm_for, plan, reference, table_bytes)
 
@@ -27,16 +24,11 @@ def err():
 # ---------------------------------------------------------------------------------------------- symbols, signatures, helpers
 def test_symbols_signatures_and_abi():
     L = _lib.lib()
-    src = open(os.path.join(ROOT, "include", "dawn_hip.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
     for n in NEW:
         assert hasattr(L, n), n
         assert n in _lib.SIGNATURES, n
-        decl = re.search(rf"\b{n}\s*\(([^)]*)\)", src)
-        assert decl, n
-        assert len(_lib.SIGNATURES[n]) == len(decl.group(1).split(",")), n
     assert L.dawn_abi_version() == 8
-    assert {"dawn_resample16k_len", "dawn_resample16k_workspace_bytes"} <= _lib.LONG_RESULT
+    assert L.dawn_resample16k_len.restype is C.c_long and L.dawn_resample16k_workspace_bytes.restype is C.c_size_t
 
 
 def test_length_and_workspace_helpers_equal_the_formulas():

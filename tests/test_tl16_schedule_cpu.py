@@ -16,12 +16,8 @@ class Sched(ctypes.Structure):
 
 
 def schedule(Fext, q0, Fq, win):
-    L = _lib.lib()
-    f = L.dawn_tl16_schedule
-    f.argtypes = [ctypes.c_int] * 4 + [ctypes.c_void_p, ctypes.c_void_p]
-    f.restype = ctypes.c_int
     s, u = Sched(), (ctypes.c_int * 8)()
-    ok = f(Fext, q0, Fq, win, ctypes.byref(s), ctypes.byref(u))
+    ok = _lib.lib().dawn_tl16_schedule(Fext, q0, Fq, win, ctypes.byref(s), ctypes.byref(u))
     return ok, [((w & 31, (w >> 5) & 31), (w >> 10) & 7, (w >> 13) & 31, (w >> 18) & 31) for w in s.w], list(u)
 
 
@@ -83,12 +79,8 @@ def test_schedule_refuses_shapes_outside_the_kernel(Fext, q0, Fq, win):
 # ---- the 13-wave form (WMODE 5, temporal_layer13_kernel): one query tile per wave, wave w on SIMD w & 3 ------------------------------
 
 def schedule13(Fext, q0, Fq, win):
-    L = _lib.lib()
-    f = L.dawn_tl13_schedule
-    f.argtypes = [ctypes.c_int] * 4 + [ctypes.c_void_p]
-    f.restype = ctypes.c_int
     w = (ctypes.c_uint * 16)()
-    ok = f(Fext, q0, Fq, win, ctypes.byref(w))
+    ok = _lib.lib().dawn_tl13_schedule(Fext, q0, Fq, win, ctypes.byref(w))
     return ok, [(x & 31, (x >> 5) & 7, (x >> 8) & 31, (x >> 13) & 31) for x in w]
 
 
