@@ -41,7 +41,7 @@ int refuse(int code, const char* who, const char* what) {
 
 struct AaTaps {
     float g[AA_MAX_K];       // the reference's fp32 1-D factors exp(-(i - mean)^2 / (2 sigma^2))
-    float sum;               // the fp32 sum of the fp32 products g[i] * g[j], row by row
+    float sum;               // the sum of the fp32 products g[i] * g[j], taken in double and rounded once
 };
 
 __device__ __forceinline__ float grid_coord(int j, int n) {
@@ -433,10 +433,12 @@ extern "C" int dawn_antialias_down(const void* in, int in_kind, long frame_strid
     const double sigma = 0.5 * (double)(s - 1), mean = 0.5 * (double)(K - 1);
     for (int i = 0; i < AA_MAX_K; ++i) taps.g[i] = i < K ? (float)exp(-((double)i - mean) * ((double)i - mean) / (2.0 * sigma * sigma)) : 0.f;
     if (s == 1) taps.g[0] = 1.f;                                 // scale 1: the reference returns its input (UTIL:257-258); here the layout change alone
-    float sum = 0.f;
+    // The reference divides by torch.sum of the K x K fp32 products, which is blocked and good to ~4e-8; a running fp32 sum of the 841
+    // products of s = 8 is not (-2.8e-6, and 6.5e-7 at s = 4: a scale error on every output), so the products are summed in double.
+    double sum = 0.0;
     for (int i = 0; i < K; ++i)
-        for (int j = 0; j < K; ++j) sum += taps.g[i] * taps.g[j];
-    taps.sum = sum;
+        for (int j = 0; j < K; ++j) sum += (double)(taps.g[i] * taps.g[j]);
+    taps.sum = (float)sum;
     const int ho = (H + s - 1) / s, wo = (W + s - 1) / s;
     const int tiles_x = dawn_cdiv(wo, AA_TILE), tiles_y = dawn_cdiv(ho, AA_TILE);
     const dim3 grid((unsigned)tiles_x * (unsigned)tiles_y, (unsigned)T);

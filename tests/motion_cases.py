@@ -24,13 +24,16 @@ S = 4                                        # 1 / scale_factor of both predicto
 TINY = dict(block_expansion=8, max_features=32, num_blocks=3)
 GEN_TINY = dict(block_expansion=16, max_features=32, num_down_blocks=2, num_bottleneck_blocks=1)      # the generator's own trunk (decode half)
 CASES = {"A": dict(H=96, W=96, T=5), "B": dict(H=256, W=256, T=2)}
+# End-to-end only (optical_flow and occlusion_map, no stage values): kept apart from CASES, whose tests expect the full stage set.
+# N is not square (h = 24, w = 32): a swap of the two sides anywhere between the frames and the latent shows here, and on no square case.
+E2E_CASES = {"N": dict(H=96, W=128, T=2)}
 GAP_MIN = 1e-3                               # relative eigen-gap below which a region's eigenvectors are not compared
 SKIP_CAP = 0.10                              # ... for at most this share of a golden's regions
 
 
 def frames_u8(case):
     """-> (source (H,W,3) uint8, driving (T,H,W,3) uint8): triangle waves of quadratic forms that drift with the frame index."""
-    c = CASES[case]
+    c = CASES[case] if case in CASES else E2E_CASES[case]
     H, W, T = c["H"], c["W"], c["T"]
     y = np.arange(H, dtype=np.int64).reshape(1, H, 1, 1)
     x = np.arange(W, dtype=np.int64).reshape(1, 1, W, 1)
@@ -48,14 +51,15 @@ def to_float(u8):
     return t.movedim(-1, -3).contiguous()
 
 
-def coordinate_grid(h, w):
-    """UTIL:51-67 in fp32, as float64: (h, w, 2) = (x, y)."""
+def coordinate_grid(h, w, dtype=torch.float64):
+    """UTIL:51-67 in fp32, as float64 (or `dtype`: the fp32 grid is an input in either): (h, w, 2) = (x, y)."""
     x = 2 * (torch.arange(w).float() / (w - 1)) - 1
     y = 2 * (torch.arange(h).float() / (h - 1)) - 1
-    return torch.stack((x.view(1, w).expand(h, w), y.view(h, 1).expand(h, w)), 2).double()
+    return torch.stack((x.view(1, w).expand(h, w), y.view(h, 1).expand(h, w)), 2).to(dtype)
 
 
 # ---------------------------------------------------------------------------------------------- the five definitions, float64
+# (`dtype`: the same restatement in another float type -- float32 is the CPU fp32 baseline of tests/motion_gate.py)
 def aa_kernel(s):
     """UTIL:222-247: the fp32 product kernel divided by its fp32 sum, (K, K)."""
     sigma = (s - 1) / 2
@@ -67,11 +71,11 @@ def aa_kernel(s):
     return k2 / torch.sum(k2)
 
 
-def antialias_down(x, s):
+def antialias_down(x, s, dtype=torch.float64):
     """UTIL:256-264: x (T,3,H,W) -> (T,3,ceil(H/s),ceil(W/s)) float64."""
-    k2 = aa_kernel(s).double()
+    k2 = aa_kernel(s).to(dtype)
     ka = k2.shape[0] // 2
-    out = F.conv2d(F.pad(x.double(), (ka, ka, ka, ka)), k2.view(1, 1, *k2.shape).repeat(3, 1, 1, 1), groups=3)
+    out = F.conv2d(F.pad(x.to(dtype), (ka, ka, ka, ka)), k2.view(1, 1, *k2.shape).repeat(3, 1, 1, 1), groups=3)
     return out[:, :, ::s, ::s]
 
 
@@ -99,68 +103,68 @@ def eigen_gap(covar):
     return 2 * rad / (0.5 * (a + c) + rad)
 
 
-def region_moments(x, h, w, temperature=TEMPERATURE):
+def region_moments(x, h, w, temperature=TEMPERATURE, dtype=torch.float64):
     """RP:84-117 after the `regions` conv: x (T, h*w, R) -> shift (T,R,2), covar (T,R,2,2), affine (T,R,2,2), float64."""
-    p = torch.softmax(x.double() / temperature, dim=1)                               # over the pixels
-    g = coordinate_grid(h, w).reshape(h * w, 2)
+    p = torch.softmax(x.to(dtype) / temperature, dim=1)                              # over the pixels
+    g = coordinate_grid(h, w, dtype).reshape(h * w, 2)
     shift = torch.einsum("tpr,pc->trc", p, g)
     d = g.view(1, 1, h * w, 2) - shift.unsqueeze(2)                                  # (T,R,hw,2)
     covar = torch.einsum("tpr,trpa,trpb->trab", p, d, d)
     return shift, covar, sqrt_factor(covar)
 
 
-def bg_params(last, fc_w, fc_b):
+def bg_params(last, fc_w, fc_b, dtype=torch.float64):
     """BG:46-52: last (T, npix, C) -> (T,3,3) float64."""
-    v = last.double().mean(dim=1) @ fc_w.double().t() + fc_b.double()
-    out = torch.eye(3, dtype=torch.float64).repeat(last.shape[0], 1, 1)
+    v = last.to(dtype).mean(dim=1) @ fc_w.to(dtype).t() + fc_b.to(dtype)
+    out = torch.eye(3, dtype=dtype).repeat(last.shape[0], 1, 1)
     out[:, :2, :] = v.view(-1, 2, 3)
     return out
 
 
-def motion_matrix(src_affine, drv_affine):
+def motion_matrix(src_affine, drv_affine, dtype=torch.float64):
     """PF:72-74: A_s . inverse(A_d) times the sign of its [0][0]."""
-    M = src_affine.double() @ torch.inverse(drv_affine.double())
+    M = src_affine.to(dtype) @ torch.inverse(drv_affine.to(dtype))
     return M * torch.sign(M[..., 0:1, 0:1])
 
 
-def sparse_motions(drv, src, bg, h, w):
+def sparse_motions(drv, src, bg, h, w, dtype=torch.float64):
     """PF:66-93: -> (T, R+1, h, w, 2) float64; drv = (shift (T,R,2), covar, affine (T,R,2,2)), src the same without T, bg (T,3,3)."""
-    g = coordinate_grid(h, w)
+    g = coordinate_grid(h, w, dtype)
     T = drv[0].shape[0]
-    M = motion_matrix(src[2].unsqueeze(0), drv[2])                                   # (T,R,2,2)
-    d = g.view(1, 1, h, w, 2) - drv[0].double().view(T, -1, 1, 1, 2)
-    k = torch.einsum("trab,trhwb->trhwa", M, d) + src[0].double().view(1, -1, 1, 1, 2)
-    gh = torch.cat((g, torch.ones(h, w, 1, dtype=torch.float64)), 2)
-    b = torch.einsum("tab,hwb->thwa", bg.double(), gh)
+    M = motion_matrix(src[2].unsqueeze(0), drv[2], dtype)                            # (T,R,2,2)
+    d = g.view(1, 1, h, w, 2) - drv[0].to(dtype).view(T, -1, 1, 1, 2)
+    k = torch.einsum("trab,trhwb->trhwa", M, d) + src[0].to(dtype).view(1, -1, 1, 1, 2)
+    gh = torch.cat((g, torch.ones(h, w, 1, dtype=dtype)), 2)
+    b = torch.einsum("tab,hwb->thwa", bg.to(dtype), gh)
     return torch.cat(((b[..., :2] / b[..., 2:3]).unsqueeze(1), k), 1)
 
 
-def gaussian(shift, covar, h, w):
+def gaussian(shift, covar, h, w, dtype=torch.float64):
     """UTIL:22-48 with a covariance: (..., R, 2), (..., R, 2, 2) -> (..., R, h, w)."""
-    d = coordinate_grid(h, w) - shift.double().unsqueeze(-2).unsqueeze(-2)
-    ci = torch.inverse(covar.double())
+    d = coordinate_grid(h, w, dtype) - shift.to(dtype).unsqueeze(-2).unsqueeze(-2)
+    ci = torch.inverse(covar.to(dtype))
     return torch.exp(-0.5 * torch.einsum("...hwa,...ab,...hwb->...hw", d, ci, d))
 
 
-def motion_inputs(drv, src, bg, src_down):
+def motion_inputs(drv, src, bg, src_down, dtype=torch.float64):
     """PF:104-120: src_down (3,h,w) -> the hourglass input (T, (R+1)*4, h, w) float64."""
     _, h, w = src_down.shape
     T = drv[0].shape[0]
-    heat = gaussian(drv[0], drv[1], h, w) - gaussian(src[0], src[1], h, w).unsqueeze(0)
-    heat = torch.cat((torch.zeros(T, 1, h, w, dtype=torch.float64), heat), 1)         # (T,R+1,h,w)
-    m = sparse_motions(drv, src, bg, h, w)
+    heat = gaussian(drv[0], drv[1], h, w, dtype) - gaussian(src[0], src[1], h, w, dtype).unsqueeze(0)
+    heat = torch.cat((torch.zeros(T, 1, h, w, dtype=dtype), heat), 1)                 # (T,R+1,h,w)
+    m = sparse_motions(drv, src, bg, h, w, dtype)
     K = m.shape[1]
-    warped = F.grid_sample(src_down.double().view(1, 3, h, w).expand(T * K, 3, h, w), m.reshape(T * K, h, w, 2), mode="bilinear",
+    warped = F.grid_sample(src_down.to(dtype).view(1, 3, h, w).expand(T * K, 3, h, w), m.reshape(T * K, h, w, 2), mode="bilinear",
                            padding_mode="zeros", align_corners=False).view(T, K, 3, h, w)
     return torch.cat((heat.unsqueeze(2), warped), 2).reshape(T, K * 4, h, w)
 
 
-def flow_combine(x, drv, src, bg):
+def flow_combine(x, drv, src, bg, dtype=torch.float64):
     """PF:124-135: x (T, R+2, h, w) = mask | occlusion conv outputs -> optical_flow (T,h,w,2), occlusion_map (T,1,h,w), float64."""
     T, _, h, w = x.shape
-    mask = torch.softmax(x[:, :-1].double(), dim=1)
-    m = sparse_motions(drv, src, bg, h, w)
-    return (m * mask.unsqueeze(-1)).sum(dim=1), torch.sigmoid(x[:, -1:].double())
+    mask = torch.softmax(x[:, :-1].to(dtype), dim=1)
+    m = sparse_motions(drv, src, bg, h, w, dtype)
+    return (m * mask.unsqueeze(-1)).sum(dim=1), torch.sigmoid(x[:, -1:].to(dtype))
 
 
 # ---------------------------------------------------------------------------------------------- layouts

@@ -3,6 +3,10 @@
 BGMotionPredictor and Generator (LFG/modules/) in the build container and running them as FlowDiffusion.forward does (FD:248-262).
 
     python tools/gen_goldens_motion.py      # writes tests/golden/motion_tiny_sd.npz, motion_A.npz, motion_B.npz (data only)
+    python tools/gen_goldens_motion.py N    # writes tests/golden/motion_N.npz alone (any names of motion_cases.CASES / E2E_CASES), from
+                                            # the same seeded models; no other file is touched
+
+The cases of motion_cases.E2E_CASES (N: 96 x 128, not square) hold the reference's optical_flow and occlusion_map only.
 
 Inputs are not stored: tests/motion_cases.frames_u8 makes them (bytes from an integer formula).  Weights: narrow instances of the shipped
 architecture (motion_cases.TINY / GEN_TINY), every parameter and BatchNorm statistic randomised -- the constructors zero `fc` -- and
@@ -73,7 +77,7 @@ def build():
 
 
 def run_case(name, rp, bg, gen):
-    c = mc.CASES[name]
+    c = mc.CASES[name] if name in mc.CASES else mc.E2E_CASES[name]
     T = c["T"]
     src_u8, drv_u8 = mc.frames_u8(name)
     src, drv = mc.to_float(src_u8).unsqueeze(0), mc.to_float(drv_u8)
@@ -111,6 +115,9 @@ def run_case(name, rp, bg, gen):
         drv_shift=dp["shift"], drv_covar=dp["covar"], drv_affine=dp["affine"], drv_u=dp["u"].view(T, mc.R, 2, 2),
         down_src=cap["down"][0][0],
         optical_flow=out["optical_flow"], occlusion_map=out["occlusion_map"], bg_params=bgp)
+    if name in mc.E2E_CASES:
+        assert tuple(out["optical_flow"].shape) == (T, h, w, 2) and h != w
+        a = dict(optical_flow=out["optical_flow"], occlusion_map=out["occlusion_map"])
     if name == "A":
         a.update(src_regions=cap["regions"][0][:1], down_drv=cap["down"][1], bg_last=cap["bg_last"], pf_in=cap["pf_in"][last], pf_in_frames=np.array(last),
                  mask_occ=torch.cat((cap["mask"], cap["occ"]), 1), prediction=out["prediction"][last], deformed=out["deformed"][last],
@@ -123,6 +130,10 @@ def run_case(name, rp, bg, gen):
 
 def main():
     rp, bg, gen = build()
+    if len(sys.argv) > 1:                                               # the named cases alone
+        for name in sys.argv[1:]:
+            run_case(name, rp, bg, gen)
+        return
     arrs = {}
     for tag, m in (("generator", gen), ("region_predictor", rp), ("bg_predictor", bg)):
         for k, v in m.state_dict().items():
