@@ -1144,7 +1144,8 @@ static int sampler_run_impl(dawn_ctx* c, int F, int h, int w, const void* clip_m
                             const float* x_init, int S, const dawn_ddim_step* steps, uint64_t seed, const float* const* noises, float* x_out,
                             float* thresholds, void* workspace, size_t workspace_bytes, const dawn_shard_comm* comm, void* stream,
                             const dawn_ancestral_step* asteps = nullptr, const dawn_clip_mode* clip = nullptr,
-                            const dawn_dpmpp_step* dsteps = nullptr) {
+                            const dawn_dpmpp_step* dsteps = nullptr, const float* known = nullptr, const unsigned char* kmask = nullptr,
+                            const float* kab = nullptr, const float* const* knoises = nullptr) {
     const bool guided = null_clip_mem && cond_scale != 1.0f;
     const int kind = clip ? clip->kind : (int)DAWN_CLIP_DYNAMIC;
     const double q = clip ? clip->q : 0.9;
@@ -1159,6 +1160,8 @@ static int sampler_run_impl(dawn_ctx* c, int F, int h, int w, const void* clip_m
         return dawn_set_error_msg(-202, "dawn_sampler_run: null argument");
     if (dsteps && S > 0 && dsteps[0].c != 0.0f)
         return dawn_set_error_msg(-215, "dawn_sampler_run_dpmpp: steps[0].c != 0, but the first step has no history");
+    if (known && (!kmask || !kab))
+        return dawn_set_error_msg(-216, "dawn_sampler_run_known: known needs known_mask and known_ab");
     if (shard_check(comm)) return -212;
     if (comm && dynamic && (!comm->allreduce_sum_u32 || !comm->allreduce_min_u32))
         return dawn_set_error_msg(-210, "dawn_sampler_run_sharded: dawn_shard_comm.allreduce_sum_u32 / allreduce_min_u32 is NULL");
@@ -1166,6 +1169,13 @@ static int sampler_run_impl(dawn_ctx* c, int F, int h, int w, const void* clip_m
     const long n = (long)3 * F * h * w;                       // this rank's elements
     const int Ftot = comm ? comm->world * F : F, f0g = comm ? comm->rank * F : 0;
     const long n_total = (long)3 * Ftot * h * w;              // the quantile is over the whole clip (MT:1186-1190)
+    // known-frame replacement at level `lvl` (include/dawn_hip.h): one launch, only when a known set was given
+#define KNOWN_AT(dst, lvl)                                                                                                        \
+    do {                                                                                                                          \
+        if (known)                                                                                                                \
+            CK(dawn_known_replace((dst), known, kmask, F, f0g, Ftot, h * w, kab[2 * (lvl)], kab[2 * (lvl) + 1],                       \
+                                  knoises ? knoises[(lvl)] : nullptr, seed, 0x80000000u + (uint32_t)(lvl), s));                  \
+    } while (0)
 #define SHARD_CB(call)                                                        \
     do {                                                                      \
         if (comm) { const int r__ = (call); if (r__ != 0) return r__ < 0 ? r__ : -211; } \
@@ -1187,6 +1197,7 @@ static int sampler_run_impl(dawn_ctx* c, int F, int h, int w, const void* clip_m
     ws += 256;
     const size_t fwd_bytes = workspace_bytes - (size_t)(ws - (char*)workspace);
     HCK(hipMemcpyAsync(x, x_init, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+    KNOWN_AT(x, 0);
     // quantile rank: torch.quantile's own fp32 arithmetic up to 2^24 elements, exact (fp64) above (ops.quantile_rank)
     unsigned long long lo;
     float weight;
@@ -1219,6 +1230,7 @@ static int sampler_run_impl(dawn_ctx* c, int F, int h, int w, const void* clip_m
             const int clamp = kind == DAWN_CLIP_STATIC;
             if (dsteps) {
                 CK(dawn_dpmpp_step_fixed(x, eps, v_prev, recip, recipm1, dsteps[i].a, dsteps[i].b, dsteps[i].c, clamp, n, noise, dst, s));
+                KNOWN_AT(dst, i + 1);
                 continue;
             }
             const float* nz = nullptr;
@@ -1228,6 +1240,7 @@ static int sampler_run_impl(dawn_ctx* c, int F, int h, int w, const void* clip_m
             }
             if (asteps) CK(dawn_ancestral_step_fixed(x, eps, nz, recip, recipm1, asteps[i].c1, asteps[i].c2, asteps[i].std, clamp, n, nullptr, dst, s));
             else CK(dawn_ddim_step_fixed(x, eps, nz, recip, recipm1, steps[i].sqrt_alpha_next, steps[i].c, steps[i].sigma, clamp, n, nullptr, dst, s));
+            KNOWN_AT(dst, i + 1);
             continue;
         }
         if (guided) {
@@ -1264,6 +1277,7 @@ static int sampler_run_impl(dawn_ctx* c, int F, int h, int w, const void* clip_m
         if (thresholds) HCK(hipMemcpyAsync(thresholds + 2 * i, sthr, 8, hipMemcpyDeviceToDevice, s));
         if (dsteps) {
             CK(dawn_dpmpp_update(x0, sthr, x, v_prev, dsteps[i].a, dsteps[i].b, dsteps[i].c, n, noise, (i + 1 == S) ? x_out : x, s));
+            KNOWN_AT((i + 1 == S) ? x_out : x, i + 1);
             continue;
         }
         const float* nz = nullptr;
@@ -1278,12 +1292,14 @@ static int sampler_run_impl(dawn_ctx* c, int F, int h, int w, const void* clip_m
             const dawn_ddim_step& st = steps[i];
             CK(dawn_ddim_update(x0, eps, sthr, nz, st.sqrt_alpha_next, st.c, st.sigma, n, (i + 1 == S) ? x_out : x, s));
         }
+        KNOWN_AT((i + 1 == S) ? x_out : x, i + 1);
     }
     if (S == 0) HCK(hipMemcpyAsync(x_out, x, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
     if (kind == DAWN_CLIP_STATIC && thresholds && S > 0)      // [1, 1] per step: 0x3f800000 is 1.0f
         HCK(hipMemsetD32Async((hipDeviceptr_t)thresholds, 0x3f800000, (size_t)2 * S, s));
     return 0;
 #undef SHARD_CB
+#undef KNOWN_AT
 }
 extern "C" int dawn_sampler_run_sharded(dawn_ctx* c, int F, int h, int w, const void* clip_mem, const float* x_init, int S,
                                         const dawn_ddim_step* steps, uint64_t seed, const float* const* noises, float* x_out,
@@ -1331,6 +1347,39 @@ extern "C" int dawn_sampler_run_dpmpp(dawn_ctx* c, int F, int h, int w, const vo
     if (!steps) return dawn_set_error_msg(-202, "dawn_sampler_run_dpmpp: null argument");
     return sampler_run_impl(c, F, h, w, clip_mem, null_clip_mem, cond_scale, x_init, S, nullptr, 0, nullptr, x_out, thresholds, workspace,
                             workspace_bytes, comm, stream, nullptr, clip, steps);
+}
+extern "C" int dawn_sampler_run_known(dawn_ctx* c, int F, int h, int w, const void* clip_mem, const void* null_clip_mem, float cond_scale,
+                                      const float* x_init, int S, int solver, const void* steps, uint64_t seed, const float* const* noises,
+                                      float* x_out, float* thresholds, void* workspace, size_t workspace_bytes, const dawn_shard_comm* comm,
+                                      const dawn_clip_mode* clip, const float* known, const unsigned char* known_mask, const float* known_ab,
+                                      const float* const* known_noises, void* stream) {
+    if (solver != DAWN_SOLVER_DDIM && solver != DAWN_SOLVER_ANCESTRAL && solver != DAWN_SOLVER_DPMPP)
+        return dawn_set_error_msg(-217, "dawn_sampler_run_known: unknown solver (DAWN_SOLVER_DDIM, DAWN_SOLVER_ANCESTRAL or DAWN_SOLVER_DPMPP)");
+    if (!steps) return dawn_set_error_msg(-202, "dawn_sampler_run_known: null argument");
+    const bool dp = solver == DAWN_SOLVER_DPMPP;
+    return sampler_run_impl(c, F, h, w, clip_mem, null_clip_mem, cond_scale, x_init, S,
+                            solver == DAWN_SOLVER_DDIM ? (const dawn_ddim_step*)steps : nullptr, seed, dp ? nullptr : noises, x_out,
+                            thresholds, workspace, workspace_bytes, comm, stream,
+                            solver == DAWN_SOLVER_ANCESTRAL ? (const dawn_ancestral_step*)steps : nullptr, clip,
+                            dp ? (const dawn_dpmpp_step*)steps : nullptr, known, known_mask, known_ab, known_noises);
+}
+// the plan of a chunked long clip (include/dawn_hip.h); pure host arithmetic
+extern "C" int dawn_chunk_plan(int T, int F, int K, int* starts, int* known, int max_chunks) {
+    if (T < 1 || F < 1 || K < 1 || K >= F)
+        return dawn_set_error_msg(-218, "dawn_chunk_plan: needs T >= 1 and 1 <= K < F");
+    int n = 0;
+    auto put = [&](int start, int kn) {
+        if (n < max_chunks) {
+            if (starts) starts[n] = start;
+            if (known) known[n] = kn;
+        }
+        ++n;
+    };
+    if (T <= F) { put(0, 0); return n; }
+    int last = 0;
+    for (long st = 0; st + F < T; st += F - K) { put((int)st, st == 0 ? 0 : K); last = (int)st; }
+    put(T - F, last + F - (T - F));
+    return n;
 }
 extern "C" int dawn_sampler_run(dawn_ctx* c, int F, int h, int w, const void* clip_mem, const float* x_init, int S,
                                 const dawn_ddim_step* steps, uint64_t seed, const float* const* noises, float* x_out,

@@ -150,6 +150,30 @@ __device__ __forceinline__ void philox_round(unsigned& c0, unsigned& c1, unsigne
     c0 = n0; c1 = n1; c2 = n2; c3 = n3;
 }
 
+// the four N(0,1) values of quad gq (= global element index / 4) of stream stream_id: Philox4x32-10 keyed by the seed, then Box-Muller.
+// ONE definition for every kernel that draws (philox_normal_kernel, known_replace_kernel): their bits agree by construction.
+__device__ __forceinline__ f32x4 philox_normal4(unsigned long long gq, unsigned long long seed, unsigned stream_id) {
+    unsigned c0 = (unsigned)gq, c1 = (unsigned)(gq >> 32), c2 = stream_id, c3 = 0x44415757u;
+    unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        philox_round(c0, c1, c2, c3, k0, k1);
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    const float u0 = ((float)c0 + 0.5f) * 2.3283064365386963e-10f;
+    const float u1 = ((float)c1 + 0.5f) * 2.3283064365386963e-10f;
+    const float u2 = ((float)c2 + 0.5f) * 2.3283064365386963e-10f;
+    const float u3 = ((float)c3 + 0.5f) * 2.3283064365386963e-10f;
+    const float r0 = sqrtf(-2.0f * logf(fminf(fmaxf(u0, 1e-10f), 1.0f)));
+    const float r1 = sqrtf(-2.0f * logf(fminf(fmaxf(u2, 1e-10f), 1.0f)));
+    float s0, c0f, s1, c1f;
+    sincosf(6.283185307179586f * u1, &s0, &c0f);
+    sincosf(6.283185307179586f * u3, &s1, &c1f);
+    f32x4 v = {r0 * c0f, r0 * s0, r1 * c1f, r1 * s1};
+    return v;
+}
+
 // out (C, F, hw) local shard of a (C, Ftotal, hw) tensor; frames [f0, f0+F).  One Philox call per 4
 // consecutive elements of the GLOBAL tensor => values do not depend on how T is sharded.
 __global__ __launch_bounds__(256) void philox_normal_kernel(float* __restrict__ out, int C, int F, int f0, int Ftotal,
@@ -161,25 +185,75 @@ __global__ __launch_bounds__(256) void philox_normal_kernel(float* __restrict__ 
         const long cf = t / qpf;
         const int f = (int)(cf % F), c = (int)(cf / F);
         const unsigned long long gq = ((unsigned long long)c * Ftotal + (f0 + f)) * qpf + qd;
-        unsigned c0 = (unsigned)gq, c1 = (unsigned)(gq >> 32), c2 = stream_id, c3 = 0x44415757u;
-        unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
+        *reinterpret_cast<f32x4*>(out + ((long)c * F + f) * hw + qd * 4) = philox_normal4(gq, seed, stream_id);
+    }
+}
+
+// ---- known-frame replacement (include/dawn_hip.h has the definition): x[:, f] = (a * known[:, f]) + (b * z[:, f]) for the frames with
+// mask[f] != 0, two products and one sum, each rounded on its own (contraction off: a fused a*k + b*z would differ from the definition
+// in the last bit); MODE 0 (b == 0): x = a * known, no noise read or drawn.  Grid (blocks per plane, frames, 3 channels): a block reads
+// its frame's mask byte ONCE -- a uniform branch -- and leaves when it is zero, so a frame outside the known set costs no traffic.
+// MODE 1, injected noise, any hw and any 4-byte alignment: when the plane's x / known / noise pointers are congruent modulo 16 bytes
+// the block peels up to three scalar elements, runs a 128-bit body and a scalar tail; otherwise the whole plane goes scalar.
+// MODE 2, the generator (hw % 4 == 0): one philox_normal4 per quad of the plane, keyed by the GLOBAL quad index exactly as
+// philox_normal_kernel keys it, so the values are those dawn_philox_normal(seed, stream_id) writes at these elements, whatever the
+// shard; 128-bit accesses when x and known are 16-byte aligned, four scalar ones otherwise.
+__device__ __forceinline__ float known_one(float a, float k, float b, float z, bool has_z) {
+#pragma clang fp contract(off)
+    const float ak = a * k;
+    if (!has_z) return ak;
+    const float bz = b * z;
+    return ak + bz;
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void known_replace_kernel(float* x, const float* __restrict__ known,
+                                                            const unsigned char* __restrict__ mask, int F, int f0, int Ftotal, int hw,
+                                                            float a, float b, const float* __restrict__ noise,
+                                                            unsigned long long seed, unsigned stream_id) {
+    const int c = blockIdx.z;
+    const int start = blockIdx.x * 256 + threadIdx.x, stride = gridDim.x * 256;
+    for (int f = blockIdx.y; f < F; f += gridDim.y) {
+        if (mask[f] == 0) continue;                                     // uniform over the block
+        const long plane = ((long)c * F + f) * hw;
+        float* xp = x + plane;
+        const float* kp = known + plane;
+        if (MODE == 2) {
+            const int qpf = hw >> 2;
+            const bool vec = (((uintptr_t)xp | (uintptr_t)kp) & 15) == 0;
+            const unsigned long long gq0 = ((unsigned long long)c * Ftotal + (f0 + f)) * qpf;
+            for (int qd = start; qd < qpf; qd += stride) {
+                const f32x4 z = philox_normal4(gq0 + qd, seed, stream_id);
+                f32x4 kv, r;
+                if (vec) kv = reinterpret_cast<const f32x4*>(kp)[qd];
+                else { kv[0] = kp[4 * qd]; kv[1] = kp[4 * qd + 1]; kv[2] = kp[4 * qd + 2]; kv[3] = kp[4 * qd + 3]; }
 #pragma unroll
-        for (int r = 0; r < 10; ++r) {
-            philox_round(c0, c1, c2, c3, k0, k1);
-            k0 += 0x9E3779B9u;
-            k1 += 0xBB67AE85u;
+                for (int k = 0; k < 4; ++k) r[k] = known_one(a, kv[k], b, z[k], true);
+                if (vec) reinterpret_cast<f32x4*>(xp)[qd] = r;
+                else { xp[4 * qd] = r[0]; xp[4 * qd + 1] = r[1]; xp[4 * qd + 2] = r[2]; xp[4 * qd + 3] = r[3]; }
+            }
+            continue;
         }
-        const float u0 = ((float)c0 + 0.5f) * 2.3283064365386963e-10f;
-        const float u1 = ((float)c1 + 0.5f) * 2.3283064365386963e-10f;
-        const float u2 = ((float)c2 + 0.5f) * 2.3283064365386963e-10f;
-        const float u3 = ((float)c3 + 0.5f) * 2.3283064365386963e-10f;
-        const float r0 = sqrtf(-2.0f * logf(fminf(fmaxf(u0, 1e-10f), 1.0f)));
-        const float r1 = sqrtf(-2.0f * logf(fminf(fmaxf(u2, 1e-10f), 1.0f)));
-        float s0, c0f, s1, c1f;
-        sincosf(6.283185307179586f * u1, &s0, &c0f);
-        sincosf(6.283185307179586f * u3, &s1, &c1f);
-        f32x4 v = {r0 * c0f, r0 * s0, r1 * c1f, r1 * s1};
-        *reinterpret_cast<f32x4*>(out + ((long)c * F + f) * hw + qd * 4) = v;
+        const float* np = MODE == 1 ? noise + plane : nullptr;
+        const unsigned ax = (unsigned)((uintptr_t)xp >> 2) & 3u;
+        const bool cong = ((unsigned)((uintptr_t)kp >> 2) & 3u) == ax && (MODE != 1 || ((unsigned)((uintptr_t)np >> 2) & 3u) == ax);
+        int head = cong ? (int)((4u - ax) & 3u) : hw;                   // scalar elements before the 128-bit body
+        if (head > hw) head = hw;
+        const int n4 = (hw - head) >> 2;
+        for (int i = start; i < n4; i += stride) {
+            const f32x4 kv = reinterpret_cast<const f32x4*>(kp + head)[i];
+            f32x4 zv = {0.f, 0.f, 0.f, 0.f};
+            if (MODE == 1) zv = reinterpret_cast<const f32x4*>(np + head)[i];
+            f32x4 r;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) r[k] = known_one(a, kv[k], b, zv[k], MODE == 1);
+            reinterpret_cast<f32x4*>(xp + head)[i] = r;
+        }
+        const int ns = hw - 4 * n4;                                     // scalar elements: [0, head) and [head + 4 n4, hw)
+        for (int j = start; j < ns; j += stride) {
+            const int i = j < head ? j : j + 4 * n4;
+            xp[i] = known_one(a, kp[i], b, MODE == 1 ? np[i] : 0.f, MODE == 1);
+        }
     }
 }
 
@@ -487,6 +561,33 @@ extern "C" int dawn_philox_normal(float* out, int C, int F, int f0, int Ftotal, 
     if (hw % 4 != 0) return dawn_set_error_msg(-72, "dawn_philox_normal: h*w must be a multiple of 4");
     hipLaunchKernelGGL(philox_normal_kernel, dim3(grid_for((long)C * F * (hw / 4))), dim3(256), 0, (hipStream_t)stream,
                        out, C, F, f0, Ftotal, hw, (unsigned long long)seed, stream_id);
+    DAWN_LAUNCH_CHECK();
+    return 0;
+}
+/* the definition stands in include/dawn_hip.h */
+extern "C" int dawn_known_replace(float* x, const float* known, const unsigned char* mask, int F, int f0, int Ftotal, int hw, float a,
+                                  float b, const float* noise, uint64_t seed, uint32_t stream_id, void* stream) {
+    if (!x || !known || !mask) return dawn_set_error_msg(-86, "dawn_known_replace: null argument (x, known and mask are required)");
+    if (F < 0 || f0 < 0 || hw < 0 || (long)f0 + F > (long)Ftotal)
+        return dawn_set_error_msg(-87, "dawn_known_replace: frames out of range (F >= 0, f0 >= 0, hw >= 0 and f0 + F <= Ftotal)");
+    const long n = (long)3 * F * hw;
+    if (ranges_overlap(x, known, n) || ranges_overlap(x, noise, n))
+        return dawn_set_error_msg(-88, "dawn_known_replace: x must not overlap known or noise");
+    const int mode = b == 0.0f ? 0 : noise ? 1 : 2;                  // b == 0: no noise is read or drawn
+    if (mode == 2 && hw % 4 != 0) return dawn_set_error_msg(-72, "dawn_known_replace: h*w must be a multiple of 4 when the generator draws the noise");
+    if (F == 0 || hw == 0) return 0;
+    int bx = ((hw + 3) / 4 + 255) / 256;
+    if (bx > 64) bx = 64;
+    const dim3 grid(bx, F < 65535 ? F : 65535, 3);
+    if (mode == 0)
+        hipLaunchKernelGGL(known_replace_kernel<0>, grid, dim3(256), 0, (hipStream_t)stream, x, known, mask, F, f0, Ftotal, hw, a, b,
+                           (const float*)nullptr, (unsigned long long)seed, stream_id);
+    else if (mode == 1)
+        hipLaunchKernelGGL(known_replace_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, x, known, mask, F, f0, Ftotal, hw, a, b, noise,
+                           (unsigned long long)seed, stream_id);
+    else
+        hipLaunchKernelGGL(known_replace_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream, x, known, mask, F, f0, Ftotal, hw, a, b,
+                           (const float*)nullptr, (unsigned long long)seed, stream_id);
     DAWN_LAUNCH_CHECK();
     return 0;
 }

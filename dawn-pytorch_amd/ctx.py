@@ -53,6 +53,7 @@ class ClipMode(C.Structure):
 
 
 CLIP_KINDS = {"dynamic": 0, "static": 1, "none": 2}      # DAWN_CLIP_DYNAMIC / _STATIC / _NONE
+SOLVER_DDIM, SOLVER_ANCESTRAL, SOLVER_DPMPP = 0, 1, 2    # DAWN_SOLVER_DDIM / _ANCESTRAL / _DPMPP
 
 
 def _clip_struct(clip, ancestral: bool) -> ClipMode:
@@ -328,8 +329,11 @@ class CtxEvaluator(_Evaluator):
 
     def sample(self, clip: dict, x_init: Tensor, steps: Sequence[dict], seed: int = 0,
                noises: Optional[List[Optional[Tensor]]] = None, want_thresholds: bool = False,
-               shard: Optional[ShardCallbacks] = None, null_clip: Optional[dict] = None, cond_scale: float = 1.0, x0_clip=None):
+               shard: Optional[ShardCallbacks] = None, null_clip: Optional[dict] = None, cond_scale: float = 1.0, x0_clip=None,
+               known=None, known_entry: bool = False):
         """cond_scale != 1 (with null_clip = prepare_null_clip(...)): guided sampling, dawn_sampler_run_guided.
+        known (sampler.KnownFrames): known-frame conditioning through dawn_sampler_run_known (every form: guided, sharded, any clipping
+        mode); known_entry=True takes that entry without a known set too (bit-identical to the entries below).
         x0_clip (sampler.clip_mode; None: dynamic thresholding at 0.9 through the entries above): any x0 clipping mode through
         dawn_sampler_run_clip, single / guided / sharded alike.  Thresholds: static [1, 1] per step, none: rows left as allocated."""
         F, h, w = clip["F"], clip["h"], clip["w"]
@@ -346,6 +350,9 @@ class CtxEvaluator(_Evaluator):
                 if t is not None and not (t.is_cuda and t.is_contiguous() and t.numel() == 3 * F * h * w and t.dtype == torch.float32):
                     raise _lib.DawnHipError(f"sample: noises[{i}] must be a contiguous fp32 GPU tensor of {3 * F * h * w} elements")
                 nz[i] = None if t is None else t.data_ptr()
+        if known is not None or known_entry:
+            return self._sample_known(SOLVER_DDIM, "sample", clip, x_init, arr, S, seed, nz, want_thresholds, shard, null_clip, cond_scale,
+                                      x0_clip, known)
         x_init = x_init.contiguous().float()
         out = torch.empty_like(x_init)
         thr = torch.empty(S, 2, device=self.device) if want_thresholds else None
@@ -397,14 +404,68 @@ class CtxEvaluator(_Evaluator):
                                       self._stream()), "dawn_sampler_run")
         return (out, thr) if want_thresholds else out
 
+    def _sample_known(self, solver: int, who: str, clip: dict, x_init: Tensor, arr, S: int, seed: int, nz, want_thresholds: bool,
+                      shard: Optional[ShardCallbacks], null_clip: Optional[dict], cond_scale: float, x0_clip, known):
+        """dawn_sampler_run_known: the loop of `solver` over the step array `arr`, with the known set (sampler.KnownFrames, or None)."""
+        F, h, w = clip["F"], clip["h"], clip["w"]
+        n = 3 * F * h * w
+        guided = cond_scale != 1.0
+        if guided and null_clip is None:
+            raise _lib.DawnHipError(f"{who}: cond_scale != 1 needs null_clip (prepare_null_clip)")
+        lat = msk = ab = kz = None
+        keep = []
+        if known is not None:
+            lat, msk = known.latent, known.mask
+            if not (lat.is_cuda and lat.is_contiguous() and lat.dtype == torch.float32 and lat.numel() == n):
+                raise _lib.DawnHipError(f"{who}: known.latent must be a contiguous fp32 GPU tensor of {n} elements")
+            if not (msk.is_cuda and msk.is_contiguous() and msk.dtype == torch.uint8 and msk.numel() == F):
+                raise _lib.DawnHipError(f"{who}: known.mask must be {F} uint8 values on the GPU")
+            if len(known.levels) != S + 1:
+                raise _lib.DawnHipError(f"{who}: known.levels must hold {S + 1} (a, b) pairs")
+            ab = (C.c_float * (2 * (S + 1)))(*[float(v) for lv in known.levels for v in lv])
+            if known.noise_fn is not None:
+                kz = (C.c_void_p * (S + 1))()
+                for i, (_, b) in enumerate(known.levels):
+                    z = known.noise_fn(i) if b != 0.0 else None
+                    if z is not None and not (z.is_cuda and z.is_contiguous() and z.dtype == torch.float32 and z.numel() == n):
+                        raise _lib.DawnHipError(f"{who}: known noise {i} must be a contiguous fp32 GPU tensor of {n} elements")
+                    if z is None and b != 0.0:
+                        raise _lib.DawnHipError(f"{who}: known noise {i} missing for a level with b != 0")
+                    keep.append(z)
+                    kz[i] = None if z is None else z.data_ptr()
+            else:                                # the entry has ONE seed: step noise on streams i + 1, known-frame noise on 0x80000000 + i
+                if nz is None and solver != SOLVER_DPMPP and int(seed) != int(known.seed):
+                    raise _lib.DawnHipError(f"{who}: known.seed must equal the step-noise seed (the C entry takes one seed for both)")
+                seed = known.seed
+        x_init = x_init.contiguous().float()
+        out = torch.empty_like(x_init)
+        thr = torch.empty(S, 2, device=self.device) if want_thresholds else None
+        mode = None if x0_clip is None else _clip_struct(x0_clip, solver == SOLVER_ANCESTRAL)
+        ws = self.workspace(F, h, w, shard, guided=guided)
+        comm = None
+        if shard is not None:
+            shard.ws = ws
+            comm = C.addressof(shard.c)
+        rc = self.L.dawn_sampler_run_known(self.h, F, h, w, clip["mem"].data_ptr(), null_clip["mem"].data_ptr() if guided else None,
+                                           float(cond_scale), x_init.data_ptr(), S, solver, arr, int(seed), nz, out.data_ptr(),
+                                           None if thr is None else thr.data_ptr(), ws.data_ptr(), ws.numel(), comm,
+                                           None if mode is None else C.addressof(mode), None if lat is None else lat.data_ptr(),
+                                           None if msk is None else msk.data_ptr(), ab, kz, self._stream())
+        if shard is not None:
+            self._shard_call(shard, rc, "dawn_sampler_run_known")
+        else:
+            check(rc, "dawn_sampler_run_known")
+        del keep
+        return (out, thr) if want_thresholds else out
+
     def sample_ancestral(self, clip: dict, x_init: Tensor, steps: Sequence[dict], seed: int = 0,
                          noises: Optional[List[Optional[Tensor]]] = None, want_thresholds: bool = False,
                          shard: Optional[ShardCallbacks] = None, null_clip: Optional[dict] = None, cond_scale: float = 1.0,
-                         x0_clip=None):
+                         x0_clip=None, known=None, known_entry: bool = False):
         """dawn_sampler_run_ancestral: the ancestral loop (sampler.ancestral_step_scalars), guided when cond_scale != 1 (null_clip =
         prepare_null_clip(...)), one T-shard rank when `shard` is given.  noises[i] is read only for steps with t > 0.
         x0_clip (sampler.clip_mode; None: dynamic thresholding at 0.9 through that entry): ("dynamic", q) or ("static",) through
-        dawn_sampler_run_ancestral_clip."""
+        dawn_sampler_run_ancestral_clip.  known / known_entry: as for sample()."""
         F, h, w = clip["F"], clip["h"], clip["w"]
         S = len(steps)
         arr = (AncestralStep * max(S, 1))()
@@ -421,6 +482,9 @@ class CtxEvaluator(_Evaluator):
                 if t is None and steps[i]["t"] > 0:
                     raise _lib.DawnHipError(f"sample_ancestral: noises[{i}] missing for a step with t > 0")
                 nz[i] = None if t is None else t.data_ptr()
+        if known is not None or known_entry:
+            return self._sample_known(SOLVER_ANCESTRAL, "sample_ancestral", clip, x_init, arr, S, seed, nz, want_thresholds, shard, null_clip,
+                                      cond_scale, x0_clip, known)
         guided = cond_scale != 1.0
         if guided and null_clip is None:
             raise _lib.DawnHipError("sample_ancestral: cond_scale != 1 needs null_clip (prepare_null_clip)")
@@ -447,8 +511,9 @@ class CtxEvaluator(_Evaluator):
         return (out, thr) if want_thresholds else out
 
     def sample_dpmpp(self, clip: dict, x_init: Tensor, steps: Sequence[dict], want_thresholds: bool = False,
-                     shard: Optional[ShardCallbacks] = None, null_clip: Optional[dict] = None, cond_scale: float = 1.0, x0_clip=None):
-        """dawn_sampler_run_dpmpp: the DPM-Solver++(2M) loop (sampler.dpmpp_step_scalars), guided when cond_scale != 1 (null_clip =
+                     shard: Optional[ShardCallbacks] = None, null_clip: Optional[dict] = None, cond_scale: float = 1.0, x0_clip=None,
+                     known=None, known_entry: bool = False):
+        """known / known_entry: as for sample() (the known-frame noise is the only noise this loop draws).  dawn_sampler_run_dpmpp: the DPM-Solver++(2M) loop (sampler.dpmpp_step_scalars), guided when cond_scale != 1 (null_clip =
         prepare_null_clip(...)), one T-shard rank when `shard` is given.  Deterministic: no seed, no noises.  x0_clip (sampler.clip_mode;
         None: dynamic thresholding at 0.9): any clipping mode.  Thresholds: static [1, 1] per step, none: rows left as allocated."""
         F, h, w = clip["F"], clip["h"], clip["w"]
@@ -457,6 +522,9 @@ class CtxEvaluator(_Evaluator):
         for i, st in enumerate(steps):
             arr[i].t, arr[i].recip, arr[i].recipm1 = int(st["t"]), st["recip"], st["recipm1"]
             arr[i].a, arr[i].b, arr[i].c = st["a"], st["b"], st["c"]
+        if known is not None or known_entry:
+            return self._sample_known(SOLVER_DPMPP, "sample_dpmpp", clip, x_init, arr, S, 0, None, want_thresholds, shard, null_clip, cond_scale,
+                                      x0_clip, known)
         guided = cond_scale != 1.0
         if guided and null_clip is None:
             raise _lib.DawnHipError("sample_dpmpp: cond_scale != 1 needs null_clip (prepare_null_clip)")

@@ -17,8 +17,9 @@ from typing import List, Optional, Sequence
 import torch
 from torch import nn
 
-from .sampler import (CLIP_DEFAULT, ancestral_sample_clip, ancestral_step_scalars, clip_mode, cosine_schedule_buffers, ddim_sample_clip,
-                      ddim_step_scalars, dpmpp_sample_clip, dpmpp_step_scalars)
+from .sampler import (CLIP_DEFAULT, KnownFrames, ancestral_sample_clip, ancestral_step_scalars, chunk_plan, clip_mode,
+                      cosine_schedule_buffers, ddim_sample_clip, ddim_step_scalars, dpmpp_sample_clip, dpmpp_step_scalars,
+                      known_level_scalars)
 
 Tensor = torch.Tensor
 
@@ -102,32 +103,65 @@ class GaussianDiffusion(nn.Module):
     # ------------------------------------------------------------------ reference call surface
     @torch.inference_mode()
     def sample(self, fea, bbox_mask, cond=None, cond_scale=1., batch_size=16, *, x_init: Optional[Tensor] = None,
-               noises: Optional[Sequence[Tensor]] = None, trace: bool = False, comm=None):
+               noises: Optional[Sequence[Tensor]] = None, trace: bool = False, comm=None, known_latent: Optional[Tensor] = None,
+               known_mask: Optional[Tensor] = None, known_noises: Optional[Sequence[Optional[Tensor]]] = None):
         """fea (B,256,h,w), bbox_mask (B,16,h,w), cond (B,T,1032) -> (B,3,T,h,w)   (MT:1137-1153).
 
         Extra keyword-only hooks (not in the reference): `x_init` / `noises` inject the random draws of
         MT:1166 / MT:1201 for parity tests; `comm` = T-shard communicator (cond then holds this rank's
-        frames only)."""
+        frames only).
+        Known-frame conditioning (not in the reference; defined in include/dawn_hip.h, quality on a trained checkpoint unmeasured):
+        `known_latent` (B,3,T,h,w) with `known_mask` (T,) or (B,T), nonzero = known, pins those frames -- the latent entering every
+        step holds them at that step's noise level and the result holds them bit for bit; the other frames are generated to fit.
+        `known_noises` (hook): S + 1 tensors (B,3,T,h,w), the noise of every level (the last, b = 0, may be None); default: the
+        counter-based generator.  With `comm` both hold this rank's frames."""
         batch_size = cond.shape[0] if cond is not None else batch_size
         fea = torch.cat([fea, bbox_mask], dim=1)                                     # MT:1151
         shape = (batch_size, self.channels, self.num_frames, fea.shape[-1], fea.shape[-1])
         sample_fn = self.ddim_sample if self.is_ddim_sampling else self.p_sample_loop  # MT:1150
-        return sample_fn(fea, shape, cond=cond, cond_scale=cond_scale, x_init=x_init, noises=noises, trace=trace, comm=comm)
+        return sample_fn(fea, shape, cond=cond, cond_scale=cond_scale, x_init=x_init, noises=noises, trace=trace, comm=comm,
+                         known_latent=known_latent, known_mask=known_mask, known_noises=known_noises)
 
     @torch.inference_mode()
-    def p_sample_loop(self, fea, shape, cond=None, cond_scale=1., *, x_init=None, noises=None, trace=False, comm=None):
+    def p_sample_loop(self, fea, shape, cond=None, cond_scale=1., *, x_init=None, noises=None, trace=False, comm=None,
+                      known_latent=None, known_mask=None, known_noises=None):
         """The ancestral loop (MT:1124-1135): `num_timesteps` evaluations at t = num_timesteps-1 ... 0, whatever
         sampling_timesteps is.  noises[i] (hook) is read only for steps with t > 0, so num_timesteps - 1 entries suffice."""
-        return self._sample_loop("ancestral", fea, shape, cond, cond_scale, x_init, noises, trace, comm, self.clip)
+        return self._sample_loop("ancestral", fea, shape, cond, cond_scale, x_init, noises, trace, comm, self.clip,
+                                 (known_latent, known_mask, known_noises))
 
     @torch.no_grad()
     def ddim_sample(self, fea, shape, cond=None, cond_scale=1., clip_denoised=True, *, x_init=None, noises=None,
-                    trace=False, comm=None):
+                    trace=False, comm=None, known_latent=None, known_mask=None, known_noises=None):
         """clip_denoised=False (MT:1183): x0 is used as predicted, neither thresholded nor clamped."""
         return self._sample_loop("ddim", fea, shape, cond, cond_scale, x_init, noises, trace, comm,
-                                 self.clip if clip_denoised else ("none", None))
+                                 self.clip if clip_denoised else ("none", None), (known_latent, known_mask, known_noises))
 
-    def _sample_loop(self, kind, fea, shape, cond, cond_scale, x_init, noises, trace, comm, clip):
+    def _known_frames(self, known, b, steps, kind, shape, device, seed):
+        """sampler.KnownFrames of batch element b from the known_latent / known_mask / known_noises keywords, or None."""
+        latent, mask, kz = known
+        if latent is None:
+            if mask is not None or kz is not None:
+                raise ValueError("known_mask / known_noises need known_latent")
+            return None
+        if mask is None:
+            raise ValueError("known_latent needs known_mask")
+        B, C, T, h, w = shape
+        if tuple(latent.shape) != (B, 3, T, h, w):
+            raise ValueError(f"known_latent must be (B, 3, T, h, w) = {(B, 3, T, h, w)}, got {tuple(latent.shape)}")
+        if mask.dim() == 1:
+            mask = mask[None].expand(B, -1)
+        if tuple(mask.shape) != (B, T):
+            raise ValueError(f"known_mask must be (T,) or (B, T) with T = {T}, got {tuple(mask.shape)}")
+        levels = known_level_scalars({k: getattr(self, k) for k in ("alphas_cumprod", "alphas_cumprod_prev")}, steps,
+                                     "dpmpp" if self.solver == "dpmpp2m" else kind, self.num_timesteps)
+        if kz is not None and len(kz) < len(levels) - 1:
+            raise ValueError(f"known_noises: {len(levels)} entries needed (one per level; the last may be None), got {len(kz)}")
+        noise_fn = None if kz is None else (lambda i: kz[i][b].contiguous().float().to(device))
+        return KnownFrames((latent[b].contiguous().float().to(device)), (mask[b] != 0).to(torch.uint8).contiguous().to(device), levels,
+                           noise_fn, seed)
+
+    def _sample_loop(self, kind, fea, shape, cond, cond_scale, x_init, noises, trace, comm, clip, known=(None, None, None)):
         """One host loop for every sampler (kind "ddim" / "ancestral"; solver "dpmpp2m" turns "ddim" into the DPM-Solver++(2M) steps
         on the same time pairs): the C-side evaluator when use_ctx, else the Python orchestration; they share the evaluation and
         differ in the step scalars and the step tail.  clip = (kind, q) of sampler.clip_mode."""
@@ -187,12 +221,15 @@ class GaussianDiffusion(nn.Module):
                     # generator -- S x 3 x T x h x w floats of pre-drawn noise would be GBs for the long clips the path supports
                     run_seed = int(torch.randint(0, 2 ** 62, (1,)).item())
                 x0_clip = None if clip == CLIP_DEFAULT else clip
+                if known[0] is not None and run_seed is None and known[2] is None:
+                    run_seed = int(torch.randint(0, 2 ** 62, (1,)).item())            # (unseeded: ONE draw seeds the known-frame noise)
+                kf = self._known_frames(known, b, steps, kind, shape, device, run_seed or 0)
                 if dpmpp:
-                    outs.append(ev.sample_dpmpp(clip_mem, x0, steps, null_clip=null_clip, cond_scale=cond_scale, x0_clip=x0_clip))
+                    outs.append(ev.sample_dpmpp(clip_mem, x0, steps, null_clip=null_clip, cond_scale=cond_scale, x0_clip=x0_clip, known=kf))
                     continue
                 run = ev.sample_ancestral if ancestral else ev.sample
                 outs.append(run(clip_mem, x0, steps, seed=run_seed or 0, noises=nz, null_clip=null_clip, cond_scale=cond_scale,
-                                x0_clip=x0_clip))
+                                x0_clip=x0_clip, known=kf))
             self.last_trace = None
             self.last_route = "ctx"
             return torch.stack(outs, 0)
@@ -219,17 +256,68 @@ class GaussianDiffusion(nn.Module):
             else:
                 x0 = torch.randn(3, T, h, w, device=device)                           # MT:1166
             tr = [] if trace else None
+            kseed = seed + b if seed is not None else None
+            if known[0] is not None and kseed is None and known[2] is None:
+                kseed = int(torch.randint(0, 2 ** 62, (1,)).item())                   # (unseeded: ONE draw seeds the known-frame noise)
+            kf = self._known_frames(known, b, steps, kind, shape, device, kseed or 0)
             if dpmpp:
                 outs.append(dpmpp_sample_clip(ops, P, cs, x0, steps, cond_scale, cs_null, tr, use_graph=self.use_graph,
-                                              eager_every=self.eager_every, clip=clip))
+                                              eager_every=self.eager_every, clip=clip, known=kf))
             else:
                 outs.append((ancestral_sample_clip if ancestral else ddim_sample_clip)(
                     ops, P, cs, x0, steps, noise_fn, cond_scale, cs_null, tr, use_graph=self.use_graph, eager_every=self.eager_every,
-                    clip=clip))
+                    clip=clip, known=kf))
             traces.append(tr)
         self.last_trace = traces if trace else None
         self.last_route = "python"
         return torch.stack(outs, 0)
+
+    # ------------------------------------------------------------------ chunked generation of a long clip (not in the reference)
+    def iter_chunks(self, fea, bbox_mask, cond, cond_scale=1., *, chunk_frames: int, overlap: int, comm=None):
+        """Sample a clip of T = cond.shape[1] frames as the chunks of sampler.chunk_plan(T, chunk_frames, overlap), yielding
+        (first_frame, latent (B,3,n,h,w)) as each chunk finishes -- the frames it emits, in order, so a host can decode and show them
+        while the next chunk samples.  Chunk j runs `sample` on the cond rows of its frames with the previous chunk's overlapping
+        frames as its known set (known_latent / known_mask over its first known_j frames) and the seed noise_seed + (j << 32)
+        (unseeded: the global generator, as always).  The cond rows are those of the whole clip, computed once by the caller, so
+        init_pose / init_eye stay anchored to frame 0.  Every chunk has one shape (one workspace, one clip_mem size, one graph).
+        An overlapping frame is bit-identical in both chunks that hold it.  Whether a seam shows or the motion drifts on a trained
+        checkpoint, and which overlap is enough, has not been measured.  T-shard (comm) cannot be combined with chunking."""
+        if comm is not None:
+            raise ValueError("chunked sampling cannot be combined with a T-shard (comm): shard the whole clip, or chunk it on one GPU")
+        if cond is None:
+            raise ValueError("chunked sampling needs cond (B, T, cond_dim): its length is the clip's")
+        plan = chunk_plan(int(cond.shape[1]), int(chunk_frames), int(overlap))      # (refusals raise here, not at the first next())
+        return self._chunks(plan, fea, bbox_mask, cond, cond_scale)
+
+    def _chunks(self, plan, fea, bbox_mask, cond, cond_scale):
+        prev, prev_start = None, 0
+        for j, (start, n, kn) in enumerate(plan):
+            kl = km = None
+            if kn:
+                kl = torch.zeros_like(prev)
+                kl[:, :, :kn] = prev[:, :, start - prev_start:start - prev_start + kn]
+                km = torch.zeros(n, dtype=torch.uint8, device=prev.device)
+                km[:kn] = 1
+            saved = (self.num_frames, getattr(self.denoise_fn, "num_frames", None), self.noise_seed)
+            try:
+                self.num_frames = n
+                if saved[1] is not None:
+                    self.denoise_fn.num_frames = n
+                if saved[2] is not None:
+                    self.noise_seed = saved[2] + (j << 32)
+                out = self.sample(fea, bbox_mask, cond=cond[:, start:start + n].contiguous(), cond_scale=cond_scale, known_latent=kl,
+                                  known_mask=km)
+            finally:
+                self.num_frames, self.noise_seed = saved[0], saved[2]
+                if saved[1] is not None:
+                    self.denoise_fn.num_frames = saved[1]
+            prev, prev_start = out, start
+            yield start + kn, out[:, :, kn:]
+
+    def sample_chunked(self, fea, bbox_mask, cond, cond_scale=1., *, chunk_frames: int, overlap: int, comm=None):
+        """The whole clip (B,3,T,h,w) from iter_chunks: the emitted frames concatenated."""
+        return torch.cat([lat for _, lat in self.iter_chunks(fea, bbox_mask, cond, cond_scale, chunk_frames=chunk_frames, overlap=overlap,
+                                                              comm=comm)], dim=2)
 
     def forward(self, *a, **k):
         raise NotImplementedError("training (p_losses, MT:1234-1281) is out of scope of the HIP inference build")

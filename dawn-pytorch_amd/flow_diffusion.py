@@ -96,6 +96,10 @@ class FlowDiffusion(nn.Module):
         self.inputs_via_c = False       # True: bbox_mask and cond of a GPU clip with B == 1 from dawn_clip_inputs (ctx.InputsEvaluator)
         self._inputs_ev = None
         self.motion_via_c = False       # True: encode_video / reenact encode a GPU clip with B == 1 through dawn_motion_encode_clip (ctx.MotionEvaluator)
+        # chunked sampling of a long clip (not in the reference; GaussianDiffusion.sample_chunked): plain attributes like diffusion.solver.
+        # chunk_frames = None: the clip is sampled whole, as always
+        self.chunk_frames: Optional[int] = None
+        self.chunk_overlap = 0
 
     def update_num_frames(self, new_num_frames):
         """FD:177-180."""
@@ -243,7 +247,10 @@ class FlowDiffusion(nn.Module):
         fea = self.generator.compute_fea(sample_img)                                   # (B,256,h,w)  GEN:132-136
         bbox_mask, cond = self.clip_inputs(sample_img, sample_audio_hubert, sample_pose, sample_eye, sample_bbox, init_pose, init_eye)
         t0 = time.time()
-        pred = self.diffusion.sample(fea, bbox_mask, cond=cond, batch_size=fea.size(0), cond_scale=cond_scale)
+        if self.chunk_frames is not None:     # cond rows of the whole clip (init_pose / init_eye anchored to frame 0), sampled chunk by chunk
+            pred = self.diffusion.sample_chunked(fea, bbox_mask, cond, cond_scale, chunk_frames=self.chunk_frames, overlap=self.chunk_overlap)
+        else:
+            pred = self.diffusion.sample(fea, bbox_mask, cond=cond, batch_size=fea.size(0), cond_scale=cond_scale)
         out["sample_vid_grid"] = pred[:, :2]
         out["sample_vid_conf"] = (pred[:, 2].unsqueeze(1) + 1) * 0.5
         out["ddim_seconds"] = time.time() - t0

@@ -752,6 +752,30 @@ class HipOps:
               "dawn_philox_normal")
         return out
 
+    def known_replace(self, x: Tensor, known: Tensor, mask: Tensor, a: float, b: float, noise: Optional[Tensor] = None, seed: int = 0,
+                      stream_id: int = 0, f0: int = 0, Ftotal: Optional[int] = None, out: Optional[Tensor] = None) -> Tensor:
+        """Known-frame replacement (dawn_known_replace; the definition is in include/dawn_hip.h): the frames f of x (3, F, h, w) with
+        mask[f] != 0 become a*known + b*z, z = `noise` or, when it is None and b != 0, the counter-based generator at (seed, stream_id)
+        keyed by the global element index (this rank holds frames [f0, f0 + F) of Ftotal).  In place by default; out= receives a copy of
+        x first and is replaced instead.  mask: F bytes on the device."""
+        _need(x.dim() >= 2 and x.shape[0] == 3 and x.is_contiguous() and x.dtype == torch.float32, "known_replace: contiguous fp32 x (3, F, ...)")
+        F = x.shape[1]
+        hw = x.numel() // (3 * F) if F else 0
+        _need(known.dtype == torch.float32 and known.is_contiguous() and known.numel() == x.numel(), "known_replace: contiguous fp32 known of x's size")
+        _need(mask.dtype == torch.uint8 and mask.is_contiguous() and mask.numel() == F and mask.device == x.device,
+              "known_replace: mask must be F uint8 values on x's device")
+        _need(noise is None or (noise.dtype == torch.float32 and noise.is_contiguous() and noise.numel() == x.numel()),
+              "known_replace: contiguous fp32 noise of x's size")
+        self._require(x, known, mask, noise, out)
+        if out is not None:
+            _need(out.is_contiguous() and out.dtype == torch.float32 and out.shape == x.shape, "known_replace: out contiguous fp32 of x's shape")
+            if out.data_ptr() != x.data_ptr():
+                out.copy_(x)
+            x = out
+        check(self.L.dawn_known_replace(_p(x), _p(known), _p(mask), F, int(f0), F if Ftotal is None else int(Ftotal), hw, float(a), float(b),
+                                        _p(noise), int(seed), int(stream_id), self._stream()), "dawn_known_replace")
+        return x
+
     # ------------------------------------------------------------------ LFG flow decode (SURVEY 8f N1)
     def affine_act(self, x: Tensor, a: Tensor, b: Tensor, act: int = 1) -> Tensor:
         """out = act(x*a[c] + b[c]) on (rows, C); act 1 = ReLU (eval-mode BatchNorm + ReLU, UTIL:83-88)."""

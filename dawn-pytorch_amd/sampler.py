@@ -8,7 +8,8 @@ No host synchronisation inside the step loop."""
 from __future__ import annotations
 
 import math
-from typing import Callable, Dict, List, Optional, Sequence
+from dataclasses import dataclass
+from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import torch
 import torch.nn.functional as F_
@@ -115,6 +116,58 @@ def dpmpp_step_scalars(bufs: Dict[str, Tensor], S: int, total: int = 1000, order
     return out
 
 
+KNOWN_STREAM0 = 0x80000000             # generator stream of the known-frame noise of level i: KNOWN_STREAM0 + i (include/dawn_hip.h)
+
+
+def known_level_scalars(bufs: Dict[str, Tensor], steps: Sequence[dict], kind: str = "ddim", timesteps: int = 1000) -> List[Tuple[float, float]]:
+    """The S + 1 noise levels (a_i, b_i) of known-frame conditioning (the definition is in include/dawn_hip.h; not in the reference):
+    level i is where the latent entering step i lies, level S where the result does.  abar from the fp32 table, fp64 after that, a =
+    sqrt(abar) and b = sqrt(1 - abar) rounded to fp32 once.  kind "ddim" / "dpmpp": abar_0 = alphas_cumprod_prev[steps[0].t], after step
+    i alphas_cumprod_prev[t_next] (the table and index of MT:1170-1171); "ancestral": abar_0 = alphas_cumprod[timesteps - 1], after the
+    step at t alphas_cumprod_prev[t].  The last step lands on alphas_cumprod_prev[0] = 1: (1.0, 0.0)."""
+    if kind not in ("ddim", "ancestral", "dpmpp"):
+        raise ValueError(f"unknown sampler step kind {kind!r}")
+    prev = bufs["alphas_cumprod_prev"].detach().float().cpu()
+    f32 = lambda v: float(torch.tensor(v, dtype=torch.float64).float())          # noqa: E731
+    level = lambda ab: (f32(math.sqrt(ab)), f32(math.sqrt(1.0 - ab)))            # noqa: E731
+    if not steps:
+        return [(1.0, 0.0)]
+    if kind == "ancestral":
+        first = float(bufs["alphas_cumprod"].detach().float().cpu()[timesteps - 1])
+        return [level(first)] + [level(float(prev[st["t"]])) for st in steps]
+    return [level(float(prev[steps[0]["t"]]))] + [level(float(prev[st["t_next"]])) for st in steps]
+
+
+def chunk_plan(T: int, F: int, K: int) -> List[Tuple[int, int, int]]:
+    """The chunks (start, frames, known) of a T-frame clip sampled F frames at a time with the first K frames of every later chunk pinned
+    to what is already generated (dawn_chunk_plan is the same function; include/dawn_hip.h).  T <= F: one chunk (0, T, 0).  Otherwise
+    chunks of exactly F frames start at 0, F - K, 2 (F - K), ... while start + F < T, and the last starts at T - F with however many of
+    its frames are already generated (K ... F - 1) known.  Chunk j emits the frames [start + known, start + frames)."""
+    if T < 1 or F < 1 or not 1 <= K < F:
+        raise ValueError(f"chunk_plan: needs T >= 1 and 1 <= K < F, got T={T}, F={F}, K={K}")
+    if T <= F:
+        return [(0, T, 0)]
+    plan, st = [], 0
+    while st + F < T:
+        plan.append((st, F, K if st else 0))
+        st += F - K
+    last = plan[-1][0]
+    plan.append((T - F, F, last + F - (T - F)))
+    return plan
+
+
+@dataclass
+class KnownFrames:
+    """The known set of one clip for ddim_sample_clip(known=...): `latent` (3, F, h, w) and `mask` (F,) uint8 on the ops' device (this
+    rank's frames), `levels` = known_level_scalars(...) (S + 1 pairs), `noise_fn(i)` -> the injected z_i (3, F, h, w) of a level with
+    b_i != 0, or None: the counter-based generator at (seed, KNOWN_STREAM0 + i)."""
+    latent: Tensor
+    mask: Tensor
+    levels: Sequence[Tuple[float, float]]
+    noise_fn: Optional[Callable[[int], Optional[Tensor]]] = None
+    seed: int = 0
+
+
 CLIP_DEFAULT = ("dynamic", 0.9)        # the shipped pipeline's setting (FD:164)
 
 
@@ -147,25 +200,26 @@ def clip_mode(clip, ancestral: bool = False):
 def ancestral_sample_clip(ops, P: PackedUNet, cs: ClipState, x_init: Tensor, steps: Sequence[dict],
                           noise_fn: Callable[[int], Optional[Tensor]], cond_scale: float = 1.0,
                           cs_null: Optional[ClipState] = None, trace: Optional[list] = None, use_graph: bool = False,
-                          eager_every: int = 0, clip=CLIP_DEFAULT) -> Tensor:
+                          eager_every: int = 0, clip=CLIP_DEFAULT, known: Optional[KnownFrames] = None) -> Tensor:
     """The ancestral loop (steps = ancestral_step_scalars(...)): the evaluation, x0 and quantile of ddim_sample_clip, then
     ops.ancestral_update; noise_fn(i) is only called when t > 0 (MT:1120).  clip: ("dynamic", q) or ("static",), see clip_mode."""
     return ddim_sample_clip(ops, P, cs, x_init, steps, noise_fn, cond_scale, cs_null, trace, use_graph, eager_every, kind="ancestral",
-                            clip=clip)
+                            clip=clip, known=known)
 
 
 def dpmpp_sample_clip(ops, P: PackedUNet, cs: ClipState, x_init: Tensor, steps: Sequence[dict], cond_scale: float = 1.0,
                       cs_null: Optional[ClipState] = None, trace: Optional[list] = None, use_graph: bool = False,
-                      eager_every: int = 0, clip=CLIP_DEFAULT) -> Tensor:
+                      eager_every: int = 0, clip=CLIP_DEFAULT, known: Optional[KnownFrames] = None) -> Tensor:
     """The DPM-Solver++(2M) loop (steps = dpmpp_step_scalars(...)): the evaluation, x0 and quantile of ddim_sample_clip, then
     ops.dpmpp_update / ops.dpmpp_step_fixed.  Deterministic: no noise is drawn."""
-    return ddim_sample_clip(ops, P, cs, x_init, steps, None, cond_scale, cs_null, trace, use_graph, eager_every, kind="dpmpp", clip=clip)
+    return ddim_sample_clip(ops, P, cs, x_init, steps, None, cond_scale, cs_null, trace, use_graph, eager_every, kind="dpmpp", clip=clip,
+                            known=known)
 
 
 def ddim_sample_clip(ops, P: PackedUNet, cs: ClipState, x_init: Tensor, steps: Sequence[dict],
                      noise_fn: Callable[[int], Optional[Tensor]], cond_scale: float = 1.0,
                      cs_null: Optional[ClipState] = None, trace: Optional[list] = None, use_graph: bool = False,
-                     eager_every: int = 0, kind: str = "ddim", clip=CLIP_DEFAULT) -> Tensor:
+                     eager_every: int = 0, kind: str = "ddim", clip=CLIP_DEFAULT, known: Optional[KnownFrames] = None) -> Tensor:
     """x_init (3, F, h, w) on the ops' device -> final latent (3, F, h, w).
 
     noise_fn(i) returns the N(0,1) tensor of step i (only called when t_next > 0, MT:1201).
@@ -178,7 +232,10 @@ def ddim_sample_clip(ops, P: PackedUNet, cs: ClipState, x_init: Tensor, steps: S
     constant [1, 1] tensor; none: None).
     kind = "dpmpp": the step tail of DPM-Solver++(2M) (dpmpp_sample_clip; noise_fn is never called).  ONE history tensor holds the
     clipped x0 of the previous step; the tail updates it in place and is handed it only when the step's c != 0 (it is uninitialised
-    before the first step).  Trace entries carry `x0c`, a copy of it, next to eps, s and x."""
+    before the first step).  Trace entries carry `x0c`, a copy of it, next to eps, s and x.
+    known (KnownFrames; not in the reference, defined in include/dawn_hip.h): the frames of its mask are set to the known latent at level
+    0 on a copy of x_init and at level i + 1 after the tail of step i (ops.known_replace, in place: a trace entry's x is the latent that
+    enters the next step); nothing else changes, and without it nothing more is launched."""
     if kind not in ("ddim", "ancestral", "dpmpp"):
         raise ValueError(f"unknown sampler step kind {kind!r}")
     ancestral, dpmpp = kind == "ancestral", kind == "dpmpp"
@@ -188,6 +245,17 @@ def ddim_sample_clip(ops, P: PackedUNet, cs: ClipState, x_init: Tensor, steps: S
     hist_v = None                                # dpmpp: the clipped x0 of the previous step
     s_one = None
     x = x_init.contiguous()
+    if known is not None:
+        if len(known.levels) != len(steps) + 1:
+            raise ValueError(f"known: {len(steps) + 1} levels needed (one per step and one for the result), got {len(known.levels)}")
+        f0 = cs.f0 if cs.comm is not None else 0
+
+        def replace(x, i, out=None):
+            a, b = known.levels[i]
+            z = known.noise_fn(i) if b != 0.0 and known.noise_fn is not None else None
+            return ops.known_replace(x, known.latent, known.mask, a, b, noise=z, seed=known.seed, stream_id=KNOWN_STREAM0 + i, f0=f0,
+                                     Ftotal=cs.Ttotal, out=out)
+        x = replace(x, 0, out=torch.empty_like(x))               # (x_init stays the caller's)
     n_total = 3 * cs.Ttotal * cs.h * cs.w
     graphed = None
     guided = cond_scale != 1.0
@@ -226,6 +294,8 @@ def ddim_sample_clip(ops, P: PackedUNet, cs: ClipState, x_init: Tensor, steps: S
             else:
                 noise = noise_fn(i) if st["t_next"] > 0 else None
                 x = ops.ddim_step_fixed(x, eps, noise, st["recip"], st["recipm1"], st["sqrt_alpha_next"], st["c"], st["sigma"], clamp)
+            if known is not None:
+                x = replace(x, i + 1)
             if trace is not None:
                 if clamp and s_one is None:
                     s_one = torch.ones(2, device=x.device, dtype=torch.float32)
@@ -249,6 +319,8 @@ def ddim_sample_clip(ops, P: PackedUNet, cs: ClipState, x_init: Tensor, steps: S
         else:
             noise = noise_fn(i) if st["t_next"] > 0 else None
             x = ops.ddim_update(x0, eps, s, noise, st["sqrt_alpha_next"], st["c"], st["sigma"])
+        if known is not None:
+            x = replace(x, i + 1)
         if trace is not None:
             # a graphed evaluation returns its static output buffer: clone, or every entry would alias the last step
             trace.append(dict(eps=eps.clone() if graphed is not None and not guided else eps, s=s, x=x))

@@ -436,6 +436,36 @@ int dawn_cfg_x0(const float* e_null, const float* e_cond, float scale, const flo
 /* counter-based N(0,1): Philox4x32-10 keyed by seed, counter = (stream_id, global element index / 4) */
 int dawn_philox_normal(float* out, int C, int F, int f0, int Ftotal, int hw, uint64_t seed, uint32_t stream_id,
                        void* stream);
+/* ---- known-frame conditioning: the "replacement method" of video diffusion.  NOT in the reference: its values are THIS definition.
+ * Quality on a trained checkpoint -- whether a continued clip drifts, whether a seam shows, which overlap is enough -- has not been
+ * measured by anyone; nothing here claims it.
+ *   Given a known latent `known` (3, F, h, w), a per-frame mask (frame f is known when mask[f] != 0) and a noise level (a_i, b_i) for
+ *   i = 0 ... S, the latent that ENTERS step i of a sampler loop has its known frames set to the known latent at level i, and the latent
+ *   the loop RETURNS has them at level S:
+ *       x[:, f] = fadd(fmul(a_i, known[:, f]), fmul(b_i, z_i[:, f]))          for the known frames f
+ *   each operation a separate fp32 rounding, no contraction.  Frames with mask[f] == 0 are neither read nor written by the replacement.
+ *   Levels (host arithmetic, sampler.known_level_scalars): abar is read from the fp32 table, everything after it is fp64, a = sqrt(abar)
+ *   and b = sqrt(1 - abar) are rounded to fp32 once.
+ *       after a DDIM or DPM-Solver++ step      abar = alphas_cumprod_prev[t_next]   (the table and index the loop itself uses, MT:1170-1171)
+ *       after an ancestral step                abar = alphas_cumprod_prev[t]
+ *       level 0, DDIM and DPM-Solver++         abar = alphas_cumprod_prev[steps[0].t]
+ *       level 0, ancestral                     abar = alphas_cumprod[timesteps - 1]
+ *   The last step of every loop lands on alphas_cumprod_prev[0] = 1: a_S = 1, b_S = 0.  When b == 0 no noise is read or drawn and
+ *   x = fmul(a, known), so the known frames of the result ARE the known latent, bit for bit -- chunks stitched over an overlap agree
+ *   exactly there.
+ *   Noise z_i: an injected tensor (the test hook, like `noises`) or the counter-based generator: exactly what
+ *   dawn_philox_normal(seed, stream_id = 0x80000000 + i) writes at those elements (keyed by the GLOBAL element index: shard-invariant).
+ *   These stream ids are disjoint from the step streams i + 1, the initial latent's stream 0 and PBnet's 0xFFFFFFFE / 0xFFFFFFFF.
+ *   Unchanged by the replacement: x0, the dynamic-threshold quantile (over the whole clip, known frames included), the step tails, the
+ *   DPM-Solver++ history (it holds x0 predictions) and the thresholds output.
+ * dawn_known_replace: ONE launch on a (3, F, hw) latent, this rank's frames [f0, f0 + F) of a clip of Ftotal frames (f0 and Ftotal only
+ * key the generator).  mask: F bytes of DEVICE memory.  The grid is laid out per frame: a block reads its frame's mask byte once and
+ * leaves if it is zero.  noise != NULL: injected, (3, F, hw), any hw and any 4-byte alignment (128-bit accesses where the three
+ * pointers allow, scalar elsewhere).  noise == NULL and b != 0: drawn inline for the known frames only; hw % 4 != 0 is then an error, as
+ * in dawn_philox_normal.  b == 0: `noise` is not read, nothing is drawn.  Refused with a message, nothing launched: x, known or mask
+ * NULL; x overlapping known or noise; F < 0, f0 < 0 or f0 + F > Ftotal.  F == 0 succeeds and launches nothing. */
+int dawn_known_replace(float* x, const float* known, const unsigned char* mask, int F, int f0, int Ftotal, int hw, float a, float b,
+                       const float* noise, uint64_t seed, uint32_t stream_id, void* stream);
 
 /* ---- LFG flow decode, batched over the frames of a clip -----------------------------------------
  * (GEN = LFG/modules/generator.py:62-90, 138-171; blocks UTIL = LFG/modules/util.py:70-150; loop FD:372-385).
@@ -733,6 +763,34 @@ typedef struct dawn_dpmpp_step { int t; float recip, recipm1; float a, b, c; } d
 int dawn_sampler_run_dpmpp(dawn_ctx* ctx, int F, int h, int w, const void* clip_mem, const void* null_clip_mem, float cond_scale,
                            const float* x_init, int S, const dawn_dpmpp_step* steps, float* x_out, float* thresholds, void* workspace,
                            size_t workspace_bytes, const dawn_shard_comm* comm, const dawn_clip_mode* clip, void* stream);
+/* ---- known-frame conditioning on the whole path (the definition stands with dawn_known_replace above).  ONE entry for every loop:
+ * `solver` names the kind of `steps` (DAWN_SOLVER_DDIM: dawn_ddim_step[S], DAWN_SOLVER_ANCESTRAL: dawn_ancestral_step[S],
+ * DAWN_SOLVER_DPMPP: dawn_dpmpp_step[S]; for DPMPP `noises` is not read and `seed` keys the known-frame noise only).  Guided when null_clip_mem != NULL and cond_scale != 1,
+ * T-sharded when comm != NULL, clip = NULL means {DAWN_CLIP_DYNAMIC, 0.9}; every other argument as in the entry of that solver.
+ *   known        (3, F, h, w) device, this rank's frames of the known latent (frames outside the mask are never read)
+ *   known_mask   F bytes, device
+ *   known_ab     host, 2 (S + 1) floats: a_0, b_0, ..., a_S, b_S (sampler.known_level_scalars)
+ *   known_noises optional, host array of S + 1 device pointers: z_i (3, F, h, w) of every level with b_i != 0 (the others may be NULL);
+ *                NULL: the counter-based generator (seed, stream 0x80000000 + i), keyed by the global element index
+ * The replacement runs on the copy of x_init (level 0) and after every step tail (level i + 1), one dawn_known_replace launch each.
+ * known == NULL: the result is bit-identical to the existing entry of that solver (known_mask / known_ab / known_noises are not read).
+ * known != NULL with known_mask or known_ab NULL, or an unknown solver: error return with a message, nothing launched.  The known latent
+ * is the caller's buffer, so the existing workspace queries cover this entry too. */
+enum { DAWN_SOLVER_DDIM = 0, DAWN_SOLVER_ANCESTRAL = 1, DAWN_SOLVER_DPMPP = 2 };
+int dawn_sampler_run_known(dawn_ctx* ctx, int F, int h, int w, const void* clip_mem, const void* null_clip_mem, float cond_scale,
+                           const float* x_init, int S, int solver, const void* steps, uint64_t seed, const float* const* noises,
+                           float* x_out, float* thresholds, void* workspace, size_t workspace_bytes, const dawn_shard_comm* comm,
+                           const dawn_clip_mode* clip, const float* known, const unsigned char* known_mask, const float* known_ab,
+                           const float* const* known_noises, void* stream);
+/* ---- chunked generation of a long clip: the plan (pure host arithmetic, no GPU; sampler.chunk_plan is the same function).  A clip of T
+ * frames is sampled as chunks of F frames of which the first K (the overlap, 1 <= K < F) are already generated and pinned as the known
+ * set.  T <= F: one chunk (0, T frames, known 0).  T > F: chunks of exactly F frames start at 0, F - K, 2 (F - K), ... while
+ * start + F < T; the last chunk starts at T - F and its known count is however many of its frames are already generated (between K
+ * and F - 1).  Every chunk has ONE shape: one workspace, one clip_mem size, one captured graph.  Chunk j emits the frames
+ * [starts[j] + known[j], starts[j] + F).  Returns the number of chunks and writes the first min(n, max_chunks) entries of starts /
+ * known (either may be NULL); a precondition that fails (T < 1, F < 1, K < 1 or K >= F) returns a negative code with a message.  A C host
+ * loops over the plan with dawn_clip_prepare + dawn_sampler_run_known itself (INTEGRATION.md has the loop). */
+int dawn_chunk_plan(int T, int F, int K, int* starts, int* known, int max_chunks);
 /* ---- SURVEY 8(f) N1 + N2 as a whole path: the LFG flow decode of a sampled clip, down to uint8 frames (csrc/dawn_decoder.hip).
  * The same launch sequence as dawn-pytorch_amd/flow_decoder.py (FlowDecoder.encode / _decode_frames / decode_clip), results bit-identical
  * to it (tests/test_hip_decode_u8.py).  Same contract as dawn_ctx: opaque handle, device pointers by name, caller-owned memory, every
