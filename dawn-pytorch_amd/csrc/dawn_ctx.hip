@@ -1056,6 +1056,8 @@ extern "C" int dawn_clip_prepare(dawn_ctx* c, int F, int h, int w, const float* 
     return 0;
 }
 
+// sampler state on top of one evaluation, as sampler_run_impl carves it: x, eps, x0, noise (`lat` bytes each) + histograms / scalars
+static size_t sampler_state_bytes(size_t lat) { return 4 * lat + al256(2048 * 4) + 2 * al256(1024 * 4) + 4 * 256; }
 static size_t workspace_bytes_impl(dawn_ctx* c, int F, int h, int w, const dawn_shard_comm* shard, bool guided = false) {
     if (!c || F <= 0 || h <= 0 || w <= 0) return 0;
     // sized for BOTH schedules (two-stream: frees inside a side-stream region are deferred to the join; one-stream: immediate --
@@ -1076,11 +1078,8 @@ static size_t workspace_bytes_impl(dawn_ctx* c, int F, int h, int w, const dawn_
     }
     c->overlap = overlap_saved;
     c->arena.reset(nullptr, 0, false);
-    // sampler state on top of one evaluation: x, eps, x0, noise (3*F*h*w floats each) + histograms / scalars
-    const size_t lat = al256((size_t)3 * F * h * w * 4);
-    const size_t samp = 4 * lat + al256(2048 * 4) + 2 * al256(1024 * 4) + 4 * 256;
     const size_t prep = clip_scratch_bytes(c, F, h, w);
-    size_t need = fwd + samp;
+    size_t need = fwd + sampler_state_bytes(al256((size_t)3 * F * h * w * 4));
     return need > prep ? need : prep;
 }
 extern "C" size_t dawn_workspace_bytes(dawn_ctx* c, int F, int h, int w) { return workspace_bytes_impl(c, F, h, w, nullptr); }
@@ -1136,31 +1135,90 @@ extern "C" int dawn_unet_forward(dawn_ctx* c, int F, int h, int w, const void* c
 }
 
 // null_clip_mem != NULL and cond_scale != 1: every evaluation guided (Eval::forward_guided, whose last launch is dawn_cfg_x0).
-// Loop kind: DDIM steps (`steps`) or ancestral steps (`asteps`, exactly one of the two non-NULL); they differ in the step tail only.
-// `dsteps` instead: DPM-Solver++(2M) steps (dawn_sampler_run_dpmpp) -- deterministic, so the `noise` latent carries the history v_prev.
-// clip = NULL: dynamic thresholding at 0.9, what the entries without a mode have always run.  DAWN_CLIP_STATIC / DAWN_CLIP_NONE: the
-// evaluation (guided: ending in dawn_cfg_combine, the eps dawn_cfg_x0 forms) and ONE fused tail launch, no selection, no all-reduce.
+// What the nine entries differ in: the solver (the three loops differ in the step scalars and the step tail only), its step array, the
+// clipping mode and the known-frame set.
+struct SamplerRun {
+    int solver;                                // DAWN_SOLVER_*: `steps` is an array of dawn_ddim_step / dawn_ancestral_step / dawn_dpmpp_step
+    const void* steps;
+    // NULL: dynamic thresholding at 0.9, what the entries without a mode have always run.  DAWN_CLIP_STATIC / DAWN_CLIP_NONE: the evaluation
+    // (guided: ending in dawn_cfg_combine, the eps dawn_cfg_x0 forms) and ONE fused tail launch, no selection, no all-reduce.
+    const dawn_clip_mode* clip = nullptr;
+    const float* known = nullptr;              // the known set of dawn_sampler_run_known, or all NULL
+    const unsigned char* kmask = nullptr;
+    const float* kab = nullptr;
+    const float* const* knoises = nullptr;
+};
+// Step i of any solver, read once per iteration.
+struct StepView {
+    int t;
+    float recip, recipm1;
+    bool draws_noise;                          // DDIM: t_next > 0 (MT:1201); ancestral: t > 0 (MT:1120); DPM-Solver++(2M): never
+    float k0, k1, k2;                          // DDIM: sqrt_alpha_next, c, sigma; ancestral: c1, c2, std; DPM-Solver++(2M): a, b, c
+};
+static StepView step_view(const SamplerRun& run, int i) {
+    if (run.solver == DAWN_SOLVER_DPMPP) {
+        const dawn_dpmpp_step& st = ((const dawn_dpmpp_step*)run.steps)[i];
+        return {st.t, st.recip, st.recipm1, false, st.a, st.b, st.c};
+    }
+    if (run.solver == DAWN_SOLVER_ANCESTRAL) {
+        const dawn_ancestral_step& st = ((const dawn_ancestral_step*)run.steps)[i];
+        return {st.t, st.recip, st.recipm1, st.t > 0, st.c1, st.c2, st.std};
+    }
+    const dawn_ddim_step& st = ((const dawn_ddim_step*)run.steps)[i];
+    return {st.t, st.recip, st.recipm1, st.t_next > 0, st.sqrt_alpha_next, st.c, st.sigma};
+}
+// The selection scratch of dynamic thresholding, inside the sampler state (sampler_state_bytes).
+struct SelectScratch {
+    unsigned *hist1, *hist2, *hist3, *state, *hmin;
+    float* sthr;
+};
+// s = max(1, quantile_q(|x0|)) over the whole clip -> sel.sthr (and `thr_out`): the three passes after the first histogram (`hist1`, filled
+// by the launch that formed x0) and the minimum, each all-reduced over the T-shard ranks.
+static int select_threshold(const SelectScratch& sel, const float* x0, long n, unsigned long long lo, float weight, float* thr_out,
+                            const dawn_shard_comm* comm, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+#define SHARD_CB(call)                                                        \
+    do {                                                                      \
+        if (comm) { const int r__ = (call); if (r__ != 0) return r__ < 0 ? r__ : -211; } \
+    } while (0)
+    SHARD_CB(comm->allreduce_sum_u32(comm->user, sel.hist1, 2048, stream));
+    HCK(hipMemsetAsync(sel.state, 0, 16, s));
+    CK(dawn_select_scan(sel.hist1, 2048, lo, sel.state, 1, s));
+    HCK(hipMemsetAsync(sel.hist2, 0, 1024 * 4, s));
+    CK(dawn_select_hist(x0, n, sel.state, 2, sel.hist2, s));
+    SHARD_CB(comm->allreduce_sum_u32(comm->user, sel.hist2, 1024, stream));
+    CK(dawn_select_scan(sel.hist2, 1024, 0, sel.state, 2, s));
+    HCK(hipMemsetAsync(sel.hist3, 0, 1024 * 4, s));
+    CK(dawn_select_hist(x0, n, sel.state, 3, sel.hist3, s));
+    SHARD_CB(comm->allreduce_sum_u32(comm->user, sel.hist3, 1024, stream));
+    CK(dawn_select_scan(sel.hist3, 1024, 0, sel.state, 3, s));
+    HCK(hipMemsetD32Async((hipDeviceptr_t)sel.hmin, 0x7fffffff, 4, s));
+    CK(dawn_select_hist(x0, n, sel.state, 4, sel.hmin, s));
+    SHARD_CB(comm->allreduce_min_u32(comm->user, sel.hmin, 1, stream));
+    CK(dawn_select_finalize(sel.state, sel.hmin, weight, sel.sthr, s));
+    if (thr_out) HCK(hipMemcpyAsync(thr_out, sel.sthr, 8, hipMemcpyDeviceToDevice, s));
+    return 0;
+#undef SHARD_CB
+}
+// null_clip_mem != NULL and cond_scale != 1: every evaluation guided (Eval::forward_guided, whose last launch is dawn_cfg_x0).
 static int sampler_run_impl(dawn_ctx* c, int F, int h, int w, const void* clip_mem, const void* null_clip_mem, float cond_scale,
-                            const float* x_init, int S, const dawn_ddim_step* steps, uint64_t seed, const float* const* noises, float* x_out,
-                            float* thresholds, void* workspace, size_t workspace_bytes, const dawn_shard_comm* comm, void* stream,
-                            const dawn_ancestral_step* asteps = nullptr, const dawn_clip_mode* clip = nullptr,
-                            const dawn_dpmpp_step* dsteps = nullptr, const float* known = nullptr, const unsigned char* kmask = nullptr,
-                            const float* kab = nullptr, const float* const* knoises = nullptr) {
+                            const float* x_init, int S, const SamplerRun& run, uint64_t seed, const float* const* noises, float* x_out,
+                            float* thresholds, void* workspace, size_t workspace_bytes, const dawn_shard_comm* comm, void* stream) {
     const bool guided = null_clip_mem && cond_scale != 1.0f;
-    const int kind = clip ? clip->kind : (int)DAWN_CLIP_DYNAMIC;
-    const double q = clip ? clip->q : 0.9;
+    const int kind = run.clip ? run.clip->kind : (int)DAWN_CLIP_DYNAMIC;
+    const double q = run.clip ? run.clip->q : 0.9;
     if (kind != DAWN_CLIP_DYNAMIC && kind != DAWN_CLIP_STATIC && kind != DAWN_CLIP_NONE)
         return dawn_set_error_msg(-214, "dawn_clip_mode: unknown kind (DAWN_CLIP_DYNAMIC, DAWN_CLIP_STATIC or DAWN_CLIP_NONE)");
     if (kind == DAWN_CLIP_DYNAMIC && !(q >= 0.0 && q <= 1.0))
         return dawn_set_error_msg(-214, "dawn_clip_mode: q must lie in [0, 1]");
-    if (kind == DAWN_CLIP_NONE && asteps)
+    if (kind == DAWN_CLIP_NONE && run.solver == DAWN_SOLVER_ANCESTRAL)
         return dawn_set_error_msg(-214, "dawn_clip_mode: DAWN_CLIP_NONE does not exist for ancestral steps (p_sample always clips, MT:1113)");
     const bool dynamic = kind == DAWN_CLIP_DYNAMIC;
-    if (!c || !clip_mem || !x_init || !(steps || asteps || dsteps) || !x_out || !workspace)
+    if (!c || !clip_mem || !x_init || !run.steps || !x_out || !workspace)
         return dawn_set_error_msg(-202, "dawn_sampler_run: null argument");
-    if (dsteps && S > 0 && dsteps[0].c != 0.0f)
+    if (run.solver == DAWN_SOLVER_DPMPP && S > 0 && ((const dawn_dpmpp_step*)run.steps)[0].c != 0.0f)
         return dawn_set_error_msg(-215, "dawn_sampler_run_dpmpp: steps[0].c != 0, but the first step has no history");
-    if (known && (!kmask || !kab))
+    if (run.known && (!run.kmask || !run.kab))
         return dawn_set_error_msg(-216, "dawn_sampler_run_known: known needs known_mask and known_ab");
     if (shard_check(comm)) return -212;
     if (comm && dynamic && (!comm->allreduce_sum_u32 || !comm->allreduce_min_u32))
@@ -1172,28 +1230,25 @@ static int sampler_run_impl(dawn_ctx* c, int F, int h, int w, const void* clip_m
     // known-frame replacement at level `lvl` (include/dawn_hip.h): one launch, only when a known set was given
 #define KNOWN_AT(dst, lvl)                                                                                                        \
     do {                                                                                                                          \
-        if (known)                                                                                                                \
-            CK(dawn_known_replace((dst), known, kmask, F, f0g, Ftot, h * w, kab[2 * (lvl)], kab[2 * (lvl) + 1],                       \
-                                  knoises ? knoises[(lvl)] : nullptr, seed, 0x80000000u + (uint32_t)(lvl), s));                  \
-    } while (0)
-#define SHARD_CB(call)                                                        \
-    do {                                                                      \
-        if (comm) { const int r__ = (call); if (r__ != 0) return r__ < 0 ? r__ : -211; } \
+        if (run.known)                                                                                                            \
+            CK(dawn_known_replace((dst), run.known, run.kmask, F, f0g, Ftot, h * w, run.kab[2 * (lvl)], run.kab[2 * (lvl) + 1],       \
+                                  run.knoises ? run.knoises[(lvl)] : nullptr, seed, 0x80000000u + (uint32_t)(lvl), s));          \
     } while (0)
     const size_t lat = al256((size_t)n * 4);
     char* ws = (char*)workspace;
-    const size_t samp = 4 * lat + al256(2048 * 4) + 2 * al256(1024 * 4) + 4 * 256;
-    if (workspace_bytes < samp) return dawn_set_error_msg(-201, "dawn_sampler_run: workspace too small");
+    if (workspace_bytes < sampler_state_bytes(lat)) return dawn_set_error_msg(-201, "dawn_sampler_run: workspace too small");
     float* x = (float*)ws; ws += lat;
     float* eps = (float*)ws; ws += lat;
     float* x0 = (float*)ws; ws += lat;
     float* noise = (float*)ws; ws += lat;
-    unsigned* hist1 = (unsigned*)ws; ws += al256(2048 * 4);
-    unsigned* hist2 = (unsigned*)ws; ws += al256(1024 * 4);
-    unsigned* hist3 = (unsigned*)ws; ws += al256(1024 * 4);
-    unsigned* state = (unsigned*)ws; ws += 256;
-    unsigned* hmin = (unsigned*)ws; ws += 256;
-    float* sthr = (float*)ws; ws += 256;
+    float* const v_hist = noise;              // DPM-Solver++(2M) draws no noise: the same latent carries its history, the clipped x0
+    SelectScratch sel;
+    sel.hist1 = (unsigned*)ws; ws += al256(2048 * 4);
+    sel.hist2 = (unsigned*)ws; ws += al256(1024 * 4);
+    sel.hist3 = (unsigned*)ws; ws += al256(1024 * 4);
+    sel.state = (unsigned*)ws; ws += 256;
+    sel.hmin = (unsigned*)ws; ws += 256;
+    sel.sthr = (float*)ws; ws += 256;
     ws += 256;
     const size_t fwd_bytes = workspace_bytes - (size_t)(ws - (char*)workspace);
     HCK(hipMemcpyAsync(x, x_init, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
@@ -1213,123 +1268,84 @@ static int sampler_run_impl(dawn_ctx* c, int F, int h, int w, const void* clip_m
         weight = (float)(pos - fl);
     }
     for (int i = 0; i < S; ++i) {
-        const int t = dsteps ? dsteps[i].t : asteps ? asteps[i].t : steps[i].t;
-        const float recip = dsteps ? dsteps[i].recip : asteps ? asteps[i].recip : steps[i].recip;
-        const float recipm1 = dsteps ? dsteps[i].recipm1 : asteps ? asteps[i].recipm1 : steps[i].recipm1;
-        const float* v_prev = dsteps && dsteps[i].c != 0.0f ? noise : nullptr;      // (the history: written by step i - 1)
+        const StepView st = step_view(run, i);
         c->arena.reset(ws, fwd_bytes, false);
-        if (!dynamic) {
-            {
-                Eval ev(c, s, F, h, w, clip_mem);
-                ev.set_shard(comm);
-                if (guided) ev.forward_guided(x, (float)t, null_clip_mem, cond_scale, eps);
-                else ev.forward(x, (float)t, eps);
-                if (ev.rc) return ev.rc;
-            }
-            float* dst = (i + 1 == S) ? x_out : x;
-            const int clamp = kind == DAWN_CLIP_STATIC;
-            if (dsteps) {
-                CK(dawn_dpmpp_step_fixed(x, eps, v_prev, recip, recipm1, dsteps[i].a, dsteps[i].b, dsteps[i].c, clamp, n, noise, dst, s));
-                KNOWN_AT(dst, i + 1);
-                continue;
-            }
-            const float* nz = nullptr;
-            if (asteps ? t > 0 : steps[i].t_next > 0) {
-                if (noises) nz = noises[i];
-                else { CK(dawn_philox_normal(noise, 3, F, f0g, Ftot, h * w, seed, (uint32_t)(i + 1), s)); nz = noise; }
-            }
-            if (asteps) CK(dawn_ancestral_step_fixed(x, eps, nz, recip, recipm1, asteps[i].c1, asteps[i].c2, asteps[i].std, clamp, n, nullptr, dst, s));
-            else CK(dawn_ddim_step_fixed(x, eps, nz, recip, recipm1, steps[i].sqrt_alpha_next, steps[i].c, steps[i].sigma, clamp, n, nullptr, dst, s));
-            KNOWN_AT(dst, i + 1);
-            continue;
-        }
-        if (guided) {
-            HCK(hipMemsetAsync(hist1, 0, 2048 * 4, s));
+        float* dst = (i + 1 == S) ? x_out : x;
+        // the evaluation -> eps; dynamic: x0 and the first histogram with it, in the guided evaluation's last launch or in dawn_ddim_x0
+        if (dynamic && guided) HCK(hipMemsetAsync(sel.hist1, 0, 2048 * 4, s));
+        {
             Eval ev(c, s, F, h, w, clip_mem);
             ev.set_shard(comm);
-            ev.forward_guided(x, (float)t, null_clip_mem, cond_scale, eps, x0, hist1, recip, recipm1);
+            if (!guided) ev.forward(x, (float)st.t, eps);
+            else if (dynamic) ev.forward_guided(x, (float)st.t, null_clip_mem, cond_scale, eps, x0, sel.hist1, st.recip, st.recipm1);
+            else ev.forward_guided(x, (float)st.t, null_clip_mem, cond_scale, eps);
             if (ev.rc) return ev.rc;
-        } else {
-            {
-                Eval ev(c, s, F, h, w, clip_mem);
-                ev.set_shard(comm);
-                ev.forward(x, (float)t, eps);
-                if (ev.rc) return ev.rc;
-            }
-            HCK(hipMemsetAsync(hist1, 0, 2048 * 4, s));
-            CK(dawn_ddim_x0(x, eps, recip, recipm1, n, x0, hist1, s));
         }
-        SHARD_CB(comm->allreduce_sum_u32(comm->user, hist1, 2048, stream));
-        HCK(hipMemsetAsync(state, 0, 16, s));
-        CK(dawn_select_scan(hist1, 2048, lo, state, 1, s));
-        HCK(hipMemsetAsync(hist2, 0, 1024 * 4, s));
-        CK(dawn_select_hist(x0, n, state, 2, hist2, s));
-        SHARD_CB(comm->allreduce_sum_u32(comm->user, hist2, 1024, stream));
-        CK(dawn_select_scan(hist2, 1024, 0, state, 2, s));
-        HCK(hipMemsetAsync(hist3, 0, 1024 * 4, s));
-        CK(dawn_select_hist(x0, n, state, 3, hist3, s));
-        SHARD_CB(comm->allreduce_sum_u32(comm->user, hist3, 1024, stream));
-        CK(dawn_select_scan(hist3, 1024, 0, state, 3, s));
-        HCK(hipMemsetD32Async((hipDeviceptr_t)hmin, 0x7fffffff, 4, s));
-        CK(dawn_select_hist(x0, n, state, 4, hmin, s));
-        SHARD_CB(comm->allreduce_min_u32(comm->user, hmin, 1, stream));
-        CK(dawn_select_finalize(state, hmin, weight, sthr, s));
-        if (thresholds) HCK(hipMemcpyAsync(thresholds + 2 * i, sthr, 8, hipMemcpyDeviceToDevice, s));
-        if (dsteps) {
-            CK(dawn_dpmpp_update(x0, sthr, x, v_prev, dsteps[i].a, dsteps[i].b, dsteps[i].c, n, noise, (i + 1 == S) ? x_out : x, s));
-            KNOWN_AT((i + 1 == S) ? x_out : x, i + 1);
-            continue;
+        if (dynamic) {
+            if (!guided) {
+                HCK(hipMemsetAsync(sel.hist1, 0, 2048 * 4, s));
+                CK(dawn_ddim_x0(x, eps, st.recip, st.recipm1, n, x0, sel.hist1, s));
+            }
+            CK(select_threshold(sel, x0, n, lo, weight, thresholds ? thresholds + 2 * i : nullptr, comm, stream));
         }
         const float* nz = nullptr;
-        if (asteps ? t > 0 : steps[i].t_next > 0) {            // noise only if t_next > 0 (MT:1201) / t > 0 (MT:1120)
+        if (st.draws_noise) {
             if (noises) nz = noises[i];
             else { CK(dawn_philox_normal(noise, 3, F, f0g, Ftot, h * w, seed, (uint32_t)(i + 1), s)); nz = noise; }
         }
-        if (asteps) {
-            const dawn_ancestral_step& st = asteps[i];
-            CK(dawn_ancestral_update(x0, x, sthr, nz, st.c1, st.c2, st.std, n, (i + 1 == S) ? x_out : x, s));
-        } else {
-            const dawn_ddim_step& st = steps[i];
-            CK(dawn_ddim_update(x0, eps, sthr, nz, st.sqrt_alpha_next, st.c, st.sigma, n, (i + 1 == S) ? x_out : x, s));
+        const int clamp = kind == DAWN_CLIP_STATIC;
+        switch (run.solver) {
+        case DAWN_SOLVER_DPMPP: {
+            const float* v_prev = st.k2 != 0.0f ? v_hist : nullptr;        // (the history: written by step i - 1)
+            if (dynamic) CK(dawn_dpmpp_update(x0, sel.sthr, x, v_prev, st.k0, st.k1, st.k2, n, v_hist, dst, s));
+            else CK(dawn_dpmpp_step_fixed(x, eps, v_prev, st.recip, st.recipm1, st.k0, st.k1, st.k2, clamp, n, v_hist, dst, s));
+            break;
         }
-        KNOWN_AT((i + 1 == S) ? x_out : x, i + 1);
+        case DAWN_SOLVER_ANCESTRAL:
+            if (dynamic) CK(dawn_ancestral_update(x0, x, sel.sthr, nz, st.k0, st.k1, st.k2, n, dst, s));
+            else CK(dawn_ancestral_step_fixed(x, eps, nz, st.recip, st.recipm1, st.k0, st.k1, st.k2, clamp, n, nullptr, dst, s));
+            break;
+        default:
+            if (dynamic) CK(dawn_ddim_update(x0, eps, sel.sthr, nz, st.k0, st.k1, st.k2, n, dst, s));
+            else CK(dawn_ddim_step_fixed(x, eps, nz, st.recip, st.recipm1, st.k0, st.k1, st.k2, clamp, n, nullptr, dst, s));
+        }
+        KNOWN_AT(dst, i + 1);
     }
     if (S == 0) HCK(hipMemcpyAsync(x_out, x, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
     if (kind == DAWN_CLIP_STATIC && thresholds && S > 0)      // [1, 1] per step: 0x3f800000 is 1.0f
         HCK(hipMemsetD32Async((hipDeviceptr_t)thresholds, 0x3f800000, (size_t)2 * S, s));
     return 0;
-#undef SHARD_CB
 #undef KNOWN_AT
 }
 extern "C" int dawn_sampler_run_sharded(dawn_ctx* c, int F, int h, int w, const void* clip_mem, const float* x_init, int S,
                                         const dawn_ddim_step* steps, uint64_t seed, const float* const* noises, float* x_out,
                                         float* thresholds, void* workspace, size_t workspace_bytes, const dawn_shard_comm* comm,
                                         void* stream) {
-    return sampler_run_impl(c, F, h, w, clip_mem, nullptr, 1.0f, x_init, S, steps, seed, noises, x_out, thresholds, workspace,
-                            workspace_bytes, comm, stream);
+    return sampler_run_impl(c, F, h, w, clip_mem, nullptr, 1.0f, x_init, S, SamplerRun{DAWN_SOLVER_DDIM, steps}, seed, noises, x_out,
+                            thresholds, workspace, workspace_bytes, comm, stream);
 }
 extern "C" int dawn_sampler_run_guided(dawn_ctx* c, int F, int h, int w, const void* clip_mem, const void* null_clip_mem, float cond_scale,
                                        const float* x_init, int S, const dawn_ddim_step* steps, uint64_t seed, const float* const* noises,
                                        float* x_out, float* thresholds, void* workspace, size_t workspace_bytes, const dawn_shard_comm* comm,
                                        void* stream) {
     if (!null_clip_mem) return dawn_set_error_msg(-202, "dawn_sampler_run_guided: null argument");
-    return sampler_run_impl(c, F, h, w, clip_mem, null_clip_mem, cond_scale, x_init, S, steps, seed, noises, x_out, thresholds,
-                            workspace, workspace_bytes, comm, stream);
+    return sampler_run_impl(c, F, h, w, clip_mem, null_clip_mem, cond_scale, x_init, S, SamplerRun{DAWN_SOLVER_DDIM, steps}, seed, noises,
+                            x_out, thresholds, workspace, workspace_bytes, comm, stream);
 }
 extern "C" int dawn_sampler_run_ancestral(dawn_ctx* c, int F, int h, int w, const void* clip_mem, const void* null_clip_mem,
                                           float cond_scale, const float* x_init, int S, const dawn_ancestral_step* steps, uint64_t seed,
                                           const float* const* noises, float* x_out, float* thresholds, void* workspace,
                                           size_t workspace_bytes, const dawn_shard_comm* comm, void* stream) {
-    return sampler_run_impl(c, F, h, w, clip_mem, null_clip_mem, cond_scale, x_init, S, nullptr, seed, noises, x_out, thresholds,
-                            workspace, workspace_bytes, comm, stream, steps);
+    return sampler_run_impl(c, F, h, w, clip_mem, null_clip_mem, cond_scale, x_init, S, SamplerRun{DAWN_SOLVER_ANCESTRAL, steps}, seed, noises,
+                            x_out, thresholds, workspace, workspace_bytes, comm, stream);
 }
 extern "C" int dawn_sampler_run_clip(dawn_ctx* c, int F, int h, int w, const void* clip_mem, const void* null_clip_mem, float cond_scale,
                                      const float* x_init, int S, const dawn_ddim_step* steps, uint64_t seed, const float* const* noises,
                                      float* x_out, float* thresholds, void* workspace, size_t workspace_bytes, const dawn_shard_comm* comm,
                                      const dawn_clip_mode* clip, void* stream) {
     if (!steps) return dawn_set_error_msg(-202, "dawn_sampler_run_clip: null argument");
-    return sampler_run_impl(c, F, h, w, clip_mem, null_clip_mem, cond_scale, x_init, S, steps, seed, noises, x_out, thresholds,
-                            workspace, workspace_bytes, comm, stream, nullptr, clip);
+    return sampler_run_impl(c, F, h, w, clip_mem, null_clip_mem, cond_scale, x_init, S, SamplerRun{DAWN_SOLVER_DDIM, steps, clip}, seed, noises,
+                            x_out, thresholds, workspace, workspace_bytes, comm, stream);
 }
 extern "C" int dawn_sampler_run_ancestral_clip(dawn_ctx* c, int F, int h, int w, const void* clip_mem, const void* null_clip_mem,
                                                float cond_scale, const float* x_init, int S, const dawn_ancestral_step* steps,
@@ -1337,16 +1353,16 @@ extern "C" int dawn_sampler_run_ancestral_clip(dawn_ctx* c, int F, int h, int w,
                                                void* workspace, size_t workspace_bytes, const dawn_shard_comm* comm,
                                                const dawn_clip_mode* clip, void* stream) {
     if (!steps) return dawn_set_error_msg(-202, "dawn_sampler_run_ancestral_clip: null argument");
-    return sampler_run_impl(c, F, h, w, clip_mem, null_clip_mem, cond_scale, x_init, S, nullptr, seed, noises, x_out, thresholds,
-                            workspace, workspace_bytes, comm, stream, steps, clip);
+    return sampler_run_impl(c, F, h, w, clip_mem, null_clip_mem, cond_scale, x_init, S, SamplerRun{DAWN_SOLVER_ANCESTRAL, steps, clip}, seed,
+                            noises, x_out, thresholds, workspace, workspace_bytes, comm, stream);
 }
 extern "C" int dawn_sampler_run_dpmpp(dawn_ctx* c, int F, int h, int w, const void* clip_mem, const void* null_clip_mem, float cond_scale,
                                       const float* x_init, int S, const dawn_dpmpp_step* steps, float* x_out, float* thresholds,
                                       void* workspace, size_t workspace_bytes, const dawn_shard_comm* comm, const dawn_clip_mode* clip,
                                       void* stream) {
     if (!steps) return dawn_set_error_msg(-202, "dawn_sampler_run_dpmpp: null argument");
-    return sampler_run_impl(c, F, h, w, clip_mem, null_clip_mem, cond_scale, x_init, S, nullptr, 0, nullptr, x_out, thresholds, workspace,
-                            workspace_bytes, comm, stream, nullptr, clip, steps);
+    return sampler_run_impl(c, F, h, w, clip_mem, null_clip_mem, cond_scale, x_init, S, SamplerRun{DAWN_SOLVER_DPMPP, steps, clip}, 0, nullptr,
+                            x_out, thresholds, workspace, workspace_bytes, comm, stream);
 }
 extern "C" int dawn_sampler_run_known(dawn_ctx* c, int F, int h, int w, const void* clip_mem, const void* null_clip_mem, float cond_scale,
                                       const float* x_init, int S, int solver, const void* steps, uint64_t seed, const float* const* noises,
@@ -1356,12 +1372,9 @@ extern "C" int dawn_sampler_run_known(dawn_ctx* c, int F, int h, int w, const vo
     if (solver != DAWN_SOLVER_DDIM && solver != DAWN_SOLVER_ANCESTRAL && solver != DAWN_SOLVER_DPMPP)
         return dawn_set_error_msg(-217, "dawn_sampler_run_known: unknown solver (DAWN_SOLVER_DDIM, DAWN_SOLVER_ANCESTRAL or DAWN_SOLVER_DPMPP)");
     if (!steps) return dawn_set_error_msg(-202, "dawn_sampler_run_known: null argument");
-    const bool dp = solver == DAWN_SOLVER_DPMPP;
     return sampler_run_impl(c, F, h, w, clip_mem, null_clip_mem, cond_scale, x_init, S,
-                            solver == DAWN_SOLVER_DDIM ? (const dawn_ddim_step*)steps : nullptr, seed, dp ? nullptr : noises, x_out,
-                            thresholds, workspace, workspace_bytes, comm, stream,
-                            solver == DAWN_SOLVER_ANCESTRAL ? (const dawn_ancestral_step*)steps : nullptr, clip,
-                            dp ? (const dawn_dpmpp_step*)steps : nullptr, known, known_mask, known_ab, known_noises);
+                            SamplerRun{solver, steps, clip, known, known_mask, known_ab, known_noises}, seed, noises, x_out, thresholds,
+                            workspace, workspace_bytes, comm, stream);
 }
 // the plan of a chunked long clip (include/dawn_hip.h); pure host arithmetic
 extern "C" int dawn_chunk_plan(int T, int F, int K, int* starts, int* known, int max_chunks) {

@@ -56,6 +56,16 @@ CLIP_KINDS = {"dynamic": 0, "static": 1, "none": 2}      # DAWN_CLIP_DYNAMIC / _
 SOLVER_DDIM, SOLVER_ANCESTRAL, SOLVER_DPMPP = 0, 1, 2    # DAWN_SOLVER_DDIM / _ANCESTRAL / _DPMPP
 
 
+# CtxEvaluator method -> (solver tag, mirror of its step struct, sampler.draws_noise kind)
+_SOLVERS = {"sample": (SOLVER_DDIM, DdimStep, "ddim"), "sample_ancestral": (SOLVER_ANCESTRAL, AncestralStep, "ancestral"),
+            "sample_dpmpp": (SOLVER_DPMPP, DpmppStep, "dpmpp")}
+# solver tag -> its entry when (x0_clip is given, guided, sharded, none of these); CtxEvaluator._entry
+_ENTRIES = {SOLVER_DDIM: ("dawn_sampler_run_clip", "dawn_sampler_run_guided", "dawn_sampler_run_sharded", "dawn_sampler_run"),
+            SOLVER_ANCESTRAL: ("dawn_sampler_run_ancestral_clip",) + ("dawn_sampler_run_ancestral",) * 3,
+            SOLVER_DPMPP: ("dawn_sampler_run_dpmpp",) * 4}
+_NO_CLIP_MODE = ("dawn_sampler_run", "dawn_sampler_run_sharded", "dawn_sampler_run_guided", "dawn_sampler_run_ancestral")
+
+
 def _clip_struct(clip, ancestral: bool) -> ClipMode:
     from .sampler import clip_mode
     kind, q = clip_mode(clip, ancestral)
@@ -332,131 +342,13 @@ class CtxEvaluator(_Evaluator):
                shard: Optional[ShardCallbacks] = None, null_clip: Optional[dict] = None, cond_scale: float = 1.0, x0_clip=None,
                known=None, known_entry: bool = False):
         """cond_scale != 1 (with null_clip = prepare_null_clip(...)): guided sampling, dawn_sampler_run_guided.
+        noises[i] is read only for steps with t_next > 0, and must be there for those.
         known (sampler.KnownFrames): known-frame conditioning through dawn_sampler_run_known (every form: guided, sharded, any clipping
         mode); known_entry=True takes that entry without a known set too (bit-identical to the entries below).
         x0_clip (sampler.clip_mode; None: dynamic thresholding at 0.9 through the entries above): any x0 clipping mode through
         dawn_sampler_run_clip, single / guided / sharded alike.  Thresholds: static [1, 1] per step, none: rows left as allocated."""
-        F, h, w = clip["F"], clip["h"], clip["w"]
-        S = len(steps)
-        arr = (DdimStep * max(S, 1))()
-        for i, st in enumerate(steps):
-            arr[i].t, arr[i].t_next = int(st["t"]), int(st["t_next"])
-            arr[i].recip, arr[i].recipm1 = st["recip"], st["recipm1"]
-            arr[i].sqrt_alpha_next, arr[i].c, arr[i].sigma = st["sqrt_alpha_next"], st["c"], st["sigma"]
-        nz = None
-        if noises is not None:
-            nz = (C.c_void_p * S)()
-            for i, t in enumerate(noises):
-                if t is not None and not (t.is_cuda and t.is_contiguous() and t.numel() == 3 * F * h * w and t.dtype == torch.float32):
-                    raise _lib.DawnHipError(f"sample: noises[{i}] must be a contiguous fp32 GPU tensor of {3 * F * h * w} elements")
-                nz[i] = None if t is None else t.data_ptr()
-        if known is not None or known_entry:
-            return self._sample_known(SOLVER_DDIM, "sample", clip, x_init, arr, S, seed, nz, want_thresholds, shard, null_clip, cond_scale,
-                                      x0_clip, known)
-        x_init = x_init.contiguous().float()
-        out = torch.empty_like(x_init)
-        thr = torch.empty(S, 2, device=self.device) if want_thresholds else None
-        if x0_clip is not None:
-            mode = _clip_struct(x0_clip, False)
-            guided = cond_scale != 1.0
-            if guided and null_clip is None:
-                raise _lib.DawnHipError("sample: cond_scale != 1 needs null_clip (prepare_null_clip)")
-            ws = self.workspace(F, h, w, shard, guided=guided)
-            comm = None
-            if shard is not None:
-                shard.ws = ws
-                comm = C.addressof(shard.c)
-            rc = self.L.dawn_sampler_run_clip(self.h, F, h, w, clip["mem"].data_ptr(), null_clip["mem"].data_ptr() if guided else None,
-                                              float(cond_scale), x_init.data_ptr(), S, arr, int(seed), nz, out.data_ptr(),
-                                              None if thr is None else thr.data_ptr(), ws.data_ptr(), ws.numel(), comm,
-                                              C.addressof(mode), self._stream())
-            if shard is not None:
-                self._shard_call(shard, rc, "dawn_sampler_run_clip")
-            else:
-                check(rc, "dawn_sampler_run_clip")
-            return (out, thr) if want_thresholds else out
-        if cond_scale != 1.0:
-            if null_clip is None:
-                raise _lib.DawnHipError("sample: cond_scale != 1 needs null_clip (prepare_null_clip)")
-            ws = self.workspace(F, h, w, shard, guided=True)
-            comm = None
-            if shard is not None:
-                shard.ws = ws
-                comm = C.addressof(shard.c)
-            rc = self.L.dawn_sampler_run_guided(self.h, F, h, w, clip["mem"].data_ptr(), null_clip["mem"].data_ptr(), float(cond_scale),
-                                                x_init.data_ptr(), S, arr, int(seed), nz, out.data_ptr(),
-                                                None if thr is None else thr.data_ptr(), ws.data_ptr(), ws.numel(), comm, self._stream())
-            if shard is not None:
-                self._shard_call(shard, rc, "dawn_sampler_run_guided")
-            else:
-                check(rc, "dawn_sampler_run_guided")
-            return (out, thr) if want_thresholds else out
-        ws = self.workspace(F, h, w, shard)
-        if shard is not None:
-            shard.ws = ws
-            self._shard_call(shard, self.L.dawn_sampler_run_sharded(self.h, F, h, w, clip["mem"].data_ptr(), x_init.data_ptr(), S, arr,
-                                                                    int(seed), nz, out.data_ptr(), None if thr is None else thr.data_ptr(),
-                                                                    ws.data_ptr(), ws.numel(), C.addressof(shard.c), self._stream()),
-                             "dawn_sampler_run_sharded")
-            return (out, thr) if want_thresholds else out
-        check(self.L.dawn_sampler_run(self.h, F, h, w, clip["mem"].data_ptr(), x_init.data_ptr(), S, arr, int(seed), nz,
-                                      out.data_ptr(), None if thr is None else thr.data_ptr(), ws.data_ptr(), ws.numel(),
-                                      self._stream()), "dawn_sampler_run")
-        return (out, thr) if want_thresholds else out
-
-    def _sample_known(self, solver: int, who: str, clip: dict, x_init: Tensor, arr, S: int, seed: int, nz, want_thresholds: bool,
-                      shard: Optional[ShardCallbacks], null_clip: Optional[dict], cond_scale: float, x0_clip, known):
-        """dawn_sampler_run_known: the loop of `solver` over the step array `arr`, with the known set (sampler.KnownFrames, or None)."""
-        F, h, w = clip["F"], clip["h"], clip["w"]
-        n = 3 * F * h * w
-        guided = cond_scale != 1.0
-        if guided and null_clip is None:
-            raise _lib.DawnHipError(f"{who}: cond_scale != 1 needs null_clip (prepare_null_clip)")
-        lat = msk = ab = kz = None
-        keep = []
-        if known is not None:
-            lat, msk = known.latent, known.mask
-            if not (lat.is_cuda and lat.is_contiguous() and lat.dtype == torch.float32 and lat.numel() == n):
-                raise _lib.DawnHipError(f"{who}: known.latent must be a contiguous fp32 GPU tensor of {n} elements")
-            if not (msk.is_cuda and msk.is_contiguous() and msk.dtype == torch.uint8 and msk.numel() == F):
-                raise _lib.DawnHipError(f"{who}: known.mask must be {F} uint8 values on the GPU")
-            if len(known.levels) != S + 1:
-                raise _lib.DawnHipError(f"{who}: known.levels must hold {S + 1} (a, b) pairs")
-            ab = (C.c_float * (2 * (S + 1)))(*[float(v) for lv in known.levels for v in lv])
-            if known.noise_fn is not None:
-                kz = (C.c_void_p * (S + 1))()
-                for i, (_, b) in enumerate(known.levels):
-                    z = known.noise_fn(i) if b != 0.0 else None
-                    if z is not None and not (z.is_cuda and z.is_contiguous() and z.dtype == torch.float32 and z.numel() == n):
-                        raise _lib.DawnHipError(f"{who}: known noise {i} must be a contiguous fp32 GPU tensor of {n} elements")
-                    if z is None and b != 0.0:
-                        raise _lib.DawnHipError(f"{who}: known noise {i} missing for a level with b != 0")
-                    keep.append(z)
-                    kz[i] = None if z is None else z.data_ptr()
-            else:                                # the entry has ONE seed: step noise on streams i + 1, known-frame noise on 0x80000000 + i
-                if nz is None and solver != SOLVER_DPMPP and int(seed) != int(known.seed):
-                    raise _lib.DawnHipError(f"{who}: known.seed must equal the step-noise seed (the C entry takes one seed for both)")
-                seed = known.seed
-        x_init = x_init.contiguous().float()
-        out = torch.empty_like(x_init)
-        thr = torch.empty(S, 2, device=self.device) if want_thresholds else None
-        mode = None if x0_clip is None else _clip_struct(x0_clip, solver == SOLVER_ANCESTRAL)
-        ws = self.workspace(F, h, w, shard, guided=guided)
-        comm = None
-        if shard is not None:
-            shard.ws = ws
-            comm = C.addressof(shard.c)
-        rc = self.L.dawn_sampler_run_known(self.h, F, h, w, clip["mem"].data_ptr(), null_clip["mem"].data_ptr() if guided else None,
-                                           float(cond_scale), x_init.data_ptr(), S, solver, arr, int(seed), nz, out.data_ptr(),
-                                           None if thr is None else thr.data_ptr(), ws.data_ptr(), ws.numel(), comm,
-                                           None if mode is None else C.addressof(mode), None if lat is None else lat.data_ptr(),
-                                           None if msk is None else msk.data_ptr(), ab, kz, self._stream())
-        if shard is not None:
-            self._shard_call(shard, rc, "dawn_sampler_run_known")
-        else:
-            check(rc, "dawn_sampler_run_known")
-        del keep
-        return (out, thr) if want_thresholds else out
+        return self._run("sample", clip, x_init, steps, seed, noises, want_thresholds, shard, null_clip, cond_scale, x0_clip, known,
+                         known_entry)
 
     def sample_ancestral(self, clip: dict, x_init: Tensor, steps: Sequence[dict], seed: int = 0,
                          noises: Optional[List[Optional[Tensor]]] = None, want_thresholds: bool = False,
@@ -466,85 +358,118 @@ class CtxEvaluator(_Evaluator):
         prepare_null_clip(...)), one T-shard rank when `shard` is given.  noises[i] is read only for steps with t > 0.
         x0_clip (sampler.clip_mode; None: dynamic thresholding at 0.9 through that entry): ("dynamic", q) or ("static",) through
         dawn_sampler_run_ancestral_clip.  known / known_entry: as for sample()."""
-        F, h, w = clip["F"], clip["h"], clip["w"]
-        S = len(steps)
-        arr = (AncestralStep * max(S, 1))()
-        for i, st in enumerate(steps):
-            arr[i].t, arr[i].recip, arr[i].recipm1 = int(st["t"]), st["recip"], st["recipm1"]
-            arr[i].c1, arr[i].c2, arr[i].std = st["c1"], st["c2"], st["std"]
-        nz = None
-        if noises is not None:
-            nz = (C.c_void_p * max(S, 1))()
-            for i in range(S):
-                t = noises[i] if i < len(noises) and steps[i]["t"] > 0 else None
-                if t is not None and not (t.is_cuda and t.is_contiguous() and t.numel() == 3 * F * h * w and t.dtype == torch.float32):
-                    raise _lib.DawnHipError(f"sample_ancestral: noises[{i}] must be a contiguous fp32 GPU tensor of {3 * F * h * w} elements")
-                if t is None and steps[i]["t"] > 0:
-                    raise _lib.DawnHipError(f"sample_ancestral: noises[{i}] missing for a step with t > 0")
-                nz[i] = None if t is None else t.data_ptr()
-        if known is not None or known_entry:
-            return self._sample_known(SOLVER_ANCESTRAL, "sample_ancestral", clip, x_init, arr, S, seed, nz, want_thresholds, shard, null_clip,
-                                      cond_scale, x0_clip, known)
-        guided = cond_scale != 1.0
-        if guided and null_clip is None:
-            raise _lib.DawnHipError("sample_ancestral: cond_scale != 1 needs null_clip (prepare_null_clip)")
-        x_init = x_init.contiguous().float()
-        out = torch.empty_like(x_init)
-        thr = torch.empty(S, 2, device=self.device) if want_thresholds else None
-        ws = self.workspace(F, h, w, shard, guided=guided)
-        comm = None
-        if shard is not None:
-            shard.ws = ws
-            comm = C.addressof(shard.c)
-        args = (self.h, F, h, w, clip["mem"].data_ptr(), null_clip["mem"].data_ptr() if guided else None, float(cond_scale),
-                x_init.data_ptr(), S, arr, int(seed), nz, out.data_ptr(), None if thr is None else thr.data_ptr(), ws.data_ptr(),
-                ws.numel(), comm)
-        if x0_clip is not None:
-            mode = _clip_struct(x0_clip, True)
-            rc, what = self.L.dawn_sampler_run_ancestral_clip(*args, C.addressof(mode), self._stream()), "dawn_sampler_run_ancestral_clip"
-        else:
-            rc, what = self.L.dawn_sampler_run_ancestral(*args, self._stream()), "dawn_sampler_run_ancestral"
-        if shard is not None:
-            self._shard_call(shard, rc, what)
-        else:
-            check(rc, what)
-        return (out, thr) if want_thresholds else out
+        return self._run("sample_ancestral", clip, x_init, steps, seed, noises, want_thresholds, shard, null_clip, cond_scale, x0_clip,
+                         known, known_entry)
 
     def sample_dpmpp(self, clip: dict, x_init: Tensor, steps: Sequence[dict], want_thresholds: bool = False,
                      shard: Optional[ShardCallbacks] = None, null_clip: Optional[dict] = None, cond_scale: float = 1.0, x0_clip=None,
                      known=None, known_entry: bool = False):
-        """known / known_entry: as for sample() (the known-frame noise is the only noise this loop draws).  dawn_sampler_run_dpmpp: the DPM-Solver++(2M) loop (sampler.dpmpp_step_scalars), guided when cond_scale != 1 (null_clip =
+        """dawn_sampler_run_dpmpp: the DPM-Solver++(2M) loop (sampler.dpmpp_step_scalars), guided when cond_scale != 1 (null_clip =
         prepare_null_clip(...)), one T-shard rank when `shard` is given.  Deterministic: no seed, no noises.  x0_clip (sampler.clip_mode;
-        None: dynamic thresholding at 0.9): any clipping mode.  Thresholds: static [1, 1] per step, none: rows left as allocated."""
-        F, h, w = clip["F"], clip["h"], clip["w"]
-        S = len(steps)
-        arr = (DpmppStep * max(S, 1))()
+        None: dynamic thresholding at 0.9): any clipping mode.  Thresholds: static [1, 1] per step, none: rows left as allocated.
+        known / known_entry: as for sample() (the known-frame noise is the only noise this loop draws)."""
+        return self._run("sample_dpmpp", clip, x_init, steps, 0, None, want_thresholds, shard, null_clip, cond_scale, x0_clip, known,
+                         known_entry)
+
+    @staticmethod
+    def _entry(solver: int, known: bool, clipped: bool, guided: bool, sharded: bool) -> str:
+        """The C entry a sampler method takes: the first column of its row that applies (known or known_entry, x0_clip given, guided,
+        shard, neither).  Several entries reach one loop, and the GPU tests compare them: the choice is behaviour."""
+        if known:
+            return "dawn_sampler_run_known"
+        return _ENTRIES[solver][0 if clipped else 1 if guided else 2 if sharded else 3]
+
+    @staticmethod
+    def _noise_ptrs(who: str, kind: str, steps: Sequence[dict], noises, n: int):
+        """noises -> the `noises` array of the C entries: the tensor of every step that draws noise, NULL for the others (never read)."""
+        from .sampler import draws_noise
+        nz = (C.c_void_p * max(len(steps), 1))()
         for i, st in enumerate(steps):
-            arr[i].t, arr[i].recip, arr[i].recipm1 = int(st["t"]), st["recip"], st["recipm1"]
-            arr[i].a, arr[i].b, arr[i].c = st["a"], st["b"], st["c"]
-        if known is not None or known_entry:
-            return self._sample_known(SOLVER_DPMPP, "sample_dpmpp", clip, x_init, arr, S, 0, None, want_thresholds, shard, null_clip, cond_scale,
-                                      x0_clip, known)
-        guided = cond_scale != 1.0
-        if guided and null_clip is None:
-            raise _lib.DawnHipError("sample_dpmpp: cond_scale != 1 needs null_clip (prepare_null_clip)")
+            if not draws_noise(kind, st):
+                continue
+            t = noises[i] if i < len(noises) else None
+            if t is None:                        # (the C loop would take NULL for "no noise" and return a wrong clip)
+                raise _lib.DawnHipError(f"{who}: noises[{i}] missing for a step that draws noise (t = {st['t']})")
+            if not (t.is_cuda and t.is_contiguous() and t.numel() == n and t.dtype == torch.float32):
+                raise _lib.DawnHipError(f"{who}: noises[{i}] must be a contiguous fp32 GPU tensor of {n} elements")
+            nz[i] = t.data_ptr()
+        return nz
+
+    @staticmethod
+    def _sample_known(who: str, solver: int, known, S: int, F: int, n: int, seed: int, nz):
+        """The known-set arguments of dawn_sampler_run_known (sampler.KnownFrames, or None: all NULL) and the seed the entry runs with:
+        ((latent, mask, ab, known noises), seed, the tensors to keep alive over the call)."""
+        if known is None:
+            return (None, None, None, None), seed, []
+        lat, msk, kz, keep = known.latent, known.mask, None, []
+        if not (lat.is_cuda and lat.is_contiguous() and lat.dtype == torch.float32 and lat.numel() == n):
+            raise _lib.DawnHipError(f"{who}: known.latent must be a contiguous fp32 GPU tensor of {n} elements")
+        if not (msk.is_cuda and msk.is_contiguous() and msk.dtype == torch.uint8 and msk.numel() == F):
+            raise _lib.DawnHipError(f"{who}: known.mask must be {F} uint8 values on the GPU")
+        if len(known.levels) != S + 1:
+            raise _lib.DawnHipError(f"{who}: known.levels must hold {S + 1} (a, b) pairs")
+        ab = (C.c_float * (2 * (S + 1)))(*[float(v) for lv in known.levels for v in lv])
+        if known.noise_fn is not None:
+            kz = (C.c_void_p * (S + 1))()
+            for i, (_, b) in enumerate(known.levels):
+                z = known.noise_fn(i) if b != 0.0 else None
+                if z is not None and not (z.is_cuda and z.is_contiguous() and z.dtype == torch.float32 and z.numel() == n):
+                    raise _lib.DawnHipError(f"{who}: known noise {i} must be a contiguous fp32 GPU tensor of {n} elements")
+                if z is None and b != 0.0:
+                    raise _lib.DawnHipError(f"{who}: known noise {i} missing for a level with b != 0")
+                keep.append(z)
+                kz[i] = None if z is None else z.data_ptr()
+        else:                                    # the entry has ONE seed: step noise on streams i + 1, known-frame noise on 0x80000000 + i
+            if nz is None and solver != SOLVER_DPMPP and int(seed) != int(known.seed):
+                raise _lib.DawnHipError(f"{who}: known.seed must equal the step-noise seed (the C entry takes one seed for both)")
+            seed = known.seed
+        return (lat.data_ptr(), msk.data_ptr(), ab, kz), seed, keep
+
+    def _run(self, who: str, clip: dict, x_init: Tensor, steps: Sequence[dict], seed: int, noises, want_thresholds: bool,
+             shard: Optional[ShardCallbacks], null_clip: Optional[dict], cond_scale: float, x0_clip, known, known_entry: bool):
+        """One sampler call of any method: marshal the steps and the noises, choose the entry (_entry), then allocate, check, size the
+        workspace, wire the shard, call, and raise what the call or a shard callback refused."""
+        solver, step_type, kind = _SOLVERS[who]
+        F, h, w = clip["F"], clip["h"], clip["w"]
+        S, n, guided = len(steps), 3 * F * h * w, cond_scale != 1.0
+        arr = (step_type * max(S, 1))()
+        for i, st in enumerate(steps):
+            for field, ctype in step_type._fields_:      # (the mirror's field names are the keys of the step dicts)
+                setattr(arr[i], field, int(st[field]) if ctype is C.c_int else st[field])
+        nz = None if noises is None else self._noise_ptrs(who, kind, steps, noises, n)
+        name = self._entry(solver, known is not None or known_entry, x0_clip is not None, guided, shard is not None)
+        known_args, keep = (), None
+        if name == "dawn_sampler_run_known":
+            known_args, seed, keep = self._sample_known(who, solver, known, S, F, n, seed, nz)
         x_init = x_init.contiguous().float()
         out = torch.empty_like(x_init)
         thr = torch.empty(S, 2, device=self.device) if want_thresholds else None
-        mode = None if x0_clip is None else _clip_struct(x0_clip, False)
+        if guided and null_clip is None:
+            raise _lib.DawnHipError(f"{who}: cond_scale != 1 needs null_clip (prepare_null_clip)")
+        mode = None if x0_clip is None else _clip_struct(x0_clip, solver == SOLVER_ANCESTRAL)
         ws = self.workspace(F, h, w, shard, guided=guided)
         comm = None
         if shard is not None:
             shard.ws = ws
             comm = C.addressof(shard.c)
-        rc = self.L.dawn_sampler_run_dpmpp(self.h, F, h, w, clip["mem"].data_ptr(), null_clip["mem"].data_ptr() if guided else None,
-                                           float(cond_scale), x_init.data_ptr(), S, arr, out.data_ptr(),
-                                           None if thr is None else thr.data_ptr(), ws.data_ptr(), ws.numel(), comm,
-                                           None if mode is None else C.addressof(mode), self._stream())
+        # the entries' argument lists differ in what they leave out
+        args = [self.h, F, h, w, clip["mem"].data_ptr()]
+        if name not in ("dawn_sampler_run", "dawn_sampler_run_sharded"):
+            args += [null_clip["mem"].data_ptr() if guided else None, float(cond_scale)]
+        args += [x_init.data_ptr(), S] + ([solver] if name == "dawn_sampler_run_known" else []) + [arr]
+        if name != "dawn_sampler_run_dpmpp":
+            args += [int(seed), nz]
+        args += [out.data_ptr(), None if thr is None else thr.data_ptr(), ws.data_ptr(), ws.numel()]
+        if name != "dawn_sampler_run":
+            args.append(comm)
+        if name not in _NO_CLIP_MODE:
+            args.append(None if mode is None else C.addressof(mode))
+        rc = getattr(self.L, name)(*args, *known_args, self._stream())
+        del keep
         if shard is not None:
-            self._shard_call(shard, rc, "dawn_sampler_run_dpmpp")
+            self._shard_call(shard, rc, name)
         else:
-            check(rc, "dawn_sampler_run_dpmpp")
+            check(rc, name)
         return (out, thr) if want_thresholds else out
 
     def profile_read(self):

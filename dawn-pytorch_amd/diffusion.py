@@ -17,9 +17,8 @@ from typing import List, Optional, Sequence
 import torch
 from torch import nn
 
-from .sampler import (CLIP_DEFAULT, KnownFrames, ancestral_sample_clip, ancestral_step_scalars, chunk_plan, clip_mode,
-                      cosine_schedule_buffers, ddim_sample_clip, ddim_step_scalars, dpmpp_sample_clip, dpmpp_step_scalars,
-                      known_level_scalars)
+from .sampler import (CLIP_DEFAULT, KnownFrames, ancestral_step_scalars, chunk_plan, clip_mode, cosine_schedule_buffers, ddim_sample_clip,
+                      ddim_step_scalars, dpmpp_step_scalars, draws_noise, known_level_scalars)
 
 Tensor = torch.Tensor
 
@@ -161,6 +160,16 @@ class GaussianDiffusion(nn.Module):
         return KnownFrames((latent[b].contiguous().float().to(device)), (mask[b] != 0).to(torch.uint8).contiguous().to(device), levels,
                            noise_fn, seed)
 
+    def _step_scalars(self, kind):
+        """The per-step scalars of the loop `kind` under self.solver, from the schedule buffers."""
+        bufs = {k: getattr(self, k) for k in ("alphas_cumprod_prev", "sqrt_recip_alphas_cumprod", "sqrt_recipm1_alphas_cumprod",
+                                              "posterior_mean_coef1", "posterior_mean_coef2", "posterior_log_variance_clipped")}
+        if kind == "ancestral":
+            return ancestral_step_scalars(bufs, self.num_timesteps)
+        if self.solver == "dpmpp2m":
+            return dpmpp_step_scalars(bufs, self.sampling_timesteps, self.num_timesteps)
+        return ddim_step_scalars(bufs, self.sampling_timesteps, self.ddim_sampling_eta, self.num_timesteps)
+
     def _sample_loop(self, kind, fea, shape, cond, cond_scale, x_init, noises, trace, comm, clip, known=(None, None, None)):
         """One host loop for every sampler (kind "ddim" / "ancestral"; solver "dpmpp2m" turns "ddim" into the DPM-Solver++(2M) steps
         on the same time pairs): the C-side evaluator when use_ctx, else the Python orchestration; they share the evaluation and
@@ -179,25 +188,27 @@ class GaussianDiffusion(nn.Module):
         _long_clip_allocator(shape[2], fea)
         P = unet.packed()
         B, C, T, h, w = shape
-        if ancestral:
-            steps = ancestral_step_scalars({k: getattr(self, k) for k in (
-                "sqrt_recip_alphas_cumprod", "sqrt_recipm1_alphas_cumprod", "posterior_mean_coef1", "posterior_mean_coef2",
-                "posterior_log_variance_clipped")}, self.num_timesteps)
-        elif dpmpp:
-            steps = dpmpp_step_scalars({k: getattr(self, k) for k in ("alphas_cumprod_prev", "sqrt_recip_alphas_cumprod",
-                                                                       "sqrt_recipm1_alphas_cumprod")}, self.sampling_timesteps,
-                                       self.num_timesteps)
-        else:
-            S, eta = self.sampling_timesteps, self.ddim_sampling_eta
-            steps = ddim_step_scalars({k: getattr(self, k) for k in ("alphas_cumprod_prev", "sqrt_recip_alphas_cumprod",
-                                                                      "sqrt_recipm1_alphas_cumprod")}, S, eta,
-                                      self.num_timesteps)
-        # steps that draw noise (MT:1120 / MT:1201); DPM-Solver++(2M) draws none
-        noisy = [not dpmpp and (st["t"] > 0 if ancestral else st["t_next"] > 0) for st in steps]
+        steps = self._step_scalars(kind)
+        step_kind = "dpmpp" if dpmpp else kind
         device = fea.device
         Ttotal, f0 = (T, 0) if comm is None else (comm.Ttotal, comm.f0)
         if cond is not None and cond.shape[1] != T:
             raise ValueError(f"cond has {cond.shape[1]} frames but num_frames={T}; call update_num_frames first (UVG:370)")
+        seed = self.noise_seed
+
+        def initial_latent(b):
+            if x_init is not None:
+                return x_init[b].contiguous().float()
+            if seed is not None:
+                return ops.philox_normal(3, T, f0, Ttotal, h * w, seed + b, 0, device).reshape(3, T, h, w)
+            return torch.randn(3, T, h, w, device=device)                             # MT:1166
+
+        def known_seed(s):
+            """The seed of the known-frame noise: `s`, or unseeded (and no known_noises given) ONE draw from the global generator."""
+            if known[0] is not None and s is None and known[2] is None:
+                s = int(torch.randint(0, 2 ** 62, (1,)).item())
+            return s
+
         outs, traces = [], []
         if self.use_ctx and comm is None and not trace and fea.is_cuda:
             ev = unet.ctx_evaluator()
@@ -205,31 +216,22 @@ class GaussianDiffusion(nn.Module):
             for b in range(B):
                 clip_mem = ev.prepare_clip(fea[b].contiguous().float(), cond[b].contiguous().float(), rcos, rsin)
                 null_clip = ev.prepare_null_clip(fea[b].contiguous().float(), T, rcos, rsin) if cond_scale != 1.0 else None
-                seed = self.noise_seed
-                if x_init is not None:
-                    x0 = x_init[b].contiguous().float()
-                elif seed is not None:
-                    x0 = ops.philox_normal(3, T, 0, T, h * w, seed + b, 0, device).reshape(3, T, h, w)
-                else:
-                    x0 = torch.randn(3, T, h, w, device=device)                       # MT:1166
+                x0 = initial_latent(b)
                 nz = None
                 if noises is not None:
-                    nz = [noises[i][b].contiguous() if noisy[i] else None for i in range(len(steps))]
+                    nz = [noises[i][b].contiguous() if draws_noise(step_kind, st) else None for i, st in enumerate(steps)]
                 run_seed = (seed + b) if seed is not None else None
                 if nz is None and run_seed is None and not dpmpp:
                     # unseeded (MT:1201 draws from the global generator): ONE draw from it seeds the evaluator's counter-based
                     # generator -- S x 3 x T x h x w floats of pre-drawn noise would be GBs for the long clips the path supports
                     run_seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-                x0_clip = None if clip == CLIP_DEFAULT else clip
-                if known[0] is not None and run_seed is None and known[2] is None:
-                    run_seed = int(torch.randint(0, 2 ** 62, (1,)).item())            # (unseeded: ONE draw seeds the known-frame noise)
-                kf = self._known_frames(known, b, steps, kind, shape, device, run_seed or 0)
-                if dpmpp:
-                    outs.append(ev.sample_dpmpp(clip_mem, x0, steps, null_clip=null_clip, cond_scale=cond_scale, x0_clip=x0_clip, known=kf))
-                    continue
-                run = ev.sample_ancestral if ancestral else ev.sample
-                outs.append(run(clip_mem, x0, steps, seed=run_seed or 0, noises=nz, null_clip=null_clip, cond_scale=cond_scale,
-                                x0_clip=x0_clip, known=kf))
+                run_seed = known_seed(run_seed)
+                kw = dict(null_clip=null_clip, cond_scale=cond_scale, x0_clip=None if clip == CLIP_DEFAULT else clip,
+                          known=self._known_frames(known, b, steps, kind, shape, device, run_seed or 0))
+                if not dpmpp:
+                    kw.update(seed=run_seed or 0, noises=nz)
+                run = ev.sample_dpmpp if dpmpp else ev.sample_ancestral if ancestral else ev.sample
+                outs.append(run(clip_mem, x0, steps, **kw))
             self.last_trace = None
             self.last_route = "ctx"
             return torch.stack(outs, 0)
@@ -240,7 +242,6 @@ class GaussianDiffusion(nn.Module):
             if cond_scale != 1.0:
                 cs_null = unet.build_clip(fea[b].contiguous().float(), torch.zeros_like(cond[b]).float(), comm=comm,
                                           Ttotal=Ttotal, f0=f0)
-            seed = self.noise_seed
 
             def noise_fn(i, b=b):
                 if noises is not None:
@@ -249,24 +250,11 @@ class GaussianDiffusion(nn.Module):
                     return ops.philox_normal(3, T, f0, Ttotal, h * w, seed + b, i + 1, device).reshape(3, T, h, w)
                 return torch.randn(3, T, h, w, device=device)                         # MT:1201
 
-            if x_init is not None:
-                x0 = x_init[b].contiguous().float()
-            elif seed is not None:
-                x0 = ops.philox_normal(3, T, f0, Ttotal, h * w, seed + b, 0, device).reshape(3, T, h, w)
-            else:
-                x0 = torch.randn(3, T, h, w, device=device)                           # MT:1166
+            x0 = initial_latent(b)
             tr = [] if trace else None
-            kseed = seed + b if seed is not None else None
-            if known[0] is not None and kseed is None and known[2] is None:
-                kseed = int(torch.randint(0, 2 ** 62, (1,)).item())                   # (unseeded: ONE draw seeds the known-frame noise)
-            kf = self._known_frames(known, b, steps, kind, shape, device, kseed or 0)
-            if dpmpp:
-                outs.append(dpmpp_sample_clip(ops, P, cs, x0, steps, cond_scale, cs_null, tr, use_graph=self.use_graph,
-                                              eager_every=self.eager_every, clip=clip, known=kf))
-            else:
-                outs.append((ancestral_sample_clip if ancestral else ddim_sample_clip)(
-                    ops, P, cs, x0, steps, noise_fn, cond_scale, cs_null, tr, use_graph=self.use_graph, eager_every=self.eager_every,
-                    clip=clip, known=kf))
+            kf = self._known_frames(known, b, steps, kind, shape, device, known_seed(seed + b if seed is not None else None) or 0)
+            outs.append(ddim_sample_clip(ops, P, cs, x0, steps, noise_fn, cond_scale, cs_null, tr, use_graph=self.use_graph,
+                                         eager_every=self.eager_every, kind=step_kind, clip=clip, known=kf))
             traces.append(tr)
         self.last_trace = traces if trace else None
         self.last_route = "python"

@@ -197,6 +197,14 @@ def clip_mode(clip, ancestral: bool = False):
     raise ValueError(f'unknown clipping mode {clip!r}: ("dynamic", q), ("static",) or ("none",)')
 
 
+def draws_noise(kind: str, st: dict) -> bool:
+    """Whether step `st` of the loop `kind` draws noise: DDIM where t_next > 0 (MT:1201), ancestral where t > 0 (MT:1120; the `noise`
+    field of ancestral_step_scalars), DPM-Solver++(2M) never.  The rule of every host; in C it is step_view (csrc/dawn_ctx.hip)."""
+    if kind == "dpmpp":
+        return False
+    return st["t"] > 0 if kind == "ancestral" else st["t_next"] > 0
+
+
 def ancestral_sample_clip(ops, P: PackedUNet, cs: ClipState, x_init: Tensor, steps: Sequence[dict],
                           noise_fn: Callable[[int], Optional[Tensor]], cond_scale: float = 1.0,
                           cs_null: Optional[ClipState] = None, trace: Optional[list] = None, use_graph: bool = False,
@@ -240,6 +248,7 @@ def ddim_sample_clip(ops, P: PackedUNet, cs: ClipState, x_init: Tensor, steps: S
         raise ValueError(f"unknown sampler step kind {kind!r}")
     ancestral, dpmpp = kind == "ancestral", kind == "dpmpp"
     clip_kind, q = clip_mode(clip, ancestral)
+    dynamic, clamp = clip_kind == "dynamic", clip_kind == "static"
     if dpmpp and steps and steps[0]["c"] != 0.0:
         raise ValueError("dpmpp steps: steps[0]['c'] != 0, but the first step has no history")
     hist_v = None                                # dpmpp: the clipped x0 of the previous step
@@ -277,53 +286,45 @@ def ddim_sample_clip(ops, P: PackedUNet, cs: ClipState, x_init: Tensor, steps: S
         # with a graph, every `eager_every`-th step still runs eagerly so that per-kernel HIP events (bench.py's
         # live roofline measurement) sample the timed region
         replay = graphed is not None and not (eager_every and ops.prof is not None and i % eager_every == 0)
-        if clip_kind != "dynamic":
-            if guided:
-                eps_c, eps_null = graphed(x, st["t"]) if replay else unet_forward_guided(ops, P, cs, cs_null, x, st["t"])
-                eps = ops.cfg_combine(eps_null, eps_c, cond_scale)
-                del eps_c, eps_null
-            else:
-                eps = graphed(x, st["t"]) if replay else unet_forward(ops, P, cs, x, st["t"])
-            clamp = clip_kind == "static"
-            if dpmpp:
-                x, hist_v = ops.dpmpp_step_fixed(x, eps, hist_v if st["c"] != 0.0 else None, st["recip"], st["recipm1"], st["a"], st["b"],
-                                                 st["c"], clamp, v_out=hist_v)
-            elif ancestral:
-                noise = noise_fn(i) if st["t"] > 0 else None
-                x = ops.ancestral_step_fixed(x, eps, noise, st["recip"], st["recipm1"], st["c1"], st["c2"], st["std"], clamp)
-            else:
-                noise = noise_fn(i) if st["t_next"] > 0 else None
-                x = ops.ddim_step_fixed(x, eps, noise, st["recip"], st["recipm1"], st["sqrt_alpha_next"], st["c"], st["sigma"], clamp)
-            if known is not None:
-                x = replace(x, i + 1)
-            if trace is not None:
-                if clamp and s_one is None:
-                    s_one = torch.ones(2, device=x.device, dtype=torch.float32)
-                trace.append(dict(eps=eps.clone() if graphed is not None and not guided else eps, s=s_one if clamp else None, x=x))
-                if dpmpp:
-                    trace[-1]["x0c"] = hist_v.clone()
-            continue
+        # the evaluation -> eps; dynamic: x0 and the first quantile histogram with it, then the threshold s
+        s = None
         if guided:
             eps_c, eps_null = graphed(x, st["t"]) if replay else unet_forward_guided(ops, P, cs, cs_null, x, st["t"])
-            eps, x0, hist = ops.cfg_x0(eps_null, eps_c, cond_scale, x, st["recip"], st["recipm1"])
+            if dynamic:
+                eps, x0, hist = ops.cfg_x0(eps_null, eps_c, cond_scale, x, st["recip"], st["recipm1"])
+            else:
+                eps = ops.cfg_combine(eps_null, eps_c, cond_scale)
             del eps_c, eps_null
         else:
             eps = graphed(x, st["t"]) if replay else unet_forward(ops, P, cs, x, st["t"])
-            x0, hist = ops.ddim_x0(x, eps, st["recip"], st["recipm1"])
-        s = ops.quantile_threshold(x0, hist, n_total, q)
+            if dynamic:
+                x0, hist = ops.ddim_x0(x, eps, st["recip"], st["recipm1"])
+        if dynamic:
+            s = ops.quantile_threshold(x0, hist, n_total, q)
+        noise = noise_fn(i) if draws_noise(kind, st) else None
+        # the step tail: from x0 and s (dynamic), or ONE fused launch from x and eps
         if dpmpp:
-            x, hist_v = ops.dpmpp_update(x0, s, x, hist_v if st["c"] != 0.0 else None, st["a"], st["b"], st["c"], v_out=hist_v)
+            v_prev = hist_v if st["c"] != 0.0 else None
+            if dynamic:
+                x, hist_v = ops.dpmpp_update(x0, s, x, v_prev, st["a"], st["b"], st["c"], v_out=hist_v)
+            else:
+                x, hist_v = ops.dpmpp_step_fixed(x, eps, v_prev, st["recip"], st["recipm1"], st["a"], st["b"], st["c"], clamp, v_out=hist_v)
         elif ancestral:
-            noise = noise_fn(i) if st["t"] > 0 else None
-            x = ops.ancestral_update(x0, x, s, noise, st["c1"], st["c2"], st["std"])
-        else:
-            noise = noise_fn(i) if st["t_next"] > 0 else None
+            if dynamic:
+                x = ops.ancestral_update(x0, x, s, noise, st["c1"], st["c2"], st["std"])
+            else:
+                x = ops.ancestral_step_fixed(x, eps, noise, st["recip"], st["recipm1"], st["c1"], st["c2"], st["std"], clamp)
+        elif dynamic:
             x = ops.ddim_update(x0, eps, s, noise, st["sqrt_alpha_next"], st["c"], st["sigma"])
+        else:
+            x = ops.ddim_step_fixed(x, eps, noise, st["recip"], st["recipm1"], st["sqrt_alpha_next"], st["c"], st["sigma"], clamp)
         if known is not None:
             x = replace(x, i + 1)
         if trace is not None:
+            if clamp and s_one is None:
+                s_one = torch.ones(2, device=x.device, dtype=torch.float32)
             # a graphed evaluation returns its static output buffer: clone, or every entry would alias the last step
-            trace.append(dict(eps=eps.clone() if graphed is not None and not guided else eps, s=s, x=x))
+            trace.append(dict(eps=eps.clone() if graphed is not None and not guided else eps, s=s_one if clamp else s, x=x))
             if dpmpp:
                 trace[-1]["x0c"] = hist_v.clone()
     return x
