@@ -350,13 +350,22 @@ __global__ __launch_bounds__(512) void gemm1x1_rowacc_kernel(const dawn_conv_des
         }
     };
     // LayerNorm inside the GEMM (dawn_conv_desc.ln_eps, MODE 0): one statistics sweep over the panel's rows before its K loop
-    // (the rows come back from L2 for the GEMM sweep: 32 KB per wave) -- shifted one-pass sums (shift = the row's first channel,
-    // so that E[d^2] - E[d]^2 does not cancel), both halves of a row combined by one xor-32 exchange
+    // (the rows come back from L2 for the GEMM sweep: 32 KB per wave) -- shifted one-pass sums, both halves of a row combined by one
+    // xor-32 exchange.  Shift = the mean of the row's first 16 channels (C0 >= 16; each half sums its 8, the same sum in both lanes), so
+    // that E[d^2] - E[d]^2 does not cancel: with the first channel alone as the shift, a row whose first channel lies 3..4 sigma off its
+    // mean has E[d]^2 = 10..16 Var, and 1 / sigma came out wrong by 3.2e-6 (K = 512) and 5.0e-6 (K = 1024) of its value, 9.3x the error
+    // of an fp32 GEMM in the result (tests/split_gate.py, C_ROWACC_LN); 16 channels put the shift within sigma / 4 of the mean
     auto ln_stats = [&](long panel) __attribute__((always_inline)) {
         const long r0 = panel * BM + wave * 32;
         const __amdgpu_buffer_rsrc_t ra = DAWN_BUFFER(d.in0 + r0 * d.ld0, 32 * d.ld0 * 4);
         const __amdgpu_buffer_rsrc_t rb = DAWN_BUFFER((d.in1 ? d.in1 : d.in0) + r0 * ld1, 32 * ld1 * 4);
-        const float shift = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ra, (unsigned)(l31 * d.ld0 * 4), 0, 0));
+        float shift;
+        {
+            const f32x4 a = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ra, (unsigned)((l31 * d.ld0 + 8 * half) * 4), 0, 0));
+            const f32x4 b = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ra, (unsigned)((l31 * d.ld0 + 8 * half + 4) * 4), 0, 0));
+            const float h8 = ((a.x + a.y) + (a.z + a.w)) + ((b.x + b.y) + (b.z + b.w));
+            shift = (h8 + __shfl_xor(h8, 32, 64)) * (1.0f / 16);
+        }
         float s1 = 0.f, s2 = 0.f;
         for (int kb = 0; kb < nKB; ++kb) {
             f32x4 raw[KS][2];

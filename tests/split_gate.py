@@ -28,7 +28,8 @@ measured ratio (GPU error / CPU fp32 error, max over the cases of that kernel) i
 A case is (name, kind, params).  Shapes are production ones (profiles/r6_insitu_shapes.txt = configs[2],
 profiles/r6_config1_insitu_shapes.txt = configs[1]): H, W and the channel counts, which fix the kernel instantiation and tile geometry, are
 kept; only the number of frames (rows) is reduced.  `split` names the weights the kernel consumes as bf16 planes: the mutants change only
-those."""
+those.  `form` is what dawn_conv3x3_form / dawn_gemm1x1_form must answer for the case's descriptor and `direct`, where given, the answers
+dawn_conv3x3_direct_form may give: both are asserted before the launch."""
 import json
 import math
 import os
@@ -339,8 +340,8 @@ class Case:
         W = {k_: v.to(dtype) for k_, v in Wkn.items()}
         p, k = self.p, self.kind
         if k == "gemm":
-            M = p["M"]
-            return ops.conv_gemm(T["x0"], packd(W["w"]), p["N"], in1=T["x1"], F=M // 256, Hi=16, Wi=16, res=T["res"], bias=T["bias"],
+            M, H = p["M"], p.get("H", 16)          # (rows as frames of H x H pixels: a 1x1 projection sees rows only)
+            return ops.conv_gemm(T["x0"], packd(W["w"]), p["N"], in1=T["x1"], F=M // (H * H), Hi=H, Wi=H, res=T["res"], bias=T["bias"],
                                  ln_eps=1e-5 if p.get("ln") else 0.0)
         if k == "down":
             H = p["H"]
@@ -406,25 +407,47 @@ class Case:
         return {k_: (defect(v) if k_ in self.split else v.double()) for k_, v in Wkn.items()}
 
 
-TILED, ROWREG, ROWACC, RESAMPLE = 1, 2, 3, 4          # dawn_gemm1x1_form
+NONE, TILED, ROWREG, ROWACC, RESAMPLE = 0, 1, 2, 3, 4    # dawn_gemm1x1_form
 DIRECT, WINO, WINO4 = 0, 1, 2                         # dawn_conv3x3_form
+# dawn_conv3x3_direct_form, which dawn_conv3x3_form = 0 leaves open: a case with `direct` asserts that the answer is one of these
+DIRECT_NONE, V2 = 0, (2, 3)                           # the fp32 kernels are next; conv3x3_bf16_v2_kernel, 256 x 64 / 256 x 128 tiles
 
 # Gate factors widened past C_GATE, per kernel: the GPU error / CPU fp32 error measured on an MI355X (max over that kernel's cases).
 # Each kernel accumulates K in fp32 on the matrix pipe, one chain of 6 K / 16 MFMA additions per output (CPU GEMM blocks its sums):
-C_TILED = 5.0         # gemm1x1_bf16_kernel: 3.7 (K = 512 / 256 with independent random weights; 2.0 with `coherent` ones)
-C_ROWREG = 3.0        # gemm1x1_rowreg_kernel: 2.0
-C_ROWACC = 4.0        # gemm1x1_rowacc_kernel: 2.8
-C_ROWACC_LN = 8.0     # ... with the LayerNorm inside: 6.2 -- its statistics sweep takes the variance in one pass (s2 / K - mean^2, fp32) over
-                      # K = 512 channels of mean 0.4, std 1.7, where the CPU reference subtracts the mean first
-C_RESAMPLE = 9.0      # gemm1x1_rowacc_kernel, Downsample / Upsample modes: 7.0 (Downsample, K = 4096), 4.6 (Upsample, K = 1024)
+C_TILED = 5.0         # gemm1x1_bf16_kernel: 3.7 (K = 512 / 256 with independent random weights; 2.0 with `coherent` ones); the M = 6400 / 25600
+                      # cases 2.03 (tiled_M6400_N768_K512_res; 1.61 M6400_N512_K256, 1.32 M25600_N768_K256_res, 0.64 the 256 x 64 plan at K = 96)
+C_ROWREG = 3.0        # gemm1x1_rowreg_kernel: 2.0; the K = 64 cases 0.97 (rowreg_M25600_N192_K64+64_ln; 0.94 M25600_N128_K64, 0.91 M6400_N192_K64_ln)
+C_ROWACC = 4.0        # gemm1x1_rowacc_kernel: 2.8; 1.75 (rowacc_M25600_N128_K512), 1.48 (rowacc_M6400_N64_K256)
+C_ROWACC_LN = 8.0     # ... with the LayerNorm inside: 6.2 when the factor was set -- its statistics sweep takes shifted one-pass sums in fp32 (s2 / K -
+                      # md^2 of d = x - shift) over K channels of mean 0.4, std 1.7, where the CPU reference subtracts the mean first.  With the row's
+                      # first channel as the shift, rowacc_M6400_N192_K512+512_ln (K = 1024) measured 9.31 and rowacc_M12800_N192_K512_ln 4.00: a row
+                      # whose first channel lies 3..4 sigma off its mean cancels, 1 / sigma off by 5.0e-6 / 3.2e-6 of its value (the sweep emulated in
+                      # fp32 on the CPU gives 3.1e-6 / 1.6e-6 of the 3.7e-6 / 1.6e-6 measured) -- past 0.8 x the weakest plane defect (11.6 x fp32), so
+                      # no tolerance: the kernel's shift is now the mean of the first 16 channels.  Since then 3.66 (K = 1024), 1.87 (K = 512)
+C_RESAMPLE = 9.0      # gemm1x1_rowacc_kernel, Downsample / Upsample modes: 7.0 (Downsample, K = 4096), 4.6 (Upsample, K = 1024); at 64 channels of
+                      # configs[1]'s first pair 3.79 (down_32x32_C64, K = 1024), 2.87 (up_16x16_C64, K = 256)
 C_WINO4 = 8.5         # conv3x3_wino4_kernel: 7.8 (32 x 32, 128 channels; the F(4x4) transform adds values of different magnitude in fp32; the shipped gate
                       # against the GPU's own fp32-MFMA kernel allows 5x).  The narrowest case of the file: its own error is a third of the
-                      # largest defect a weight pattern can make (2^-17), so c must sit between 7.8 and ~9 (test_split_gate_cpu)
-C_WINO = 5.5          # conv3x3_wino_kernel: 4.2 (the shipped gate against the GPU's direct split kernel allows 3x)
+                      # largest defect a weight pattern can make (2^-17), so c must sit between 7.8 and ~9 (test_split_gate_cpu).  The 32-wide
+                      # template at 64 channels: 5.28 (wino4_32x32_C64+64_N64_n01; 3.97 C64_N64_n01, 3.77 / 2.34 their spread forms)
+C_WINO4_K288 = 5.0    # ... at two chunks (wino4_64x64_C32_N64, K = 288): 3.03 (n01; 2.54 spread) x 1.5 = 4.55.  Its own factor because its chain is the
+                      # shortest the kernel runs, and C_WINO4 = 8.5 would stand above 0.8 x the weakest plane defect of its spread form (8.7 x CPU
+                      # fp32: the cap is 7.0), where the gate could pass a kernel that lost a plane
+C_WINO = 5.5          # conv3x3_wino_kernel: 4.2 (the shipped gate against the GPU's direct split kernel allows 3x); the 32 / 16 / 8-wide cases at
+                      # 64 .. 512 channels 2.75 (wino_8x8_C256+256_N128_spread; 2.15 its n01 form, 0.61 .. 1.81 the others)
 C_SLA_CTX = 3.0       # sla_context_kernel + sla_apply_kernel (fp32, no split operands): 2.46 at HW 1024 (0.94 at 256, 1.07 at 64) -- each context
                       # row is one fp32 MFMA chain over all HW pixels, its softmax denominator one sequential sum of HW / 2 terms per lane
 C_DIRECT_DEEP = 11.0  # conv3x3_bf16_v2_kernel on 4 x 4-pixel frames, K = 4608 / 9216: 9.2 -- one chain over all 9 Cin products of an
                       # output, where the Winograd forms at the same channel counts sum over Cin only (3.5 there)
+# ... at K = 2304 (256 channels), the same chain at half / a quarter of the length: factors of its own by the rule (measured x 1.5, rounded up to the
+# next 0.5), because C_DIRECT_DEEP stands above 0.8 x the weakest plane defect of three of the four cases (test_split_gate_cpu: 12.4 / 14.5 x CPU
+# fp32 the n01 forms, 10.5 / 6.1 the spread forms, the least of 8 and 16 CPU threads -- the caps are 9.9 and 4.9).  n01: 5.33 (direct_4x4_C256_N512;
+# 4.70 N256).  spread: 2.34 (direct_4x4_C256_N256; 2.08 N512) -- there the largest outputs are those of the few x 1e4 inputs, a handful of products
+# each, and the error relative to them is not the long chain's; CPU fp32's own error on that data is 1.5x its n01 one, which halves the cap
+C_DIRECT_K2304 = 8.0
+C_DIRECT_K2304_SPREAD = 4.0
+# The fp32-MFMA kernels that take the convs of an odd clip length hold C_GATE: 1.73 (fp32/conv3x3_8x8_C256_N256_F5), 1.42 (fp32/conv3x3_4x4_C512_N512_F5),
+# 2.14 (fp32/gemm1x1_M320_N768_K512_res: 4.65e-7 against 2 x 2.18e-7 + FLOOR = 5.35e-7)
 
 # deepest-level channel counts (512 -> 512 at 8 x 8 and 4 x 4, 512 + 512 -> 256) put K at 4608 / 9216
 CASES = [
@@ -440,6 +463,23 @@ CASES = [
     Case("gemm1x1/rowreg_M51200_N768_K128_ln", "gemm", form=ROWREG, c=C_ROWREG, M=51200, C0=128, N=768, ln=True),
     Case("gemm1x1/rowacc_M51200_N128_K256", "gemm", form=ROWACC, c=C_ROWACC, M=51200, C0=256, N=128),
     Case("gemm1x1/rowacc_M12800_N192_K512_ln", "gemm", form=ROWACC, c=C_ROWACC_LN, M=12800, C0=512, N=192, ln=True),
+    # ... at the other launch classes of the two configurations: M = 6400 (configs[1]'s deepest level; fewer workgroups than CUs, or barely more)
+    # and M = 25600.  (M / 256) (N / 128) = 150 and 100 wide tiles at M = 6400, which gemm1x1_split_plan turns into 128 x 64 tiles (its plan 3,
+    # M <= 12800): 600 and 400 workgroups, two per CU
+    Case("gemm1x1/tiled_M6400_N768_K512_res", "gemm", form=TILED, c=C_TILED, M=6400, C0=512, N=768, res=True),
+    Case("gemm1x1/tiled_M6400_N512_K256", "gemm", form=TILED, c=C_TILED, M=6400, C0=256, N=512),
+    # the 256 x 64 plan (gemm1x1_split_plan answers 1): N % 128 == 0 with t2 = (M / 256) (N / 128) = 100 < 128 wide tiles gives plan 1, and none
+    # of plan 3's conditions (N % 128 != 0, M <= 12800, N == 128 with M >= 204800) holds at M = 25600 -- launch_gemm1x1_bf16<1>, 200 workgroups
+    # of 256 x 64.  K = 96 keeps the row kernels away (rowreg: K = 64 / 128, rowacc: K >= 256)
+    Case("gemm1x1/tiled_plan1_M25600_N128_K96", "gemm", form=TILED, c=C_TILED, M=25600, C0=96, N=128),
+    # the 256 x 128 plan with more tiles than CUs (t2 = 600 >= 256)
+    Case("gemm1x1/tiled_M25600_N768_K256_res", "gemm", form=TILED, c=C_TILED, M=25600, C0=256, N=768, res=True),
+    Case("gemm1x1/rowreg_M6400_N192_K64_ln", "gemm", form=ROWREG, c=C_ROWREG, M=6400, C0=64, N=192, ln=True),
+    Case("gemm1x1/rowreg_M25600_N128_K64", "gemm", form=ROWREG, c=C_ROWREG, M=25600, C0=64, N=128),
+    Case("gemm1x1/rowreg_M25600_N192_K64+64_ln", "gemm", form=ROWREG, c=C_ROWREG, M=25600, C0=64, C1=64, N=192, ln=True),
+    Case("gemm1x1/rowacc_M6400_N192_K512+512_ln", "gemm", form=ROWACC, c=C_ROWACC_LN, M=6400, C0=512, C1=512, N=192, ln=True),
+    Case("gemm1x1/rowacc_M6400_N64_K256", "gemm", form=ROWACC, c=C_ROWACC, M=6400, C0=256, N=64),
+    Case("gemm1x1/rowacc_M25600_N128_K512", "gemm", form=ROWACC, c=C_ROWACC, M=25600, C0=512, N=128),
     # resample forms of the row-accumulator kernel at configs[2]'s three level pairs (M >= 12800 output / input rows)
     Case("resample/down_64x64_C64", "down", form=RESAMPLE, c=C_RESAMPLE, F=13, H=64, C=64, N=64),
     Case("resample/down_32x32_C128", "down", form=RESAMPLE, c=C_RESAMPLE, F=50, H=32, C=128, N=128),
@@ -447,8 +487,12 @@ CASES = [
     Case("resample/up_8x8_C256", "up", form=RESAMPLE, c=C_RESAMPLE, F=200, H=8, C=256, N=256),
     Case("resample/up_16x16_C128", "up", form=RESAMPLE, c=C_RESAMPLE, F=50, H=16, C=128, N=128),
     Case("resample/up_32x32_C64", "up", form=RESAMPLE, c=C_RESAMPLE, F=13, H=32, C=64, N=64),
+    # ... and configs[1]'s first pair (128 px: 64 channels at 32 x 32 / 16 x 16, which configs[2] has at 64 x 64 / 32 x 32)
+    Case("resample/down_32x32_C64", "down", form=RESAMPLE, c=C_RESAMPLE, F=50, H=32, C=64, N=64),
+    Case("resample/up_16x16_C64", "up", form=RESAMPLE, c=C_RESAMPLE, F=50, H=16, C=64, N=64),
     # 3x3 family at production geometry, N(0,1) data and data spread over 10 decades
-    *[Case(f"conv3x3/{nm}_{'spread' if s else 'n01'}", "conv3", form=fm, c=cg, spread=s, **kw) for s in (False, True) for nm, fm, cg, kw in (
+    *[Case(f"conv3x3/{nm}_{'spread' if s else 'n01'}", "conv3", form=fm, c=cg[s] if isinstance(cg, tuple) else cg, spread=s, **kw)
+      for s in (False, True) for nm, fm, cg, kw in (
         ("wino4_64x64_C64_N64", WINO4, C_WINO4, dict(F=2, H=64, C0=64, N=64)),
         ("wino4_32x32_C128_N128", WINO4, C_WINO4, dict(F=4, H=32, C0=128, N=128)),
         ("wino_64x64_C64+64_N64", WINO, C_WINO, dict(F=2, H=64, C0=64, C1=64, N=64)),
@@ -456,7 +500,31 @@ CASES = [
         ("wino_8x8_C512_N512", WINO, C_WINO, dict(F=8, H=8, C0=512, N=512)),
         ("wino_8x8_C512+512_N256", WINO, C_WINO, dict(F=8, H=8, C0=512, C1=512, N=256)),
         ("direct_4x4_C512_N512", DIRECT, C_DIRECT_DEEP, dict(F=32, H=4, C0=512, N=512)),
-        ("direct_4x4_C512+512_N256", DIRECT, C_DIRECT_DEEP, dict(F=32, H=4, C0=512, C1=512, N=256)))],
+        ("direct_4x4_C512+512_N256", DIRECT, C_DIRECT_DEEP, dict(F=32, H=4, C0=512, C1=512, N=256)),
+        # the other geometries that launch (F = the fewest frames with M % 256 == 0, at least two tiles and F % nf == 0).  F(2x2): TR = 256 / W
+        # rows per tile, nf = TR / H frames per tile once a frame is smaller than a tile (8 x 8: nf = 4); the chunk count (C0 + C1) / 16 and the
+        # chunk of the source switch (C0 / 16) differ from the cases above
+        ("wino_32x32_C128+128_N64", WINO, C_WINO, dict(F=1, H=32, C0=128, C1=128, N=64)),
+        ("wino_32x32_C128+128_N128", WINO, C_WINO, dict(F=1, H=32, C0=128, C1=128, N=128)),
+        ("wino_16x16_C64_N128", WINO, C_WINO, dict(F=4, H=16, C0=64, N=128)),
+        ("wino_16x16_C128+128_N64", WINO, C_WINO, dict(F=4, H=16, C0=128, C1=128, N=64)),
+        ("wino_16x16_C256_N256", WINO, C_WINO, dict(F=4, H=16, C0=256, N=256)),
+        ("wino_8x8_C256_N256", WINO, C_WINO, dict(F=16, H=8, C0=256, N=256)),
+        ("wino_8x8_C256+256_N128", WINO, C_WINO, dict(F=16, H=8, C0=256, C1=256, N=128)),
+        ("wino_8x8_C128_N128", WINO, C_WINO, dict(F=8, H=8, C0=128, N=128)),
+        # F(4x4), 32-wide template at configs[1]'s level 0 (four and eight chunks, one channel tile); 64-wide with the shortest K it takes
+        # (two chunks), which only WINO4_ALL_SHAPES routes there
+        ("wino4_32x32_C64_N64", WINO4, C_WINO4, dict(F=1, H=32, C0=64, N=64)),
+        ("wino4_32x32_C64+64_N64", WINO4, C_WINO4, dict(F=1, H=32, C0=64, C1=64, N=64)),
+        ("wino4_64x64_C32_N64", WINO4, C_WINO4_K288, dict(F=1, H=64, C0=32, N=64, policy=ConvPolicy.WINO4_EVERYWHERE)),
+        # the direct v2 kernel's 36-segment form (nf = 16 frames of 4 x 4 pixels per tile) at K = 2304: (n01, spread) factors
+        ("direct_4x4_C256_N256", DIRECT, (C_DIRECT_K2304, C_DIRECT_K2304_SPREAD), dict(F=32, H=4, C0=256, N=256, direct=V2)),
+        ("direct_4x4_C256_N512", DIRECT, (C_DIRECT_K2304, C_DIRECT_K2304_SPREAD), dict(F=32, H=4, C0=256, N=512, direct=V2)))],
+    # odd clip lengths (F % 4 != 0): M % 256 != 0 at the 8 x 8 and 4 x 4 levels, where every conv falls to the fp32-MFMA kernels although
+    # all its split images are handed over.  No split operand, no plane defect: held to C_GATE, as the fp32 attention kernels below
+    Case("fp32/conv3x3_8x8_C256_N256_F5", "conv3", split=(), form=DIRECT, F=5, H=8, C0=256, N=256, direct=(DIRECT_NONE,)),
+    Case("fp32/conv3x3_4x4_C512_N512_F5", "conv3", split=(), form=DIRECT, F=5, H=4, C0=512, N=512, direct=(DIRECT_NONE,)),
+    Case("fp32/gemm1x1_M320_N768_K512_res", "gemm", split=(), form=NONE, M=320, H=8, C0=512, N=768, res=True),
     # attention layers
     Case("temporal/F200_q0_w40", "temporal", split=("wqkv", "wout"), F=200, HW=16),
     Case("temporal/shard_F280_q40_Fq200", "temporal", split=("wqkv", "wout"), F=280, HW=16, q0=40, Fq=200),

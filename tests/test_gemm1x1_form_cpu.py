@@ -70,6 +70,20 @@ def form(d):
     (dict(M=51200, N=768, C0=128, policy=CP.TILED_ONLY), TILED),     # NO_ROW_KERNELS: the tiled kernel for every shape
     (dict(M=51200, N=128, C0=128, down=True, policy=CP.TILED_ONLY), NONE),
     (dict(M=51200, N=768, C0=128, policy=CP.DEFAULT & ~CP.SPLIT), NONE),      # split kernels off
+    # the M = 6400 / 25600 launch classes of the precision gates (configs[1]'s deepest level; every tile plan of gemm1x1_split_plan).  New
+    # descriptors go at the end of the table: a test's id carries its position
+    (dict(M=6400, N=768, C0=512, res=True), TILED),                 # 150 wide tiles at M <= 12800: 128 x 64 tiles
+    (dict(M=6400, N=512, C0=256), TILED),
+    (dict(M=25600, N=128, C0=96), TILED),                           # 100 wide tiles, M > 12800: the 256 x 64 plan
+    (dict(M=25600, N=768, C0=256, res=True), TILED),                # 600 wide tiles: the 256 x 128 plan
+    (dict(M=6400, N=192, C0=64, ln=True), ROWREG),                  # K = 64
+    (dict(M=25600, N=128, C0=64), ROWREG),
+    (dict(M=25600, N=192, C0=64, C1=64, ln=True), ROWREG),
+    (dict(M=6400, N=192, C0=512, C1=512, ln=True), ROWACC),         # K = 1024 from two sources, the LayerNorm inside
+    (dict(M=6400, N=64, C0=256), ROWACC),
+    (dict(M=25600, N=128, C0=512), ROWACC),
+    (dict(M=12800, N=64, C0=64, down=True), RESAMPLE),              # 64 channels at 32 x 32 -> 16 x 16 (configs[1]'s first pair)
+    (dict(M=12800, N=64, C0=64, up=True), RESAMPLE),
 ])
 def test_gemm1x1_form(kw, want):
     assert form(desc(**kw)) == want

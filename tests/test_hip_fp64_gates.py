@@ -1,6 +1,9 @@
-"""-m gpu: every split-bf16 kernel against a float64 reference at fp32 accuracy (tests/split_gate.py), at production shapes, after asserting
-which kernel the launch takes (dawn_gemm1x1_form / dawn_conv3x3_form of the very descriptor); and repeated-run bit identity of the kernels
-whose loads are placed by hand.
+"""-m gpu: every split-bf16 kernel against a float64 reference at fp32 accuracy (tests/split_gate.py), at the launch classes of the 256-px /
+200-frame and the 128-px / 400-frame configurations (profiles/r6_insitu_shapes.txt, profiles/r6_config1_insitu_shapes.txt: H, W, channel counts
+and N as they launch; the 1x1 and resample cases at their M, the 3x3 cases at the fewest frames that keep the kernel, its tile geometry and at
+least two tiles), after asserting which kernel the launch takes (dawn_gemm1x1_form / dawn_conv3x3_form / dawn_conv3x3_direct_form of the very
+descriptor); the fp32-MFMA kernels that take the same convs at an odd clip length; and repeated-run bit identity of the kernels whose loads are
+placed by hand.
 
 The gate (split_gate.fp32_gate): max|hip - fp64| / max|fp64| <= C_GATE x the same for the RefOps op in fp32 on CPU + FLOOR.
 tests/test_split_gate_cpu.py shows that every case here rejects a kernel that lost its third weight plane or read a stale one.  C_GATE = 2
@@ -42,9 +45,9 @@ def conv_call(case, T, Wkn):
     from dawn_pytorch_amd.pack import pack_bf3, pack_kn, pack_wino4_bf3, pack_wino_bf3
     p, k, w = case.p, case.kind, Wkn["w"]
     if k == "gemm":
-        M = p["M"]
+        M, H = p["M"], p.get("H", 16)
         return ((cu(T["x0"]), pack_kn(w).cuda(), p["N"]),
-                dict(in1=cu(T["x1"]), F=M // 256, Hi=16, Wi=16, res=cu(T["res"]), bias=cu(T["bias"]), ln_eps=1e-5 if p.get("ln") else 0.0,
+                dict(in1=cu(T["x1"]), F=M // (H * H), Hi=H, Wi=H, res=cu(T["res"]), bias=cu(T["bias"]), ln_eps=1e-5 if p.get("ln") else 0.0,
                      w_bf3=pack_bf3(w).cuda()))
     H = p["H"]
     if k == "down":
@@ -80,6 +83,9 @@ def test_conv_split_fp64_gate(hip, case):
         f3, f1 = hip.conv_gemm(*args, **kw, form_only=True)
         if case.kind == "conv3":
             assert (f3, f1) == (case.form, 0), (case.name, f3, f1)
+            if "direct" in case.p:           # which direct kernel, or none of them (the fp32 kernels): dawn_conv3x3_direct_form
+                fd = hip.conv_gemm(*args, **kw, form_only="direct")
+                assert fd in case.p["direct"], (case.name, fd)
         else:
             assert (f3, f1) == (0, case.form), (case.name, f3, f1)
         got = hip.conv_gemm(*args, **kw)
@@ -245,6 +251,12 @@ DET_CONV = [
     G.Case("wino4/L1_32x32_C128_N128", "conv3", form=G.WINO4, F=50, H=32, C0=128, N=128),
     G.Case("wino/L0_64x64_C64+64_N64", "conv3", form=G.WINO, F=50, H=64, C0=64, C1=64, N=64),
     G.Case("wino/L3_8x8_C512_N512", "conv3", form=G.WINO, F=200, H=8, C0=512, N=512),
+    # configs[1] (128 px): F(2x2) at its level 1 with the skip concatenated, F(4x4)'s 32-wide template at its level 0; the row kernels with the
+    # LayerNorm inside on two sources
+    G.Case("wino/L1_32x32_C128+128_N64", "conv3", form=G.WINO, F=50, H=32, C0=128, C1=128, N=64),
+    G.Case("wino4/L0_32x32_C64_N64", "conv3", form=G.WINO4, F=100, H=32, C0=64, N=64),
+    G.Case("gemm1x1/rowreg_M25600_N192_K64+64_ln", "gemm", form=G.ROWREG, M=25600, C0=64, C1=64, N=192, ln=True),
+    G.Case("gemm1x1/rowacc_M6400_N192_K512+512_ln", "gemm", form=G.ROWACC, M=6400, C0=512, C1=512, N=192, ln=True),
 ]
 
 

@@ -3,7 +3,8 @@
   * truncated to its top two bf16 planes (the a1 . b3 term lost), and
   * given the third plane of another matrix (a stale prefetch),
 and ACCEPTS the op evaluated in fp32 on CPU.  The same for the operands the attention kernels split in the kernel (split_gate.ACT_OPERANDS):
-each operand with its third plane dropped, or read from the previous head, is REJECTED, unless split_gate.BELOW_FP32_NOISE lists it.  No GPU."""
+each operand with its third plane dropped, or read from the previous head, is REJECTED, unless split_gate.BELOW_FP32_NOISE lists it.  The conv cases without split operands (an odd clip length: the fp32-MFMA kernels)
+REJECT weights truncated to 16 mantissa bits, and every conv case reaches, at its GPU shape, the kernel it names (the routing run dry).  No GPU."""
 import functools
 
 import pytest
@@ -103,7 +104,9 @@ def test_gate_rejects_activation_plane_defects(case, operand):
     assert set(kept) == listed, (case.name, operand, f"bound {bound:.3e}", kept)
 
 
-FP32_CASES = [c for c in G.CASES if c.kind in ("tattn", "sla_unfused", "frame", "xattn_unfused")]
+# (and the convs of an odd clip length, which the router hands to the fp32-MFMA kernels: conv3 / gemm cases without split operands)
+FP32_CONV_CASES = [c for c in G.CASES if c.kind in ("gemm", "conv3") and not c.split]
+FP32_CASES = [c for c in G.CASES if c.kind in ("tattn", "sla_unfused", "frame", "xattn_unfused")] + FP32_CONV_CASES
 
 
 @pytest.mark.parametrize("case", FP32_CASES, ids=[c.name for c in FP32_CASES])
@@ -114,3 +117,68 @@ def test_fp32_kernel_cases_have_an_fp32_baseline(case):
     ops = RefOps()
     e32 = G.rel_err(case.base32(ops, T, Wkn), case.ref(ops, T, Wkn, torch.float64))
     assert 1e-8 < e32 < 2e-6, e32
+
+
+@pytest.mark.parametrize("case", FP32_CONV_CASES, ids=[c.name for c in FP32_CONV_CASES])
+def test_gate_rejects_reduced_precision_weights(case):
+    """The fp32 conv cases have no plane to lose; what their gate must see is a matrix pipe of less than fp32 precision: the weights
+    truncated to their top 16 mantissa bits (decode_gate.trunc16) are REJECTED, CPU fp32 is accepted."""
+    from decode_gate import trunc16
+    ops = RefOps()
+    T, Wkn = case.make()
+    want64 = case.ref(ops, T, Wkn, torch.float64)
+    base32 = case.base32(ops, T, Wkn)
+    assert not G.gate_rejects(base32, want64, base32, c=case.c)
+    mut = case.ref(ops, T, {k: trunc16(v) for k, v in Wkn.items()}, torch.float64)
+    assert G.gate_rejects(mut, want64, base32, c=case.c), (case.name, G.rel_err(mut, want64), G.rel_err(base32, want64))
+
+
+# ---------------------------------------------------------------------------------------------- the kernel each conv case names
+CONV_CASES = [c for c in G.CASES if c.kind in ("gemm", "down", "up", "conv3")]
+
+
+def conv_desc(case):
+    """The descriptor HipOps.conv_gemm builds for the case in tests/test_hip_fp64_gates.py (conv_call), on pointers that are never read."""
+    from dawn_pytorch_amd import _lib
+    FAKE = 0x1000
+    p, k = case.p, case.kind
+    d = _lib.ConvDesc()
+    C0, C1, N = p.get("C0", p.get("C")), p.get("C1", 0), p["N"]
+    d.in0, d.C0, d.ld0 = FAKE, C0, C0
+    if C1:
+        d.in1, d.C1, d.ld1 = FAKE, C1, C1
+    d.w, d.w_bf3, d.N, d.out, d.ld_out, d.stride = FAKE, FAKE, N, FAKE, N, 1
+    H = p.get("H", 16)
+    d.F = p["M"] // (H * H) if k == "gemm" else p["F"]
+    d.Hi = d.Wi = d.Ho = d.Wo = H
+    if k == "gemm":
+        d.KH = d.KW = 1
+        if p.get("res"):
+            d.res, d.ld_res = FAKE, N
+        if p.get("bias"):
+            d.bias = FAKE
+        if p.get("ln"):
+            d.ln_eps = 1e-5
+    elif k == "down":
+        d.Ho = d.Wo = H // 2
+        d.KH, d.KW, d.stride, d.pad, d.bias = 4, 4, 2, 1, FAKE
+    elif k == "up":
+        d.Ho = d.Wo = 2 * H
+        d.KH, d.KW, d.mode, d.bias = 2, 2, 1, FAKE
+    else:
+        d.KH, d.KW, d.pad, d.w_wino, d.w_wino4 = 3, 3, 1, FAKE, FAKE
+    d.policy = int(p.get("policy", 0))
+    return d
+
+
+@pytest.mark.parametrize("case", CONV_CASES, ids=[c.name for c in CONV_CASES])
+def test_conv_case_reaches_the_kernel_it_names(case):
+    """dawn_conv3x3_form / dawn_gemm1x1_form / dawn_conv3x3_direct_form (host code: the launch's own routing run dry) of every conv case at
+    its GPU shape -- what tests/test_hip_fp64_gates.py asserts again on the very descriptor it launches."""
+    import ctypes as C
+    from dawn_pytorch_amd import _lib
+    L, d = _lib.lib(), conv_desc(case)
+    forms = (L.dawn_conv3x3_form(C.byref(d)), L.dawn_gemm1x1_form(C.byref(d)))
+    assert forms == ((case.form, 0) if case.kind == "conv3" else (0, case.form)), (case.name, forms)
+    if "direct" in case.p:
+        assert L.dawn_conv3x3_direct_form(C.byref(d)) in case.p["direct"], case.name
