@@ -38,6 +38,45 @@ def _need(ok, what: str) -> None:
         raise _lib.DawnHipError(f"HipOps precondition failed -- {what}")
 
 
+def conv_desc(in0: Tensor, w: Tensor, N: int, out: Tensor, *, F: int, Hi: int, Wi: int, Ho: int, Wo: int, KH: int = 1, KW: int = 1,
+              stride: int = 1, pad: int = 0, mode: int = 0, in1: Optional[Tensor] = None, bias: Optional[Tensor] = None,
+              row_stats: Optional[Tuple[Tensor, Tensor]] = None, ch_ab: Optional[Tuple[Tensor, Tensor]] = None, pro_act: int = 0,
+              pro_add: Optional[Tensor] = None, res: Optional[Tensor] = None, tr: Optional[Tuple[Tensor, Tensor, Tensor]] = None,
+              gn_part: Optional[Tensor] = None, w_bf3: Optional[Tensor] = None, ln_eps: float = 0.0, w_wino: Optional[Tensor] = None,
+              w_wino4: Optional[Tensor] = None, border: int = 0, policy: int = 0, sk_ws: Optional[Tensor] = None) -> ConvDesc:
+    """The dawn_conv_desc of one HipOps.conv_gemm call (arguments as there): everything the library's routers (dawn_conv3x3_form,
+    dawn_conv3x3_direct_form, dawn_gemm1x1_form) decide on.  The one place it is built: the launch, its form_only queries and the
+    tests' dry census of an evaluation (tests/length_cases.py) all see the same descriptor.  Only addresses and strides are taken
+    from the tensors; the fused GroupNorm finalisation (gn_fin) is added by the launch itself."""
+    d = ConvDesc()
+    d.in0, d.in1 = _p(in0), _p(in1)
+    d.C0, d.C1 = in0.shape[1], (in1.shape[1] if in1 is not None else 0)
+    d.ld0, d.ld1 = _ld(in0), _ld(in1)
+    d.F, d.Hi, d.Wi, d.Ho, d.Wo = F, Hi, Wi, Ho, Wo
+    d.KH, d.KW, d.stride, d.pad, d.mode = KH, KW, stride, pad, mode
+    d.border = border
+    d.w, d.bias, d.N = _p(w), _p(bias), N
+    if row_stats is not None:
+        d.row_mean, d.row_rstd = _p(row_stats[0]), _p(row_stats[1])
+    if ch_ab is not None:
+        d.ch_a, d.ch_b = _p(ch_ab[0]), _p(ch_ab[1])
+    d.pro_act = pro_act
+    d.pro_add, d.ld_add = _p(pro_add), _ld(pro_add)
+    d.res, d.ld_res = _p(res), _ld(res)
+    if tr is not None:
+        d.tr, d.ld_tr, d.tr_a, d.tr_b = _p(tr[0]), _ld(tr[0]), _p(tr[1]), _p(tr[2])
+    d.out, d.ld_out = _p(out), _ld(out)
+    d.gn_part = _p(gn_part)
+    d.w_bf3 = _p(w_bf3)
+    d.w_wino = _p(w_wino)
+    d.w_wino4 = _p(w_wino4)
+    d.policy = policy
+    d.ln_eps = ln_eps
+    if sk_ws is not None and w_bf3 is not None and KH == 3 and KW == 3 and stride == 1 and mode == 0:
+        d.sk_ws, d.sk_ws_bytes = _p(sk_ws), sk_ws.numel()        # (ignored by the shipped library)
+    return d
+
+
 class HipOps:
     """Launches on the current PyTorch stream of the tensors' device."""
 
@@ -159,32 +198,9 @@ class HipOps:
         if out is None:
             out = self.empty(rows_out, N, like=in0)
         self._require(in0, in1, w, bias, pro_add, res, out)
-        d = ConvDesc()
-        d.in0, d.in1 = _p(in0), _p(in1)
-        d.C0, d.C1 = in0.shape[1], (in1.shape[1] if in1 is not None else 0)
-        d.ld0, d.ld1 = _ld(in0), _ld(in1)
-        d.F, d.Hi, d.Wi, d.Ho, d.Wo = F, Hi, Wi, Ho, Wo
-        d.KH, d.KW, d.stride, d.pad, d.mode = KH, KW, stride, pad, mode
-        d.border = border
-        d.w, d.bias, d.N = _p(w), _p(bias), N
-        if row_stats is not None:
-            d.row_mean, d.row_rstd = _p(row_stats[0]), _p(row_stats[1])
-        if ch_ab is not None:
-            d.ch_a, d.ch_b = _p(ch_ab[0]), _p(ch_ab[1])
-        d.pro_act = pro_act
-        d.pro_add, d.ld_add = _p(pro_add), _ld(pro_add)
-        d.res, d.ld_res = _p(res), _ld(res)
-        if tr is not None:
-            d.tr, d.ld_tr, d.tr_a, d.tr_b = _p(tr[0]), _ld(tr[0]), _p(tr[1]), _p(tr[2])
-        d.out, d.ld_out = _p(out), _ld(out)
-        d.gn_part = _p(gn_part)
-        d.w_bf3 = _p(w_bf3)
-        d.w_wino = _p(w_wino)
-        d.w_wino4 = _p(w_wino4)
-        d.policy = self.conv_policy
-        d.ln_eps = ln_eps
-        if self.sk_ws is not None and w_bf3 is not None and KH == 3 and KW == 3 and stride == 1 and mode == 0:
-            d.sk_ws, d.sk_ws_bytes = _p(self.sk_ws), self.sk_ws.numel()        # (ignored by the shipped library)
+        d = conv_desc(in0, w, N, out, F=F, Hi=Hi, Wi=Wi, Ho=Ho, Wo=Wo, KH=KH, KW=KW, stride=stride, pad=pad, mode=mode, in1=in1, bias=bias,
+                      row_stats=row_stats, ch_ab=ch_ab, pro_act=pro_act, pro_add=pro_add, res=res, tr=tr, gn_part=gn_part, w_bf3=w_bf3,
+                      ln_eps=ln_eps, w_wino=w_wino, w_wino4=w_wino4, border=border, policy=self.conv_policy, sk_ws=self.sk_ws)
         if form_only == "direct":
             return int(self.L.dawn_conv3x3_direct_form(C.byref(d)))
         if form_only:

@@ -53,12 +53,18 @@ def rel_err(t, want64):
 
 def fp32_gate(name, got, want64, base32, c=C_GATE, floor=FLOOR, log=True):
     """Assert that `got` is as accurate as CPU fp32 (see the module docstring); append its errors to the op-error log (LOG)."""
+    return fp32_gate_e32(name, got, want64, rel_err(base32, want64), c, floor, log)
+
+
+def fp32_gate_e32(name, got, want64, e32, c=C_GATE, floor=FLOOR, log=True, **extra):
+    """fp32_gate where CPU fp32's own error e32 = rel_err(base32, want64) was measured beforehand (the fixtures of length_cases.py hold
+    it beside want64); `extra` goes into the record."""
     got = got.detach().cpu().double()
     diff = got - want64
-    e, e32 = rel_err(got, want64), rel_err(base32, want64)
+    e = rel_err(got, want64)
     rec = {"op": f"fp64_gate/{name}", "rel_err": e, "rel_err_cpu_fp32": e32, "ratio": e / e32 if e32 > 0 else float("inf"),
            "max_abs_err": float(diff.abs().max()), "rms_err": float(diff.pow(2).mean().sqrt()), "scale": float(want64.abs().max()),
-           "c": c, "floor": floor, "nan": bool(torch.isnan(got).any())}
+           "c": c, "floor": floor, "nan": bool(torch.isnan(got).any()), **extra}
     if log:
         os.makedirs(os.path.dirname(LOG), exist_ok=True)
         with open(LOG, "a") as f:

@@ -12,7 +12,8 @@ Weights / inputs are rebuilt from seeds (fixture checksums prove they are the sa
 Tolerance: 1e-4 * max(1, max|y|) on the predicted noise (fp32, ~300 chained ops, K up to 9216) = 6x the worst measured
 error (1.7e-5 at C3; 6e-6 / 9e-6 at T96 / C2); the 2-step trajectory 3e-5 (measured 4e-6).  Measured errors are logged to
 gpurun_out/e2e_errors.jsonl and copied into profiles/r3_parity_errors.md.  Whole 10 / 50-step trajectories:
-tests/test_hip_trajectory.py."""
+tests/test_hip_trajectory.py.  The kernel mixes of clips up to F = 128 (h = 32) / F = 32 (h = 64) are held to fp32 accuracy against a float64
+oracle by tests/test_hip_length_gates.py (T96's mix among them); the mixes of C2 and C3 (F > 128) are held at this 1e-4 only."""
 import numpy as np
 import pytest
 import torch

@@ -1,6 +1,8 @@
 """oracle/ops_ref.RefOps keeps float64 inputs in float64 for every op the fp64 precision gates use (tests/test_hip_fp64_gates.py), and its
 float32 results are bit-for-bit those of the reference as it stood before it learned float64 (commit bf46578, read from git history), which
-every fp32-tolerance GPU test compares against."""
+every fp32-tolerance GPU test compares against.  The same for the whole-UNet oracle (oracle/dawn_oracle.unet_forward), which
+tests/test_hip_length_gates.py evaluates in float64: float32 bit for bit as in the parent commit, float64 carried through."""
+import math
 import subprocess
 import types
 
@@ -118,3 +120,52 @@ def test_float64_agrees_with_float32():
     for name, case in CASES.items():
         for a, b in zip(outputs(call(RefOps(), case, torch.float64)), outputs(call(RefOps(), case, torch.float32))):
             assert float((a - b.double()).abs().max()) <= 1e-5 * max(1.0, float(a.abs().max())), name
+
+
+# ---------------------------------------------------------------------------------------------- the whole UNet (oracle/dawn_oracle.py)
+ORACLE_BEFORE = "0bc8995ed9e68a7285f400c17f5e70845871d5f7"      # the oracle before unet_forward carried float64
+
+
+@pytest.fixture(scope="module")
+def oracle_before():
+    try:
+        src = subprocess.run(["git", "-C", ROOT, "show", f"{ORACLE_BEFORE}:oracle/dawn_oracle.py"], check=True, capture_output=True,
+                             text=True).stdout
+    except (OSError, subprocess.CalledProcessError) as e:
+        pytest.skip(f"the oracle of commit {ORACLE_BEFORE[:7]} is not in this checkout's git history ({e})")
+    mod = types.ModuleType("dawn_oracle_before")
+    exec(compile(src, "dawn_oracle_before.py", "exec"), mod.__dict__)
+    return mod
+
+
+def _tiny_args(tiny, dt):
+    g, sd = tiny
+    sd = {k: (v.to(dt) if v.is_floating_point() else v) for k, v in sd.items()}
+    return sd, torch.from_numpy(g["x"]).to(dt), torch.from_numpy(g["time"]), torch.from_numpy(g["cond"]).to(dt)
+
+
+def test_unet_forward_float32_unchanged(tiny, oracle_before):
+    """oracle.dawn_oracle.unet_forward (and its guided form, and the tables it shares with the kernels) in float32: bit for bit the
+    oracle of the parent commit on the tiny golden."""
+    from oracle import dawn_oracle as O
+    sd, x, time, cond = _tiny_args(tiny, torch.float32)
+    got, want = O.unet_forward(sd, x, time, cond, win=3), oracle_before.unet_forward(sd, x, time, cond, win=3)
+    assert got.dtype == torch.float32 and torch.equal(got, want)
+    assert torch.equal(O.unet_forward_with_cond_scale(sd, x, time, cond, 2.5, win=3),
+                       oracle_before.unet_forward_with_cond_scale(sd, x, time, cond, 2.5, win=3))
+    for a, b in zip(O.rotary_tables(12) + (O.sinusoidal_emb(time, 16),), oracle_before.rotary_tables(12) + (oracle_before.sinusoidal_emb(time, 16),)):
+        assert a.dtype == torch.float32 and torch.equal(a, b)
+
+
+def test_unet_forward_carries_float64(tiny):
+    """float64 state dict and inputs: float64 out, within fp32 rounding of the float32 evaluation; the shared tables stay the fp32 ones."""
+    from oracle import dawn_oracle as O
+    sd, x, time, cond = _tiny_args(tiny, torch.float64)
+    y64 = O.unet_forward(sd, x, time, cond, win=3)
+    assert y64.dtype == torch.float64
+    y32 = O.unet_forward(*_tiny_args(tiny, torch.float32), win=3)
+    d = float((y64 - y32.double()).abs().max())
+    assert 0 < d <= 1e-5 * max(1.0, float(y64.abs().max()))
+    e64 = O.sinusoidal_emb(time, 16, torch.float64)
+    arg = (time.float()[:, None] * torch.exp(torch.arange(8, dtype=torch.float32) * -(math.log(10000) / 7))).double()
+    assert e64.dtype == torch.float64 and torch.equal(e64, torch.cat((arg.sin(), arg.cos()), -1))      # fp32 argument, float64 sine
